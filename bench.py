@@ -148,6 +148,49 @@ def timed_region(step, steps, warmup, world, dist, device, sync, spin_s=0.08, be
     return float(el.item())
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000   # --dump-outputs: at most this many bytes written per run
+
+
+def snapshot_outputs(args, rank, arrays):
+    """--dump-outputs: device copies of the arrays the timed path's LAST step wrote (name -> tensor), taken right after the timed
+    region, before any later leg reuses the buffers.  None when nothing is to be dumped (no flag, or not rank 0)."""
+    if not args.dump_outputs or rank != 0:
+        return None
+    return {name: t.detach().clone() for name, t in arrays.items()}
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write every array (name -> tensor) as <path>/<name>.npy: floating types as float32, float64 kept, integer types as float64
+    (exact).  When the whole set exceeds `budget` bytes, every array is replaced by the same fraction of its elements, a fixed
+    sample (indices drawn from a generator seeded by `seed` and the name, sorted, of the flattened array) -- identical for identical
+    shapes, so two builds compare element for element.  <path>/manifest.json records each array's shape, dtype and sampling."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "iub" else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    room = budget - 4096 * (len(host) + 1)               # (.npy headers and the manifest)
+    keep = min(1.0, room / float(total)) if total else 1.0
+    manifest = {}
+    for name, a in host.items():
+        flat = a.reshape(-1)
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": keep < 1.0}
+        if keep < 1.0:
+            n = int(flat.size * keep)
+            idx = np.sort(np.random.default_rng([seed, zlib.crc32(name.encode())]).choice(flat.size, n, replace=False))
+            flat = flat[idx]
+            entry.update(sample_seed=[seed, zlib.crc32(name.encode())], sample_size=n)
+        np.save(os.path.join(path, name + ".npy"), flat if keep < 1.0 else a)
+        manifest[name] = entry
+    with open(os.path.join(path, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+
+
 def scale_leg(step, steps, warmup, world, dist, device, sync, H, W, spin_s=0.04):
     """A second timed region of the same protocol on another frame size, run only when world > 1: the >= 6x-at-8-GPUs target of the
     north star is stated for batched 1080p pairs, the driver's scaling run uses the default (VGA) workload -- so the VGA line carries
@@ -384,6 +427,9 @@ def main_pyramid(args, world, rank, local_rank, dev, torch, dist, d, rp):
                                                   flow.data_ptr(), None))
 
     elapsed = timed_region(step, args.steps, args.warmup, world, dist, dev, torch.cuda.synchronize)
+    snap = snapshot_outputs(args, rank, {"flow": flow})
+    if snap:
+        dump_outputs(args.dump_outputs, snap)
     last_kernel = ctx.last_kernel()
     if rank == 0:
         balg = 2 * Cc * Hp * Wp * 4 + sum((Hp // r) * (Wp // r) * maxh * maxw * (2 if f16 else 4) for r in ratios)
@@ -475,6 +521,9 @@ def main_bands(args, world, rank, local_rank, dev, torch, dist, d, rp):
         out[0] = run_banded_step(frames, plan, world, rank, dist, compute, dev, torch.cuda.synchronize, timing)
 
     elapsed = timed_region(step, args.steps, args.warmup, world, dist, dev, torch.cuda.synchronize, spin_s=0.0)
+    snap = snapshot_outputs(args, rank, dict(zip(("flow", "depth") if kind == "single" else ("flow",), out[0] or [])))
+    if snap:
+        dump_outputs(args.dump_outputs, snap)
     if rank == 0:
         tm = np.array(timing[-args.steps:])
         step_s = elapsed / args.steps
@@ -531,9 +580,12 @@ def main_radial(args, world, rank, local_rank, dev, torch, dist, d, rp):
 
     elapsed = timed_region(step, args.steps, args.warmup, world, dist, dev, torch.cuda.synchronize,
                            before_timed=lambda: ctx.check(lib.dfe_profile_enable(ctx.handle, 1)))
+    snap = snapshot_outputs(args, rank, {"volume": vol, "polar_flow": pf, "flow": cart, "depth": depth, "confidence": conf})
     ms, n = C.c_double(), C.c_int()
     ctx.check(lib.dfe_profile_read(ctx.handle, C.byref(ms), C.byref(n)))
     ctx.check(lib.dfe_profile_enable(ctx.handle, 0))
+    if snap:
+        dump_outputs(args.dump_outputs, snap)
     if rank == 0:
         K = w2.shape[0]
         hf2 = hIn - (w2.shape[2] - 1)
@@ -639,10 +691,13 @@ def main_learned_single(args, world, rank, local_rank, dev, torch, dist, d, rp):
 
     elapsed = timed_region(step, args.steps, args.warmup, world, dist, dev, torch.cuda.synchronize,
                            before_timed=lambda: ctx.check(lib.dfe_profile_enable(ctx.handle, 1)))
+    snap = snapshot_outputs(args, rank, {"min": mn, "argmin": mi} if tm else {"flow": full, "confidence": fconf} if nk < 0 else {"flow_x": xf, "flow_y": yf})
     ms, n = C.c_double(), C.c_int()
     ctx.check(lib.dfe_profile_read(ctx.handle, C.byref(ms), C.byref(n)))
     ctx.check(lib.dfe_profile_enable(ctx.handle, 0))
     kernel = ctx.last_kernel()
+    if snap:
+        dump_outputs(args.dump_outputs, snap)
     stages = None
     if tm:
         for _ in range(10):
@@ -720,7 +775,12 @@ def main():
     ap.add_argument("--bands", type=int, default=1, help="*-bands workloads: at least this many row bands (default: one per rank)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: skip the (untimed) gather of the results to rank 0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB in all (a fixed seeded sample of each array beyond that; DIR/manifest.json says which)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: become the launcher (nothing below has touched the GPU yet)
@@ -792,11 +852,16 @@ def main():
         ctx.check(lib.dfe_profile_enable(ctx.handle, 1))
 
     elapsed = timed_region(step, args.steps, args.warmup, world, dist, dev, torch.cuda.synchronize, before_timed=before_timed)
+    # (the f16 step writes no scores)
+    snap = snapshot_outputs(args, rank, {"flow": flow, "depth": depth, "confidence": dconf} if f16 else
+                            {"flow": flow, "scores": scores, "depth": depth, "confidence": dconf})
     kernel = kernel[0]
     cv_ms, cv_n = C.c_double(), C.c_int()
     each = (C.c_float * max(args.steps * 4, 1))()
     ctx.check(lib.dfe_profile_read_each(ctx.handle, C.byref(cv_ms), C.byref(cv_n), each, len(each)))
     ctx.check(lib.dfe_profile_enable(ctx.handle, 0))
+    if snap:
+        dump_outputs(args.dump_outputs, snap)
     each = sorted(each[: min(cv_n.value, len(each))])
 
     # outside the timed region: the cost-volume build ALONE (dfe_ssd_cost_volume_f32, no flow epilogue), the kernel the

@@ -4,6 +4,7 @@ import ctypes
 import os
 import re
 import subprocess
+import sys
 
 import pytest
 
@@ -40,7 +41,7 @@ def test_lua_ffi_binding_declares_the_whole_abi():
     cdef = lua[lua.index("ffi.cdef[[") : lua.index("]]")]
     for s in declared_symbols():
         assert re.search(r"\b%s\s*\(" % s, cdef), "dfe_ffi.lua does not declare %s" % s
-    rc = subprocess.run(["python", os.path.join(ROOT, "tools", "gen_lua_cdef.py"), "--check"]).returncode
+    rc = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_lua_cdef.py"), "--check"]).returncode
     assert rc == 0, "dfe_ffi.lua is out of date: run tools/gen_lua_cdef.py"
 
 
