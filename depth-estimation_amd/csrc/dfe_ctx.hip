@@ -53,7 +53,9 @@ int dfe_scratch(dfe_ctx *ctx, size_t bytes, void **out, bool plain) {
             if (!contig) { (void)hipGetLastError(); arena = nullptr; }
         }
         if (!contig) e = hipMalloc(&arena, bytes);
-        if (e != hipSuccess) { arena = nullptr; return dfe_fail(ctx, DFE_E_ALLOC, "scratch hipMalloc(%zu): %s", bytes, hipGetErrorString(e)); }
+        // (a failed allocation is reported here; it must not stay behind as the thread's last HIP error, where the caller's next launch
+        //  -- of this library or of the framework around it -- would report it as its own)
+        if (e != hipSuccess) { (void)hipGetLastError(); arena = nullptr; return dfe_fail(ctx, DFE_E_ALLOC, "scratch hipMalloc(%zu): %s", bytes, hipGetErrorString(e)); }
         arena_bytes = bytes;
         // DFE_DEBUG_ARENA=1: where the arena landed and what it is made of
         if (ctx->opt[DFE_OPT_DEBUG_ARENA] > 0)
@@ -75,7 +77,7 @@ int dfe_device_alloc(dfe_ctx *ctx, size_t bytes, void **ptr, int *contiguous) {
     }
     if (!contig) {
         hipError_t e = hipMalloc(ptr, bytes);
-        if (e != hipSuccess) { *ptr = nullptr; return dfe_fail(ctx, DFE_E_ALLOC, "dfe_device_alloc hipMalloc(%zu): %s", bytes, hipGetErrorString(e)); }
+        if (e != hipSuccess) { (void)hipGetLastError(); *ptr = nullptr; return dfe_fail(ctx, DFE_E_ALLOC, "dfe_device_alloc hipMalloc(%zu): %s", bytes, hipGetErrorString(e)); }
     }
     if (contiguous) *contiguous = contig ? 1 : 0;
     return DFE_OK;
@@ -95,7 +97,7 @@ int dfe_aux_scratch(dfe_ctx *ctx, size_t bytes, void **out) {
         ctx->aux = nullptr;
         ctx->aux_bytes = 0;
         hipError_t e = hipMalloc(&ctx->aux, bytes);
-        if (e != hipSuccess) return dfe_fail(ctx, DFE_E_ALLOC, "aux hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
+        if (e != hipSuccess) { (void)hipGetLastError(); return dfe_fail(ctx, DFE_E_ALLOC, "aux hipMalloc(%zu): %s", bytes, hipGetErrorString(e)); }
         ctx->aux_bytes = bytes;
     }
     *out = ctx->aux;

@@ -189,6 +189,9 @@ bool cv_finest_plan_ok(dfe_ctx *ctx, int Hp, int Wp, int maxh, int maxw);   // c
 // arena of at least `bytes`.  plain = false: physically contiguous memory if the driver has it (the volume sweeps' arena); plain = true: a
 // plain hipMalloc, for the paths whose convolutions write many feature planes side by side (see dfe_scratch in dfe_ctx.hip for both measurements)
 int dfe_scratch(dfe_ctx *ctx, size_t bytes, void **out, bool plain = false);
+// whether the one-kernel flat matcher (feat_matching_flat.hip) takes in1 as a view -- rows pitch1, planes plane1 floats apart: the arena
+// planners leave the volume out only where it does
+bool dfe_feat_matching_flat_view_takes(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw, int pitch1, long long plane1);
 // one layer of a filter stack (filters.hip): in [nIn][H][W] -> out [nOut][H-kH+1][W-kW+1], nn.Tanh fused behind it when
 // L.tanh_after (the same tanhf as dfe_tanh_f32: bit-identical to the two separate calls)
 int dfe_filter_layer_forward(dfe_ctx *ctx, const float *in, const dfe_filter_layer &L, int H, int W, float *out);

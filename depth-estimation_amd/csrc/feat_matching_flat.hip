@@ -718,9 +718,21 @@ static bool ff_shape_ok(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int
     return true;
 }
 
-// whether dfe_feat_matching_flat_argmin will take the shape (4-byte aligned feature maps assumed): the one-call models decide with it
-// whether the volume needs a place in the scratch arena at all
-bool dfe_feat_matching_flat_argmin_takes(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw) { return ff_shape_ok(ctx, K, H1, W1, maxh, maxw); }
+// ... and in1 as a view (rows pitch1 floats apart, planes plane1 floats apart): everything ff_launch can decline on but the pointers'
+// alignment (the LDS budget holds for every shape ff_shape_ok takes: 158 KiB at most, 17 x 17 soft-max)
+static bool ff_view_ok(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw, int pitch1, long long plane1) {
+    if (!ff_shape_ok(ctx, K, H1, W1, maxh, maxw)) return false;
+    return pitch1 >= W1 && plane1 >= (long long)(H1 - 1) * pitch1 + W1 && plane1 < (1ll << 29);
+}
+
+// whether dfe_feat_matching_flat_argmin / _soft will take the shape (4-byte aligned feature maps assumed): the one-call models decide with
+// it whether the volume needs a place in the scratch arena at all -- a decline behind a `true` here would leave them without a volume
+bool dfe_feat_matching_flat_argmin_takes(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw) {
+    return ff_view_ok(ctx, K, H1, W1, maxh, maxw, W1, (long long)H1 * W1);
+}
+bool dfe_feat_matching_flat_view_takes(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw, int pitch1, long long plane1) {
+    return ff_view_ok(ctx, K, H1, W1, maxh, maxw, pitch1, plane1);
+}
 
 // *handled stays false when the shape is not this kernel's (the caller goes on to the round-3 kernels)
 static int ff_launch(dfe_ctx *ctx, const float *in1, int pitch1, long long plane1, const float *in2, int K, int H1, int W1, int maxh, int maxw, float *out,
@@ -728,10 +740,9 @@ static int ff_launch(dfe_ctx *ctx, const float *in1, int pitch1, long long plane
     const int mode = soft ? FF_SOFT : out ? FF_VOLUME : FF_ARGMIN;
     const bool argmin = mode == FF_ARGMIN;
     *handled = false;
-    if (!ff_shape_ok(ctx, K, H1, W1, maxh, maxw)) return DFE_OK;
+    if (!ff_view_ok(ctx, K, H1, W1, maxh, maxw, pitch1, plane1)) return DFE_OK;
     const int G = dfe_cdiv(W1, FF_PX);
     if (((uintptr_t)in1 | (uintptr_t)in2 | (uintptr_t)out) & 3) return DFE_OK;
-    if (pitch1 < W1 || plane1 < (long long)(H1 - 1) * pitch1 + W1 || plane1 >= (1ll << 29)) return DFE_OK;
     const long long NGl = (long long)H1 * G;
     FfArgs a{};
     a.in1 = in1; a.in2 = in2; a.out = out;

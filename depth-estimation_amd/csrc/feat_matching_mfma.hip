@@ -8,10 +8,13 @@
 // price of a dense tile on a banded problem).  K = 32: 16 MFMAs per (16 pixels, dy), 4.6 M per VGA pair = 60 us of matrix-core time
 // against the 120 us the vector form needs at its best.
 // NUMERICS: the cost is ONE fmaf chain of the MFMA: |a|^2 * 1 and 1 * |b|^2 first (the norms, summed in fp32 by fmm_norm_kernel or by the
-// convolution's epilogue, ride in the GEMM as an extra k-step), then (-2 a_k) b_k in k order.  It differs from the exact sum of squared differences by cancellation: about 1e-7 (|a|^2 + |b|^2) absolute,
-// i.e. the relative error of a SMALL cost (a good match) is larger than that of the exact kernel.  Tolerance as tested
-// (tests/test_gpu_matcher_full.py): |c - exact| <= 1e-5 |exact| + 1e-6 max|exact|; arg-min equal except where the two best exact
-// costs lie within that band.  The exact kernels stay the default.
+// convolution's epilogue, ride in the GEMM as an extra k-step), then (-2 a_k) b_k in k order.  Its error is that of a sum whose terms
+// are as large as |a|^2 + |b|^2, not as large as the cost: ABSOLUTE in N = |a|^2 + |b|^2, so the relative error of a small cost (a good
+// match) is large, and features with a common offset c (a bias, raw intensities) make N ~ 2 K c^2 whatever the cost.  Bound, u = 2^-24:
+//   |c - sum_k (a_k - b_k)^2| <= 4 u (K + 2) N
+// (K + 2 accumulation steps and the K steps of each norm, every partial sum at most 2 N in magnitude; observed errors are about
+// u sqrt(K) N).  Arg-min indices equal the exact first minimum except where the two best costs lie within twice that band.  Tested in
+// float64 by tests/test_gpu_matcher_mfma.py.  The exact kernels stay the default.
 //   block = 8 waves = 8 output rows x 16 pixels, one block per CU; wave w owns row w: 17 x 2 accumulator tiles (136 registers).  (Tried:
 //   two blocks of 4 waves per CU so that one block's MFMAs run beside the other's epilogue -- 165 against 137 us: twice the in2 rows
 //   staged per output row.)  Planes are staged 8
@@ -335,7 +338,9 @@ bool dfe_feat_matching_mfma_takes(const dfe_ctx *ctx, int K, int H1, int W1, int
     if (ctx->opt[DFE_OPT_FM_MFMA] <= 0 || ctx->cv_mode == 1) return false;
     if (!((maxh == 17 && maxw == 17) || (maxh == 16 && maxw == 16))) return false;
     if (K < 1 || K > 256 || H1 < 1 || W1 < 1) return false;
-    return (long long)K * (H1 + maxh - 1) * (W1 + maxw - 1) < (1ll << 31);
+    // the LDS-DMA requests address in2 as 32-bit BYTE offsets 4 * (k plane2 + row W2 + col) from the map's base: below 2^30 floats they do
+    // not wrap (in1 and the norm planes are smaller)
+    return (long long)K * (H1 + maxh - 1) * (W1 + maxw - 1) < (1ll << 30);
 }
 
 // out != NULL: the volume; else the first-minimum decode (idx / xflow / yflow).  norms: dfe_feat_matching_mfma_scratch floats.

@@ -99,7 +99,10 @@ extern "C" int dfe_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const f
     const int ny = (maxh + 1) / 2 - 1, nx = (maxw + 1) / 2 - 1;     // prepareInput: narrow(2, ceil(maxh/2), ..) 1-based -> first row / column, 0-based
     const int N = maxh * maxw;
     const long long P1 = (long long)H1 * W1;
-    const bool lean = dfe_feat_matching_flat_argmin_takes(ctx, K, H1, W1, maxh, maxw);
+    // the matcher reads the narrowed in1 in place when the caller ran the filter (prefilter: rows W, planes H W floats apart), else a
+    // contiguous map of the arena; the predicate sees that view and the frames' alignment, so that it declines what the launcher would
+    const bool lean = nlayers ? dfe_feat_matching_flat_argmin_takes(ctx, K, H1, W1, maxh, maxw)
+                              : dfe_feat_matching_flat_view_takes(ctx, K, H1, W1, maxh, maxw, W, (long long)H * W) && !(((uintptr_t)I0 | (uintptr_t)I1) & 3);
     // arena: cropped frame 0 | two ping-pong feature buffers per branch | (fallback) contiguous in1 | volume | probabilities | index | scores
     const int Hc = H1 + hk - 1, Wc = W1 + wk - 1;                   // the part of frame 0 the narrowed features come from
     auto al = [](size_t f) { return (f + 63) / 64 * 64; };

@@ -82,8 +82,10 @@ int dfe_set_cost_volume_tile(dfe_ctx *ctx, int tyq);
  * (DFE_<KEY> variables of the tuning scripts) -- never inside an op, so an op's behaviour depends on its ctx only.
  * Two keys trade the exact arithmetic for the matrix cores, both OFF unless set to 1: "conv_mfma" (the one-call models' filter layers as
  * implicit GEMMs, v_mfma_f32_16x16x4_f32: the reference's (input plane, ky, kx) order with FUSED multiply-adds, <= 1e-5 relative to
- * sum |terms|) and "fm_mfma" (nn.SpatialMatching as a banded GEMM, |a|^2 + |b|^2 - 2 a.b: costs within 1e-5 |c| + 1e-6 max |c| of the
- * exact k-ordered sums, arg-min indices equal except where two costs lie within that band).
+ * sum |terms|) and "fm_mfma" (nn.SpatialMatching as a banded GEMM, |a|^2 + |b|^2 - 2 a.b: each cost within 4 u (K + 2) (|a|^2 + |b|^2)
+ * of the exact sum of squared differences, u = 2^-24 -- an error ABSOLUTE in the squared norms of the two feature vectors, not relative
+ * to the cost, so features with a common offset lose the small costs' digits; arg-min indices equal except where the two best costs lie
+ * within twice that band; maps of K (H1 + maxh - 1) (W1 + maxw - 1) >= 2^30 floats take the exact kernels).
  * replaces: the option tables the reference's drivers pass down (opticalflow.lua:138-198 `geometry`), for the switches that have no
  * counterpart there.  Unknown key: DFE_E_ARG. */
 int dfe_set_option(dfe_ctx *ctx, const char *key, int value);
@@ -385,7 +387,9 @@ int dfe_multiscale_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const f
  *   index [H1][W1] int64 1-based class ids, scores [H1][W1] extractOutput's score (0 without threshold).  Pixels where no probability
  *   exceeds 0.11 -- imaxs / scores uninitialised in the reference -- get index = the centre class and score 0.
  *   16- / 17-wide windows on maps at least 253 columns wide never write the volume (the matcher's soft-max epilogue); other shapes go
- *   through the stand-alone ops.  Either way the results equal the module path's (getModel():forward + processOutput) bit for bit. */
+ *   through the stand-alone ops.  Either way the results equal the module path's (getModel():forward + processOutput) bit for bit.
+ *   The one-kernel form needs the planes of patch 1 below 2^29 floats (prefilter: H W < 2^29); beyond, the stand-alone ops materialise the
+ *   volume (H1 W1 maxh maxw floats, twice) and the call fails with DFE_E_ALLOC where that does not fit the device. */
 int dfe_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, const dfe_filter_layer *layers, int nlayers,
                                int maxh, int maxw, int use_threshold, double threshold, int hImg, int wImg, float *full, float *full_conf,
                                int64_t *index, float *scores);

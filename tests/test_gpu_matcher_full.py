@@ -260,8 +260,9 @@ def test_version2_with_matrix_core_convolution_at_vga(dfe, cuda):
 @pytest.mark.parametrize("K,H1,W1,mh", [(32, 448, 608, 17), (32, 60, 301, 17), (10, 50, 270, 16), (8, 23, 40, 17), (5, 9, 17, 16)])
 def test_matrix_core_matcher_within_tolerance_of_the_exact_kernels(dfe, cuda, K, H1, W1, mh):
     """dfe_set_option("fm_mfma", 1): nn.SpatialMatching(17, 17) / (16, 16) as a banded GEMM on the matrix cores (csrc/feat_matching_mfma.hip,
-    |a|^2 + |b|^2 - 2 a.b with v_mfma_f32_16x16x4_f32).  Against the exact kernels: every cost within 1e-5 |c| + 1e-6 max|c| (stated in
-    include/dfe.h; the oracle on row bands confirms the exact side), every cell written (NaN pre-fill), the arg-min form's index equal to the
+    |a|^2 + |b|^2 - 2 a.b with v_mfma_f32_16x16x4_f32).  Against the exact kernels: every cost within 1e-5 |c| + 1e-6 max|c| (holds for
+    these zero-mean features; the general bound, relative to |a|^2 + |b|^2, is in include/dfe.h and checked in float64 by
+    test_gpu_matcher_mfma.py; the oracle on row bands confirms the exact side), every cell written (NaN pre-fill), the arg-min form's index equal to the
     exact first minimum except where the exact volume's two best costs lie within twice that band -- the count of differing pixels is
     reported and bounded -- and the decoded flows are the index's.  Shapes: version2's VGA matcher (2128 tiles = 8.3 rounds per block),
     ragged widths / heights (W1 % 16, H1 % 8 != 0), K % 8 != 0 (zero-filled planes)."""
