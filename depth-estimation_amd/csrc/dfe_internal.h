@@ -33,6 +33,7 @@ enum DfeOpt {
     DFE_OPT_CONV_MFMA,        // one-call models: filter layers as implicit GEMMs on the matrix cores (fused multiply-adds; default 0 = exact kernels)
     DFE_OPT_FM_MFMA,          // feature matcher as a banded GEMM on the matrix cores, |a|^2 + |b|^2 - 2 a.b (default 0 = exact k-ordered sums)
     DFE_OPT_ARENA_CONTIG,     // scratch arena from physically contiguous memory (hipDeviceMallocContiguous; 0: plain hipMalloc)
+    DFE_OPT_CV_NOVOL,         // single-scale flow step without its cost volume (volume-free sweep; 0: build the volume, finalize reads it)
     DFE_NOPT
 };
 struct DfeOptName { const char *key; const char *env; bool env_presence_means_zero; };
@@ -301,8 +302,19 @@ struct CvFuseArgs {
 #define DFE_REC_NLEAD 8    // a pixel's first cells kept in its tile row's record (0: none, extractOutput reads them from the volume)
 #endif
 #define DFE_REC (32 + 8 * DFE_REC_NLEAD)   // floats per tile-row record (1 or 3 whole 128-B lines)
-#define DFE_REC_CENTRE 16  // (entries 0..15: (minimum, index) of the 8 pixels; 16..23: their centre costs; 24..31: 0)
+#define DFE_REC_CENTRE 16  // (entries 0..15: (minimum, index) of the 8 pixels; 16..23: their centre costs; 24..31: 0 or the fallback flags)
+#define DFE_REC_FLAG 24    // (entries 24..31, volume-free sweep only: 1 = fewer than M lead cells pass, extractOutput's hits are in the fallback plane)
 #define DFE_REC_LEAD 32    // (entries 32..: [pixel][DFE_REC_NLEAD] the pixels' first cells)
+// Volume-free flow sweep (ssd_cv_rowimg_flow_kernel): extractOutput's rare fall-back is taken inside the kernel, from the row image in
+// LDS.  A pixel whose first DFE_REC_NLEAD cells hold fewer than M values above the threshold gets its first M hits over all cells, in
+// index order, in the fallback plane [column group][output row][8 pixels][DFE_FB] floats = (value, 1-based index as a float) pairs,
+// zero-padded; the pixel's record flag says so.  Other pixels' entries are never written nor read.
+#define DFE_FB 16          // floats per pixel of the fallback plane: 8 (value, index) pairs, 64 B
+struct CvNovolArgs {
+    float *fb;             // the fallback plane
+    float thr;             // the largest float <= the extractOutput threshold: v > thr <=> (double)v > threshold for every float v
+    int M;                 // hits extractOutput keeps (8 if threshold < 0.2, else 4)
+};
 // ---- the finalize of a pixel from its tile row's record: flow_finalize_kernel's record path (postops.hip), kept here next to the record layout it reads
 // (round 4 also ran it at the end of the fused sweep: no gain, ssd_cost_volume.hip) ----
 // replaces: radial/radial_opticalflow_groundtruth.lua:87-105 (min(3), tie-break, decode, extractOutput)
@@ -347,10 +359,11 @@ __device__ __forceinline__ void pair_depth_px(int i, int j, float dy, float dx, 
 // A6: the record's (minimum, first index), centre override.  A9: decode.  A7: extractOutput over the pixel's first DFE_REC_NLEAD cells
 // (in the record), walking on through the volume itself only if fewer than M of them pass the threshold (extract_output.cpp:99-112 stops
 // at M as well).  p: pixel index inside the band (row-major over Wo); (fi, fj): its frame position (frame mode).
+// fb != nullptr (the volume-free sweep; vol is nullptr then): pixels whose record flag is set take their hits from the fallback plane.
 template <int M>
 __device__ __forceinline__ void dfe_finalize_rec_pixel(const float *__restrict__ rec, int rec_rows, const float *__restrict__ vol, long long p, int N,
                                                        int hWin, int wWin, int middle, double threshold, const TailOut &o, int fi, int fj,
-                                                       int iy = -1, int ix = -1) {
+                                                       int iy = -1, int ix = -1, const float *__restrict__ fb = nullptr) {
     // (iy, ix): the pixel's row / column inside the band where the caller has them (frame mode) -- else from p, as a 32-bit division
     // (the 64-bit quotient and remainder of the first version were a hundred instructions of a kernel that has few others)
     const long long pg = o.p_off + p;
@@ -387,31 +400,37 @@ __device__ __forceinline__ void dfe_finalize_rec_pixel(const float *__restrict__
 #pragma unroll
         for (int j = 0; j < M; ++j) { hv[j] = 0.f; hi[j] = 0.f; }
         int n = 0;
-        float qq[DFE_REC_NLEAD];
-        const float *lv = rp + DFE_REC_LEAD + (x - xb) * DFE_REC_NLEAD;
-        {
-            const dfe_f4v q0 = __builtin_nontemporal_load(reinterpret_cast<const dfe_f4v *>(lv)), q1 = __builtin_nontemporal_load(reinterpret_cast<const dfe_f4v *>(lv) + 1);
+        if (fb && __builtin_nontemporal_load(rp + DFE_REC_FLAG + x - xb) != 0.f) {   // rare: the kernel found fewer than M hits in the lead cells
+            const float *fp = fb + (((long long)g * rec_rows + y) * 8 + (x - xb)) * DFE_FB;
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) { qq[kk] = q0[kk]; qq[4 + kk] = q1[kk]; }
-        }
+            for (int j = 0; j < M; ++j) { hv[j] = fp[2 * j]; hi[j] = fp[2 * j + 1]; }
+        } else {
+            float qq[DFE_REC_NLEAD];
+            const float *lv = rp + DFE_REC_LEAD + (x - xb) * DFE_REC_NLEAD;
+            {
+                const dfe_f4v q0 = __builtin_nontemporal_load(reinterpret_cast<const dfe_f4v *>(lv)), q1 = __builtin_nontemporal_load(reinterpret_cast<const dfe_f4v *>(lv) + 1);
 #pragma unroll
-        for (int kk = 0; kk < DFE_REC_NLEAD; ++kk) {
-            if (kk < N && n < M && (double)qq[kk] > threshold) {
-#pragma unroll
-                for (int j = 0; j < M; ++j)
-                    if (j == n) { hv[j] = qq[kk]; hi[j] = (float)(kk + 1); }
-                ++n;
+                for (int kk = 0; kk < 4; ++kk) { qq[kk] = q0[kk]; qq[4 + kk] = q1[kk]; }
             }
-        }
-        if (n < M && N > DFE_REC_NLEAD) {   // rare: keep scanning the volume itself
-            const float *v = vol + p * N;
-            for (int kk = DFE_REC_NLEAD; kk < N && n < M; ++kk) {
-                const float t = v[kk];
-                if ((double)t > threshold) {
+#pragma unroll
+            for (int kk = 0; kk < DFE_REC_NLEAD; ++kk) {
+                if (kk < N && n < M && (double)qq[kk] > threshold) {
 #pragma unroll
                     for (int j = 0; j < M; ++j)
-                        if (j == n) { hv[j] = t; hi[j] = (float)(kk + 1); }
+                        if (j == n) { hv[j] = qq[kk]; hi[j] = (float)(kk + 1); }
                     ++n;
+                }
+            }
+            if (!fb && n < M && N > DFE_REC_NLEAD) {   // rare: keep scanning the volume itself (with fb: flag clear, n == M here)
+                const float *v = vol + p * N;
+                for (int kk = DFE_REC_NLEAD; kk < N && n < M; ++kk) {
+                    const float t = v[kk];
+                    if ((double)t > threshold) {
+#pragma unroll
+                        for (int j = 0; j < M; ++j)
+                            if (j == n) { hv[j] = t; hi[j] = (float)(kk + 1); }
+                        ++n;
+                    }
                 }
             }
         }
@@ -436,7 +455,7 @@ struct DfePairDepth { int H, W; float cx, cy; float *depth, *conf; };
 int dfe_flow_finalize(dfe_ctx *ctx, const float2 *part, const float *centre, const float *lead, int nchunks, long long Ptot,
                       const float *vol, double threshold, int rows, int Wo, int hWin, int wWin, int row_off, int64_t *idx, float *best,
                       float *fy, float *fx, float *scores, int64_t *imaxs, int pitch, int pad_t, int pad_l, int scores_padded,
-                      const struct DfePairDepth *pd = nullptr, const float *rec = nullptr, int rec_rows = 0);
+                      const struct DfePairDepth *pd = nullptr, const float *rec = nullptr, int rec_rows = 0, const float *fb = nullptr);
 struct TailOut;
 void dfe_make_tailout(TailOut *o, int64_t *idx, float *best, float *fy, float *fx, float *scores, int64_t *imaxs, int Wo, int pitch, int pad_t, int pad_l,
                       int scores_padded, int row_off, const struct DfePairDepth *pd);

@@ -184,7 +184,8 @@ __global__ void x2yx_multi_compat_kernel(CompatGeom g, const long long *__restri
 // branch, without the three-plane branch next to it (its registers, its scalar spills and 1 900 lines of code that never run here).
 template <int M>
 __global__ __launch_bounds__(256) void flow_finalize_rec_kernel(const float *__restrict__ vol, long long Pband, int N, int hWin, int wWin, int middle,
-                                                                double threshold, TailOut o, const float *__restrict__ rec, int rec_rows) {
+                                                                double threshold, TailOut o, const float *__restrict__ rec, int rec_rows,
+                                                                const float *__restrict__ fb) {
     const long long nthreads_work = o.frame_H ? (long long)o.frame_H * o.frame_W : Pband;
     for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nthreads_work; q += (long long)gridDim.x * blockDim.x) {
         long long p = q;
@@ -201,10 +202,10 @@ __global__ __launch_bounds__(256) void flow_finalize_rec_kernel(const float *__r
                 continue;
             }
             p = (long long)iy * o.Wo + ix;
-            dfe_finalize_rec_pixel<M>(rec, rec_rows, vol, p, N, hWin, wWin, middle, threshold, o, fi, fj, iy, ix);
+            dfe_finalize_rec_pixel<M>(rec, rec_rows, vol, p, N, hWin, wWin, middle, threshold, o, fi, fj, iy, ix, fb);
             continue;
         }
-        dfe_finalize_rec_pixel<M>(rec, rec_rows, vol, p, N, hWin, wWin, middle, threshold, o, fi, fj);
+        dfe_finalize_rec_pixel<M>(rec, rec_rows, vol, p, N, hWin, wWin, middle, threshold, o, fi, fj, -1, -1, fb);
     }
 }
 
@@ -512,7 +513,7 @@ void dfe_make_tailout(TailOut *po, int64_t *idx, float *best, float *fy, float *
 int dfe_flow_finalize(dfe_ctx *ctx, const float2 *part, const float *centre, const float *lead, int nchunks, long long Ptot,
                       const float *vol, double threshold, int rows, int Wo, int hWin, int wWin, int row_off, int64_t *idx, float *best,
                       float *fy, float *fx, float *scores, int64_t *imaxs, int pitch, int pad_t, int pad_l, int scores_padded,
-                      const DfePairDepth *pd, const float *rec, int rec_rows) {
+                      const DfePairDepth *pd, const float *rec, int rec_rows, const float *fb) {
     if (rec) nchunks = 1;
     TailOut o;
     dfe_make_tailout(&o, idx, best, fy, fx, scores, imaxs, Wo, pitch, pad_t, pad_l, scores_padded, row_off, pd);
@@ -520,13 +521,14 @@ int dfe_flow_finalize(dfe_ctx *ctx, const float2 *part, const float *centre, con
     const int N = hWin * wWin;
     const int middle = (wWin + 1) / 2 + wWin * ((hWin + 1) / 2 - 1);
     const int grid = grid_for(pd ? (long long)pd->H * pd->W : Pb, 256);
+    DFE_REQUIRE(ctx, !fb || (rec && N > DFE_REC_NLEAD), DFE_E_ARG, "flow finalize: a fallback plane goes with records");
     if (rec) {
         DFE_REQUIRE(ctx, Pb < (1ll << 31), DFE_E_SHAPE, "flow finalize: %lld pixels in one band", Pb);   // (32-bit pixel arithmetic in the record path)
         DFE_REQUIRE(ctx, !pd || (long long)pd->H * pd->W < (1ll << 31), DFE_E_SHAPE, "flow finalize: frame of %d x %d pixels", pd ? pd->H : 0, pd ? pd->W : 0);
         if (threshold < 0.2)   // extract_output.cpp:83-85
-            hipLaunchKernelGGL(flow_finalize_rec_kernel<8>, dim3(grid), dim3(256), 0, ctx->stream, vol, Pb, N, hWin, wWin, middle, threshold, o, rec, rec_rows);
+            hipLaunchKernelGGL(flow_finalize_rec_kernel<8>, dim3(grid), dim3(256), 0, ctx->stream, vol, Pb, N, hWin, wWin, middle, threshold, o, rec, rec_rows, fb);
         else
-            hipLaunchKernelGGL(flow_finalize_rec_kernel<4>, dim3(grid), dim3(256), 0, ctx->stream, vol, Pb, N, hWin, wWin, middle, threshold, o, rec, rec_rows);
+            hipLaunchKernelGGL(flow_finalize_rec_kernel<4>, dim3(grid), dim3(256), 0, ctx->stream, vol, Pb, N, hWin, wWin, middle, threshold, o, rec, rec_rows, fb);
         DFE_LAUNCH_CHECK(ctx);
         return DFE_OK;
     }

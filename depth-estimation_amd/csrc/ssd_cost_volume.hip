@@ -30,6 +30,8 @@
 #include "dfe_internal.h"
 #include <type_traits>
 #include <memory>
+#include <cmath>
+#include <limits>
 
 // ------------------------------------------------------------------------------------------
 // reference-order kernel
@@ -221,7 +223,7 @@ extern __shared__ __attribute__((aligned(16))) char dfe_smem[];
 // 2 waves x 4 columns spill (24 registers of ring state).
 #define DFE_NQW 4
 #endif
-#define DFE_CV_KERNEL_REV "cv-r4.1"
+#define DFE_CV_KERNEL_REV "cv-r6.0"
 #ifndef DFE_SMEM_JIT
 #define DFE_SMEM_JIT 0   // tuning: frame-0 scalars of a row loaded at its start instead of one row ahead
 #endif
@@ -876,9 +878,11 @@ template <int C, int K, int TX> struct RowimgGeom {
 // the global HALF index mod 64; the copy-out converts 8 cells per lane into one dwordx4.  Static tiles only (a 128-B line
 // holds 64 cells: completing the run's last line would take up to 63 cells of the next pixel, more than the mini task's
 // idle lanes, so partial lines stay and rely on the XCD-aware block order).
-template <int C, int K, int TX, bool SM, bool FUSE, bool SWEEP, int DC = 0, bool F16 = false>
-__global__ __launch_bounds__(1024) void ssd_cv_rowimg_kernel(const float *__restrict__ I0, const float *__restrict__ I1,
-                                                             float *__restrict__ out, CvTiledArgs p, CvFuseArgs fa) {
+// NOVOL (ssd_cv_rowimg_flow_kernel: the fused 3-channel 33 x 33 sweep of the flow step): no volume and no copy-out.  The scan waves
+// also take extractOutput's rare fall-back (CvNovolArgs) from the cells they hold, so nothing downstream needs the volume.
+template <int C, int K, int TX, bool SM, bool FUSE, bool SWEEP, int DC, bool F16, bool NOVOL>
+__device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const float *__restrict__ I1, float *__restrict__ out, CvTiledArgs p,
+                                            CvFuseArgs fa, CvNovolArgs nv) {
     using px_t = typename Px<C>::type;
     constexpr int NW = 16;
     constexpr int U = VUnroll<K>::value;
@@ -896,6 +900,7 @@ __global__ __launch_bounds__(1024) void ssd_cv_rowimg_kernel(const float *__rest
     //  wins, VGA luminance 215 against 254 us)
     constexpr bool ROLES = FUSE && (SWEEP || DFE_ROLES_STATIC) && DFE_ROLES && TX == 8 && DC == 1089 && C == 3;
     // the last wave neither scans nor copies: in the column sweep it refills the rings, with roles it carries the mini task
+    static_assert(!NOVOL || ROLES, "the volume-free sweep is the role-split one");
     constexpr bool HAS_XW = SWEEP || ROLES;
     // (Which SIMD carries what, wave w on SIMD w % 4: every SIMD has one quarter-task + scan wave (0 .. 3) and one plain scan wave (4 .. 7);
     //  SIMD 3 also has wave 15 with the mini task and the ring refill, ~93 vector instructions a row on top of its main task
@@ -1137,7 +1142,29 @@ __global__ __launch_bounds__(1024) void ssd_cv_rowimg_kernel(const float *__rest
     // (cells 9 (64 + l) ..); both units' reads in flight together, ONE wave minimum for both, the first index from the lower
     // unit if any of its lanes attains the minimum.  Plane 1 of fa.part gets +inf (finalize keeps the smaller of the two).
     float *recbuf = stage + 2 * g_stage_len;       // ROLES: [2][DFE_REC] the tile row's record, double-buffered like the images
-    auto scan_row_whole = [&](const float *stp, int rpar) {
+    // NOVOL, rare: the first M cells of the pixel's run (px, in the row image) above the threshold, in cell order, into the pixel's entry
+    // of the fallback plane, zero-padded: 64 cells a step, the hits ranked by a ballot, the count wave-uniform, done at M hits.
+    // (Behind the scan, one live value per lane: with a prefix sum over the scan's two 9-cell units, still in registers, the sweep spilled.)
+    auto fallback_walk = [&](const float *px, int yrow, int xx) {
+        int lf = lane;
+        asm volatile("" : "+v"(lf));
+        float *fbp = nv.fb + (((long long)bx * p.Ho + yrow) * TX + xx) * DFE_FB;
+        int n = 0;
+        for (int c = 0; c < D && n < nv.M; c += 64) {
+            const int cc = c + lf;
+            const float v = px[min(cc, D - 1)];
+            const bool hit = cc < D && v > nv.thr;
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+            const int k = n + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            if (hit && k < nv.M) {
+                fbp[2 * k] = v;
+                fbp[2 * k + 1] = (float)(cc + 1);
+            }
+            n += __builtin_popcountll(m);
+        }
+        if (lf >= 2 * min(n, nv.M) && lf < 2 * nv.M) fbp[lf] = 0.f;
+    };
+    auto scan_row_whole = [&](const float *stp, int rpar, int yrow) {
         constexpr int CPL = 9;
         static_assert(!ROLES || DC % CPL == 0, "whole lanes only");
         int lsc = lane;
@@ -1198,6 +1225,16 @@ __global__ __launch_bounds__(1024) void ssd_cv_rowimg_kernel(const float *__rest
         // 1.78 .. 2.21 ms depending on where the process' arena had landed (without them: 1.78 .. 1.81 ms in every process).
         // The pixel's first DFE_REC_NLEAD cells follow in the same record (lane 0 holds them already).
         static_assert(!ROLES || DC == 1089, "centre cell 544");
+        // NOVOL: extractOutput's fall-back.  Lane 0 holds the pixel's first 8 cells; fewer than M of them above the threshold (rare,
+        // wave-uniform) sends the wave through fallback_walk below, and the record's flag sends the finalize to what it wrote.
+        bool fbk = false;
+        if constexpr (NOVOL) {
+            static_assert(DFE_REC_NLEAD == 8 && DC > DFE_REC_NLEAD, "the lead cells are lane 0's first 8");
+            int nl = 0;
+#pragma unroll
+            for (int i = 0; i < DFE_REC_NLEAD; ++i) nl += __int_as_float(c0[i]) > nv.thr ? 1 : 0;
+            fbk = __builtin_amdgcn_readfirstlane(nl) < nv.M;
+        }
         {
             const float cen = stp[xx * D + 544];
             if (lsc == 0) {
@@ -1205,6 +1242,7 @@ __global__ __launch_bounds__(1024) void ssd_cv_rowimg_kernel(const float *__rest
                 rb[2 * xx] = __int_as_float(vmin);
                 rb[2 * xx + 1] = __int_as_float(idx);
                 rb[DFE_REC_CENTRE + xx] = cen;
+                if constexpr (NOVOL) rb[DFE_REC_FLAG + xx] = fbk ? 1.f : 0.f;
                 if constexpr (DFE_REC_NLEAD >= 4) {      // lane 0 holds the run's cells 0..8 already: the first 4 / 8 ride along (16-B LDS writes)
                     static_assert(DFE_REC_NLEAD == 4 || DFE_REC_NLEAD == 8, "one or two 16-B pieces");
                     typedef int i4_t __attribute__((ext_vector_type(4)));
@@ -1214,6 +1252,8 @@ __global__ __launch_bounds__(1024) void ssd_cv_rowimg_kernel(const float *__rest
                 }
             }
         }
+        if constexpr (NOVOL)
+            if (fbk) fallback_walk(stp + xx * D, yrow, xx);
     };
     // the record of the tile row whose scan ran behind the previous barrier: [column group bx][output row yrow of the pair]
     // (rb: the record's address, carried from row to row like G0 -- one 64-bit scalar instead of the base, the row pitch and the band
@@ -1430,7 +1470,7 @@ __global__ __launch_bounds__(1024) void ssd_cv_rowimg_kernel(const float *__rest
                     // (written by the first COPY wave: wave LW refills the rings and waits for its loads with vmcnt(0) -- a store of its own
                     //  would put the whole store stream's latency into that wait: 1080p 2.32 against 1.8 ms)
                     if (wave == TX && r - 1 >= K - 1 && y - 1 >= y0n) write_record((r - 1) & 1, rec_prev);
-                    if (store_row && wave < TX) scan_row_whole(st, r & 1);
+                    if (store_row && wave < TX) scan_row_whole(st, r & 1, y);
                 } else if constexpr (FUSE && !DFE_SCAN_AFTER_COPY) {
                     if (store_row) scan_row(st, pg_run);
                 }
@@ -1446,7 +1486,7 @@ __global__ __launch_bounds__(1024) void ssd_cv_rowimg_kernel(const float *__rest
                 //  only the four scan waves without a quarter task taking them 270 us.)
                 constexpr int CW0 = ROLES ? TX : FUSE ? 0 : DFE_CW0;          // first copier wave
                 constexpr int NCW = (HAS_XW ? LW : NW) - CW0;                // copier waves
-                if (store_row && wave >= CW0 && (!HAS_XW || wave != LW)) {
+                if (!NOVOL && store_row && wave >= CW0 && (!HAS_XW || wave != LW)) {
                     const int ov = nover * D;                                // floats of the run that are the neighbour's (shifted last tile)
                     int tj = tid - CW0 * 64;
                     asm volatile("" : "+v"(tj));   // keeps per-lane copy addresses from being hoisted (and spilled)
@@ -1567,6 +1607,19 @@ __global__ __launch_bounds__(1024) void ssd_cv_rowimg_kernel(const float *__rest
     //  behind the drain of the block's stores (two dependent passes over ~1100 pixels a block), which is what the launch and its boundary
     //  cost: a step is kernel + ~6 us of launch boundary whether that holds one kernel or two.  Taken out again.)
 }
+template <int C, int K, int TX, bool SM, bool FUSE, bool SWEEP, int DC = 0, bool F16 = false>
+__global__ __launch_bounds__(1024) void ssd_cv_rowimg_kernel(const float *__restrict__ I0, const float *__restrict__ I1,
+                                                             float *__restrict__ out, CvTiledArgs p, CvFuseArgs fa) {
+    rowimg_body<C, K, TX, SM, FUSE, SWEEP, DC, F16, false>(I0, I1, out, p, fa, CvNovolArgs{});
+}
+// the flow step's sweep without its volume: the fused 3-channel 33 x 33 column sweep minus the copy-out (its 7 copy waves idle behind
+// the barrier, wave TX still writes the records), plus extractOutput's fall-back in the scan waves
+template <int C, int K, int TX>
+__global__ __launch_bounds__(1024) void ssd_cv_rowimg_flow_kernel(const float *__restrict__ I0, const float *__restrict__ I1, CvTiledArgs p,
+                                                                  CvFuseArgs fa, CvNovolArgs nv) {
+    static_assert(C == 3 && K == 7 && TX == 8, "the role-split sweep's instantiation");
+    rowimg_body<C, K, TX, DFE_RI_SMEM, true, true, 1089, false, true>(I0, I1, nullptr, p, fa, nv);
+}
 
 // LDS bytes of a static-tile block of `ty` output rows (0 = does not apply) and the kernel arguments that go with it
 template <int C, int K, int TX>
@@ -1653,9 +1706,10 @@ static int sweep_aligned_k(const dfe_ctx *ctx, int ncols, int Ho) {
     const int k = ctx->ncu / ncols;
     return (k >= 2 && Ho / k >= 24) ? k : 0;
 }
+// (nv != nullptr: the volume-free flow sweep, ssd_cv_rowimg_flow_kernel -- out is not written)
 template <int C, int K, int TX, bool FUSE>
 static int launch_cv_rowimg_sweep(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, long long plane, int hWin, int wWin,
-                                  float *out, const CvFuseArgs *fa, bool *handled) {
+                                  float *out, const CvFuseArgs *fa, bool *handled, const CvNovolArgs *nv = nullptr) {
     using px_t = typename Px<C>::type;
     constexpr int U = VUnroll<K>::value;
     constexpr int R = 64, R0 = 8;                 // ring rows (frame-1: a power of two >= hWin + 2; frame-0)
@@ -1694,10 +1748,26 @@ static int launch_cv_rowimg_sweep(dfe_ctx *ctx, const float *I0, const float *I1
         return dfe_fail(ctx, DFE_E_UNSUPPORTED, "row-image sweep: LDS geometry differs from the kernel's constants");
     // the fused sweep fits the register file only with D as a constant (33 x 33); other windows: static tiles
     if (FUSE && !sq33) return DFE_OK;
+    dim3 grid(nblk, 1);
+    if constexpr (FUSE && C == 3 && K == 7 && TX == 8) {
+        if (nv) {
+            if (!sq33 || !fa) return DFE_OK;
+            auto kern = ssd_cv_rowimg_flow_kernel<C, K, TX>;
+            DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+            {
+                DfeProfScope prof(ctx, true);
+                hipExtLaunchKernelGGL(kern, grid, dim3(1024), lds_bytes, ctx->stream, prof.a, prof.b, 0, I0, I1, a, *fa, *nv);
+            }
+            DFE_LAUNCH_CHECK(ctx);
+            ctx->last_kernel = "ssd_cv_rowimg_kernel+fused_tail+novol";
+            *handled = true;
+            return DFE_OK;
+        }
+    }
+    if (nv) return DFE_OK;
     auto kern = sq33 ? ssd_cv_rowimg_kernel<C, K, TX, DFE_RI_SMEM, FUSE, true, 1089>
                             : ssd_cv_rowimg_kernel<C, K, TX, DFE_RI_SMEM, false, true>;
     DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    dim3 grid(nblk, 1);
     {
         DfeProfScope prof(ctx, true);
         hipExtLaunchKernelGGL(kern, grid, dim3(1024), lds_bytes, ctx->stream, prof.a, prof.b, 0, I0, I1, out, a, fa ? *fa : CvFuseArgs{});
@@ -2008,6 +2078,56 @@ static int band_rows(const dfe_ctx *ctx, int Ho, int Wo, int D, int elem = (int)
 }
 static int band_count(int Ho, int band) { return (Ho + band - 1) / band; }
 
+// the largest float <= t (NaN stays NaN): for every float v, v > float_at_or_below(t) <=> (double)v > t -- a hit strictly above a float
+// f <= t is at least the next float, which lies above t -- so the kernel compares in fp32 exactly as the finalize does in fp64
+static float float_at_or_below(double t) {
+    if (std::isnan(t)) return std::numeric_limits<float>::quiet_NaN();
+    if (t >= (double)std::numeric_limits<float>::max()) return std::isinf(t) ? std::numeric_limits<float>::infinity() : std::numeric_limits<float>::max();
+    if (t < -(double)std::numeric_limits<float>::max()) return -std::numeric_limits<float>::infinity();
+    float f = (float)t;
+    if ((double)f > t) f = std::nextafter(f, -std::numeric_limits<float>::infinity());
+    return f;
+}
+
+// The flow step without its cost volume (option "cv_novol", default on): the volume-free fused sweep leaves records and, for the rare
+// pixels whose lead cells hold fewer than M hits, the fallback plane; one launch for the whole pair (no bands: 112 B of scratch per
+// pixel instead of 4356), then the record finalize.  Returns DFE_OK with *done = false where the sweep does not apply.
+static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, int hWin, int wWin, double thr, int64_t *idx,
+                               float *best, float *fy, float *fx, float *scores, int64_t *imaxs, int pitch, int pad_t, int pad_l,
+                               int scores_padded, const DfePairDepth *pd, bool *pd_done, bool *done) {
+    constexpr int K = 7;
+    *done = false;
+    const int Ho = H - K + 1 - hWin + 1, Wo = W - K + 1 - wWin + 1;
+    const long long P = (long long)Ho * Wo;
+    if (Wo < 8 || P >= (1ll << 31) || (pd && (long long)pd->H * pd->W >= (1ll << 31))) return DFE_OK;   // (the finalize's 32-bit pixel arithmetic)
+    const size_t rec_bytes = ((size_t)dfe_cdiv(Wo, 8) * Ho * DFE_REC * sizeof(float) + 255) / 256 * 256;   // [tile column][output row][DFE_REC]
+    const size_t fb_bytes = (size_t)dfe_cdiv(Wo, 8) * Ho * 8 * DFE_FB * sizeof(float);                     // [tile column][output row][8][DFE_FB]
+    void *scr = nullptr;
+    int rc = dfe_scratch(ctx, rec_bytes + fb_bytes, &scr);
+    if (rc) return rc;
+    CvFuseArgs fa{};
+    fa.rec = (float *)scr;
+    fa.rec_rows = Ho;
+    fa.row_off = 0;
+    fa.Ptot = P;
+    CvNovolArgs nv;
+    nv.fb = (float *)((char *)scr + rec_bytes);
+    nv.thr = float_at_or_below(thr);
+    nv.M = thr < 0.2 ? 8 : 4;   // extract_output.cpp:83-85
+    bool handled = false;
+    {
+        DfeStageScope match(ctx, DFE_STAGE_MATCH);
+        rc = launch_cv_rowimg_sweep<3, 7, 8, true>(ctx, I0, I1, H, W, (long long)H * W, hWin, wWin, nullptr, &fa, &handled, &nv);
+        if (rc || !handled) return rc;
+    }
+    *done = true;
+    DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
+    rc = dfe_flow_finalize(ctx, nullptr, nullptr, nullptr, 2, P, nullptr, thr, Ho, Wo, hWin, wWin, 0, idx, best, fy, fx, scores, imaxs, pitch,
+                           pad_t, pad_l, scores_padded, pd, fa.rec, Ho, nv.fb);
+    if (pd && pd_done) *pd_done = true;
+    return rc;
+}
+
 // One pair through build + flow extraction.  Preferred: the fused build (per-chunk minimum + first index, the centre
 // cell and the pixel's first 16 cells leave the kernel with the volume, ~210 compact bytes per pixel) + a finalize that
 // reads only those; it goes back to the volume only for pixels whose first 16 cells hold fewer than M values above
@@ -2019,6 +2139,13 @@ static int flow_pipeline(dfe_ctx *ctx, const float *I0, const float *I1, int C, 
     // f16_scale != 0: the volume is materialised as fp16 (cost * f16_scale); arg-min, centre and lead cells still come from
     // the fp32 sums in the kernel, so indices and minima are those of the fp32 path.  No extractOutput scores then (its
     // rare fall-back reads the volume).
+    if (kh == kw && kh == 7 && f16_scale == 0.f && rowimg_writes_records(C, hWin, wWin) && ctx->opt_bool(DFE_OPT_CV_NOVOL, true) &&
+        (ctx->cv_mode == 0 || ctx->cv_mode == 3) && (ctx->cv_tyq == 0 || ctx->cv_tyq == 1)) {   // (forced static tiles: the volume path)
+        bool done = false;
+        int rc = flow_pipeline_novol(ctx, I0, I1, H, W, hWin, wWin, thr, idx, best, fy, fx, scores, imaxs, pitch, pad_t, pad_l, scores_padded, pd,
+                                     pd_done, &done);
+        if (rc || done) return rc;
+    }
     const int Ho = H - kh + 1 - hWin + 1, Wo = W - kw + 1 - wWin + 1;
     const int D = hWin * wWin, nch = (D + 63) / 64;
     const long long P = (long long)Ho * Wo;
