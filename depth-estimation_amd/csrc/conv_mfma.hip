@@ -19,12 +19,6 @@
 #ifndef DFE_CM_STAMPS
 #define DFE_CM_STAMPS 0
 #endif
-#ifndef DFE_CM_SCHED
-#define DFE_CM_SCHED 1
-#endif
-#ifndef DFE_CM_ABL
-#define DFE_CM_ABL 0   // tuning: 1 = the step loop without its LDS reads, 2 = no output stores, 3 = no staging of the next tile
-#endif
 namespace {
 
 typedef float f4v __attribute__((ext_vector_type(4)));
@@ -196,7 +190,7 @@ __global__ __launch_bounds__(1024) void conv_mfma_res_kernel(CmBatch cb, const f
 #endif
         const int tn = t + gridDim.x;
         const int nch = steps / CH;
-        if (tn < ntiles && DFE_CM_ABL != 3) load_tile(tn);          // (in flight behind the step loop)
+        if (tn < ntiles) load_tile(tn);          // (in flight behind the step loop)
         const char *tb = reinterpret_cast<const char *>(tile0 + cur * TSZ + abase);
         f4v acc[NT];
 #pragma unroll
@@ -215,69 +209,33 @@ __global__ __launch_bounds__(1024) void conv_mfma_res_kernel(CmBatch cb, const f
         float a0[CH], a1[CH];
         bv_t b0[CH], b1[CH];
         auto fetch = [&](float (&a)[CH], bv_t (&b)[CH]) {
-#if DFE_CM_ABL == 1
-#pragma unroll
-            for (int j = 0; j < CH; ++j) { a[j] = __int_as_float(off[j]); for (int nt = 0; nt < NT; ++nt) b[j][nt] = __int_as_float(off[j] + nt); }
-#else
-#if DFE_CM_ABL == 6 || DFE_CM_ABL == 9     // A operands at immediate offsets: no address adds, no tap table
-#pragma unroll
-            for (int j = 0; j < CH; ++j) a[j] = *reinterpret_cast<const float *>(tb + 64 * j);
-#elif DFE_CM_ABL == 8                      // no A reads at all
-#pragma unroll
-            for (int j = 0; j < CH; ++j) a[j] = __int_as_float(off[0]);
-#else
 #pragma unroll
             for (int j = 0; j < CH; ++j) a[j] = *reinterpret_cast<const float *>(tb + off[j]);
-#endif
-#if DFE_CM_ABL == 7 || DFE_CM_ABL == 9     // no B reads
-#pragma unroll
-            for (int j = 0; j < CH; ++j) for (int nt = 0; nt < NT; ++nt) b[j][nt] = __int_as_float(off[0]);
-#else
 #pragma unroll
             for (int j = 0; j < CH; ++j) b[j] = *reinterpret_cast<const bv_t *>(wp + j * 4 * 16 * NT);
-#endif
-#endif
             wp += CH * 4 * 16 * NT;
             kp += 4 * CH;
         };
         auto taps = [&]() {
-#if DFE_CM_ABL == 1
-#pragma unroll
-            for (int j = 0; j < CH; ++j) off[j] += j;
-#elif DFE_CM_ABL == 6 || DFE_CM_ABL == 8 || DFE_CM_ABL == 9
-#else
 #pragma unroll
             for (int j = 0; j < CH; ++j) off[j] = kp[4 * j];
-#endif
         };
         auto mm = [&](const float (&a)[CH], const bv_t (&b)[CH]) {
-#if DFE_CM_ABL == 4
-#pragma unroll
-            for (int j = 0; j < CH; ++j) asm volatile("" ::"v"(a[j]), "v"(b[j]));
-#else
 #pragma unroll
             for (int j = 0; j < CH; ++j)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j][nt], acc[nt], 0, 0, 0);
-#if DFE_CM_ABL == 5
-                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j][nt], acc[nt], 0, 0, 0);
-#endif
-                }
-#endif
+                for (int nt = 0; nt < NT; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j][nt], acc[nt], 0, 0, 0);
         };
         // (the scheduler is told to put one operand read and one address add behind every MFMA instead of all 24 reads in front of the
         //  sixteen MFMAs: a wave that runs ALONE on its SIMD -- the last one of a tile, the matrix pipe's arbitration is not fair -- then
-        //  still keeps the pipe busy: DFE_CM_SCHED)
+        //  still keeps the pipe busy)
         auto interleave = [&]() {
-#if DFE_CM_SCHED
 #pragma unroll
             for (int q = 0; q < CH * NT; ++q) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // one MFMA
                 __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);   // one VALU (an A address)
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // one LDS read
             }
-#endif
         };
         taps();
         fetch(a0, b0);                                               // chunk 0
@@ -337,7 +295,7 @@ __global__ __launch_bounds__(1024) void conv_mfma_res_kernel(CmBatch cb, const f
                         if (x + q < Wo) o[q] = sq[q];
                 }
             }
-            if (y < Ho && (DFE_CM_ABL != 2 || acc[0][0] == 1234.5f)) {
+            if (y < Ho) {
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt) {
                     const int plane = nt * 16 + m;
@@ -354,7 +312,7 @@ __global__ __launch_bounds__(1024) void conv_mfma_res_kernel(CmBatch cb, const f
                 }
             }
         }
-        if (tn < ntiles && DFE_CM_ABL != 3) store_tile(tile0 + (cur ^ 1) * TSZ);
+        if (tn < ntiles) store_tile(tile0 + (cur ^ 1) * TSZ);
         // LDS-only barrier: __syncthreads() also drains vmcnt, i.e. every wave would wait here until the tile's output stores are
         // acknowledged by the memory -- with nothing on the matrix pipe meanwhile
 #if DFE_CM_STAMPS

@@ -298,10 +298,8 @@ struct CvFuseArgs {
                            // left volume lines in the memory-side cache that slowed the next launch's stores by 10 %).
     int rec_rows;          // output rows of the pair (the record's row pitch)
 };
-#ifndef DFE_REC_NLEAD
-#define DFE_REC_NLEAD 8    // a pixel's first cells kept in its tile row's record (0: none, extractOutput reads them from the volume)
-#endif
-#define DFE_REC (32 + 8 * DFE_REC_NLEAD)   // floats per tile-row record (1 or 3 whole 128-B lines)
+#define DFE_REC_NLEAD 8    // a pixel's first cells kept in its tile row's record
+#define DFE_REC (32 + 8 * DFE_REC_NLEAD)   // floats per tile-row record (3 whole 128-B lines)
 #define DFE_REC_CENTRE 16  // (entries 0..15: (minimum, index) of the 8 pixels; 16..23: their centre costs; 24..31: 0 or the fallback flags)
 #define DFE_REC_FLAG 24    // (entries 24..31, volume-free sweep only: 1 = fewer than M lead cells pass, extractOutput's hits are in the fallback plane)
 #define DFE_REC_LEAD 32    // (entries 32..: [pixel][DFE_REC_NLEAD] the pixels' first cells)

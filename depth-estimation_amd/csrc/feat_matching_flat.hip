@@ -32,15 +32,8 @@ namespace {
 
 constexpr int FF_PX = 4;                     // pixels per lane
 constexpr int FF_GROUPS = 64;                // groups (lanes) per tile
-#ifndef FF_ST_FLAGS
-#define FF_ST_FLAGS " nt"   // cache policy of the copy-out stores
-#endif
-#ifndef FF_DEEP
-#define FF_DEEP 1     // 1: requests stay in flight for TWO planes (counted vmcnt), operands are read behind the barrier
-#endif
-#ifndef FF_BATCH
-#define FF_BATCH 8                           // (pixel, cell) pairs whose differences / squares / adds are issued as three groups
-#endif
+#define FF_ST_FLAGS " nt"                    // cache policy of the copy-out stores
+constexpr int FF_BATCH = 8;                  // (pixel, cell) pairs whose differences / squares / adds are issued as three groups
 template <int I, int N, class F> __device__ __forceinline__ void static_for_q(F &&f) {
     if constexpr (I < N) {
         f(std::integral_constant<int, I>{});
@@ -80,9 +73,6 @@ struct FfArgs {
     float *full, *full_conf, *scores;  // [2][hFull][wFull] (plane 0 = y), [hFull][wFull], [H1][W1]; each may be NULL (idx above: [H1][W1])
 };
 enum { FF_VOLUME = 0, FF_ARGMIN = 1, FF_SOFT = 2 };
-#ifndef DFE_FF_SOFT_FAST
-#define DFE_FF_SOFT_FAST 1
-#endif
 constexpr float FF_TIE = 1e-6f;   // FF_SOFT without a threshold: cells this close to a window's minimum may share its maximal probability
 
 template <int MW> struct FfGeom {
@@ -332,7 +322,7 @@ __global__ __launch_bounds__(1024) void feat_matching_flat_kernel(FfArgs p) {
         //  copies the staging pointers came out as vector registers and the requests' scalar-base form did not assemble.)
         lds_f *bs = tile, *bc = tile + BUFSZ, *bp = tile + 2 * BUFSZ;     // buffers of plane kk (requested now), kk - 2 (this iteration's arithmetic), kk - 1
         auto plane = [&](int kk, const bool STEADY) __attribute__((always_inline)) {   // STEADY: 2 <= kk < kplain, a constant at the call
-            if (FF_DEEP) read_head(bc);
+            read_head(bc);
             read_tail(bc);                                                // (kk < 2: nothing there yet, nothing is computed from it)
             if (STEADY || kk < p.K) stage(kk, bs, STEADY);
             __builtin_amdgcn_sched_barrier(0);
@@ -367,19 +357,15 @@ __global__ __launch_bounds__(1024) void feat_matching_flat_kernel(FfArgs p) {
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (!FF_DEEP) read_head(bp);     // (unconditional -- in the first and the last iteration the values are not used -- so that the operands stay
-                               //  in ONE register set: with the read under a condition the compiler kept two sets and 20 moves per plane)
-            // my requests of plane kk have landed; behind the barrier everyone's have, and every wave is past its reads of plane kk-3
-            if (FF_DEEP) {
-                // all but THIS iteration's requests have landed: the plane of the next iteration's arithmetic
-                // (plain planes: kk < K, or < K - 1 where the last plane takes the clamped path, whose request count differs)
-                // vmcnt(2) whatever the wave's role: everything but the LAST two requests has landed -- all of the previous plane's, and, for
-                // the waves with a second task, that task's requests of this plane, which went out first, a whole plane of arithmetic ago
-                // (counting the role's own 2 / 3 / 4 requests took a compare-and-branch chain per plane)
-                if (!STEADY && kk >= kplain) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
-            } else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
             { lds_f *const t = bs; bs = bc; bc = bp; bp = t; }            // (kk + 1) % 3, (kk - 1) % 3, kk % 3
+            // requests stay in flight for TWO planes: all but THIS iteration's requests have landed -- the plane of the next iteration's
+            // arithmetic, whose head operands that iteration reads behind the barrier; behind it every wave is past its reads of plane kk-3
+            // (plain planes: kk < K, or < K - 1 where the last plane takes the clamped path, whose request count differs)
+            // vmcnt(2) whatever the wave's role: everything but the LAST two requests has landed -- all of the previous plane's, and, for
+            // the waves with a second task, that task's requests of this plane, which went out first, a whole plane of arithmetic ago
+            // (counting the role's own 2 / 3 / 4 requests took a compare-and-branch chain per plane)
+            if (!STEADY && kk >= kplain) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(2)\n\ts_barrier" ::: "memory");
         };
         // fill (planes 0, 1 requested), steady planes (request + arithmetic + counted wait, none of the per-plane tests), the rest (the
         // clamped last plane where this wave has one, and the two drain iterations)
@@ -517,7 +503,7 @@ __global__ __launch_bounds__(1024) void feat_matching_flat_kernel(FfArgs p) {
                     // Windows with several such cells (flat regions, exact ties) take the full arithmetic below, wave by wave: same results.
                     bool full = p.use_thr != 0;
                     int fi = 0x7fffffff;
-                    if (!full && DFE_FF_SOFT_FAST) {
+                    if (!full) {
                         const float lim = FF_TIE - m;                     // (m = max(-c) = -cmin)
                         int cnt = 0;
 #pragma unroll
@@ -532,8 +518,6 @@ __global__ __launch_bounds__(1024) void feat_matching_flat_kernel(FfArgs p) {
                         FF_STEP(0x128) FF_STEP(0x124) FF_STEP(0x4E) FF_STEP(0xB1)
 #undef FF_STEP
                         full = __builtin_amdgcn_ballot_w64(cnt != 1) != 0;    // (wave-uniform)
-                    } else {
-                        full = true;
                     }
                     if (!full) {
                         id = (long long)fi + 1;

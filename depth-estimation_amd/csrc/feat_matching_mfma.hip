@@ -23,12 +23,6 @@
 //   B operand at an immediate offset.
 #include "dfe_internal.h"
 
-#ifndef DFE_FMM_PIPE
-#define DFE_FMM_PIPE 1
-#endif
-#ifndef DFE_FMM_KC16
-#define DFE_FMM_KC16 1
-#endif
 namespace {
 
 template <int I, int N, class F> __device__ __forceinline__ void fmm_static_for(F &&f) {
@@ -209,7 +203,7 @@ __global__ __launch_bounds__(FMM_T) void fmm_kernel(FmmArgs p) {
             const float *sb = fmm_smem + (gs & 1) * BUF;
             const float *Bw = sb + kq * BPS + wave * 32 + j;          // lane (j, kq): in2 plane kq, tile row wave + dy, column 16 tile + j
             const float *Aw = sb + KC * BPS + kq * APS + wave * 16 + j;
-            if constexpr (ARGMIN && DFE_FMM_PIPE) {
+            if constexpr (ARGMIN) {
                 // The operands of k-step ks + 1 are requested BETWEEN the MFMAs of k-step ks (one read behind every MFMA: the scheduler is told
                 // so), in a second register set -- the arg-min form has the registers (no volume addressing).  With all reads in front of a
                 // k-step's MFMAs the two waves of a SIMD, which leave every barrier together, both sat in their reads at once and the matrix
@@ -363,7 +357,7 @@ int dfe_feat_matching_mfma(dfe_ctx *ctx, const float *in1, const float *in2, int
     a.lWin = (maxw + 1) / 2 - 1; a.tWin = (maxh + 1) / 2 - 1;
     const int BROWS = (FMM_R + maxh - 1 + 3) & ~3;
     // the arg-min form stages 16 planes at a time where K allows it: three of four k-steps then have their operands requested behind MFMAs
-    const bool kc16 = DFE_FMM_KC16 && !out && K % 16 == 0;
+    const bool kc16 = !out && K % 16 == 0;
     const int KC = kc16 ? 16 : FMM_KC;
     const size_t lds = ((size_t)2 * (KC * (BROWS * 32 + 16) + KC * (FMM_R * 16)) + (size_t)2 * BROWS * 32) * sizeof(float);
     void (*kern)(FmmArgs) = out      ? (maxh == 17 ? fmm_kernel<17, 17, false> : fmm_kernel<16, 16, false>)

@@ -282,17 +282,13 @@ __global__ __launch_bounds__(256) void flow_finalize_kernel(const float2 *__rest
             float qq[DFE_LEAD];
 #pragma unroll
             for (int g4 = 0; g4 < DFE_LEAD / 4; ++g4) {                                   // pixel-major [P][DFE_LEAD]: 4 x 16 B
-                // (record mode: the pixel's first DFE_REC_NLEAD cells from its tile row's record; DFE_REC_NLEAD = 0 builds read them straight
-                //  from the volume -- p * N * 4 bytes is 4-B aligned only: scalar loads)
+                // (record mode: the pixel's first DFE_REC_NLEAD cells from its tile row's record)
                 float4 q4;
                 if (rec) {
                     if (4 * g4 < DFE_REC_NLEAD) {          // the record's copy of the pixel's first cells (32 B, whole-line reads across the tile row)
                         const int ncols = (o.Wo + 7) >> 3;
                         const int g = min(x >> 3, ncols - 1), xb = g == ncols - 1 ? o.Wo - 8 : g << 3;
                         const float *lv = rec + ((long long)g * rec_rows + y) * DFE_REC + DFE_REC_LEAD + (x - xb) * DFE_REC_NLEAD + 4 * g4;
-                        q4 = make_float4(__builtin_nontemporal_load(lv), __builtin_nontemporal_load(lv + 1), __builtin_nontemporal_load(lv + 2), __builtin_nontemporal_load(lv + 3));
-                    } else if (DFE_REC_NLEAD == 0) {
-                        const float *lv = vol + p * N + 4 * g4;
                         q4 = make_float4(__builtin_nontemporal_load(lv), __builtin_nontemporal_load(lv + 1), __builtin_nontemporal_load(lv + 2), __builtin_nontemporal_load(lv + 3));
                     } else {
                         q4 = make_float4(0.f, 0.f, 0.f, 0.f);   // (not looked at: nlead below)
@@ -301,9 +297,9 @@ __global__ __launch_bounds__(256) void flow_finalize_kernel(const float2 *__rest
                 else q4 = reinterpret_cast<const float4 *>(lead + pg * DFE_LEAD)[g4];
                 qq[4 * g4] = q4.x; qq[4 * g4 + 1] = q4.y; qq[4 * g4 + 2] = q4.z; qq[4 * g4 + 3] = q4.w;
             }
-            // (record mode with lead cells in the record: only the first DFE_REC_NLEAD are at hand; the walk through the volume below
-            //  takes over behind them -- the same cells in the same order)
-            const int nlead = (rec && DFE_REC_NLEAD > 0) ? DFE_REC_NLEAD : DFE_LEAD;
+            // (record mode: only the first DFE_REC_NLEAD are at hand; the walk through the volume below takes over behind them -- the
+            //  same cells in the same order)
+            const int nlead = rec ? DFE_REC_NLEAD : DFE_LEAD;
 #pragma unroll
             for (int kk = 0; kk < DFE_LEAD; ++kk) qq[kk] = kk < N ? qq[kk] : 0.f;
 #pragma unroll

@@ -211,22 +211,7 @@ __host__ __device__ inline int sweep_cut(int b, int B, int ncols, int Ho, int ov
 
 extern __shared__ __attribute__((aligned(16))) char dfe_smem[];
 
-#ifndef DFE_RI_SMEM
-#define DFE_RI_SMEM true   // row-image kernel: frame-0 values through warmed scalar loads (true) or LDS + DPP (false)
-#endif
-#ifndef DFE_A32
-#define DFE_A32 1
-#endif
-#ifndef DFE_NQW
-// waves that share the 17th chunk of a 33 x 33 window.  Measured at VGA: 8 waves x 1 column (shorter critical path, but 7
-// squared differences per output instead of 4) 0.3124 / 0.2529 ms fused / unfused against 0.3079 / 0.2407 ms for 4 x 2;
-// 2 waves x 4 columns spill (24 registers of ring state).
-#define DFE_NQW 4
-#endif
 #define DFE_CV_KERNEL_REV "cv-r6.0"
-#ifndef DFE_SMEM_JIT
-#define DFE_SMEM_JIT 0   // tuning: frame-0 scalars of a row loaded at its start instead of one row ahead
-#endif
 // -DDFE_MARKERS=1 (tools/isa_regions.py, no product build): assembler comments at the phase boundaries of the row loop, so that the ISA
 // between them can be counted by class (VALU / v_readlane / LDS / ...) per phase
 #if defined(DFE_MARKERS) && DFE_MARKERS
@@ -234,48 +219,11 @@ extern __shared__ __attribute__((aligned(16))) char dfe_smem[];
 #else
 #define DFE_MARK(name) do { } while (0)
 #endif
-#ifndef DFE_LEAD_FROM_IMAGE
-#define DFE_LEAD_FROM_IMAGE 1
-#endif
-#ifndef DFE_Q_UNDEF
-#define DFE_Q_UNDEF 1
-#endif
-#ifndef DFE_ROLES_STATIC
-#define DFE_ROLES_STATIC 1
-#endif
-#ifndef DFE_ROLES
-#define DFE_ROLES 1
-#endif
-#ifndef DFE_REFILL_AHEAD
-#define DFE_REFILL_AHEAD 2   // column sweep: row steps between the request of a ring row and its deposit in LDS (1, 2 or 3)
-#endif
-#ifndef DFE_LW_PRIO
-#define DFE_LW_PRIO 0        // column sweep: issue priority of the wave that refills the rings
-#endif
-#ifndef DFE_SCAN_AFTER_COPY
-#define DFE_SCAN_AFTER_COPY 0   // tuning: the fused arg-min scan behind the copy-out instead of in front of it
-#endif
-#ifndef DFE_SCAN_SIDX
-#define DFE_SCAN_SIDX 0   // fused scan: the winning lane's first cell found on the scalar unit (1) or by per-lane select chains + v_readlane (0).
-                          // Measured in one call (r04_c): 1 is 0.5 % SLOWER at VGA and 0.3 % at 1080p -- 8 fewer vector instructions, but a serial
-                          // chain of 8 compare -> scalar test pairs on the scan waves' path to the barrier
-#endif
-#ifndef DFE_COPY_FAST
-#define DFE_COPY_FAST 1   // copy-out of whole runs: unclamped pieces addressed by one lane offset + scalar bases (0: every piece clamped and compared)
-#endif
-#ifndef DFE_CW0
-#define DFE_CW0 5    // row-image kernel: first wave that takes part in the copy-out (0 = all waves)
-#endif
-#ifndef DFE_REC_ST_FLAGS
-#define DFE_REC_ST_FLAGS ""   // cache-policy bits of the per-pixel record stores (tuning)
-#endif
-#ifndef DFE_ST_FLAGS
 // cache-policy bits of the copy-out stores.  The volume streams out and nothing re-reads it from L2: with the non-temporal
 // hint the build measures 268 instead of 285 us at VGA and the step's finalize pass finds its planes still cached
 // (step -4 %); " sc1", " sc0 sc1" and combinations with " nt" measure the same as " nt" alone.  (Whole lines only: on the
 // tiled kernel's 256-B per-wave dword stores the same hint costs 44 % -- 554 against 385 us.)
 #define DFE_ST_FLAGS " nt"
-#endif
 
 
 // global_store_dword with a wave-uniform 64-bit base in SGPRs and a 32-bit per-lane byte offset:
@@ -889,7 +837,10 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
     constexpr int R0 = 8;                        // column sweep: rows of the frame-0 ring
     constexpr int LW = NW - 1;                   // column sweep: the wave that streams the tiles and never stores
     constexpr int NE = TX + K - 1;
-    constexpr int NQW = DFE_NQW;                 // waves that carry a share of the 17th chunk (tuning: 4 or 8)
+    // waves that carry a share of the 17th chunk.  Measured at VGA: 8 waves x 1 column (shorter critical path, but 7 squared
+    // differences per output instead of 4) 0.3124 / 0.2529 ms fused / unfused against 0.3079 / 0.2407 ms for 4 x 2; 2 waves x 4
+    // columns spill (24 registers of ring state).
+    constexpr int NQW = 4;
     constexpr int TQ = TX / NQW;                 // columns of such a share ("quarter task")
     // Fused column sweep: the waves split the work behind the barrier -- waves 0..7 scan one pixel's run each for its minimum,
     // waves 8..14 copy the image out (wave 15 refills the rings) -- instead of every wave doing a half-pixel scan AND three
@@ -898,7 +849,7 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
     // path, 2.7 of 5.1 kilocycles of a VGA row spent before the slowest waves began their main task (s_memtime stamps of two blocks, round 2).
     // (3-channel frames only: with one channel the main task is half as long and the all-waves scan of the plain layout
     //  wins, VGA luminance 215 against 254 us)
-    constexpr bool ROLES = FUSE && (SWEEP || DFE_ROLES_STATIC) && DFE_ROLES && TX == 8 && DC == 1089 && C == 3;
+    constexpr bool ROLES = FUSE && TX == 8 && DC == 1089 && C == 3;
     // the last wave neither scans nor copies: in the column sweep it refills the rings, with roles it carries the mini task
     static_assert(!NOVOL || ROLES, "the volume-free sweep is the role-split one");
     constexpr bool HAS_XW = SWEEP || ROLES;
@@ -1006,7 +957,7 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
     const int RUN = TX * D;                       // floats in the block's run
     const int l16 = lane & 15;
     float av[C][NE];
-    if constexpr (SM && !DFE_SMEM_JIT) {
+    if constexpr (SM) {
 #pragma unroll
         for (int c = 0; c < C; ++c) uload<NE>((cfptr)(I0 + a_base + c * HW), av[c]);
     }
@@ -1076,13 +1027,15 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
     //  de-phase LDS reads and reductions across the lock-stepped waves -- 13 % slower.)
     if (has_q) __builtin_amdgcn_s_setprio(3);
     else if (has_m) __builtin_amdgcn_s_setprio(2);
-    else if (SWEEP && DFE_LW_PRIO && wave == LW) __builtin_amdgcn_s_setprio(DFE_LW_PRIO);
     float ring[U][TX], ringq[U][TQ];
     // the mini task's box-filter state lives in LDS ([U][64] floats behind the frame-0 tile; only wave 4 touches it)
     float *rm = reinterpret_cast<float *>(dfe_smem + g_tile0_off + t0rows * kT0W * sizeof(px_t)) + lane;
-    float hold[DFE_REFILL_AHEAD][C];              // column sweep, wave LW: the tile pixels requested DFE_REFILL_AHEAD row steps ago
+    // column sweep: row steps between the request of a ring row and its deposit in LDS (one step -- 1.3 us -- is about a memory
+    // round trip behind this kernel's own store stream, and the wait is on every wave's path to the next barrier)
+    constexpr int RA = 2;
+    float hold[RA][C];                            // column sweep, wave LW: the tile pixels requested RA row steps ago
 #pragma unroll
-    for (int i = 0; i < DFE_REFILL_AHEAD; ++i)
+    for (int i = 0; i < RA; ++i)
 #pragma unroll
         for (int c = 0; c < C; ++c) hold[i][c] = 0.f;
 #pragma unroll
@@ -1186,24 +1139,6 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
         // any of its lanes attains it
         const unsigned long long m0 = __builtin_amdgcn_ballot_w64(b0 == vmin);
         int idx;
-#if DFE_SCAN_SIDX
-        // The first cell of the first lane that attains the minimum.  Only that lane's answer is wanted, so the search is scalar: one
-        // compare per cell into a lane mask, bit f of it tested on the scalar unit -- 8 vector instructions instead of 8 compares + 8
-        // selects + a v_readlane (round 4: the scan waves are as close to the row's critical path as the copy waves).
-        if (m0) {
-            const int f = __builtin_ctzll(m0);
-            int i0 = CPL - 1;
-#pragma unroll
-            for (int i = CPL - 2; i >= 0; --i) i0 = ((__builtin_amdgcn_ballot_w64(c0[i] == vmin) >> f) & 1) ? i : i0;
-            idx = f * CPL + i0;
-        } else {
-            const int f = __builtin_ctzll(__builtin_amdgcn_ballot_w64(b1 == vmin));
-            int i1 = CPL - 1;
-#pragma unroll
-            for (int i = CPL - 2; i >= 0; --i) i1 = ((__builtin_amdgcn_ballot_w64(c1[i] == vmin) >> f) & 1) ? i : i1;
-            idx = (64 + f) * CPL + i1;
-        }
-#else
         if (m0) {
             int i0 = CPL - 1;
 #pragma unroll
@@ -1217,7 +1152,6 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
             const int f = __builtin_ctzll(__builtin_amdgcn_ballot_w64(b1 == vmin));
             idx = (64 + f) * CPL + __builtin_amdgcn_readlane(i1, f);
         }
-#endif
         // The pixel's minimum, first index and centre cost go into the tile row's RECORD in LDS (8 x (min, idx) | 8 x centre | 0 ...);
         // behind the NEXT barrier one wave writes the 128-B record out whole (write_record below).  Until round 3 every scan wave
         // stored its pixel's entries into three planes itself: two 8-B entries, 64 B of lead cells, 4 B of centre per pixel and row
@@ -1243,13 +1177,12 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
                 rb[2 * xx + 1] = __int_as_float(idx);
                 rb[DFE_REC_CENTRE + xx] = cen;
                 if constexpr (NOVOL) rb[DFE_REC_FLAG + xx] = fbk ? 1.f : 0.f;
-                if constexpr (DFE_REC_NLEAD >= 4) {      // lane 0 holds the run's cells 0..8 already: the first 4 / 8 ride along (16-B LDS writes)
-                    static_assert(DFE_REC_NLEAD == 4 || DFE_REC_NLEAD == 8, "one or two 16-B pieces");
-                    typedef int i4_t __attribute__((ext_vector_type(4)));
-                    i4_t *lp4 = reinterpret_cast<i4_t *>(rb + DFE_REC_LEAD + DFE_REC_NLEAD * xx);
-                    lp4[0] = i4_t{c0[0], c0[1], c0[2], c0[3]};
-                    if constexpr (DFE_REC_NLEAD == 8) lp4[1] = i4_t{c0[4], c0[5], c0[6], c0[7]};
-                }
+                // lane 0 holds the run's cells 0..8 already: the first 8 ride along (two 16-B LDS writes)
+                static_assert(DFE_REC_NLEAD == 8, "two 16-B pieces");
+                typedef int i4_t __attribute__((ext_vector_type(4)));
+                i4_t *lp4 = reinterpret_cast<i4_t *>(rb + DFE_REC_LEAD + DFE_REC_NLEAD * xx);
+                lp4[0] = i4_t{c0[0], c0[1], c0[2], c0[3]};
+                lp4[1] = i4_t{c0[4], c0[5], c0[6], c0[7]};
             }
         }
         if constexpr (NOVOL)
@@ -1264,7 +1197,7 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
         asm volatile("" : "+v"(lw));
         if (lw < DFE_REC / 4) {
             const f4_t v = *reinterpret_cast<const f4_t *>(recbuf + rpar * DFE_REC + 4 * lw);
-            asm volatile("global_store_dwordx4 %0, %1, %2" DFE_REC_ST_FLAGS ::"v"((unsigned)lw * 16u), "v"(v), "s"(rb) : "memory");
+            asm volatile("global_store_dwordx4 %0, %1, %2" ::"v"((unsigned)lw * 16u), "v"(v), "s"(rb) : "memory");
         }
     };
     if constexpr (ROLES) {   // the record's tail (8 zeros per buffer) is written once per piece; the scans fill the rest
@@ -1301,23 +1234,17 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
             if constexpr (FUSE) pg_next += p.Wo;
             const int a0 = (int)(((unsigned)G0b / (unsigned)ES) & (unsigned)LM);
             float *st = stage + (r & 1) * g_stage_len + a0;                  // image of the run, congruent mod 32
-            [[maybe_unused]] const int rn = min(r + 1, nsweep - 1);   // next frame-0 row of the non-A32 form (clamped: the row after the last is never used)
             const int t0r = (SWEEP ? (r & (R0 - 1)) : r) * kT0W;
             auto do_main = [&]() {
                 {
                     px_t a{};
                     if constexpr (!SM) a = t0[t0r + l16];
                     float v[TX];
-                    if constexpr (SM && DFE_SMEM_JIT) {   // this row's scalars, just in time: they land while the first LDS batch is in flight
-#pragma unroll
-                        for (int c = 0; c < C; ++c) uload<NE>((cfptr)(I0 + a_base + (long long)r * p.W + c * HW), av[c]);
-                    }
                     rowimg_task_row<C, K, TX, m, SM>(row_ptr(lp, r), a, av, ring, v);
                     if constexpr (SWEEP) ring_step(lp);
-                    if constexpr (SM && !DFE_SMEM_JIT) {   // next row's scalars (requested behind the last squared difference instead --
-                                                           // inside the task row, in front of the sums -- the 42 scalars are live across the
-                                                           // sums as well and the 3-channel sweeps spill: 62 / 99 scalars, 104 / 124 B of scratch)
-#if DFE_A32
+                    if constexpr (SM) {   // next row's scalars (requested behind the last squared difference instead -- inside the
+                                          // task row, in front of the sums -- the 42 scalars are live across the sums as well and
+                                          // the 3-channel sweeps spill: 62 / 99 scalars, 104 / 124 B of scratch)
                         // (32-bit unsigned row / plane offsets next to ONE 64-bit base: the scalar loads take them as soffset, and the
                         //  sweep keeps 3 scalars fewer than with a running 64-bit pointer and two 64-bit plane offsets)
                         const char *ab = reinterpret_cast<const char *>(I0 + a_base);
@@ -1325,17 +1252,13 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
                         a_roff += (unsigned)p.W * 4u;
 #pragma unroll
                         for (int c = 0; c < C; ++c) uload<NE>((cfptr)(ab + (unsigned long long)(roff + (unsigned)c * hwb)), av[c]);
-#else
-#pragma unroll
-                        for (int c = 0; c < C; ++c) uload<NE>((cfptr)(I0 + a_base + (long long)rn * p.W + c * HW), av[c]);
-#endif
                     }
                     // deposit at once (image (r&1) was last read for row r-2, before the barrier of row r-1)
                     if (store_row && valid) {
 #pragma unroll
                         for (int x = 0; x < TX; ++x) st[x * D + d] = v[x];
                     }
-                    if constexpr (FUSE && !(ROLES && DFE_LEAD_FROM_IMAGE)) {   // centre cell and lead cells leave from registers; the minimum comes from the image
+                    if constexpr (FUSE && !ROLES) {   // centre cell and lead cells leave from registers; the minimum comes from the image
                         if (store_row) {
                             int lf = lane;
                             asm volatile("" : "+v"(lf));
@@ -1359,7 +1282,7 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
 #pragma unroll
                         for (int x = 0; x < TQ; ++x) st[(TQ * (wave - QW0) + x) * D + dqf] = v[x];
                     }
-                } else if constexpr (K == 7 && DFE_Q_UNDEF) {
+                } else if constexpr (K == 7) {
                     // the other waves never read their quarter state: "redefine" the two slots the task would have written, so that the join
                     // of the two paths needs no register copies on this side (4 v_mov per row on 12 waves otherwise)
 #pragma unroll
@@ -1442,10 +1365,7 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
                         int lw = lane;
                         asm volatile("" : "+v"(lw));
                         const bool t1lane = lw < g_lcols, t0lane = !t1lane && lw - g_lcols <= NE;
-                        // (the requests are DFE_REFILL_AHEAD = 2 row steps old when they are waited for: one step -- 1.3 us -- is
-                        //  about a memory round trip behind this kernel's own store stream, and the wait is on every wave's path
-                        //  to the next barrier)
-                        constexpr int RA = DFE_REFILL_AHEAD, hs = m % RA;
+                        constexpr int hs = m % RA;   // (the requests are RA row steps old when they are waited for)
                         static_assert(VUnroll<K>::value % RA == 0, "hold slot = row step mod RA must be a compile-time value");
                         if (r >= RA) {
                             px_t px;
@@ -1471,11 +1391,11 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
                     //  would put the whole store stream's latency into that wait: 1080p 2.32 against 1.8 ms)
                     if (wave == TX && r - 1 >= K - 1 && y - 1 >= y0n) write_record((r - 1) & 1, rec_prev);
                     if (store_row && wave < TX) scan_row_whole(st, r & 1, y);
-                } else if constexpr (FUSE && !DFE_SCAN_AFTER_COPY) {
+                } else if constexpr (FUSE) {
                     if (store_row) scan_row(st, pg_run);
                 }
                 DFE_MARK("copy");
-                // Copy-out by the waves WITHOUT an extra task (DFE_CW0.., 10 or 11 of them): a CU's vector-memory path takes 64 B
+                // Copy-out by the waves WITHOUT an extra task (5.., 10 or 11 of them): a CU's vector-memory path takes 64 B
                 // per clock, i.e. ~545 cycles for the 34 848 B of a row, and every wave that stores waits its turn in it.  With all
                 // waves copying, the four quarter-task waves -- the critical path of the sweep -- started the next row up to 0.2 us
                 // late (per-CU row step 1.48 us against 1.27 us of compute, measured with the memory unsaturated); the copier waves
@@ -1484,7 +1404,7 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
                 //  copiers then only take longer: 298 against 290 us.  Fused 3-channel sweep: ROLES above -- the copy waves are 8..14;
                 //  6 / 5 / 4 of them measured 269 / 277 / 297 against 258 us, scan waves taking one or two pieces each 289 / 294 us,
                 //  only the four scan waves without a quarter task taking them 270 us.)
-                constexpr int CW0 = ROLES ? TX : FUSE ? 0 : DFE_CW0;          // first copier wave
+                constexpr int CW0 = ROLES ? TX : FUSE ? 0 : 5;                // first copier wave
                 constexpr int NCW = (HAS_XW ? LW : NW) - CW0;                // copier waves
                 if (!NOVOL && store_row && wave >= CW0 && (!HAS_XW || wave != LW)) {
                     const int ov = nover * D;                                // floats of the run that are the neighbour's (shifted last tile)
@@ -1537,7 +1457,7 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
                     // no execution mask, and their addresses are ONE per-lane offset (16 tj) next to per-piece LDS immediates and per-piece scalar
                     // bases (SALU) -- 2 vector instructions per thread and row instead of 5 per piece (round 4: the copy waves' address
                     // arithmetic was 30 of their 55 VALU per row, tools/isa_regions.py).
-                    constexpr int NFULL = (DFE_COPY_FAST && CG && !F16) ? ((2168 / STR < NPC - 1) ? 2168 / STR : NPC - 1) : 0;
+                    constexpr int NFULL = (CG && !F16) ? ((2168 / STR < NPC - 1) ? 2168 / STR : NPC - 1) : 0;
                     if (NFULL > 0 && nover == 0) {   // block-uniform
                         const unsigned vo = (unsigned)tj * 16u;
                         const char *sbb = reinterpret_cast<const char *>(sb) + vo;
@@ -1581,9 +1501,6 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
                         }
                     }
                 }
-                if constexpr (FUSE && DFE_SCAN_AFTER_COPY) {
-                    if (store_row) scan_row(st, pg_run);
-                }
             }
             DFE_MARK("rowend");
             if constexpr (ROLES) rec_prev += DFE_REC;
@@ -1607,6 +1524,7 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
     //  behind the drain of the block's stores (two dependent passes over ~1100 pixels a block), which is what the launch and its boundary
     //  cost: a step is kernel + ~6 us of launch boundary whether that holds one kernel or two.  Taken out again.)
 }
+// SM: the main task's frame-0 values through warmed scalar loads (true, every launch) or LDS + DPP (false)
 template <int C, int K, int TX, bool SM, bool FUSE, bool SWEEP, int DC = 0, bool F16 = false>
 __global__ __launch_bounds__(1024) void ssd_cv_rowimg_kernel(const float *__restrict__ I0, const float *__restrict__ I1,
                                                              float *__restrict__ out, CvTiledArgs p, CvFuseArgs fa) {
@@ -1618,7 +1536,7 @@ template <int C, int K, int TX>
 __global__ __launch_bounds__(1024) void ssd_cv_rowimg_flow_kernel(const float *__restrict__ I0, const float *__restrict__ I1, CvTiledArgs p,
                                                                   CvFuseArgs fa, CvNovolArgs nv) {
     static_assert(C == 3 && K == 7 && TX == 8, "the role-split sweep's instantiation");
-    rowimg_body<C, K, TX, DFE_RI_SMEM, true, true, 1089, false, true>(I0, I1, nullptr, p, fa, nv);
+    rowimg_body<C, K, TX, true, true, true, 1089, false, true>(I0, I1, nullptr, p, fa, nv);
 }
 
 // LDS bytes of a static-tile block of `ty` output rows (0 = does not apply) and the kernel arguments that go with it
@@ -1666,8 +1584,8 @@ static int launch_cv_rowimg_one(dfe_ctx *ctx, const float *I0, const float *I1, 
     if (hWin == 33 && wWin == 33 && (a.pitch != RowimgGeom<C, K, TX>::pitch33 ||
                                      a.stage_len != (F16 ? RowimgGeom<C, K, TX>::stage_len33h : RowimgGeom<C, K, TX>::stage_len33)))
         return dfe_fail(ctx, DFE_E_UNSUPPORTED, "row-image kernel: LDS geometry differs from the kernel's constants");
-    auto kern = (hWin == 33 && wWin == 33) ? ssd_cv_rowimg_kernel<C, K, TX, DFE_RI_SMEM, FUSE, false, 1089, F16>
-                                      : ssd_cv_rowimg_kernel<C, K, TX, DFE_RI_SMEM, FUSE, false, 0, F16>;
+    auto kern = (hWin == 33 && wWin == 33) ? ssd_cv_rowimg_kernel<C, K, TX, true, FUSE, false, 1089, F16>
+                                      : ssd_cv_rowimg_kernel<C, K, TX, true, FUSE, false, 0, F16>;
     DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     dim3 grid(dfe_cdiv(a.Wo, TX), dfe_cdiv(a.Ho, ty));
     {
@@ -1765,8 +1683,8 @@ static int launch_cv_rowimg_sweep(dfe_ctx *ctx, const float *I0, const float *I1
         }
     }
     if (nv) return DFE_OK;
-    auto kern = sq33 ? ssd_cv_rowimg_kernel<C, K, TX, DFE_RI_SMEM, FUSE, true, 1089>
-                            : ssd_cv_rowimg_kernel<C, K, TX, DFE_RI_SMEM, false, true>;
+    auto kern = sq33 ? ssd_cv_rowimg_kernel<C, K, TX, true, FUSE, true, 1089>
+                            : ssd_cv_rowimg_kernel<C, K, TX, true, false, true>;
     DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     {
         DfeProfScope prof(ctx, true);
@@ -1849,7 +1767,7 @@ static int launch_cv_rowimg_f16(dfe_ctx *ctx, const float *I0, const float *I1, 
 }
 
 // the row-image kernel's role-split instantiations (3 channels, 33 x 33, fused) leave per-pixel RECORDS (fa.rec) instead of the planes
-static bool rowimg_writes_records(int C, int hWin, int wWin) { return DFE_ROLES && DFE_ROLES_STATIC && DFE_LEAD_FROM_IMAGE && C == 3 && hWin == 33 && wWin == 33; }
+static bool rowimg_writes_records(int C, int hWin, int wWin) { return C == 3 && hWin == 33 && wWin == 33; }
 
 // fp16 build of raw frames (C in {1, 3}, k = 7, 769..1096 window cells); *handled = false: no fast kernel for the shape
 int cv_frames_dispatch_f16(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, long long plane, int k, int hWin, int wWin,
