@@ -4,6 +4,7 @@
 //   dfe_rgb2y_f32                      [3][H][W] -> [1][H][W], 0.299 R + 0.587 G + 0.114 B accumulated in that order, each product and
 //                                      sum rounded separately (image.rgb2y's THTensor cadd chain; `image` is un-vendored: parity unpinned)
 //   dfe_flow_depth_pair_u8             dfe_flow_depth_pair_f32 on uint8 frames
+//   dfe_flow_depth_pair_subpixel_u8    dfe_flow_depth_pair_subpixel_f32 on uint8 frames
 //   dfe_multiscale_flow_pair_u8        dfe_multiscale_flow_pair_f32 / _f16 on uint8 frames
 // The uint8 entries convert into a per-ctx frame buffer (one pass: 0.9 MB read, 3.7 MB written per VGA frame, ~2 us) and run the fp32
 // pipeline on it -- bit-identical to the fp32 entry called on float(frame) * scale.  The conversion is NOT folded into the cost-volume
@@ -177,6 +178,18 @@ int dfe_flow_depth_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, i
     int rc = ingest_pair(ctx, I0, I1, (long long)C * H * W, scale, &f0, &f1);
     if (rc) return rc;
     return dfe_flow_depth_pair_f32(ctx, f0, f1, C, H, W, k, hWin, wWin, foe_x, foe_y, extract_threshold, flow, scores, depth, depth_conf);
+}
+
+int dfe_flow_depth_pair_subpixel_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x,
+                                    float foe_y, double extract_threshold, float scale, float *flow, float *scores, float *depth, float *depth_conf) {
+    DFE_ENTER(ctx);
+    DFE_REQUIRE(ctx, I0 && I1, DFE_E_ARG, "dfe_flow_depth_pair_subpixel_u8: NULL frame");
+    DFE_REQUIRE(ctx, C > 0 && H > 0 && W > 0 && scale > 0, DFE_E_ARG, "dfe_flow_depth_pair_subpixel_u8: C=%d %dx%d scale=%g", C, H, W, (double)scale);
+    float *f0 = nullptr, *f1 = nullptr;
+    int rc = ingest_pair(ctx, I0, I1, (long long)C * H * W, scale, &f0, &f1);
+    if (rc) return rc;
+    // (the refinement reads the converted frames too: bit-identical to the fp32 entry on float(frame) * scale)
+    return dfe_flow_depth_pair_subpixel_f32(ctx, f0, f1, C, H, W, k, hWin, wWin, foe_x, foe_y, extract_threshold, flow, scores, depth, depth_conf);
 }
 
 // ---- pipelined ingest: host frames of pair i+1 travel while pair i computes -------------------------------------------------------

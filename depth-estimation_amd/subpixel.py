@@ -1,0 +1,64 @@
+"""The single-scale raw-patch step as one call, with its opt-in sub-pixel flow (not in the reference: include/dfe.h).
+
+    flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0)
+        dfe_flow_depth_pair_f32 / _u8, or their _subpixel_ forms: frames -> flow, extractOutput scores, depth, depth confidence
+    refineFlowSubpixel(img1, img2, idx, hKer, wKer, hWin, wWin)
+        dfe_flow_refine_subpixel_f32: the sub-pixel flow of an arg-min index map (dfe_ssd_flow_f32's 1-based idx)
+"""
+import torch
+
+from ._lib import lib
+from .context import get_ctx, ptr
+
+
+def _frames(img1, img2, name):
+    if not (img1.is_cuda and img2.is_cuda):
+        raise TypeError("%s: CUDA tensors expected" % name)
+    if img1.dtype != img2.dtype or img1.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("%s: two float32 or two uint8 frames expected, got %s and %s" % (name, img1.dtype, img2.dtype))
+    if img1.dim() != 3 or img1.shape != img2.shape:
+        raise ValueError("%s: two C x H x W frames of one shape expected, got %s and %s" % (name, tuple(img1.shape), tuple(img2.shape)))
+    return img1.contiguous(), img2.contiguous()
+
+
+def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0):
+    """One frame pair through the single-scale step: C x H x W frames (float32, or uint8 read as float(byte) * scale), a k x k patch,
+    an hWin x wWin search window, foe = (x, y) focus of expansion.  Returns dict(flow [2][H][W] (y, x), scores, depth, depth_conf [H][W]),
+    zero outside the centre-pasted output region.  subpixel=True: the flow is refined to sub-pixel precision and depth follows it;
+    scores are the same either way."""
+    a, b = _frames(img1, img2, "flowDepthPair")
+    C, H, W = a.shape
+    flow = torch.empty((2, H, W), dtype=torch.float32, device=a.device)
+    scores = torch.empty((H, W), dtype=torch.float32, device=a.device)
+    depth = torch.empty_like(scores)
+    conf = torch.empty_like(scores)
+    ctx = get_ctx(a)
+    fx, fy = float(foe[0]), float(foe[1])
+    l = lib()
+    if a.dtype == torch.uint8:
+        fn = l.dfe_flow_depth_pair_subpixel_u8 if subpixel else l.dfe_flow_depth_pair_u8
+        rc = fn(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, threshold, float(scale), ptr(flow), ptr(scores), ptr(depth), ptr(conf))
+    else:
+        fn = l.dfe_flow_depth_pair_subpixel_f32 if subpixel else l.dfe_flow_depth_pair_f32
+        rc = fn(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, threshold, ptr(flow), ptr(scores), ptr(depth), ptr(conf))
+    ctx.check(rc)
+    return {"flow": flow, "scores": scores, "depth": depth, "depth_conf": conf}
+
+
+def refineFlowSubpixel(img1, img2, idx, hKer, wKer, hWin, wWin):
+    """Sub-pixel flow of float32 C x H x W frames from the arg-min index map idx [Ho][Wo] (int64, 1-based, as dfe_ssd_flow_f32 and
+    compute_cartesian_groundtruth_cross_correlation give it).  Returns (fy, fx), float32 [Ho][Wo]; pixels whose idx is not a cell of the
+    window are NaN."""
+    a, b = _frames(img1, img2, "refineFlowSubpixel")
+    if a.dtype != torch.float32:
+        raise TypeError("refineFlowSubpixel: float32 frames expected")
+    C, H, W = a.shape
+    Ho, Wo = H - hKer + 1 - hWin + 1, W - wKer + 1 - wWin + 1
+    if idx.dtype != torch.int64 or tuple(idx.shape) != (Ho, Wo) or idx.device != a.device:
+        raise ValueError("refineFlowSubpixel: idx must be int64 [%d][%d] on %s, got %s %s" % (Ho, Wo, a.device, idx.dtype, tuple(idx.shape)))
+    idx = idx.contiguous()
+    fy = torch.full((Ho, Wo), float("nan"), dtype=torch.float32, device=a.device)
+    fx = torch.full_like(fy, float("nan"))
+    ctx = get_ctx(a)
+    ctx.check(lib().dfe_flow_refine_subpixel_f32(ctx.handle, ptr(a), ptr(b), C, H, W, hKer, wKer, hWin, wWin, ptr(idx), ptr(fy), ptr(fx), Wo, 0, 0))
+    return fy, fx

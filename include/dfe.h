@@ -492,6 +492,31 @@ int dfe_contrastive_normalization_f32(dfe_ctx *ctx, const float *in, int C, int 
 /* ---- frames as the camera delivers them: uint8 planes ("upload frames as uint8, not fp32") ---------------------- */
 /* dst[i] = float(src[i]) * scale (scale = 1: the integer values; 1/255: image.load's [0, 1] range). */
 int dfe_u8_to_f32(dfe_ctx *ctx, const uint8_t *src, int64_t n, float scale, float *dst);
+/* ---- sub-pixel flow for the single-scale step (NOT in the reference: its flow is the integer arg-min cell) -------------------- */
+/* For an output pixel (y, x) with arg-min cell (r, s) -- the cell the step picks, centre tie-break included; decoded flow
+ * dy = r - (hWin-1)/2, dx = s - (wWin-1)/2 -- cost(r', s') is the SSD of dfe_ssd_cost_volume_f32 for that pixel and cell (frame 0's
+ * patch at (y + (hWin-1)/2, x + (wWin-1)/2), frame 1's at (y + r', x + s')).  Per axis (x shown; y alike with r -+ 1), in fp32:
+ *   c0 = cost(r, s), cm = cost(r, s-1), cp = cost(r, s+1);
+ *   off = 0 if s-1 < 0 or s+1 >= wWin (a neighbour outside the searched window);
+ *   else den = (cm - c0) + (cp - c0); off = den > 0 ? clamp((cm - cp) / (2 den), -0.5, 0.5) : 0   (this order, IEEE division);
+ *   fx = (float)dx + off_x, fy = (float)dy + off_y.
+ * Costs are recomputed from the frames (C (kh kw + (kh+2)(kw+2)) reads per pixel); on byte-valued frames every cost is an integer
+ * below 2^24, so the refined flow is exact and reproducible on the host.
+ * dfe_flow_depth_pair_subpixel_f32 / _u8: the arguments and outputs of dfe_flow_depth_pair_f32 / _u8; the step runs unchanged, then
+ *   its centre-pasted flow is refined in place and depth / depth_conf (NULL together, as there) are the step's per-pixel formula
+ *   (dfe_flow_to_depth_cartesian, fix_dot = 0) on the refined flow.  The border stays zero; scores are the step's.
+ * dfe_flow_refine_subpixel_f32: the refinement alone, from the 1-based idx [Ho][Wo] of dfe_ssd_flow_f32 (Ho = H - kh + 1 - hWin + 1,
+ *   Wo = W - kw + 1 - wWin + 1); fy / fx written at [(y + pad_t) * pitch + x + pad_l] as dfe_flow_tail does.  Pixels whose idx is
+ *   outside 1..hWin*wWin keep their fy / fx. */
+int dfe_flow_depth_pair_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin,
+                                     float foe_x, float foe_y, double extract_threshold, float *flow, float *scores, float *depth,
+                                     float *depth_conf);
+int dfe_flow_depth_pair_subpixel_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin,
+                                    float foe_x, float foe_y, double extract_threshold, float scale, float *flow, float *scores,
+                                    float *depth, float *depth_conf);
+int dfe_flow_refine_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int kh, int kw, int hWin,
+                                 int wWin, const int64_t *idx, float *fy, float *fx, int pitch, int pad_t, int pad_l);
+
 /* replaces: image.rgb2y as prepareInput calls it (opticalflow_model.lua:136-138; un-vendored `image`, restated: parity unpinned).
  *   rgb [3][H][W] -> y [1][H][W] = 0.299 R + 0.587 G + 0.114 B, accumulated in that order with separately rounded products and sums. */
 int dfe_rgb2y_f32(dfe_ctx *ctx, const float *rgb, int H, int W, float *y);

@@ -1,0 +1,19 @@
+"""The sub-pixel refinement kernel (csrc/subpixel.hip) inside the register file: no scratch for any instantiation (the fixed-width forms
+keep three frame-0 rows and a frame-1 row in registers; a spill would put those reads back into memory), and at most 96 VGPRs, which
+keeps 5 waves per SIMD (94 / 74 / 55 for the 7 x 7, 5 x 5 and any-patch forms when this was written)."""
+import os
+import re
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_refine_kernel_stays_inside_the_register_file():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kres.py"), os.path.join(ROOT, "depth-estimation_amd", "csrc", "subpixel.hip"),
+                          "flow_refine_subpixel"], capture_output=True, text=True).stdout
+    rows = re.findall(r"flow_refine_subpixel_kernel<(\d+)>\s+VGPR (\d+) scratch (\d+) sgpr-spill (\d+)", out)
+    assert sorted(int(r[0]) for r in rows) == [0, 5, 7], out
+    for kw, vgpr, scratch, spill in rows:
+        assert int(scratch) == 0 and int(spill) == 0 and int(vgpr) <= 96, "flow_refine_subpixel_kernel<%s>: %s VGPRs, %s B scratch, %s SGPR spills" % (
+            kw, vgpr, scratch, spill)
