@@ -115,6 +115,22 @@ class OutputExtractor(Module):
         self.output = [x, y]
         return self.output
 
+    def updateGradInput(self, input, gradOutput):
+        """OutputExtractor.lua:37-42: gradInput = gradOutput[1] * xmul + gradOutput[2] * ymul, xmul[k] / ymul[k] the 1-based
+        column / row of window cell k.  The reference squeezes each gradOutput to the scalar of the trainer's 1 x 1 output;
+        here every pixel takes its own pair (gradOutput[1], gradOutput[2] of the output's H x W shape), which is the same thing
+        at 1 x 1.  Same roundings as the reference: zero + gx * xmul, then + gy * ymul."""
+        gx, gy = gradOutput
+        shape = input.shape[:-1]
+        if gx.numel() != shape.numel() or gy.numel() != shape.numel():
+            raise ValueError("OutputExtractor: gradOutput must be two tensors of %s elements" % shape.numel())
+        k = torch.arange(self.maxh * self.maxw, device=input.device)
+        xmul, ymul = (k % self.maxw + 1).to(torch.float32), (k // self.maxw + 1).to(torch.float32)
+        gx = gx.to(device=input.device, dtype=torch.float32).reshape(*shape, 1)
+        gy = gy.to(device=input.device, dtype=torch.float32).reshape(*shape, 1)
+        self.gradInput = gx * xmul + gy * ymul
+        return self.gradInput
+
 
 def postProcessImage(input, mask, winsize, method):
     """opticalflow_model.lua:323-472: method 'max' = masked mode filter of the rounded flow, anything else = masked
