@@ -20,6 +20,8 @@ no CPU fallback -- a missing library or device raises.
     version2.getNetwork, getTrainerNetwork, decodeFlow, flowPair   (version2/network.lua, version2/test.lua)
     flowDepthPair, refineFlowSubpixel                   (not in the reference: the single-scale step in one call, and its
                                                         opt-in sub-pixel flow -- subpixel.py)
+    getModel(geometry).forwardFlow                      (a trained single-scale model per frame pair in one call,
+                                                        output_extraction_method 'max' or 'mean' -- network.py)
 """
 from ._lib import lib, DfeError, LIB_PATH  # noqa: F401
 from .context import Context, get_ctx  # noqa: F401

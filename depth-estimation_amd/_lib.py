@@ -54,6 +54,8 @@ PROTOTYPES = {
     "dfe_spatial_matching_argmin_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3),
     "dfe_flow_pair_filtered_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FilterLayer), C.c_int, C.c_int, C.c_int, C.c_int,
                                              C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dfe_flow_pair_filtered_mean_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FilterLayer), C.c_int, C.c_int,
+                                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dfe_spatial_matching_strided_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "dfe_spatial_convolution_tanh_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
     "dfe_ingest_submit_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int)]),

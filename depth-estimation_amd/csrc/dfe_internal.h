@@ -193,6 +193,11 @@ int dfe_scratch(dfe_ctx *ctx, size_t bytes, void **out, bool plain = false);
 // whether the one-kernel flat matcher (feat_matching_flat.hip) takes in1 as a view -- rows pitch1, planes plane1 floats apart: the arena
 // planners leave the volume out only where it does
 bool dfe_feat_matching_flat_view_takes(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw, int pitch1, long long plane1);
+// ... and its soft-max epilogue with processOutput's 'mean' branch (soft arg-max, row-marginal confidence) behind it: full / full_conf /
+// index as DfeSoftOut describes them, y and x as floats; *handled stays false where the shape is not the kernel's
+struct DfeSoftOut;
+int dfe_feat_matching_flat_mean(dfe_ctx *ctx, const float *in1, int pitch1, long long plane1, const float *in2, int K, int H1, int W1, int maxh, int maxw,
+                                const DfeSoftOut *soft, bool *handled);
 // one layer of a filter stack (filters.hip): in [nIn][H][W] -> out [nOut][H-kH+1][W-kW+1], nn.Tanh fused behind it when
 // L.tanh_after (the same tanhf as dfe_tanh_f32: bit-identical to the two separate calls)
 int dfe_filter_layer_forward(dfe_ctx *ctx, const float *in, const dfe_filter_layer &L, int H, int W, float *out);

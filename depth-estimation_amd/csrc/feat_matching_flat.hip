@@ -72,7 +72,7 @@ struct FfArgs {
     long long fullplane;               // hFull * wFull
     float *full, *full_conf, *scores;  // [2][hFull][wFull] (plane 0 = y), [hFull][wFull], [H1][W1]; each may be NULL (idx above: [H1][W1])
 };
-enum { FF_VOLUME = 0, FF_ARGMIN = 1, FF_SOFT = 2 };
+enum { FF_VOLUME = 0, FF_ARGMIN = 1, FF_SOFT = 2, FF_MEAN = 3 };
 constexpr float FF_TIE = 1e-6f;   // FF_SOFT without a threshold: cells this close to a window's minimum may share its maximal probability
 
 template <int MW> struct FfGeom {
@@ -124,10 +124,11 @@ template <int NT> __device__ __forceinline__ void ff_glds_row(unsigned voff0, un
 // maxh <= 16: waves 0 .. maxh-1 each sweep one window row.  EXTRA (maxh == 17): 16 waves, row 16 as the extra task.
 // ARGMIN: no volume -- the arithmetic's result goes through the first-minimum decode of version2/test.lua:45-51 (FfArgs::idx / xflow /
 // yflow) instead of the copy-out: the volume of a 17 x 17 window on VGA features is 316 MB that the one-call model never reads back.
-template <int MW, bool EXTRA, int MODE = FF_VOLUME>
-__global__ __launch_bounds__(1024) void feat_matching_flat_kernel(FfArgs p) {
+// MEAN (FF_MEAN, feat_matching_flat_mean_kernel): the soft-max epilogue's probabilities, then processOutput's 'mean' branch on them.
+template <int MW, bool EXTRA, int MODE>
+__device__ __forceinline__ void ff_body(FfArgs p) {
 #pragma clang fp contract(off)
-    constexpr bool ARGMIN = MODE == FF_ARGMIN, SOFT = MODE == FF_SOFT;
+    constexpr bool ARGMIN = MODE == FF_ARGMIN, MEAN = MODE == FF_MEAN, SOFT = MODE == FF_SOFT || MEAN;
     constexpr int PX = FF_PX;
     constexpr int PITCH = FfGeom<MW>::PITCH, NLOAD = FfGeom<MW>::NLOAD, NB4 = FfGeom<MW>::NB4;
     const int nd = EXTRA ? 16 : p.nd;                      // window rows of this block (a half tile: maxh / 2)
@@ -495,13 +496,13 @@ __global__ __launch_bounds__(1024) void feat_matching_flat_kernel(FfArgs p) {
                     const int xg = ll >= nA ? (ll - nA) * PX : xA0 + ll * PX;
                     const bool live = g0 + ll < p.NG && xg + q < p.W1;
                     long long id = 0;
-                    float score = 0.f, conf = 1.f;
+                    float score = 0.f, conf = 1.f, my = 0.f, mx = 0.f;
                     // Without a threshold only the arg-max of the probabilities leaves the kernel.  p = e * (1 / sum) with e = exp2((cmin - c) log2 e):
                     // the largest e is exactly 1 (the minimum's), and a cell more than FF_TIE above the minimum has e <= 1 - 2^-20, whose product
                     // with 1 / sum rounds strictly below 1 / sum.  So a window with ONE cell within FF_TIE of its minimum has that cell as its only
                     // maximal probability whatever the sum is -- no exponential, no sum, no division: 3 instead of 12 vector instructions per cell.
                     // Windows with several such cells (flat regions, exact ties) take the full arithmetic below, wave by wave: same results.
-                    bool full = p.use_thr != 0;
+                    bool full = MEAN || p.use_thr != 0;
                     int fi = 0x7fffffff;
                     if (!full) {
                         const float lim = FF_TIE - m;                     // (m = max(-c) = -cmin)
@@ -536,7 +537,46 @@ __global__ __launch_bounds__(1024) void feat_matching_flat_kernel(FfArgs p) {
                     const float inv = 1.0f / s;
 #pragma unroll
                     for (int n = 0; n < 4 * NJ4; ++n) v[n] = v[n] * inv;   // (cells beyond the window: 0 * inv = 0, below every probability's use)
-                    if (!p.use_thr) {
+                    if constexpr (MEAN) {
+                        // processOutput's 'mean' branch (opticalflow_model.lua:171-199, 218-226) on the probabilities.  The soft arg-max
+                        // x = sum p_k (k mod maxw + 1), y = sum p_k (k div maxw + 1) in OutputExtractor's order (output_extractor_kernel,
+                        // postfilters.hip: lane l of 64 runs cells l, l + 64, .. through fused multiply-adds, then an xor butterfly over
+                        // offsets 32 .. 1): lane t here holds cells 64 j + 4 t + i, i.e. that kernel's lanes 4 t + i, one running sum per i;
+                        // offsets 32, 16, 8, 4 are lanes t ^ 8, t ^ 4, t ^ 2, t ^ 1 (row16_sum_f32_ordered), offsets 2 and 1 pair up the i.
+                        float sx[4] = {0.f, 0.f, 0.f, 0.f}, sy[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                        for (int j = 0; j < NJ4; ++j)
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                const int k = 64 * j + 4 * t + i, r = k / MW;
+                                if (k < WN) {
+                                    sx[i] = __builtin_fmaf(v[4 * j + i], (float)(k - r * MW + 1), sx[i]);
+                                    sy[i] = __builtin_fmaf(v[4 * j + i], (float)(r + 1), sy[i]);
+                                }
+                            }
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) { sx[i] = row16_sum_f32_ordered(sx[i]); sy[i] = row16_sum_f32_ordered(sy[i]); }
+                        mx = (sx[0] + sx[2]) + (sx[1] + sx[3]);
+                        my = (sy[0] + sy[2]) + (sy[1] + sy[3]);
+                        // the confidence: extractOutput(m, scores, 0.11, imaxs) on the row marginals m_r = sum_c p[r maxw + c]
+                        // (marginal_sum_kernel: a double sum in column order, rounded to float), then scores > 0.  A score is written, and
+                        // positive, exactly where some m_r exceeds 0.11 as a double.  The probabilities go back into the window's image;
+                        // lane t sums row t (lane 0 also row 16).
+                        lds_f *pw = img + ll * WNP + 4 * t;
+#pragma unroll
+                        for (int j = 0; j < NJ4; ++j)
+                            if (64 * j + 4 * t < WN) *(lds_f4 *)(pw + 64 * j) = ff_f4{v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]};
+                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the group's lanes are this wave's: its LDS operations are in order)
+                        bool hit = false;
+                        for (int r = t; r < (EXTRA ? 17 : p.maxh); r += 16) {
+                            const lds_f *rw = img + ll * WNP + r * MW;
+                            double a = 0;
+#pragma unroll
+                            for (int c = 0; c < MW; ++c) a = a + (double)rw[c];
+                            hit = hit || (double)(float)a > 0.11;
+                        }
+                        conf = ((__ballot(hit) >> (16 * g)) & 0xffffull) ? 1.f : 0.f;
+                    } else if (!p.use_thr) {
                         // input:max(3), first maximum; where it equals the centre cell's probability the index is the centre's (:156-160)
                         float b = v[0];
                         int bi = 4 * t;
@@ -595,13 +635,23 @@ __global__ __launch_bounds__(1024) void feat_matching_flat_kernel(FfArgs p) {
                     if (live && t == 0) {
                         const int py = y_first + (ll >= nA ? 1 : 0), pxc = xg + q;
                         const long long px = (long long)py * p.W1 + pxc;
+                        const long long fo = (long long)(p.ho + py) * p.wFull + p.wo + pxc;
+                        if constexpr (MEAN) {
+                            // index = yx2x(floor(y + 0.5), floor(x + 0.5)) in fp32 (:221), then y, x minus centered2onebased(0, 0)
+                            const float fy = floorf(my + 0.5f), fx = floorf(mx + 0.5f);
+                            if (p.idx) p.idx[px] = (long long)((fy - 1.f) * (float)MW + fx);
+                            if (p.full) {
+                                p.full[fo] = my - (float)yoffc;
+                                p.full[p.fullplane + fo] = mx - (float)xoffc;
+                            }
+                        } else {
                         const int i0 = (int)id - 1, ty = i0 / MW;
                         if (p.idx) p.idx[px] = id;
                         if (p.scores) p.scores[px] = score;
-                        const long long fo = (long long)(p.ho + py) * p.wFull + p.wo + pxc;
                         if (p.full) {
                             p.full[fo] = (float)(ty + 1 - yoffc);
                             p.full[p.fullplane + fo] = (float)(i0 - ty * MW + 1 - xoffc);
+                        }
                         }
                         if (p.full_conf) p.full_conf[fo] = conf;
                     }
@@ -688,6 +738,16 @@ __global__ __launch_bounds__(1024) void feat_matching_flat_kernel(FfArgs p) {
     }
 }
 
+template <int MW, bool EXTRA, int MODE = FF_VOLUME>
+__global__ __launch_bounds__(1024) void feat_matching_flat_kernel(FfArgs p) {
+    ff_body<MW, EXTRA, MODE>(p);
+}
+// the soft-max epilogue with processOutput's 'mean' branch behind it (dfe_flow_pair_filtered_mean_f32)
+template <int MW, bool EXTRA>
+__global__ __launch_bounds__(1024) void feat_matching_flat_mean_kernel(FfArgs p) {
+    ff_body<MW, EXTRA, FF_MEAN>(p);
+}
+
 }  // namespace
 
 // the shapes this kernel takes (the pointers' alignment apart): 16- / 17-wide windows of 4 .. 17 rows on frames at least 64 groups wide
@@ -720,8 +780,8 @@ bool dfe_feat_matching_flat_view_takes(const dfe_ctx *ctx, int K, int H1, int W1
 
 // *handled stays false when the shape is not this kernel's (the caller goes on to the round-3 kernels)
 static int ff_launch(dfe_ctx *ctx, const float *in1, int pitch1, long long plane1, const float *in2, int K, int H1, int W1, int maxh, int maxw, float *out,
-                     long long *idx, float *xflow, float *yflow, const DfeSoftOut *soft, bool *handled) {
-    const int mode = soft ? FF_SOFT : out ? FF_VOLUME : FF_ARGMIN;
+                     long long *idx, float *xflow, float *yflow, const DfeSoftOut *soft, bool *handled, bool mean = false) {
+    const int mode = soft ? (mean ? FF_MEAN : FF_SOFT) : out ? FF_VOLUME : FF_ARGMIN;
     const bool argmin = mode == FF_ARGMIN;
     *handled = false;
     if (!ff_view_ok(ctx, K, H1, W1, maxh, maxw, pitch1, plane1)) return DFE_OK;
@@ -759,12 +819,14 @@ static int ff_launch(dfe_ctx *ctx, const float *in1, int pitch1, long long plane
     // the copy-out image [64][WNP]; the arg-min form keeps its candidates there instead -- cv[256][NC] and ci[256][NC], NC = 16 (20 with
     // the extra task) whatever the window's height: larger than the image of a window of fewer than 8 rows; the soft-max form reads its
     // windows in 16-B pieces up to cell 4 * 16 * ceil(WN / 64) of the last window and keeps extractOutput's candidates [64][16] behind
-    const size_t img_floats = mode == FF_SOFT ? (size_t)64 * WNP + 64 * 16 + 64
+    const size_t img_floats = mode >= FF_SOFT ? (size_t)64 * WNP + 64 * 16 + 64
                                               : std::max((size_t)64 * WNP, argmin ? (size_t)2 * 256 * (extra ? 20 : 16) : (size_t)0);
     const size_t lds = ((size_t)3 * (extra ? 18 : a.nd + 1) * PITCH + 3 * 64 * FF_PX + 64 + img_floats) * sizeof(float);
     if (lds * a.S > 160 * 1024) return DFE_OK;
     void (*kern)(FfArgs);
-    if (mode == FF_SOFT) kern = maxw == 17 ? (extra ? feat_matching_flat_kernel<17, true, FF_SOFT> : feat_matching_flat_kernel<17, false, FF_SOFT>)
+    if (mode == FF_MEAN) kern = maxw == 17 ? (extra ? feat_matching_flat_mean_kernel<17, true> : feat_matching_flat_mean_kernel<17, false>)
+                                           : feat_matching_flat_mean_kernel<16, false>;
+    else if (mode == FF_SOFT) kern = maxw == 17 ? (extra ? feat_matching_flat_kernel<17, true, FF_SOFT> : feat_matching_flat_kernel<17, false, FF_SOFT>)
                                            : feat_matching_flat_kernel<16, false, FF_SOFT>;
     else if (argmin) kern = maxw == 17 ? (extra ? feat_matching_flat_kernel<17, true, FF_ARGMIN> : feat_matching_flat_kernel<17, false, FF_ARGMIN>)
                                        : feat_matching_flat_kernel<16, false, FF_ARGMIN>;
@@ -776,7 +838,7 @@ static int ff_launch(dfe_ctx *ctx, const float *in1, int pitch1, long long plane
         hipLaunchKernelGGL(kern, dim3(nblk), dim3(64 * NW), lds, ctx->stream, a);
     }
     DFE_LAUNCH_CHECK(ctx);
-    ctx->last_kernel = mode == FF_SOFT ? "feat_matching_flat_kernel+softmax" : argmin ? "feat_matching_flat_kernel+argmin" : "feat_matching_flat_kernel";
+    ctx->last_kernel = mode == FF_MEAN ? "feat_matching_flat_mean_kernel" : mode == FF_SOFT ? "feat_matching_flat_kernel+softmax" : argmin ? "feat_matching_flat_kernel+argmin" : "feat_matching_flat_kernel";
     *handled = true;
     return DFE_OK;
 }
@@ -814,4 +876,13 @@ int dfe_feat_matching_flat_soft(dfe_ctx *ctx, const float *in1, int pitch1, long
     *handled = false;
     if (!soft) return DFE_OK;
     return ff_launch(ctx, in1, pitch1, plane1, in2, K, H1, W1, maxh, maxw, nullptr, nullptr, nullptr, nullptr, soft, handled);
+}
+
+// nn.SpatialMatching -> nn.Minus -> SoftMax over the window -> processOutput's 'mean' branch, without the volume (the FF_MEAN epilogue;
+// soft->use_threshold, threshold and scores are not read)
+int dfe_feat_matching_flat_mean(dfe_ctx *ctx, const float *in1, int pitch1, long long plane1, const float *in2, int K, int H1, int W1, int maxh, int maxw,
+                                const DfeSoftOut *soft, bool *handled) {
+    *handled = false;
+    if (!soft) return DFE_OK;
+    return ff_launch(ctx, in1, pitch1, plane1, in2, K, H1, W1, maxh, maxw, nullptr, nullptr, nullptr, nullptr, soft, handled, true);
 }

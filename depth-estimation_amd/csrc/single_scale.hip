@@ -11,6 +11,9 @@
 // the CU: the flat-tile matcher's soft-max epilogue (feat_matching_flat.hip, FF_SOFT) does the per-pixel tail on the costs it has just
 // summed.  Shapes that kernel does not take go through the stand-alone device ops in the same order (the same arithmetic: every soft-max
 // on the device is softmin_body's), so the results are the module path's bit for bit either way.
+// dfe_flow_pair_filtered_mean_f32 is the same step for a model built with output_extraction_method 'mean': processOutput's 'mean' branch
+// (:171-199, 218-226: soft arg-max y, x, confidence from extractOutput on the row marginals) behind the soft-max, in the matcher's FF_MEAN
+// epilogue or through the stand-alone ops.
 #include "dfe_internal.h"
 
 namespace {
@@ -45,6 +48,27 @@ __global__ __launch_bounds__(256) void ss_paste_kernel(const long long *__restri
     }
 }
 
+// processOutput's 'mean' branch (opticalflow_model.lua:218-250) behind the stand-alone OutputExtractor / marginal / extractOutput ops:
+// index = yx2x(floor(y + 0.5), floor(x + 0.5)) in fp32, y and x minus centered2onebased(0, 0), confidence = scores > 0, centre paste
+__global__ __launch_bounds__(256) void ss_paste_mean_kernel(const float *__restrict__ y, const float *__restrict__ x, const float *__restrict__ scores, int H1,
+                                                            int W1, int maxh, int maxw, int ho, int wo, int wFull, long long fullplane, float *__restrict__ full,
+                                                            float *__restrict__ full_conf, long long *__restrict__ idx) {
+#pragma clang fp contract(off)
+    const long long P = (long long)H1 * W1;
+    const float yoff = (float)((maxh + 1) / 2), xoff = (float)((maxw + 1) / 2);
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += (long long)gridDim.x * blockDim.x) {
+        const int py = (int)(p / W1), px = (int)(p - (long long)py * W1);
+        const float yv = y[p], xv = x[p];
+        if (idx) idx[p] = (long long)((floorf(yv + 0.5f) - 1.f) * (float)maxw + floorf(xv + 0.5f));
+        const long long fo = (long long)(ho + py) * wFull + wo + px;
+        if (full) {
+            full[fo] = yv - yoff;
+            full[fullplane + fo] = xv - xoff;
+        }
+        if (full_conf) full_conf[fo] = scores[p] > 0.f ? 1.f : 0.f;
+    }
+}
+
 // torch.Tensor(2, hImg, wImg):zero() / full_confidences:zero() (opticalflow_model.lua:236,243) where the paste does not write: the frame
 // around the pasted region (two hipMemsetAsync of the whole planes cost 10 us of a 200-us step)
 __global__ __launch_bounds__(256) void ss_border_kernel(float *__restrict__ full, float *__restrict__ full_conf, int hImg, int wImg, int ho, int wo, int H1, int W1) {
@@ -72,20 +96,21 @@ int ss_grid(long long n) {
 
 }  // namespace
 
-extern "C" int dfe_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, const dfe_filter_layer *layers, int nlayers,
-                                          int maxh, int maxw, int use_threshold, double threshold, int hImg, int wImg, float *full, float *full_conf,
-                                          int64_t *index, float *scores) {
-    DFE_ENTER(ctx);
-    DFE_REQUIRE(ctx, I0 && I1 && (nlayers == 0 || layers), DFE_E_ARG, "dfe_flow_pair_filtered_f32: NULL argument");
-    DFE_REQUIRE(ctx, full || full_conf || index || scores, DFE_E_ARG, "dfe_flow_pair_filtered_f32: no output requested");
+// dfe_flow_pair_filtered_f32 (mean = false) and dfe_flow_pair_filtered_mean_f32 (mean = true: processOutput's 'mean' branch, no threshold,
+// no scores); fn: the entry's name for the messages
+static int ss_flow_pair(dfe_ctx *ctx, const char *fn, bool mean, const float *I0, const float *I1, int C, int H, int W, const dfe_filter_layer *layers,
+                        int nlayers, int maxh, int maxw, int use_threshold, double threshold, int hImg, int wImg, float *full, float *full_conf,
+                        int64_t *index, float *scores) {
+    DFE_REQUIRE(ctx, I0 && I1 && (nlayers == 0 || layers), DFE_E_ARG, "%s: NULL argument", fn);
+    DFE_REQUIRE(ctx, full || full_conf || index || scores, DFE_E_ARG, "%s: no output requested", fn);
     DFE_REQUIRE(ctx, C > 0 && H > 0 && W > 0 && nlayers >= 0 && nlayers <= 8 && maxh > 0 && maxw > 0, DFE_E_ARG,
-                "dfe_flow_pair_filtered_f32: C=%d %dx%d, %d layers, window %dx%d", C, H, W, nlayers, maxh, maxw);
+                "%s: C=%d %dx%d, %d layers, window %dx%d", fn, C, H, W, nlayers, maxh, maxw);
     int hk = 1, wk = 1, K = C, maxplanes = C;
     for (int i = 0; i < nlayers; ++i) {
         DFE_REQUIRE(ctx, layers[i].weight && layers[i].kH > 0 && layers[i].kW > 0 && layers[i].nIn > 0 && layers[i].nOut > 0, DFE_E_ARG,
-                    "dfe_flow_pair_filtered_f32: layer %d is incomplete", i);
+                    "%s: layer %d is incomplete", fn, i);
         DFE_REQUIRE(ctx, (i == 0 ? layers[0].nIn == C : (layers[i].conn || layers[i].nIn == layers[i - 1].nOut)), DFE_E_SHAPE,
-                    "dfe_flow_pair_filtered_f32: layer %d reads %d planes, its input has %d", i, layers[i].nIn, i == 0 ? C : layers[i - 1].nOut);
+                    "%s: layer %d reads %d planes, its input has %d", fn, i, layers[i].nIn, i == 0 ? C : layers[i - 1].nOut);
         hk += layers[i].kH - 1;
         wk += layers[i].kW - 1;
         K = layers[i].nOut;
@@ -93,8 +118,8 @@ extern "C" int dfe_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const f
     }
     const int Hf = H - hk + 1, Wf = W - wk + 1;                     // the feature maps (in2 of the matcher)
     const int H1 = Hf - maxh + 1, W1 = Wf - maxw + 1;               // the model's output region = the narrowed in1
-    DFE_REQUIRE(ctx, H1 > 0 && W1 > 0, DFE_E_SHAPE, "dfe_flow_pair_filtered_f32: frame %dx%d too small for window %dx%d behind a %dx%d filter", H, W, maxh, maxw, hk, wk);
-    DFE_REQUIRE(ctx, !(full || full_conf) || (hImg >= H1 && wImg >= W1), DFE_E_SHAPE, "dfe_flow_pair_filtered_f32: full frame %dx%d smaller than the output %dx%d", hImg, wImg,
+    DFE_REQUIRE(ctx, H1 > 0 && W1 > 0, DFE_E_SHAPE, "%s: frame %dx%d too small for window %dx%d behind a %dx%d filter", fn, H, W, maxh, maxw, hk, wk);
+    DFE_REQUIRE(ctx, !(full || full_conf) || (hImg >= H1 && wImg >= W1), DFE_E_SHAPE, "%s: full frame %dx%d smaller than the output %dx%d", fn, hImg, wImg,
                 H1, W1);
     const int ny = (maxh + 1) / 2 - 1, nx = (maxw + 1) / 2 - 1;     // prepareInput: narrow(2, ceil(maxh/2), ..) 1-based -> first row / column, 0-based
     const int N = maxh * maxw;
@@ -104,15 +129,18 @@ extern "C" int dfe_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const f
     const bool lean = nlayers ? dfe_feat_matching_flat_argmin_takes(ctx, K, H1, W1, maxh, maxw)
                               : dfe_feat_matching_flat_view_takes(ctx, K, H1, W1, maxh, maxw, W, (long long)H * W) && !(((uintptr_t)I0 | (uintptr_t)I1) & 3);
     // arena: cropped frame 0 | two ping-pong feature buffers per branch | (fallback) contiguous in1 | volume | probabilities | index | scores
+    // ('mean' fallback: imaxs | scores | x | y | row marginals in place of index and scores)
     const int Hc = H1 + hk - 1, Wc = W1 + wk - 1;                   // the part of frame 0 the narrowed features come from
     auto al = [](size_t f) { return (f + 63) / 64 * 64; };
     const size_t f_c0 = nlayers ? (size_t)C * Hc * Wc : 0;
     const size_t f_fa = nlayers ? (size_t)maxplanes * Hc * Wc : 0, f_fb = nlayers ? (size_t)maxplanes * H * W : 0;
     const size_t f_in1 = (!lean && !nlayers) ? (size_t)K * P1 : 0;
     const size_t f_vol = lean ? 0 : (size_t)P1 * N;
-    const size_t f_idx = (lean || index) ? 0 : (size_t)P1 * 2, f_sc = (lean || scores || !use_threshold) ? 0 : (size_t)P1;
+    const size_t f_idx = (lean || index || mean) ? 0 : (size_t)P1 * 2, f_sc = (lean || scores || !use_threshold || mean) ? 0 : (size_t)P1;
+    const size_t f_mean = (lean || !mean) ? 0 : (size_t)P1 * (5 + maxh);
     void *scr = nullptr;
-    int rc = dfe_scratch(ctx, (al(f_c0) + 2 * al(f_fa) + 2 * al(f_fb) + al(f_in1) + 2 * al(f_vol) + al(f_idx) + al(f_sc)) * sizeof(float), &scr, nlayers > 0);
+    int rc = dfe_scratch(ctx, (al(f_c0) + 2 * al(f_fa) + 2 * al(f_fb) + al(f_in1) + 2 * al(f_vol) + al(f_idx) + al(f_sc) + al(f_mean)) * sizeof(float), &scr,
+                     nlayers > 0);
     if (rc) return rc;
     float *c0 = (float *)scr;
     float *fa[2] = {c0 + al(f_c0), c0 + al(f_c0) + al(f_fa)};
@@ -120,6 +148,7 @@ extern "C" int dfe_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const f
     float *in1c = fb[1] + al(f_fb), *vol = in1c + al(f_in1), *prob = vol + al(f_vol);
     long long *idx_s = (long long *)(prob + al(f_vol));
     float *sc_s = (float *)idx_s + al(f_idx);
+    float *mean_s = sc_s + al(f_sc);
     const float *in1 = nullptr, *in2 = nullptr;
     int pitch1 = W1;
     long long plane1 = P1;
@@ -154,7 +183,7 @@ extern "C" int dfe_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const f
             ia = o2[0]; ib = o2[1];
             ha -= layers[i].kH - 1; wa -= layers[i].kW - 1; hb -= layers[i].kH - 1; wb -= layers[i].kW - 1;
         }
-        DFE_REQUIRE(ctx, ha == H1 && wa == W1 && hb == Hf && wb == Wf, DFE_E_SHAPE, "dfe_flow_pair_filtered_f32: internal shape mismatch");
+        DFE_REQUIRE(ctx, ha == H1 && wa == W1 && hb == Hf && wb == Wf, DFE_E_SHAPE, "%s: internal shape mismatch", fn);
         in1 = ia; in2 = ib;
     } else {
         // geometry.prefilter: the caller ran the filter (depth_estimation_opticalflow.lua:66-75) -- patch 1's narrow is a view of its map
@@ -172,9 +201,10 @@ extern "C" int dfe_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const f
         so.use_threshold = use_threshold ? 1 : 0; so.threshold = (float)threshold;
         so.hFull = hImg; so.wFull = wImg; so.full = full; so.full_conf = full_conf; so.index = (long long *)index; so.scores = scores;
         bool done = false;
-        rc = dfe_feat_matching_flat_soft(ctx, in1, pitch1, plane1, in2, K, H1, W1, maxh, maxw, &so, &done);
+        rc = mean ? dfe_feat_matching_flat_mean(ctx, in1, pitch1, plane1, in2, K, H1, W1, maxh, maxw, &so, &done)
+                  : dfe_feat_matching_flat_soft(ctx, in1, pitch1, plane1, in2, K, H1, W1, maxh, maxw, &so, &done);
         if (rc || done) return rc;
-        return dfe_fail(ctx, DFE_E_UNSUPPORTED, "dfe_flow_pair_filtered_f32: the matcher declined a shape its predicate took");
+        return dfe_fail(ctx, DFE_E_UNSUPPORTED, "%s: the matcher declined a shape its predicate took", fn);
     }
     if (!nlayers) {
         hipLaunchKernelGGL(ss_crop_kernel, dim3(ss_grid((long long)K * P1)), dim3(256), 0, ctx->stream, I0, (long long)H * W, W, ny, nx, H1, W1, (long long)K * P1, in1c);
@@ -189,6 +219,22 @@ extern "C" int dfe_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const f
         if (rc) return rc;
     }
     DfeStageScope st(ctx, DFE_STAGE_EXTRACT);
+    if (mean) {
+        // getOutputConfidences2 (opticalflow_model.lua:171-199): OutputExtractor, the row marginals, extractOutput on them into zeroed scores
+        long long *im = (long long *)mean_s;
+        float *sc = mean_s + 2 * P1, *xs = sc + P1, *ys = xs + P1, *marg = ys + P1;
+        rc = dfe_output_extractor_f32(ctx, prob, P1, maxh, maxw, xs, ys);
+        if (rc) return rc;
+        rc = dfe_marginal_sum_f32(ctx, prob, P1, maxh, maxw, marg);
+        if (rc) return rc;
+        DFE_HIP(ctx, hipMemsetAsync(mean_s, 0, (size_t)P1 * 3 * sizeof(float), ctx->stream));   // imaxs and scores
+        rc = dfe_extract_output(ctx, marg, H1, W1, maxh, sc, 0.11, (int64_t *)im);
+        if (rc) return rc;
+        hipLaunchKernelGGL(ss_paste_mean_kernel, dim3(ss_grid(P1)), dim3(256), 0, ctx->stream, ys, xs, sc, H1, W1, maxh, maxw, ho, wo, wImg, (long long)hImg * wImg,
+                           full, full_conf, (long long *)index);
+        DFE_LAUNCH_CHECK(ctx);
+        return DFE_OK;
+    }
     long long *idx_d = index ? (long long *)index : idx_s;
     float *sc_d = scores ? scores : sc_s;
     const int middle = (maxw + 1) / 2 + maxw * ((maxh + 1) / 2 - 1);
@@ -208,6 +254,21 @@ extern "C" int dfe_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const f
         DFE_LAUNCH_CHECK(ctx);
     }
     return DFE_OK;
+}
+
+extern "C" int dfe_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, const dfe_filter_layer *layers, int nlayers,
+                                          int maxh, int maxw, int use_threshold, double threshold, int hImg, int wImg, float *full, float *full_conf,
+                                          int64_t *index, float *scores) {
+    DFE_ENTER(ctx);
+    return ss_flow_pair(ctx, "dfe_flow_pair_filtered_f32", false, I0, I1, C, H, W, layers, nlayers, maxh, maxw, use_threshold, threshold, hImg, wImg, full,
+                        full_conf, index, scores);
+}
+
+extern "C" int dfe_flow_pair_filtered_mean_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, const dfe_filter_layer *layers,
+                                               int nlayers, int maxh, int maxw, int hImg, int wImg, float *full, float *full_conf, int64_t *index) {
+    DFE_ENTER(ctx);
+    return ss_flow_pair(ctx, "dfe_flow_pair_filtered_mean_f32", true, I0, I1, C, H, W, layers, nlayers, maxh, maxw, 0, 0.0, hImg, wImg, full, full_conf, index,
+                        nullptr);
 }
 
 // nn.SpatialMatching whose first input is a VIEW (rows pitch1 floats apart, planes plane1 floats apart): prepareInput's narrow handed on

@@ -11,6 +11,8 @@
 -- output.index (h x w LongTensor), output.y / output.x (h x w, centred displacements), output.confidences.  The filter's weights are read
 -- from `filter` (getFilter(geometry)) on every call, so a model that keeps training keeps working; the script's own model:forward stays
 -- what it is, module by module.  With 16- / 17-wide windows the H1 x W1 x maxh x maxw volume is never written (dfe_flow_pair_filtered_f32).
+-- geometry.output_extraction_method == 'mean' (depth_estimation_api.lua:25-31): processOutput's 'mean' branch instead
+-- (dfe_flow_pair_filtered_mean_f32) -- output.y / output.x are the soft arg-max, sub-pixel; threshold is ignored, as processOutput does.
 local dfe = require 'dfe_ffi'
 local ffi = require 'ffi'
 local M = {}
@@ -51,8 +53,13 @@ local function run(geometry, layers, nlayers, hk, wk, a, b, threshold)
    local dfull = ffi.cast('float*', B.full:reserve(2 * hImg * wImg * 4))
    local dconf = ffi.cast('float*', B.conf:reserve(hImg * wImg * 4))
    local didx = ffi.cast('int64_t*', B.idx:reserve(h * w * 8))
-   dfe.check(dfe.lib.dfe_flow_pair_filtered_f32(dfe.ctx, ffi.cast('const float*', da), ffi.cast('const float*', db), C, H, W, layers, nlayers,
-                                                geometry.maxh, geometry.maxw, threshold and 1 or 0, threshold or 0, hImg, wImg, dfull, dconf, didx, nil))
+   if geometry.output_extraction_method == 'mean' then
+      dfe.check(dfe.lib.dfe_flow_pair_filtered_mean_f32(dfe.ctx, ffi.cast('const float*', da), ffi.cast('const float*', db), C, H, W, layers, nlayers,
+                                                         geometry.maxh, geometry.maxw, hImg, wImg, dfull, dconf, didx))
+   else
+      dfe.check(dfe.lib.dfe_flow_pair_filtered_f32(dfe.ctx, ffi.cast('const float*', da), ffi.cast('const float*', db), C, H, W, layers, nlayers,
+                                                   geometry.maxh, geometry.maxw, threshold and 1 or 0, threshold or 0, hImg, wImg, dfull, dconf, didx, nil))
+   end
    local ret = {full = torch.FloatTensor(2, hImg, wImg), full_confidences = torch.FloatTensor(hImg, wImg), index = torch.LongTensor(h, w)}
    dfe.download(ret.full, dfull); dfe.download(ret.full_confidences, dconf); dfe.download(ret.index, didx)
    local ho, wo = math.floor((hImg - h) / 2), math.floor((wImg - w) / 2)                              -- opticalflow_model.lua:228-230

@@ -428,15 +428,23 @@ def single_scale_forward_flow(model, geometry, input, threshold=None, one_call=T
       one_call=True: dfe_flow_pair_filtered_f32 -- filter stack of both frames, the narrow, matcher, Minus / SoftMax, the arg-max with the
         centre tie-break or extractOutput, decode and centre paste; with 16- / 17-wide windows the volume is never written;
       one_call=False: the modules, then processOutput -- the same results bit for bit.
-    Returns processOutput's table: index, confidences, y, x, full, full_confidences (+ scores with a threshold)."""
+    Returns processOutput's table: index, confidences, y, x, full, full_confidences (+ scores with a threshold).
+    output_extraction_method 'mean' (depth_estimation_api.lua:25-31): processOutput's 'mean' branch on the soft-max's output -- y, x are the
+    soft arg-max (floats), the threshold is not used, and the OutputExtractor getModel appends is not run (processOutput computes the same
+    soft arg-max itself); one_call=True takes dfe_flow_pair_filtered_mean_f32 while the modules are the ones getModel built."""
     from .opticalflow_model import prepareInput, processOutput, _g
     from .multiscale import filter_layers_array
 
     a, b = input
     g = geometry
     maxh, maxw = _g(g, "maxh"), _g(g, "maxw")
-    if _g(g, "output_extraction_method", "max") != "max" or len(model.modules) != (3 if prefiltered else 4) or not one_call:
-        # ('mean' extraction, training mode, or a model whose module list a caller has patched: module by module)
+    mean = _g(g, "output_extraction_method", "max") == "mean"
+    if mean:
+        staged = not one_call or not _built_for_mean(model, maxh, maxw, prefiltered)
+    else:
+        staged = _g(g, "output_extraction_method", "max") != "max" or len(model.modules) != (3 if prefiltered else 4) or not one_call
+    if staged:
+        # (training mode, or a model whose module list a caller has patched: module by module)
         if prefiltered:
             inp = prepareInput(dict(g, prefilter=True) if isinstance(g, dict) else g, a, b)
         else:
@@ -446,8 +454,11 @@ def single_scale_forward_flow(model, geometry, input, threshold=None, one_call=T
             f1, f2 = par.modules[0].forward(a), par.modules[1].forward(b)
             y0, x0 = math.ceil(maxh / 2) - 1, math.ceil(maxw / 2) - 1
             inp = [f1[:, y0 : y0 + f1.shape[1] - maxh + 1, x0 : x0 + f1.shape[2] - maxw + 1], f2]
+        mods = model.modules if prefiltered else model.modules[1:]
+        if mean and mods and isinstance(mods[-1], glue.OutputExtractor):   # processOutput takes the probabilities, not its {x, y} list
+            mods = mods[:-1]
         out = inp
-        for m in (model.modules if prefiltered else model.modules[1:]):
+        for m in mods:
             out = m.forward(out)
         return processOutput(g, out, True, threshold)
     if a.dtype != torch.float32 or b.dtype != torch.float32 or tuple(a.shape) != tuple(b.shape) or a.dim() != 3:
@@ -468,15 +479,35 @@ def single_scale_forward_flow(model, geometry, input, threshold=None, one_call=T
     full = torch.empty((2, hImg, wImg), dtype=torch.float32, device=dev)
     fc = torch.empty((hImg, wImg), dtype=torch.float32, device=dev)
     idx = torch.empty((H1, W1), dtype=torch.int64, device=dev)
-    sc = torch.empty((H1, W1), dtype=torch.float32, device=dev) if threshold is not None else None
+    sc = torch.empty((H1, W1), dtype=torch.float32, device=dev) if threshold is not None and not mean else None
     ctx = get_ctx(a)
-    ctx.check(lib().dfe_flow_pair_filtered_f32(ctx.handle, ptr(a), ptr(b), Cc, H, W, arr, nl, maxh, maxw, 0 if threshold is None else 1,
-                                               float(threshold or 0.0), hImg, wImg, ptr(full), ptr(fc), ptr(idx), ptr(sc)))
+    if mean:
+        ctx.check(lib().dfe_flow_pair_filtered_mean_f32(ctx.handle, ptr(a), ptr(b), Cc, H, W, arr, nl, maxh, maxw, hImg, wImg, ptr(full), ptr(fc), ptr(idx)))
+    else:
+        ctx.check(lib().dfe_flow_pair_filtered_f32(ctx.handle, ptr(a), ptr(b), Cc, H, W, arr, nl, maxh, maxw, 0 if threshold is None else 1,
+                                                   float(threshold or 0.0), hImg, wImg, ptr(full), ptr(fc), ptr(idx), ptr(sc)))
     del keep
     ho, wo = (hImg - H1) // 2, (wImg - W1) // 2
-    ret = {"index": idx, "full": full, "full_confidences": fc,
-           "y": full[0, ho : ho + H1, wo : wo + W1].to(torch.int64), "x": full[1, ho : ho + H1, wo : wo + W1].to(torch.int64),
+    y, x = full[0, ho : ho + H1, wo : wo + W1], full[1, ho : ho + H1, wo : wo + W1]
+    ret = {"index": idx, "full": full, "full_confidences": fc, "y": y if mean else y.to(torch.int64), "x": x if mean else x.to(torch.int64),
            "confidences": fc[ho : ho + H1, wo : wo + W1]}
     if sc is not None:
         ret["scores"] = sc
     return ret
+
+
+def _built_for_mean(model, maxh, maxw, prefiltered):
+    """Whether `model.modules` are still the ones getModel built for 'mean' -- [ParallelTable of two filter branches,] SpatialMatching(maxh,
+    maxw), Minus, SoftMaxWindow, OutputExtractor -- so that the one-call entry computes what they would (a caller who replaces a module
+    keeps the count, hence the types)."""
+    mods = model.modules
+    want = ([ParallelTable] if not prefiltered else []) + [SpatialMatching, Minus, SoftMaxWindow, glue.OutputExtractor]
+    if len(mods) != len(want) or any(type(m) is not t for m, t in zip(mods, want)):
+        return False
+    sm = mods[-4]
+    if (sm.maxh, sm.maxw) != (maxh, maxw):
+        return False
+    if not prefiltered:
+        par = mods[0]
+        return len(par.modules) == 2 and type(par.modules[0]) is Sequential and type(par.modules[1]) is _SharedFilter and par.modules[1].filt is par.modules[0]
+    return True

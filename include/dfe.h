@@ -396,6 +396,21 @@ int dfe_multiscale_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const f
 int dfe_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, const dfe_filter_layer *layers, int nlayers,
                                int maxh, int maxw, int use_threshold, double threshold, int hImg, int wImg, float *full, float *full_conf,
                                int64_t *index, float *scores);
+/* replaces: the same per-pair step for a model built with geometry.output_extraction_method = 'mean' (depth_estimation_api.lua:25-31,
+ *   164-182; test_opticalflow.lua:347-353): getModel's SpatialMatching -> Minus -> SoftMax, then processOutput's 'mean' branch
+ *   (opticalflow_model.lua:171-199, 218-226) --
+ *     y, x        the probability-weighted mean cell of the window, 1-based (OutputExtractor), minus centered2onebased(0, 0): sub-pixel flow
+ *     confidence  extractOutput(m, scores, 0.11, imaxs) on the window's row marginals m_r = sum_c p[r][c], then scores > 0 -- i.e. 1 where
+ *                 some m_r exceeds 0.11, else 0
+ *     index       yx2x(floor(y + 0.5), floor(x + 0.5)) of the uncentred y, x (fp32), int64
+ *   Frames, layers, nlayers (0: I0 / I1 are the feature maps, patch 1's narrow a view) and the output region as dfe_flow_pair_filtered_f32.
+ *   Outputs (each may be NULL, not all): full [2][hImg][wImg] (plane 0 = y, plane 1 = x, floats; zero outside the pasted region),
+ *   full_conf [hImg][wImg], index [H1][W1].  There is no threshold (processOutput's 'mean' branch ignores it).
+ *   16- / 17-wide windows on maps at least 253 columns wide never write the volume (the matcher's soft-arg-max epilogue); other shapes go
+ *   through the stand-alone ops (dfe_output_extractor_f32, dfe_marginal_sum_f32, dfe_extract_output).  Either way the results equal the
+ *   module path's (getModel():forward up to the soft-max + processOutput) bit for bit. */
+int dfe_flow_pair_filtered_mean_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, const dfe_filter_layer *layers,
+                                    int nlayers, int maxh, int maxw, int hImg, int wImg, float *full, float *full_conf, int64_t *index);
 /* replaces: nn.SpatialMatching(maxh, maxw, false):forward({patch1, patch2}) where patch1 is the NARROW of a larger map
  *   (prepareInput, opticalflow_model.lua:147-149: `patch1:narrow(2, ..):narrow(3, ..)` is a view; nnx made it contiguous inside the
  *   module): in1 is read in place, rows in1_pitch floats apart and planes in1_plane floats apart.  Same output as dfe_spatial_matching_f32. */
