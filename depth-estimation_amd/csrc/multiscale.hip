@@ -10,7 +10,6 @@
 #include <cstring>
 #include <type_traits>
 #include <cmath>
-#include <memory>
 
 namespace {
 
@@ -997,55 +996,505 @@ int dfe_pyramid_scale_volume_f32(dfe_ctx *ctx, const float *I0, const float *I1,
     return cv_frames_dispatch(ctx, p0, p1, C, Hp, Wp, (long long)Hp * Wp, kh, kw, maxh, maxw, out);
 }
 
+// ---- the one-call pyramid matcher: plan (ms_plan), buffers (ms_bufs), stages (ms_prep_raw ... ms_cascade_cell) ------------------
 // f16_scale != 0: every scale's volume is stored as half(cost * f16_scale) (dfe_multiscale_flow_pair_f16)
 // the learned patch filters of the matcher (NULL = raw patches, the identity filter): layers [share ? 1 : nratios][nlayers]
 struct MsFilter { const dfe_filter_layer *layers; int nlayers, share; };
 // u8_scale > 0: I0 / I1 point to uint8 frames (raw-patch pyramid only: the preparation kernels, the frames' only readers, convert)
+struct MsArgs {
+    const float *I0, *I1;
+    int C, H, W, k, maxh, maxw;
+    const int *ratios;
+    int nratios;
+    float *flow;
+    int64_t *idx;
+    float f16_scale;
+    const MsFilter *filt;
+    float u8_scale;
+};
+// one scale: its sizes and where its buffers start in the arena (bytes)
+struct MsScale {
+    int r, Hs, Ws, Hp, Wp;         // ratio, the scale's frame, its padded frame
+    size_t feat, fbuf;             // learned filters: four feature buffers of fbuf bytes (ping-pong per frame), each the largest layer output
+    size_t frames, cost, prob, best;
+};
+// everything that is decided before the first launch
+struct MsPlan {
+    MsArgs a;
+    float *fx;                     // the flow's second plane, or NULL
+    int N, hk, wk, hp, wp, pt, pl, middle;
+    MsScale sc[DFE_MAX_RATIOS];
+    size_t total;                  // arena bytes
+    long long frame_max;           // the largest padded frame, C * Hp * Wp elements
+    CascadeGeom g;                 // (in / out_scale are the cell cascade's to fill)
+    MultiGeom mg;
+    bool fast;                     // one-cell-per-lane path of the cascade kernel
+    bool px_path;                  // lane <-> pixel path (cascade_px_kernel)
+    bool half_asked;               // fp16 volumes are asked for as halves from the volume kernels / matchers
+    bool fuse_fine, fuse_mid;      // the finest / the second scale has no volume: fused into its volume kernel or matcher
+    bool lone_parent;              // the coarsest scale gets a launch of its own (its child is a fused scale)
+    bool prep_tiles;               // raw frames: prep_tiles_kernel (every scale from one read) instead of prep_scales_kernel
+    bool same_k;                   // learned filters: every scale's stack ends in fK planes
+    int s0;                        // the first scale whose volume is materialised
+    int nq_hint, fK;               // cv_frames_dispatch_multi's hint; planes of the finest scale's features
+    size_t lds;                    // cascade_argmax_kernel's dynamic LDS
+};
+// the arena as pointers: the one place that adds the plan's offsets to the arena's base
+struct MsBufs {
+    float *p0[DFE_MAX_RATIOS], *p1[DFE_MAX_RATIOS];   // padded frames
+    float *cost[DFE_MAX_RATIOS];                      // volumes
+    float *prob[DFE_MAX_RATIOS];                      // soft-min probabilities (lane <-> cell) / cascaded windows (lane <-> pixel)
+    float2 *best[DFE_MAX_RATIOS];                     // running best (lane <-> pixel)
+    float *feat[DFE_MAX_RATIOS][4];
+};
+// what the launchers report back and a later stage depends on
+struct MsRun {
+    bool merged, soft_done, half_vol;   // the volumes came from one launch / it took the coarser scales' soft-mins / they are halves
+    const float *feat[2][2];            // learned filters: the two finest scales' feature planes [scale][frame 0, frame 1]
+};
+
+// receptive field of the patch filter: k x k raw patches, or hKernel = sum kH - (nlayers - 1) of the learned stack (opticalflow.lua:154-171)
+static int ms_filter_field(dfe_ctx *ctx, const MsArgs &a, int *hk, int *wk, int *maxplanes) {
+    const MsFilter *filt = a.filt;
+    for (int v = 0; v < (filt->share ? 1 : a.nratios); ++v) {
+        int h = 1, w = 1, nin = a.C;
+        for (int l = 0; l < filt->nlayers; ++l) {
+            const dfe_filter_layer &L = filt->layers[v * filt->nlayers + l];
+            DFE_REQUIRE(ctx, L.weight && L.nIn > 0 && L.nOut > 0 && L.kH > 0 && L.kW > 0, DFE_E_ARG, "dfe_multiscale_flow_pair_filtered_f32: layer %d: bad description", l);
+            DFE_REQUIRE(ctx, L.conn ? L.nIn <= nin : L.nIn == nin, DFE_E_SHAPE, "dfe_multiscale_flow_pair_filtered_f32: layer %d reads %d planes, the layer before it makes %d", l, L.nIn, nin);
+            h += L.kH - 1; w += L.kW - 1; nin = L.nOut;
+            if (L.nOut > *maxplanes) *maxplanes = L.nOut;
+        }
+        DFE_REQUIRE(ctx, v == 0 || (h == *hk && w == *wk), DFE_E_SHAPE, "dfe_multiscale_flow_pair_filtered_f32: the scales' filter stacks have different receptive fields");
+        *hk = h; *wk = w;
+    }
+    return DFE_OK;
+}
+
+// Every check, the geometry, the arena layout and every path decision of the one-call matcher.  Launches and allocates nothing.
+static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
+    MsPlan &P = *plan;
+    const int C = a.C, H = a.H, W = a.W, k = a.k, maxh = a.maxh, maxw = a.maxw, nratios = a.nratios;
+    const int *ratios = a.ratios;
+    DFE_REQUIRE(ctx, a.I0 && a.I1 && (a.flow || a.idx), DFE_E_ARG, "dfe_multiscale_flow_pair_f32: NULL tensor");
+    DFE_REQUIRE(ctx, C > 0 && k > 0 && maxh > 0 && maxw > 0, DFE_E_ARG, "dfe_multiscale_flow_pair_f32: bad size");
+    P.a = a;
+    P.fx = a.flow ? a.flow + (size_t)H * W : nullptr;
+    int rc = fill_cascade(ctx, P.g, ratios, nratios, maxh, maxw);
+    if (rc) return rc;
+    P.g.H = H; P.g.W = W;
+    const int N = P.N = maxh * maxw;
+    P.middle = ((maxh + 1) / 2 - 1) * maxw + (maxw + 1) / 2;   // yx2xMulti(0, 0)
+    int maxplanes = C;
+    P.hk = P.wk = k;
+    if (a.filt) {
+        rc = ms_filter_field(ctx, a, &P.hk, &P.wk, &maxplanes);
+        if (rc) return rc;
+    }
+    const int hp = P.hp = maxh - 1 + P.hk - 1, wp = P.wp = maxw - 1 + P.wk - 1;   // hPatch2-1 (opticalflow_model_multiscale.lua:136-141)
+    P.pt = hp / 2; P.pl = wp / 2;
+    P.total = 0;
+    for (int s = 0; s < nratios; ++s) {
+        MsScale &sc = P.sc[s];
+        const int r = sc.r = ratios[s];
+        DFE_REQUIRE(ctx, H % r == 0 && W % r == 0, DFE_E_SHAPE,
+                    "dfe_multiscale_flow_pair_f32: frame %dx%d is not a multiple of ratio %d (opticalflow_model_multiscale.lua:238-243)", H, W, r);
+        sc.Hs = H / r; sc.Ws = W / r; sc.Hp = sc.Hs + hp; sc.Wp = sc.Ws + wp;
+        const size_t np = (size_t)C * sc.Hp * sc.Wp, nv = (size_t)sc.Hs * sc.Ws * N;
+        // learned filters: four feature buffers per scale (ping-pong per frame), each the largest layer output
+        sc.fbuf = a.filt ? ((size_t)maxplanes * sc.Hp * sc.Wp * sizeof(float) + 255) / 256 * 256 : 0;
+        sc.feat = P.total; P.total += 4 * sc.fbuf;
+        sc.frames = P.total; P.total += (2 * np * sizeof(float) + 255) / 256 * 256;
+        sc.cost = P.total; P.total += (nv * sizeof(float) + 255) / 256 * 256;
+        sc.prob = P.total; P.total += (nv * sizeof(float) + 255) / 256 * 256;
+        sc.best = P.total; P.total += ((size_t)sc.Hs * sc.Ws * sizeof(float2) + 255) / 256 * 256;
+    }
+    P.mg.maxh = maxh; P.mg.maxw = maxw; P.mg.nratios = nratios;
+    P.frame_max = 0;
+    for (int s = 0; s < nratios; ++s) {
+        const long long np = (long long)C * P.sc[s].Hp * P.sc[s].Wp;
+        DFE_REQUIRE(ctx, 2 * np < (1ll << 31), DFE_E_SHAPE, "dfe_multiscale_flow_pair_f32: frame too large");
+        if (np > P.frame_max) P.frame_max = np;
+        P.mg.ratios[s] = ratios[s];
+        P.mg.d[s] = P.g.d[s];
+    }
+    P.fast = N <= 64 && nratios <= 5;   // one-cell-per-lane path of the cascade kernel
+    // lane <-> pixel path (cascade_px_kernel): 8 x 8 windows, ratios 1, 2, 4, ...; DFE_CASCADE_PX=0 keeps the lane <-> cell kernels
+    bool px_path = P.fast && maxh == 8 && maxw == 8;
+    for (int s = 0; s < nratios; ++s)
+        if (ratios[s] != (1 << s) || (s > 0 && P.g.d[s] != 2)) px_path = false;   // (ring width 2: the kernel's compile-time class order)
+    P.px_path = px_path && ctx->opt[DFE_OPT_CASCADE_PX] != 0;
+    // fp16 volumes: written as halves by the volume kernel itself where the lane <-> pixel cascade will read them (8 x 8
+    // windows, C = 3, k = 7); any other shape builds fp32 volumes and rounds them to half precision in place -- same values
+    P.half_asked = a.f16_scale != 0.f && P.px_path;
+    // raw patches, 3 channels, 7 x 7, on the lane <-> pixel path: the finest scale is fused into its volume kernel (no volume)
+    // -- where it pays: the fused kernel is VALU-bound (three 64-lane reductions per pixel), the volume it saves is HBM traffic that the
+    // small frames hide behind the coarse scales' launches.  Measured, volume path -> fused: VGA 0.076 -> 0.099 ms, 720p 0.213 ->
+    // 0.185, 1080p 0.430 -> 0.366, 4K 1.94 -> 1.40; fp16 volumes (half the bytes to save): 1080p 0.344 -> 0.368, 4K 1.48 -> 1.32.
+    // DFE_FINE_FUSE=0 / 1 forces the choice.
+    // Learned filters: the same epilogue behind the one-chunk feature matcher (feat_matching_win64_fine_kernel), where every scale's
+    // stack ends in the same number of planes (<= 16).
+    P.fK = 0;
+    P.same_k = true;
+    bool fine_shape = C == 3 && k == 7;
+    if (a.filt) {
+        P.fK = a.filt->layers[a.filt->nlayers - 1].nOut;
+        for (int s = 1; s < nratios && !a.filt->share; ++s) P.same_k = P.same_k && a.filt->layers[s * a.filt->nlayers + a.filt->nlayers - 1].nOut == P.fK;
+        fine_shape = dfe_feat_matching_win64_ok(ctx, P.fK, maxh, maxw) && P.same_k;   // the launcher's own conditions (cv_mode, fm64, K, LDS)
+    }
+    // (learned filters, volume path -> fused: VGA 0.193 -> 0.183 ms, 1080p 1.064 -> 0.912: the matcher's launch is long enough at VGA already)
+    P.fuse_fine = P.px_path && fine_shape && (long long)H * W >= (a.filt ? 250000ll : a.f16_scale != 0.f ? 3000000ll : 600000ll);
+    if (ctx->opt[DFE_OPT_FINE_FUSE] >= 0) P.fuse_fine = P.px_path && fine_shape && ctx->opt[DFE_OPT_FINE_FUSE] != 0;
+    // the second scale the same way (its volume, 21 % of the rest, is otherwise written by the volume kernel and read back by its
+    // cascade launch): wherever the finest scale is fused and a coarser scale exists above it.  DFE_MID_FUSE=0 / 1 forces the choice.
+    // Measured, finest scale fused -> both: 1080p 0.363 -> 0.346 ms, 4K 1.40 -> 1.29; 720p 0.179 -> 0.205 (230 k pixels: one partial round
+    // of blocks, latency-bound); fp16 volumes (half the bytes to save) 4K 1.315 -> 1.320.
+    const bool mid_shape = nratios >= 3 && (a.filt ? (P.sc[1].Hs >= 16 && P.sc[1].Ws >= 8 && (P.sc[1].Hs | P.sc[1].Ws) % 2 == 0)
+                                                   : cv_finest_plan_ok(ctx, P.sc[1].Hp, P.sc[1].Wp, maxh, maxw));
+    P.fuse_mid = P.fuse_fine && a.f16_scale == 0.f && (long long)H * W >= 1500000ll && mid_shape;
+    if (ctx->opt[DFE_OPT_MID_FUSE] >= 0) P.fuse_mid = P.fuse_fine && ctx->opt[DFE_OPT_MID_FUSE] != 0 && mid_shape;
+    P.s0 = P.fuse_mid ? 2 : P.fuse_fine ? 1 : 0;      // the first scale whose volume is materialised
+    // where the coarsest scale is the parent of a fused scale it needs a launch of its own (it cannot be recomputed inside its child's)
+    P.lone_parent = (P.fuse_mid && nratios == 3) || (P.fuse_fine && !P.fuse_mid && nratios == 2);
+    P.nq_hint = (P.fuse_fine && (long long)H * W < 4000000ll) ? 3 : 0;
+    // raw frames: every scale from one read of the frames (prep_tiles_kernel; PrepTile holds five scales) or scale by scale
+    bool pow2 = nratios <= 5;
+    for (int s = 0; s < nratios; ++s) pow2 = pow2 && (ratios[s] == 1 || ratios[s] == 2 || ratios[s] == 4 || ratios[s] == 8 || ratios[s] == 16);
+    // (large frames only: at VGA the per-scale kernel's 8.8 us are all latency and the tile kernel's sequential r x r sums are
+    //  slower -- 0.082 against 0.076 ms per pair; 1080p 0.451 -> 0.430 ms, 4K five levels 1.69 -> 1.48 ms)
+    // (tried: the finest scale's padded frames made on a second stream next to the coarse scales' chain, forked here and joined in
+    //  front of the fused kernel, which alone reads them -- 720p 0.178 -> 0.190 ms, 1080p 0.347 -> 0.348, 4K 1.27 -> 1.31: the
+    //  frames are read twice and the cross-stream waits cost more than the overlap gives)
+    P.prep_tiles = !a.filt && pow2 && (long long)H * W >= 1500000 && ctx->opt[DFE_OPT_PREP_TILES] != 0;
+    // the lane <-> cell cascade's LDS: a wave's two window buffers, or the class -> displacement table where that is larger
+    P.lds = (size_t)kWaves * 2 * N * sizeof(float);
+    DFE_REQUIRE(ctx, P.px_path || P.lds <= 64 * 1024, DFE_E_UNSUPPORTED, "dfe_multiscale_flow_pair_f32: window %dx%d too large", maxh, maxw);
+    if (P.lds < (size_t)P.g.ncls * sizeof(int2)) P.lds = (size_t)P.g.ncls * sizeof(int2);
+    return DFE_OK;
+}
+
+static void ms_bufs(const MsPlan &P, void *scr, MsBufs *bufs) {
+    MsBufs &B = *bufs;
+    char *base = (char *)scr;
+    for (int s = 0; s < P.a.nratios; ++s) {
+        const MsScale &sc = P.sc[s];
+        B.p0[s] = (float *)(base + sc.frames);
+        B.p1[s] = B.p0[s] + (size_t)P.a.C * sc.Hp * sc.Wp;
+        B.cost[s] = (float *)(base + sc.cost);
+        B.prob[s] = (float *)(base + sc.prob);
+        B.best[s] = (float2 *)(base + sc.best);
+        for (int j = 0; j < 4; ++j) B.feat[s][j] = (float *)(base + sc.feat + j * sc.fbuf);
+    }
+}
+
+// stage "filter" of the raw-patch pyramid: every scale's padded frames from the float or uint8 frames in one launch
+static int ms_prep_raw(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B) {
+    const MsArgs &a = P.a;
+    const unsigned char *b0 = (const unsigned char *)a.I0, *b1 = (const unsigned char *)a.I1;
+    DfeStageScope st(ctx, DFE_STAGE_FILTER);
+    if (P.prep_tiles) {       // every scale from one read of the frames
+        PrepTile pq;
+        pq.ns = a.nratios;
+        for (int s = 0; s < a.nratios; ++s) { pq.r[s] = P.sc[s].r; pq.Hp[s] = P.sc[s].Hp; pq.Wp[s] = P.sc[s].Wp; pq.p[0][s] = B.p0[s]; pq.p[1][s] = B.p1[s]; }
+        const dim3 grid(dfe_cdiv(a.W, PT), dfe_cdiv(a.H, PT), 2 * a.C);
+        if (a.u8_scale > 0.f) hipLaunchKernelGGL(prep_tiles_kernel<unsigned char>, grid, dim3(256), 0, ctx->stream, b0, b1, a.C, a.H, a.W, P.pl, P.pt, pq, a.u8_scale);
+        else hipLaunchKernelGGL(prep_tiles_kernel<float>, grid, dim3(256), 0, ctx->stream, a.I0, a.I1, a.C, a.H, a.W, P.pl, P.pt, pq, 0.f);
+    } else {
+        PrepScales ps;
+        for (int s = 0; s < a.nratios; ++s) { ps.r[s] = P.sc[s].r; ps.Hp[s] = P.sc[s].Hp; ps.Wp[s] = P.sc[s].Wp; ps.p0[s] = B.p0[s]; ps.p1[s] = B.p1[s]; }
+        const dim3 grid(grid1d(2 * P.frame_max, 256 * PREP_EPT), a.nratios);
+        if (a.u8_scale > 0.f) hipLaunchKernelGGL(prep_scales_kernel<unsigned char>, grid, dim3(256), 0, ctx->stream, b0, b1, a.C, a.H, a.W, P.pl, P.pt, ps, a.u8_scale);
+        else hipLaunchKernelGGL(prep_scales_kernel<float>, grid, dim3(256), 0, ctx->stream, a.I0, a.I1, a.C, a.H, a.W, P.pl, P.pt, ps, 0.f);
+    }
+    DFE_LAUNCH_CHECK(ctx);
+    return DFE_OK;
+}
+
+// the learned-filter front: padded frames, the filter stacks, every materialised scale's nn.SpatialMatching
+static int ms_learned_front(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, MsRun &R) {
+    const MsArgs &a = P.a;
+    const MsFilter *filt = a.filt;
+    const int nratios = a.nratios, maxh = a.maxh, maxw = a.maxw;
+    // learned filters (getModelMultiscale's filter1 / filter2, opticalflow_model_multiscale.lua:196-211): frame 0 is cropped by
+    // the search window BEFORE the filter (its zero padding shrinks by floor / ceil((maxh-1)/2)), both padded frames go
+    // through the stack, nn.SpatialMatching(maxh, maxw) runs on the K-plane features
+    const int ct = (maxh - 1) / 2, cl = (maxw - 1) / 2;
+    PrepFrames pf;
+    for (int s = 0; s < nratios; ++s) {
+        const MsScale &sc = P.sc[s];
+        pf.img[2 * s] = a.I0; pf.out[2 * s] = B.p0[s]; pf.r[2 * s] = sc.r;
+        pf.pl[2 * s] = P.pl - cl; pf.pt[2 * s] = P.pt - ct; pf.Hp[2 * s] = sc.Hs + P.hk - 1; pf.Wp[2 * s] = sc.Ws + P.wk - 1;
+        pf.img[2 * s + 1] = a.I1; pf.out[2 * s + 1] = B.p1[s]; pf.r[2 * s + 1] = sc.r;
+        pf.pl[2 * s + 1] = P.pl; pf.pt[2 * s + 1] = P.pt; pf.Hp[2 * s + 1] = sc.Hp; pf.Wp[2 * s + 1] = sc.Wp;
+    }
+    {
+        DfeStageScope st(ctx, DFE_STAGE_FILTER);
+        hipLaunchKernelGGL(prep_frames_kernel, dim3(grid1d(P.frame_max, 256 * 8), 2 * nratios), dim3(256), 0, ctx->stream, a.C, a.H, a.W, pf);
+    }
+    DFE_LAUNCH_CHECK(ctx);
+    // layer by layer, both frames of every scale in ONE launch (18 launches of a few microseconds each otherwise)
+    const float *cur[2 * DFE_MAX_RATIOS];
+    int ch[2 * DFE_MAX_RATIOS], cw[2 * DFE_MAX_RATIOS];
+    for (int e = 0; e < 2 * nratios; ++e) { cur[e] = pf.out[e]; ch[e] = pf.Hp[e]; cw[e] = pf.Wp[e]; }
+    for (int l = 0; l < filt->nlayers; ++l) {
+        DfeStageScope st(ctx, DFE_STAGE_FILTER);
+        const dfe_filter_layer *Lp[2 * DFE_MAX_RATIOS];
+        float *dst[2 * DFE_MAX_RATIOS];
+        for (int e = 0; e < 2 * nratios; ++e) {
+            const int s = e >> 1, f = e & 1;
+            Lp[e] = filt->layers + (filt->share ? 0 : s) * filt->nlayers + l;
+            dst[e] = B.feat[s][2 * f + (l & 1)];
+        }
+        const int rc = dfe_filter_layer_forward_batch(ctx, 2 * nratios, cur, Lp, ch, cw, dst);
+        if (rc) return rc;
+        for (int e = 0; e < 2 * nratios; ++e) { cur[e] = dst[e]; ch[e] -= Lp[e]->kH - 1; cw[e] -= Lp[e]->kW - 1; }
+    }
+    // every scale's nn.SpatialMatching in ONE launch where the one-chunk matcher applies (8 x 8 windows) -- with fp16 volumes
+    // written as halves directly when the lane <-> pixel cascade will read them; else scale by scale
+    DfeStageScope st(ctx, DFE_STAGE_MATCH);
+    const int s0 = P.s0;
+    const float *m1[DFE_MAX_RATIOS], *m2[DFE_MAX_RATIOS];
+    int mh[DFE_MAX_RATIOS], mw[DFE_MAX_RATIOS];
+    for (int s = 0; s < nratios; ++s) { m1[s] = cur[2 * s]; m2[s] = cur[2 * s + 1]; mh[s] = P.sc[s].Hs; mw[s] = P.sc[s].Ws; }
+    R.feat[0][0] = m1[0]; R.feat[0][1] = m2[0];
+    if (nratios > 1) { R.feat[1][0] = m1[1]; R.feat[1][1] = m2[1]; }
+    bool done = nratios - s0 < 1;       // (s0 = 1: the finest scale's matcher runs last, with the fused epilogue -- ms_cascade_px)
+    if (P.same_k && !done) {
+        const int rc = dfe_feat_matching_win64_batch(ctx, nratios - s0, m1 + s0, m2 + s0, P.fK, mh + s0, mw + s0, maxh, maxw, B.cost + s0, P.half_asked ? a.f16_scale : 0.f, &done);
+        if (rc) return rc;
+        R.half_vol = done && P.half_asked;
+    }
+    for (int s = s0; s < nratios && !done; ++s) {
+        const dfe_filter_layer *Ls = filt->layers + (filt->share ? 0 : s) * filt->nlayers;
+        const int rc = dfe_spatial_matching_dispatch(ctx, m1[s], m2[s], Ls[filt->nlayers - 1].nOut, mh[s], mw[s], maxh, maxw, B.cost[s]);
+        if (rc) return rc;
+    }
+    R.merged = true;
+    return DFE_OK;
+}
+
+// the raw-patch volumes of the scales s0 .. nratios-1
+static int ms_raw_volumes(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, MsRun &R) {
+    const MsArgs &a = P.a;
+    // one launch for every scale's volume; on the fast path the coarser scales leave it as soft-min probabilities already
+    // (their blocks run next to the scale-1 blocks that dominate the launch), scale 1 as costs for the cascade's SOFT0
+    // (s0 = 1: the finest scale has NO volume -- its task rows are consumed inside the volume kernel, cv_frames_finest_fused in ms_cascade_px)
+    float *pr[DFE_MAX_RATIOS];
+    int vh[DFE_MAX_RATIOS], vw[DFE_MAX_RATIOS];
+    const int s0 = P.s0, nv = a.nratios - s0;
+    for (int s = s0; s < a.nratios; ++s) {
+        vh[s - s0] = P.sc[s].Hp; vw[s - s0] = P.sc[s].Wp;
+        pr[s - s0] = (P.fast && s > 0 && !P.px_path) ? B.prob[s] : nullptr;
+    }
+    int rc;
+    if (P.half_asked && nv >= 1) {
+        rc = cv_frames_dispatch_multi(ctx, nv, B.p0 + s0, B.p1 + s0, a.C, vh, vw, a.k, a.maxh, a.maxw, B.cost + s0, nullptr, &R.merged, &R.soft_done, a.f16_scale, P.nq_hint);
+        if (rc) return rc;
+        R.half_vol = R.merged;
+    }
+    if (!R.merged && nv >= 1) {
+        rc = cv_frames_dispatch_multi(ctx, nv, B.p0 + s0, B.p1 + s0, a.C, vh, vw, a.k, a.maxh, a.maxw, B.cost + s0, a.f16_scale != 0.f ? nullptr : pr, &R.merged, &R.soft_done, 0.f, P.nq_hint);
+        if (rc) return rc;
+    }
+    for (int s = s0; s < a.nratios && !R.merged; ++s) {
+        rc = cv_frames_dispatch(ctx, B.p0[s], B.p1[s], a.C, P.sc[s].Hp, P.sc[s].Wp, (long long)P.sc[s].Hp * P.sc[s].Wp, a.k, a.k, a.maxh, a.maxw, B.cost[s]);
+        if (rc) return rc;
+    }
+    return DFE_OK;
+}
+
+// fp16 entry, volumes that were built as fp32: scales [s_begin, s_end) rounded to half precision in place
+static void ms_round_half(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, int s_begin, int s_end) {
+    for (int s = s_begin; s < s_end; ++s) {
+        const long long n = (long long)P.sc[s].Hs * P.sc[s].Ws * P.N;
+        hipLaunchKernelGGL(round_half_kernel, dim3(grid1d(n, 256)), dim3(256), 0, ctx->stream, B.cost[s], n, P.a.f16_scale, 1.0f / P.a.f16_scale);
+    }
+}
+
+// the one place cascade_px_kernel is launched: one block per 256 pixels of the scale
+static void launch_cascade_px(dfe_ctx *ctx, bool finest, bool inl, bool h16, const CascadePxArgs &ca, const DecodeTab &dt) {
+    const dim3 grid((unsigned)(((long long)ca.Hs * ca.Ws + 255) / 256)), block(256);
+    if (!finest) {
+        if (h16) {
+            if (inl) hipLaunchKernelGGL((cascade_px_kernel<false, true, true>), grid, block, 0, ctx->stream, ca, dt);
+            else hipLaunchKernelGGL((cascade_px_kernel<false, false, true>), grid, block, 0, ctx->stream, ca, dt);
+        } else if (inl) hipLaunchKernelGGL((cascade_px_kernel<false, true>), grid, block, 0, ctx->stream, ca, dt);
+        else hipLaunchKernelGGL((cascade_px_kernel<false, false>), grid, block, 0, ctx->stream, ca, dt);
+    } else {
+        if (h16) {
+            if (inl) hipLaunchKernelGGL((cascade_px_kernel<true, true, true>), grid, block, 0, ctx->stream, ca, dt);
+            else hipLaunchKernelGGL((cascade_px_kernel<true, false, true>), grid, block, 0, ctx->stream, ca, dt);
+        } else if (inl) hipLaunchKernelGGL((cascade_px_kernel<true, true>), grid, block, 0, ctx->stream, ca, dt);
+        else hipLaunchKernelGGL((cascade_px_kernel<true, false>), grid, block, 0, ctx->stream, ca, dt);
+    }
+}
+
+// scale s (0 or 1) without its volume: raw patches through the volume kernel's fused epilogue, learned features through the matcher's
+static int ms_fused_scale(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const MsRun &R, int s, const CvFineArgs &fa, bool *done) {
+    const MsArgs &a = P.a;
+    if (!a.filt) return cv_frames_finest_fused(ctx, B.p0[s], B.p1[s], a.C, P.sc[s].Hp, P.sc[s].Wp, a.k, a.maxh, a.maxw, fa, done);
+    float *none = nullptr;
+    return dfe_feat_matching_win64_batch(ctx, 1, &R.feat[s][0], &R.feat[s][1], P.fK, &P.sc[s].Hs, &P.sc[s].Ws, a.maxh, a.maxw, &none, 0.f, done, &fa);
+}
+
+// the lane <-> pixel cascade, coarse -> fine: one launch per scale, except that the coarsest scale is recomputed inside its child's launch
+static int ms_cascade_px(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const MsRun &R) {
+    const MsArgs &a = P.a;
+    const int nratios = a.nratios;
+    const float f16_inv = a.f16_scale != 0.f ? 1.0f / a.f16_scale : 0.f;
+    DecodeTab dt;
+    fill_decode_tab(P.mg, P.g.ncls, dt);
+    fill_cell_maps(P.g, dt);
+    const int top = nratios >= 2 ? nratios - 2 : 0;
+    int rc;
+    for (int s = P.lone_parent ? nratios - 1 : top; s >= 0; --s) {
+        if (s == 1 && P.fuse_mid) {
+            CvFineArgs mid{};
+            mid.pcasc = B.prob[2];
+            mid.pbest = B.best[2];
+            mid.casc = B.prob[1];
+            mid.best = B.best[1];
+            mid.cls_base = P.g.base[1];
+            mid.f16_scale = a.f16_scale;
+            mid.f16_inv = f16_inv;
+            bool mid_done = false;
+            rc = ms_fused_scale(ctx, P, B, R, 1, mid, &mid_done);
+            if (rc) return rc;
+            DFE_REQUIRE(ctx, mid_done, DFE_E_UNSUPPORTED, "multiscale: no plan for the fused second scale (%d x %d) although cv_finest_plan_ok said so", P.sc[1].Hp, P.sc[1].Wp);
+            continue;
+        }
+        if (s == 0 && P.fuse_fine) {
+            CvFineArgs fine{};
+            if (nratios >= 2) {
+                fine.pcasc = B.prob[1];
+                fine.pbest = B.best[1];
+            }
+            fine.idx = (long long *)a.idx;
+            fine.fy = a.flow;
+            fine.fx = P.fx;
+            fine.middle = P.middle;
+            fine.f16_scale = a.f16_scale;
+            fine.f16_inv = f16_inv;
+            for (int c = 0; c < 5 * 64; ++c) fine.dec[c] = c < P.g.ncls ? dt.v[c] : 0;
+            bool fine_done = false;
+            rc = ms_fused_scale(ctx, P, B, R, 0, fine, &fine_done);
+            if (rc) return rc;
+            if (fine_done) break;
+            // no plan for this frame: the scale-1 volume after all (fp32; rounded in place for the fp16 entry), then the px kernel
+            if (a.filt) rc = dfe_spatial_matching_dispatch(ctx, R.feat[0][0], R.feat[0][1], P.fK, a.H, a.W, a.maxh, a.maxw, B.cost[0]);
+            else rc = cv_frames_dispatch(ctx, B.p0[0], B.p1[0], a.C, P.sc[0].Hp, P.sc[0].Wp, (long long)P.sc[0].Hp * P.sc[0].Wp, a.k, a.k, a.maxh, a.maxw, B.cost[0]);
+            if (rc) return rc;
+            if (a.f16_scale != 0.f) ms_round_half(ctx, P, B, 0, 1);
+        }
+        // What depends on the run as well as on the plan.  A finest scale that arrives here although it was to be fused has just got
+        // an fp32 volume (rounded in place), whatever the other scales' are: it reads floats, and its parent's cascaded window (the
+        // parent had a launch of its own).  Else the volumes are halves where the volume launch wrote halves, and the coarsest scale is
+        // recomputed inside its child's launch (inl) unless it is the parent of a fused scale.
+        const bool fell_back = s == 0 && P.fuse_fine;
+        const bool h16 = R.half_vol && !fell_back;
+        const bool inl = nratios >= 2 && s == top && !P.lone_parent && !fell_back;
+        CascadePxArgs ca{};
+        ca.cost = B.cost[s];
+        ca.Hs = P.sc[s].Hs; ca.Ws = P.sc[s].Ws; ca.scale = s; ca.middle = P.middle; ca.cls_base = P.g.base[s];
+        ca.inv_scale = h16 ? 1.0f / a.f16_scale : 1.0f;
+        if (inl) {
+            ca.pcost = B.cost[s + 1];
+            ca.pcls_base = P.g.base[s + 1];
+        } else if (s + 1 < nratios) {
+            ca.pcasc = B.prob[s + 1];
+            ca.pbest = B.best[s + 1];
+        }
+        if (s > 0) {
+            ca.casc = B.prob[s];
+            ca.best = B.best[s];
+        } else {
+            ca.idx = (long long *)a.idx;
+            ca.fy = a.flow;
+            ca.fx = P.fx;
+        }
+        launch_cascade_px(ctx, s == 0, inl, h16, ca, dt);
+    }
+    DFE_LAUNCH_CHECK(ctx);
+    return DFE_OK;
+}
+
+// the lane <-> cell cascade (one-cell-per-lane or generic): the coarser scales' soft-mins, then cascade + arg-max + decode in one kernel
+static int ms_cascade_cell(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const MsRun &R) {
+    const MsArgs &a = P.a;
+    const int nratios = a.nratios, N = P.N;
+    CascadeGeom g = P.g;
+    SoftScales ss;
+    long long soft_max = 0;
+    for (int s = 0; s < nratios; ++s) {
+        ss.cost[s] = B.cost[s];
+        ss.prob[s] = B.prob[s];
+        ss.P[s] = (long long)P.sc[s].Hs * P.sc[s].Ws;
+        if (ss.P[s] > soft_max) soft_max = ss.P[s];
+        g.in[s] = ss.prob[s];
+        g.out_scale[s] = nullptr;
+    }
+    // one-cell-per-lane path: the scale-1 soft-min happens inside the cascade kernel (SOFT0), the coarser scales' here
+    int nsoft = nratios;
+    if (P.fast) {   // scale 1 is skipped here: the remaining scales move up one slot, so that no idle blocks are launched for it
+        g.in[0] = ss.cost[0];
+        soft_max = 0;
+        for (int s = 1; s < nratios; ++s) {
+            ss.cost[s - 1] = ss.cost[s]; ss.prob[s - 1] = ss.prob[s]; ss.P[s - 1] = ss.P[s];
+            if (ss.P[s] > soft_max) soft_max = ss.P[s];
+        }
+        nsoft = nratios - 1;
+    }
+    if (soft_max > 0 && nsoft > 0 && !R.soft_done) {   // (soft_done: the volume launch has taken the coarser scales' soft-mins)
+        hipLaunchKernelGGL(softmin_scales_kernel, dim3(grid1d(soft_max, kWaves * (N <= 64 ? 8 : 4)), nsoft), dim3(kWaves * 64), 0, ctx->stream, ss, N);
+        DFE_LAUNCH_CHECK(ctx);
+    }
+    DecodeTab dt;
+    fill_decode_tab(P.mg, g.ncls, dt);
+    if (P.fast) {
+        fill_cell_maps(g, dt);
+        hipLaunchKernelGGL(cascade_argmax_kernel<true>, cascade_fast_grid(a.H, a.W), dim3(kWaves * 64), P.lds, ctx->stream, g, P.mg, P.middle, (long long *)a.idx,
+                           (float *)nullptr, a.flow, P.fx, a.W, 0, 0, dt);
+    } else {
+        hipLaunchKernelGGL(cascade_argmax_kernel<false>, dim3(grid1d((long long)a.H * a.W, kWaves)), dim3(kWaves * 64), P.lds, ctx->stream, g, P.mg, P.middle,
+                           (long long *)a.idx, (float *)nullptr, a.flow, P.fx, a.W, 0, 0, dt);
+    }
+    DFE_LAUNCH_CHECK(ctx);
+    return DFE_OK;
+}
+
+// every launch of one call, in order
+// the scales are independent until the cascade: one launch prepares every scale's frames, one per scale builds its
+// volume, one takes every soft-min (2 + nratios launches + the cascade instead of 3 nratios + 1)
+static int ms_run(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B) {
+    MsRun R{};
+    int rc = P.a.filt ? ms_learned_front(ctx, P, B, R) : ms_prep_raw(ctx, P, B);
+    if (rc) return rc;
+    // stage "match": volumes, soft-min, cascade + fused arg-max (with learned filters it re-opens behind the per-scale filter / matching scopes)
+    DfeStageScope st(ctx, DFE_STAGE_MATCH);
+    if (!P.a.filt) {
+        rc = ms_raw_volumes(ctx, P, B, R);
+        if (rc) return rc;
+    }
+    if (P.a.f16_scale != 0.f && !R.half_vol) {
+        ms_round_half(ctx, P, B, P.s0, P.a.nratios);
+        DFE_LAUNCH_CHECK(ctx);
+    }
+    return P.px_path ? ms_cascade_px(ctx, P, B, R) : ms_cascade_cell(ctx, P, B, R);
+}
+
+// Plan, allocate, look up the graph, run the stages.  The graph key holds the buffers and the shape, not the options (DFE_FINE_FUSE,
+// DFE_MID_FUSE, ... / the cost-volume mode): a replay keeps the plan it was captured with until a buffer or the shape changes.
 static int multiscale_flow_pair(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw,
                                 const int *ratios, int nratios, float *flow, int64_t *idx, float f16_scale, const MsFilter *filt = nullptr,
                                 float u8_scale = 0.f) {
-    DFE_REQUIRE(ctx, I0 && I1 && (flow || idx), DFE_E_ARG, "dfe_multiscale_flow_pair_f32: NULL tensor");
-    DFE_REQUIRE(ctx, C > 0 && k > 0 && maxh > 0 && maxw > 0, DFE_E_ARG, "dfe_multiscale_flow_pair_f32: bad size");
-    CascadeGeom g;
-    int rc = fill_cascade(ctx, g, ratios, nratios, maxh, maxw);
+    const MsArgs a{I0, I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, f16_scale, filt, u8_scale};
+    MsPlan P;
+    int rc = ms_plan(ctx, a, &P);
     if (rc) return rc;
-    const int N = maxh * maxw;
-    // receptive field of the patch filter: k x k raw patches, or hKernel = sum kH - (nlayers - 1) of the learned stack (opticalflow.lua:154-171)
-    int hk = k, wk = k, maxplanes = C;
-    if (filt) {
-        for (int v = 0; v < (filt->share ? 1 : nratios); ++v) {
-            int h = 1, w = 1, nin = C;
-            for (int l = 0; l < filt->nlayers; ++l) {
-                const dfe_filter_layer &L = filt->layers[v * filt->nlayers + l];
-                DFE_REQUIRE(ctx, L.weight && L.nIn > 0 && L.nOut > 0 && L.kH > 0 && L.kW > 0, DFE_E_ARG, "dfe_multiscale_flow_pair_filtered_f32: layer %d: bad description", l);
-                DFE_REQUIRE(ctx, L.conn ? L.nIn <= nin : L.nIn == nin, DFE_E_SHAPE, "dfe_multiscale_flow_pair_filtered_f32: layer %d reads %d planes, the layer before it makes %d", l, L.nIn, nin);
-                h += L.kH - 1; w += L.kW - 1; nin = L.nOut;
-                if (L.nOut > maxplanes) maxplanes = L.nOut;
-            }
-            DFE_REQUIRE(ctx, v == 0 || (h == hk && w == wk), DFE_E_SHAPE, "dfe_multiscale_flow_pair_filtered_f32: the scales' filter stacks have different receptive fields");
-            hk = h; wk = w;
-        }
-    }
-    const int hp = maxh - 1 + hk - 1, wp = maxw - 1 + wk - 1;   // hPatch2-1 (opticalflow_model_multiscale.lua:136-141)
-    const int pt = hp / 2, pl = wp / 2;
-    size_t off_p[DFE_MAX_RATIOS], off_v[DFE_MAX_RATIOS], off_q[DFE_MAX_RATIOS], off_b[DFE_MAX_RATIOS], off_f[DFE_MAX_RATIOS], fbuf[DFE_MAX_RATIOS], total = 0;
-    for (int s = 0; s < nratios; ++s) {
-        const int r = ratios[s];
-        DFE_REQUIRE(ctx, H % r == 0 && W % r == 0, DFE_E_SHAPE,
-                    "dfe_multiscale_flow_pair_f32: frame %dx%d is not a multiple of ratio %d (opticalflow_model_multiscale.lua:238-243)", H, W, r);
-        const size_t np = (size_t)C * (H / r + hp) * (W / r + wp), nv = (size_t)(H / r) * (W / r) * N;
-        // learned filters: four feature buffers per scale (ping-pong per frame), each the largest layer output
-        fbuf[s] = filt ? ((size_t)maxplanes * (H / r + hp) * (W / r + wp) * sizeof(float) + 255) / 256 * 256 : 0;
-        off_f[s] = total; total += 4 * fbuf[s];
-        off_p[s] = total; total += (2 * np * sizeof(float) + 255) / 256 * 256;
-        off_v[s] = total; total += (nv * sizeof(float) + 255) / 256 * 256;
-        off_q[s] = total; total += (nv * sizeof(float) + 255) / 256 * 256;
-        off_b[s] = total; total += ((size_t)(H / r) * (W / r) * sizeof(float2) + 255) / 256 * 256;
-    }
-    // the per-scale cost volumes below use the same arena for their own temporaries only through cv_frames_dispatch, which
+    // the per-scale cost volumes use the same arena for their own temporaries only through cv_frames_dispatch, which
     // needs none; one allocation up front keeps every stage's buffers alive until the cascade has read them
     void *scr = nullptr;
-    rc = dfe_scratch(ctx, total, &scr, filt != nullptr);   // (learned filters: the convolutions' arena, see dfe_scratch)
+    rc = dfe_scratch(ctx, P.total, &scr, filt != nullptr);   // (learned filters: the convolutions' arena, see dfe_scratch)
     if (rc) return rc;
     // the same call again (same buffers, shapes and arena): replay its launches as a graph
     struct { const void *I0, *I1, *flow, *idx, *scr; int C, H, W, k, maxh, maxw, nratios, ratios[DFE_MAX_RATIOS]; float f16, u8; } gkey;
@@ -1059,330 +1508,10 @@ static int multiscale_flow_pair(dfe_ctx *ctx, const float *I0, const float *I1, 
         ctx->last_kernel = "multiscale graph";
         return DFE_OK;
     }
-    auto launch_all = [&]() -> int {
-    MultiGeom mg;
-    mg.maxh = maxh; mg.maxw = maxw; mg.nratios = nratios;
-    // the scales are independent until the cascade: one launch prepares every scale's frames, one per scale builds its
-    // volume, one takes every soft-min (2 + nratios launches + the cascade instead of 3 nratios + 1)
-    PrepScales ps;
-    SoftScales ss;
-    long long prep_max = 0, soft_max = 0;
-    for (int s = 0; s < nratios; ++s) {
-        const int r = ratios[s], Hs = H / r, Ws = W / r, Hp = Hs + hp, Wp = Ws + wp;
-        ps.r[s] = r; ps.Hp[s] = Hp; ps.Wp[s] = Wp;
-        ps.p0[s] = (float *)((char *)scr + off_p[s]);
-        ps.p1[s] = ps.p0[s] + (size_t)C * Hp * Wp;
-        ss.cost[s] = (float *)((char *)scr + off_v[s]);
-        ss.prob[s] = (float *)((char *)scr + off_q[s]);
-        ss.P[s] = (long long)Hs * Ws;
-        DFE_REQUIRE(ctx, 2ll * C * Hp * Wp < (1ll << 31), DFE_E_SHAPE, "dfe_multiscale_flow_pair_f32: frame too large");
-        if (2ll * C * Hp * Wp > prep_max) prep_max = 2ll * C * Hp * Wp;
-        if (ss.P[s] > soft_max) soft_max = ss.P[s];
-        g.in[s] = ss.prob[s];
-        g.out_scale[s] = nullptr;
-        mg.ratios[s] = r;
-        mg.d[s] = g.d[s];
-    }
-    const bool fast = N <= 64 && nratios <= 5;   // one-cell-per-lane path of the cascade kernel
-    // lane <-> pixel path (cascade_px_kernel): 8 x 8 windows, ratios 1, 2, 4, ...; DFE_CASCADE_PX=0 keeps the lane <-> cell kernels
-    bool px_path = fast && maxh == 8 && maxw == 8;
-    for (int s = 0; s < nratios; ++s)
-        if (ratios[s] != (1 << s) || (s > 0 && g.d[s] != 2)) px_path = false;   // (ring width 2: the kernel's compile-time class order)
-    px_path = px_path && ctx->opt[DFE_OPT_CASCADE_PX] != 0;
-    // raw patches, 3 channels, 7 x 7, on the lane <-> pixel path: the finest scale is fused into its volume kernel (no volume)
-    // -- where it pays: the fused kernel is VALU-bound (three 64-lane reductions per pixel), the volume it saves is HBM traffic that the
-    // small frames hide behind the coarse scales' launches.  Measured, volume path -> fused: VGA 0.076 -> 0.099 ms, 720p 0.213 ->
-    // 0.185, 1080p 0.430 -> 0.366, 4K 1.94 -> 1.40; fp16 volumes (half the bytes to save): 1080p 0.344 -> 0.368, 4K 1.48 -> 1.32.
-    // DFE_FINE_FUSE=0 / 1 forces the choice.
-    // Learned filters: the same epilogue behind the one-chunk feature matcher (feat_matching_win64_fine_kernel), where every scale's
-    // stack ends in the same number of planes (<= 16).
-    int fK = 0;
-    bool fine_shape = C == 3 && k == 7;
-    if (filt) {
-        fK = filt->layers[filt->nlayers - 1].nOut;
-        fine_shape = dfe_feat_matching_win64_ok(ctx, fK, maxh, maxw);   // the launcher's own conditions (cv_mode, fm64, K, LDS)
-        for (int s = 1; s < nratios && !filt->share; ++s) fine_shape = fine_shape && filt->layers[s * filt->nlayers + filt->nlayers - 1].nOut == fK;
-    }
-    // (learned filters, volume path -> fused: VGA 0.193 -> 0.183 ms, 1080p 1.064 -> 0.912: the matcher's launch is long enough at VGA already)
-    bool try_fine = px_path && fine_shape && (long long)H * W >= (filt ? 250000ll : f16_scale != 0.f ? 3000000ll : 600000ll);
-    if (ctx->opt[DFE_OPT_FINE_FUSE] >= 0) try_fine = px_path && fine_shape && ctx->opt[DFE_OPT_FINE_FUSE] != 0;
-    // the second scale the same way (its volume, 21 % of the rest, is otherwise written by the volume kernel and read back by its
-    // cascade launch): wherever the finest scale is fused and a coarser scale exists above it.  DFE_MID_FUSE=0 / 1 forces the choice.
-    // Measured, finest scale fused -> both: 1080p 0.363 -> 0.346 ms, 4K 1.40 -> 1.29; 720p 0.179 -> 0.205 (230 k pixels: one partial round
-    // of blocks, latency-bound); fp16 volumes (half the bytes to save) 4K 1.315 -> 1.320.
-    const bool mid_shape = nratios >= 3 && (filt ? (H / ratios[1] >= 16 && W / ratios[1] >= 8 && ((H / ratios[1]) | (W / ratios[1])) % 2 == 0)
-                                                 : cv_finest_plan_ok(ctx, H / ratios[1] + k - 1 + maxh - 1, W / ratios[1] + k - 1 + maxw - 1, maxh, maxw));
-    bool try_mid = try_fine && f16_scale == 0.f && (long long)H * W >= 1500000ll && mid_shape;
-    if (ctx->opt[DFE_OPT_MID_FUSE] >= 0) try_mid = try_fine && ctx->opt[DFE_OPT_MID_FUSE] != 0 && mid_shape;
-    const int s0 = try_mid ? 2 : try_fine ? 1 : 0;      // the first scale whose volume is materialised
-    if (!filt) {
-        DfeStageScope st(ctx, DFE_STAGE_FILTER);
-        bool pow2 = nratios <= 5;
-        for (int s = 0; s < nratios; ++s) pow2 = pow2 && (ratios[s] == 1 || ratios[s] == 2 || ratios[s] == 4 || ratios[s] == 8 || ratios[s] == 16);
-        // (large frames only: at VGA the per-scale kernel's 8.8 us are all latency and the tile kernel's sequential r x r sums are
-        //  slower -- 0.082 against 0.076 ms per pair; 1080p 0.451 -> 0.430 ms, 4K five levels 1.69 -> 1.48 ms)
-        // (tried: the finest scale's padded frames made on a second stream next to the coarse scales' chain, forked here and joined in
-        //  front of the fused kernel, which alone reads them -- 720p 0.178 -> 0.190 ms, 1080p 0.347 -> 0.348, 4K 1.27 -> 1.31: the
-        //  frames are read twice and the cross-stream waits cost more than the overlap gives)
-        if (pow2 && (long long)H * W >= 1500000 && ctx->opt[DFE_OPT_PREP_TILES] != 0) {       // every scale from one read of the frames
-            PrepTile pq;
-            pq.ns = nratios;
-            for (int s = 0; s < nratios; ++s) { pq.r[s] = ps.r[s]; pq.Hp[s] = ps.Hp[s]; pq.Wp[s] = ps.Wp[s]; pq.p[0][s] = ps.p0[s]; pq.p[1][s] = ps.p1[s]; }
-            if (u8_scale > 0.f)
-                hipLaunchKernelGGL(prep_tiles_kernel<unsigned char>, dim3(dfe_cdiv(W, PT), dfe_cdiv(H, PT), 2 * C), dim3(256), 0, ctx->stream,
-                                   (const unsigned char *)I0, (const unsigned char *)I1, C, H, W, pl, pt, pq, u8_scale);
-            else
-                hipLaunchKernelGGL(prep_tiles_kernel<float>, dim3(dfe_cdiv(W, PT), dfe_cdiv(H, PT), 2 * C), dim3(256), 0, ctx->stream, I0, I1, C, H, W, pl, pt, pq, 0.f);
-        } else {
-            if (u8_scale > 0.f)
-                hipLaunchKernelGGL(prep_scales_kernel<unsigned char>, dim3(grid1d(prep_max, 256 * PREP_EPT), nratios), dim3(256), 0, ctx->stream,
-                                   (const unsigned char *)I0, (const unsigned char *)I1, C, H, W, pl, pt, ps, u8_scale);
-            else
-                hipLaunchKernelGGL(prep_scales_kernel<float>, dim3(grid1d(prep_max, 256 * PREP_EPT), nratios), dim3(256), 0, ctx->stream, I0, I1, C, H, W, pl, pt, ps, 0.f);
-        }
-        DFE_LAUNCH_CHECK(ctx);
-    }
-    bool merged = false, soft_done = false, half_vol = false;
-    const float *feat0[2] = {nullptr, nullptr}, *feat1[2] = {nullptr, nullptr};      // learned filters: the two finest scales' feature planes (frame 0, frame 1)
-    // stage "match": volumes, soft-min, cascade + fused arg-max (with learned filters it opens behind the per-scale filter / matching scopes)
-    std::unique_ptr<DfeStageScope> match_rest;
-    if (!filt) match_rest.reset(new DfeStageScope(ctx, DFE_STAGE_MATCH));
-    if (filt) {
-        // learned filters (getModelMultiscale's filter1 / filter2, opticalflow_model_multiscale.lua:196-211): frame 0 is cropped by
-        // the search window BEFORE the filter (its zero padding shrinks by floor / ceil((maxh-1)/2)), both padded frames go
-        // through the stack, nn.SpatialMatching(maxh, maxw) runs on the K-plane features
-        const int ct = (maxh - 1) / 2, cl = (maxw - 1) / 2;
-        PrepFrames pf;
-        long long pmax = 0;
-        for (int s = 0; s < nratios; ++s) {
-            const int r = ratios[s], Hs = H / r, Ws = W / r;
-            pf.img[2 * s] = I0; pf.out[2 * s] = ps.p0[s]; pf.r[2 * s] = r;
-            pf.pl[2 * s] = pl - cl; pf.pt[2 * s] = pt - ct; pf.Hp[2 * s] = Hs + hk - 1; pf.Wp[2 * s] = Ws + wk - 1;
-            pf.img[2 * s + 1] = I1; pf.out[2 * s + 1] = ps.p1[s]; pf.r[2 * s + 1] = r;
-            pf.pl[2 * s + 1] = pl; pf.pt[2 * s + 1] = pt; pf.Hp[2 * s + 1] = Hs + hp; pf.Wp[2 * s + 1] = Ws + wp;
-            if ((long long)C * (Hs + hp) * (Ws + wp) > pmax) pmax = (long long)C * (Hs + hp) * (Ws + wp);
-        }
-        {
-            DfeStageScope st(ctx, DFE_STAGE_FILTER);
-            hipLaunchKernelGGL(prep_frames_kernel, dim3(grid1d(pmax, 256 * 8), 2 * nratios), dim3(256), 0, ctx->stream, C, H, W, pf);
-        }
-        DFE_LAUNCH_CHECK(ctx);
-        // layer by layer, both frames of every scale in ONE launch (18 launches of a few microseconds each otherwise)
-        const float *cur[2 * DFE_MAX_RATIOS];
-        int ch[2 * DFE_MAX_RATIOS], cw[2 * DFE_MAX_RATIOS];
-        for (int e = 0; e < 2 * nratios; ++e) { cur[e] = pf.out[e]; ch[e] = pf.Hp[e]; cw[e] = pf.Wp[e]; }
-        for (int l = 0; l < filt->nlayers; ++l) {
-            DfeStageScope st(ctx, DFE_STAGE_FILTER);
-            const dfe_filter_layer *Lp[2 * DFE_MAX_RATIOS];
-            float *dst[2 * DFE_MAX_RATIOS];
-            for (int e = 0; e < 2 * nratios; ++e) {
-                const int s = e >> 1, f = e & 1;
-                Lp[e] = filt->layers + (filt->share ? 0 : s) * filt->nlayers + l;
-                dst[e] = (float *)((char *)scr + off_f[s] + (size_t)(2 * f + (l & 1)) * fbuf[s]);
-            }
-            rc = dfe_filter_layer_forward_batch(ctx, 2 * nratios, cur, Lp, ch, cw, dst);
-            if (rc) return rc;
-            for (int e = 0; e < 2 * nratios; ++e) { cur[e] = dst[e]; ch[e] -= Lp[e]->kH - 1; cw[e] -= Lp[e]->kW - 1; }
-        }
-        {
-            // every scale's nn.SpatialMatching in ONE launch where the one-chunk matcher applies (8 x 8 windows) -- with fp16 volumes
-            // written as halves directly when the lane <-> pixel cascade will read them; else scale by scale
-            DfeStageScope st(ctx, DFE_STAGE_MATCH);
-            const int K = filt->layers[filt->nlayers - 1].nOut;
-            bool same_k = true;
-            for (int s = 1; s < nratios && !filt->share; ++s) same_k = same_k && filt->layers[s * filt->nlayers + filt->nlayers - 1].nOut == K;
-            const float *m1[DFE_MAX_RATIOS], *m2[DFE_MAX_RATIOS];
-            float *mo[DFE_MAX_RATIOS];
-            int mh[DFE_MAX_RATIOS], mw[DFE_MAX_RATIOS];
-            for (int s = 0; s < nratios; ++s) { m1[s] = cur[2 * s]; m2[s] = cur[2 * s + 1]; mo[s] = (float *)ss.cost[s]; mh[s] = H / ratios[s]; mw[s] = W / ratios[s]; }
-            feat0[0] = m1[0]; feat0[1] = m2[0];
-            if (nratios > 1) { feat1[0] = m1[1]; feat1[1] = m2[1]; }
-            bool done = nratios - s0 < 1;       // (s0 = 1: the finest scale's matcher runs last, with the fused epilogue -- below)
-            if (same_k && !done) {
-                rc = dfe_feat_matching_win64_batch(ctx, nratios - s0, m1 + s0, m2 + s0, K, mh + s0, mw + s0, maxh, maxw, mo + s0, (f16_scale != 0.f && px_path) ? f16_scale : 0.f, &done);
-                if (rc) return rc;
-                half_vol = done && f16_scale != 0.f && px_path;
-            }
-            for (int s = s0; s < nratios && !done; ++s) {
-                const dfe_filter_layer *Ls = filt->layers + (filt->share ? 0 : s) * filt->nlayers;
-                rc = dfe_spatial_matching_dispatch(ctx, m1[s], m2[s], Ls[filt->nlayers - 1].nOut, mh[s], mw[s], maxh, maxw, mo[s]);
-                if (rc) return rc;
-            }
-        }
-        merged = true;
-        match_rest.reset(new DfeStageScope(ctx, DFE_STAGE_MATCH));
-    } else {
-        // one launch for every scale's volume; on the fast path the coarser scales leave it as soft-min probabilities already
-        // (their blocks run next to the scale-1 blocks that dominate the launch), scale 1 as costs for the cascade's SOFT0
-        // (s0 = 1: the finest scale has NO volume -- its task rows are consumed inside the volume kernel, cv_frames_finest_fused below)
-        const float *f0[DFE_MAX_RATIOS], *f1[DFE_MAX_RATIOS];
-        float *vo[DFE_MAX_RATIOS], *pr[DFE_MAX_RATIOS];
-        int vh[DFE_MAX_RATIOS], vw[DFE_MAX_RATIOS];
-        const int nv = nratios - s0;
-        const int nq_hint = (try_fine && (long long)H * W < 4000000ll) ? 3 : 0;
-        for (int s = s0; s < nratios; ++s) {
-            f0[s - s0] = ps.p0[s]; f1[s - s0] = ps.p1[s]; vo[s - s0] = (float *)ss.cost[s]; vh[s - s0] = ps.Hp[s]; vw[s - s0] = ps.Wp[s];
-            pr[s - s0] = (fast && s > 0 && !px_path) ? ss.prob[s] : nullptr;
-        }
-        // fp16 volumes: written as halves by the volume kernel itself where the lane <-> pixel cascade will read them (8 x 8
-        // windows, C = 3, k = 7); any other shape builds fp32 volumes and rounds them to half precision in place -- same values
-        if (f16_scale != 0.f && px_path && nv >= 1) {
-            rc = cv_frames_dispatch_multi(ctx, nv, f0, f1, C, vh, vw, k, maxh, maxw, vo, nullptr, &merged, &soft_done, f16_scale, nq_hint);
-            if (rc) return rc;
-            half_vol = merged;
-        }
-        if (!merged && nv >= 1) {
-            rc = cv_frames_dispatch_multi(ctx, nv, f0, f1, C, vh, vw, k, maxh, maxw, vo, f16_scale != 0.f ? nullptr : pr, &merged, &soft_done, 0.f, nq_hint);
-            if (rc) return rc;
-        }
-    }
-    for (int s = s0; s < nratios && !merged; ++s) {
-        rc = cv_frames_dispatch(ctx, ps.p0[s], ps.p1[s], C, ps.Hp[s], ps.Wp[s], (long long)ps.Hp[s] * ps.Wp[s], k, k, maxh, maxw,
-                                (float *)ss.cost[s]);
-        if (rc) return rc;
-    }
-    if (f16_scale != 0.f && !half_vol) {
-        for (int s = s0; s < nratios; ++s) {
-            const long long n = ss.P[s] * N;
-            hipLaunchKernelGGL(round_half_kernel, dim3(grid1d(n, 256)), dim3(256), 0, ctx->stream, (float *)ss.cost[s], n, f16_scale, 1.0f / f16_scale);
-        }
-        DFE_LAUNCH_CHECK(ctx);
-    }
-    const int middle = ((maxh + 1) / 2 - 1) * maxw + (maxw + 1) / 2;   // yx2xMulti(0, 0)
-    if (px_path) {
-        DecodeTab dt;
-        fill_decode_tab(mg, g.ncls, dt);
-        fill_cell_maps(g, dt);
-        // coarse -> fine: one launch per scale, except that the coarsest scale is recomputed inside its child's launch
-        const int top = nratios >= 2 ? nratios - 2 : 0;
-        bool fine_done = false;
-        // where the coarsest scale is the parent of a fused scale it needs a launch of its own (it cannot be recomputed inside its child's)
-        const bool lone_parent = (try_mid && nratios == 3) || (try_fine && !try_mid && nratios == 2);
-        for (int s = lone_parent ? nratios - 1 : top; s >= 0; --s) {
-            const int r = ratios[s];
-            if (s == 1 && try_mid) {
-                CvFineArgs mid{};
-                mid.pcasc = (const float *)((char *)scr + off_q[2]);
-                mid.pbest = (const float2 *)((char *)scr + off_b[2]);
-                mid.casc = (float *)((char *)scr + off_q[1]);
-                mid.best = (float2 *)((char *)scr + off_b[1]);
-                mid.cls_base = g.base[1];
-                mid.f16_scale = f16_scale;
-                mid.f16_inv = f16_scale != 0.f ? 1.0f / f16_scale : 0.f;
-                bool mid_done = false;
-                if (filt) {
-                    float *none = nullptr;
-                    const int h1 = H / ratios[1], w1 = W / ratios[1];
-                    rc = dfe_feat_matching_win64_batch(ctx, 1, &feat1[0], &feat1[1], fK, &h1, &w1, maxh, maxw, &none, 0.f, &mid_done, &mid);
-                } else {
-                    rc = cv_frames_finest_fused(ctx, ps.p0[1], ps.p1[1], C, ps.Hp[1], ps.Wp[1], k, maxh, maxw, mid, &mid_done);
-                }
-                if (rc) return rc;
-                DFE_REQUIRE(ctx, mid_done, DFE_E_UNSUPPORTED, "multiscale: no plan for the fused second scale (%d x %d) although cv_finest_plan_ok said so", ps.Hp[1], ps.Wp[1]);
-                continue;
-            }
-            if (s == 0 && try_fine) {
-                CvFineArgs fine{};
-                if (nratios >= 2) {
-                    fine.pcasc = (const float *)((char *)scr + off_q[1]);
-                    fine.pbest = (const float2 *)((char *)scr + off_b[1]);
-                }
-                fine.idx = (long long *)idx;
-                fine.fy = flow;
-                fine.fx = flow ? flow + (size_t)H * W : nullptr;
-                fine.middle = middle;
-                fine.f16_scale = f16_scale;
-                fine.f16_inv = f16_scale != 0.f ? 1.0f / f16_scale : 0.f;
-                for (int c = 0; c < 5 * 64; ++c) fine.dec[c] = c < g.ncls ? dt.v[c] : 0;
-                if (filt) {
-                    float *none = nullptr;
-                    rc = dfe_feat_matching_win64_batch(ctx, 1, &feat0[0], &feat0[1], fK, &H, &W, maxh, maxw, &none, 0.f, &fine_done, &fine);
-                } else {
-                    rc = cv_frames_finest_fused(ctx, ps.p0[0], ps.p1[0], C, ps.Hp[0], ps.Wp[0], k, maxh, maxw, fine, &fine_done);
-                }
-                if (rc) return rc;
-                if (fine_done) break;
-                // no plan for this frame: the scale-1 volume after all (fp32; rounded in place for the fp16 entry), then the px kernel
-                if (filt) rc = dfe_spatial_matching_dispatch(ctx, feat0[0], feat0[1], fK, H, W, maxh, maxw, (float *)ss.cost[0]);
-                else rc = cv_frames_dispatch(ctx, ps.p0[0], ps.p1[0], C, ps.Hp[0], ps.Wp[0], (long long)ps.Hp[0] * ps.Wp[0], k, k, maxh, maxw, (float *)ss.cost[0]);
-                if (rc) return rc;
-                if (f16_scale != 0.f) {
-                    const long long n = ss.P[0] * N;
-                    hipLaunchKernelGGL(round_half_kernel, dim3(grid1d(n, 256)), dim3(256), 0, ctx->stream, (float *)ss.cost[0], n, f16_scale, 1.0f / f16_scale);
-                }
-            }
-            CascadePxArgs a{};
-            a.cost = (const float *)ss.cost[s];
-            a.Hs = H / r; a.Ws = W / r; a.scale = s; a.middle = middle; a.cls_base = g.base[s];
-            a.inv_scale = (half_vol && !(s == 0 && try_fine)) ? 1.0f / f16_scale : 1.0f;
-            const bool inl = nratios >= 2 && s == top && !lone_parent && !(s == 0 && try_fine);
-            if (inl) {
-                a.pcost = (const float *)ss.cost[s + 1];
-                a.pcls_base = g.base[s + 1];
-            } else if (s + 1 < nratios) {
-                a.pcasc = (const float *)((char *)scr + off_q[s + 1]);
-                a.pbest = (const float2 *)((char *)scr + off_b[s + 1]);
-            }
-            const int blocks = (int)(((long long)a.Hs * a.Ws + 255) / 256);
-            if (s > 0) {
-                a.casc = (float *)((char *)scr + off_q[s]);
-                a.best = (float2 *)((char *)scr + off_b[s]);
-                if (half_vol) {
-                    if (inl) hipLaunchKernelGGL((cascade_px_kernel<false, true, true>), dim3(blocks), dim3(256), 0, ctx->stream, a, dt);
-                    else hipLaunchKernelGGL((cascade_px_kernel<false, false, true>), dim3(blocks), dim3(256), 0, ctx->stream, a, dt);
-                } else if (inl) hipLaunchKernelGGL((cascade_px_kernel<false, true>), dim3(blocks), dim3(256), 0, ctx->stream, a, dt);
-                else hipLaunchKernelGGL((cascade_px_kernel<false, false>), dim3(blocks), dim3(256), 0, ctx->stream, a, dt);
-            } else {
-                a.idx = (long long *)idx;
-                a.fy = flow;
-                a.fx = flow ? flow + (size_t)H * W : nullptr;
-                if (half_vol && !try_fine) {
-                    if (inl) hipLaunchKernelGGL((cascade_px_kernel<true, true, true>), dim3(blocks), dim3(256), 0, ctx->stream, a, dt);
-                    else hipLaunchKernelGGL((cascade_px_kernel<true, false, true>), dim3(blocks), dim3(256), 0, ctx->stream, a, dt);
-                } else if (inl) hipLaunchKernelGGL((cascade_px_kernel<true, true>), dim3(blocks), dim3(256), 0, ctx->stream, a, dt);
-                else hipLaunchKernelGGL((cascade_px_kernel<true, false>), dim3(blocks), dim3(256), 0, ctx->stream, a, dt);
-            }
-        }
-        DFE_LAUNCH_CHECK(ctx);
-        (void)fine_done;
-        return DFE_OK;
-    }
-    // one-cell-per-lane path: the scale-1 soft-min happens inside the cascade kernel (SOFT0), the coarser scales' here
-    int nsoft = nratios;
-    if (fast) {   // scale 1 is skipped here: the remaining scales move up one slot, so that no idle blocks are launched for it
-        g.in[0] = ss.cost[0];
-        soft_max = 0;
-        for (int s = 1; s < nratios; ++s) {
-            ss.cost[s - 1] = ss.cost[s]; ss.prob[s - 1] = ss.prob[s]; ss.P[s - 1] = ss.P[s];
-            if (ss.P[s] > soft_max) soft_max = ss.P[s];
-        }
-        nsoft = nratios - 1;
-    }
-    if (soft_max > 0 && nsoft > 0 && !soft_done) {   // (soft_done: the volume launch has taken the coarser scales' soft-mins)
-        hipLaunchKernelGGL(softmin_scales_kernel, dim3(grid1d(soft_max, kWaves * (N <= 64 ? 8 : 4)), nsoft), dim3(kWaves * 64), 0, ctx->stream, ss, N);
-        DFE_LAUNCH_CHECK(ctx);
-    }
-    g.H = H; g.W = W;
-    size_t lds = (size_t)kWaves * 2 * N * sizeof(float);
-    DFE_REQUIRE(ctx, lds <= 64 * 1024, DFE_E_UNSUPPORTED, "dfe_multiscale_flow_pair_f32: window %dx%d too large", maxh, maxw);
-    if (lds < (size_t)g.ncls * sizeof(int2)) lds = (size_t)g.ncls * sizeof(int2);
-    dim3 grid(grid1d((long long)H * W, kWaves));
-    DecodeTab dt;
-    fill_decode_tab(mg, g.ncls, dt);
-    if (g.maxh * g.maxw <= 64 && g.nratios <= 5) fill_cell_maps(g, dt);
-    if (fast) {
-        grid = cascade_fast_grid(H, W);
-        hipLaunchKernelGGL(cascade_argmax_kernel<true>, grid, dim3(kWaves * 64), lds, ctx->stream, g, mg, middle, (long long *)idx, (float *)nullptr,
-                           flow, flow ? flow + (size_t)H * W : nullptr, W, 0, 0, dt);
-    } else {
-        hipLaunchKernelGGL(cascade_argmax_kernel<false>, grid, dim3(kWaves * 64), lds, ctx->stream, g, mg, middle, (long long *)idx, (float *)nullptr,
-                           flow, flow ? flow + (size_t)H * W : nullptr, W, 0, 0, dt);
-    }
-    DFE_LAUNCH_CHECK(ctx);
-    return DFE_OK;
-    };
-    if (gmode == 1) return dfe_graph_finish(ctx, ctx->ms_graph, launch_all());
-    return launch_all();
+    MsBufs B;
+    ms_bufs(P, scr, &B);
+    rc = ms_run(ctx, P, B);
+    return gmode == 1 ? dfe_graph_finish(ctx, ctx->ms_graph, rc) : rc;
 }
 
 int dfe_multiscale_flow_pair_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw,
