@@ -219,6 +219,16 @@ extern __shared__ __attribute__((aligned(16))) char dfe_smem[];
 #else
 #define DFE_MARK(name) do { } while (0)
 #endif
+// -DDFE_TIMELINE=1 (tools/timeline.py, no product build): the volume-free sweep stamps the shader clock at the same boundaries -- lane 0 of
+// every wave, rows DFE_TL_R0 .. + DFE_TL_NR of the first piece of blocks 0 and 1, into spare LDS behind the records; the two blocks copy their
+// stamps into the head of the fallback plane at the end of the kernel and the host writes them to the file $DFE_TIMELINE_OUT names.  Every
+// stamp waits for the wave's outstanding LDS traffic (the clock arrives through lgkmcnt), so phases end a little later than in the product.
+#if defined(DFE_TIMELINE) && DFE_TIMELINE
+#define DFE_TL 1
+#else
+#define DFE_TL 0
+#endif
+constexpr int DFE_TL_R0 = 24, DFE_TL_NR = 32, DFE_TL_NS = 8, DFE_TL_WORDS = DFE_TL_NR * 16 * DFE_TL_NS;
 // cache-policy bits of the copy-out stores.  The volume streams out and nothing re-reads it from L2: with the non-temporal
 // hint the build measures 268 instead of 285 us at VGA and the step's finalize pass finds its planes still cached
 // (step -4 %); " sc1", " sc0 sc1" and combinations with " nt" measure the same as " nt" alone.  (Whole lines only: on the
@@ -856,7 +866,15 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
     // (Which SIMD carries what, wave w on SIMD w % 4: every SIMD has one quarter-task + scan wave (0 .. 3) and one plain scan wave (4 .. 7);
     //  SIMD 3 also has wave 15 with the mini task and the ring refill, ~93 vector instructions a row on top of its main task
     //  (tools/isa_regions.py).  Round 4 tried pixel 7's scan on wave 8 (SIMD 0) with wave 7 copying instead: no difference, r04_d.)
-    constexpr int QW0 = 0;                       // first wave with a quarter task (on the copy waves, 8..11, instead: 265 against 258 us)
+    // first wave with a quarter task (on the copy waves, 8..11, instead: 265 against 258 us; in the volume-free sweep, where those waves
+    // idle behind the barrier, 246 against 230 us: a quarter task there runs beside the second half of its SIMD's main tasks)
+    constexpr int QW0 = 0;
+    // NOVOL: a scan wave scans row r-1 at the END of its row r (main task -> quarter task -> scan), not behind the barrier in front of its
+    // main task.  In front, waves 0..7 began their main task when waves 8..14 were half way through theirs -- two shifts of two waves per
+    // SIMD (s_memtime stamps, profiles/r07_timeline_vga.txt); now all sixteen start at the barrier and the scan, a latency-bound chain,
+    // fills the end of the row beside the quarter tasks, the mini task and the refill.  VGA step 0.2293 -> 0.2199 ms, same call (round 7).
+    // (The volume kernels keep the scan in front: their waves 8..14 copy the image out behind the barrier.)
+    constexpr bool SCAN_BEHIND = NOVOL;
     static_assert(NE <= 16, "row_newbcast reaches 16 positions");
     static_assert(TX % NQW == 0, "whole columns per quarter task");
     // 33 x 33 instantiation: the LDS geometry is a compile-time constant (rowimg_plan / launch_cv_rowimg_sweep compute the same
@@ -891,6 +909,7 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
     // filled a row step ahead, so the K-1 warm-up rows are paid once per piece instead of once per TY rows.
     // (static tiles: p.seg_rows is the tile height, a run-time value -- one instantiation serves every height)
     int pos = 0, pend = 1, bx = 0, by = 0;
+    [[maybe_unused]] bool tl_first = true;
     if constexpr (SWEEP) {
         const int ncols = (p.Wo + TX - 1) / TX;
         pos = sweep_cut(blockIdx.x, gridDim.x, ncols, p.Ho, p.sw_ovh, p.sw_min);
@@ -1095,6 +1114,21 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
     // (cells 9 (64 + l) ..); both units' reads in flight together, ONE wave minimum for both, the first index from the lower
     // unit if any of its lanes attains the minimum.  Plane 1 of fa.part gets +inf (finalize keeps the smaller of the two).
     float *recbuf = stage + 2 * g_stage_len;       // ROLES: [2][DFE_REC] the tile row's record, double-buffered like the images
+    constexpr bool TL = NOVOL && DFE_TL;
+    unsigned *tl = reinterpret_cast<unsigned *>(recbuf + 2 * DFE_REC);
+    const bool tl_piece = TL && blockIdx.x < 2 && tl_first;
+    auto stamp = [&](int r, int i) {
+        if constexpr (TL) {
+            if (tl_piece && r >= DFE_TL_R0 && r < DFE_TL_R0 + DFE_TL_NR) {
+                const unsigned t = (unsigned)__builtin_amdgcn_s_memtime();
+                if (lane_id_fresh() == 0) tl[((r - DFE_TL_R0) * NW + wave) * DFE_TL_NS + i] = t;
+            }
+        }
+    };
+    if constexpr (TL) {
+        if (tl_piece)
+            for (int i = tid; i < DFE_TL_WORDS; i += NW * 64) tl[i] = 0u;   // (ordered by the first row barrier: the stamps start at row DFE_TL_R0)
+    }
     // NOVOL, rare: the first M cells of the pixel's run (px, in the row image) above the threshold, in cell order, into the pixel's entry
     // of the fallback plane, zero-padded: 64 cells a step, the hits ranked by a ballot, the count wave-uniform, done at M hits.
     // (Behind the scan, one live value per lane: with a prefix sum over the scan's two 9-cell units, still in registers, the sweep spilled.)
@@ -1341,12 +1375,27 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
             // (order of a wave's tasks within a row: the latency-bound extra tasks in front of the main task -- so that they run
             //  while the SIMD's other waves are busy, instead of alone behind them -- measured +-1 %)
             DFE_MARK("main");
+            stamp(r, 0);
             do_main();
             DFE_MARK("quarter");
+            stamp(r, 1);
             do_quarter();
             DFE_MARK("mini");
+            stamp(r, 2);
             do_mini();
+            if constexpr (SCAN_BEHIND) {
+                // Row r-1's image stays whole until the barrier of row r lets row r+1 deposit into it (the fall-back walk reads it too); its
+                // record buffer is read behind that barrier and rewritten by the scan of row r+1, behind the next one.
+                // (in front of the quarter task instead, main -> scan -> quarter: 0.2200 against 0.2186 ms as side libraries, profiles/r07_roles_ab.txt)
+                DFE_MARK("scan");
+                stamp(r, 7);
+                if (r - 1 >= r_store && wave < TX) {
+                    const int a0p = (int)((((unsigned)G0b - (unsigned)G0b_step) / (unsigned)ES) & (unsigned)LM);
+                    scan_row_whole(stage + ((m + 1) & 1) * g_stage_len + a0p, (m + 1) & 1, y - 1);
+                }
+            }
             DFE_MARK("barrier");
+            stamp(r, 3);
             if (SWEEP || store_row) {
                 // LDS-only barrier: __syncthreads() would also drain vmcnt, i.e. wait for the previous row's
                 // global stores to be acknowledged before every barrier and serialise stores with compute.
@@ -1355,6 +1404,7 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
                 // (The column sweep needs it in the warm-up rows too: it also frees the tile row the sweep has just left.)
                 asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 DFE_MARK("refill");
+                stamp(r, 4);
                 if constexpr (SWEEP) {
                     if (wave == LW) {
                         // Stream the rings: the pixels requested one row step ago go into the slots of the rows the sweep
@@ -1384,13 +1434,15 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
                     }
                 }
                 DFE_MARK("record+scan");
+                stamp(r, 5);
                 if constexpr (ROLES) {
                     // (row r-1's record is complete: every scan wave has passed this barrier; its buffer is rewritten by the scan of
                     //  row r+1, behind the next barrier)
                     // (written by the first COPY wave: wave LW refills the rings and waits for its loads with vmcnt(0) -- a store of its own
                     //  would put the whole store stream's latency into that wait: 1080p 2.32 against 1.8 ms)
                     if (wave == TX && r - 1 >= K - 1 && y - 1 >= y0n) write_record((r - 1) & 1, rec_prev);
-                    if (store_row && wave < TX) scan_row_whole(st, r & 1, y);
+                    if constexpr (!SCAN_BEHIND)
+                        if (store_row && wave < TX) scan_row_whole(st, r & 1, y);
                 } else if constexpr (FUSE) {
                     if (store_row) scan_row(st, pg_run);
                 }
@@ -1503,20 +1555,37 @@ __device__ __forceinline__ void rowimg_body(const float *__restrict__ I0, const 
                 }
             }
             DFE_MARK("rowend");
+            stamp(r, 6);
             if constexpr (ROLES) rec_prev += DFE_REC;
         });
     }
     if constexpr (ROLES) {   // the piece's last row: its scan has no next barrier to be written behind
+        if constexpr (SCAN_BEHIND) {   // ... and no next main task to run behind
+            const int rs = nsweep - 1;
+            if (rs >= r_store && wave < TX) {
+                const int a0l = (int)((((unsigned)G0b_run - (unsigned)G0b_step) / (unsigned)ES) & (unsigned)LM);
+                scan_row_whole(stage + (rs & 1) * g_stage_len + a0l, rs & 1, y0 + rs - (K - 1));
+            }
+        }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         const int rl = nsweep - 1, yl = y0 + rl - (K - 1);
         if (wave == TX && rl >= K - 1 && yl >= y0n) write_record(rl & 1, rec_prev);   // (rec_prev has been stepped past the last row: its record)
     }
     if constexpr (!SWEEP) break;
+    tl_first = false;
     pos += prows;
     if (pos >= pend) break;
     // next piece: every wave is past its last reads of the rings and the images (LDS-only barrier, the stores drain on)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   }
+    if constexpr (NOVOL && DFE_TL) {
+        // (only where the fallback plane, [tile columns][Ho][TX][DFE_FB] floats, holds both blocks' stamps)
+        if (blockIdx.x < 2 && (long long)((p.Wo + TX - 1) / TX) * p.Ho * TX * DFE_FB >= 2ll * DFE_TL_WORDS) {
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            const unsigned *tlr = reinterpret_cast<const unsigned *>(reinterpret_cast<const float *>(dfe_smem + g_stage_off) + 2 * g_stage_len + 2 * DFE_REC);
+            for (int i = threadIdx.x; i < DFE_TL_WORDS; i += NW * 64) reinterpret_cast<unsigned *>(nv.fb)[blockIdx.x * DFE_TL_WORDS + i] = tlr[i];
+        }
+    }
     // (Round 4 tried the finalize INSIDE this kernel: at the end of the launch each block finished the pixels of its own tile rows --
     //  centre override, decode, extractOutput, depth, its share of the frame border -- with the code flow_finalize_kernel runs
     //  (dfe_finalize_rec_pixel), bit-identical, no second launch.  Same-call A/B, profiles/r04_ac_ab_finalize_in_sweep.txt: step
@@ -1531,7 +1600,9 @@ __global__ __launch_bounds__(1024) void ssd_cv_rowimg_kernel(const float *__rest
     rowimg_body<C, K, TX, SM, FUSE, SWEEP, DC, F16, false>(I0, I1, out, p, fa, CvNovolArgs{});
 }
 // the flow step's sweep without its volume: the fused 3-channel 33 x 33 column sweep minus the copy-out (its 7 copy waves idle behind
-// the barrier, wave TX still writes the records), plus extractOutput's fall-back in the scan waves
+// the barrier, wave TX still writes the records), plus extractOutput's fall-back in the scan waves; the scan waves scan at the end of
+// their row instead of behind the barrier (SCAN_BEHIND in rowimg_body).  128 VGPRs, 0 B scratch, 55 spilled
+// SGPRs (48 with the scan in front of the main task; tests/test_novol_guard_cpu.py)
 template <int C, int K, int TX>
 __global__ __launch_bounds__(1024) void ssd_cv_rowimg_flow_kernel(const float *__restrict__ I0, const float *__restrict__ I1, CvTiledArgs p,
                                                                   CvFuseArgs fa, CvNovolArgs nv) {
@@ -1670,6 +1741,7 @@ static int launch_cv_rowimg_sweep(dfe_ctx *ctx, const float *I0, const float *I1
     if constexpr (FUSE && C == 3 && K == 7 && TX == 8) {
         if (nv) {
             if (!sq33 || !fa) return DFE_OK;
+            if (DFE_TL) lds_bytes += DFE_TL_WORDS * sizeof(unsigned);
             auto kern = ssd_cv_rowimg_flow_kernel<C, K, TX>;
             DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
             {
@@ -2043,6 +2115,16 @@ static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, i
     rc = dfe_flow_finalize(ctx, nullptr, nullptr, nullptr, 2, P, nullptr, thr, Ho, Wo, hWin, wWin, 0, idx, best, fy, fx, scores, imaxs, pitch,
                            pad_t, pad_l, scores_padded, pd, fa.rec, Ho, nv.fb);
     if (pd && pd_done) *pd_done = true;
+#if DFE_TL
+    if (const char *path = getenv("DFE_TIMELINE_OUT"); path && !rc && fb_bytes >= 2 * DFE_TL_WORDS * sizeof(unsigned)) {
+        static unsigned host[2 * DFE_TL_WORDS];
+        if (hipStreamSynchronize(ctx->stream) == hipSuccess && hipMemcpy(host, nv.fb, sizeof(host), hipMemcpyDeviceToHost) == hipSuccess)
+            if (FILE *f = fopen(path, "wb")) {
+                fwrite(host, 1, sizeof(host), f);
+                fclose(f);
+            }
+    }
+#endif
     return rc;
 }
 

@@ -48,7 +48,7 @@ for l in lines[start + 1:end]:
         counts[phase][klass(op)] += 1
 classes = ["valu fp", "valu int", "valu mov", "valu cmp/sel", "valu dpp", "lane<->sgpr", "lds", "vmem", "smem", "salu", "branch", "s_waitcnt", "s_nop"]
 print("%-14s %5s " % ("phase", "x") + " ".join("%12s" % c for c in classes) + "   VALU total")
-for ph in ["prologue", "main", "quarter", "mini", "barrier", "refill", "record+scan", "copy", "rowend"]:
+for ph in ["prologue", "main", "quarter", "mini", "scan", "barrier", "refill", "record+scan", "copy", "rowend"]:
     if ph not in counts: continue
     n = max(seen[ph], 1)
     c = counts[ph]

@@ -273,6 +273,100 @@ template <int VAR, bool HYB = false> void runp(const float *a0, float *d, int wp
     printf("%-28s waves/SIMD=%d  %.3f ms  %.4f us per row step (all waves of a SIMD)  = %.0f cycles @2.3GHz per wave-row\n", name, wps, best,
            us_per_row, us_per_row * 2300.0 / wps);
 }
+// Round 7: the same task row with the frame-0 operands from VGPRs.  Per read batch of BS positions the frame-0 pixels come from a
+// wave-uniform LDS address (ds_read_b128, every lane the same address: a broadcast without bank conflicts) next to the frame-1 pixels; the
+// subtractions are VGPR - VGPR; no scalar loads, no 42 scalars.  VAR 3: reads + arithmetic, 4: + 8 ds_write_b32, 5: + barrier.
+template <int BS, int VAR> __global__ __launch_bounds__(1024) void ka(const float *__restrict__ a0, float *out, int iters) {
+    for (int i = threadIdx.x; i < 64 * 49; i += blockDim.x) lds4[i] = make_float4(i * 0.5f, i * 0.25f, i * 0.125f, 0.f);
+    float *stage = reinterpret_cast<float *>(lds4 + 64 * 49);
+    float4 *t0 = lds4 + 64 * 49 + 4400;                       // frame-0 ring: 8 rows x 24 pixels behind the two images
+    for (int i = threadIdx.x; i < 8 * 24; i += blockDim.x) t0[i] = make_float4(a0[i & 31] + i, a0[(i + 1) & 31] - i, a0[(i + 2) & 31], 0.f);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float4 *lr0 = lds4 + (lane / 33) * 49 + (lane % 33);
+    float ring[6][8];
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int x = 0; x < 8; ++x) ring[i][x] = 0.f;
+    float acc = 0.f;
+    constexpr int NB = (14 + BS - 1) / BS;
+    for (int it = 0; it < iters; ++it) {
+#pragma unroll
+        for (int m = 0; m < 6; ++m) {
+            float e[14];
+            const float4 *lr = lr0 + ((it * 6 + m) & 15) * 49;
+            const float4 *ar = t0 + ((it * 6 + m) & 7) * 24;
+#pragma unroll
+            for (int bb = 0; bb < NB; ++bb) {
+                float4 b[BS], a[BS];
+#pragma unroll
+                for (int s = 0; s < BS; ++s)
+                    if (bb * BS + s < 14) { b[s] = lr[bb * BS + s]; a[s] = ar[bb * BS + s]; }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int s = 0; s < BS; ++s)
+                    if (bb * BS + s < 14) {
+                        asm volatile("" ::"v"(b[s].w), "v"(a[s].w));   // keep ds_read_b128
+                        const float d0 = a[s].x - b[s].x, d1 = a[s].y - b[s].y, d2 = a[s].z - b[s].z;
+                        e[bb * BS + s] = fmaf(d2, d2, fmaf(d1, d1, d0 * d0));
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            float sa[7], pb[7], h[8];
+            sa[6] = e[6];
+#pragma unroll
+            for (int i = 5; i >= 0; --i) sa[i] = e[i] + sa[i + 1];
+            pb[0] = e[7];
+#pragma unroll
+            for (int j = 1; j < 7; ++j) pb[j] = pb[j - 1] + e[7 + j];
+            h[0] = sa[0];
+#pragma unroll
+            for (int x = 1; x < 7; ++x) h[x] = sa[x] + pb[x - 1];
+            h[7] = pb[6];
+#pragma unroll
+            for (int x = 0; x < 8; ++x) {
+                float v = (ring[m][x] + ring[(m + 2) % 6][x]) + (ring[(m + 4) % 6][x] + h[x]);
+                ring[(m + 5) % 6][x] += h[x];
+                ring[m][x] = h[x];
+                if (VAR >= 4) stage[(m & 1) * 8800 + x * 1089 + wave * 64 + lane] = v; else
+                acc += v;
+            }
+            if (VAR >= 5) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        }
+    }
+    out[blockIdx.x * blockDim.x + threadIdx.x] = acc;
+}
+template <int BS, int VAR> void runa(const float *a0, float *d, int wps, const char *name) {
+    int iters = 512, blocks = 256, threads = 256 * wps;
+    hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    (void)hipFuncSetAttribute((const void *)ka<BS, VAR>, hipFuncAttributeMaxDynamicSharedMemorySize, 140000);
+    hipLaunchKernelGGL((ka<BS, VAR>), dim3(blocks), dim3(threads), 140000, 0, a0, d, 8);
+    (void)hipDeviceSynchronize();
+    float best = 1e9;
+    for (int rep = 0; rep < 3; ++rep) {
+        (void)hipEventRecord(e0);
+        hipLaunchKernelGGL((ka<BS, VAR>), dim3(blocks), dim3(threads), 140000, 0, a0, d, iters);
+        (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
+        float ms; (void)hipEventElapsedTime(&ms, e0, e1);
+        if (ms < best) best = ms;
+    }
+    double rows = (double)iters * 6;
+    double us_per_row = best * 1e3 / rows;
+    printf("%-28s waves/SIMD=%d  %.3f ms  %.4f us per row step (all waves of a SIMD)  = %.0f cycles @2.3GHz per wave-row\n", name, wps, best,
+           us_per_row, us_per_row * 2300.0 / wps);
+}
+template <int VAR> void run(const float *a0, float *d, int wps, const char *name);
+// `mix a`: only the round-7 comparison, the scalar-operand row against the VGPR-operand forms, three interleaved passes
+static void compare_a(const float *a0, float *d) {
+    for (int pass = 0; pass < 3; ++pass)
+        for (int w : {4, 2}) {
+            run<3>(a0, d, w, "SGPR operands: reads + arith"); run<5>(a0, d, w, "SGPR + writes, barrier");
+            runa<5, 3>(a0, d, w, "VGPR 3x5: reads + arith"); runa<5, 5>(a0, d, w, "VGPR 3x5 + writes, barrier");
+            runa<4, 3>(a0, d, w, "VGPR 4x4: reads + arith"); runa<4, 5>(a0, d, w, "VGPR 4x4 + writes, barrier");
+            runa<3, 3>(a0, d, w, "VGPR 5x3: reads + arith"); runa<3, 5>(a0, d, w, "VGPR 5x3 + writes, barrier");
+        }
+}
 template <int VAR> void run(const float *a0, float *d, int wps, const char *name) {
     int iters = 512, blocks = 256, threads = 256 * wps;
     hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
@@ -292,9 +386,10 @@ template <int VAR> void run(const float *a0, float *d, int wps, const char *name
     printf("%-28s waves/SIMD=%d  %.3f ms  %.4f us per row step (all waves of a SIMD)  = %.0f cycles @2.3GHz per wave-row\n", name, wps, best,
            us_per_row, us_per_row * 2300.0 / wps);
 }
-int main() {
+int main(int argc, char **argv) {
     float *a0, *d; (void)hipMalloc(&a0, 64 * 4); (void)hipMalloc(&d, 256 * 1024 * 4);
     (void)hipMemset(a0, 0, 64 * 4);
+    if (argc > 1 && argv[1][0] == 'a') { compare_a(a0, d); return 0; }
     for (int w : {4, 2, 1}) { run<0>(a0, d, w, "arithmetic only"); run<3>(a0, d, w, "+ 14 ds_read_b128"); run<4>(a0, d, w, "+ reads + 8 ds_write_b32"); run<5>(a0, d, w, "+ reads, writes, barrier"); }
     for (int w : {4, 2, 1}) { runi<0>(a0, d, w, "INT16 dot2: reads + arith"); runi<1>(a0, d, w, "INT16 + 8 cvt + ds_write_b32"); runi<2>(a0, d, w, "INT16 + writes, barrier"); }
     for (int w : {4, 2, 1}) { runp<0>(a0, d, w, "PACKED planar: reads + arith"); runp<1>(a0, d, w, "PACKED + 8 ds_write_b32"); runp<2>(a0, d, w, "PACKED + writes, barrier"); }
