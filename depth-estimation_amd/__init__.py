@@ -20,6 +20,7 @@ no CPU fallback -- a missing library or device raises.
     version2.getNetwork, getTrainerNetwork, decodeFlow, flowPair   (version2/network.lua, version2/test.lua)
     flowDepthPair, refineFlowSubpixel                   (not in the reference: the single-scale step in one call, and its
                                                         opt-in sub-pixel flow -- subpixel.py)
+    radialFlowDepth(..., subpixel=True), refineRadialFlowSubpixel   (not in the reference: sub-pixel radial flow -- radial.py)
     getModel(geometry).forwardFlow                      (a trained single-scale model per frame pair in one call,
                                                         output_extraction_method 'max' or 'mean' -- network.py)
 """
@@ -49,7 +50,7 @@ from .subpixel import flowDepthPair, refineFlowSubpixel  # noqa: F401
 from .multiscale import CascadingAddTable, MultiscaleModel, MultiscalePrefilter, getModelMultiscale, getMultiscalePrefilter  # noqa: F401
 from .network import getFilter, getFilterRadial, getModel, tables_random  # noqa: F401
 from .radial import (getRMax, getC2PMask, getP2CMask, cartesian2polar, flow2depth, getKOutput, getP2CMaskOF,  # noqa: F401
-                     computeDepthMapFromFlow, getTesterNetwork, getTrainerNetwork, getMatcher, radialFlowDepth, radial_out_shape)
+                     computeDepthMapFromFlow, getTesterNetwork, getTrainerNetwork, getMatcher, radialFlowDepth, radial_out_shape, refineRadialFlowSubpixel)
 from .glue import SmartReshape, FunctionWrapper, Mul2, Log2, OutputExtractor, postProcessImage, enlargeMask  # noqa: F401
 from . import torch7_io, model_io  # noqa: F401
 from .model_io import (saveModel, loadModel, loadWeightsFrom, saveNetwork, loadTesterNetwork, loadTrainerNetwork, copyWeights)  # noqa: F401

@@ -17,9 +17,13 @@
 //   conv_cols_kernel         kH x 1 correlation, RY output rows per thread: a column of RY + kH - 1 inputs is read once per plane
 //   radial_match_kernel      A1r + arg-min: lanes over x (coalesced planes), RY rows per thread share their hWin + RY - 1
 //                            frame-1 rows, features summed in order k = 0..K-1; the volume leaves through an LDS transpose
-//                            as whole rows of W * hWin contiguous floats; first-minimum index - 1 = the radial flow
+//                            as whole rows of W * hWin contiguous floats; first-minimum index - 1 = the radial flow;
+//                            SUB: + the parabolic sub-pixel offset from the winner's two neighbours, an epilogue
+//                            on the costs in registers
+//   radial_refine_subpixel_kernel   the same offset from a stored volume and an integer flow (the staged path)
 //   p2c_flow_depth_kernel    P2C grid in place + bilinear sample of the polar flow + flow2depth
 #include "dfe_internal.h"
+#include "subpixel_offset.h"
 #include <memory>
 #include <cmath>
 
@@ -269,7 +273,10 @@ __global__ __launch_bounds__(256) void conv_cols_kernel(const float *__restrict_
 
 // A1r + arg-min.  in1 [K][H1p >= H1][W] (only the first H1 rows of a plane are used: the cropped previous frame), in2 [K][H1+HW-1][W]; vol [H1][W][HW] (may be NULL), flow [H1][W] = first-min index (0-based)
 // as float, the last row zeroed when zero_last (train_radial:180).  Block = 64 columns x RY rows per thread x 4 row groups.
-template <int HWIN, int RY>
+// SUB: flow = index + subpixel_offset(cost before, at, after the first minimum) (include/dfe.h).  The cost before the winner is
+// carried through the scan and the one after it picked by a second chain of selects: acc[r][] is never indexed by a run-time value
+// (that would move it to scratch).
+template <int HWIN, int RY, bool SUB>
 __global__ __launch_bounds__(256) void radial_match_kernel(const float *__restrict__ in1, int H1p, const float *__restrict__ in2, int K, int H1, int W,
                                                           float *__restrict__ vol, float *__restrict__ flow, int zero_last) {
 #pragma clang fp contract(off)
@@ -308,10 +315,22 @@ __global__ __launch_bounds__(256) void radial_match_kernel(const float *__restri
             if (inx) {
                 float best = acc[r][0];
                 int bi = 0;
+                if constexpr (SUB) {
+                    float cm = 0.f, cp = 0.f;
 #pragma unroll
-                for (int d = 1; d < HWIN; ++d)
-                    if (acc[r][d] < best) { best = acc[r][d]; bi = d; }   // strict: TH min keeps the first minimum
-                flow[(long long)y * W + x] = (zero_last && y == H1 - 1) ? 0.f : (float)bi;
+                    for (int d = 1; d < HWIN; ++d)
+                        if (acc[r][d] < best) { best = acc[r][d]; bi = d; cm = acc[r][d - 1]; }
+#pragma unroll
+                    for (int d = 2; d < HWIN; ++d)
+                        if (bi == d - 1) cp = acc[r][d];
+                    const float f = (float)bi + subpixel_offset(bi >= 1 && bi + 1 < HWIN, cm, best, cp);
+                    flow[(long long)y * W + x] = (zero_last && y == H1 - 1) ? 0.f : f;
+                } else {
+#pragma unroll
+                    for (int d = 1; d < HWIN; ++d)
+                        if (acc[r][d] < best) { best = acc[r][d]; bi = d; }   // strict: TH min keeps the first minimum
+                    flow[(long long)y * W + x] = (zero_last && y == H1 - 1) ? 0.f : (float)bi;
+                }
             }
             if (vol) {
 #pragma unroll
@@ -322,6 +341,24 @@ __global__ __launch_bounds__(256) void radial_match_kernel(const float *__restri
                 __builtin_amdgcn_wave_barrier();
             }
         }
+    }
+}
+
+// the sub-pixel offset of radial_match_kernel<.., true> from a stored volume [P][hWin] and the integer flow [P] (as float): one pixel
+// per thread, the three cells around the minimum.  Pixels at the window's edge (or whose flow is no index of the window) keep their
+// value: (float)bi + 0.  fin == fout is allowed (a thread reads its pixel before it writes it).
+__global__ __launch_bounds__(256) void radial_refine_subpixel_kernel(const float *__restrict__ vol, const float *fin, long long P, int hWin,
+                                                                    float *fout) {
+#pragma clang fp contract(off)
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < P; e += (long long)gridDim.x * blockDim.x) {
+        const float f = fin[e];
+        float o = f;
+        if (f >= 1.f && f < (float)(hWin - 1)) {   // (false for NaN)
+            const int bi = (int)f;
+            const float *c = vol + e * hWin + bi;
+            o = (float)bi + subpixel_offset(true, c[-1], c[0], c[1]);
+        }
+        fout[e] = o;
     }
 }
 
@@ -415,46 +452,62 @@ int dfe_radial_out_shape(const dfe_radial_params *p, int *hMatch, int *hOut, int
     return DFE_OK;
 }
 
-int dfe_radial_match_argmin_f32(dfe_ctx *ctx, const float *in1, int in1_plane_rows, const float *in2, int K, int H1, int W, int hWin,
-                                float *volume, float *flow, int zero_last_row) {
-    DFE_ENTER(ctx);
+}  // extern "C"
+
+// dfe_radial_match_argmin_f32 (sub = false) / dfe_radial_match_subpixel_f32 (sub = true)
+static int radial_match(dfe_ctx *ctx, const char *fn, bool sub, const float *in1, int in1_plane_rows, const float *in2, int K, int H1, int W,
+                        int hWin, float *volume, float *flow, int zero_last_row) {
     if (in1_plane_rows <= 0) in1_plane_rows = H1;
-    DFE_REQUIRE(ctx, in1_plane_rows >= H1, DFE_E_SHAPE, "dfe_radial_match_argmin_f32: in1 planes of %d rows for %d output rows", in1_plane_rows, H1);
-    DFE_REQUIRE(ctx, in1 && in2 && flow, DFE_E_ARG, "dfe_radial_match_argmin_f32: NULL tensor");
-    DFE_REQUIRE(ctx, K > 0 && H1 > 0 && W > 0 && hWin > 0, DFE_E_SHAPE, "dfe_radial_match_argmin_f32: K=%d H1=%d W=%d hWin=%d", K, H1, W, hWin);
+    DFE_REQUIRE(ctx, in1_plane_rows >= H1, DFE_E_SHAPE, "%s: in1 planes of %d rows for %d output rows", fn, in1_plane_rows, H1);
+    DFE_REQUIRE(ctx, in1 && in2 && flow, DFE_E_ARG, "%s: NULL tensor", fn);
+    DFE_REQUIRE(ctx, K > 0 && H1 > 0 && W > 0 && hWin > 0, DFE_E_SHAPE, "%s: K=%d H1=%d W=%d hWin=%d", fn, K, H1, W, hWin);
     DFE_REQUIRE(ctx, hWin == 15 || hWin == 12 || hWin == 8 || hWin == 16, DFE_E_UNSUPPORTED,
-                "dfe_radial_match_argmin_f32: hWin %d has no instantiation (8, 12, 15, 16); use dfe_radial_matching_f32 + dfe_argbest_center", hWin);
+                "%s: hWin %d has no instantiation (8, 12, 15, 16); use dfe_radial_matching_f32 + dfe_argbest_center%s", fn, hWin,
+                sub ? " + dfe_radial_refine_subpixel_f32" : "");
     // output rows per thread (measured 720p, K = 10, hWin = 15: 4 rows 33.7 us, 6 rows 35.5, 8 rows 27.6, 10 rows 48.6 -- 256 VGPRs, one
     // wave per SIMD)
     constexpr int RYM = 8;
     dim3 grid(dfe_cdiv(W, 64), dfe_cdiv(H1, 4 * RYM));
     {
         DfeProfScope prof(ctx);
-        switch (hWin) {
-            case 15: hipLaunchKernelGGL((radial_match_kernel<15, RYM>), grid, dim3(256), 0, ctx->stream, in1, in1_plane_rows, in2, K, H1, W, volume, flow, zero_last_row); break;
-            case 12: hipLaunchKernelGGL((radial_match_kernel<12, RYM>), grid, dim3(256), 0, ctx->stream, in1, in1_plane_rows, in2, K, H1, W, volume, flow, zero_last_row); break;
-            case 16: hipLaunchKernelGGL((radial_match_kernel<16, RYM>), grid, dim3(256), 0, ctx->stream, in1, in1_plane_rows, in2, K, H1, W, volume, flow, zero_last_row); break;
-            default: hipLaunchKernelGGL((radial_match_kernel<8, RYM>), grid, dim3(256), 0, ctx->stream, in1, in1_plane_rows, in2, K, H1, W, volume, flow, zero_last_row); break;
+#define DFE_RM_LAUNCH(HW, SUB)                                                                                                             \
+    hipLaunchKernelGGL((radial_match_kernel<HW, RYM, SUB>), grid, dim3(256), 0, ctx->stream, in1, in1_plane_rows, in2, K, H1, W, volume, flow, \
+                       zero_last_row)
+        if (sub) {
+            switch (hWin) {
+                case 15: DFE_RM_LAUNCH(15, true); break;
+                case 12: DFE_RM_LAUNCH(12, true); break;
+                case 16: DFE_RM_LAUNCH(16, true); break;
+                default: DFE_RM_LAUNCH(8, true); break;
+            }
+        } else {
+            switch (hWin) {
+                case 15: DFE_RM_LAUNCH(15, false); break;
+                case 12: DFE_RM_LAUNCH(12, false); break;
+                case 16: DFE_RM_LAUNCH(16, false); break;
+                default: DFE_RM_LAUNCH(8, false); break;
+            }
         }
+#undef DFE_RM_LAUNCH
     }
     DFE_LAUNCH_CHECK(ctx);
     ctx->last_kernel = "radial_match_kernel";
     return DFE_OK;
 }
 
-int dfe_radial_flow_depth_pair_f32(dfe_ctx *ctx, const dfe_radial_params *p, const float *prev, const float *cur, double e2x, double e2y,
-                                   const float *w1, const float *b1, const float *w2, const float *b2, float *volume, float *polar_flow,
-                                   float *cart_flow, float *depth, float *conf) {
-    DFE_ENTER(ctx);
-    DFE_REQUIRE(ctx, p && prev && cur && w1 && w2, DFE_E_ARG, "dfe_radial_flow_depth_pair_f32: NULL argument");
+// dfe_radial_flow_depth_pair_f32 (sub = false) / dfe_radial_flow_depth_pair_subpixel_f32 (sub = true)
+static int radial_flow_depth_pair(dfe_ctx *ctx, const char *fn, bool sub, const dfe_radial_params *p, const float *prev, const float *cur, double e2x,
+                                  double e2y, const float *w1, const float *b1, const float *w2, const float *b2, float *volume,
+                                  float *polar_flow, float *cart_flow, float *depth, float *conf) {
+    DFE_REQUIRE(ctx, p && prev && cur && w1 && w2, DFE_E_ARG, "%s: NULL argument", fn);
     DFE_REQUIRE(ctx, p->C > 0 && p->hImg > 0 && p->wImg > 0 && p->hInput > 0 && p->wInput > 0 && p->n1 > 0 && p->n2 > 0 && p->kW1 > 0 && p->kH2 > 0 &&
                          p->hWin > 0 && p->alpha_polar > 0 && p->kinfty > 0,
-                DFE_E_ARG, "dfe_radial_flow_depth_pair_f32: bad parameter block");
+                DFE_E_ARG, "%s: bad parameter block", fn);
     int hm, hOut, wOut;
     DFE_REQUIRE(ctx, dfe_radial_out_shape(p, &hm, &hOut, &wOut) == DFE_OK && hOut > 0 && wOut > 0, DFE_E_SHAPE,
-                "dfe_radial_flow_depth_pair_f32: polar height %d too small for kernel %d + window %d", p->hInput, p->kH2, p->hWin);
+                "%s: polar height %d too small for kernel %d + window %d", fn, p->hInput, p->kH2, p->hWin);
     const int lpad = (p->kW1 - 1) / 2, rpad = (p->kW1 - 1) - lpad;        // floor / ceil((wKernel-1)/2): test_radial:190-191
-    DFE_REQUIRE(ctx, lpad <= p->wInput && rpad <= p->wInput, DFE_E_SHAPE, "dfe_radial_flow_depth_pair_f32: wInput %d below the kernel width", p->wInput);
+    DFE_REQUIRE(ctx, lpad <= p->wInput && rpad <= p->wInput, DFE_E_SHAPE, "%s: wInput %d below the kernel width", fn, p->wInput);
     const int Wp = p->wInput + lpad + rpad, H = p->hInput, W = p->wInput;
     const int Hf2 = H - (p->kH2 - 1);                                        // feature rows of a full polar frame
     // scratch: two polar frames, one row-filter buffer, two feature maps, the polar flow
@@ -503,7 +556,7 @@ int dfe_radial_flow_depth_pair_f32(dfe_ctx *ctx, const dfe_radial_params *p, con
     stage.reset(new DfeStageScope(ctx, DFE_STAGE_MATCH));
     // 3. matcher + arg-min (+ the volume when asked for); the last flow row zeroed only on request (train_radial:178-180 does
     //    it for its display; test_radial:204-207, the path this call replaces, does not)
-    rc = dfe_radial_match_argmin_f32(ctx, feat1, Hf2, feat2, p->n2, hm, W, p->hWin, volume, pflow, p->zero_last_row != 0);
+    rc = radial_match(ctx, fn, sub, feat1, Hf2, feat2, p->n2, hm, W, p->hWin, volume, pflow, p->zero_last_row != 0);
     if (rc) return rc;
     stage.reset();
     stage.reset(new DfeStageScope(ctx, DFE_STAGE_EXTRACT));
@@ -524,6 +577,50 @@ int dfe_radial_flow_depth_pair_f32(dfe_ctx *ctx, const dfe_radial_params *p, con
     }
     ctx->last_kernel = "radial_match_kernel";
     return DFE_OK;
+}
+
+extern "C" {
+
+int dfe_radial_match_argmin_f32(dfe_ctx *ctx, const float *in1, int in1_plane_rows, const float *in2, int K, int H1, int W, int hWin,
+                                float *volume, float *flow, int zero_last_row) {
+    DFE_ENTER(ctx);
+    return radial_match(ctx, "dfe_radial_match_argmin_f32", false, in1, in1_plane_rows, in2, K, H1, W, hWin, volume, flow, zero_last_row);
+}
+
+int dfe_radial_match_subpixel_f32(dfe_ctx *ctx, const float *in1, int in1_plane_rows, const float *in2, int K, int H1, int W, int hWin,
+                                  float *volume, float *flow, int zero_last_row) {
+    DFE_ENTER(ctx);
+    return radial_match(ctx, "dfe_radial_match_subpixel_f32", true, in1, in1_plane_rows, in2, K, H1, W, hWin, volume, flow, zero_last_row);
+}
+
+int dfe_radial_refine_subpixel_f32(dfe_ctx *ctx, const float *volume, const float *flow_in, int64_t P, int hWin, float *flow_out) {
+    DFE_ENTER(ctx);
+    DFE_REQUIRE(ctx, volume && flow_in && flow_out, DFE_E_ARG, "dfe_radial_refine_subpixel_f32: NULL tensor");
+    DFE_REQUIRE(ctx, P > 0 && hWin > 0, DFE_E_SHAPE, "dfe_radial_refine_subpixel_f32: P=%lld hWin=%d", (long long)P, hWin);
+    {
+        DfeProfScope prof(ctx);
+        hipLaunchKernelGGL(radial_refine_subpixel_kernel, dim3(grid1d((long long)P)), dim3(256), 0, ctx->stream, volume, flow_in, (long long)P, hWin,
+                           flow_out);
+    }
+    DFE_LAUNCH_CHECK(ctx);
+    ctx->last_kernel = "radial_refine_subpixel_kernel";
+    return DFE_OK;
+}
+
+int dfe_radial_flow_depth_pair_f32(dfe_ctx *ctx, const dfe_radial_params *p, const float *prev, const float *cur, double e2x, double e2y,
+                                   const float *w1, const float *b1, const float *w2, const float *b2, float *volume, float *polar_flow,
+                                   float *cart_flow, float *depth, float *conf) {
+    DFE_ENTER(ctx);
+    return radial_flow_depth_pair(ctx, "dfe_radial_flow_depth_pair_f32", false, p, prev, cur, e2x, e2y, w1, b1, w2, b2, volume, polar_flow, cart_flow,
+                                  depth, conf);
+}
+
+int dfe_radial_flow_depth_pair_subpixel_f32(dfe_ctx *ctx, const dfe_radial_params *p, const float *prev, const float *cur, double e2x, double e2y,
+                                            const float *w1, const float *b1, const float *w2, const float *b2, float *volume, float *polar_flow,
+                                            float *cart_flow, float *depth, float *conf) {
+    DFE_ENTER(ctx);
+    return radial_flow_depth_pair(ctx, "dfe_radial_flow_depth_pair_subpixel_f32", true, p, prev, cur, e2x, e2y, w1, b1, w2, b2, volume, polar_flow,
+                                  cart_flow, depth, conf);
 }
 
 }  // extern "C"

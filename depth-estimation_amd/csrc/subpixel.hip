@@ -15,6 +15,7 @@
 // The sums run in the reference's (c, i, j) order with separately rounded multiply and add (ssd_cv_ref_kernel), so each cost is the
 // bit pattern dfe_ssd_cost_volume_f32's reference kernel gives for that cell.
 #include "dfe_internal.h"
+#include "subpixel_offset.h"   // the parabola's vertex on one axis (include/dfe.h: this order, IEEE division)
 
 namespace {
 
@@ -27,19 +28,6 @@ struct RefineArgs {
     float *depth, *conf;           // pair form only, same addressing as fy / fx; or null
     float mw, mh, infty;           // focus of expansion, depth clamp (pair_depth_px)
 };
-
-// the parabola's vertex on one axis (include/dfe.h: this order, IEEE division)
-__device__ __forceinline__ float subpixel_offset(bool inside, float cm, float c0, float cp) {
-    float off = 0.f;
-    if (inside) {
-        const float den = (cm - c0) + (cp - c0);
-        if (den > 0.f) {
-            off = (cm - cp) / (2.f * den);
-            off = fminf(fmaxf(off, -0.5f), 0.5f);
-        }
-    }
-    return off;
-}
 
 // K > 0: a K x K patch, known at compile time: frame-0 rows stay in registers (the ring above) and the row loop unrolls, so that a
 // channel's loads are in flight together; K == 0: any patch, each term read where it is used (6 loads per term).

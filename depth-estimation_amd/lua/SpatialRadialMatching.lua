@@ -3,12 +3,15 @@
 -- radial/radial_opticalflow_network.lua:33,71-72 and radial/radial_opticalflow_groundtruth.lua:152.
 -- self.flow (H1 x W, = output:min(3) - 1 as the callers compute it, train_radial:166-167) is filled on the way when the
 -- window has a fused instantiation (hWin 8, 12, 15, 16).
+-- self.subpixel = true (opt-in, not in the reference: DESIGN.md section 4.21) makes self.flow the sub-pixel radial flow of
+-- dfe_radial_match_subpixel_f32: the first-minimum index plus the vertex of the parabola through the costs around it.
 local dfe = require 'dfe_ffi'
 local SpatialRadialMatching, parent = torch.class('nn.SpatialRadialMatching', 'nn.Module')
 
 function SpatialRadialMatching:__init(hWin)
    parent.__init(self)
    self.hWin = hWin
+   self.subpixel = false
    self.flow = torch.FloatTensor()
    self.d1, self.d2, self.dout, self.dflow = dfe.newBuffer(), dfe.newBuffer(), dfe.newBuffer(), dfe.newBuffer()
 end
@@ -28,7 +31,8 @@ function SpatialRadialMatching:updateOutput(input)
    if fused then
       self.flow:resize(H1, W)
       local dflow = self.dflow:reserve(H1 * W * 4)
-      dfe.check(dfe.lib.dfe_radial_match_argmin_f32(dfe.ctx, d1, H1, d2, K, H1, W, self.hWin, dout, dflow, 0))
+      local match = self.subpixel and dfe.lib.dfe_radial_match_subpixel_f32 or dfe.lib.dfe_radial_match_argmin_f32
+      dfe.check(match(dfe.ctx, d1, H1, d2, K, H1, W, self.hWin, dout, dflow, 0))
       dfe.download(self.flow, dflow)
    else
       dfe.check(dfe.lib.dfe_radial_matching_f32(dfe.ctx, d1, d2, K, H1, W, self.hWin, dout))

@@ -243,7 +243,25 @@ def radial_out_shape(networkp):
     return hPolar, int(networkp["hImg"] * k), int(networkp["wImg"] * k)
 
 
-def radialFlowDepth(networkp, network, prev_img, img, e2, kinfty=0.65, alpha_polar=1.0, one_call=True, want_volume=False, zero_last_row=False):
+def refineRadialFlowSubpixel(volume, flow):
+    """Not in the reference: the sub-pixel radial flow from a matcher volume [H1][W][hWin] (or [P][hWin]) and
+    its integer flow [H1][W] (first-minimum index - 1, as float) -> a new tensor flow + off, off the vertex of the parabola through
+    the costs before, at and after the minimum, clamped to [-0.5, 0.5]; 0 at the window's edge (include/dfe.h:
+    dfe_radial_refine_subpixel_f32).  Any hWin >= 1."""
+    if volume.dtype != torch.float32 or flow.dtype != torch.float32:
+        raise ValueError("refineRadialFlowSubpixel: float32 tensors, got %s / %s" % (volume.dtype, flow.dtype))
+    hW = volume.shape[-1]
+    if volume.dim() < 2 or tuple(volume.shape[:-1]) != tuple(flow.shape):
+        raise ValueError("refineRadialFlowSubpixel: volume %s does not match flow %s" % (tuple(volume.shape), tuple(flow.shape)))
+    volume, flow = volume.contiguous(), flow.contiguous()
+    out = torch.empty_like(flow)
+    ctx = get_ctx(volume)
+    ctx.check(lib().dfe_radial_refine_subpixel_f32(ctx.handle, ptr(volume), ptr(flow), flow.numel(), hW, ptr(out)))
+    return out
+
+
+def radialFlowDepth(networkp, network, prev_img, img, e2, kinfty=0.65, alpha_polar=1.0, one_call=True, want_volume=False, zero_last_row=False,
+                    subpixel=False):
     """radial/test_radial_opticalflow.lua:186-225 for one frame pair: polar warps of both frames around the epipole e2,
     getTesterNetwork:forward, min(3) - 1, back to cartesian through getP2CMaskOF, flow2depth.  prev_img is the previous
     frame after the caller's ego-motion correction (sfm2.removeEgoMotion: `sfm2.removeEgoMotion` of this package, or the caller's own).  Returns a dict
@@ -251,7 +269,10 @@ def radialFlowDepth(networkp, network, prev_img, img, e2, kinfty=0.65, alpha_pol
     one_call: everything inside dfe_radial_flow_depth_pair_f32 (default separable filter stacks); else the staged module
     calls -- same numbers bit for bit.
     zero_last_row: also zero the last polar flow row, as the trainer's display path does (train_radial:178-180:
-    `test:sub(h,h,1,w):zero()`); test_radial:204-207 -- the default here -- does not."""
+    `test:sub(h,h,1,w):zero()`); test_radial:204-207 -- the default here -- does not.
+    subpixel (not in the reference): the polar flow is the first-minimum index plus the vertex of the parabola
+    through the costs around it (dfe_radial_flow_depth_pair_subpixel_f32; staged: dfe_radial_refine_subpixel_f32 after the arg-min);
+    everything after it is unchanged and sees a fractional polar flow."""
     hK, wK = networkp_kernel_size(networkp)
     prev_img, img = prev_img.contiguous(), img.contiguous()
     Cc, hImg, wImg = img.shape
@@ -271,8 +292,9 @@ def radialFlowDepth(networkp, network, prev_img, img, e2, kinfty=0.65, alpha_pol
         pf = torch.empty((hm, networkp["wInput"]), dtype=torch.float32, device=dev)
         cart, depth, conf = (torch.empty((hOut, wOut), dtype=torch.float32, device=dev) for _ in range(3))
         ctx = get_ctx(img)
-        ctx.check(lib().dfe_radial_flow_depth_pair_f32(ctx.handle, C.byref(prm), ptr(prev_img), ptr(img), float(e2[0]), float(e2[1]), ptr(w1), ptr(b1),
-                                                       ptr(w2), ptr(b2), ptr(vol) if want_volume else None, ptr(pf), ptr(cart), ptr(depth), ptr(conf)))
+        entry = lib().dfe_radial_flow_depth_pair_subpixel_f32 if subpixel else lib().dfe_radial_flow_depth_pair_f32
+        ctx.check(entry(ctx.handle, C.byref(prm), ptr(prev_img), ptr(img), float(e2[0]), float(e2[1]), ptr(w1), ptr(b1),
+                        ptr(w2), ptr(b2), ptr(vol) if want_volume else None, ptr(pf), ptr(cart), ptr(depth), ptr(conf)))
         ret.update(polar_flow=pf, flow=cart, depth=depth, confs=conf)
         if want_volume:
             ret["output"] = vol
@@ -286,6 +308,8 @@ def radialFlowDepth(networkp, network, prev_img, img, e2, kinfty=0.65, alpha_pol
     ctx = get_ctx(output)
     ctx.check(lib().dfe_argbest_center(ctx.handle, ptr(output), H1 * Wi, hW, 0, 0, ptr(imin), None))   # output:min(3): first minimum, no centre rule
     idx = (imin - 1).to(torch.float32)                   # idx:add(-1), test_radial:207
+    if subpixel:
+        ctx.check(lib().dfe_radial_refine_subpixel_f32(ctx.handle, ptr(output), ptr(idx), H1 * Wi, hW, ptr(idx)))   # in place
     if zero_last_row:
         idx[-1].zero_()                                  # train_radial:178-180 (the trainer's display path only)
     np2 = dict(networkp, hKernel=hK, wKernel=wK)

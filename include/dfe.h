@@ -179,6 +179,25 @@ int dfe_radial_matching_f32(dfe_ctx *ctx, const float *in1, const float *in2, in
  *   hWin in {8, 12, 15, 16}. */
 int dfe_radial_match_argmin_f32(dfe_ctx *ctx, const float *in1, int in1_plane_rows, const float *in2, int K, int H1, int W,
                                 int hWin, float *volume, float *flow, int zero_last_row);
+/* not in the reference: dfe_radial_match_argmin_f32 with a sub-pixel radial flow.  Same arguments,
+ *   same volume, same hWin set {8, 12, 15, 16} (DFE_E_UNSUPPORTED otherwise).  For a pixel with costs c[0 .. hWin-1] (its
+ *   volume cells, fp32):
+ *     bi  = the first minimum, by strict `<` scan from 0 (as dfe_radial_match_argmin_f32);
+ *     off = 0 if bi == 0 or bi == hWin - 1 (a neighbour lies outside the searched window); otherwise, with
+ *           c0 = c[bi], cm = c[bi-1], cp = c[bi+1], den = (cm - c0) + (cp - c0):
+ *           off = (cm - cp) / (2 * den) clamped to [-0.5, 0.5] if den > 0, else 0;
+ *     flow = (float)bi + off.
+ *   Every operation is fp32, separately rounded, in exactly this order, with IEEE division -- the per-axis rule of
+ *   dfe_flow_refine_subpixel_f32.  The last row is 0 when zero_last_row.  The arithmetic is an epilogue on the costs the
+ *   matcher's thread already holds: no second pass over the features. */
+int dfe_radial_match_subpixel_f32(dfe_ctx *ctx, const float *in1, int in1_plane_rows, const float *in2, int K, int H1, int W,
+                                  int hWin, float *volume, float *flow, int zero_last_row);
+/* not in the reference: the same rule as a stage of its own, for any hWin >= 1 and any filter stack.  volume [P][hWin]
+ *   (dfe_radial_matching_f32's output, P = H1 * W), flow_in [P] the integer radial flow as float (first-minimum index - 1,
+ *   i.e. bi) -> flow_out [P] = flow_in + off.  Pixels whose flow_in is 0, hWin - 1 or no index of the window keep their
+ *   value.  flow_out may be flow_in (in place).  Bit-identical to dfe_radial_match_subpixel_f32 on the same volume. */
+int dfe_radial_refine_subpixel_f32(dfe_ctx *ctx, const float *volume, const float *flow_in, int64_t P, int hWin,
+                                   float *flow_out);
 
 /* networkp of the radial scripts (radial/train_radial_opticalflow.lua:83-97) for the default separable filter stack
  * {{C,1,kW1,n1},{n1,kH2,1,n2}} (train_radial:27), optionally with 'tanh' between the two convolutions. */
@@ -208,6 +227,14 @@ int dfe_radial_out_shape(const dfe_radial_params *p, int *hMatch, int *hOut, int
 int dfe_radial_flow_depth_pair_f32(dfe_ctx *ctx, const dfe_radial_params *p, const float *prev, const float *cur, double e2x,
                                    double e2y, const float *w1, const float *b1, const float *w2, const float *b2,
                                    float *volume, float *polar_flow, float *cart_flow, float *depth, float *conf);
+/* not in the reference: dfe_radial_flow_depth_pair_f32 with the sub-pixel polar flow of dfe_radial_match_subpixel_f32
+ *   (DESIGN section 4.21).  Same arguments and outputs; everything after the matcher is unchanged -- the P2C bilinear
+ *   sample, `f < 0.1 -> infty`, d / f, conf and the infty normalisation see a fractional polar flow instead of one of
+ *   {0 .. hWin-1}.  Bit-identical to the staged calls with dfe_radial_refine_subpixel_f32 after the arg-min. */
+int dfe_radial_flow_depth_pair_subpixel_f32(dfe_ctx *ctx, const dfe_radial_params *p, const float *prev, const float *cur,
+                                            double e2x, double e2y, const float *w1, const float *b1, const float *w2,
+                                            const float *b2, float *volume, float *polar_flow, float *cart_flow, float *depth,
+                                            float *conf);
 
 /* ---- N2: gradients of the two matchers (training drivers call model:backward through them) ------- */
 /* replaces: nn.SpatialMatching:updateGradInput / nn.SpatialRadialMatching:updateGradInput (un-vendored nnx), reached
