@@ -218,8 +218,20 @@ int dfe_contrastive_normalization_run(dfe_ctx *ctx, const float *in, int C, int 
 int dfe_contrastive_normalization_run2(dfe_ctx *ctx, const float *in0, const float *in1, int C, int H, int W, const float *kernel_host, int k,
                                        float threshold, float thresval, float *scratch, float *out0, float *out1, int cx, int cy, int cw, int ch);
 // the raw-patch pyramid on uint8 frames, converted inside its preparation kernels (multiscale.hip; f16_scale 0 = fp32 volumes)
+// subpixel: the sub-pixel refinement behind the matcher (dfe_multiscale_flow_pair_subpixel_u8)
 int dfe_multiscale_flow_pair_bytes(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int maxh, int maxw,
-                                   const int *ratios, int nratios, float u8_scale, float f16_scale, float *flow, int64_t *idx);
+                                   const int *ratios, int nratios, float u8_scale, float f16_scale, float *flow, int64_t *idx, bool subpixel = false);
+// the pyramid's sub-pixel refinement (multiscale_subpixel.hip): from the class map and every scale's padded frames to the refined flow
+struct MsSubpixelArgs {
+    const float *p0[DFE_MAX_RATIOS], *p1[DFE_MAX_RATIOS];   // padded scale frames [C][Hp][Wp] (frame 0, frame 1)
+    int r[DFE_MAX_RATIOS], Hp[DFE_MAX_RATIOS], Wp[DFE_MAX_RATIOS];
+    int base[DFE_MAX_RATIOS];   // 0-based class id of the scale's first class in the joined vector
+    int d[DFE_MAX_RATIOS];      // ring width of scale s >= 1
+    int nratios, ncls, C, H, W, k, maxh, maxw;
+    const long long *idx;       // [H][W], 1-based class ids
+    float *fy, *fx;             // [H][W] each, written where idx is a class id
+};
+int dfe_multiscale_subpixel_launch(dfe_ctx *ctx, const MsSubpixelArgs &a);
 // nn.SpatialMatching on feature maps, fast kernels or the reference-order one (ssd_cost_volume.hip)
 int dfe_spatial_matching_dispatch(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int maxh, int maxw, float *out);
 

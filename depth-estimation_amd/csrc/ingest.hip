@@ -6,6 +6,7 @@
 //   dfe_flow_depth_pair_u8             dfe_flow_depth_pair_f32 on uint8 frames
 //   dfe_flow_depth_pair_subpixel_u8    dfe_flow_depth_pair_subpixel_f32 on uint8 frames
 //   dfe_multiscale_flow_pair_u8        dfe_multiscale_flow_pair_f32 / _f16 on uint8 frames
+//   dfe_multiscale_flow_pair_subpixel_u8   ... with the pyramid's sub-pixel refinement behind it
 // The uint8 entries convert into a per-ctx frame buffer (one pass: 0.9 MB read, 3.7 MB written per VGA frame, ~2 us) and run the fp32
 // pipeline on it -- bit-identical to the fp32 entry called on float(frame) * scale.  The conversion is NOT folded into the cost-volume
 // kernel: its frame-0 operands are scalar loads of whole fp32 rows (42 SGPRs a row, requested a row ahead), and unpacking bytes on the
@@ -280,6 +281,17 @@ int dfe_multiscale_flow_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *
     // no conversion pass: the pyramid's preparation kernels are the only readers of the frames and take the bytes as they are
     // (float(byte) * scale at the load: the bits of dfe_u8_to_f32 followed by the fp32 entry)
     return dfe_multiscale_flow_pair_bytes(ctx, I0, I1, C, H, W, k, maxh, maxw, ratios, nratios, scale, f16_scale, flow, idx);
+}
+
+// ... with the sub-pixel refinement behind it (multiscale_subpixel.hip): the padded scale frames it reads are the ones the preparation
+// kernels made from the bytes, so the result is that of dfe_multiscale_flow_pair_subpixel_f32 on the converted frames
+int dfe_multiscale_flow_pair_subpixel_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int maxh, int maxw,
+                                         const int *ratios, int nratios, float scale, float f16_scale, float *flow, int64_t *idx) {
+    DFE_ENTER(ctx);
+    DFE_REQUIRE(ctx, I0 && I1 && flow, DFE_E_ARG, "dfe_multiscale_flow_pair_subpixel_u8: NULL tensor");
+    DFE_REQUIRE(ctx, C > 0 && H > 0 && W > 0 && scale > 0, DFE_E_ARG, "dfe_multiscale_flow_pair_subpixel_u8: C=%d %dx%d scale=%g", C, H, W, (double)scale);
+    DFE_REQUIRE(ctx, f16_scale >= 0.f && f16_scale < INFINITY, DFE_E_ARG, "dfe_multiscale_flow_pair_subpixel_u8: f16_scale=%g", (double)f16_scale);
+    return dfe_multiscale_flow_pair_bytes(ctx, I0, I1, C, H, W, k, maxh, maxw, ratios, nratios, scale, f16_scale, flow, idx, true);
 }
 
 }  // extern "C"

@@ -1011,6 +1011,8 @@ struct MsArgs {
     float f16_scale;
     const MsFilter *filt;
     float u8_scale;
+    bool subpixel;                 // the sub-pixel refinement behind the matcher (raw patches only; flow required)
+    const char *entry;             // the C entry's name, for its error messages (NULL: dfe_multiscale_flow_pair_f32)
 };
 // one scale: its sizes and where its buffers start in the arena (bytes)
 struct MsScale {
@@ -1025,6 +1027,7 @@ struct MsPlan {
     int N, hk, wk, hp, wp, pt, pl, middle;
     MsScale sc[DFE_MAX_RATIOS];
     size_t total;                  // arena bytes
+    size_t idx_tmp;                // sub-pixel entry called without idx: the class map the refinement reads, in the arena
     long long frame_max;           // the largest padded frame, C * Hp * Wp elements
     CascadeGeom g;                 // (in / out_scale are the cell cascade's to fill)
     MultiGeom mg;
@@ -1076,8 +1079,10 @@ static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
     MsPlan &P = *plan;
     const int C = a.C, H = a.H, W = a.W, k = a.k, maxh = a.maxh, maxw = a.maxw, nratios = a.nratios;
     const int *ratios = a.ratios;
-    DFE_REQUIRE(ctx, a.I0 && a.I1 && (a.flow || a.idx), DFE_E_ARG, "dfe_multiscale_flow_pair_f32: NULL tensor");
-    DFE_REQUIRE(ctx, C > 0 && k > 0 && maxh > 0 && maxw > 0, DFE_E_ARG, "dfe_multiscale_flow_pair_f32: bad size");
+    const char *entry = a.entry ? a.entry : "dfe_multiscale_flow_pair_f32";
+    DFE_REQUIRE(ctx, a.I0 && a.I1 && (a.flow || a.idx), DFE_E_ARG, "%s: NULL tensor", entry);
+    DFE_REQUIRE(ctx, !a.subpixel || a.flow, DFE_E_ARG, "%s: flow is NULL", entry);
+    DFE_REQUIRE(ctx, C > 0 && k > 0 && maxh > 0 && maxw > 0, DFE_E_ARG, "%s: bad size", entry);
     P.a = a;
     P.fx = a.flow ? a.flow + (size_t)H * W : nullptr;
     int rc = fill_cascade(ctx, P.g, ratios, nratios, maxh, maxw);
@@ -1098,7 +1103,7 @@ static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
         MsScale &sc = P.sc[s];
         const int r = sc.r = ratios[s];
         DFE_REQUIRE(ctx, H % r == 0 && W % r == 0, DFE_E_SHAPE,
-                    "dfe_multiscale_flow_pair_f32: frame %dx%d is not a multiple of ratio %d (opticalflow_model_multiscale.lua:238-243)", H, W, r);
+                    "%s: frame %dx%d is not a multiple of ratio %d (opticalflow_model_multiscale.lua:238-243)", entry, H, W, r);
         sc.Hs = H / r; sc.Ws = W / r; sc.Hp = sc.Hs + hp; sc.Wp = sc.Ws + wp;
         const size_t np = (size_t)C * sc.Hp * sc.Wp, nv = (size_t)sc.Hs * sc.Ws * N;
         // learned filters: four feature buffers per scale (ping-pong per frame), each the largest layer output
@@ -1109,11 +1114,13 @@ static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
         sc.prob = P.total; P.total += (nv * sizeof(float) + 255) / 256 * 256;
         sc.best = P.total; P.total += ((size_t)sc.Hs * sc.Ws * sizeof(float2) + 255) / 256 * 256;
     }
+    P.idx_tmp = P.total;
+    if (a.subpixel && !a.idx) P.total += ((size_t)H * W * sizeof(int64_t) + 255) / 256 * 256;
     P.mg.maxh = maxh; P.mg.maxw = maxw; P.mg.nratios = nratios;
     P.frame_max = 0;
     for (int s = 0; s < nratios; ++s) {
         const long long np = (long long)C * P.sc[s].Hp * P.sc[s].Wp;
-        DFE_REQUIRE(ctx, 2 * np < (1ll << 31), DFE_E_SHAPE, "dfe_multiscale_flow_pair_f32: frame too large");
+        DFE_REQUIRE(ctx, 2 * np < (1ll << 31), DFE_E_SHAPE, "%s: frame too large", entry);
         if (np > P.frame_max) P.frame_max = np;
         P.mg.ratios[s] = ratios[s];
         P.mg.d[s] = P.g.d[s];
@@ -1168,7 +1175,7 @@ static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
     P.prep_tiles = !a.filt && pow2 && (long long)H * W >= 1500000 && ctx->opt[DFE_OPT_PREP_TILES] != 0;
     // the lane <-> cell cascade's LDS: a wave's two window buffers, or the class -> displacement table where that is larger
     P.lds = (size_t)kWaves * 2 * N * sizeof(float);
-    DFE_REQUIRE(ctx, P.px_path || P.lds <= 64 * 1024, DFE_E_UNSUPPORTED, "dfe_multiscale_flow_pair_f32: window %dx%d too large", maxh, maxw);
+    DFE_REQUIRE(ctx, P.px_path || P.lds <= 64 * 1024, DFE_E_UNSUPPORTED, "%s: window %dx%d too large", entry, maxh, maxw);
     if (P.lds < (size_t)P.g.ncls * sizeof(int2)) P.lds = (size_t)P.g.ncls * sizeof(int2);
     return DFE_OK;
 }
@@ -1482,12 +1489,28 @@ static int ms_run(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B) {
     return P.px_path ? ms_cascade_px(ctx, P, B, R) : ms_cascade_cell(ctx, P, B, R);
 }
 
+// the sub-pixel refinement of the class map `idx` into P.a.flow, from the padded scale frames ms_prep_raw left in the arena (they
+// survive every path of ms_run: volumes, fused finest / second scale, uint8 frames).  Every shape takes its costs from the frames.
+// Reading the five values from a scale's raw fp32 volume, where the plan leaves one intact, has not been tried.
+static int ms_subpixel(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const int64_t *idx) {
+    MsSubpixelArgs sa{};
+    for (int s = 0; s < P.a.nratios; ++s) {
+        sa.p0[s] = B.p0[s]; sa.p1[s] = B.p1[s];
+        sa.r[s] = P.sc[s].r; sa.Hp[s] = P.sc[s].Hp; sa.Wp[s] = P.sc[s].Wp;
+        sa.base[s] = P.g.base[s]; sa.d[s] = P.g.d[s];
+    }
+    sa.nratios = P.a.nratios; sa.ncls = P.g.ncls; sa.C = P.a.C; sa.H = P.a.H; sa.W = P.a.W; sa.k = P.a.k; sa.maxh = P.a.maxh; sa.maxw = P.a.maxw;
+    sa.idx = (const long long *)idx; sa.fy = P.a.flow; sa.fx = P.fx;
+    return dfe_multiscale_subpixel_launch(ctx, sa);
+}
+
 // Plan, allocate, look up the graph, run the stages.  The graph key holds the buffers and the shape, not the options (DFE_FINE_FUSE,
-// DFE_MID_FUSE, ... / the cost-volume mode): a replay keeps the plan it was captured with until a buffer or the shape changes.
+// DFE_MID_FUSE, ... / the cost-volume mode): a replay keeps the plan it was captured with until a buffer or the shape changes.  It
+// holds the sub-pixel switch too: the two entries never replay each other's capture.
 static int multiscale_flow_pair(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw,
                                 const int *ratios, int nratios, float *flow, int64_t *idx, float f16_scale, const MsFilter *filt = nullptr,
-                                float u8_scale = 0.f) {
-    const MsArgs a{I0, I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, f16_scale, filt, u8_scale};
+                                float u8_scale = 0.f, bool subpixel = false, const char *entry = nullptr) {
+    const MsArgs a{I0, I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, f16_scale, filt, u8_scale, subpixel, entry};
     MsPlan P;
     int rc = ms_plan(ctx, a, &P);
     if (rc) return rc;
@@ -1497,10 +1520,10 @@ static int multiscale_flow_pair(dfe_ctx *ctx, const float *I0, const float *I1, 
     rc = dfe_scratch(ctx, P.total, &scr, filt != nullptr);   // (learned filters: the convolutions' arena, see dfe_scratch)
     if (rc) return rc;
     // the same call again (same buffers, shapes and arena): replay its launches as a graph
-    struct { const void *I0, *I1, *flow, *idx, *scr; int C, H, W, k, maxh, maxw, nratios, ratios[DFE_MAX_RATIOS]; float f16, u8; } gkey;
+    struct { const void *I0, *I1, *flow, *idx, *scr; int C, H, W, k, maxh, maxw, nratios, ratios[DFE_MAX_RATIOS]; float f16, u8; int subpixel; } gkey;
     memset(&gkey, 0, sizeof gkey);
     gkey.I0 = I0; gkey.I1 = I1; gkey.flow = flow; gkey.idx = idx; gkey.scr = scr;
-    gkey.C = C; gkey.H = H; gkey.W = W; gkey.k = k; gkey.maxh = maxh; gkey.maxw = maxw; gkey.nratios = nratios; gkey.f16 = f16_scale; gkey.u8 = u8_scale;
+    gkey.C = C; gkey.H = H; gkey.W = W; gkey.k = k; gkey.maxh = maxh; gkey.maxw = maxw; gkey.nratios = nratios; gkey.f16 = f16_scale; gkey.u8 = u8_scale; gkey.subpixel = subpixel;
     for (int s = 0; s < nratios; ++s) gkey.ratios[s] = ratios[s];
     const int gmode = filt ? 0 : dfe_graph_lookup(ctx, ctx->ms_graph, &gkey, sizeof gkey);
     if (gmode == 2) {
@@ -1510,7 +1533,9 @@ static int multiscale_flow_pair(dfe_ctx *ctx, const float *I0, const float *I1, 
     }
     MsBufs B;
     ms_bufs(P, scr, &B);
+    if (subpixel && !idx) P.a.idx = (int64_t *)((char *)scr + P.idx_tmp);   // (the refinement reads the class map)
     rc = ms_run(ctx, P, B);
+    if (!rc && subpixel) rc = ms_subpixel(ctx, P, B, P.a.idx);
     return gmode == 1 ? dfe_graph_finish(ctx, ctx->ms_graph, rc) : rc;
 }
 
@@ -1518,6 +1543,39 @@ int dfe_multiscale_flow_pair_f32(dfe_ctx *ctx, const float *I0, const float *I1,
                                  const int *ratios, int nratios, float *flow, int64_t *idx) {
     DFE_ENTER(ctx);
     return multiscale_flow_pair(ctx, I0, I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, 0.f);
+}
+
+int dfe_multiscale_flow_pair_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw,
+                                          const int *ratios, int nratios, float *flow, int64_t *idx) {
+    DFE_ENTER(ctx);
+    return multiscale_flow_pair(ctx, I0, I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, 0.f, nullptr, 0.f, true, "dfe_multiscale_flow_pair_subpixel_f32");
+}
+
+// the refinement alone: the plan's checks and geometry, an arena of the padded scale frames only (no volumes), ms_prep_raw, the kernel
+int dfe_multiscale_refine_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw,
+                                       const int *ratios, int nratios, const int64_t *idx, float *flow) {
+    DFE_ENTER(ctx);
+    DFE_REQUIRE(ctx, idx && flow, DFE_E_ARG, "dfe_multiscale_refine_subpixel_f32: NULL tensor");
+    const MsArgs a{I0, I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, nullptr, 0.f, nullptr, 0.f, false, "dfe_multiscale_refine_subpixel_f32"};
+    MsPlan P;
+    int rc = ms_plan(ctx, a, &P);
+    if (rc) return rc;
+    size_t off[DFE_MAX_RATIOS], total = 0;
+    for (int s = 0; s < nratios; ++s) {
+        off[s] = total;
+        total += (2 * (size_t)C * P.sc[s].Hp * P.sc[s].Wp * sizeof(float) + 255) / 256 * 256;
+    }
+    void *scr = nullptr;
+    rc = dfe_scratch(ctx, total, &scr);
+    if (rc) return rc;
+    MsBufs B{};
+    for (int s = 0; s < nratios; ++s) {
+        B.p0[s] = (float *)((char *)scr + off[s]);
+        B.p1[s] = B.p0[s] + (size_t)C * P.sc[s].Hp * P.sc[s].Wp;
+    }
+    rc = ms_prep_raw(ctx, P, B);
+    if (rc) return rc;
+    return ms_subpixel(ctx, P, B, idx);
 }
 
 int dfe_multiscale_flow_pair_f16(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw,
@@ -1654,6 +1712,7 @@ int dfe_cascading_add_backward_f32(dfe_ctx *ctx, const float *const *gradOut, co
 
 // uint8 frames straight into the preparation kernels (dfe_multiscale_flow_pair_u8, ingest.hip); f16_scale as in the _f16 entry, 0 = fp32 volumes
 int dfe_multiscale_flow_pair_bytes(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int maxh, int maxw,
-                                   const int *ratios, int nratios, float u8_scale, float f16_scale, float *flow, int64_t *idx) {
-    return multiscale_flow_pair(ctx, (const float *)I0, (const float *)I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, f16_scale, nullptr, u8_scale);
+                                   const int *ratios, int nratios, float u8_scale, float f16_scale, float *flow, int64_t *idx, bool subpixel) {
+    return multiscale_flow_pair(ctx, (const float *)I0, (const float *)I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, f16_scale, nullptr, u8_scale,
+                                subpixel, subpixel ? "dfe_multiscale_flow_pair_subpixel_u8" : nullptr);
 }

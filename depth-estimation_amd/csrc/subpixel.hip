@@ -8,14 +8,11 @@
 //
 // Layout: no LDS tile.  A wave is 64 consecutive output pixels of one row, one pixel per lane, reading both frames through L1/L2:
 // frame 0's rows are the same for every lane and coalesce to two 128-B lines per load; frame 1's rows coalesce wherever neighbouring
-// pixels share their flow, which is most of a frame.  The five costs share their reads: per channel, frame 1's k + 2 rows around the
-// arg-min cell are read once, k + 2 values each (the x neighbours are the same row shifted by one), and each frame-0 row once, kept in a
-// ring of three rows (row t of frame 1 meets frame-0 rows t - 1, t, t + 1 for the y+1 cost, the centre row and the y-1 cost).  That is
-// C (kh kw + (kh + 2)(kw + 2)) loads per pixel -- 390 at k = 7, C = 3 -- against 5 C kh kw = 735 for five independent sums.
-// The sums run in the reference's (c, i, j) order with separately rounded multiply and add (ssd_cv_ref_kernel), so each cost is the
-// bit pattern dfe_ssd_cost_volume_f32's reference kernel gives for that cell.
+// pixels share their flow, which is most of a frame.  The five costs share their reads and are the bit patterns of
+// dfe_ssd_cost_volume_f32's reference kernel (subpixel_costs.h).
 #include "dfe_internal.h"
 #include "subpixel_offset.h"   // the parabola's vertex on one axis (include/dfe.h: this order, IEEE division)
+#include "subpixel_costs.h"    // the five costs, from the frames
 
 namespace {
 
@@ -29,8 +26,7 @@ struct RefineArgs {
     float mw, mh, infty;           // focus of expansion, depth clamp (pair_depth_px)
 };
 
-// K > 0: a K x K patch, known at compile time: frame-0 rows stay in registers (the ring above) and the row loop unrolls, so that a
-// channel's loads are in flight together; K == 0: any patch, each term read where it is used (6 loads per term).
+// K > 0: a K x K patch, known at compile time; K == 0: any patch (subpixel_costs.h).
 template <int K>
 __global__ __launch_bounds__(256) void flow_refine_subpixel_kernel(RefineArgs a) {
 #pragma clang fp contract(off)
@@ -53,65 +49,10 @@ __global__ __launch_bounds__(256) void flow_refine_subpixel_kernel(RefineArgs a)
     const bool inx = s >= 1 && s + 1 < a.wWin, iny = r >= 1 && r + 1 < a.hWin;
     const int sm = inx ? s - 1 : s, sp = inx ? s + 1 : s, rm = iny ? r - 1 : r, rp = iny ? r + 1 : r;
     const long long plane = (long long)a.H * a.W;
-    float c0 = 0.f, cxm = 0.f, cxp = 0.f, cym = 0.f, cyp = 0.f;
-    for (int c = 0; c < a.C; ++c) {
-        const float *A = a.I0 + c * plane + (long long)(y + oy) * a.W + x + ox;   // frame-0 patch, row i at A + i W
-        const float *B = a.I1 + c * plane + x + s;                               // frame-1 column of the arg-min cell
-        if constexpr (K > 0) {
-            constexpr int KW = K;
-            float ap[KW], ac[KW], an[KW];   // frame-0 rows t - 1, t, t + 1
-#pragma unroll
-            for (int j = 0; j < KW; ++j) { ap[j] = 0.f; ac[j] = 0.f; an[j] = 0.f; }
-#pragma unroll
-            for (int t = -1; t <= K; ++t) {
-                // frame-1 row r + t (rows -1 and kh only feed the y-1 / y+1 costs: rm, rp stand in for them at the window's edge),
-                // columns s - 1 .. s + KW (the end columns only feed the x costs: sm, sp at the edge)
-                const int row = t < 0 ? rm : t >= K ? rp + K - 1 : r + t;
-                const float *bp = B + (long long)(y + row) * a.W;
-                float b[KW + 2];
-                b[0] = bp[sm - s];
-#pragma unroll
-                for (int j = 0; j < KW; ++j) b[j + 1] = bp[j];
-                b[KW + 1] = bp[sp - s + KW - 1];
-#pragma unroll
-                for (int j = 0; j < KW; ++j) { ap[j] = ac[j]; ac[j] = an[j]; }
-                if (t + 1 < K) {
-#pragma unroll
-                    for (int j = 0; j < KW; ++j) an[j] = A[(long long)(t + 1) * a.W + j];
-                }
-                // ap / ac / an now hold frame-0 rows t - 1, t, t + 1
-                if (t >= 0 && t < K) {
-#pragma unroll
-                    for (int j = 0; j < KW; ++j) {
-                        float d = ac[j] - b[j + 1]; float d2 = d * d; c0 = c0 + d2;
-                        d = ac[j] - b[j]; d2 = d * d; cxm = cxm + d2;
-                        d = ac[j] - b[j + 2]; d2 = d * d; cxp = cxp + d2;
-                    }
-                }
-                if (t + 1 < K) {   // row t of frame 1 against frame-0 row t + 1: the cell one row up
-#pragma unroll
-                    for (int j = 0; j < KW; ++j) { const float d = an[j] - b[j + 1]; const float d2 = d * d; cym = cym + d2; }
-                }
-                if (t >= 1) {         // against frame-0 row t - 1: the cell one row down
-#pragma unroll
-                    for (int j = 0; j < KW; ++j) { const float d = ap[j] - b[j + 1]; const float d2 = d * d; cyp = cyp + d2; }
-                }
-            }
-        } else {
-            for (int i = 0; i < a.kh; ++i) {
-                const float *ar = A + (long long)i * a.W;
-                const float *b0 = B + (long long)(y + r + i) * a.W, *bm = B + (long long)(y + rm + i) * a.W, *bq = B + (long long)(y + rp + i) * a.W;
-                for (int j = 0; j < a.kw; ++j) {
-                    const float v = ar[j];
-                    float d = v - b0[j]; float d2 = d * d; c0 = c0 + d2;
-                    d = v - b0[j + sm - s]; d2 = d * d; cxm = cxm + d2;
-                    d = v - b0[j + sp - s]; d2 = d * d; cxp = cxp + d2;
-                    d = v - bm[j]; d2 = d * d; cym = cym + d2;
-                    d = v - bq[j]; d2 = d * d; cyp = cyp + d2;
-                }
-            }
-        }
-    }
+    const float *A = a.I0 + (long long)(y + oy) * a.W + x + ox;   // frame-0 patch, row i at A + i W
+    const float *B = a.I1 + (long long)y * a.W + x + s;           // frame-1 column of the arg-min cell, row 0 of the pixel's window
+    float c0, cxm, cxp, cym, cyp;
+    subpixel_five_costs<K>(A, B, plane, a.W, a.C, a.kh, a.kw, r, rm, rp, sm - s, sp - s, c0, cxm, cxp, cym, cyp);
     const float fy = (float)(r - oy) + subpixel_offset(iny, cym, c0, cyp);
     const float fx = (float)(s - ox) + subpixel_offset(inx, cxm, c0, cxp);
     a.fy[fo] = fy;

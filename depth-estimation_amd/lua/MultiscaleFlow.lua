@@ -3,6 +3,8 @@
 -- getModelMultiscale (opticalflow_model_multiscale.lua:196-229): ONE C call, no per-scale Torch tensors.
 --   local msflow = require 'MultiscaleFlow'
 --   local out = msflow.forwardFlow(geometry, model, I0, I1)    -- {index = LongTensor HxW, y, x, full = 2 x H x W, confidences}
+--   local out = msflow.forwardFlow(geometry, model, I0, I1, true)   -- raw-patch model: the sub-pixel flow (not in the reference;
+--      include/dfe.h: dfe_multiscale_flow_pair_subpixel_f32): y_sub, x_sub = FloatTensor HxW, full carries them; index, y, x as without
 -- The weights are read from model:getWeights() on every call ('layer<i>' when geometry.share_filters, else
 -- 'scale<r>_layer<i>', opticalflow_model_multiscale.lua:347-370) and the biases from the filter modules themselves
 -- (getWeights lists no biases, opticalflow_model.lua:66-76), so a loadModel'ed or freshly trained model needs no conversion.
@@ -16,7 +18,7 @@ local function filter_of_scale(model, i)   -- processors[i].modules[1].modules[1
    return model.pyramid.processors[i].modules[1].modules[1].modules[3]
 end
 
-function M.forwardFlow(geometry, model, I0, I1)
+function M.forwardFlow(geometry, model, I0, I1, subpixel)
    dfe.checktype(I0, 'torch.FloatTensor', 'forwardFlow: I0'); dfe.checktype(I1, 'torch.FloatTensor', 'forwardFlow: I1')
    local C, H, W = I0:size(1), I0:size(2), I0:size(3)
    local rmax = geometry.ratios[#geometry.ratios]
@@ -28,10 +30,12 @@ function M.forwardFlow(geometry, model, I0, I1)
    end
    local nr = #geometry.ratios
    local ratios = ffi.new('int[?]', nr, geometry.ratios)
+   local learned = geometry.layers and #geometry.layers > 0
+   if subpixel and learned then error('forwardFlow: subpixel needs the raw-patch model (no learned filters)') end
    local d0, d1 = dfe.upload(I0, B.i0), dfe.upload(I1, B.i1)
    local dflow = ffi.cast('float*', B.flow:reserve(2 * H * W * 4))
    local didx = ffi.cast('int64_t*', B.idx:reserve(H * W * 8))
-   if geometry.layers and #geometry.layers > 0 then
+   if learned then
       local nstacks = geometry.share_filters and 1 or nr
       local layers, nl, k = nil, 0, 0
       for s = 1, nstacks do
@@ -60,12 +64,25 @@ function M.forwardFlow(geometry, model, I0, I1)
       dfe.check(dfe.lib.dfe_multiscale_flow_pair_filtered_f32(dfe.ctx, d0, d1, C, H, W, geometry.maxh, geometry.maxw, ratios, nr, layers, nl,
                                                              geometry.share_filters and 1 or 0, 0, dflow, didx))
    else
-      dfe.check(dfe.lib.dfe_multiscale_flow_pair_f32(dfe.ctx, d0, d1, C, H, W, geometry.hKernel, geometry.maxh, geometry.maxw, ratios, nr, dflow, didx))
+      local fn = subpixel and dfe.lib.dfe_multiscale_flow_pair_subpixel_f32 or dfe.lib.dfe_multiscale_flow_pair_f32
+      dfe.check(fn(dfe.ctx, d0, d1, C, H, W, geometry.hKernel, geometry.maxh, geometry.maxw, ratios, nr, dflow, didx))
    end
    local full, index = torch.FloatTensor(2, H, W), torch.LongTensor(H, W)
    dfe.download(full, dflow); dfe.download(index, didx)
-   return {index = index, y = full[1]:long(), x = full[2]:long(), full = full, confidences = torch.FloatTensor(H, W):fill(1),
-           full_confidences = torch.FloatTensor(H, W):fill(1)}
+   local out = {index = index, full = full, confidences = torch.FloatTensor(H, W):fill(1), full_confidences = torch.FloatTensor(H, W):fill(1)}
+   if subpixel then   -- y, x: the integer flow, decoded from the class ids (the refined flow is within r / 2 of it)
+      local y, x = torch.LongTensor(H, W), torch.LongTensor(H, W)
+      local oy, ox = ffi.new('int64_t[1]'), ffi.new('int64_t[1]')
+      local ip, yp, xp = index:data(), y:data(), x:data()
+      for i = 0, H * W - 1 do
+         dfe.lib.dfe_x2yx_multi_number(geometry.maxh, geometry.maxw, ratios, nr, ip[i], oy, ox)
+         yp[i], xp[i] = oy[0], ox[0]
+      end
+      out.y, out.x, out.y_sub, out.x_sub = y, x, full[1], full[2]
+   else
+      out.y, out.x = full[1]:long(), full[2]:long()
+   end
+   return out
 end
 
 return M

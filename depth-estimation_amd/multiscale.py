@@ -377,16 +377,27 @@ class MultiscaleModel(Module):
         self.output = out
         return out
 
-    def forwardFlow(self, input, process_full=True, one_call=True, f16_scale=None):
+    def forwardFlow(self, input, process_full=True, one_call=True, f16_scale=None, subpixel=False):
         """model:forward(input) followed by processOutput(geometry, output, process_full) for the 'max' extraction
         without a threshold (opticalflow_model.lua:201-252), fused: the H x W x nclasses tensor is never built
         (dfe_cascade_flow_f32).  Returns the same table: index, confidences (all 1), y, x [, full, full_confidences].
         one_call: everything inside ONE C call (dfe_multiscale_flow_pair_f32 / _f16 / _filtered_f32).
         f16_scale: the per-scale cost volumes are stored as half(cost * f16_scale) (the staged path rounds its fp32 volumes to
-        half precision the same way)."""
+        half precision the same way).
+        subpixel (raw-patch model, square patches, fp32 volumes; not in the reference): the flow is refined per axis by the parabola
+        through the winning cell's cost and its two neighbours' at the winning scale (include/dfe.h:
+        dfe_multiscale_flow_pair_subpixel_f32, or dfe_multiscale_refine_subpixel_f32 behind the staged path).  The table gains y_sub, x_sub
+        (float32 [H][W]) and full carries them; index, y, x and the confidences are those of subpixel=False."""
         g = self.geometry
         maxh, maxw = _g(g, "maxh"), _g(g, "maxw")
         kh, kw = self._hk()
+        if subpixel:
+            if self.filters is not None or self.prefiltered:
+                raise ValueError("MultiscaleModel.forwardFlow: subpixel=True needs the raw-patch model (no learned filters, not prefiltered)")
+            if f16_scale:
+                raise ValueError("MultiscaleModel.forwardFlow: subpixel=True is not available with f16_scale")
+            if kh != kw:
+                raise ValueError("MultiscaleModel.forwardFlow: subpixel=True needs square patches, got %d x %d" % (kh, kw))
         l = lib()
         N = maxh * maxw
         rr, n = ratios_array(self.ratios)
@@ -407,7 +418,8 @@ class MultiscaleModel(Module):
             elif f16_scale:
                 ctx.check(l.dfe_multiscale_flow_pair_f16(ctx.handle, ptr(i0), ptr(i1), Cc, H, W, kh, maxh, maxw, rr, n, float(f16_scale), ptr(flow), ptr(idx)))
             else:
-                ctx.check(l.dfe_multiscale_flow_pair_f32(ctx.handle, ptr(i0), ptr(i1), Cc, H, W, kh, maxh, maxw, rr, n, ptr(flow), ptr(idx)))
+                fn = l.dfe_multiscale_flow_pair_subpixel_f32 if subpixel else l.dfe_multiscale_flow_pair_f32
+                ctx.check(fn(ctx.handle, ptr(i0), ptr(i1), Cc, H, W, kh, maxh, maxw, rr, n, ptr(flow), ptr(idx)))
             fy, fx = flow[0], flow[1]
             self.volumes, self.probs = None, None
         else:
@@ -419,9 +431,22 @@ class MultiscaleModel(Module):
             fy = torch.empty((H, W), dtype=torch.float32, device=dev)
             fx = torch.empty_like(fy)
             ctx.check(l.dfe_cascade_flow_f32(ctx.handle, _ptr_array(self.probs), rr, n, H, W, maxh, maxw, ptr(idx), None, ptr(fy), ptr(fx)))
+            if subpixel:   # the stand-alone refinement of the staged path's class map, on the frames padded as _volumes pads them
+                i0, i1 = input
+                i0, i1 = _f32c(i0, "MultiscaleModel: input[1]"), _f32c(i1, "MultiscaleModel: input[2]")
+                i0, i1, H2, W2 = _pad_to_multiple(i0, i1, self.ratios[-1])
+                assert (H2, W2) == (H, W)
+                flow = torch.stack([fy, fx])
+                ctx.check(l.dfe_multiscale_refine_subpixel_f32(ctx.handle, ptr(i0), ptr(i1), i0.shape[0], H, W, kh, maxh, maxw, rr, n, ptr(idx), ptr(flow)))
+                fy, fx = flow[0], flow[1]
         dev = idx.device
-        ret = {"index": idx, "confidences": torch.ones((H, W), dtype=torch.float32, device=dev),
-               "y": fy.to(torch.int64), "x": fx.to(torch.int64)}
+        ret = {"index": idx, "confidences": torch.ones((H, W), dtype=torch.float32, device=dev)}
+        if subpixel:   # y, x: the integer flow (the refined one is within r / 2 of d r: not recoverable by rounding where r > 1)
+            ret["y"], ret["x"] = torch.empty_like(idx), torch.empty_like(idx)
+            ctx.check(l.dfe_x2yx_multi(ctx.handle, maxh, maxw, rr, n, ptr(idx), H * W, ptr(ret["y"]), ptr(ret["x"]), 0))
+            ret["y_sub"], ret["x_sub"] = fy, fx
+        else:
+            ret["y"], ret["x"] = fy.to(torch.int64), fx.to(torch.int64)
         if process_full:
             hImg, wImg = _g(g, "hImg"), _g(g, "wImg")
             ho, wo = (hImg - H) // 2, (wImg - W) // 2

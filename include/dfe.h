@@ -576,6 +576,30 @@ int dfe_flow_depth_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, i
  * at the load), so the results are bit-identical to the fp32 entries on the converted frames. */
 int dfe_multiscale_flow_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int maxh, int maxw,
                                 const int *ratios, int nratios, float scale, float f16_scale, float *flow, int64_t *idx);
+/* ---- sub-pixel flow for the raw-patch pyramid matcher (NOT in the reference: its flow is d * r for a whole cell d) --------------- */
+/* For a pixel (y, x) with class id `id`: id decodes (x2yxMultiNumber, dfe_x2yx_multi) to a scale s with ratio r and a cell (a, b) of
+ * that scale's maxh x maxw window; the integer displacement is ((a + 1 - chh) r, (b + 1 - chw) r), chh = (maxh + 1) / 2, chw alike.
+ * cost(a', b') is the fp32 SSD of dfe_pyramid_scale_volume_f32 for scale s at the scale's pixel (y / r, x / r) and cell (a', b') --
+ * the value that volume holds, inside the ring hole of a coarse scale too.  Per axis (x shown; y alike with a -+ 1), in fp32:
+ *   c0 = cost(a, b), cm = cost(a, b-1), cp = cost(a, b+1);
+ *   off = 0 if b-1 < 0 or b+1 >= maxw (a neighbour outside the window);
+ *   else den = (cm - c0) + (cp - c0); off = den > 0 ? clamp((cm - cp) / (2 den), -0.5, 0.5) : 0   (the single-scale rule above);
+ *   fx = (float)(dx r) + (float)r * off   (product and sum separately rounded).
+ * The class id, and with it the integer flow, never changes; the refined flow is within r / 2 of it per axis.  The costs are fp32
+ * sums over the prepared (down-sampled, zero-padded) scale frames, whatever form the matcher stored its volumes in: where every cost
+ * of a frame pair is exactly representable in fp32 the result is defined bit for bit, else up to the rounding of the costs.
+ * dfe_multiscale_flow_pair_subpixel_f32 / _u8: the arguments of dfe_multiscale_flow_pair_f32 / _u8; the matcher runs unchanged, then
+ *   flow (required) is refined in place; idx (optional) is the matcher's.
+ * dfe_multiscale_refine_subpixel_f32: the refinement alone, from any 1-based class map idx [H][W] (the staged path's
+ *   dfe_cascade_flow_f32 / dfe_argbest_center, or another producer) into flow [2][H][W]; it prepares the padded scales itself.
+ *   Pixels whose idx is not a class id keep what flow held. */
+int dfe_multiscale_flow_pair_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw,
+                                          const int *ratios, int nratios, float *flow, int64_t *idx);
+int dfe_multiscale_flow_pair_subpixel_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int maxh,
+                                         int maxw, const int *ratios, int nratios, float scale, float f16_scale, float *flow,
+                                         int64_t *idx);
+int dfe_multiscale_refine_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw,
+                                       const int *ratios, int nratios, const int64_t *idx, float *flow);
 /* ---- pipelined ingest: the frame loop's host boundary --------------------------------------------------------------------------- */
 /* replaces: the serial load -> filter -> match of depth_estimation_opticalflow.lua:66-150 (loader:getNextFrame, then the model) where
  *   frames arrive in HOST memory.  dfe_ingest_submit_u8 starts the upload of a uint8 frame pair (nbytes per frame; pinned host memory --
