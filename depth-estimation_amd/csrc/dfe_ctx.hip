@@ -14,7 +14,7 @@ const DfeOptName dfe_opt_names[DFE_NOPT] = {
     {"fm_rows", "DFE_FM_ROWS", false},         {"sweep_ovh", "DFE_SWEEP_OVH", false},         {"sweep_blocks", "DFE_SWEEP_BLOCKS", false},
     {"debug_arena", "DFE_DEBUG_ARENA", false}, {"fm_flat", "DFE_FM_FLAT", false},             {"fm_split", "DFE_FM_SPLIT", false},
     {"conv_narrow", "DFE_CONV_NARROW", false}, {"conv_mfma", "DFE_CONV_MFMA", false},         {"fm_mfma", "DFE_FM_MFMA", false},
-    {"arena_contig", "DFE_ARENA_CONTIG", false}, {"cv_novol", "DFE_CV_NOVOL", false},
+    {"arena_contig", "DFE_ARENA_CONTIG", false}, {"cv_novol", "DFE_CV_NOVOL", false},       {"conv_nt", "DFE_CONV_NT", false},
 };
 
 int dfe_fail(dfe_ctx *ctx, int code, const char *fmt, ...) {

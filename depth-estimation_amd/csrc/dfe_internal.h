@@ -34,6 +34,7 @@ enum DfeOpt {
     DFE_OPT_FM_MFMA,          // feature matcher as a banded GEMM on the matrix cores, |a|^2 + |b|^2 - 2 a.b (default 0 = exact k-ordered sums)
     DFE_OPT_ARENA_CONTIG,     // scratch arena from physically contiguous memory (hipDeviceMallocContiguous; 0: plain hipMalloc)
     DFE_OPT_CV_NOVOL,         // single-scale flow step without its cost volume (volume-free sweep; 0: build the volume, finalize reads it)
+    DFE_OPT_CONV_NT,          // batched convolution: n > 0 = n output planes per thread where nOut % n == 0 and <kW, n> is instantiated (tests)
     DFE_NOPT
 };
 struct DfeOptName { const char *key; const char *env; bool env_presence_means_zero; };

@@ -242,6 +242,18 @@ __global__ __launch_bounds__(256) void conv_batch_kernel(ConvBatch cb, int nIn, 
     }
 }
 
+// ctx->last_kernel names the instantiation: "conv_batch_kernel<KW,NT>", then "+tanh" with the tanh epilogue, then "+narrow" for 64 x 16
+// tiles -- e.g. "conv_batch_kernel<5,10>+tanh+narrow".  false: nothing was launched (the tiles of all input planes exceed 64 KB of LDS, or
+// the runtime refuses the size) and the caller's direct kernel names itself.
+template <int KW, int NT> static const char *conv_batch_name(bool tanh_after, bool narrow) {
+    struct Names {
+        char s[4][48];
+        Names() { for (int v = 0; v < 4; ++v) snprintf(s[v], sizeof s[v], "conv_batch_kernel<%d,%d>%s%s", KW, NT, (v & 1) ? "+tanh" : "", (v & 2) ? "+narrow" : ""); }
+    };
+    static const Names names;
+    return names.s[(tanh_after ? 1 : 0) | (narrow ? 2 : 0)];
+}
+
 template <int KW, int NT>
 static bool launch_conv_batch(dfe_ctx *ctx, const ConvBatch &cb, int n, int nIn, int nOut, int kH, int tanh_after, int maxblocks) {
     const int groups = nOut / NT;
@@ -263,6 +275,7 @@ static bool launch_conv_batch(dfe_ctx *ctx, const ConvBatch &cb, int n, int nIn,
     for (int e = 0; e < n; ++e) c2.blk0[e + 1] = c2.blk0[e] + dfe_cdiv(cb.W[e] - KW + 1, TW) * dfe_cdiv(cb.H[e] - kH + 1, TH) * groups;
     (void)maxblocks;
     hipLaunchKernelGGL(kern, dim3(c2.blk0[n]), dim3(256), lds, ctx->stream, c2, nIn, nOut, kH, groups);
+    ctx->last_kernel = conv_batch_name<KW, NT>(tanh_after != 0, narrow);
     return true;
 }
 
@@ -296,11 +309,18 @@ static int conv_batch_try(dfe_ctx *ctx, int n, const float *const *in, const dfe
         const bool narrow_k = ctx->opt_bool(DFE_OPT_CONV_NARROW, L0.kW >= 9 && L0.kH >= 9);   // (the tile shape launch_conv_batch picks)
         for (int e = 0; e < n; ++e) tiles += (long long)dfe_cdiv(W[e] - L0.kW + 1, narrow_k ? 64 : 128) * dfe_cdiv(H[e] - L0.kH + 1, narrow_k ? 16 : 8);
         const int cand[6] = {10, 8, 5, 4, 2, 1};
+        const int forced = ctx->opt[DFE_OPT_CONV_NT];   // option conv_nt (tests): this count for every layer that can take it, whatever the frame size
         int nt = 0;
-        for (int c = 0; c < 6; ++c) {
+        bool taken = false;
+        for (int c = 0; c < 6 && !taken; ++c) {
+            if (L0.nOut % cand[c]) continue;
+            if (L0.kW == 17 && (cand[c] == 10 || cand[c] == 5 || cand[c] == 1)) continue;     // (instantiated for 17 x 17: 8, 4, 2)
+            if (cand[c] == forced) { nt = forced; taken = true; }
+        }
+        for (int c = 0; c < 6 && !taken; ++c) {
             if (L0.nOut % cand[c]) continue;
             if (cand[c] == 10 && ctx->opt[DFE_OPT_CONV_NT10] == 0) continue;
-            if (L0.kW == 17 && (cand[c] == 10 || cand[c] == 5 || cand[c] == 1)) continue;     // (instantiated for 17 x 17: 8, 4, 2)
+            if (L0.kW == 17 && (cand[c] == 10 || cand[c] == 5 || cand[c] == 1)) continue;
             nt = cand[c];
             if (tiles * (L0.nOut / nt) >= 2ll * ctx->ncu) break;
         }
@@ -361,6 +381,7 @@ int dfe_filter_layer_forward(dfe_ctx *ctx, const float *in, const dfe_filter_lay
         hipLaunchKernelGGL(conv_layer_kernel<true>, dim3(g), dim3(256), 0, ctx->stream, in, L.weight, L.bias, (const int *)L.conn, L.nConn, L.nIn, L.nOut, H, W, L.kH, L.kW, out);
     else
         hipLaunchKernelGGL(conv_layer_kernel<false>, dim3(g), dim3(256), 0, ctx->stream, in, L.weight, L.bias, (const int *)L.conn, L.nConn, L.nIn, L.nOut, H, W, L.kH, L.kW, out);
+    ctx->last_kernel = "conv_layer_kernel";
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -385,6 +406,7 @@ int dfe_spatial_convolution_f32(dfe_ctx *ctx, const float *in, const float *weig
     }
     hipLaunchKernelGGL(conv_kernel, dim3(grid_n((long long)nOut * (H - kH + 1) * (W - kW + 1))), dim3(256), 0, ctx->stream, in, weight, bias,
                        nIn, nOut, H, W, kH, kW, out);
+    ctx->last_kernel = "conv_kernel";
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -416,6 +438,7 @@ int dfe_spatial_convolution_map_f32(dfe_ctx *ctx, const float *in, const float *
                 "dfe_spatial_convolution_map_f32: %d connections %d->%d planes, %dx%d kernel on %dx%d", nConn, nIn, nOut, kH, kW, H, W);
     hipLaunchKernelGGL(conv_map_kernel, dim3(grid_n((long long)nOut * (H - kH + 1) * (W - kW + 1))), dim3(256), 0, ctx->stream, in, weight,
                        bias, conn, nConn, nOut, H, W, kH, kW, out);
+    ctx->last_kernel = "conv_map_kernel";
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }

@@ -78,7 +78,7 @@ int dfe_set_cost_volume_tile(dfe_ctx *ctx, int tyq);
 /* Behaviour switches of the launchers (tuning and tests; none is needed for correct results -- every choice has a parity test or is
  * a pure scheduling choice).  value >= 0 forces, -1 restores the launcher's own choice per shape.  Keys: "cascade_px", "fine_fuse",
  * "mid_fuse", "fine_nq", "mid_nq", "prep_tiles", "xpose", "xpose_nt", "soft_epilogue", "conv_batch", "conv_nt10", "fm64", "fm_rows",
- * "sweep_ovh", "sweep_blocks", "debug_arena", "fm_flat", "fm_split", "conv_narrow", "conv_mfma", "fm_mfma", "arena_contig", "graphs", "cv_novol".  The library reads the environment ONCE, in dfe_ctx_create
+ * "sweep_ovh", "sweep_blocks", "debug_arena", "fm_flat", "fm_split", "conv_narrow", "conv_mfma", "fm_mfma", "arena_contig", "graphs", "cv_novol", "conv_nt".  The library reads the environment ONCE, in dfe_ctx_create
  * (DFE_<KEY> variables of the tuning scripts) -- never inside an op, so an op's behaviour depends on its ctx only.
  * Two keys trade the exact arithmetic for the matrix cores, both OFF unless set to 1: "conv_mfma" (the one-call models' filter layers as
  * implicit GEMMs, v_mfma_f32_16x16x4_f32: the reference's (input plane, ky, kx) order with FUSED multiply-adds, <= 1e-5 relative to
@@ -89,7 +89,9 @@ int dfe_set_cost_volume_tile(dfe_ctx *ctx, int tyq);
  * replaces: the option tables the reference's drivers pass down (opticalflow.lua:138-198 `geometry`), for the switches that have no
  * counterpart there.  "cv_novol" (default 1): the single-scale flow step (dfe_ssd_flow_f32, dfe_flow_depth_pair_f32) of 3-channel frames,
  * 7 x 7 patch, 33 x 33 window builds no cost volume -- one launch whatever the frame size, bit-identical outputs; 0 materialises the
- * volume in ctx scratch (bands of dfe_set_scratch_limit) and the finalize reads it.  Unknown key: DFE_E_ARG. */
+ * volume in ctx scratch (bands of dfe_set_scratch_limit) and the finalize reads it.  "conv_nt" (tests): n > 0 makes the batched convolution
+ * give a thread n output planes in every layer whose plane count n divides and whose kernel width is built with n; other layers keep the
+ * automatic choice.  Unknown key: DFE_E_ARG. */
 int dfe_set_option(dfe_ctx *ctx, const char *key, int value);
 int dfe_get_option(dfe_ctx *ctx, const char *key, int *value);
 /* name of the kernel the last cost-volume call launched (static string) */

@@ -29,6 +29,21 @@ def conv(x, w, b, conn=None, nOut=None):
     return torch.stack([sum(p, zero) for p in planes]) + b[:, None, None]
 
 
+def spatial_convolution64(x, w, b=None):
+    """nn.SpatialConvolution's forward in float64 numpy, from its definition: out[o][y][x] = b[o] + sum_{i,u,v} w[o][i][u][v] in[i][y+u][x+v].
+    Returns (value, sum|w . in| + |b|): the second bounds the rounding error of any float32 summation order -- T + 1 sequentially added,
+    separately rounded terms are within (T + 1) 2^-24 of it, T = nIn kH kW."""
+    x, w = np.asarray(x, np.float64), np.asarray(w, np.float64)
+    kH, kW = w.shape[2], w.shape[3]
+    win = np.lib.stride_tricks.sliding_window_view(x, (kH, kW), axis=(1, 2))          # [nIn][Ho][Wo][kH][kW]
+    val = np.einsum("oiuv,iyxuv->oyx", w, win, optimize=True)
+    mag = np.einsum("oiuv,iyxuv->oyx", np.abs(w), np.abs(win), optimize=True)
+    if b is not None:
+        b = np.asarray(b, np.float64)
+        val, mag = val + b[:, None, None], mag + np.abs(b)[:, None, None]
+    return val, mag
+
+
 def conv_backward(x, w, go, conn=None, nOut=None, dtype=torch.float64):
     """(gradInput, gradWeight, gradBias) by autograd, from zero"""
     x, w, go = t64(x, dtype).requires_grad_(), t64(w, dtype).requires_grad_(), t64(go, dtype)
