@@ -68,7 +68,8 @@ __global__ void undistort_kernel(const float *__restrict__ img, int C, int H, in
     }
 }
 
-// partial sums of the FOE normal equations over pixels with |flow| >= min_flow and conf > 0:
+// partial sums of the FOE normal equations over pixels with a finite |flow| >= min_flow, |flow| > 0 and conf > 0 (a NaN in the flow
+// or the confidence fails every comparison, so it is skipped; a zero vector has no line to intersect):
 //   n = (-v, u)/|flow| (unit normal of the flow line through p), residual r = n . (c - p), weight w
 //   A = sum w n n^T, b = sum w n (n . p)  ->  5 doubles per block: Axx, Axy, Ayy, bx, by
 __global__ __launch_bounds__(256) void foe_sums_kernel(const float *__restrict__ fy, const float *__restrict__ fx, const float *__restrict__ conf, int H,
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(256) void foe_sums_kernel(const float *__restrict__
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < P; e += (long long)gridDim.x * 256) {
         const float u = fx[e], v = fy[e];
         const float mag = sqrtf(u * u + v * v);
-        if (mag < min_flow || (conf && conf[e] <= 0.f)) continue;
+        if (!(mag >= min_flow) || !(mag > 0.f) || !(mag < INFINITY) || (conf && !(conf[e] > 0.f))) continue;
         const int y = (int)(e / W), x = (int)(e - (long long)y * W);
         const double nx = -v / mag, ny = u / mag;
         double w = 1.0;
@@ -143,6 +144,15 @@ int dfe_remove_ego_motion_f32(dfe_ctx *ctx, const float *img, int C, int H, int 
     }
     mat3_mul(K9, Ru, t);
     mat3_mul(t, Ki, Hd);
+    {   // an entry below the rounding error of its own sum of products is noise: 0.  (K I K^-1 is the identity only up to such entries,
+        // and a -1e-17 in the offset column puts the source of column 0 outside the frame.)
+        double aK[9], aR[9], aKi[9], at[9], aH[9];
+        for (int i = 0; i < 9; ++i) { aK[i] = fabs(K9[i]); aR[i] = fabs(Ru[i]); aKi[i] = fabs(Ki[i]); }
+        mat3_mul(aK, aR, at);
+        mat3_mul(at, aKi, aH);
+        for (int i = 0; i < 9; ++i)
+            if (fabs(Hd[i]) <= 16 * 2.220446049250313e-16 * aH[i]) Hd[i] = 0;
+    }
     Mat3 Hm;
     for (int i = 0; i < 9; ++i) Hm.m[i] = (float)Hd[i];
     hipLaunchKernelGGL(homography_warp_kernel, dim3(grid_e((long long)H * W)), dim3(256), 0, ctx->stream, img, C, H, W, Hm, out, mask);

@@ -134,21 +134,23 @@ __host__ __device__ inline unsigned ego_rand(unsigned seed, unsigned h, unsigned
 struct EgoK { double Ki[9]; };
 
 // one thread per hypothesis: 8 distinct valid correspondences -> E on the essential manifold -> F in pixels.  hypF[h][9] (all zero:
-// no model, scores no inlier)
-__global__ __launch_bounds__(64) void ego_hypotheses_kernel(const float *__restrict__ p1, const float *__restrict__ p2, const float *__restrict__ w, int N,
+// no model, scores no inlier).  Draws are taken among the M valid correspondences: valid[] lists their indices in index order
+// (NULL: all N are valid, M = N), so that a sparse weight vector costs no draws and cannot exhaust the tries.
+__global__ __launch_bounds__(64) void ego_hypotheses_kernel(const float *__restrict__ p1, const float *__restrict__ p2, const int *__restrict__ valid, int M,
                                                            EgoK kk, unsigned seed, int nh, double *__restrict__ hypF) {
     const int h = blockIdx.x * 64 + threadIdx.x;
     if (h >= nh) return;
     double *Fo = hypF + (size_t)h * 9;
     for (int i = 0; i < 9; ++i) Fo[i] = 0;
+    if (M < 8) return;                                     // too few valid correspondences
     int pick[8];
     unsigned k = 0;
     for (int n = 0; n < 8; ++n) {
         int tries = 0;
         for (;; ++tries) {
-            if (tries > 64) return;                        // too few valid correspondences
-            const int c = (int)(ego_rand(seed, (unsigned)h, k++) % (unsigned)N);
-            if (w && !(w[c] > 0.f)) continue;
+            if (tries > 64) return;                        // (64 repeats in a row: only when M is 8 or little more)
+            const int d = (int)(ego_rand(seed, (unsigned)h, k++) % (unsigned)M);
+            const int c = valid ? valid[d] : d;
             bool dup = false;
             for (int m = 0; m < n; ++m) dup = dup || pick[m] == c;
             if (!dup) { pick[n] = c; break; }
@@ -280,8 +282,8 @@ int cheirality(const double *R, const double *t, const std::vector<float> &p1, c
 }
 
 // arena layout behind `scr_off` bytes of the caller's own data: hypotheses' F, their inlier counts, the best F, the inlier mask, the
-// refit partial sums
-struct EgoLayout { size_t off_f, off_c, off_b, off_m, off_p, total; int nblk; };
+// refit partial sums, the indices of the valid correspondences
+struct EgoLayout { size_t off_f, off_c, off_b, off_m, off_p, off_v, total; int nblk; };
 EgoLayout ego_layout(int N, int nh, size_t scr_off) {
     EgoLayout l;
     l.nblk = N < 256 * 64 ? (N + 255) / 256 : 64;
@@ -290,12 +292,14 @@ EgoLayout ego_layout(int N, int nh, size_t scr_off) {
     l.off_b = l.off_c + ((size_t)nh * 4 + 255) / 256 * 256;
     l.off_m = l.off_b + 256;
     l.off_p = l.off_m + ((size_t)N + 255) / 256 * 256;
-    l.total = l.off_p + (size_t)l.nblk * 46 * 8;
+    l.off_v = l.off_p + ((size_t)l.nblk * 46 * 8 + 255) / 256 * 256;
+    l.total = l.off_v + (size_t)N * 4;
     return l;
 }
 
-int ego_from_points(dfe_ctx *ctx, const float *p1, const float *p2, const float *w, int N, const double *K9, double max_dist, int iterations, unsigned seed,
-                    double *R9, double *T3, int *n_inliers, double *F9, size_t scr_off) {
+// hw: the host's copy of the weights w (NULL with w)
+int ego_from_points(dfe_ctx *ctx, const float *p1, const float *p2, const float *w, const float *hw, int N, const double *K9, double max_dist, int iterations,
+                    unsigned seed, double *R9, double *T3, int *n_inliers, double *F9, size_t scr_off) {
     EgoK kk;
     DFE_REQUIRE(ctx, mat3_inv_d(K9, kk.Ki), DFE_E_ARG, "ego motion: K is singular");
     const int nh = iterations;
@@ -312,7 +316,18 @@ int ego_from_points(dfe_ctx *ctx, const float *p1, const float *p2, const float 
     double *bestF = (double *)((char *)scr + off_b);
     unsigned char *mask = (unsigned char *)scr + off_m;
     double *part = (double *)((char *)scr + off_p);
-    hipLaunchKernelGGL(ego_hypotheses_kernel, dim3((nh + 63) / 64), dim3(64), 0, ctx->stream, p1, p2, w, N, kk, seed, nh, hypF);
+    // the valid correspondences, listed on the host in index order (deterministic, unlike a compaction by atomics)
+    int *valid = nullptr, M = N;
+    std::vector<int> hv;
+    if (w) {
+        hv.reserve(N);
+        for (int n = 0; n < N; ++n)
+            if (hw[n] > 0.f) hv.push_back(n);
+        M = (int)hv.size();
+        valid = (int *)((char *)scr + lay.off_v);
+        if (M > 0) DFE_HIP(ctx, hipMemcpyAsync(valid, hv.data(), (size_t)M * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    hipLaunchKernelGGL(ego_hypotheses_kernel, dim3((nh + 63) / 64), dim3(64), 0, ctx->stream, p1, p2, (const int *)valid, M, kk, seed, nh, hypF);
     hipLaunchKernelGGL(ego_score_kernel, dim3(nh), dim3(256), 0, ctx->stream, p1, p2, w, N, (const double *)hypF, max_dist * max_dist, counts);
     DFE_LAUNCH_CHECK(ctx);
     std::vector<int> hc(nh);
@@ -391,7 +406,13 @@ int dfe_ego_motion_from_points_f32(dfe_ctx *ctx, const float *pts1, const float 
     DFE_REQUIRE(ctx, pts1 && pts2 && K9 && R9 && T3, DFE_E_ARG, "dfe_ego_motion_from_points_f32: NULL argument");
     DFE_REQUIRE(ctx, N >= 8 && iterations >= 1 && iterations <= 65536 && ransac_max_dist > 0, DFE_E_ARG,
                 "dfe_ego_motion_from_points_f32: N=%d (>= 8) iterations=%d (1..65536) ransac_max_dist=%g", N, iterations, ransac_max_dist);
-    return ego_from_points(ctx, pts1, pts2, weights, N, K9, ransac_max_dist, iterations, seed, R9, T3, n_inliers, F9, 0);
+    std::vector<float> hw;
+    if (weights) {
+        hw.resize(N);
+        DFE_HIP(ctx, hipMemcpyAsync(hw.data(), weights, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
+        DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return ego_from_points(ctx, pts1, pts2, weights, weights ? hw.data() : nullptr, N, K9, ransac_max_dist, iterations, seed, R9, T3, n_inliers, F9, 0);
 }
 
 int dfe_ego_motion_from_flow_f32(dfe_ctx *ctx, const float *flow_y, const float *flow_x, const float *conf, int H, int W, const double *K9, int max_points,
@@ -413,16 +434,16 @@ int dfe_ego_motion_from_flow_f32(dfe_ctx *ctx, const float *flow_y, const float 
     float *p1 = (float *)scr, *p2 = p1 + 2 * (size_t)N, *w = p2 + 2 * (size_t)N;
     hipLaunchKernelGGL(ego_sample_flow_kernel, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, flow_y, flow_x, conf, H, W, step, y0, x0, gh, gw, p1, p2, w);
     DFE_LAUNCH_CHECK(ctx);
+    std::vector<float> hw(N);
+    DFE_HIP(ctx, hipMemcpyAsync(hw.data(), w, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
+    DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (n_found) {
-        std::vector<float> hw(N);
-        DFE_HIP(ctx, hipMemcpyAsync(hw.data(), w, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
-        DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
         int c = 0;
         for (int n = 0; n < N; ++n) c += hw[n] > 0.f;
         *n_found = c;
         DFE_REQUIRE(ctx, c >= 8, DFE_E_ARG, "dfe_ego_motion_from_flow_f32: only %d usable flow samples", c);
     }
-    return ego_from_points(ctx, p1, p2, w, N, K9, ransac_max_dist, iterations, seed, R9, T3, n_inliers, F9, pts_bytes);
+    return ego_from_points(ctx, p1, p2, w, hw.data(), N, K9, ransac_max_dist, iterations, seed, R9, T3, n_inliers, F9, pts_bytes);
 }
 
 }  // extern "C"

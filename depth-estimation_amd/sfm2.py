@@ -55,7 +55,8 @@ def getEpipole(K, T, scale=1.0):
 
 def getFOEFromFlow(flow, confidences=None, min_flow=0.5, iterations=2):
     """Focus of expansion (x, y) of a dense flow field 2 x H x W (plane 0 = y, plane 1 = x, the layout of processOutput's
-    `full`): the point closest to all flow lines, Huber re-weighted `iterations` times.  Also returns the weight sum."""
+    `full`): the point closest to all flow lines, Huber re-weighted `iterations` times.  Also returns the weight sum.  Skipped:
+    vectors shorter than min_flow, of non-finite or zero length, and pixels whose confidence is <= 0 or NaN."""
     flow = flow.contiguous()
     _, H, W = flow.shape
     conf = confidences.contiguous() if confidences is not None else None
@@ -71,7 +72,8 @@ def getEgoMotion2(K, flow=None, confidences=None, pts1=None, pts2=None, weights=
     (radial/radial_opticalflow_data.lua:211-217; getEgoMotion: depth_estimation_api.lua:141).  The reference hands over the two
     IMAGES and sfm2 tracks corners itself; here the correspondences are given: either `flow` (2 x H x W, plane 0 = y, 1 = x: the
     matcher's dense flow from frame 1 to frame 2, sampled on a regular grid of at most maxPoints points, `confidences` <= 0
-    skipped) or `pts1` / `pts2` (N x 2 (x, y) pixel positions, `weights` <= 0 skipped).  Returns R (3 x 3 float64 tensor), T (3,
+    or non-finite flow skipped) or `pts1` / `pts2` (N x 2 (x, y) pixel positions, `weights` <= 0 skipped).  The RANSAC draws are
+    taken among the valid correspondences only, however few of the N they are.  Returns R (3 x 3 float64 tensor), T (3,
     |T| = 1), nFound, nInliers, fundmat (3 x 3) with x2 ~ R x1 + T: getEpipole(K, T) is the FOE in the current frame and
     removeEgoMotion(prev, K, R, inverse=True) takes the rotation out of the previous frame."""
     R, T, F = (C.c_double * 9)(), (C.c_double * 3)(), (C.c_double * 9)()

@@ -690,16 +690,19 @@ int dfe_marginal_sum_f32(dfe_ctx *ctx, const float *in, int64_t P, int A, int B,
 int dfe_epipole(const double *K9, const double *T3, double scale, double *e2_xy);
 /* sfm2.removeEgoMotion(img, K, R, 'bilinear') -> warped, mask: out(p) = bilinear(img, K R K^-1 p) (inverse != 0: R^T),
  * mask(p) = 1 where the source lies inside the frame, else 0 (and out = 0).  img / out [C][H][W], mask [H][W] or NULL;
- * K, R row-major host doubles. */
+ * K, R row-major host doubles.  The homography is formed in double; entries below the rounding error of their own sum of products
+ * (16 eps x the sum of the absolute products) are set to 0 before it is rounded to float32, so that R = I gives the identity map. */
 int dfe_remove_ego_motion_f32(dfe_ctx *ctx, const float *img, int C, int H, int W, const double *K9, const double *R9,
                               int inverse, float *out, float *mask);
-/* sfm2.undistortImage(img, K, distP): inverse-map undistortion with the (k1, k2, p1, p2, k3) model of the .cal files. */
+/* sfm2.undistortImage(img, K, distP): inverse-map undistortion with the (k1, k2, p1, p2, k3) model of the .cal files (no skew:
+ * fx, fy, cx, cy of K are used). */
 int dfe_undistort_image_f32(dfe_ctx *ctx, const float *img, int C, int H, int W, const double *K9, const double *dist5,
                             float *out);
 /* NOT IN THE REFERENCE: an estimator of this library for the pure-translation case (the reference obtains the focus of expansion
  * as the epipole K T of sfm2.getEgoMotion2's pose: dfe_ego_motion_from_*_f32 + dfe_epipole below are that route).
- * Focus of expansion of a dense flow field (flow_y, flow_x [H][W]; conf [H][W] or NULL: pixels with conf <= 0 or
- * |flow| < min_flow are skipped): least-squares intersection of the flow lines, `iterations` Huber re-weightings (0..16).
+ * Focus of expansion of a dense flow field (flow_y, flow_x [H][W]; conf [H][W] or NULL: pixels with conf <= 0 or a NaN conf,
+ * with |flow| < min_flow, and vectors of non-finite or zero length are skipped): least-squares intersection of the flow lines,
+ * `iterations` Huber re-weightings (0..16).
  * foe_xy = (x, y) in pixels (host); n_used (may be NULL) = sum of the weights.  DFE_E_ARG when the lines are parallel. */
 int dfe_foe_from_flow_f32(dfe_ctx *ctx, const float *flow_y, const float *flow_x, const float *conf, int H, int W,
                           float min_flow, int iterations, double *foe_xy, double *n_used);
@@ -710,7 +713,8 @@ int dfe_foe_from_flow_f32(dfe_ctx *ctx, const float *flow_y, const float *flow_x
  *   depth_estimation_api.lua:141).  sfm2 (un-vendored, OpenCV) finds and tracks sparse corners itself; here the correspondences
  *   are an INPUT: pts1 / pts2 [N][2] = (x, y) pixel positions in the previous / current frame (device floats; weights [N] or NULL:
  *   entries <= 0 are skipped), or samples of the dense flow the matcher has produced (_from_flow: p2 = p1 + flow(p1) on a centred
- *   regular grid of at most max_points samples, conf <= 0 skipped).  `iterations` 8-point RANSAC hypotheses are built and scored
+ *   regular grid of at most max_points samples, conf <= 0 and non-finite flow skipped).  `iterations` 8-point RANSAC hypotheses are
+ *   built -- each from 8 draws among the VALID correspondences only, so sparse weights cost no draws -- and scored
  *   in parallel on the device (Sampson distance <= ransac_max_dist pixels), the best is refitted over its inliers, projected onto
  *   the essential manifold and decomposed; cheirality picks among the four (R, T).  Restated from the calling convention: parity
  *   unpinned (3P).  Outputs (host doubles): R9 row-major, T3 (|T| = 1) with x2 ~ R x1 + T for camera coordinates of frame 1 in

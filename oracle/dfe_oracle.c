@@ -1098,6 +1098,14 @@ int orc_remove_ego_motion(const float *img, int C, int H, int W, const double *K
     }
     orc_mul3(K9, Ru, t);
     orc_mul3(t, Ki, Hd);
+    {   /* entries below the rounding error of their own sum of products are noise: 0 (K I K^-1 must be the identity) */
+        double aK[9], aR[9], aKi[9], at[9], aH[9];
+        for (int i = 0; i < 9; ++i) { aK[i] = fabs(K9[i]); aR[i] = fabs(Ru[i]); aKi[i] = fabs(Ki[i]); }
+        orc_mul3(aK, aR, at);
+        orc_mul3(at, aKi, aH);
+        for (int i = 0; i < 9; ++i)
+            if (fabs(Hd[i]) <= 16 * 2.220446049250313e-16 * aH[i]) Hd[i] = 0;
+    }
     float Hm[9];
     for (int i = 0; i < 9; ++i) Hm[i] = (float)Hd[i];
     size_t P = (size_t)H * W;
@@ -1143,7 +1151,7 @@ int orc_foe_from_flow(const float *fy, const float *fx, const float *conf, int H
                 size_t e = (size_t)y * W + x;
                 float u = fx[e], v = fy[e];
                 float mag = sqrtf(u * u + v * v);
-                if (mag < min_flow || (conf && conf[e] <= 0.f)) continue;
+                if (!(mag >= min_flow) || !(mag > 0.f) || !(mag < INFINITY) || (conf && !(conf[e] > 0.f))) continue;   /* non-finite or zero length: no line */
                 double nx = -v / mag, ny = u / mag, w = 1.0;
                 if (it > 0) {
                     double r = fabs(nx * ((double)(float)cx - x) + ny * ((double)(float)cy - y));
@@ -1286,14 +1294,17 @@ int orc_ego_motion_from_points(const float *p1, const float *p2, const float *w,
     double bestF[9];
     int bestc = -1;
     const double md2 = max_dist * max_dist;
-    for (int h = 0; h < iterations; ++h) {
+    /* draws are taken among the valid correspondences, listed in index order (as the device code does) */
+    int *valid = (int *)malloc((size_t)N * sizeof(int)), M = 0;
+    for (int n = 0; n < N; ++n)
+        if (!w || w[n] > 0.f) valid[M++] = n;
+    for (int h = 0; h < iterations && M >= 8; ++h) {
         int pick[8], ok = 1;
         unsigned k = 0;
         for (int n = 0; n < 8 && ok; ++n)
             for (int tries = 0;; ++tries) {
                 if (tries > 64) { ok = 0; break; }
-                int c = (int)(orc_ego_rand(seed, (unsigned)h, k++) % (unsigned)N);
-                if (w && !(w[c] > 0.f)) continue;
+                int c = valid[orc_ego_rand(seed, (unsigned)h, k++) % (unsigned)M];
                 int dup = 0;
                 for (int m = 0; m < n; ++m) dup |= pick[m] == c;
                 if (!dup) { pick[n] = c; break; }
@@ -1308,6 +1319,7 @@ int orc_ego_motion_from_points(const float *p1, const float *p2, const float *w,
             if (!w || w[n] > 0.f) c += orc_sampson2(F, p1[2 * n], p1[2 * n + 1], p2[2 * n], p2[2 * n + 1]) <= md2;
         if (c > bestc) { bestc = c; memcpy(bestF, F, sizeof F); }
     }
+    free(valid);
     if (bestc < 8) return -2;
     double A[81] = {0}, Ep[9], U[9], V[9];
     unsigned char *mask = (unsigned char *)calloc((size_t)N, 1);

@@ -176,3 +176,219 @@ def grads(out, leaves, gradOut):
     else:
         out.backward(t64(gradOut, out.dtype).reshape(out.shape))
     return [l.grad for l in leaves]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Ego-motion, rectification and focus of expansion (csrc/egopose.hip, csrc/egomotion.hip), float64 numpy from the definitions
+def sampson64(F, p1, p2):
+    """Sampson distance in pixels of the correspondences p1 -> p2 ([N][2], (x, y)) to the fundamental matrix F (p2^T F p1 = 0):
+    |p2^T F p1| / sqrt((F p1)_1^2 + (F p1)_2^2 + (F^T p2)_1^2 + (F^T p2)_2^2)."""
+    F = np.asarray(F, np.float64)
+    h1 = np.concatenate([np.asarray(p1, np.float64), np.ones((len(p1), 1))], 1)
+    h2 = np.concatenate([np.asarray(p2, np.float64), np.ones((len(p2), 1))], 1)
+    a, b = h1 @ F.T, h2 @ F
+    return np.abs((h2 * a).sum(1)) / np.sqrt(a[:, 0] ** 2 + a[:, 1] ** 2 + b[:, 0] ** 2 + b[:, 1] ** 2)
+
+
+def fund_from_pose64(K, R, T):
+    """F = K^-T [T]x R K^-1 with unit Frobenius norm (x2 ~ R x1 + T)"""
+    K, R, T = np.asarray(K, np.float64), np.asarray(R, np.float64), np.asarray(T, np.float64)
+    Tx = np.array([[0, -T[2], T[1]], [T[2], 0, -T[0]], [-T[1], T[0], 0]])
+    Ki = np.linalg.inv(K)
+    F = Ki.T @ Tx @ R @ Ki
+    return F / np.linalg.norm(F)
+
+
+def pose_fit64(K, p1, p2):
+    """(R, T) with x2 ~ R x1 + T, |T| = 1, by the linear eight-point method over ALL the given correspondences ([N][2] pixels), written
+    with numpy's SVD: rows kron(x2, x1) of the epipolar constraint in camera coordinates, the right singular vector of the smallest
+    singular value, projection onto the essential manifold (singular values 1, 1, 0), the four decompositions, and the one that puts
+    most points in front of both cameras (depths from the least-squares solution of z2 x2 = z1 R x1 + T).  No RANSAC: give it inliers."""
+    Ki = np.linalg.inv(np.asarray(K, np.float64))
+    a = np.concatenate([np.asarray(p1, np.float64), np.ones((len(p1), 1))], 1) @ Ki.T
+    b = np.concatenate([np.asarray(p2, np.float64), np.ones((len(p2), 1))], 1) @ Ki.T
+    A = (b[:, :, None] * a[:, None, :]).reshape(-1, 9)
+    E = np.linalg.svd(A, full_matrices=False)[2][-1].reshape(3, 3)
+    U, _, Vt = np.linalg.svd(E)
+    U, Vt = U * np.sign(np.linalg.det(U)), Vt * np.sign(np.linalg.det(Vt))
+    Wm = np.array([[0.0, -1, 0], [1, 0, 0], [0, 0, 1]])
+    best = None
+    for R in (U @ Wm @ Vt, U @ Wm.T @ Vt):
+        for t in (U[:, 2], -U[:, 2]):
+            ra = a @ R.T
+            # [ra  -b] (z1, z2)^T = -t per point, normal equations
+            m00, m01, m11 = (ra * ra).sum(1), -(ra * b).sum(1), (b * b).sum(1)
+            r0, r1 = -(ra @ t), b @ t
+            det = m00 * m11 - m01 * m01
+            z1, z2 = (r0 * m11 - m01 * r1) / det, (m00 * r1 - m01 * r0) / det
+            good = int(((z1 > 0) & (z2 > 0)).sum())
+            if best is None or good > best[0]:
+                best = (good, R, t)
+    return best[1], best[2]
+
+
+def bilinear64(img, sy, sx):
+    """bilinear sample of img [C][H][W] at float64 (sy, sx), coordinates clamped to the frame, the far neighbour clamped to the last
+    row / column (its weight is 0 there)"""
+    img = np.asarray(img, np.float64)
+    H, W = img.shape[1:]
+    sy, sx = np.clip(sy, 0, H - 1), np.clip(sx, 0, W - 1)
+    y0, x0 = np.floor(sy).astype(np.int64), np.floor(sx).astype(np.int64)
+    y1, x1 = np.minimum(y0 + 1, H - 1), np.minimum(x0 + 1, W - 1)
+    wy, wx = sy - y0, sx - x0
+    top = (1 - wx) * img[:, y0, x0] + wx * img[:, y0, x1]
+    bot = (1 - wx) * img[:, y1, x0] + wx * img[:, y1, x1]
+    return (1 - wy) * top + wy * bot
+
+
+def lipschitz64(img):
+    """(gy, gx): the largest |difference| of vertically / horizontally adjacent pixels of img [C][H][W] -- the Lipschitz constants of its
+    bilinear interpolant along y and x (0 for a single row / column)"""
+    img = np.asarray(img, np.float64)
+    gy = np.abs(np.diff(img, axis=1)).max() if img.shape[1] > 1 else 0.0
+    gx = np.abs(np.diff(img, axis=2)).max() if img.shape[2] > 1 else 0.0
+    return float(gy), float(gx)
+
+
+def local_lipschitz64(img, sy, sx):
+    """per-pixel (gy, gx) [H'][W'] for sources (sy, sx): the largest |difference| of vertically / horizontally adjacent pixels of img
+    [C][H][W] (over the channels) in the source's bilinear cell and the eight cells around it -- a coordinate error far below one pixel
+    cannot leave them, so this is the Lipschitz constant of the interpolant along the way from the exact to the perturbed source.
+    Sources outside the frame (or non-finite) are clamped; their value is not used."""
+    img = np.asarray(img, np.float64)
+    _, H, W = img.shape
+    dy = np.zeros((H + 3, W + 2))                          # dy[1 + y][1 + x] = max_c |img[y+1][x] - img[y][x]|, 0 outside
+    dx = np.zeros((H + 2, W + 3))
+    if H > 1:
+        dy[1:H, 1 : W + 1] = np.abs(np.diff(img, axis=1)).max(0)
+    if W > 1:
+        dx[1 : H + 1, 1:W] = np.abs(np.diff(img, axis=2)).max(0)
+    # vertical differences a 3 x 3 block of cells around (y0, x0) can see: rows y0-1 .. y0+1 (pairs), columns x0-1 .. x0+2; likewise dx
+    my = np.zeros((H, W))
+    mx = np.zeros((H, W))
+    for a in range(3):
+        for b in range(4):
+            my = np.maximum(my, np.pad(dy, ((0, 0), (1, 1)))[a : a + H, b : b + W])
+            mx = np.maximum(mx, np.pad(dx, ((1, 1), (0, 0)))[b : b + H, a : a + W])
+    y0 = np.clip(np.floor(np.nan_to_num(sy, nan=0.0, posinf=0.0, neginf=0.0)), 0, H - 1).astype(np.int64)
+    x0 = np.clip(np.floor(np.nan_to_num(sx, nan=0.0, posinf=0.0, neginf=0.0)), 0, W - 1).astype(np.int64)
+    return my[y0, x0], mx[y0, x0]
+
+
+def homography_warp64(img, K, R, inverse=False):
+    """removeEgoMotion from its definition: out(p) = bilinear(img, Hm p), Hm = K R K^-1 (inverse: R^T), for pixels whose source lies in
+    front of the camera (Z > 0) and inside [0, W-1] x [0, H-1]; 0 elsewhere.  Returns dict(out [C][H][W], val (the sample at the clamped
+    source whatever the mask says: what a pixel on the frame edge carries if it is taken as inside), mask [H][W] bool, sy, sx (the
+    float64 source; NaN / inf where Z = 0), Z, edge = distance of the source to the nearest frame edge in pixels (inf where Z <= 0),
+    cerr_y, cerr_x = a bound on the error of a float32 evaluation of the source coordinates, roundings counted (u = 2^-24, first order,
+    times 1.001 for the rest): X = h0 x + h1 y + h2 with the coefficients rounded to float32 (u per term), two products (u each), the
+    first sum (u on the two products), the second (u on all three): |dX| <= 4 u (|h0 x| + |h1 y|) + 2 u |h2|; a fused multiply-add
+    only removes roundings.  Then sx = X / Z: |dsx| <= (dX + |sx| dZ) / |Z| + u |sx|)."""
+    img = np.asarray(img, np.float64)
+    _, H, W = img.shape
+    K, R = np.asarray(K, np.float64), np.asarray(R, np.float64)
+    Hm = K @ (R.T if inverse else R) @ np.linalg.inv(K)
+    ys, xs = np.mgrid[0:H, 0:W].astype(np.float64)
+    X = Hm[0, 0] * xs + Hm[0, 1] * ys + Hm[0, 2]
+    Y = Hm[1, 0] * xs + Hm[1, 1] * ys + Hm[1, 2]
+    Z = Hm[2, 0] * xs + Hm[2, 1] * ys + Hm[2, 2]
+    aH = np.abs(Hm)
+    u = 1.001 * 2.0 ** -24
+    dX, dY, dZ = (4 * u * (aH[r, 0] * xs + aH[r, 1] * ys) + 2 * u * aH[r, 2] for r in range(3))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sx, sy = X / Z, Y / Z
+        mask = (Z > 0) & (sx >= 0) & (sx <= W - 1) & (sy >= 0) & (sy <= H - 1)
+        edge = np.where(Z > 0, np.minimum(np.minimum(np.abs(sx), np.abs(sx - (W - 1))), np.minimum(np.abs(sy), np.abs(sy - (H - 1)))), np.inf)
+        cerr_x = (dX + np.abs(sx) * dZ) / np.abs(Z) + u * np.abs(sx)
+        cerr_y = (dY + np.abs(sy) * dZ) / np.abs(Z) + u * np.abs(sy)
+    val = bilinear64(img, np.nan_to_num(np.where(Z > 0, sy, 0), posinf=0.0), np.nan_to_num(np.where(Z > 0, sx, 0), posinf=0.0))
+    return dict(out=np.where(mask, val, 0.0), val=val, mask=mask, sy=sy, sx=sx, Z=Z, edge=edge, cerr_y=cerr_y, cerr_x=cerr_x)
+
+
+def undistort64(img, K, dist5):
+    """undistortImage from its definition, the inverse map of the radial-tangential model (k1, k2, p1, p2, k3) of the .cal files:
+    (xn, yn) = ((x - cx) / fx, (y - cy) / fy), r2 = xn^2 + yn^2, xd = xn (1 + k1 r2 + k2 r2^2 + k3 r2^3) + 2 p1 xn yn + p2 (r2 + 2 xn^2),
+    yd likewise, source = (fx xd + cx, fy yd + cy); out = bilinear(img, source) inside [0, W-1] x [0, H-1], else 0.  (The model has no
+    skew: only fx, fy, cx, cy of K are used, as the library documents.)  Returns dict(out, val (the sample at the clamped source whatever the mask says), mask, sy, sx, edge, cerr_y, cerr_x); the
+    coordinate error bound of a float32 evaluation counts its roundings and carries them through (_undistort_budget)."""
+    img = np.asarray(img, np.float64)
+    _, H, W = img.shape
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+    k1, k2, p1, p2, k3 = [float(v) for v in np.asarray(dist5, np.float64).reshape(-1)]
+    ys, xs = np.mgrid[0:H, 0:W].astype(np.float64)
+    xn, yn = (xs - cx) / fx, (ys - cy) / fy
+    r2 = xn * xn + yn * yn
+    rad = 1 + r2 * (k1 + r2 * (k2 + r2 * k3))
+    xd = xn * rad + 2 * p1 * xn * yn + p2 * (r2 + 2 * xn * xn)
+    yd = yn * rad + p1 * (r2 + 2 * yn * yn) + 2 * p2 * xn * yn
+    sx, sy = xd * fx + cx, yd * fy + cy
+    cerr_x = _undistort_budget(xs, xn, yn, fx, cx, fy, cy, ys, (k1, k2, k3), p1, p2, rad, xd)
+    cerr_y = _undistort_budget(ys, yn, xn, fy, cy, fx, cx, xs, (k1, k2, k3), p2, p1, rad, yd)
+    mask = (sx >= 0) & (sx <= W - 1) & (sy >= 0) & (sy <= H - 1)
+    edge = np.minimum(np.minimum(np.abs(sx), np.abs(sx - (W - 1))), np.minimum(np.abs(sy), np.abs(sy - (H - 1))))
+    val = bilinear64(img, sy, sx)
+    return dict(out=np.where(mask, val, 0.0), val=val, mask=mask, sy=sy, sx=sx, edge=edge, cerr_x=cerr_x, cerr_y=cerr_y)
+
+
+def _undistort_budget(xs, xn, yn, fx, cx, fy, cy, ys, k, p1, p2, rad, xd):
+    """Bound on the error of sx = fx xd + cx evaluated in float32 as the library does, every rounding counted once (u = 2^-24, first
+    order, times 1.001 for the rest; a fused multiply-add only removes roundings).  Written for the x coordinate; the y coordinate is the
+    same expression with the roles of x and y, and of p1 and p2, exchanged.
+      xn = (x - cx) / fx        cx, fx rounded to float32, one subtraction, one division:  e_xn = u (|cx| / |fx| + 3 |xn|)
+      r2 = xn xn + yn yn        two products, one sum:                                     e_r2 = 2 |xn| e_xn + 2 |yn| e_yn + 2 u r2
+      rad = 1 + r2 (k1 + r2 (k2 + r2 k3))   Horner, 6 operations on partial results <= 1 + P, coefficients rounded (u P), P = sum |k_i| r2^i:
+                                                                                           e_rad = P' e_r2 + u P + 6 u (1 + P)
+      xd = xn rad + 2 p1 xn yn + p2 (r2 + 2 xn xn)
+           t1 = xn rad:               |rad| e_xn + |xn| e_rad + u |t1|
+           t2 = 2 p1 xn yn:           |2 p1| (|yn| e_xn + |xn| e_yn) + 3 u |t2|      (p1 rounded, two products)
+           t3 = p2 (r2 + 2 xn xn):    |p2| (e_r2 + 4 |xn| e_xn + 3 u s) + 2 u |t3|   (s = r2 + 2 xn^2: one product, one sum; p2 rounded, one product)
+           two sums:                  2 u (|t1| + |t2| + |t3|)
+      sx = xd fx + cx           fx rounded, one product, cx rounded, one sum:              |fx| e_xd + 3 u |fx xd| + 2 u |cx|"""
+    u = 1.001 * 2.0 ** -24
+    k1, k2, k3 = (abs(v) for v in k)
+    axn, ayn = np.abs(xn), np.abs(yn)
+    e_xn = u * (abs(cx) / abs(fx) + 3 * axn)
+    e_yn = u * (abs(cy) / abs(fy) + 3 * ayn)
+    r2 = xn * xn + yn * yn
+    e_r2 = 2 * axn * e_xn + 2 * ayn * e_yn + 2 * u * r2
+    P = r2 * (k1 + r2 * (k2 + r2 * k3))
+    dP = k1 + r2 * (2 * k2 + r2 * 3 * k3)
+    e_rad = dP * e_r2 + u * P + 6 * u * (1 + P)
+    t1, t2, s = axn * np.abs(rad), 2 * abs(p1) * axn * ayn, r2 + 2 * xn * xn
+    t3 = abs(p2) * s
+    e_xd = (np.abs(rad) * e_xn + axn * e_rad + u * t1) + (2 * abs(p1) * (ayn * e_xn + axn * e_yn) + 3 * u * t2) \
+        + (abs(p2) * (e_r2 + 4 * axn * e_xn + 3 * u * s) + 2 * u * t3) + 2 * u * (t1 + t2 + t3)
+    return abs(fx) * e_xd + 3 * u * np.abs(fx * xd) + 2 * u * abs(cx)
+
+
+def foe64(flow, conf=None, min_flow=0.5, iterations=2, huber=2.0):
+    """Focus of expansion of a dense flow field [2][H][W] (plane 0 = y, 1 = x): the point c minimising sum w (n . (c - p))^2 over the
+    pixels p with a usable vector, n = (-v, u) / |flow| the unit normal of the flow line through p.  Usable: finite flow of non-zero
+    length >= min_flow, and conf > 0 where conf is given (a NaN confidence is not usable).  The 2 x 2 normal equations are solved with
+    np.linalg.solve; `iterations` Huber re-weightings w = min(1, huber / |n . (c - p)|), seeded at (W / 2, H / 2).  Returns ((x, y), sum
+    of the weights); raises np.linalg.LinAlgError when the normal matrix is singular."""
+    v, u = np.asarray(flow[0], np.float64), np.asarray(flow[1], np.float64)
+    H, W = u.shape
+    with np.errstate(invalid="ignore", over="ignore"):
+        mag = np.sqrt(u * u + v * v)
+        ok = np.isfinite(mag) & (mag > 0) & (mag >= min_flow)
+        if conf is not None:
+            ok &= np.asarray(conf, np.float64) > 0
+    ys, xs = np.mgrid[0:H, 0:W].astype(np.float64)
+    y, x, nx, ny = ys[ok], xs[ok], -v[ok] / mag[ok], u[ok] / mag[ok]
+    npd = nx * x + ny * y
+    c = np.array([W / 2.0, H / 2.0])
+    wsum = 0.0
+    for it in range(iterations + 1):
+        w = np.ones_like(nx)
+        if it > 0:
+            r = np.abs(nx * (c[0] - x) + ny * (c[1] - y))
+            w = np.where(r <= huber, 1.0, huber / np.maximum(r, 1e-300))
+        A = np.array([[np.sum(w * nx * nx), np.sum(w * nx * ny)], [np.sum(w * nx * ny), np.sum(w * ny * ny)]])
+        b = np.array([np.sum(w * nx * npd), np.sum(w * ny * npd)])
+        wsum = float(np.sum(w))
+        if not abs(np.linalg.det(A)) > 1e-9 * (A[0, 0] + A[1, 1]) ** 2 + 1e-300:
+            raise np.linalg.LinAlgError("foe64: the flow lines do not intersect in a point")
+        c = np.linalg.solve(A, b)
+    return (float(c[0]), float(c[1])), wsum
