@@ -159,6 +159,13 @@ PROTOTYPES = {
     "dfe_radial_match_subpixel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int]),
     "dfe_radial_refine_subpixel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "dfe_radial_flow_depth_pair_subpixel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 9),
+    "dfe_corner_response_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dfe_select_corners_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "dfe_pyr_down_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dfe_track_points_lk_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dfe_ego_motion_from_images_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_double, C.c_int, C.c_uint,
+                                                C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
 }
 
 
@@ -167,6 +174,12 @@ class RadialParams(C.Structure):
     _fields_ = [("C", C.c_int), ("hImg", C.c_int), ("wImg", C.c_int), ("hInput", C.c_int), ("wInput", C.c_int), ("hWin", C.c_int),
                 ("n1", C.c_int), ("kW1", C.c_int), ("n2", C.c_int), ("kH2", C.c_int), ("tanh_between", C.c_int),
                 ("alpha_polar", C.c_float), ("kinfty", C.c_double), ("zero_last_row", C.c_int)]
+
+
+class TrackerParams(C.Structure):
+    """dfe_tracker_params (include/dfe.h)"""
+    _fields_ = [("max_points", C.c_int), ("quality", C.c_float), ("min_dist", C.c_float), ("win", C.c_int), ("levels", C.c_int),
+                ("max_iters", C.c_int), ("eps", C.c_float), ("min_eig", C.c_float), ("max_err", C.c_float)]
 
 _lib = None
 

@@ -400,6 +400,8 @@ int ego_from_points(dfe_ctx *ctx, const float *p1, const float *p2, const float 
 
 extern "C" {
 
+// (takes its scratch from the arena only, never from the ctx's side buffer (dfe_aux_scratch): dfe_ego_motion_from_images_f32 keeps its point
+//  lists and weights there across this call -- tracker.hip)
 int dfe_ego_motion_from_points_f32(dfe_ctx *ctx, const float *pts1, const float *pts2, const float *weights, int N, const double *K9, double ransac_max_dist,
                                    int iterations, unsigned seed, double *R9, double *T3, int *n_inliers, double *F9) {
     DFE_ENTER(ctx);

@@ -8,6 +8,7 @@ ffi.cdef[[
 typedef struct dfe_ctx dfe_ctx;
 typedef struct dfe_radial_params { int C, hImg, wImg; int hInput, wInput; int hWin; int n1, kW1; int n2, kH2; int tanh_between; float alpha_polar; double kinfty; int zero_last_row; } dfe_radial_params;
 typedef struct dfe_filter_layer { int nIn, nOut, kH, kW; const float *weight; const float *bias; const int32_t *conn; int nConn; int tanh_after; } dfe_filter_layer;
+typedef struct dfe_tracker_params { int max_points; float quality; float min_dist; int win; int levels; int max_iters; float eps; float min_eig; float max_err; } dfe_tracker_params;
 int dfe_version(void);
 const char *dfe_kernel_revision(void);
 int dfe_ctx_create(int device, void *stream, int own_stream, dfe_ctx **out);
@@ -120,6 +121,11 @@ int dfe_undistort_image_f32(dfe_ctx *ctx, const float *img, int C, int H, int W,
 int dfe_foe_from_flow_f32(dfe_ctx *ctx, const float *flow_y, const float *flow_x, const float *conf, int H, int W, float min_flow, int iterations, double *foe_xy, double *n_used);
 int dfe_ego_motion_from_points_f32(dfe_ctx *ctx, const float *pts1, const float *pts2, const float *weights, int N, const double *K9, double ransac_max_dist, int iterations, unsigned seed, double *R9, double *T3, int *n_inliers, double *F9);
 int dfe_ego_motion_from_flow_f32(dfe_ctx *ctx, const float *flow_y, const float *flow_x, const float *conf, int H, int W, const double *K9, int max_points, double ransac_max_dist, int iterations, unsigned seed, double *R9, double *T3, int *n_found, int *n_inliers, double *F9);
+int dfe_corner_response_f32(dfe_ctx *ctx, const float *Y, int H, int W, float *resp);
+int dfe_select_corners_f32(dfe_ctx *ctx, const float *resp, int H, int W, float quality, float min_dist, int max_points, float *pts, float *resp_out, int *n_out);
+int dfe_pyr_down_f32(dfe_ctx *ctx, const float *in, int H, int W, float *out);
+int dfe_track_points_lk_f32(dfe_ctx *ctx, const float *Y0, const float *Y1, int H, int W, const float *pts0, int N, const dfe_tracker_params *params, float *pts1, int *status, float *err);
+int dfe_ego_motion_from_images_f32(dfe_ctx *ctx, const float *im0, const float *im1, int C, int H, int W, const double *K9, const dfe_tracker_params *params, double ransac_max_dist, int iterations, unsigned seed, double *R9, double *T3, int *n_found, int *n_inliers, double *F9, float *pts0_out, float *pts1_out, int *status_out, int *n_corners);
 ]]
 
 local M = {}

@@ -728,6 +728,55 @@ int dfe_ego_motion_from_flow_f32(dfe_ctx *ctx, const float *flow_y, const float 
                                  const double *K9, int max_points, double ransac_max_dist, int iterations, unsigned seed, double *R9,
                                  double *T3, int *n_found, int *n_inliers, double *F9);
 
+/* ---- N4, the step in front of the pose: corner detection and pyramidal Lucas-Kanade tracking, so that the pose can start from two
+ *      IMAGES as sfm2.getEgoMotion{im1, im2, K, maxPoints, pointsQuality, pointsMinDistance} does (radial/radial_opticalflow_data.lua:
+ *      211-217, depth_estimation_api.lua:141, test_opticalflow.lua:282, groundtruth_opticalflow.lua:283, version2/data.lua:96).  sfm2 is
+ *      un-vendored (OpenCV behind it): parity is unpinned; this is the library's own tracker, every stage defined in DESIGN section 4
+ *      and tested on its own against a float64 reference written from those definitions. -------------------------------------------- */
+/* parameters of the corner selection and the tracker; the .cal files' sfm table carries max_points, points_quality, points_min_dist
+ * and tracker_win_size */
+typedef struct dfe_tracker_params {
+    int max_points;        /* corners kept, 1..4096 */
+    float quality;         /* a corner needs response >= quality * the frame's largest response, 0..1 */
+    float min_dist;        /* kept corners are pairwise more than this many pixels apart, >= 1 */
+    int win;               /* tracking window, odd, 3..31 */
+    int levels;            /* pyramid levels, 1..8 (1: the frame only) */
+    int max_iters;         /* Gauss-Newton steps per level, 1..64 */
+    float eps;             /* a level stops after a step shorter than this, >= 0 */
+    float min_eig;         /* a window whose structure tensor's smaller eigenvalue / win^2 is below this is not tracked */
+    float max_err;         /* > 0: points whose mean absolute residual exceeds this are lost */
+} dfe_tracker_params;
+/* Corner response: gx(y, x) = (Y(y, x+1) - Y(y, x-1)) / 2 and gy likewise, indices clamped to the frame; a = sum gx^2, b = sum gx gy,
+ * c = sum gy^2 over the 3 x 3 block around the pixel (clamped indices); resp = ((a + c) - sqrt((a - c)^2 + 4 b^2)) / 2, the smaller
+ * eigenvalue.  Y, resp [H][W]. */
+int dfe_corner_response_f32(dfe_ctx *ctx, const float *Y, int H, int W, float *resp);
+/* Corner selection on a response map [H][W] (H, W <= 32768).  M = the largest response (NaNs ignored); none when M <= 0.  A pixel is
+ * a candidate iff resp > 0 and resp >= quality * M (one float32 product); it is kept iff no other pixel within
+ * dx^2 + dy^2 <= floor(min_dist^2) has a larger response, or an equal one at a smaller linear index y W + x (NaN never dominates).
+ * The kept points, sorted by (response descending, linear index ascending) and cut to the first max_points, go to pts [n][2] = (x, y)
+ * (device floats, capacity max_points) and resp_out [n] (or NULL); n_out (host) = n.  The result does not depend on scheduling.
+ * 1 <= min_dist, 1 <= max_points <= 4096, 0 <= quality <= 1, else DFE_E_ARG.  Synchronises. */
+int dfe_select_corners_f32(dfe_ctx *ctx, const float *resp, int H, int W, float quality, float min_dist, int max_points, float *pts,
+                           float *resp_out, int *n_out);
+/* One pyramid step: out [(H+1)/2][(W+1)/2], out(y, x) = sum_{i,j=-2..2} w_i w_j in(rho(2y+i, H), rho(2x+j, W)), w = (1,4,6,4,1)/16,
+ * rho the reflection about the first and the last sample (-1 -> 1, n -> n-2; n = 1: always 0). */
+int dfe_pyr_down_f32(dfe_ctx *ctx, const float *in, int H, int W, float *out);
+/* Pyramidal Lucas-Kanade (DESIGN section 4 has the definition step by step).  Y0, Y1 [H][W]; pts0 / pts1 [N][2] = (x, y) device
+ * floats; status [N] int32 (1 = tracked); err [N] (or NULL) = mean |residual| of the last evaluation at level 0.  Uses win, levels,
+ * max_iters, eps, min_eig, max_err of params.  A point is lost when its level-0 window is weaker than min_eig, when pts1 leaves
+ * [0, W-1] x [0, H-1], when the point or its displacement is not finite, or when max_err > 0 and err > max_err; lost points keep
+ * pts1 = pts0 and err = 0.  The same call gives the same bits.  N = 0 does nothing. */
+int dfe_track_points_lk_f32(dfe_ctx *ctx, const float *Y0, const float *Y1, int H, int W, const float *pts0, int N,
+                            const dfe_tracker_params *params, float *pts1, int *status, float *err);
+/* sfm2.getEgoMotion{im1, im2, K, ...} in one call: im0 / im1 [C][H][W], C = 3 (dfe_rgb2y_f32 first) or 1; response and corners of
+ * frame 0, tracked into frame 1, then dfe_ego_motion_from_points_f32 with the status as the weights (same outputs, same conventions).
+ * n_found = tracked corners.  pts0_out / pts1_out [max_points][2], status_out [max_points] (device; each may be NULL) receive the
+ * first n_corners (host int, may be NULL) entries.  DFE_E_ARG when fewer than 8 corners are found or tracked.  Synchronises. */
+int dfe_ego_motion_from_images_f32(dfe_ctx *ctx, const float *im0, const float *im1, int C, int H, int W, const double *K9,
+                                   const dfe_tracker_params *params, double ransac_max_dist, int iterations, unsigned seed, double *R9,
+                                   double *T3, int *n_found, int *n_inliers, double *F9, float *pts0_out, float *pts1_out,
+                                   int *status_out, int *n_corners);
+
 #ifdef __cplusplus
 }
 #endif
