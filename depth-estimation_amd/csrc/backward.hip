@@ -15,13 +15,6 @@
 
 namespace {
 
-int grid_n(long long n) {
-    long long b = (n + 255) / 256;
-    if (b > 256 * 32) b = 256 * 32;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 // gradIn[i][y][x] = sum_o sum_u sum_v w[o][i][u][v] * gO[o][y-u][x-v]
 __global__ void conv_grad_input_kernel(const float *__restrict__ go, const float *__restrict__ w, int nIn, int nOut, int H, int W, int kH, int kW,
                                        float *__restrict__ gi) {
@@ -194,7 +187,7 @@ int dfe_spatial_convolution_grad_input_f32(dfe_ctx *ctx, const float *gradOut, c
     DFE_REQUIRE(ctx, gradOut && weight && gradIn, DFE_E_ARG, "dfe_spatial_convolution_grad_input_f32: NULL tensor");
     DFE_REQUIRE(ctx, nIn > 0 && nOut > 0 && kH > 0 && kW > 0 && H >= kH && W >= kW, DFE_E_SHAPE,
                 "dfe_spatial_convolution_grad_input_f32: %d->%d planes, %dx%d kernel on %dx%d", nIn, nOut, kH, kW, H, W);
-    hipLaunchKernelGGL(conv_grad_input_kernel, dim3(grid_n((long long)nIn * H * W)), dim3(256), 0, ctx->stream, gradOut, weight, nIn, nOut, H, W,
+    hipLaunchKernelGGL(conv_grad_input_kernel, dim3(dfe_grid1d((long long)nIn * H * W)), dim3(256), 0, ctx->stream, gradOut, weight, nIn, nOut, H, W,
                        kH, kW, gradIn);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
@@ -221,7 +214,7 @@ int dfe_spatial_convolution_map_grad_input_f32(dfe_ctx *ctx, const float *gradOu
     DFE_REQUIRE(ctx, gradOut && weight && conn && gradIn, DFE_E_ARG, "dfe_spatial_convolution_map_grad_input_f32: NULL tensor");
     DFE_REQUIRE(ctx, nIn > 0 && nConn > 0 && kH > 0 && kW > 0 && H >= kH && W >= kW, DFE_E_SHAPE,
                 "dfe_spatial_convolution_map_grad_input_f32: %d connections, %dx%d kernel on %dx%d", nConn, kH, kW, H, W);
-    hipLaunchKernelGGL(conv_map_grad_input_kernel, dim3(grid_n((long long)nIn * H * W)), dim3(256), 0, ctx->stream, gradOut, weight, conn, nConn,
+    hipLaunchKernelGGL(conv_map_grad_input_kernel, dim3(dfe_grid1d((long long)nIn * H * W)), dim3(256), 0, ctx->stream, gradOut, weight, conn, nConn,
                        nIn, H, W, kH, kW, gradIn);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
@@ -246,7 +239,7 @@ int dfe_tanh_backward_f32(dfe_ctx *ctx, const float *out, const float *gradOut, 
     DFE_REQUIRE(ctx, n >= 0, DFE_E_SHAPE, "dfe_tanh_backward_f32: n=%lld", (long long)n);
     if (n == 0) return DFE_OK;
     DFE_REQUIRE(ctx, out && gradOut && gradIn, DFE_E_ARG, "dfe_tanh_backward_f32: NULL tensor");
-    hipLaunchKernelGGL(tanh_backward_kernel, dim3(grid_n(n)), dim3(256), 0, ctx->stream, out, gradOut, (long long)n, gradIn);
+    hipLaunchKernelGGL(tanh_backward_kernel, dim3(dfe_grid1d(n)), dim3(256), 0, ctx->stream, out, gradOut, (long long)n, gradIn);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -256,7 +249,7 @@ int dfe_log2_forward_f32(dfe_ctx *ctx, float *input, int64_t n, float null_epsil
     DFE_REQUIRE(ctx, n >= 0, DFE_E_SHAPE, "dfe_log2_forward_f32: n=%lld", (long long)n);
     if (n == 0) return DFE_OK;
     DFE_REQUIRE(ctx, input && out, DFE_E_ARG, "dfe_log2_forward_f32: NULL tensor");
-    hipLaunchKernelGGL(log_clamp_kernel, dim3(grid_n(n)), dim3(256), 0, ctx->stream, input, (long long)n, null_epsilon, clamp, out);
+    hipLaunchKernelGGL(log_clamp_kernel, dim3(dfe_grid1d(n)), dim3(256), 0, ctx->stream, input, (long long)n, null_epsilon, clamp, out);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -266,7 +259,7 @@ int dfe_log2_backward_f32(dfe_ctx *ctx, const float *input, const float *gradOut
     DFE_REQUIRE(ctx, n >= 0, DFE_E_SHAPE, "dfe_log2_backward_f32: n=%lld", (long long)n);
     if (n == 0) return DFE_OK;
     DFE_REQUIRE(ctx, input && gradOut && gradIn, DFE_E_ARG, "dfe_log2_backward_f32: NULL tensor");
-    hipLaunchKernelGGL(div_kernel, dim3(grid_n(n)), dim3(256), 0, ctx->stream, gradOut, input, (long long)n, gradIn);
+    hipLaunchKernelGGL(div_kernel, dim3(dfe_grid1d(n)), dim3(256), 0, ctx->stream, gradOut, input, (long long)n, gradIn);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -276,7 +269,7 @@ int dfe_log_softmax_f32(dfe_ctx *ctx, const float *in, int64_t P, int N, float *
     DFE_REQUIRE(ctx, P >= 0 && N > 0, DFE_E_SHAPE, "dfe_log_softmax_f32: P=%lld N=%d", (long long)P, N);
     if (P == 0) return DFE_OK;
     DFE_REQUIRE(ctx, in && out, DFE_E_ARG, "dfe_log_softmax_f32: NULL tensor");
-    hipLaunchKernelGGL(log_softmax_kernel, dim3(grid_n(P * 64)), dim3(256), 0, ctx->stream, in, (long long)P, N, out);
+    hipLaunchKernelGGL(log_softmax_kernel, dim3(dfe_grid1d(P * 64)), dim3(256), 0, ctx->stream, in, (long long)P, N, out);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -286,7 +279,7 @@ int dfe_log_softmax_backward_f32(dfe_ctx *ctx, const float *out, const float *gr
     DFE_REQUIRE(ctx, P >= 0 && N > 0, DFE_E_SHAPE, "dfe_log_softmax_backward_f32: P=%lld N=%d", (long long)P, N);
     if (P == 0) return DFE_OK;
     DFE_REQUIRE(ctx, out && gradOut && gradIn, DFE_E_ARG, "dfe_log_softmax_backward_f32: NULL tensor");
-    hipLaunchKernelGGL(log_softmax_backward_kernel, dim3(grid_n(P * 64)), dim3(256), 0, ctx->stream, out, gradOut, (long long)P, N, gradIn);
+    hipLaunchKernelGGL(log_softmax_backward_kernel, dim3(dfe_grid1d(P * 64)), dim3(256), 0, ctx->stream, out, gradOut, (long long)P, N, gradIn);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -296,7 +289,7 @@ int dfe_softmax_backward_f32(dfe_ctx *ctx, const float *out, const float *gradOu
     DFE_REQUIRE(ctx, P >= 0 && N > 0, DFE_E_SHAPE, "dfe_softmax_backward_f32: P=%lld N=%d", (long long)P, N);
     if (P == 0) return DFE_OK;
     DFE_REQUIRE(ctx, out && gradOut && gradIn, DFE_E_ARG, "dfe_softmax_backward_f32: NULL tensor");
-    hipLaunchKernelGGL(softmax_backward_kernel, dim3(grid_n(P * 64)), dim3(256), 0, ctx->stream, out, gradOut, (long long)P, N, gradIn);
+    hipLaunchKernelGGL(softmax_backward_kernel, dim3(dfe_grid1d(P * 64)), dim3(256), 0, ctx->stream, out, gradOut, (long long)P, N, gradIn);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }

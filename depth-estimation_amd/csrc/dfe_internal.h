@@ -272,6 +272,35 @@ struct DfeDeviceGuard {
 
 
 static inline int dfe_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+// blocks of a grid-stride launch over n elements: ceil(n / per_block), at least 1, at most cap
+static inline int dfe_grid1d(long long n, int per_block = 256, int cap = 256 * 32) {
+    const long long b = (n + per_block - 1) / per_block;
+    return (int)(b < 1 ? 1 : b > cap ? cap : b);
+}
+// 0-based offset of the centre in a window side of n cells, ceil(n / 2) - 1: datap.lWin / tWin (version2/test.lua:18-21), and the first
+// row / column that prepareInput's narrow(2, ceil(maxh / 2), ..) keeps of patch 1 (opticalflow_model.lua)
+static inline int dfe_window_lead(int n) { return (n + 1) / 2 - 1; }
+// 1-based class of the centre cell of an hWin x wWin window: getMiddleIndex = yx2x(centered2onebased(0, 0)) (opticalflow_model.lua:12-14,
+// 28-43), yx2xMulti(0, 0) of the pyramid, the centre override of radial/radial_opticalflow_groundtruth.lua:91
+static inline int dfe_window_middle(int hWin, int wWin) { return (wWin + 1) / 2 + wWin * dfe_window_lead(hWin); }
+// o = a b and o = m^-1 (false: singular) of row-major 3 x 3 matrices on the host (egomotion.hip, egopose.hip)
+static inline void dfe_mat3_mul(const double *a, const double *b, double *o) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) o[i * 3 + j] = a[i * 3] * b[j] + a[i * 3 + 1] * b[3 + j] + a[i * 3 + 2] * b[6 + j];
+}
+static inline bool dfe_mat3_inv(const double *m, double *o) {
+    const double d = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
+    if (fabs(d) < 1e-300) return false;
+    o[0] = (m[4] * m[8] - m[5] * m[7]) / d; o[1] = (m[2] * m[7] - m[1] * m[8]) / d; o[2] = (m[1] * m[5] - m[2] * m[4]) / d;
+    o[3] = (m[5] * m[6] - m[3] * m[8]) / d; o[4] = (m[0] * m[8] - m[2] * m[6]) / d; o[5] = (m[2] * m[3] - m[0] * m[5]) / d;
+    o[6] = (m[3] * m[7] - m[4] * m[6]) / d; o[7] = (m[1] * m[6] - m[0] * m[7]) / d; o[8] = (m[0] * m[4] - m[1] * m[3]) / d;
+    return true;
+}
+// one description of a learned filter stack (filters.hip), the one rule of every entry that takes dfe_filter_layer[]: every layer complete
+// (DFE_E_ARG); layer 0 reads the frames' C planes, a full layer the planes of the layer before it, a connection-table layer at most those
+// (DFE_E_SHAPE).  nlayers == 0: {1, 1, C, C}
+struct DfeStackGeom { int hk, wk, K, maxplanes; };   // receptive field, planes of the last layer, the widest layer (>= C)
+int dfe_filter_stack_geom(dfe_ctx *ctx, const char *entry, const dfe_filter_layer *layers, int nlayers, int C, DfeStackGeom *g);
 
 
 // ---- shared by the fused cost-volume epilogue (ssd_cost_volume.hip) and the tail kernels (postops.hip) ----

@@ -18,13 +18,6 @@
 
 namespace {
 
-int grid_e(long long n) {
-    long long b = (n + 255) / 256;
-    if (b > 256 * 32) b = 256 * 32;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 __device__ __forceinline__ float bilin_masked(const float *__restrict__ p, int H, int W, float fy, float fx) {
 #pragma clang fp contract(off)
     fy = fy < 0 ? 0 : (fy > (float)(H - 1) ? (float)(H - 1) : fy);
@@ -101,20 +94,6 @@ __global__ __launch_bounds__(256) void foe_sums_kernel(const float *__restrict__
     if (threadIdx.x < 5) part[blockIdx.x * 5 + threadIdx.x] = sm[threadIdx.x][0] + sm[threadIdx.x][1] + sm[threadIdx.x][2] + sm[threadIdx.x][3];
 }
 
-void mat3_mul(const double *a, const double *b, double *o) {
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) o[i * 3 + j] = a[i * 3] * b[j] + a[i * 3 + 1] * b[3 + j] + a[i * 3 + 2] * b[6 + j];
-}
-
-bool mat3_inv(const double *m, double *o) {
-    const double d = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-    if (fabs(d) < 1e-300) return false;
-    o[0] = (m[4] * m[8] - m[5] * m[7]) / d; o[1] = (m[2] * m[7] - m[1] * m[8]) / d; o[2] = (m[1] * m[5] - m[2] * m[4]) / d;
-    o[3] = (m[5] * m[6] - m[3] * m[8]) / d; o[4] = (m[0] * m[8] - m[2] * m[6]) / d; o[5] = (m[2] * m[3] - m[0] * m[5]) / d;
-    o[6] = (m[3] * m[7] - m[4] * m[6]) / d; o[7] = (m[1] * m[6] - m[0] * m[7]) / d; o[8] = (m[0] * m[4] - m[1] * m[3]) / d;
-    return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -135,27 +114,27 @@ int dfe_remove_ego_motion_f32(dfe_ctx *ctx, const float *img, int C, int H, int 
     DFE_REQUIRE(ctx, img && K9 && R9 && out, DFE_E_ARG, "dfe_remove_ego_motion_f32: NULL argument");
     DFE_REQUIRE(ctx, C > 0 && H > 0 && W > 0, DFE_E_SHAPE, "dfe_remove_ego_motion_f32: C=%d %dx%d", C, H, W);
     double Ki[9], Rt[9], t[9], Hd[9];
-    DFE_REQUIRE(ctx, mat3_inv(K9, Ki), DFE_E_ARG, "dfe_remove_ego_motion_f32: K is singular");
+    DFE_REQUIRE(ctx, dfe_mat3_inv(K9, Ki), DFE_E_ARG, "dfe_remove_ego_motion_f32: K is singular");
     const double *Ru = R9;
     if (inverse) {
         for (int i = 0; i < 3; ++i)
             for (int j = 0; j < 3; ++j) Rt[i * 3 + j] = R9[j * 3 + i];
         Ru = Rt;
     }
-    mat3_mul(K9, Ru, t);
-    mat3_mul(t, Ki, Hd);
+    dfe_mat3_mul(K9, Ru, t);
+    dfe_mat3_mul(t, Ki, Hd);
     {   // an entry below the rounding error of its own sum of products is noise: 0.  (K I K^-1 is the identity only up to such entries,
         // and a -1e-17 in the offset column puts the source of column 0 outside the frame.)
         double aK[9], aR[9], aKi[9], at[9], aH[9];
         for (int i = 0; i < 9; ++i) { aK[i] = fabs(K9[i]); aR[i] = fabs(Ru[i]); aKi[i] = fabs(Ki[i]); }
-        mat3_mul(aK, aR, at);
-        mat3_mul(at, aKi, aH);
+        dfe_mat3_mul(aK, aR, at);
+        dfe_mat3_mul(at, aKi, aH);
         for (int i = 0; i < 9; ++i)
             if (fabs(Hd[i]) <= 16 * 2.220446049250313e-16 * aH[i]) Hd[i] = 0;
     }
     Mat3 Hm;
     for (int i = 0; i < 9; ++i) Hm.m[i] = (float)Hd[i];
-    hipLaunchKernelGGL(homography_warp_kernel, dim3(grid_e((long long)H * W)), dim3(256), 0, ctx->stream, img, C, H, W, Hm, out, mask);
+    hipLaunchKernelGGL(homography_warp_kernel, dim3(dfe_grid1d((long long)H * W)), dim3(256), 0, ctx->stream, img, C, H, W, Hm, out, mask);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -164,7 +143,7 @@ int dfe_undistort_image_f32(dfe_ctx *ctx, const float *img, int C, int H, int W,
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, img && K9 && dist5 && out, DFE_E_ARG, "dfe_undistort_image_f32: NULL argument");
     DFE_REQUIRE(ctx, C > 0 && H > 0 && W > 0 && K9[0] != 0 && K9[4] != 0, DFE_E_SHAPE, "dfe_undistort_image_f32: C=%d %dx%d fx=%g fy=%g", C, H, W, K9[0], K9[4]);
-    hipLaunchKernelGGL(undistort_kernel, dim3(grid_e((long long)H * W)), dim3(256), 0, ctx->stream, img, C, H, W, (float)K9[0], (float)K9[4], (float)K9[2],
+    hipLaunchKernelGGL(undistort_kernel, dim3(dfe_grid1d((long long)H * W)), dim3(256), 0, ctx->stream, img, C, H, W, (float)K9[0], (float)K9[4], (float)K9[2],
                        (float)K9[5], (float)dist5[0], (float)dist5[1], (float)dist5[2], (float)dist5[3], (float)dist5[4], out);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
@@ -175,7 +154,7 @@ int dfe_foe_from_flow_f32(dfe_ctx *ctx, const float *flow_y, const float *flow_x
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, flow_y && flow_x && foe_xy, DFE_E_ARG, "dfe_foe_from_flow_f32: NULL argument");
     DFE_REQUIRE(ctx, H > 0 && W > 0 && iterations >= 0 && iterations <= 16, DFE_E_SHAPE, "dfe_foe_from_flow_f32: %dx%d, %d iterations", H, W, iterations);
-    const int nb = grid_e((long long)H * W) > 256 ? 256 : grid_e((long long)H * W);
+    const int nb = dfe_grid1d((long long)H * W) > 256 ? 256 : dfe_grid1d((long long)H * W);
     void *scr = nullptr;
     int rc = dfe_scratch(ctx, (size_t)nb * 5 * sizeof(double), &scr);
     if (rc) return rc;

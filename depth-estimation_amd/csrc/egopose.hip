@@ -249,15 +249,6 @@ __global__ void ego_sample_flow_kernel(const float *__restrict__ fy, const float
     w[n] = ok ? 1.f : 0.f;
 }
 
-bool mat3_inv_d(const double *m, double *o) {
-    const double d = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-    if (fabs(d) < 1e-300) return false;
-    o[0] = (m[4] * m[8] - m[5] * m[7]) / d; o[1] = (m[2] * m[7] - m[1] * m[8]) / d; o[2] = (m[1] * m[5] - m[2] * m[4]) / d;
-    o[3] = (m[5] * m[6] - m[3] * m[8]) / d; o[4] = (m[0] * m[8] - m[2] * m[6]) / d; o[5] = (m[2] * m[3] - m[0] * m[5]) / d;
-    o[6] = (m[3] * m[7] - m[4] * m[6]) / d; o[7] = (m[1] * m[6] - m[0] * m[7]) / d; o[8] = (m[0] * m[4] - m[1] * m[3]) / d;
-    return true;
-}
-
 // number of inliers in front of both cameras for the pose (R, t): x2 ~ R x1 + t.  Depths from the two-view linear system
 // z2 b = z1 R a + t, solved in the least-squares sense per point.
 int cheirality(const double *R, const double *t, const std::vector<float> &p1, const std::vector<float> &p2, const std::vector<unsigned char> &mask,
@@ -301,7 +292,7 @@ EgoLayout ego_layout(int N, int nh, size_t scr_off) {
 int ego_from_points(dfe_ctx *ctx, const float *p1, const float *p2, const float *w, const float *hw, int N, const double *K9, double max_dist, int iterations,
                     unsigned seed, double *R9, double *T3, int *n_inliers, double *F9, size_t scr_off) {
     EgoK kk;
-    DFE_REQUIRE(ctx, mat3_inv_d(K9, kk.Ki), DFE_E_ARG, "ego motion: K is singular");
+    DFE_REQUIRE(ctx, dfe_mat3_inv(K9, kk.Ki), DFE_E_ARG, "ego motion: K is singular");
     const int nh = iterations;
     const EgoLayout lay = ego_layout(N, nh, scr_off);
     const int nblk = lay.nblk;

@@ -794,9 +794,9 @@ static int ff_launch(dfe_ctx *ctx, const float *in1, int pitch1, long long plane
     a.K = K; a.H1 = H1; a.W1 = W1; a.maxh = maxh; a.H2 = H1 + maxh - 1; a.W2 = W1 + maxw - 1;
     a.G = G; a.NG = (int)NGl; a.ntiles = dfe_cdiv(NGl, FF_GROUPS);
     a.idx = idx; a.xflow = xflow; a.yflow = yflow;
-    a.lWin = (maxw + 1) / 2 - 1; a.tWin = (maxh + 1) / 2 - 1;            // version2/test.lua:18-19
+    a.lWin = dfe_window_lead(maxw); a.tWin = dfe_window_lead(maxh);
     if (soft) {
-        a.middle = (maxw + 1) / 2 + maxw * ((maxh + 1) / 2 - 1);           // getMiddleIndex: yx2x(centered2onebased(0, 0)), opticalflow_model.lua:12-14,28-43
+        a.middle = dfe_window_middle(maxh, maxw);
         a.use_thr = soft->use_threshold; a.thr = soft->threshold;
         a.wFull = soft->wFull; a.fullplane = (long long)soft->hFull * soft->wFull;
         a.ho = (soft->hFull - H1) / 2; a.wo = (soft->wFull - W1) / 2;    // processOutput: floor((hImg - h) / 2), :228-230

@@ -354,7 +354,7 @@ int dfe_feat_matching_mfma(dfe_ctx *ctx, const float *in1, const float *in2, int
     a.in1 = in1; a.in2 = in2; a.na = na; a.nb = nb; a.out = out; a.idx = idx; a.xflow = xflow; a.yflow = yflow;
     a.K = K; a.H1 = H1; a.W1 = W1; a.H2 = H2; a.W2 = W2;
     a.gx = dfe_cdiv(W1, 16); a.ntiles = a.gx * dfe_cdiv(H1, FMM_R);
-    a.lWin = (maxw + 1) / 2 - 1; a.tWin = (maxh + 1) / 2 - 1;
+    a.lWin = dfe_window_lead(maxw); a.tWin = dfe_window_lead(maxh);
     const int BROWS = (FMM_R + maxh - 1 + 3) & ~3;
     // the arg-min form stages 16 planes at a time where K allows it: three of four k-steps then have their operands requested behind MFMAs
     const bool kc16 = !out && K % 16 == 0;

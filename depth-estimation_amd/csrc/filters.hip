@@ -79,13 +79,6 @@ __global__ void tanh_kernel(const float *__restrict__ in, long long n, float *__
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x) out[e] = tanhf(in[e]);
 }
 
-int grid_n(long long n) {
-    long long b = (n + 255) / 256;
-    if (b > 256 * 32) b = 256 * 32;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 }  // namespace
 
 // ---- the same layer for a BATCH of independent inputs in one launch (both frames of every pyramid scale), LDS-tiled ----------------
@@ -376,13 +369,28 @@ int dfe_filter_layer_forward(dfe_ctx *ctx, const float *in, const dfe_filter_lay
     DFE_REQUIRE(ctx, in && L.weight && out, DFE_E_ARG, "filter layer: NULL tensor");
     DFE_REQUIRE(ctx, L.nIn > 0 && L.nOut > 0 && L.kH > 0 && L.kW > 0 && H >= L.kH && W >= L.kW && (!L.conn || L.nConn > 0), DFE_E_SHAPE,
                 "filter layer: %d->%d planes, %dx%d kernel on %dx%d", L.nIn, L.nOut, L.kH, L.kW, H, W);
-    const int g = grid_n((long long)L.nOut * (H - L.kH + 1) * (W - L.kW + 1));
+    const int g = dfe_grid1d((long long)L.nOut * (H - L.kH + 1) * (W - L.kW + 1));
     if (L.tanh_after)
         hipLaunchKernelGGL(conv_layer_kernel<true>, dim3(g), dim3(256), 0, ctx->stream, in, L.weight, L.bias, (const int *)L.conn, L.nConn, L.nIn, L.nOut, H, W, L.kH, L.kW, out);
     else
         hipLaunchKernelGGL(conv_layer_kernel<false>, dim3(g), dim3(256), 0, ctx->stream, in, L.weight, L.bias, (const int *)L.conn, L.nConn, L.nIn, L.nOut, H, W, L.kH, L.kW, out);
     ctx->last_kernel = "conv_layer_kernel";
     DFE_LAUNCH_CHECK(ctx);
+    return DFE_OK;
+}
+
+// hKernel = sum kH - (nlayers - 1) of the stack (opticalflow.lua:154-171) and the planes it needs room for, under the rule of dfe_internal.h
+int dfe_filter_stack_geom(dfe_ctx *ctx, const char *entry, const dfe_filter_layer *layers, int nlayers, int C, DfeStackGeom *g) {
+    *g = DfeStackGeom{1, 1, C, C};
+    for (int i = 0; i < nlayers; ++i) {
+        const dfe_filter_layer &L = layers[i];
+        DFE_REQUIRE(ctx, L.weight && L.kH > 0 && L.kW > 0 && L.nIn > 0 && L.nOut > 0, DFE_E_ARG, "%s: layer %d is incomplete", entry, i);
+        DFE_REQUIRE(ctx, (i > 0 && L.conn) ? L.nIn <= g->K : L.nIn == g->K, DFE_E_SHAPE, "%s: layer %d reads %d planes, its input has %d", entry, i, L.nIn, g->K);
+        g->hk += L.kH - 1;
+        g->wk += L.kW - 1;
+        g->K = L.nOut;
+        g->maxplanes = g->maxplanes > g->K ? g->maxplanes : g->K;
+    }
     return DFE_OK;
 }
 
@@ -404,7 +412,7 @@ int dfe_spatial_convolution_f32(dfe_ctx *ctx, const float *in, const float *weig
         int rc = conv_batch_try(ctx, 1, &in, &Lp, &H, &W, &out, &done);
         if (rc != DFE_OK || done) return rc;
     }
-    hipLaunchKernelGGL(conv_kernel, dim3(grid_n((long long)nOut * (H - kH + 1) * (W - kW + 1))), dim3(256), 0, ctx->stream, in, weight, bias,
+    hipLaunchKernelGGL(conv_kernel, dim3(dfe_grid1d((long long)nOut * (H - kH + 1) * (W - kW + 1))), dim3(256), 0, ctx->stream, in, weight, bias,
                        nIn, nOut, H, W, kH, kW, out);
     ctx->last_kernel = "conv_kernel";
     DFE_LAUNCH_CHECK(ctx);
@@ -436,7 +444,7 @@ int dfe_spatial_convolution_map_f32(dfe_ctx *ctx, const float *in, const float *
     DFE_REQUIRE(ctx, in && weight && conn && out, DFE_E_ARG, "dfe_spatial_convolution_map_f32: NULL tensor");
     DFE_REQUIRE(ctx, nIn > 0 && nOut > 0 && nConn > 0 && kH > 0 && kW > 0 && H >= kH && W >= kW, DFE_E_SHAPE,
                 "dfe_spatial_convolution_map_f32: %d connections %d->%d planes, %dx%d kernel on %dx%d", nConn, nIn, nOut, kH, kW, H, W);
-    hipLaunchKernelGGL(conv_map_kernel, dim3(grid_n((long long)nOut * (H - kH + 1) * (W - kW + 1))), dim3(256), 0, ctx->stream, in, weight,
+    hipLaunchKernelGGL(conv_map_kernel, dim3(dfe_grid1d((long long)nOut * (H - kH + 1) * (W - kW + 1))), dim3(256), 0, ctx->stream, in, weight,
                        bias, conn, nConn, nOut, H, W, kH, kW, out);
     ctx->last_kernel = "conv_map_kernel";
     DFE_LAUNCH_CHECK(ctx);
@@ -448,7 +456,7 @@ int dfe_tanh_f32(dfe_ctx *ctx, const float *in, int64_t n, float *out) {
     DFE_REQUIRE(ctx, n >= 0, DFE_E_SHAPE, "dfe_tanh_f32: n=%lld", (long long)n);
     if (n == 0) return DFE_OK;
     DFE_REQUIRE(ctx, in && out, DFE_E_ARG, "dfe_tanh_f32: NULL tensor");
-    hipLaunchKernelGGL(tanh_kernel, dim3(grid_n(n)), dim3(256), 0, ctx->stream, in, (long long)n, out);
+    hipLaunchKernelGGL(tanh_kernel, dim3(dfe_grid1d(n)), dim3(256), 0, ctx->stream, in, (long long)n, out);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }

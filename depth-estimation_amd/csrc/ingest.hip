@@ -105,16 +105,11 @@ __global__ __launch_bounds__(64 * MD_RG) void min_dim0_kernel(const float *__res
     }
 }
 
-int in_grid(long long n) {
-    long long b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : b > 8192 ? 8192 : b);
-}
-
 int launch_u8(dfe_ctx *ctx, const unsigned char *src, long long n, float scale, float *dst) {
     if ((((uintptr_t)src) & 3) == 0 && (((uintptr_t)dst) & 15) == 0)
-        hipLaunchKernelGGL(u8_to_f32_kernel, dim3(in_grid(n >> 2)), dim3(256), 0, ctx->stream, src, n, scale, dst);
+        hipLaunchKernelGGL(u8_to_f32_kernel, dim3(dfe_grid1d(n >> 2)), dim3(256), 0, ctx->stream, src, n, scale, dst);
     else
-        hipLaunchKernelGGL(u8_to_f32_bytes_kernel, dim3(in_grid(n)), dim3(256), 0, ctx->stream, src, n, scale, dst);
+        hipLaunchKernelGGL(u8_to_f32_bytes_kernel, dim3(dfe_grid1d(n)), dim3(256), 0, ctx->stream, src, n, scale, dst);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -165,7 +160,7 @@ int dfe_rgb2y_f32(dfe_ctx *ctx, const float *rgb, int H, int W, float *y) {
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, rgb && y, DFE_E_ARG, "dfe_rgb2y_f32: NULL tensor");
     DFE_REQUIRE(ctx, H > 0 && W > 0, DFE_E_SHAPE, "dfe_rgb2y_f32: %dx%d", H, W);
-    hipLaunchKernelGGL(rgb2y_kernel, dim3(in_grid((long long)H * W)), dim3(256), 0, ctx->stream, rgb, (long long)H * W, y);
+    hipLaunchKernelGGL(rgb2y_kernel, dim3(dfe_grid1d((long long)H * W)), dim3(256), 0, ctx->stream, rgb, (long long)H * W, y);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -265,7 +260,7 @@ int dfe_flow_depth_pair_u8_slot(dfe_ctx *ctx, int slot, int C, int H, int W, int
     float *f0 = (float *)ctx->ingest, *f1 = (float *)((char *)ctx->ingest + bytes);
     {
         DfeStageScope st(ctx, DFE_STAGE_LOAD);
-        hipLaunchKernelGGL(u8_fetch_pair_kernel, dim3(in_grid(2 * (n >> 4))), dim3(256), 0, ctx->stream, d0, d1, n, scale, f0, f1);
+        hipLaunchKernelGGL(u8_fetch_pair_kernel, dim3(dfe_grid1d(2 * (n >> 4))), dim3(256), 0, ctx->stream, d0, d1, n, scale, f0, f1);
         DFE_LAUNCH_CHECK(ctx);
     }
     DFE_HIP(ctx, hipEventRecord(ctx->consumed[slot], ctx->stream));   // (the conversion is the slot's only reader)

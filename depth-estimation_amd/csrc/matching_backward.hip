@@ -54,13 +54,6 @@ __global__ void matching_grad2_kernel(MatchGeom g, const float *__restrict__ in1
     }
 }
 
-int grid_for_n(long long n) {
-    long long b = (n + 255) / 256;
-    if (b > 256 * 32) b = 256 * 32;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 }  // namespace
 
 extern "C" {
@@ -73,10 +66,10 @@ int dfe_spatial_matching_backward_f32(dfe_ctx *ctx, const float *in1, const floa
                 "dfe_spatial_matching_backward_f32: K=%d H1=%d W1=%d window %dx%d must be positive", K, H1, W1, maxh, maxw);
     MatchGeom g{K, H1, W1, maxh, maxw, H1 + maxh - 1, W1 + maxw - 1};
     if (gradIn1)
-        hipLaunchKernelGGL(matching_grad1_kernel, dim3(grid_for_n((long long)K * H1 * W1)), dim3(256), 0, ctx->stream, g, in1, in2, gradOut,
+        hipLaunchKernelGGL(matching_grad1_kernel, dim3(dfe_grid1d((long long)K * H1 * W1)), dim3(256), 0, ctx->stream, g, in1, in2, gradOut,
                            gradIn1);
     if (gradIn2)
-        hipLaunchKernelGGL(matching_grad2_kernel, dim3(grid_for_n((long long)K * g.H2 * g.W2)), dim3(256), 0, ctx->stream, g, in1, in2,
+        hipLaunchKernelGGL(matching_grad2_kernel, dim3(dfe_grid1d((long long)K * g.H2 * g.W2)), dim3(256), 0, ctx->stream, g, in1, in2,
                            gradOut, gradIn2);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;

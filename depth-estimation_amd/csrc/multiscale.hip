@@ -43,6 +43,21 @@ template <int R, typename T = float> __device__ __forceinline__ float box_sum(co
     for (int k = 0; k < R * R; ++k) s = s + t[k];
     return s;
 }
+// the mean of the r x r box at src: box_sum for the usual ratios, the generic row-major loop otherwise, then * inv = 1 / (r r); r == 1 is
+// the pixel itself (0 + p, and p * 1.0f, are p)
+template <typename T = float> __device__ __forceinline__ float box_mean(const T *__restrict__ src, int W, int r, float inv, float sc = 0.f) {
+#pragma clang fp contract(off)
+    float s = 0.f;
+    if (r == 1) s = 0.f + px_ld(src, 0, sc);
+    else if (r == 2) s = box_sum<2, T>(src, W, sc);
+    else if (r == 4) s = box_sum<4, T>(src, W, sc);
+    else if (r == 8) s = box_sum<8, T>(src, W, sc);
+    else {
+        for (int i = 0; i < r; ++i)
+            for (int j = 0; j < r; ++j) s = s + px_ld(src, (long long)i * W + j, sc);
+    }
+    return r > 1 ? s * inv : s;
+}
 __global__ void downsample_box_kernel(const float *__restrict__ img, int C, int H, int W, int r, float *__restrict__ out) {
 #pragma clang fp contract(off)
     const int Ho = H / r, Wo = W / r;
@@ -53,15 +68,7 @@ __global__ void downsample_box_kernel(const float *__restrict__ img, int C, int 
         long long t = e / Wo;
         int y = (int)(t % Ho), c = (int)(t / Ho);
         const float *src = img + ((long long)c * H + y * r) * W + x * r;
-        float s = 0.f;
-        if (r == 2) s = box_sum<2>(src, W);
-        else if (r == 4) s = box_sum<4>(src, W);
-        else if (r == 8) s = box_sum<8>(src, W);
-        else {
-            for (int i = 0; i < r; ++i)
-                for (int j = 0; j < r; ++j) s = s + src[(long long)i * W + j];
-        }
-        out[e] = s * inv;
+        out[e] = box_mean(src, W, r, inv);
     }
 }
 
@@ -99,16 +106,7 @@ __device__ __forceinline__ void prep_scale_body(const T *__restrict__ I0, const 
         float v = 0.f;
         if (sy >= 0 && sy < Hs && sx >= 0 && sx < Ws) {
             const T *src = img + ((long long)c * H + sy * r) * W + sx * r;
-            float s = 0.f;
-            if (r == 1) s = 0.f + px_ld(src, 0, sc);
-            else if (r == 2) s = box_sum<2, T>(src, W, sc);
-            else if (r == 4) s = box_sum<4, T>(src, W, sc);
-            else if (r == 8) s = box_sum<8, T>(src, W, sc);
-            else {
-                for (int i = 0; i < r; ++i)
-                    for (int j = 0; j < r; ++j) s = s + px_ld(src, (long long)i * W + j, sc);
-            }
-            v = r > 1 ? s * inv : s;
+            v = box_mean<T>(src, W, r, inv, sc);
         }
         (second ? p1 : p0)[ee] = v;
     }
@@ -212,16 +210,7 @@ __global__ void prep_frames_kernel(int C, int H, int W, PrepFrames pf) {
         float v = 0.f;
         if (sy >= 0 && sy < Hs && sx >= 0 && sx < Ws) {
             const float *src = img + ((long long)c * H + sy * r) * W + sx * r;
-            float s = 0.f;
-            if (r == 1) s = 0.f + src[0];
-            else if (r == 2) s = box_sum<2>(src, W);
-            else if (r == 4) s = box_sum<4>(src, W);
-            else if (r == 8) s = box_sum<8>(src, W);
-            else {
-                for (int i = 0; i < r; ++i)
-                    for (int j = 0; j < r; ++j) s = s + src[(long long)i * W + j];
-            }
-            v = r > 1 ? s * inv : s;
+            v = box_mean(src, W, r, inv);
         }
         out[e] = v;
     }
@@ -947,13 +936,6 @@ int fill_cascade(dfe_ctx *ctx, CascadeGeom &g, const int *ratios, int nratios, i
 }
 
 constexpr int PREP_EPT = 8;   // elements per thread of prep_scales_kernel (measured: EXPERIMENTS.md)
-int grid1d(long long n, int per_block) {
-    long long b = (n + per_block - 1) / per_block;
-    if (b > 256 * 32) b = 256 * 32;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 }  // namespace
 
 extern "C" {
@@ -961,7 +943,7 @@ extern "C" {
 int dfe_downsample_box_f32(dfe_ctx *ctx, const float *img, int C, int H, int W, int r, float *out) {
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, img && out && C > 0 && r > 0 && H >= r && W >= r, DFE_E_ARG, "dfe_downsample_box_f32: bad argument");
-    hipLaunchKernelGGL(downsample_box_kernel, dim3(grid1d((long long)C * (H / r) * (W / r), 256)), dim3(256), 0, ctx->stream, img, C, H, W,
+    hipLaunchKernelGGL(downsample_box_kernel, dim3(dfe_grid1d((long long)C * (H / r) * (W / r), 256)), dim3(256), 0, ctx->stream, img, C, H, W,
                        r, out);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
@@ -985,12 +967,12 @@ int dfe_pyramid_scale_volume_f32(dfe_ctx *ctx, const float *I0, const float *I1,
     float *d0 = (float *)scr, *d1 = d0 + nd, *p0 = d1 + nd, *p1 = p0 + np;
     const float *s0 = I0, *s1 = I1;
     if (r > 1) {
-        hipLaunchKernelGGL(downsample_box_kernel, dim3(grid1d((long long)nd, 256)), dim3(256), 0, ctx->stream, I0, C, H, W, r, d0);
-        hipLaunchKernelGGL(downsample_box_kernel, dim3(grid1d((long long)nd, 256)), dim3(256), 0, ctx->stream, I1, C, H, W, r, d1);
+        hipLaunchKernelGGL(downsample_box_kernel, dim3(dfe_grid1d((long long)nd, 256)), dim3(256), 0, ctx->stream, I0, C, H, W, r, d0);
+        hipLaunchKernelGGL(downsample_box_kernel, dim3(dfe_grid1d((long long)nd, 256)), dim3(256), 0, ctx->stream, I1, C, H, W, r, d1);
         s0 = d0; s1 = d1;
     }
-    hipLaunchKernelGGL(zero_pad_kernel, dim3(grid1d((long long)np, 256)), dim3(256), 0, ctx->stream, s0, C, Hs, Ws, pl, pt, Hp, Wp, p0);
-    hipLaunchKernelGGL(zero_pad_kernel, dim3(grid1d((long long)np, 256)), dim3(256), 0, ctx->stream, s1, C, Hs, Ws, pl, pt, Hp, Wp, p1);
+    hipLaunchKernelGGL(zero_pad_kernel, dim3(dfe_grid1d((long long)np, 256)), dim3(256), 0, ctx->stream, s0, C, Hs, Ws, pl, pt, Hp, Wp, p0);
+    hipLaunchKernelGGL(zero_pad_kernel, dim3(dfe_grid1d((long long)np, 256)), dim3(256), 0, ctx->stream, s1, C, Hs, Ws, pl, pt, Hp, Wp, p1);
     DFE_LAUNCH_CHECK(ctx);
     // frame-0 crop floor/ceil((maxw-1)/2) (:198-202) is the oy/ox offset of the cost-volume op
     return cv_frames_dispatch(ctx, p0, p1, C, Hp, Wp, (long long)Hp * Wp, kh, kw, maxh, maxw, out);
@@ -1060,16 +1042,12 @@ struct MsRun {
 static int ms_filter_field(dfe_ctx *ctx, const MsArgs &a, int *hk, int *wk, int *maxplanes) {
     const MsFilter *filt = a.filt;
     for (int v = 0; v < (filt->share ? 1 : a.nratios); ++v) {
-        int h = 1, w = 1, nin = a.C;
-        for (int l = 0; l < filt->nlayers; ++l) {
-            const dfe_filter_layer &L = filt->layers[v * filt->nlayers + l];
-            DFE_REQUIRE(ctx, L.weight && L.nIn > 0 && L.nOut > 0 && L.kH > 0 && L.kW > 0, DFE_E_ARG, "dfe_multiscale_flow_pair_filtered_f32: layer %d: bad description", l);
-            DFE_REQUIRE(ctx, L.conn ? L.nIn <= nin : L.nIn == nin, DFE_E_SHAPE, "dfe_multiscale_flow_pair_filtered_f32: layer %d reads %d planes, the layer before it makes %d", l, L.nIn, nin);
-            h += L.kH - 1; w += L.kW - 1; nin = L.nOut;
-            if (L.nOut > *maxplanes) *maxplanes = L.nOut;
-        }
-        DFE_REQUIRE(ctx, v == 0 || (h == *hk && w == *wk), DFE_E_SHAPE, "dfe_multiscale_flow_pair_filtered_f32: the scales' filter stacks have different receptive fields");
-        *hk = h; *wk = w;
+        DfeStackGeom sg;
+        const int rc = dfe_filter_stack_geom(ctx, "dfe_multiscale_flow_pair_filtered_f32", filt->layers + v * filt->nlayers, filt->nlayers, a.C, &sg);
+        if (rc) return rc;
+        DFE_REQUIRE(ctx, v == 0 || (sg.hk == *hk && sg.wk == *wk), DFE_E_SHAPE, "dfe_multiscale_flow_pair_filtered_f32: the scales' filter stacks have different receptive fields");
+        *hk = sg.hk; *wk = sg.wk;
+        if (sg.maxplanes > *maxplanes) *maxplanes = sg.maxplanes;
     }
     return DFE_OK;
 }
@@ -1089,7 +1067,7 @@ static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
     if (rc) return rc;
     P.g.H = H; P.g.W = W;
     const int N = P.N = maxh * maxw;
-    P.middle = ((maxh + 1) / 2 - 1) * maxw + (maxw + 1) / 2;   // yx2xMulti(0, 0)
+    P.middle = dfe_window_middle(maxh, maxw);   // yx2xMulti(0, 0)
     int maxplanes = C;
     P.hk = P.wk = k;
     if (a.filt) {
@@ -1209,7 +1187,7 @@ static int ms_prep_raw(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B) {
     } else {
         PrepScales ps;
         for (int s = 0; s < a.nratios; ++s) { ps.r[s] = P.sc[s].r; ps.Hp[s] = P.sc[s].Hp; ps.Wp[s] = P.sc[s].Wp; ps.p0[s] = B.p0[s]; ps.p1[s] = B.p1[s]; }
-        const dim3 grid(grid1d(2 * P.frame_max, 256 * PREP_EPT), a.nratios);
+        const dim3 grid(dfe_grid1d(2 * P.frame_max, 256 * PREP_EPT), a.nratios);
         if (a.u8_scale > 0.f) hipLaunchKernelGGL(prep_scales_kernel<unsigned char>, grid, dim3(256), 0, ctx->stream, b0, b1, a.C, a.H, a.W, P.pl, P.pt, ps, a.u8_scale);
         else hipLaunchKernelGGL(prep_scales_kernel<float>, grid, dim3(256), 0, ctx->stream, a.I0, a.I1, a.C, a.H, a.W, P.pl, P.pt, ps, 0.f);
     }
@@ -1236,7 +1214,7 @@ static int ms_learned_front(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, MsRu
     }
     {
         DfeStageScope st(ctx, DFE_STAGE_FILTER);
-        hipLaunchKernelGGL(prep_frames_kernel, dim3(grid1d(P.frame_max, 256 * 8), 2 * nratios), dim3(256), 0, ctx->stream, a.C, a.H, a.W, pf);
+        hipLaunchKernelGGL(prep_frames_kernel, dim3(dfe_grid1d(P.frame_max, 256 * 8), 2 * nratios), dim3(256), 0, ctx->stream, a.C, a.H, a.W, pf);
     }
     DFE_LAUNCH_CHECK(ctx);
     // layer by layer, both frames of every scale in ONE launch (18 launches of a few microseconds each otherwise)
@@ -1314,7 +1292,7 @@ static int ms_raw_volumes(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, MsRun 
 static void ms_round_half(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, int s_begin, int s_end) {
     for (int s = s_begin; s < s_end; ++s) {
         const long long n = (long long)P.sc[s].Hs * P.sc[s].Ws * P.N;
-        hipLaunchKernelGGL(round_half_kernel, dim3(grid1d(n, 256)), dim3(256), 0, ctx->stream, B.cost[s], n, P.a.f16_scale, 1.0f / P.a.f16_scale);
+        hipLaunchKernelGGL(round_half_kernel, dim3(dfe_grid1d(n, 256)), dim3(256), 0, ctx->stream, B.cost[s], n, P.a.f16_scale, 1.0f / P.a.f16_scale);
     }
 }
 
@@ -1452,7 +1430,7 @@ static int ms_cascade_cell(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const
         nsoft = nratios - 1;
     }
     if (soft_max > 0 && nsoft > 0 && !R.soft_done) {   // (soft_done: the volume launch has taken the coarser scales' soft-mins)
-        hipLaunchKernelGGL(softmin_scales_kernel, dim3(grid1d(soft_max, kWaves * (N <= 64 ? 8 : 4)), nsoft), dim3(kWaves * 64), 0, ctx->stream, ss, N);
+        hipLaunchKernelGGL(softmin_scales_kernel, dim3(dfe_grid1d(soft_max, kWaves * (N <= 64 ? 8 : 4)), nsoft), dim3(kWaves * 64), 0, ctx->stream, ss, N);
         DFE_LAUNCH_CHECK(ctx);
     }
     DecodeTab dt;
@@ -1462,7 +1440,7 @@ static int ms_cascade_cell(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const
         hipLaunchKernelGGL(cascade_argmax_kernel<true>, cascade_fast_grid(a.H, a.W), dim3(kWaves * 64), P.lds, ctx->stream, g, P.mg, P.middle, (long long *)a.idx,
                            (float *)nullptr, a.flow, P.fx, a.W, 0, 0, dt);
     } else {
-        hipLaunchKernelGGL(cascade_argmax_kernel<false>, dim3(grid1d((long long)a.H * a.W, kWaves)), dim3(kWaves * 64), P.lds, ctx->stream, g, P.mg, P.middle,
+        hipLaunchKernelGGL(cascade_argmax_kernel<false>, dim3(dfe_grid1d((long long)a.H * a.W, kWaves)), dim3(kWaves * 64), P.lds, ctx->stream, g, P.mg, P.middle,
                            (long long *)a.idx, (float *)nullptr, a.flow, P.fx, a.W, 0, 0, dt);
     }
     DFE_LAUNCH_CHECK(ctx);
@@ -1591,8 +1569,6 @@ int dfe_multiscale_flow_pair_filtered_f32(dfe_ctx *ctx, const float *I0, const f
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, layers && nlayers >= 1 && nlayers <= 16, DFE_E_ARG, "dfe_multiscale_flow_pair_filtered_f32: nlayers=%d", nlayers);
     DFE_REQUIRE(ctx, f16_scale >= 0.f && f16_scale < INFINITY, DFE_E_ARG, "dfe_multiscale_flow_pair_filtered_f32: f16_scale=%g", (double)f16_scale);
-    DFE_REQUIRE(ctx, layers[0].nIn == C || layers[0].conn, DFE_E_SHAPE, "dfe_multiscale_flow_pair_filtered_f32: frames have %d channels, the first layer reads %d", C,
-                layers[0].nIn);
     const MsFilter filt{layers, nlayers, share_filters};
     return multiscale_flow_pair(ctx, I0, I1, C, H, W, 1, maxh, maxw, ratios, nratios, flow, idx, f16_scale, &filt);
 }
@@ -1602,7 +1578,7 @@ int dfe_softmin_f32(dfe_ctx *ctx, const float *cost, int64_t P, int N, float *pr
     DFE_REQUIRE(ctx, P >= 0 && N > 0, DFE_E_SHAPE, "dfe_softmin_f32: P=%lld N=%d", (long long)P, N);
     if (P == 0) return DFE_OK;
     DFE_REQUIRE(ctx, cost && prob, DFE_E_ARG, "dfe_softmin_f32: NULL tensor");
-    hipLaunchKernelGGL(softmin_kernel, dim3(grid1d(P, kWaves * (N <= 64 ? 8 : 4))), dim3(kWaves * 64), 0, ctx->stream, cost, (long long)P, N, prob);
+    hipLaunchKernelGGL(softmin_kernel, dim3(dfe_grid1d(P, kWaves * (N <= 64 ? 8 : 4))), dim3(kWaves * 64), 0, ctx->stream, cost, (long long)P, N, prob);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -1623,7 +1599,7 @@ int dfe_cascade_ring_f32(dfe_ctx *ctx, const float *const *prob, const int *rati
     g.H = H; g.W = W;
     size_t lds = (size_t)kWaves * 2 * maxh * maxw * sizeof(float);
     DFE_REQUIRE(ctx, lds <= 64 * 1024, DFE_E_UNSUPPORTED, "dfe_cascade_ring_f32: window %dx%d too large", maxh, maxw);
-    hipLaunchKernelGGL(cascade_kernel<true>, dim3(grid1d((long long)H * W, kWaves)), dim3(kWaves * 64), lds, ctx->stream, g, out);
+    hipLaunchKernelGGL(cascade_kernel<true>, dim3(dfe_grid1d((long long)H * W, kWaves)), dim3(kWaves * 64), lds, ctx->stream, g, out);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -1649,11 +1625,11 @@ int dfe_cascade_flow_f32(dfe_ctx *ctx, const float *const *prob, const int *rati
     }
     g.H = H; g.W = W;
     // middle class = yx2xMulti(0, 0): the centre cell of scale 1 (opticalflow_model.lua:36-43)
-    const int middle = ((maxh + 1) / 2 - 1) * maxw + (maxw + 1) / 2;
+    const int middle = dfe_window_middle(maxh, maxw);
     size_t lds = (size_t)kWaves * 2 * maxh * maxw * sizeof(float);
     DFE_REQUIRE(ctx, lds <= 64 * 1024, DFE_E_UNSUPPORTED, "dfe_cascade_flow_f32: window %dx%d too large", maxh, maxw);
     if (lds < (size_t)g.ncls * sizeof(int2)) lds = (size_t)g.ncls * sizeof(int2);   // fast path: class -> displacement table
-    dim3 grid(grid1d((long long)H * W, kWaves));
+    dim3 grid(dfe_grid1d((long long)H * W, kWaves));
     if (maxh * maxw <= 64 && nratios <= 5) grid = cascade_fast_grid(H, W);   // fast path: one row per blockIdx.y
     DecodeTab dt;
     fill_decode_tab(mg, g.ncls, dt);
@@ -1681,7 +1657,7 @@ int dfe_cascading_add_f32(dfe_ctx *ctx, const float *const *in, const int *ratio
     g.H = 1; g.W = (int)P;
     size_t lds = (size_t)kWaves * 2 * maxh * maxw * sizeof(float);
     DFE_REQUIRE(ctx, lds <= 64 * 1024, DFE_E_UNSUPPORTED, "dfe_cascading_add_f32: window %dx%d too large", maxh, maxw);
-    hipLaunchKernelGGL(cascade_kernel<false>, dim3(grid1d(P, kWaves)), dim3(kWaves * 64), lds, ctx->stream, g, (float *)nullptr);
+    hipLaunchKernelGGL(cascade_kernel<false>, dim3(dfe_grid1d(P, kWaves)), dim3(kWaves * 64), lds, ctx->stream, g, (float *)nullptr);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -1703,7 +1679,7 @@ int dfe_cascading_add_backward_f32(dfe_ctx *ctx, const float *const *gradOut, co
     g.H = 1; g.W = (int)P;
     size_t lds = (size_t)kWaves * 2 * maxh * maxw * sizeof(float);
     DFE_REQUIRE(ctx, lds <= 64 * 1024, DFE_E_UNSUPPORTED, "dfe_cascading_add_backward_f32: window %dx%d too large", maxh, maxw);
-    hipLaunchKernelGGL(cascade_backward_kernel, dim3(grid1d(P, kWaves)), dim3(kWaves * 64), lds, ctx->stream, g);
+    hipLaunchKernelGGL(cascade_backward_kernel, dim3(dfe_grid1d(P, kWaves)), dim3(kWaves * 64), lds, ctx->stream, g);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }

@@ -125,13 +125,6 @@ __global__ void flow_to_depth_ardrone_kernel(const float *__restrict__ xflow, co
     }
 }
 
-int grid1d(long long n) {
-    long long b = (n + 255) / 256;
-    if (b > 256 * 32) b = 256 * 32;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 }  // namespace
 
 extern "C" {
@@ -145,10 +138,10 @@ int dfe_polar_grid_c2p_f32(dfe_ctx *ctx, int wsrc, int hsrc, int wdst, int hdst,
     const int Wp = wdst + lpadding + rpadding;
     const float kr = (float)((double)rmax / pow((double)hdst, (double)alpha));   // cartesian2polar.lua:13
     const float ktheta = (float)(2 * M_PI / wdst);                                 // :14
-    hipLaunchKernelGGL(c2p_kernel, dim3(grid1d((long long)hdst * wdst)), dim3(256), 0, ctx->stream, wdst, hdst, Wp, lpadding, xcenter,
+    hipLaunchKernelGGL(c2p_kernel, dim3(dfe_grid1d((long long)hdst * wdst)), dim3(256), 0, ctx->stream, wdst, hdst, Wp, lpadding, xcenter,
                        ycenter, kr, ktheta, alpha, mask);
     if (lpadding + rpadding > 0)
-        hipLaunchKernelGGL(c2p_pad_kernel, dim3(grid1d(2ll * hdst * (lpadding + rpadding))), dim3(256), 0, ctx->stream, wdst, hdst, Wp,
+        hipLaunchKernelGGL(c2p_pad_kernel, dim3(dfe_grid1d(2ll * hdst * (lpadding + rpadding))), dim3(256), 0, ctx->stream, wdst, hdst, Wp,
                            lpadding, rpadding, mask);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
@@ -162,7 +155,7 @@ int dfe_polar_grid_p2c_f32(dfe_ctx *ctx, int wsrc, int hsrc, int wdst, int hdst,
     const float kx = (float)((double)wsrc / (2 * M_PI));                                   // :59
     const float ky = (float)((double)hsrc / pow((double)rmax, 1.0 / (double)alpha));       // :60
     const float invalpha = (float)(1.0 / (double)alpha) * 0.5f;                            // :70
-    hipLaunchKernelGGL(p2c_kernel, dim3(grid1d((long long)hdst * wdst)), dim3(256), 0, ctx->stream, wdst, hdst, xcenter, ycenter, kx, ky,
+    hipLaunchKernelGGL(p2c_kernel, dim3(dfe_grid1d((long long)hdst * wdst)), dim3(256), 0, ctx->stream, wdst, hdst, xcenter, ycenter, kx, ky,
                        pi2, invalpha, mask);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
@@ -173,7 +166,7 @@ int dfe_warp_bilinear_f32(dfe_ctx *ctx, const float *img, int C, int H, int W, c
     DFE_REQUIRE(ctx, C > 0 && H > 0 && W > 0 && Hd >= 0 && Wd >= 0, DFE_E_SHAPE, "dfe_warp_bilinear_f32: bad shape");
     if ((long long)Hd * Wd == 0) return DFE_OK;
     DFE_REQUIRE(ctx, img && mask && out, DFE_E_ARG, "dfe_warp_bilinear_f32: NULL tensor");
-    hipLaunchKernelGGL(warp_bilinear_kernel, dim3(grid1d((long long)Hd * Wd)), dim3(256), 0, ctx->stream, img, C, H, W, mask, Hd, Wd, out);
+    hipLaunchKernelGGL(warp_bilinear_kernel, dim3(dfe_grid1d((long long)Hd * Wd)), dim3(256), 0, ctx->stream, img, C, H, W, mask, Hd, Wd, out);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -184,7 +177,7 @@ int dfe_flow_to_depth_radial(dfe_ctx *ctx, const float *rflow, int H, int W, flo
     DFE_REQUIRE(ctx, H >= 0 && W >= 0, DFE_E_SHAPE, "dfe_flow_to_depth_radial: H=%d W=%d", H, W);
     if ((long long)H * W == 0) return DFE_OK;
     DFE_REQUIRE(ctx, rflow && depth && conf, DFE_E_ARG, "dfe_flow_to_depth_radial: NULL tensor");
-    hipLaunchKernelGGL(flow_to_depth_radial_kernel, dim3(grid1d((long long)H * W)), dim3(256), 0, ctx->stream, rflow, H, W, xcenter,
+    hipLaunchKernelGGL(flow_to_depth_radial_kernel, dim3(dfe_grid1d((long long)H * W)), dim3(256), 0, ctx->stream, rflow, H, W, xcenter,
                        ycenter, infty, depth, conf);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
@@ -196,7 +189,7 @@ int dfe_flow_to_depth_ardrone(dfe_ctx *ctx, const float *xflow, const float *mas
     DFE_REQUIRE(ctx, H >= 0 && W >= 0, DFE_E_SHAPE, "dfe_flow_to_depth_ardrone: H=%d W=%d", H, W);
     if ((long long)H * W == 0) return DFE_OK;
     DFE_REQUIRE(ctx, xflow && mask && depth && conf, DFE_E_ARG, "dfe_flow_to_depth_ardrone: NULL tensor");
-    hipLaunchKernelGGL(flow_to_depth_ardrone_kernel, dim3(grid1d((long long)H * W)), dim3(256), 0, ctx->stream, xflow, mask, H, W,
+    hipLaunchKernelGGL(flow_to_depth_ardrone_kernel, dim3(dfe_grid1d((long long)H * W)), dim3(256), 0, ctx->stream, xflow, mask, H, W,
                        imu_tx, depth, conf);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;

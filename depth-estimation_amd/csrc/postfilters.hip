@@ -8,13 +8,6 @@
 
 namespace {
 
-int grid1d(long long n, int per = 256) {
-    long long b = (n + per - 1) / per;
-    if (b > 256 * 32) b = 256 * 32;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 // floor(flow + 0.5) and the global min / max of the result (over both planes) through ordered-int atomics
 __device__ __forceinline__ int ordered(float f) { int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
 __global__ void round_minmax_kernel(const float *__restrict__ flow, long long n, float *__restrict__ R, int *__restrict__ mm) {
@@ -156,7 +149,7 @@ int dfe_postprocess_image_f32(dfe_ctx *ctx, const float *flow, const float *mask
         DFE_REQUIRE(ctx, winsize * winsize <= 32, DFE_E_ARG,
                     "dfe_postprocess_image_f32: median window %dx%d exceeds the reference's 32-value buffer (opticalflow_model.lua:405)",
                     winsize, winsize);
-        hipLaunchKernelGGL(median_filter_kernel, dim3(grid1d(HW)), dim3(256), 0, ctx->stream, flow, mask, H, W, winsize, out);
+        hipLaunchKernelGGL(median_filter_kernel, dim3(dfe_grid1d(HW)), dim3(256), 0, ctx->stream, flow, mask, H, W, winsize, out);
         DFE_LAUNCH_CHECK(ctx);
         return DFE_OK;
     }
@@ -167,7 +160,7 @@ int dfe_postprocess_image_f32(dfe_ctx *ctx, const float *flow, const float *mask
     int *mm = (int *)((char *)scr + 2 * HW * sizeof(float));
     const int init[2] = {0x7fffffff, (int)0x80000000};
     DFE_HIP(ctx, hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(round_minmax_kernel, dim3(grid1d(2 * HW)), dim3(256), 0, ctx->stream, flow, 2 * HW, R, mm);
+    hipLaunchKernelGGL(round_minmax_kernel, dim3(dfe_grid1d(2 * HW)), dim3(256), 0, ctx->stream, flow, 2 * HW, R, mm);
     int h[2];
     DFE_HIP(ctx, hipMemcpyAsync(h, mm, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -175,8 +168,8 @@ int dfe_postprocess_image_f32(dfe_ctx *ctx, const float *flow, const float *mask
     DFE_REQUIRE(ctx, unord(h[1]) - unord(h[0]) <= 15.f, DFE_E_ARG,
                 "dfe_postprocess_image_f32: rounded flow spans %g..%g, more than the reference's 16x16 histogram (opticalflow_model.lua:349-351)",
                 unord(h[0]), unord(h[1]));
-    hipLaunchKernelGGL(mode_filter_kernel, dim3(grid1d(HW)), dim3(256), 0, ctx->stream, R, mask, H, W, winsize, mm, out);
-    hipLaunchKernelGGL(add_scalar_kernel, dim3(grid1d(2 * HW)), dim3(256), 0, ctx->stream, out, 2 * HW, mm);
+    hipLaunchKernelGGL(mode_filter_kernel, dim3(dfe_grid1d(HW)), dim3(256), 0, ctx->stream, R, mask, H, W, winsize, mm, out);
+    hipLaunchKernelGGL(add_scalar_kernel, dim3(dfe_grid1d(2 * HW)), dim3(256), 0, ctx->stream, out, 2 * HW, mm);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -186,8 +179,8 @@ int dfe_enlarge_mask_f32(dfe_ctx *ctx, float *mask, int H, int W, int ix, int iy
     DFE_REQUIRE(ctx, H >= 0 && W >= 0, DFE_E_SHAPE, "dfe_enlarge_mask_f32: H=%d W=%d", H, W);
     if ((long long)H * W == 0) return DFE_OK;
     DFE_REQUIRE(ctx, mask, DFE_E_ARG, "dfe_enlarge_mask_f32: NULL tensor");
-    hipLaunchKernelGGL(enlarge_rows_kernel, dim3(grid1d(H, 64)), dim3(64), 0, ctx->stream, mask, H, W, ix);
-    hipLaunchKernelGGL(enlarge_cols_kernel, dim3(grid1d(W, 64)), dim3(64), 0, ctx->stream, mask, H, W, iy);
+    hipLaunchKernelGGL(enlarge_rows_kernel, dim3(dfe_grid1d(H, 64)), dim3(64), 0, ctx->stream, mask, H, W, ix);
+    hipLaunchKernelGGL(enlarge_cols_kernel, dim3(dfe_grid1d(W, 64)), dim3(64), 0, ctx->stream, mask, H, W, iy);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -197,7 +190,7 @@ int dfe_output_extractor_f32(dfe_ctx *ctx, const float *input, int64_t P, int ma
     DFE_REQUIRE(ctx, P >= 0 && maxh > 0 && maxw > 0, DFE_E_SHAPE, "dfe_output_extractor_f32: P=%lld window %dx%d", (long long)P, maxh, maxw);
     if (P == 0) return DFE_OK;
     DFE_REQUIRE(ctx, input && x && y, DFE_E_ARG, "dfe_output_extractor_f32: NULL tensor");
-    hipLaunchKernelGGL(output_extractor_kernel, dim3(grid1d(P, 4)), dim3(256), 0, ctx->stream, input, (long long)P, maxh, maxw, x, y);
+    hipLaunchKernelGGL(output_extractor_kernel, dim3(dfe_grid1d(P, 4)), dim3(256), 0, ctx->stream, input, (long long)P, maxh, maxw, x, y);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }

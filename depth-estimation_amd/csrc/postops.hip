@@ -484,13 +484,6 @@ int fill_geom(dfe_ctx *ctx, MultiGeom &g, int maxh, int maxw, const int *ratios,
     return DFE_OK;
 }
 
-int grid_for(long long n, int block) {
-    long long b = (n + block - 1) / block;
-    if (b > 256 * 32) b = 256 * 32;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 }  // namespace
 
 void dfe_make_tailout(TailOut *po, int64_t *idx, float *best, float *fy, float *fx, float *scores, int64_t *imaxs, int Wo, int pitch, int pad_t, int pad_l,
@@ -515,8 +508,8 @@ int dfe_flow_finalize(dfe_ctx *ctx, const float2 *part, const float *centre, con
     dfe_make_tailout(&o, idx, best, fy, fx, scores, imaxs, Wo, pitch, pad_t, pad_l, scores_padded, row_off, pd);
     const long long Pb = (long long)rows * Wo;
     const int N = hWin * wWin;
-    const int middle = (wWin + 1) / 2 + wWin * ((hWin + 1) / 2 - 1);
-    const int grid = grid_for(pd ? (long long)pd->H * pd->W : Pb, 256);
+    const int middle = dfe_window_middle(hWin, wWin);
+    const int grid = dfe_grid1d(pd ? (long long)pd->H * pd->W : Pb, 256);
     DFE_REQUIRE(ctx, !fb || (rec && N > DFE_REC_NLEAD), DFE_E_ARG, "flow finalize: a fallback plane goes with records");
     if (rec) {
         DFE_REQUIRE(ctx, Pb < (1ll << 31), DFE_E_SHAPE, "flow finalize: %lld pixels in one band", Pb);   // (32-bit pixel arithmetic in the record path)
@@ -541,7 +534,7 @@ int dfe_flow_finalize(dfe_ctx *ctx, const float2 *part, const float *centre, con
 int dfe_pair_border_depth(dfe_ctx *ctx, float *flow, float *scores, int H, int W, int pad_t, int pad_l, int Ho, int Wo, float cx,
                           float cy, float *depth, float *conf) {
     const float infty = (float)((double)W / 2);   // test_opticalflow.lua:148 geometry.wImg/2
-    hipLaunchKernelGGL(pair_border_depth_kernel, dim3(grid_for((long long)H * W, 256)), dim3(256), 0, ctx->stream, flow, scores, H, W,
+    hipLaunchKernelGGL(pair_border_depth_kernel, dim3(dfe_grid1d((long long)H * W, 256)), dim3(256), 0, ctx->stream, flow, scores, H, W,
                        pad_t, pad_l, Ho, Wo, cx, cy, infty, depth, conf);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
@@ -556,7 +549,7 @@ int dfe_argbest_center(dfe_ctx *ctx, const float *vol, int64_t P, int N, int mid
     DFE_REQUIRE(ctx, middle <= N, DFE_E_ARG, "dfe_argbest_center: middle=%d > N=%d", middle, N);
     if (P == 0) return DFE_OK;
     DFE_REQUIRE(ctx, vol && idx, DFE_E_ARG, "dfe_argbest_center: NULL tensor");
-    int grid = grid_for(P, kWavesPerBlock);
+    int grid = dfe_grid1d(P, kWavesPerBlock);
     if (take_max)
         hipLaunchKernelGGL(argbest_kernel<true>, dim3(grid), dim3(kWavesPerBlock * 64), 0, ctx->stream, vol, (long long)P, N,
                            middle, (long long *)idx, best);
@@ -574,7 +567,7 @@ int dfe_extract_output(dfe_ctx *ctx, const float *input, int H, int W, int N, fl
     long long P = (long long)H * W;
     if (P == 0) return DFE_OK;
     DFE_REQUIRE(ctx, input && scores && imaxs, DFE_E_ARG, "dfe_extract_output: NULL tensor");
-    int grid = grid_for(P, kWavesPerBlock);
+    int grid = dfe_grid1d(P, kWavesPerBlock);
     if (threshold < 0.2)   // extract_output.cpp:83-85
         hipLaunchKernelGGL((extract_kernel<8, false>), dim3(grid), dim3(kWavesPerBlock * 64), 0, ctx->stream, input, P, N,
                            threshold, 0.0, (long long *)imaxs, scores, (long long *)nullptr);
@@ -593,7 +586,7 @@ int dfe_extract_output_marginalized(dfe_ctx *ctx, const float *input, int H, int
     if (P == 0) return DFE_OK;
     DFE_REQUIRE(ctx, input && ret && retgd, DFE_E_ARG, "dfe_extract_output_marginalized: NULL tensor");
     DFE_HIP(ctx, hipMemsetAsync(retgd, 0, sizeof(int64_t) * P, ctx->stream));   // :166 THLongTensor_zero(retgd)
-    int grid = grid_for(P, kWavesPerBlock);
+    int grid = dfe_grid1d(P, kWavesPerBlock);
     if (threshold < 0.2)
         hipLaunchKernelGGL((extract_kernel<8, true>), dim3(grid), dim3(kWavesPerBlock * 64), 0, ctx->stream, input, P, N,
                            threshold, threshold_acc, (long long *)ret, (float *)nullptr, (long long *)retgd);
@@ -609,7 +602,7 @@ int dfe_x2yx(dfe_ctx *ctx, const int64_t *idx, int64_t P, int maxh, int maxw, in
     DFE_REQUIRE(ctx, P >= 0 && maxh > 0 && maxw > 0, DFE_E_ARG, "dfe_x2yx: P=%lld maxh=%d maxw=%d", (long long)P, maxh, maxw);
     if (P == 0) return DFE_OK;
     DFE_REQUIRE(ctx, idx && y && x, DFE_E_ARG, "dfe_x2yx: NULL tensor");
-    hipLaunchKernelGGL(x2yx_kernel, dim3(grid_for(P, 256)), dim3(256), 0, ctx->stream, (const long long *)idx, (long long)P,
+    hipLaunchKernelGGL(x2yx_kernel, dim3(dfe_grid1d(P, 256)), dim3(256), 0, ctx->stream, (const long long *)idx, (long long)P,
                        maxh, maxw, (long long *)y, (long long *)x);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
@@ -632,13 +625,13 @@ int dfe_x2yx_multi(dfe_ctx *ctx, int maxh, int maxw, const int *ratios, int nrat
             c.borders[i] = (int)roundf((float)maxw * ((float)c.ratios[i] - (float)c.ratios[i - 1]) / (2.0f * (float)c.ratios[i]));
             c.lengths[i] = 2 * maxw + 2 * (maxh - 2 * c.borders[i]) * c.borders[i];   // :41
         }
-        hipLaunchKernelGGL(x2yx_multi_compat_kernel, dim3(grid_for(P, 256)), dim3(256), 0, ctx->stream, c,
+        hipLaunchKernelGGL(x2yx_multi_compat_kernel, dim3(dfe_grid1d(P, 256)), dim3(256), 0, ctx->stream, c,
                            (const long long *)idx, (long long)P, (long long *)y, (long long *)x);
         DFE_LAUNCH_CHECK(ctx);
         return DFE_OK;
     }
     DFE_HIP(ctx, hipMemsetAsync(ctx->dflag, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(x2yx_multi_kernel, dim3(grid_for(P, 256)), dim3(256), 0, ctx->stream, g, (const long long *)idx,
+    hipLaunchKernelGGL(x2yx_multi_kernel, dim3(dfe_grid1d(P, 256)), dim3(256), 0, ctx->stream, g, (const long long *)idx,
                        (long long)P, (long long *)y, (long long *)x, ctx->dflag);
     DFE_LAUNCH_CHECK(ctx);
     int flag = 0;
@@ -708,9 +701,9 @@ int dfe_flow_tail(dfe_ctx *ctx, const float *vol, int rows, int Wo, int hWin, in
     o.p_off = (long long)row_off * Wo; o.row_off = row_off;
     const long long Pb = (long long)rows * Wo;
     const int N = hWin * wWin;
-    const int middle = (wWin + 1) / 2 + wWin * ((hWin + 1) / 2 - 1);   // radial/radial_opticalflow_groundtruth.lua:91
+    const int middle = dfe_window_middle(hWin, wWin);
     DFE_REQUIRE(ctx, N <= 64 * 36, DFE_E_UNSUPPORTED, "dfe_flow_tail: window %dx%d has more than 2304 cells", hWin, wWin);
-    int grid = grid_for(Pb, kWavesPerBlock);
+    int grid = dfe_grid1d(Pb, kWavesPerBlock);
     const bool m8 = threshold < 0.2;   // extract_output.cpp:83-85
 #define DFE_TAIL(MM, NCH) hipLaunchKernelGGL((flow_tail_kernel<MM, NCH>), dim3(grid), dim3(kWavesPerBlock * 64), 0, ctx->stream, vol, Pb, N, hWin, wWin, middle, threshold, o)
     if (N <= 64 * 2) { if (m8) DFE_TAIL(8, 2); else DFE_TAIL(4, 2); }
@@ -729,7 +722,7 @@ int dfe_flow_to_depth_cartesian(dfe_ctx *ctx, const float *flow, int H, int W, f
     if ((long long)H * W == 0) return DFE_OK;
     DFE_REQUIRE(ctx, flow && depth && conf, DFE_E_ARG, "dfe_flow_to_depth_cartesian: NULL tensor");
     float infty = (float)((double)W / 2);   // test_opticalflow.lua:148 geometry.wImg/2
-    hipLaunchKernelGGL(flow_to_depth_cart_kernel, dim3(grid_for((long long)H * W, 256)), dim3(256), 0, ctx->stream, flow, H, W, cx,
+    hipLaunchKernelGGL(flow_to_depth_cart_kernel, dim3(dfe_grid1d((long long)H * W, 256)), dim3(256), 0, ctx->stream, flow, H, W, cx,
                        cy, infty, fix_dot, depth, conf);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;

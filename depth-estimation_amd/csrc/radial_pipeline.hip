@@ -29,13 +29,6 @@
 
 namespace {
 
-int grid1d(long long n, int bs = 256) {
-    long long b = (n + bs - 1) / bs;
-    if (b > 256 * 32) b = 256 * 32;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 __device__ __forceinline__ float bilinear_at(const float *__restrict__ p, int H, int W, float fy, float fx) {
 #pragma clang fp contract(off)
     fy = fy < 0 ? 0 : (fy > (float)(H - 1) ? (float)(H - 1) : fy);
@@ -535,7 +528,7 @@ static int radial_flow_depth_pair(dfe_ctx *ctx, const char *fn, bool sub, const 
         hipLaunchKernelGGL(polar_tables_kernel, dim3(dfe_cdiv(H > W ? H : W, 256)), dim3(256), 0, ctx->stream, W, H, kr, ktheta, p->alpha_polar, rt, sn, cs);
         if (il) {
             float4 *i0 = (float4 *)(tb + tab_b), *i1 = (float4 *)(tb + tab_b + il_b);
-            hipLaunchKernelGGL(interleave_pair_kernel, dim3(grid1d((long long)p->hImg * p->wImg)), dim3(256), 0, ctx->stream, prev, cur, p->C,
+            hipLaunchKernelGGL(interleave_pair_kernel, dim3(dfe_grid1d((long long)p->hImg * p->wImg)), dim3(256), 0, ctx->stream, prev, cur, p->C,
                                (long long)p->hImg * p->wImg, i0, i1);
             hipLaunchKernelGGL(polar_warp_pair_kernel<true>, dim3(dfe_cdiv(H, 8) * dfe_cdiv(Wp, 32)), dim3(256), 0, ctx->stream, (const float *)i0,
                                (const float *)i1, p->C, p->hImg, p->wImg, W, H, Wp, lpad, (float)e2x, (float)e2y, rt, sn, cs, pol0, pol1);
@@ -570,7 +563,7 @@ static int radial_flow_depth_pair(dfe_ctx *ctx, const char *fn, bool sub, const 
         const double kOut2 = (double)(H - (p->kH2 - 1) / 2 - p->hWin + 1) / (double)H;           // getKOutput polar.lua:12-16 (sic: not kOut)
         const double c2x = e2x * kOut2, c2y = e2y * kOut2;
         const float infty = (float)(lua_rmax(p->hImg, p->wImg, c2x, c2y) * p->kinfty);
-        hipLaunchKernelGGL(p2c_flow_depth_kernel, dim3(grid1d((long long)hOut * wOut)), dim3(256), 0, ctx->stream, pflow, hm, W, wOut, hOut,
+        hipLaunchKernelGGL(p2c_flow_depth_kernel, dim3(dfe_grid1d((long long)hOut * wOut)), dim3(256), 0, ctx->stream, pflow, hm, W, wOut, hOut,
                            (float)(e2x * kOut), (float)(e2y * kOut), kx, ky, pi2, invalpha, (float)c2x, (float)c2y, infty,
                            cart_flow, depth, conf);
         DFE_LAUNCH_CHECK(ctx);
@@ -599,7 +592,7 @@ int dfe_radial_refine_subpixel_f32(dfe_ctx *ctx, const float *volume, const floa
     DFE_REQUIRE(ctx, P > 0 && hWin > 0, DFE_E_SHAPE, "dfe_radial_refine_subpixel_f32: P=%lld hWin=%d", (long long)P, hWin);
     {
         DfeProfScope prof(ctx);
-        hipLaunchKernelGGL(radial_refine_subpixel_kernel, dim3(grid1d((long long)P)), dim3(256), 0, ctx->stream, volume, flow_in, (long long)P, hWin,
+        hipLaunchKernelGGL(radial_refine_subpixel_kernel, dim3(dfe_grid1d((long long)P)), dim3(256), 0, ctx->stream, volume, flow_in, (long long)P, hWin,
                            flow_out);
     }
     DFE_LAUNCH_CHECK(ctx);

@@ -89,11 +89,6 @@ __global__ __launch_bounds__(256) void ss_fill_kernel(long long *__restrict__ id
     }
 }
 
-int ss_grid(long long n) {
-    const long long b = (n + 255) / 256;
-    return (int)(b < 1 ? 1 : b > 16384 ? 16384 : b);
-}
-
 }  // namespace
 
 // dfe_flow_pair_filtered_f32 (mean = false) and dfe_flow_pair_filtered_mean_f32 (mean = true: processOutput's 'mean' branch, no threshold,
@@ -105,23 +100,16 @@ static int ss_flow_pair(dfe_ctx *ctx, const char *fn, bool mean, const float *I0
     DFE_REQUIRE(ctx, full || full_conf || index || scores, DFE_E_ARG, "%s: no output requested", fn);
     DFE_REQUIRE(ctx, C > 0 && H > 0 && W > 0 && nlayers >= 0 && nlayers <= 8 && maxh > 0 && maxw > 0, DFE_E_ARG,
                 "%s: C=%d %dx%d, %d layers, window %dx%d", fn, C, H, W, nlayers, maxh, maxw);
-    int hk = 1, wk = 1, K = C, maxplanes = C;
-    for (int i = 0; i < nlayers; ++i) {
-        DFE_REQUIRE(ctx, layers[i].weight && layers[i].kH > 0 && layers[i].kW > 0 && layers[i].nIn > 0 && layers[i].nOut > 0, DFE_E_ARG,
-                    "%s: layer %d is incomplete", fn, i);
-        DFE_REQUIRE(ctx, (i == 0 ? layers[0].nIn == C : (layers[i].conn || layers[i].nIn == layers[i - 1].nOut)), DFE_E_SHAPE,
-                    "%s: layer %d reads %d planes, its input has %d", fn, i, layers[i].nIn, i == 0 ? C : layers[i - 1].nOut);
-        hk += layers[i].kH - 1;
-        wk += layers[i].kW - 1;
-        K = layers[i].nOut;
-        maxplanes = maxplanes > K ? maxplanes : K;
-    }
+    DfeStackGeom sg;
+    int rc = dfe_filter_stack_geom(ctx, fn, layers, nlayers, C, &sg);
+    if (rc) return rc;
+    const int hk = sg.hk, wk = sg.wk, K = sg.K, maxplanes = sg.maxplanes;
     const int Hf = H - hk + 1, Wf = W - wk + 1;                     // the feature maps (in2 of the matcher)
     const int H1 = Hf - maxh + 1, W1 = Wf - maxw + 1;               // the model's output region = the narrowed in1
     DFE_REQUIRE(ctx, H1 > 0 && W1 > 0, DFE_E_SHAPE, "%s: frame %dx%d too small for window %dx%d behind a %dx%d filter", fn, H, W, maxh, maxw, hk, wk);
     DFE_REQUIRE(ctx, !(full || full_conf) || (hImg >= H1 && wImg >= W1), DFE_E_SHAPE, "%s: full frame %dx%d smaller than the output %dx%d", fn, hImg, wImg,
                 H1, W1);
-    const int ny = (maxh + 1) / 2 - 1, nx = (maxw + 1) / 2 - 1;     // prepareInput: narrow(2, ceil(maxh/2), ..) 1-based -> first row / column, 0-based
+    const int ny = dfe_window_lead(maxh), nx = dfe_window_lead(maxw);   // prepareInput's narrow: first row / column of patch 1
     const int N = maxh * maxw;
     const long long P1 = (long long)H1 * W1;
     // the matcher reads the narrowed in1 in place when the caller ran the filter (prefilter: rows W, planes H W floats apart), else a
@@ -139,8 +127,7 @@ static int ss_flow_pair(dfe_ctx *ctx, const char *fn, bool mean, const float *I0
     const size_t f_idx = (lean || index || mean) ? 0 : (size_t)P1 * 2, f_sc = (lean || scores || !use_threshold || mean) ? 0 : (size_t)P1;
     const size_t f_mean = (lean || !mean) ? 0 : (size_t)P1 * (5 + maxh);
     void *scr = nullptr;
-    int rc = dfe_scratch(ctx, (al(f_c0) + 2 * al(f_fa) + 2 * al(f_fb) + al(f_in1) + 2 * al(f_vol) + al(f_idx) + al(f_sc) + al(f_mean)) * sizeof(float), &scr,
-                     nlayers > 0);
+    rc = dfe_scratch(ctx, (al(f_c0) + 2 * al(f_fa) + 2 * al(f_fb) + al(f_in1) + 2 * al(f_vol) + al(f_idx) + al(f_sc) + al(f_mean)) * sizeof(float), &scr, nlayers > 0);
     if (rc) return rc;
     float *c0 = (float *)scr;
     float *fa[2] = {c0 + al(f_c0), c0 + al(f_c0) + al(f_fa)};
@@ -172,7 +159,7 @@ static int ss_flow_pair(dfe_ctx *ctx, const char *fn, bool mean, const float *I0
                 rc = dfe_filter_layer_forward_batch_view(ctx, 2, in_, L2, H2, W2, pit, pla, o2, &viewed);
                 if (rc) return rc;
                 if (!viewed) {
-                    hipLaunchKernelGGL(ss_crop_kernel, dim3(ss_grid((long long)C * Hc * Wc)), dim3(256), 0, ctx->stream, I0, (long long)H * W, W, ny, nx, Hc, Wc,
+                    hipLaunchKernelGGL(ss_crop_kernel, dim3(dfe_grid1d((long long)C * Hc * Wc, 256, 16384)), dim3(256), 0, ctx->stream, I0, (long long)H * W, W, ny, nx, Hc, Wc,
                                        (long long)C * Hc * Wc, c0);
                     DFE_LAUNCH_CHECK(ctx);
                     in_[0] = c0;
@@ -192,7 +179,7 @@ static int ss_flow_pair(dfe_ctx *ctx, const char *fn, bool mean, const float *I0
     }
     const int ho = (hImg - H1) / 2, wo = (wImg - W1) / 2;
     if ((full || full_conf) && (hImg > H1 || wImg > W1)) {
-        hipLaunchKernelGGL(ss_border_kernel, dim3(ss_grid((long long)hImg * wImg)), dim3(256), 0, ctx->stream, full, full_conf, hImg, wImg, ho, wo, H1, W1);
+        hipLaunchKernelGGL(ss_border_kernel, dim3(dfe_grid1d((long long)hImg * wImg, 256, 16384)), dim3(256), 0, ctx->stream, full, full_conf, hImg, wImg, ho, wo, H1, W1);
         DFE_LAUNCH_CHECK(ctx);
     }
     if (lean) {
@@ -207,7 +194,7 @@ static int ss_flow_pair(dfe_ctx *ctx, const char *fn, bool mean, const float *I0
         return dfe_fail(ctx, DFE_E_UNSUPPORTED, "%s: the matcher declined a shape its predicate took", fn);
     }
     if (!nlayers) {
-        hipLaunchKernelGGL(ss_crop_kernel, dim3(ss_grid((long long)K * P1)), dim3(256), 0, ctx->stream, I0, (long long)H * W, W, ny, nx, H1, W1, (long long)K * P1, in1c);
+        hipLaunchKernelGGL(ss_crop_kernel, dim3(dfe_grid1d((long long)K * P1, 256, 16384)), dim3(256), 0, ctx->stream, I0, (long long)H * W, W, ny, nx, H1, W1, (long long)K * P1, in1c);
         DFE_LAUNCH_CHECK(ctx);
         in1 = in1c;
     }
@@ -230,26 +217,26 @@ static int ss_flow_pair(dfe_ctx *ctx, const char *fn, bool mean, const float *I0
         DFE_HIP(ctx, hipMemsetAsync(mean_s, 0, (size_t)P1 * 3 * sizeof(float), ctx->stream));   // imaxs and scores
         rc = dfe_extract_output(ctx, marg, H1, W1, maxh, sc, 0.11, (int64_t *)im);
         if (rc) return rc;
-        hipLaunchKernelGGL(ss_paste_mean_kernel, dim3(ss_grid(P1)), dim3(256), 0, ctx->stream, ys, xs, sc, H1, W1, maxh, maxw, ho, wo, wImg, (long long)hImg * wImg,
+        hipLaunchKernelGGL(ss_paste_mean_kernel, dim3(dfe_grid1d(P1, 256, 16384)), dim3(256), 0, ctx->stream, ys, xs, sc, H1, W1, maxh, maxw, ho, wo, wImg, (long long)hImg * wImg,
                            full, full_conf, (long long *)index);
         DFE_LAUNCH_CHECK(ctx);
         return DFE_OK;
     }
     long long *idx_d = index ? (long long *)index : idx_s;
     float *sc_d = scores ? scores : sc_s;
-    const int middle = (maxw + 1) / 2 + maxw * ((maxh + 1) / 2 - 1);
+    const int middle = dfe_window_middle(maxh, maxw);
     if (!use_threshold) {
         rc = dfe_argbest_center(ctx, prob, P1, N, middle, 1, (int64_t *)idx_d, nullptr);
         if (rc) return rc;
         if (scores) DFE_HIP(ctx, hipMemsetAsync(scores, 0, (size_t)P1 * sizeof(float), ctx->stream));
     } else {
-        hipLaunchKernelGGL(ss_fill_kernel, dim3(ss_grid(P1)), dim3(256), 0, ctx->stream, idx_d, sc_d, P1, (long long)middle);
+        hipLaunchKernelGGL(ss_fill_kernel, dim3(dfe_grid1d(P1, 256, 16384)), dim3(256), 0, ctx->stream, idx_d, sc_d, P1, (long long)middle);
         DFE_LAUNCH_CHECK(ctx);
         rc = dfe_extract_output(ctx, prob, H1, W1, N, sc_d, 0.11, (int64_t *)idx_d);
         if (rc) return rc;
     }
     if (full || full_conf) {
-        hipLaunchKernelGGL(ss_paste_kernel, dim3(ss_grid(P1)), dim3(256), 0, ctx->stream, idx_d, sc_d, H1, W1, maxh, maxw, use_threshold ? 1 : 0, (float)threshold, ho, wo,
+        hipLaunchKernelGGL(ss_paste_kernel, dim3(dfe_grid1d(P1, 256, 16384)), dim3(256), 0, ctx->stream, idx_d, sc_d, H1, W1, maxh, maxw, use_threshold ? 1 : 0, (float)threshold, ho, wo,
                            wImg, (long long)hImg * wImg, full, full_conf);
         DFE_LAUNCH_CHECK(ctx);
     }
@@ -289,7 +276,7 @@ extern "C" int dfe_spatial_matching_strided_f32(dfe_ctx *ctx, const float *in1, 
     rc = dfe_scratch(ctx, (size_t)K * H1 * W1 * sizeof(float), &scr);
     if (rc) return rc;
     // (a view with rows pitch apart inside planes plane apart: the crop kernel's (plane, W) pair)
-    hipLaunchKernelGGL(ss_crop_kernel, dim3(ss_grid((long long)K * H1 * W1)), dim3(256), 0, ctx->stream, in1, (long long)in1_plane, in1_pitch, 0, 0, H1, W1,
+    hipLaunchKernelGGL(ss_crop_kernel, dim3(dfe_grid1d((long long)K * H1 * W1, 256, 16384)), dim3(256), 0, ctx->stream, in1, (long long)in1_plane, in1_pitch, 0, 0, H1, W1,
                        (long long)K * H1 * W1, (float *)scr);
     DFE_LAUNCH_CHECK(ctx);
     return dfe_spatial_matching_dispatch(ctx, (const float *)scr, in2, K, H1, W1, maxh, maxw, out);

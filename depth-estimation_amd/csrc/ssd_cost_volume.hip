@@ -2170,7 +2170,7 @@ static int flow_pipeline(dfe_ctx *ctx, const float *I0, const float *I1, int C, 
     fa.rec_rows = Ho;
     fa.Ptot = P;
     {
-        const int middle = (wWin + 1) / 2 + wWin * ((hWin + 1) / 2 - 1);   // radial/radial_opticalflow_groundtruth.lua:91
+        const int middle = dfe_window_middle(hWin, wWin);
         fa.cmid = (middle - 1) >> 6; fa.lmid = (middle - 1) & 63;
     }
     const int nb = band_count(Ho, band);

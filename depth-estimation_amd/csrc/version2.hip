@@ -40,11 +40,6 @@ __global__ __launch_bounds__(256) void v2_argmin_decode_kernel(const float *__re
     }
 }
 
-int v2_grid(long long n, int per_block) {
-    long long b = (n + per_block - 1) / per_block;
-    return (int)(b < 1 ? 1 : b > 65535 * 16 ? 65535 * 16 : b);
-}
-
 }  // namespace
 
 extern "C" int dfe_version2_flow_pair_f32(dfe_ctx *ctx, const float *prev, const float *cur, int C, int H, int W, const float *norm_kernel_host,
@@ -54,26 +49,17 @@ extern "C" int dfe_version2_flow_pair_f32(dfe_ctx *ctx, const float *prev, const
     DFE_REQUIRE(ctx, prev && cur && norm_kernel_host && layers, DFE_E_ARG, "dfe_version2_flow_pair_f32: NULL argument");
     DFE_REQUIRE(ctx, C > 0 && H > 0 && W > 0 && nlayers > 0 && nlayers <= 8 && hWin > 0 && wWin > 0, DFE_E_ARG,
                 "dfe_version2_flow_pair_f32: C=%d %dx%d, %d layers, window %dx%d", C, H, W, nlayers, hWin, wWin);
-    DFE_REQUIRE(ctx, layers[0].nIn == C, DFE_E_SHAPE, "dfe_version2_flow_pair_f32: the first layer reads %d planes, the frames have %d", layers[0].nIn, C);
-    // datap.lWin = ceil(wWin / 2) - 1, tWin = ceil(hWin / 2) - 1, rWin = floor(wWin / 2), bWin = floor(hWin / 2) (version2/test.lua:18-21)
-    const int lWin = (wWin + 1) / 2 - 1, tWin = (hWin + 1) / 2 - 1;
+    DfeStackGeom sg;
+    int rc = dfe_filter_stack_geom(ctx, "dfe_version2_flow_pair_f32", layers, nlayers, C, &sg);
+    if (rc) return rc;
+    const int hk = sg.hk, wk = sg.wk, K = sg.K, maxplanes = sg.maxplanes;
+    const int lWin = dfe_window_lead(wWin), tWin = dfe_window_lead(hWin);   // datap.lWin, tWin; rWin = floor(wWin / 2), bWin = floor(hWin / 2)
     const int Hc = H - (hWin - 1), Wc = W - (wWin - 1);           // the cropped branch's frame
-    int hk = 1, wk = 1;
-    for (int i = 0; i < nlayers; ++i) {
-        DFE_REQUIRE(ctx, layers[i].weight && layers[i].kH > 0 && layers[i].kW > 0 && layers[i].nIn > 0 && layers[i].nOut > 0, DFE_E_ARG,
-                    "dfe_version2_flow_pair_f32: layer %d is incomplete", i);
-        DFE_REQUIRE(ctx, i == 0 || layers[i].conn || layers[i].nIn == layers[i - 1].nOut, DFE_E_SHAPE, "dfe_version2_flow_pair_f32: layer %d reads %d planes, layer %d makes %d", i,
-                    layers[i].nIn, i - 1, layers[i - 1].nOut);
-        hk += layers[i].kH - 1;
-        wk += layers[i].kW - 1;
-    }
     const int H1 = Hc - hk + 1, W1 = Wc - wk + 1;                 // matcher output = the dense inference region
     DFE_REQUIRE(ctx, H1 > 0 && W1 > 0, DFE_E_SHAPE, "dfe_version2_flow_pair_f32: frame %dx%d too small for window %dx%d + kernel %dx%d", H, W, hWin, wWin, hk, wk);
-    const int K = layers[nlayers - 1].nOut, N = hWin * wWin;
+    const int N = hWin * wWin;
     const long long P = (long long)H * W, P1 = (long long)H1 * W1;
     // arena: normalisation scratch | normalised cur | cropped normalised prev | two ping-pong feature buffers per branch | volume (unless the caller gave one)
-    int maxplanes = C;
-    for (int i = 0; i < nlayers; ++i) maxplanes = maxplanes > layers[i].nOut ? maxplanes : layers[i].nOut;
     const size_t f_cn = ((size_t)C + 3) * P, f_n = (size_t)C * P, f_c = (size_t)C * Hc * Wc;
     const size_t f_fa = (size_t)maxplanes * Hc * Wc, f_fb = (size_t)maxplanes * P;
     // (the volume needs a place in the arena only when nobody gave one AND the matcher + arg-min kernel will not take the shape:
@@ -86,7 +72,7 @@ extern "C" int dfe_version2_flow_pair_f32(dfe_ctx *ctx, const float *prev, const
                          !layers[nlayers - 1].conn;
     const size_t f_nrm = mm_both ? dfe_feat_matching_mfma_scratch(H1, W1, hWin, wWin) : 0;
     void *scr = nullptr;
-    int rc = dfe_scratch(ctx, (al(f_cn) + al(f_n) + al(f_c) + 2 * al(f_fa) + 2 * al(f_fb) + al(f_vol) + al(f_nrm)) * sizeof(float), &scr);
+    rc = dfe_scratch(ctx, (al(f_cn) + al(f_n) + al(f_c) + 2 * al(f_fa) + 2 * al(f_fb) + al(f_vol) + al(f_nrm)) * sizeof(float), &scr);
     if (rc) return rc;
     float *s_cn = (float *)scr, *n1 = s_cn + al(f_cn), *c0 = n1 + al(f_n);
     float *fa[2] = {c0 + al(f_c), c0 + al(f_c) + al(f_fa)};
@@ -143,7 +129,7 @@ extern "C" int dfe_version2_flow_pair_f32(dfe_ctx *ctx, const float *prev, const
     {
         DfeStageScope st(ctx, DFE_STAGE_EXTRACT);
         if (xflow || yflow || idx) {
-            hipLaunchKernelGGL(v2_argmin_decode_kernel, dim3(v2_grid(P1, 4)), dim3(256), 0, ctx->stream, vol, P1, N, wWin, lWin, tWin, (long long *)idx, xflow, yflow);
+            hipLaunchKernelGGL(v2_argmin_decode_kernel, dim3(dfe_grid1d(P1, 4, 65535 * 16)), dim3(256), 0, ctx->stream, vol, P1, N, wWin, lWin, tWin, (long long *)idx, xflow, yflow);
             DFE_LAUNCH_CHECK(ctx);
         }
     }
@@ -159,7 +145,7 @@ extern "C" int dfe_spatial_matching_argmin_f32(dfe_ctx *ctx, const float *in1, c
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, in1 && in2 && (idx || xflow || yflow), DFE_E_ARG, "dfe_spatial_matching_argmin_f32: NULL argument");
     DFE_REQUIRE(ctx, K > 0 && H1 > 0 && W1 > 0 && maxh > 0 && maxw > 0, DFE_E_ARG, "dfe_spatial_matching_argmin_f32: K=%d %dx%d window %dx%d", K, H1, W1, maxh, maxw);
-    const int lWin = (maxw + 1) / 2 - 1, tWin = (maxh + 1) / 2 - 1;
+    const int lWin = dfe_window_lead(maxw), tWin = dfe_window_lead(maxh);
     bool done = false;
     {
         DfeStageScope st(ctx, DFE_STAGE_MATCH);
@@ -177,7 +163,7 @@ extern "C" int dfe_spatial_matching_argmin_f32(dfe_ctx *ctx, const float *in1, c
         if (rc) return rc;
     }
     DfeStageScope st(ctx, DFE_STAGE_EXTRACT);
-    hipLaunchKernelGGL(v2_argmin_decode_kernel, dim3(v2_grid(P1, 4)), dim3(256), 0, ctx->stream, (const float *)scr, P1, N, maxw, lWin, tWin, (long long *)idx, xflow, yflow);
+    hipLaunchKernelGGL(v2_argmin_decode_kernel, dim3(dfe_grid1d(P1, 4, 65535 * 16)), dim3(256), 0, ctx->stream, (const float *)scr, P1, N, maxw, lWin, tWin, (long long *)idx, xflow, yflow);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }

@@ -380,7 +380,10 @@ int dfe_multiscale_flow_pair_f16(dfe_ctx *ctx, const float *I0, const float *I1,
 /* ---- A2..A6 + A10 + A15 in one call: the multiscale matcher with its LEARNED patch filters ------------------------------- */
 /* One layer of getFilter(geometry) (opticalflow_model.lua:45-79): nn.SpatialConvolution(nIn, nOut, kW, kH), or
  * nn.SpatialConvolutionMap over a connection table when conn != NULL, followed by nn.Tanh when tanh_after (getFilter puts
- * one behind every layer but the last).  All pointers are DEVICE pointers. */
+ * one behind every layer but the last).  All pointers are DEVICE pointers.
+ * A stack of them is an array in layer order, and every entry that takes one checks it by the same rule: each layer has weight != NULL
+ * and kH, kW, nIn, nOut > 0 (else DFE_E_ARG); layers[0].nIn == C, the frames' planes; a later layer has nIn == nOut of the layer before
+ * it, or with a connection table nIn <= that nOut -- the table can name no plane the layer before does not make (else DFE_E_SHAPE). */
 typedef struct dfe_filter_layer {
     int nIn, nOut, kH, kW;
     const float *weight;   /* [nOut][nIn][kH][kW]; with conn: [nConn][kH][kW] */

@@ -58,6 +58,7 @@ def _same(one, stg, threshold):
     (44, 301, [(3, 5, 5, 6)], 12, 17, 30.0, 1.0),     # 12 rows of a 17-wide window, W1 % 4 = 1
     (40, 290, [(3, 3, 3, 5)], 6, 16, 30.0, 1.0),      # a window of fewer rows than a DPP row has lanes
     (48, 64, [(3, 5, 5, 4), (4, 3, 3, 6)], 9, 9, 1.0, 30.0),   # other windows: the stand-alone ops, same results
+    (48, 64, [(3, 5, 5, 4), (2, 3, 3, 6)], 9, 9, 1.0, 30.0),   # second layer's fan-in differs: nn.SpatialConvolutionMap over a random table
 ])
 def test_single_scale_one_call_equals_staged_and_oracle(dfe, cuda, H, W, layers, mh, mw, gain, wgain, threshold):
     """(gain / wgain: contrast of the frames / a factor on the last layer's weights, chosen so that 30 .. 50 % of the pixels have SEVERAL
@@ -263,3 +264,57 @@ def test_single_scale_unique_minimum_fast_path_and_its_ties(dfe, cuda):
     assert (idx[5:10] == 3 * mw + 4 + 1).all()
     assert (idx[12:17, :200] == 3 * mw + 4 + 1).all()                                       # the first of two equal maxima
     assert (idx[28:33, :200] == 3 * mw + 4 + 1).all()
+
+
+DFE_E_ARG, DFE_E_SHAPE = -1, -2
+
+
+def test_filter_stack_rule_is_the_same_in_every_entry(dfe, cuda):
+    """include/dfe.h's rule for a dfe_filter_layer[] stack, checked by hand-built arrays at the three entries that take one
+    (dfe_flow_pair_filtered_f32, dfe_version2_flow_pair_f32, dfe_multiscale_flow_pair_filtered_f32) on a zero 3 x 40 x 52 frame pair:
+    a connection-table layer that declares more input planes than the layer before it makes, a connection-table first layer that reads
+    fewer planes than the frames have, a full layer whose planes do not match -> DFE_E_SHAPE; a layer without weights -> DFE_E_ARG (all
+    before the first launch); the legal stack 3 -> 4 (5 x 5, tanh), 4 -> 6 (3 x 3) through a table that reads 2 of the 4 planes -> 0."""
+    import ctypes as C
+
+    from depth_estimation_amd._lib import FilterLayer, ratios_array
+
+    Cc, H, W = 3, 40, 52
+    ctx, lib = dfe.get_ctx(0), dfe.lib()
+    z0, z1 = torch.zeros((Cc, H, W), device=cuda), torch.zeros((Cc, H, W), device=cuda)
+    w = torch.zeros(6 * 5 * 5 * 5, device=cuda)                        # room for the weights of every layer below
+    bias = torch.zeros(6, device=cuda)
+    table = torch.tensor([[f, t] for t in range(1, 7) for f in (1, 3)], dtype=torch.int32, device=cuda)   # planes 1 and 3 of 4 -> 6 planes
+    nconn = table.shape[0]
+
+    def layer(nIn, nOut, k, conn=False, tanh=0, weight=True):
+        L = FilterLayer()
+        L.nIn, L.nOut, L.kH, L.kW, L.tanh_after = nIn, nOut, k, k, tanh
+        L.weight, L.bias = (w.data_ptr() if weight else None), bias.data_ptr()
+        L.conn, L.nConn = (table.data_ptr() if conn else None), (nconn if conn else 0)
+        return L
+
+    first = layer(3, 4, 5, tanh=1)
+    stacks = {
+        "legal": ([first, layer(3, 6, 3, conn=True)], 0),
+        "table layer declares prev.nOut + 1 planes": ([first, layer(5, 6, 3, conn=True)], DFE_E_SHAPE),
+        "table first layer reads C - 1 planes": ([layer(2, 6, 3, conn=True)], DFE_E_SHAPE),
+        "full layer reads other planes than the layer before makes": ([first, layer(3, 6, 3)], DFE_E_SHAPE),
+        "no weights": ([first, layer(4, 6, 3, weight=False)], DFE_E_ARG),
+    }
+    mh = mw = 8
+    full, conf = torch.empty((2, H, W), device=cuda), torch.empty((H, W), device=cuda)
+    idx = torch.empty((H, W), dtype=torch.int64, device=cuda)         # (larger than any entry's output region)
+    xf, yf = torch.empty((H, W), device=cuda), torch.empty((H, W), device=cuda)
+    kern = (C.c_float * 5)(*([0.2] * 5))
+    rr, n = ratios_array([1, 2])
+    p = lambda t: t.data_ptr()
+    for name, (layers, want) in stacks.items():
+        arr, nl = (FilterLayer * len(layers))(*layers), len(layers)
+        got = {
+            "single-scale": lib.dfe_flow_pair_filtered_f32(ctx.handle, p(z0), p(z1), Cc, H, W, arr, nl, mh, mw, 0, 0.0, H, W, p(full), p(conf), p(idx), None),
+            "version2": lib.dfe_version2_flow_pair_f32(ctx.handle, p(z0), p(z1), Cc, H, W, kern, 5, 1e-4, 1e-4, arr, nl, mh, mw, p(xf), p(yf), p(idx), None),
+            "pyramid": lib.dfe_multiscale_flow_pair_filtered_f32(ctx.handle, p(z0), p(z1), Cc, H, W, mh, mw, rr, n, arr, nl, 1, 0.0, p(full), p(idx)),
+        }
+        assert got == dict.fromkeys(got, want), (name, got, lib.dfe_last_error(ctx.handle).decode())
+    torch.cuda.synchronize()
