@@ -23,6 +23,8 @@ no CPU fallback -- a missing library or device raises.
     radialFlowDepth(..., subpixel=True), refineRadialFlowSubpixel   (not in the reference: sub-pixel radial flow -- radial.py)
     getModel(geometry).forwardFlow                      (a trained single-scale model per frame pair in one call,
                                                         output_extraction_method 'max' or 'mean' -- network.py)
+    imageScale, DepthEstimationAPI(...).nextFrameDepth  (image.scale; depth_estimation_api.lua:134-198, video -> depth per camera
+                                                        frame over the library's stream object -- stream.py)
 """
 from ._lib import lib, DfeError, LIB_PATH  # noqa: F401
 from .context import Context, get_ctx  # noqa: F401
@@ -52,6 +54,8 @@ from .network import getFilter, getFilterRadial, getModel, tables_random  # noqa
 from .radial import (getRMax, getC2PMask, getP2CMask, cartesian2polar, flow2depth, getKOutput, getP2CMaskOF,  # noqa: F401
                      computeDepthMapFromFlow, getTesterNetwork, getTrainerNetwork, getMatcher, radialFlowDepth, radial_out_shape, refineRadialFlowSubpixel)
 from .glue import SmartReshape, FunctionWrapper, Mul2, Log2, OutputExtractor, postProcessImage, enlargeMask  # noqa: F401
+from . import stream  # noqa: F401
+from .stream import imageScale, DepthEstimationAPI  # noqa: F401
 from . import torch7_io, model_io  # noqa: F401
 from .model_io import (saveModel, loadModel, loadWeightsFrom, saveNetwork, loadTesterNetwork, loadTrainerNetwork, copyWeights)  # noqa: F401
 from .torch7_io import load_calibration  # noqa: F401

@@ -166,6 +166,15 @@ PROTOTYPES = {
     "dfe_ego_motion_from_images_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p, C.c_double, C.c_int, C.c_uint,
                                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "dfe_image_scale_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    "dfe_image_scale_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float] + [C.c_int] * 5 + [C.c_void_p]),
+    "dfe_mask_paste_mul_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "dfe_stream_shapes": (C.c_int, [C.c_void_p] + [c_i32p] * 8),
+    "dfe_stream_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "dfe_stream_push_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 5 + [C.POINTER(C.c_double)] * 2 + [c_i32p] * 3),
+    "dfe_stream_push_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 5 + [C.POINTER(C.c_double)] * 2 + [c_i32p] * 3),
+    "dfe_stream_reset": (C.c_int, [C.c_void_p]),
+    "dfe_stream_destroy": (None, [C.c_void_p]),
 }
 
 
@@ -180,6 +189,15 @@ class TrackerParams(C.Structure):
     """dfe_tracker_params (include/dfe.h)"""
     _fields_ = [("max_points", C.c_int), ("quality", C.c_float), ("min_dist", C.c_float), ("win", C.c_int), ("levels", C.c_int),
                 ("max_iters", C.c_int), ("eps", C.c_float), ("min_eig", C.c_float), ("max_err", C.c_float)]
+
+
+class StreamParams(C.Structure):
+    """dfe_stream_params (include/dfe.h)"""
+    _fields_ = [("C", C.c_int), ("Hsrc", C.c_int), ("Wsrc", C.c_int), ("hImg", C.c_int), ("wImg", C.c_int), ("K", C.c_double * 9), ("has_dist", C.c_int),
+                ("dist", C.c_double * 5), ("layers", C.POINTER(FilterLayer)), ("nlayers", C.c_int), ("maxh", C.c_int), ("maxw", C.c_int), ("extraction", C.c_int),
+                ("threshold", C.c_double), ("rectify", C.c_int), ("fix_mask_offset", C.c_int), ("tracker", TrackerParams), ("ransac_max_dist", C.c_double),
+                ("iterations", C.c_int), ("seed", C.c_uint), ("min_inlier_ratio", C.c_double)]
+
 
 _lib = None
 

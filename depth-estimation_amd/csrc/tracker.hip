@@ -506,6 +506,9 @@ int dfe_ego_motion_from_images_f32(dfe_ctx *ctx, const float *im0, const float *
     int n = 0;
     rc = select_run(ctx, resp, H, W, params->quality, params->min_dist, mp, p0, nullptr, &n, (char *)scr + off_sel);
     if (rc) return rc;
+    // dfe_stream_push_* (stream.hip) tells the two "fewer than 8" refusals below from an argument error by the counts: *n_corners and
+    // *n_found are written BEFORE the refusal they explain, every argument error returns before *n_corners is written, and nothing
+    // behind the second refusal returns DFE_E_ARG with a count under 8.  Keep that order, or give the refusals a code of their own.
     if (n_corners) *n_corners = n;
     if (n_found) *n_found = 0;
     DFE_REQUIRE(ctx, n >= 8, DFE_E_ARG, "dfe_ego_motion_from_images_f32: only %d corners", n);

@@ -6,9 +6,11 @@ local ffi = require 'ffi'
 
 ffi.cdef[[
 typedef struct dfe_ctx dfe_ctx;
+typedef struct dfe_stream dfe_stream;
 typedef struct dfe_radial_params { int C, hImg, wImg; int hInput, wInput; int hWin; int n1, kW1; int n2, kH2; int tanh_between; float alpha_polar; double kinfty; int zero_last_row; } dfe_radial_params;
 typedef struct dfe_filter_layer { int nIn, nOut, kH, kW; const float *weight; const float *bias; const int32_t *conn; int nConn; int tanh_after; } dfe_filter_layer;
 typedef struct dfe_tracker_params { int max_points; float quality; float min_dist; int win; int levels; int max_iters; float eps; float min_eig; float max_err; } dfe_tracker_params;
+typedef struct dfe_stream_params { int C, Hsrc, Wsrc; int hImg, wImg; double K[9]; int has_dist; double dist[5]; const dfe_filter_layer *layers; int nlayers; int maxh, maxw; int extraction; double threshold; int rectify; int fix_mask_offset; dfe_tracker_params tracker; double ransac_max_dist; int iterations; unsigned seed; double min_inlier_ratio; } dfe_stream_params;
 int dfe_version(void);
 const char *dfe_kernel_revision(void);
 int dfe_ctx_create(int device, void *stream, int own_stream, dfe_ctx **out);
@@ -126,6 +128,15 @@ int dfe_select_corners_f32(dfe_ctx *ctx, const float *resp, int H, int W, float 
 int dfe_pyr_down_f32(dfe_ctx *ctx, const float *in, int H, int W, float *out);
 int dfe_track_points_lk_f32(dfe_ctx *ctx, const float *Y0, const float *Y1, int H, int W, const float *pts0, int N, const dfe_tracker_params *params, float *pts1, int *status, float *err);
 int dfe_ego_motion_from_images_f32(dfe_ctx *ctx, const float *im0, const float *im1, int C, int H, int W, const double *K9, const dfe_tracker_params *params, double ransac_max_dist, int iterations, unsigned seed, double *R9, double *T3, int *n_found, int *n_inliers, double *F9, float *pts0_out, float *pts1_out, int *status_out, int *n_corners);
+int dfe_image_scale_f32(dfe_ctx *ctx, const float *src, int C, int Hs, int Ws, int Hd, int Wd, float *dst);
+int dfe_image_scale_u8(dfe_ctx *ctx, const uint8_t *src, float scale, int C, int Hs, int Ws, int Hd, int Wd, float *dst);
+int dfe_mask_paste_mul_f32(dfe_ctx *ctx, const float *mask, int Hm, int Wm, const float *conf, int H, int W, int oy, int ox, float *out);
+int dfe_stream_shapes(const dfe_stream_params *p, int *Hf, int *Wf, int *H1, int *W1, int *oy, int *ox, int *ix, int *iy);
+int dfe_stream_create(dfe_ctx *ctx, const dfe_stream_params *p, dfe_stream **out);
+int dfe_stream_push_f32(dfe_stream *s, const float *frame, float imu_tx, float *im_scaled, float *flow, float *mask, float *depth, float *depth_conf, double *R9, double *T3, int *n_found, int *n_inliers, int *status);
+int dfe_stream_push_u8(dfe_stream *s, const uint8_t *frame, float scale, float imu_tx, float *im_scaled, float *flow, float *mask, float *depth, float *depth_conf, double *R9, double *T3, int *n_found, int *n_inliers, int *status);
+int dfe_stream_reset(dfe_stream *s);
+void dfe_stream_destroy(dfe_stream *s);
 ]]
 
 local M = {}

@@ -1,0 +1,160 @@
+"""Video to depth in one session: the reference's only public entry point, nextFrameDepth() of depth_estimation_api.lua:134-198 (the
+drone's C++ calls it once per camera frame, ardrone/ardrone_api.cpp:77-84; test_opticalflow.lua:276-367 runs the same loop offline), over
+the library's stream object (include/dfe.h: dfe_stream_*), and image.scale (imageScale), the one stage of that loop that had no kernel.
+
+    api = DepthEstimationAPI(geometry, filter, K, distP)      # what the script's top level sets up (:25-72)
+    for frame in camera:
+        r = api.nextFrameDepth(frame)                          # None for the first frame, then (im_scaled, xflow, mask)  (:196)
+"""
+import ctypes as C
+
+import torch
+
+from ._lib import DfeError, FilterLayer, StreamParams, lib
+from .context import get_ctx, ptr
+from .opticalflow_model import _g
+from .sfm2 import _d, _sfm, _tracker_params
+
+RECTIFY = {"features": 0, "image": 1}
+
+
+def imageScale(src, width, height):
+    """image.scale(src, width, height), bilinear (depth_estimation_api.lua:71,144): src C x H x W or H x W, float32 or uint8 (uint8: the
+    byte values as floats) -> float32 C x height x width.  The definition is the library's own (dfe_image_scale_f32 in include/dfe.h):
+    pixel centres at half-integers, edge clamp, no anti-aliasing."""
+    squeeze = src.dim() == 2
+    if squeeze:
+        src = src.unsqueeze(0)
+    if src.dim() != 3 or src.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("imageScale: a float32 or uint8 C x H x W (or H x W) tensor expected")
+    src = src.contiguous()
+    Cc, H, W = src.shape
+    out = torch.empty((Cc, int(height), int(width)), dtype=torch.float32, device=src.device)
+    ctx = get_ctx(src)
+    if src.dtype == torch.uint8:
+        ctx.check(lib().dfe_image_scale_u8(ctx.handle, ptr(src), 1.0, Cc, H, W, int(height), int(width), ptr(out)))
+    else:
+        ctx.check(lib().dfe_image_scale_f32(ctx.handle, ptr(src), Cc, H, W, int(height), int(width), ptr(out)))
+    return out[0] if squeeze else out
+
+
+def stream_params(geometry, filter, K, distP, C_, Hsrc, Wsrc, rectify="features", threshold=None, fixMaskOffset=False, minInlierRatio=0.2, calibration=None,
+                  maxPoints=None, pointsQuality=None, pointsMinDistance=None, trackerWinSize=None, trackerLevels=None, trackerMaxIters=None, trackerEps=None,
+                  trackerMinEig=None, trackerMaxErr=None, ransacMaxDist=None, iterations=512, seed=0):
+    """dfe_stream_params for a geometry, a getFilter module (or None: raw frames are the features) and a camera -> (struct, keepalive).
+    The sfm keywords are getEgoMotion2's, with the same defaults (the `calibration` dict's sfm table, then sfm2.SFM_DEFAULTS)."""
+    from .multiscale import filter_layers_array
+
+    if rectify not in RECTIFY:
+        raise ValueError("rectify = %r: 'features' or 'image'" % (rectify,))
+    p = StreamParams()
+    p.C, p.Hsrc, p.Wsrc, p.hImg, p.wImg = int(C_), int(Hsrc), int(Wsrc), int(_g(geometry, "hImg")), int(_g(geometry, "wImg"))
+    p.K = _d(K, 9)
+    p.has_dist = 0 if distP is None else 1
+    if distP is not None:
+        p.dist = _d(distP, 5)
+    keep = None
+    if filter is not None:
+        arr, nl, keep = filter_layers_array([filter])
+        p.layers, p.nlayers = C.cast(arr, C.POINTER(FilterLayer)), nl
+        keep = (arr, keep)
+    p.maxh, p.maxw = int(_g(geometry, "maxh")), int(_g(geometry, "maxw"))
+    method = _g(geometry, "output_extraction_method", "max")
+    if method not in ("max", "mean"):
+        raise ValueError("output_extraction_method = %r: 'max' or 'mean'" % (method,))
+    p.extraction = 2 if method == "mean" else (1 if threshold is not None else 0)
+    p.threshold = float(threshold or 0.0)
+    p.rectify, p.fix_mask_offset = RECTIFY[rectify], int(bool(fixMaskOffset))
+    p.tracker = _tracker_params(_sfm(calibration, "max_points", maxPoints), _sfm(calibration, "points_quality", pointsQuality),
+                                _sfm(calibration, "points_min_dist", pointsMinDistance), _sfm(calibration, "tracker_win_size", trackerWinSize),
+                                _sfm(calibration, "tracker_levels", trackerLevels), _sfm(calibration, "tracker_max_iters", trackerMaxIters),
+                                _sfm(calibration, "tracker_eps", trackerEps), _sfm(calibration, "tracker_min_eig", trackerMinEig),
+                                _sfm(calibration, "tracker_max_err", trackerMaxErr))
+    p.ransac_max_dist = float(_sfm(calibration, "ransac2_max_dist", ransacMaxDist))
+    p.iterations, p.seed, p.min_inlier_ratio = int(iterations), int(seed), float(minInlierRatio)
+    return p, keep
+
+
+def stream_shapes(params):
+    """dfe_stream_shapes (host only) -> dict(Hf, Wf, H1, W1, oy, ox, ix, iy)"""
+    v = [C.c_int() for _ in range(8)]
+    rc = lib().dfe_stream_shapes(C.byref(params), *[C.byref(x) for x in v])
+    if rc != 0:
+        raise DfeError(rc, lib().dfe_last_error(None).decode())
+    return dict(zip(("Hf", "Wf", "H1", "W1", "oy", "ox", "ix", "iy"), (x.value for x in v)))
+
+
+class DepthEstimationAPI:
+    """depth_estimation_api.lua as an object.  geometry: hImg, wImg, maxh, maxw, output_extraction_method ('max' / 'mean'; the script sets
+    'mean', :31); filter: the getFilter module (loaded.filter, :28) or None for raw frames; K 3 x 3 and distP (k1, k2, p1, p2, k3) of the
+    camera frame (:32-47; distP None: no undistortion, the gopro branch of test_opticalflow.lua:279); rectify 'features' (the script, :147)
+    or 'image' (test_opticalflow.lua:284); threshold: processOutput's, for 'max' (the script passes nil, :168); fixMaskOffset: paste the
+    mask at the features' centre, not one pixel up and left of it as the script does (:177-179); minInlierRatio: the bad-image gate
+    (:159); u8Scale: what a uint8 frame is multiplied by (1 / 255: image.load's range); calibration=, and the remaining keywords: the
+    tracker's and the RANSAC's, as sfm2.getEgoMotion2 takes them.  The stream is made when the first frame shows the camera's size."""
+
+    def __init__(self, geometry, filter, K, distP=None, calibration=None, rectify="features", u8Scale=1.0 / 255.0, **sfm):
+        self.geometry, self.filter, self.K, self.distP = geometry, filter, K, distP
+        self.kw = dict(sfm, calibration=calibration, rectify=rectify)
+        self.u8Scale = float(u8Scale)
+        self.handle, self.ctx, self.shape, self.params, self._keep = None, None, None, None, None
+        self.last = {}
+
+    def _open(self, frame):
+        Cc, H, W = frame.shape
+        self.params, self._keep = stream_params(self.geometry, self.filter, self.K, self.distP, Cc, H, W, **self.kw)
+        self.ctx = get_ctx(frame)
+        h = C.c_void_p()
+        self.ctx.check(lib().dfe_stream_create(self.ctx.handle, C.byref(self.params), C.byref(h)))
+        self.handle, self.shape = h, (Cc, H, W)
+
+    def nextFrameDepth(self, frame, imu_tx=None):
+        """frame: float32 or uint8 C x H x W device tensor -> None for the first frame, else (im_scaled, xflow, mask) (:196).  self.last
+        holds status (0 first frame, 1 result, 2 bad image: zero flow and mask), im_scaled, yflow, R, T, nFound, nInliers, and with imu_tx
+        depth / depth_conf (ARdroneAPI::computeDepthMapFromFlow on the x-flow and the mask)."""
+        if frame.dim() != 3 or frame.dtype not in (torch.float32, torch.uint8):
+            raise TypeError("nextFrameDepth: a float32 or uint8 C x H x W tensor expected")
+        frame = frame.contiguous()
+        if self.handle is None:
+            self._open(frame)
+        if tuple(frame.shape) != self.shape:
+            raise DfeError(-2, "nextFrameDepth: frame %s, the stream was opened for %s" % (tuple(frame.shape), self.shape))
+        if get_ctx(frame) is not self.ctx:
+            raise DfeError(-1, "nextFrameDepth: the frame is on another device or stream than the first one")
+        p, dev = self.params, frame.device
+        ims = torch.empty((p.C, p.hImg, p.wImg), dtype=torch.float32, device=dev)
+        flow = torch.empty((2, p.hImg, p.wImg), dtype=torch.float32, device=dev)
+        mask = torch.empty((p.hImg, p.wImg), dtype=torch.float32, device=dev)
+        depth = torch.empty_like(mask) if imu_tx is not None else None
+        dconf = torch.empty_like(mask) if imu_tx is not None else None
+        R, T, nf, ni, st = (C.c_double * 9)(), (C.c_double * 3)(), C.c_int(), C.c_int(), C.c_int()
+        tail = (float(imu_tx or 0.0), ptr(ims), ptr(flow), ptr(mask), ptr(depth), ptr(dconf), R, T, C.byref(nf), C.byref(ni), C.byref(st))
+        if frame.dtype == torch.uint8:
+            self.ctx.check(lib().dfe_stream_push_u8(self.handle, ptr(frame), self.u8Scale, *tail))
+        else:
+            self.ctx.check(lib().dfe_stream_push_f32(self.handle, ptr(frame), *tail))
+        self.last = dict(status=st.value, im_scaled=ims, nFound=nf.value, nInliers=ni.value)
+        if st.value == 0:
+            return None
+        self.last.update(yflow=flow[0], xflow=flow[1], mask=mask, R=torch.tensor(R[:], dtype=torch.float64).reshape(3, 3), T=torch.tensor(T[:], dtype=torch.float64))
+        if imu_tx is not None:
+            self.last.update(depth=depth, depth_conf=dconf)
+        return ims, flow[1], mask
+
+    def reset(self):
+        """forget the previous frame: the next nextFrameDepth returns None again"""
+        if self.handle is not None:
+            self.ctx.check(lib().dfe_stream_reset(self.handle))
+        self.last = {}
+
+    def close(self):
+        if self.handle is not None:
+            lib().dfe_stream_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            if self.ctx is not None and self.ctx.handle:   # (a stream must go before its ctx)
+                self.close()
+        except Exception:
+            pass

@@ -780,6 +780,83 @@ int dfe_ego_motion_from_images_f32(dfe_ctx *ctx, const float *im0, const float *
                                    double *T3, int *n_found, int *n_inliers, double *F9, float *pts0_out, float *pts1_out,
                                    int *status_out, int *n_corners);
 
+/* ---- video to depth in one session: nextFrameDepth() of depth_estimation_api.lua:134-198 (the loop of test_opticalflow.lua:276-367) --- */
+/* image.scale(src, width, height), bilinear: src [C][Hs][Ws] -> dst [C][Hd][Wd] (depth_estimation_api.lua:71,144,
+ * test_opticalflow.lua:278,283).  `image` is un-vendored: this is the library's own definition, parity unpinned.
+ * Per axis (x shown; y alike with Hs, Hd), in exact int64 arithmetic: num = (2 x + 1) Ws - Wd, den = 2 Wd.  num < 0: i0 = 0, w = 0.
+ * Otherwise i0 = num / den (integer division), w = float32(double(num % den) / double(den)).  i1 = min(i0 + 1, Ws - 1); if
+ * i0 >= Ws - 1 then i0 = Ws - 1 and w = 0.  (Pixel centres at half-integers, edge clamp, no anti-aliasing: the mapping of
+ * torch.nn.functional.interpolate(mode = "bilinear", align_corners = False).)  Value, in fp32: top = a + wx (b - a), bot alike on the row
+ * below, out = top + wy (bot - top); a weight of exactly 0 takes the first operand as it is (no arithmetic on it).
+ * Consequences: equal sizes give a bit copy; a 2 x reduction of integer-valued frames is the exact 2 x 2 mean.
+ * _u8: the source is first converted as dfe_u8_to_f32 does, float(src) * scale, then the same arithmetic.
+ * Every size 1 .. 32768, else DFE_E_ARG. */
+int dfe_image_scale_f32(dfe_ctx *ctx, const float *src, int C, int Hs, int Ws, int Hd, int Wd, float *dst);
+int dfe_image_scale_u8(dfe_ctx *ctx, const uint8_t *src, float scale, int C, int Hs, int Ws, int Hd, int Wd, float *dst);
+/* replaces: depth_estimation_api.lua:176-182 -- mask2 = zeros(H, W); mask2:narrow(..):narrow(..):copy(mask); mask2:cmul(conf).
+ * out [H][W] = 0, and out(y + oy, x + ox) = mask(y, x) conf(y + oy, x + ox) for mask [Hm][Wm]; conf [H][W].  out may be conf itself,
+ * not mask.  DFE_E_ARG when the pasted region leaves [0, H) x [0, W). */
+int dfe_mask_paste_mul_f32(dfe_ctx *ctx, const float *mask, int Hm, int Wm, const float *conf, int H, int W, int oy, int ox, float *out);
+
+/* The stream: one object that carries what nextFrameDepth() keeps from frame to frame -- the previous undistorted frame, the previous
+ * scaled frame and the previous frame's features -- and runs the whole step per camera frame. */
+typedef struct dfe_stream dfe_stream;
+typedef struct dfe_stream_params {
+    int C, Hsrc, Wsrc;     /* the camera frame [C][Hsrc][Wsrc], C = 1 or 3 */
+    int hImg, wImg;        /* geometry.hImg / wImg: the size the model works at */
+    double K[9];           /* row-major, of the camera frame */
+    int has_dist;          /* 0: no undistortion (the gopro branch, test_opticalflow.lua:279) */
+    double dist[5];        /* (k1, k2, p1, p2, k3) */
+    const dfe_filter_layer *layers;   /* HOST array, copied by dfe_stream_create; the device weights stay the caller's */
+    int nlayers;           /* 0: the scaled frames are the features */
+    int maxh, maxw;        /* the search window */
+    int extraction;        /* 0 'max', 1 'max' with extractOutput + threshold, 2 'mean' */
+    double threshold;
+    int rectify;           /* 0 FEATURES: the previous features are warped (depth_estimation_api.lua:147);
+                              1 IMAGE: the previous scaled image is warped, then filtered (test_opticalflow.lua:284) */
+    int fix_mask_offset;   /* 0: the mask is pasted where the reference pastes it, one pixel up and left of the centre; 1: at the centre */
+    dfe_tracker_params tracker;
+    double ransac_max_dist;
+    int iterations;
+    unsigned seed;
+    double min_inlier_ratio;   /* bad image below it; 0.2 in the reference (depth_estimation_api.lua:159) */
+} dfe_stream_params;
+/* Host only, no ctx: checks the parameters and returns the shapes they imply (each pointer may be NULL) --
+ *   Hf, Wf   the feature maps, hImg - hKernel + 1 etc. (hKernel = sum kH - (nlayers - 1))
+ *   H1, W1   the matcher's output region, Hf - maxh + 1 etc.
+ *   oy, ox   where the rectification mask is pasted into [hImg][wImg].  FEATURES: floor((hImg - Hf) / 2) - 1 -- the reference hands a
+ *            0-based offset to the 1-based narrow (depth_estimation_api.lua:177-179) -- or floor((hImg - Hf) / 2) with fix_mask_offset;
+ *            a negative offset (Hf == hImg without the fix: an error in Lua too) is DFE_E_ARG.  IMAGE: 0.
+ *   ix, iy   enlargeMask's arguments, ceil((wImg - W1) / 2) and ceil((hImg - H1) / 2) (:172-174)
+ * DFE_E_SHAPE when the window does not fit the feature map; dfe_last_error(NULL) has the text. */
+int dfe_stream_shapes(const dfe_stream_params *p, int *Hf, int *Wf, int *H1, int *W1, int *oy, int *ox, int *ix, int *iy);
+/* Allocates every buffer the stream needs (pushes allocate nothing of their own; the ctx's arena settles during the first pair). */
+int dfe_stream_create(dfe_ctx *ctx, const dfe_stream_params *p, dfe_stream **out);
+/* One camera frame (device [C][Hsrc][Wsrc]; _u8: converted as dfe_u8_to_f32 does).  In the reference's order: undistort (:139, if
+ * has_dist); dfe_ego_motion_from_images_f32(previous, current, K) (:141); dfe_image_scale to wImg x hImg (:144); with
+ * K_small = diag(wImg / Wsrc, hImg / Hsrc, 1) K (the reference's Khalf) dfe_remove_ego_motion_f32(previous features, K_small, R,
+ * inverse = 1) -> features, mask [Hf][Wf] (:147) -- IMAGE: the previous scaled image instead, mask [hImg][wImg], then the filter stack --;
+ * the filter stack on the scaled frame (:149); dfe_flow_pair_filtered_f32 / _mean_f32 with nlayers = 0 on the two feature maps (:164-168);
+ * dfe_enlarge_mask_f32(mask, ix, iy) (:172-174); dfe_mask_paste_mul_f32 with full_confidences (:176-182); the current frame, scaled
+ * frame and features become the previous ones (:187-189).  Each result equals that composition of the public entries bit for bit.
+ * Device outputs (each may be NULL): im_scaled [C][hImg][wImg]; flow [2][hImg][wImg], plane 0 = y, plane 1 = x; mask [hImg][wImg];
+ * depth, depth_conf [hImg][wImg] = dfe_flow_to_depth_ardrone(plane 1, mask, imu_tx), computed when either is given.
+ * Host outputs (each may be NULL): R9, T3, n_found, n_inliers as dfe_ego_motion_from_images_f32; status --
+ *   0  the first frame (after create or reset): the state is primed, only im_scaled is written
+ *   1  a result
+ *   2  bad image (:159-162): n_inliers / n_found < min_inlier_ratio, or the pose step found or tracked fewer than 8 corners.  flow, mask,
+ *      depth and depth_conf are zero (at hImg x wImg; the reference sizes them by the camera frame), R9 / T3 are not written in the
+ *      second case, the return code is 0 and the state advances as after a result.
+ * Any other error leaves the state as it was.  Synchronises (the pose is needed on the host). */
+int dfe_stream_push_f32(dfe_stream *s, const float *frame, float imu_tx, float *im_scaled, float *flow, float *mask, float *depth,
+                        float *depth_conf, double *R9, double *T3, int *n_found, int *n_inliers, int *status);
+int dfe_stream_push_u8(dfe_stream *s, const uint8_t *frame, float scale, float imu_tx, float *im_scaled, float *flow, float *mask,
+                       float *depth, float *depth_conf, double *R9, double *T3, int *n_found, int *n_inliers, int *status);
+/* forgets the previous frame: the next push returns status 0 */
+int dfe_stream_reset(dfe_stream *s);
+/* (before its ctx is destroyed) */
+void dfe_stream_destroy(dfe_stream *s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@ def cdef_from_header(h):
     h = re.sub(r"//[^\n]*", "", h)
     lines = [l for l in h.splitlines() if not l.strip().startswith("#") and 'extern "C"' not in l and l.strip() not in ("}",)]
     text = "\n".join(lines)
-    out = ["typedef struct dfe_ctx dfe_ctx;"]
+    # the opaque handles (dfe_ctx, dfe_stream)
+    out = ["typedef struct %s %s;" % (m.group(1), m.group(2)) for m in re.finditer(r"typedef\s+struct\s+(\w+)\s+(\w+)\s*;", text)]
     # the struct types the prototypes use (dfe_radial_params, dfe_filter_layer): LuaJIT rejects the whole cdef when one is missing
     for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{([^}]*)\}\s*(\w+)\s*;", text):
         body = " ".join(re.sub(r"\s+", " ", m.group(2)).strip().split())
