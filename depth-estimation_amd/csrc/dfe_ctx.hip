@@ -26,43 +26,56 @@ int dfe_fail(dfe_ctx *ctx, int code, const char *fmt, ...) {
     return code;
 }
 
+// The one place that allocates and frees what a ctx owns (dfe_ctx_destroy frees the rest): grow-only, empty (nullptr, 0) after a failure.
+int dfe_grow(dfe_ctx *ctx, DfeBuf &b, size_t bytes, const char *name, int flags, bool *contig_out) {
+    if (contig_out) *contig_out = false;
+    if (bytes <= b.bytes) return DFE_OK;
+    // a free/realloc here is a stream-ordered hazard only if a previous op still uses the buffer, so drain the stream(s) first
+    // (rare: sizes settle after the first call)
+    if ((flags & DFE_GROW_COPY_STREAM) && ctx->copy_stream) DFE_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+    DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    void *p = b.p;
+    b = DfeBuf();
+    if (p) DFE_HIP(ctx, hipFree(p));
+    p = nullptr;
+    hipError_t e = hipErrorUnknown;
+    bool contig = false;
+    // Physically contiguous memory first.  A plain hipMalloc of this size is assembled from scattered pieces, and how they happen to
+    // lie decides up to 10 % of a sweep's time: vga-luma 0.250 against 0.224 ms per pair, the same in EVERY call on a given arena, one
+    // plain arena in three to six fast, every contiguous one fast; vga-pyramid 0.077 -> 0.073, 720p-radial 0.180 -> 0.172
+    // (tools/mode_probe.py, profiles/r05_q_*, r05_r_*).  The per-CU translation counters are the same for both kinds
+    // (profiles/r05_v_*): the difference is behind the L2, in how the physical layout spreads the sweep's row-sized write streams
+    // over DRAM channels and banks.  Falls back to hipMalloc when no contiguous range is free.
+    // Callers without DFE_GROW_CONTIG (the plain arena): the batched convolution writes 4..32 feature planes side by side from every
+    // block; in contiguous memory the planes' fixed distance puts those streams on the same channels (conv 4 -> 10 planes: 45.6 against
+    // 36.1 us for a VGA pair, vga-learned 0.211 against 0.196 ms, tools/conv_place_probe.py), which scattered pages break up.
+    if ((flags & DFE_GROW_CONTIG) && ctx->opt_bool(DFE_OPT_ARENA_CONTIG, true)) {
+        e = hipExtMallocWithFlags(&p, bytes, hipDeviceMallocContiguous);
+        contig = e == hipSuccess;
+        if (!contig) { (void)hipGetLastError(); p = nullptr; }
+    }
+    if (!contig) e = hipMalloc(&p, bytes);
+    // (a failed allocation is reported here; it must not stay behind as the thread's last HIP error, where the caller's next launch
+    //  -- of this library or of the framework around it -- would report it as its own)
+    if (e != hipSuccess) { (void)hipGetLastError(); return dfe_fail(ctx, DFE_E_ALLOC, "%s hipMalloc(%zu): %s", name, bytes, hipGetErrorString(e)); }
+    b.p = p;
+    b.bytes = bytes;
+    if (contig_out) *contig_out = contig;
+    return DFE_OK;
+}
+
 int dfe_scratch(dfe_ctx *ctx, size_t bytes, void **out, bool plain) {
-    void *&arena = plain ? ctx->scratch_plain : ctx->scratch;
-    size_t &arena_bytes = plain ? ctx->scratch_plain_bytes : ctx->scratch_bytes;
-    if (bytes > arena_bytes) {
-        // grow-only; a free/realloc here is a stream-ordered hazard only if a previous op still
-        // uses the arena, so drain the stream first (rare: sizes settle after the first call).
-        DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (arena) DFE_HIP(ctx, hipFree(arena));
-        arena = nullptr;
-        arena_bytes = 0;
-        hipError_t e = hipErrorUnknown;
+    DfeBuf &arena = plain ? ctx->scratch_plain : ctx->scratch;
+    if (bytes > arena.bytes) {
         bool contig = false;
-        // Physically contiguous memory first.  A plain hipMalloc of this size is assembled from scattered pieces, and how they happen to
-        // lie decides up to 10 % of a sweep's time: vga-luma 0.250 against 0.224 ms per pair, the same in EVERY call on a given arena, one
-        // plain arena in three to six fast, every contiguous one fast; vga-pyramid 0.077 -> 0.073, 720p-radial 0.180 -> 0.172
-        // (tools/mode_probe.py, profiles/r05_q_*, r05_r_*).  The per-CU translation counters are the same for both kinds
-        // (profiles/r05_v_*): the difference is behind the L2, in how the physical layout spreads the sweep's row-sized write streams
-        // over DRAM channels and banks.  Falls back to hipMalloc when no contiguous range is free.
-        // `plain` callers: the batched convolution writes 4..32 feature planes side by side from every block; in contiguous memory the
-        // planes' fixed distance puts those streams on the same channels (conv 4 -> 10 planes: 45.6 against 36.1 us for a VGA pair,
-        // vga-learned 0.211 against 0.196 ms, tools/conv_place_probe.py), which scattered pages break up.
-        if (!plain && ctx->opt_bool(DFE_OPT_ARENA_CONTIG, true)) {
-            e = hipExtMallocWithFlags(&arena, bytes, hipDeviceMallocContiguous);
-            contig = e == hipSuccess;
-            if (!contig) { (void)hipGetLastError(); arena = nullptr; }
-        }
-        if (!contig) e = hipMalloc(&arena, bytes);
-        // (a failed allocation is reported here; it must not stay behind as the thread's last HIP error, where the caller's next launch
-        //  -- of this library or of the framework around it -- would report it as its own)
-        if (e != hipSuccess) { (void)hipGetLastError(); arena = nullptr; return dfe_fail(ctx, DFE_E_ALLOC, "scratch hipMalloc(%zu): %s", bytes, hipGetErrorString(e)); }
-        arena_bytes = bytes;
+        int rc = dfe_grow(ctx, arena, bytes, "scratch", plain ? 0 : DFE_GROW_CONTIG, &contig);
+        if (rc) return rc;
         // DFE_DEBUG_ARENA=1: where the arena landed and what it is made of
         if (ctx->opt[DFE_OPT_DEBUG_ARENA] > 0)
-            fprintf(stderr, "[dfe] scratch arena %p .. %p (%zu bytes, %s2 MiB-aligned, %s)\n", arena, (char *)arena + bytes, bytes,
-                    ((uintptr_t)arena & ((1u << 21) - 1)) ? "not " : "", contig ? "physically contiguous" : "plain hipMalloc");
+            fprintf(stderr, "[dfe] scratch arena %p .. %p (%zu bytes, %s2 MiB-aligned, %s)\n", arena.p, (char *)arena.p + bytes, bytes,
+                    ((uintptr_t)arena.p & ((1u << 21) - 1)) ? "not " : "", contig ? "physically contiguous" : "plain hipMalloc");
     }
-    *out = arena;
+    *out = arena.p;
     return DFE_OK;
 }
 
@@ -70,15 +83,11 @@ int dfe_device_alloc(dfe_ctx *ctx, size_t bytes, void **ptr, int *contiguous) {
     DFE_REQUIRE(ctx, ptr && bytes > 0, DFE_E_ARG, "dfe_device_alloc: ptr = %p, bytes = %zu", (void *)ptr, bytes);
     DFE_HIP(ctx, hipSetDevice(ctx->device));
     *ptr = nullptr;
+    DfeBuf b;   // (the caller's from here on: dfe_device_free)
     bool contig = false;
-    if (ctx->opt_bool(DFE_OPT_ARENA_CONTIG, true)) {
-        contig = hipExtMallocWithFlags(ptr, bytes, hipDeviceMallocContiguous) == hipSuccess;
-        if (!contig) { (void)hipGetLastError(); *ptr = nullptr; }
-    }
-    if (!contig) {
-        hipError_t e = hipMalloc(ptr, bytes);
-        if (e != hipSuccess) { (void)hipGetLastError(); *ptr = nullptr; return dfe_fail(ctx, DFE_E_ALLOC, "dfe_device_alloc hipMalloc(%zu): %s", bytes, hipGetErrorString(e)); }
-    }
+    int rc = dfe_grow(ctx, b, bytes, "dfe_device_alloc", DFE_GROW_CONTIG, &contig);
+    if (rc) return rc;
+    *ptr = b.p;
     if (contiguous) *contiguous = contig ? 1 : 0;
     return DFE_OK;
 }
@@ -91,17 +100,9 @@ int dfe_device_free(dfe_ctx *ctx, void *ptr) {
 }
 
 int dfe_aux_scratch(dfe_ctx *ctx, size_t bytes, void **out) {
-    if (bytes > ctx->aux_bytes) {
-        DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->aux) DFE_HIP(ctx, hipFree(ctx->aux));
-        ctx->aux = nullptr;
-        ctx->aux_bytes = 0;
-        hipError_t e = hipMalloc(&ctx->aux, bytes);
-        if (e != hipSuccess) { (void)hipGetLastError(); return dfe_fail(ctx, DFE_E_ALLOC, "aux hipMalloc(%zu): %s", bytes, hipGetErrorString(e)); }
-        ctx->aux_bytes = bytes;
-    }
-    *out = ctx->aux;
-    return DFE_OK;
+    int rc = dfe_grow(ctx, ctx->aux, bytes, "aux");
+    *out = ctx->aux.p;
+    return rc;
 }
 
 int dfe_graph_lookup(dfe_ctx *ctx, dfe_ctx::GraphSlot &slot, const void *key, size_t bytes) {
@@ -191,13 +192,10 @@ void dfe_ctx_destroy(dfe_ctx *ctx) {
     if (ctx->ms_graph.exec) (void)hipGraphExecDestroy(ctx->ms_graph.exec);
     for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
     for (const dfe_ctx::StageEvent &e : ctx->stage_events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
-    if (ctx->scratch_plain) (void)hipFree(ctx->scratch_plain);
-    if (ctx->cn_coef) (void)hipFree(ctx->cn_coef);
-    if (ctx->ingest) (void)hipFree(ctx->ingest);
-    if (ctx->aux) (void)hipFree(ctx->aux);
+    for (DfeBuf *b : {&ctx->scratch, &ctx->scratch_plain, &ctx->cn_coef, &ctx->ingest, &ctx->aux})
+        if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < DFE_NSLOT; ++i) {
-        if (ctx->slot[i]) (void)hipFree(ctx->slot[i]);
+        if (ctx->slot[i].p) (void)hipFree(ctx->slot[i].p);
         if (ctx->copied[i]) (void)hipEventDestroy(ctx->copied[i]);
         if (ctx->consumed[i]) (void)hipEventDestroy(ctx->consumed[i]);
     }

@@ -7,6 +7,7 @@
 #include <vector>
 #include <hip/hip_ext.h>
 #include "../../include/dfe.h"
+#include "dfe_carve.h"
 
 // Behaviour switches of the launchers (dfe_set_option / dfe_get_option, include/dfe.h).  -1 = automatic: the launcher's own choice
 // per shape.  The environment is read ONCE, in dfe_ctx_create (tuning scripts), never inside a launcher.
@@ -41,6 +42,8 @@ struct DfeOptName { const char *key; const char *env; bool env_presence_means_ze
 extern const DfeOptName dfe_opt_names[DFE_NOPT];
 
 constexpr int DFE_NSLOT = 3;   // device slots of the pipelined ingest (ingest.hip)
+// a grow-only device buffer that a ctx owns: grown by dfe_grow and by nothing else, freed with the ctx; empty = {nullptr, 0}
+struct DfeBuf { void *p = nullptr; size_t bytes = 0; };
 struct dfe_ctx {
     int opt[DFE_NOPT];
     dfe_ctx() { for (int i = 0; i < DFE_NOPT; ++i) opt[i] = -1; }
@@ -54,27 +57,23 @@ struct dfe_ctx {
     int cv_tyq = 0;                   // 0 = pick the tile height per shape; else dfe_set_cost_volume_tile's code (tuning / tests)
     int ncu = 256;                    // compute units of the device
     const char *last_kernel = "";
-    void *scratch = nullptr;          // grow-only device arena (never shrinks; freed with the ctx), physically contiguous where the driver grants it
-    size_t scratch_bytes = 0;
-    void *scratch_plain = nullptr;    // the arena of the paths that run learned filter stacks: a plain hipMalloc (dfe_scratch's `plain`)
-    size_t scratch_plain_bytes = 0;
+    DfeBuf scratch;                   // grow-only device arena (never shrinks; freed with the ctx), physically contiguous where the driver grants it
+    DfeBuf scratch_plain;             // the arena of the paths that run learned filter stacks: a plain hipMalloc (dfe_scratch's `plain`)
     size_t scratch_limit = (size_t)16 << 30;   // cost-volume bands are sized to fit (dfe_set_scratch_limit)
-    void *ingest = nullptr;           // grow-only fp32 copy of a uint8 frame pair (ingest.hip), freed with the ctx
-    size_t ingest_bytes = 0;
+    DfeBuf ingest;                    // fp32 copy of a uint8 frame pair (ingest.hip)
     // pipelined ingest (ingest.hip): a copy stream of the ctx's own and DFE_NSLOT device slots for frame pairs -- the upload (+ conversion)
     // of pair i+1 runs beside the step of pair i; copied[s] / consumed[s] order the two streams per slot
     hipStream_t copy_stream = nullptr;
-    void *slot[DFE_NSLOT] = {};        // two uint8 frames each
+    DfeBuf slot[DFE_NSLOT];           // two uint8 frames each
     size_t slot_bytes = 0;            // bytes of ONE frame of a slot
     hipEvent_t copied[DFE_NSLOT] = {}, consumed[DFE_NSLOT] = {};
     bool slot_used[DFE_NSLOT] = {};
     int slot_next = 0;
-    void *aux = nullptr;              // grow-only side buffer for small per-call planes (the matrix-core matcher's norms): NOT the arena, whose
-    size_t aux_bytes = 0;             // carved pointers a nested launcher must not invalidate
+    DfeBuf aux;                       // side buffer for small per-call planes (the matrix-core matcher's norms): NOT the arena, whose carved
+                                      // pointers a nested launcher must not invalidate
     // nn.SpatialContrastiveNormalization's border-correction plane (the estimator of a tensor of ones): a function of the frame size, the
     // plane count and the kernel only -- kept from call to call (filters.hip)
-    float *cn_coef = nullptr;
-    size_t cn_coef_floats = 0;
+    DfeBuf cn_coef;
     int cn_key[4] = {0, 0, 0, 0};     // H, W, C, k of the plane that is there (k = 0: none)
     float cn_key_kn[33] = {};
     int *dflag = nullptr;             // one device int for error flags raised by kernels
@@ -191,6 +190,23 @@ bool cv_finest_plan_ok(dfe_ctx *ctx, int Hp, int Wp, int maxh, int maxw);   // c
 // arena of at least `bytes`.  plain = false: physically contiguous memory if the driver has it (the volume sweeps' arena); plain = true: a
 // plain hipMalloc, for the paths whose convolutions write many feature planes side by side (see dfe_scratch in dfe_ctx.hip for both measurements)
 int dfe_scratch(dfe_ctx *ctx, size_t bytes, void **out, bool plain = false);
+// grows `b` to at least `bytes` (dfe_ctx.hip): no-op when it is large enough; else drains ctx->stream (and the copy stream with
+// DFE_GROW_COPY_STREAM), frees, allocates (physically contiguous first with DFE_GROW_CONTIG and option arena_contig).  On failure `b` is
+// empty, HIP's last error is cleared and DFE_E_ALLOC names the buffer
+enum { DFE_GROW_CONTIG = 1, DFE_GROW_COPY_STREAM = 2 };
+int dfe_grow(dfe_ctx *ctx, DfeBuf &b, size_t bytes, const char *name, int flags = 0, bool *contig_out = nullptr);
+// A launcher's layout `lay` (a function over a DfeCarve & that takes its buffers in order, dfe_carve.h) run for the size, the arena grown
+// to it, and `lay` run again on the arena
+template <class L> int dfe_scratch_carve(dfe_ctx *ctx, L &&lay, bool plain = false) {
+    DfeCarve plan;
+    lay(plan);
+    void *scr = nullptr;
+    int rc = dfe_scratch(ctx, plan.off, &scr, plain);
+    if (rc) return rc;
+    DfeCarve c(scr);
+    lay(c);
+    return DFE_OK;
+}
 // whether the one-kernel flat matcher (feat_matching_flat.hip) takes in1 as a view -- rows pitch1, planes plane1 floats apart: the arena
 // planners leave the volume out only where it does
 bool dfe_feat_matching_flat_view_takes(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw, int pitch1, long long plane1);

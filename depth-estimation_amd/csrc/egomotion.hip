@@ -155,14 +155,14 @@ int dfe_foe_from_flow_f32(dfe_ctx *ctx, const float *flow_y, const float *flow_x
     DFE_REQUIRE(ctx, flow_y && flow_x && foe_xy, DFE_E_ARG, "dfe_foe_from_flow_f32: NULL argument");
     DFE_REQUIRE(ctx, H > 0 && W > 0 && iterations >= 0 && iterations <= 16, DFE_E_SHAPE, "dfe_foe_from_flow_f32: %dx%d, %d iterations", H, W, iterations);
     const int nb = dfe_grid1d((long long)H * W) > 256 ? 256 : dfe_grid1d((long long)H * W);
-    void *scr = nullptr;
-    int rc = dfe_scratch(ctx, (size_t)nb * 5 * sizeof(double), &scr);
+    double *scr = nullptr;   // per block: the five sums
+    int rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { scr = c.take<double>((size_t)nb * 5); });
     if (rc) return rc;
     std::vector<double> host((size_t)nb * 5);
     double cx = W / 2.0, cy = H / 2.0;
     for (int it = 0; it <= iterations; ++it) {
         hipLaunchKernelGGL(foe_sums_kernel, dim3(nb), dim3(256), 0, ctx->stream, flow_y, flow_x, conf, H, W, min_flow, (float)cx, (float)cy, 2.0f, it > 0,
-                           (double *)scr);
+                           scr);
         DFE_LAUNCH_CHECK(ctx);
         DFE_HIP(ctx, hipMemcpyAsync(host.data(), scr, host.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));

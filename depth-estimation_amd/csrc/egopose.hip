@@ -272,41 +272,30 @@ int cheirality(const double *R, const double *t, const std::vector<float> &p1, c
     return good;
 }
 
-// arena layout behind `scr_off` bytes of the caller's own data: hypotheses' F, their inlier counts, the best F, the inlier mask, the
-// refit partial sums, the indices of the valid correspondences
-struct EgoLayout { size_t off_f, off_c, off_b, off_m, off_p, off_v, total; int nblk; };
-EgoLayout ego_layout(int N, int nh, size_t scr_off) {
-    EgoLayout l;
-    l.nblk = N < 256 * 64 ? (N + 255) / 256 : 64;
-    l.off_f = (scr_off + 255) / 256 * 256;
-    l.off_c = l.off_f + ((size_t)nh * 9 * 8 + 255) / 256 * 256;
-    l.off_b = l.off_c + ((size_t)nh * 4 + 255) / 256 * 256;
-    l.off_m = l.off_b + 256;
-    l.off_p = l.off_m + ((size_t)N + 255) / 256 * 256;
-    l.off_v = l.off_p + ((size_t)l.nblk * 46 * 8 + 255) / 256 * 256;
-    l.total = l.off_v + (size_t)N * 4;
-    return l;
+// the pose step's buffers: hypotheses' F, their inlier counts, the best F, the inlier mask, the refit partial sums, the indices of the
+// valid correspondences.  A caller with data of its own in the arena (the flow sampler) takes that first, on the same carver.
+struct EgoBufs { double *hypF; int *counts; double *bestF; unsigned char *mask; double *part; int *valid; int nblk; };
+EgoBufs ego_layout(DfeCarve &c, int N, int nh) {
+    EgoBufs b;
+    b.nblk = N < 256 * 64 ? dfe_cdiv(N, 256) : 64;
+    b.hypF = c.take<double>((size_t)nh * 9);
+    b.counts = c.take<int>(nh);
+    b.bestF = c.take<double>(9);
+    b.mask = c.take<unsigned char>(N);
+    b.part = c.take<double>((size_t)b.nblk * 46);
+    b.valid = c.take<int>(N);
+    return b;
 }
 
-// hw: the host's copy of the weights w (NULL with w)
+// hw: the host's copy of the weights w (NULL with w); lay: ego_layout(.., N, iterations) on the arena
 int ego_from_points(dfe_ctx *ctx, const float *p1, const float *p2, const float *w, const float *hw, int N, const double *K9, double max_dist, int iterations,
-                    unsigned seed, double *R9, double *T3, int *n_inliers, double *F9, size_t scr_off) {
+                    unsigned seed, double *R9, double *T3, int *n_inliers, double *F9, const EgoBufs &lay) {
     EgoK kk;
     DFE_REQUIRE(ctx, dfe_mat3_inv(K9, kk.Ki), DFE_E_ARG, "ego motion: K is singular");
-    const int nh = iterations;
-    const EgoLayout lay = ego_layout(N, nh, scr_off);
-    const int nblk = lay.nblk;
-    const size_t off_f = lay.off_f, off_c = lay.off_c, off_b = lay.off_b, off_m = lay.off_m, off_p = lay.off_p;
-    void *scr = nullptr;
-    int rc = dfe_scratch(ctx, lay.total, &scr);
-    if (rc) return rc;
-    // (a caller that placed its correspondences in the arena -- the flow sampler -- passes their extent as scr_off and has reserved
-    //  lay.total itself: the arena only ever grows, so this call does not move it)
-    double *hypF = (double *)((char *)scr + off_f);
-    int *counts = (int *)((char *)scr + off_c);
-    double *bestF = (double *)((char *)scr + off_b);
-    unsigned char *mask = (unsigned char *)scr + off_m;
-    double *part = (double *)((char *)scr + off_p);
+    const int nh = iterations, nblk = lay.nblk;
+    double *hypF = lay.hypF, *bestF = lay.bestF, *part = lay.part;
+    int *counts = lay.counts;
+    unsigned char *mask = lay.mask;
     // the valid correspondences, listed on the host in index order (deterministic, unlike a compaction by atomics)
     int *valid = nullptr, M = N;
     std::vector<int> hv;
@@ -315,7 +304,7 @@ int ego_from_points(dfe_ctx *ctx, const float *p1, const float *p2, const float 
         for (int n = 0; n < N; ++n)
             if (hw[n] > 0.f) hv.push_back(n);
         M = (int)hv.size();
-        valid = (int *)((char *)scr + lay.off_v);
+        valid = lay.valid;
         if (M > 0) DFE_HIP(ctx, hipMemcpyAsync(valid, hv.data(), (size_t)M * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     hipLaunchKernelGGL(ego_hypotheses_kernel, dim3((nh + 63) / 64), dim3(64), 0, ctx->stream, p1, p2, (const int *)valid, M, kk, seed, nh, hypF);
@@ -405,7 +394,10 @@ int dfe_ego_motion_from_points_f32(dfe_ctx *ctx, const float *pts1, const float 
         DFE_HIP(ctx, hipMemcpyAsync(hw.data(), weights, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
         DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    return ego_from_points(ctx, pts1, pts2, weights, weights ? hw.data() : nullptr, N, K9, ransac_max_dist, iterations, seed, R9, T3, n_inliers, F9, 0);
+    EgoBufs lay;
+    int rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { lay = ego_layout(c, N, iterations); });
+    if (rc) return rc;
+    return ego_from_points(ctx, pts1, pts2, weights, weights ? hw.data() : nullptr, N, K9, ransac_max_dist, iterations, seed, R9, T3, n_inliers, F9, lay);
 }
 
 int dfe_ego_motion_from_flow_f32(dfe_ctx *ctx, const float *flow_y, const float *flow_x, const float *conf, int H, int W, const double *K9, int max_points,
@@ -419,12 +411,13 @@ int dfe_ego_motion_from_flow_f32(dfe_ctx *ctx, const float *flow_y, const float 
     const int gh = (H - 1) / step + 1, gw = (W - 1) / step + 1;
     const int y0 = ((H - 1) - (gh - 1) * step) / 2, x0 = ((W - 1) - (gw - 1) * step) / 2;    // the grid centred in the frame
     const int N = gh * gw;
-    const size_t pts_bytes = ((size_t)N * 5 * 4 + 255) / 256 * 256;
-    // reserve the whole arena first (samples + what ego_from_points lays out behind them), so that its own dfe_scratch call cannot move it
-    void *scr = nullptr;
-    int rc = dfe_scratch(ctx, ego_layout(N, iterations, pts_bytes).total, &scr);
+    // one layout for the samples and what the pose step keeps behind them: nothing below calls dfe_scratch again, so the arena cannot move
+    // under the samples.  (p1 | p2 | w are ONE block of 5 N floats, split below.)
+    float *p1 = nullptr;
+    EgoBufs lay;
+    int rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { p1 = c.take<float>((size_t)N * 5); lay = ego_layout(c, N, iterations); });
     if (rc) return rc;
-    float *p1 = (float *)scr, *p2 = p1 + 2 * (size_t)N, *w = p2 + 2 * (size_t)N;
+    float *p2 = p1 + 2 * (size_t)N, *w = p2 + 2 * (size_t)N;
     hipLaunchKernelGGL(ego_sample_flow_kernel, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, flow_y, flow_x, conf, H, W, step, y0, x0, gh, gw, p1, p2, w);
     DFE_LAUNCH_CHECK(ctx);
     std::vector<float> hw(N);
@@ -436,7 +429,7 @@ int dfe_ego_motion_from_flow_f32(dfe_ctx *ctx, const float *flow_y, const float 
         *n_found = c;
         DFE_REQUIRE(ctx, c >= 8, DFE_E_ARG, "dfe_ego_motion_from_flow_f32: only %d usable flow samples", c);
     }
-    return ego_from_points(ctx, p1, p2, w, hw.data(), N, K9, ransac_max_dist, iterations, seed, R9, T3, n_inliers, F9, pts_bytes);
+    return ego_from_points(ctx, p1, p2, w, hw.data(), N, K9, ransac_max_dist, iterations, seed, R9, T3, n_inliers, F9, lay);
 }
 
 }  // extern "C"

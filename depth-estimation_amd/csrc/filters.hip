@@ -641,23 +641,16 @@ int dfe_contrastive_normalization_run2(dfe_ctx *ctx, const float *in0, const flo
     const int nf = in1 ? 2 : 1;
     a.in[0] = in0; a.in[1] = in1; a.out[0] = out0; a.out[1] = out1;
     // the border-correction plane depends on (H, W, C, kernel) only: computed by the first call with these, read by every later one
-    bool same = ctx->cn_coef && ctx->cn_key[0] == H && ctx->cn_key[1] == W && ctx->cn_key[2] == C && ctx->cn_key[3] == k;
+    bool same = ctx->cn_coef.p && ctx->cn_key[0] == H && ctx->cn_key[1] == W && ctx->cn_key[2] == C && ctx->cn_key[3] == k;
     for (int i = 0; same && i < k; ++i) same = ctx->cn_key_kn[i] == a.kk.kn[i];
     if (!same) {
-        if ((size_t)P > ctx->cn_coef_floats) {
-            DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->cn_coef) DFE_HIP(ctx, hipFree(ctx->cn_coef));
-            ctx->cn_coef = nullptr; ctx->cn_coef_floats = 0; ctx->cn_key[3] = 0;
-            hipError_t e = hipMalloc(&ctx->cn_coef, (size_t)P * sizeof(float));
-            if (e != hipSuccess) return dfe_fail(ctx, DFE_E_ALLOC, "normalisation coefficients hipMalloc(%lld floats): %s", P, hipGetErrorString(e));
-            ctx->cn_coef_floats = (size_t)P;
-        }
-        ctx->cn_key[0] = H; ctx->cn_key[1] = W; ctx->cn_key[2] = C; ctx->cn_key[3] = k;
-        for (int i = 0; i < k; ++i) ctx->cn_key_kn[i] = a.kk.kn[i];
+        ctx->cn_key[3] = 0;   // no plane until the launch that writes this one is known to be enqueued
+        int rc = dfe_grow(ctx, ctx->cn_coef, (size_t)P * sizeof(float), "normalisation coefficients");
+        if (rc) return rc;
     }
     a.coef_ready = same ? 1 : 0;
     for (int f = 0; f < 2; ++f) {
-        a.coef[f] = ctx->cn_coef;
+        a.coef[f] = (float *)ctx->cn_coef.p;
         a.est[f] = scratch + (2 * f + 1) * P;
         a.cx[f] = 0; a.cy[f] = 0; a.cw[f] = W; a.ch[f] = H;
     }
@@ -673,6 +666,10 @@ int dfe_contrastive_normalization_run2(dfe_ctx *ctx, const float *in0, const flo
     hipLaunchKernelGGL(k0, grid, dim3(256), lds0, ctx->stream, a);
     hipLaunchKernelGGL(k1, grid, dim3(256), lds1, ctx->stream, a);
     DFE_LAUNCH_CHECK(ctx);
+    if (!same) {
+        ctx->cn_key[0] = H; ctx->cn_key[1] = W; ctx->cn_key[2] = C; ctx->cn_key[3] = k;
+        for (int i = 0; i < k; ++i) ctx->cn_key_kn[i] = a.kk.kn[i];
+    }
     return DFE_OK;
 }
 

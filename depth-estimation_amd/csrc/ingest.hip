@@ -115,21 +115,18 @@ int launch_u8(dfe_ctx *ctx, const unsigned char *src, long long n, float scale, 
 }
 
 // the per-ctx fp32 copy of a uint8 frame pair (grow-only, next to the scratch arena that the pipelines themselves use)
+int ingest_frames(dfe_ctx *ctx, long long n, float **f0, float **f1) {
+    auto lay = [&](DfeCarve c) { *f0 = c.take<float>(n); *f1 = c.take<float>(n); return c.off; };
+    int rc = dfe_grow(ctx, ctx->ingest, lay(DfeCarve()), "frame buffer");
+    if (rc) return rc;
+    lay(DfeCarve(ctx->ingest.p));
+    return DFE_OK;
+}
 int ingest_pair(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, long long n, float scale, float **f0, float **f1) {
-    const size_t bytes = ((size_t)n * sizeof(float) + 255) / 256 * 256;
-    if (2 * bytes > ctx->ingest_bytes) {
-        DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->ingest) DFE_HIP(ctx, hipFree(ctx->ingest));
-        ctx->ingest = nullptr;
-        ctx->ingest_bytes = 0;
-        hipError_t e = hipMalloc(&ctx->ingest, 2 * bytes);
-        if (e != hipSuccess) return dfe_fail(ctx, DFE_E_ALLOC, "frame buffer hipMalloc(%zu): %s", 2 * bytes, hipGetErrorString(e));
-        ctx->ingest_bytes = 2 * bytes;
-    }
-    *f0 = (float *)ctx->ingest;
-    *f1 = (float *)((char *)ctx->ingest + bytes);
+    int rc = ingest_frames(ctx, n, f0, f1);
+    if (rc) return rc;
     DfeStageScope st(ctx, DFE_STAGE_LOAD);
-    int rc = launch_u8(ctx, I0, n, scale, *f0);
+    rc = launch_u8(ctx, I0, n, scale, *f0);
     if (rc) return rc;
     return launch_u8(ctx, I1, n, scale, *f1);
 }
@@ -210,18 +207,12 @@ int dfe_ingest_submit_u8(dfe_ctx *ctx, const uint8_t *hI0, const uint8_t *hI1, i
         }
     }
     if ((size_t)nbytes > ctx->slot_bytes) {                      // (grow-only; sizes settle with the first pair)
-        DFE_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
-        DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < DFE_NSLOT; ++i) {
-            if (ctx->slot[i]) DFE_HIP(ctx, hipFree(ctx->slot[i]));
-            ctx->slot[i] = nullptr;
-            ctx->slot_used[i] = false;
-        }
         ctx->slot_bytes = 0;
-        const size_t fb = ((size_t)nbytes + 255) / 256 * 256;
+        const size_t fb = DfeCarve::up((size_t)nbytes);
         for (int i = 0; i < DFE_NSLOT; ++i) {
-            hipError_t e = hipMalloc(&ctx->slot[i], 2 * fb);
-            if (e != hipSuccess) return dfe_fail(ctx, DFE_E_ALLOC, "ingest slot hipMalloc(%zu): %s", 2 * fb, hipGetErrorString(e));
+            ctx->slot_used[i] = false;
+            int rc = dfe_grow(ctx, ctx->slot[i], 2 * fb, "ingest slot", DFE_GROW_COPY_STREAM);
+            if (rc) return rc;
         }
         ctx->slot_bytes = fb;
     }
@@ -229,8 +220,8 @@ int dfe_ingest_submit_u8(dfe_ctx *ctx, const uint8_t *hI0, const uint8_t *hI1, i
     ctx->slot_next = (s + 1) % DFE_NSLOT;
     // the slot's previous pair must have been consumed before its bytes are overwritten: ordered on the host (see above)
     if (ctx->slot_used[s]) DFE_HIP(ctx, hipEventSynchronize(ctx->consumed[s]));
-    DFE_HIP(ctx, hipMemcpyAsync(ctx->slot[s], hI0, (size_t)nbytes, hipMemcpyHostToDevice, ctx->copy_stream));
-    DFE_HIP(ctx, hipMemcpyAsync((char *)ctx->slot[s] + ctx->slot_bytes, hI1, (size_t)nbytes, hipMemcpyHostToDevice, ctx->copy_stream));
+    DFE_HIP(ctx, hipMemcpyAsync(ctx->slot[s].p, hI0, (size_t)nbytes, hipMemcpyHostToDevice, ctx->copy_stream));
+    DFE_HIP(ctx, hipMemcpyAsync((char *)ctx->slot[s].p + ctx->slot_bytes, hI1, (size_t)nbytes, hipMemcpyHostToDevice, ctx->copy_stream));
     DFE_HIP(ctx, hipEventRecord(ctx->copied[s], ctx->copy_stream));
     ctx->slot_used[s] = true;
     *slot_out = s;
@@ -244,20 +235,12 @@ int dfe_flow_depth_pair_u8_slot(dfe_ctx *ctx, int slot, int C, int H, int W, int
     DFE_REQUIRE(ctx, C > 0 && H > 0 && W > 0 && scale > 0 && (size_t)C * H * W <= ctx->slot_bytes, DFE_E_SHAPE,
                 "dfe_flow_depth_pair_u8_slot: %dx%dx%d bytes (scale %g), the slot holds %zu", C, H, W, (double)scale, ctx->slot_bytes);
     DFE_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->copied[slot], 0));
-    const uint8_t *d0 = (const uint8_t *)ctx->slot[slot], *d1 = d0 + ctx->slot_bytes;
+    const uint8_t *d0 = (const uint8_t *)ctx->slot[slot].p, *d1 = d0 + ctx->slot_bytes;
     // both frames converted by ONE launch (the serial entry's two conversion launches are 12 us of a 245-us step)
     const long long n = (long long)C * H * W;
-    const size_t bytes = ((size_t)n * sizeof(float) + 255) / 256 * 256;
-    if (2 * bytes > ctx->ingest_bytes) {
-        DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->ingest) DFE_HIP(ctx, hipFree(ctx->ingest));
-        ctx->ingest = nullptr;
-        ctx->ingest_bytes = 0;
-        hipError_t e = hipMalloc(&ctx->ingest, 2 * bytes);
-        if (e != hipSuccess) return dfe_fail(ctx, DFE_E_ALLOC, "frame buffer hipMalloc(%zu): %s", 2 * bytes, hipGetErrorString(e));
-        ctx->ingest_bytes = 2 * bytes;
-    }
-    float *f0 = (float *)ctx->ingest, *f1 = (float *)((char *)ctx->ingest + bytes);
+    float *f0 = nullptr, *f1 = nullptr;
+    int rc = ingest_frames(ctx, n, &f0, &f1);
+    if (rc) return rc;
     {
         DfeStageScope st(ctx, DFE_STAGE_LOAD);
         hipLaunchKernelGGL(u8_fetch_pair_kernel, dim3(dfe_grid1d(2 * (n >> 4))), dim3(256), 0, ctx->stream, d0, d1, n, scale, f0, f1);

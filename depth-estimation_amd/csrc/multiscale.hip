@@ -961,10 +961,10 @@ int dfe_pyramid_scale_volume_f32(dfe_ctx *ctx, const float *I0, const float *I1,
     const int pt = hp / 2, pl = wp / 2;
     const int Hp = Hs + hp, Wp = Ws + wp;
     const size_t nd = (size_t)C * Hs * Ws, np = (size_t)C * Hp * Wp;
-    void *scr = nullptr;
-    int rc = dfe_scratch(ctx, (2 * nd + 2 * np) * sizeof(float), &scr);
+    float *d, *p;   // both downsampled frames | both padded frames
+    int rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { d = c.take<float>(2 * nd); p = c.take<float>(2 * np); });
     if (rc) return rc;
-    float *d0 = (float *)scr, *d1 = d0 + nd, *p0 = d1 + nd, *p1 = p0 + np;
+    float *d0 = d, *d1 = d + nd, *p0 = p, *p1 = p + np;
     const float *s0 = I0, *s1 = I1;
     if (r > 1) {
         hipLaunchKernelGGL(downsample_box_kernel, dim3(dfe_grid1d((long long)nd, 256)), dim3(256), 0, ctx->stream, I0, C, H, W, r, d0);
@@ -996,11 +996,9 @@ struct MsArgs {
     bool subpixel;                 // the sub-pixel refinement behind the matcher (raw patches only; flow required)
     const char *entry;             // the C entry's name, for its error messages (NULL: dfe_multiscale_flow_pair_f32)
 };
-// one scale: its sizes and where its buffers start in the arena (bytes)
+// one scale's sizes
 struct MsScale {
     int r, Hs, Ws, Hp, Wp;         // ratio, the scale's frame, its padded frame
-    size_t feat, fbuf;             // learned filters: four feature buffers of fbuf bytes (ping-pong per frame), each the largest layer output
-    size_t frames, cost, prob, best;
 };
 // everything that is decided before the first launch
 struct MsPlan {
@@ -1008,8 +1006,7 @@ struct MsPlan {
     float *fx;                     // the flow's second plane, or NULL
     int N, hk, wk, hp, wp, pt, pl, middle;
     MsScale sc[DFE_MAX_RATIOS];
-    size_t total;                  // arena bytes
-    size_t idx_tmp;                // sub-pixel entry called without idx: the class map the refinement reads, in the arena
+    int maxplanes;                 // learned filters: planes of the widest layer (>= C)
     long long frame_max;           // the largest padded frame, C * Hp * Wp elements
     CascadeGeom g;                 // (in / out_scale are the cell cascade's to fill)
     MultiGeom mg;
@@ -1024,13 +1021,14 @@ struct MsPlan {
     int nq_hint, fK;               // cv_frames_dispatch_multi's hint; planes of the finest scale's features
     size_t lds;                    // cascade_argmax_kernel's dynamic LDS
 };
-// the arena as pointers: the one place that adds the plan's offsets to the arena's base
+// the arena as pointers (ms_bufs)
 struct MsBufs {
     float *p0[DFE_MAX_RATIOS], *p1[DFE_MAX_RATIOS];   // padded frames
     float *cost[DFE_MAX_RATIOS];                      // volumes
     float *prob[DFE_MAX_RATIOS];                      // soft-min probabilities (lane <-> cell) / cascaded windows (lane <-> pixel)
     float2 *best[DFE_MAX_RATIOS];                     // running best (lane <-> pixel)
-    float *feat[DFE_MAX_RATIOS][4];
+    float *feat[DFE_MAX_RATIOS][4];                   // learned filters: four feature buffers (ping-pong per frame), each the largest layer output
+    int64_t *idx_tmp;                                 // sub-pixel entry called without idx: the class map the refinement reads
 };
 // what the launchers report back and a later stage depends on
 struct MsRun {
@@ -1052,7 +1050,7 @@ static int ms_filter_field(dfe_ctx *ctx, const MsArgs &a, int *hk, int *wk, int 
     return DFE_OK;
 }
 
-// Every check, the geometry, the arena layout and every path decision of the one-call matcher.  Launches and allocates nothing.
+// Every check, the geometry and every path decision of the one-call matcher.  Launches and allocates nothing.
 static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
     MsPlan &P = *plan;
     const int C = a.C, H = a.H, W = a.W, k = a.k, maxh = a.maxh, maxw = a.maxw, nratios = a.nratios;
@@ -1076,24 +1074,14 @@ static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
     }
     const int hp = P.hp = maxh - 1 + P.hk - 1, wp = P.wp = maxw - 1 + P.wk - 1;   // hPatch2-1 (opticalflow_model_multiscale.lua:136-141)
     P.pt = hp / 2; P.pl = wp / 2;
-    P.total = 0;
+    P.maxplanes = maxplanes;
     for (int s = 0; s < nratios; ++s) {
         MsScale &sc = P.sc[s];
         const int r = sc.r = ratios[s];
         DFE_REQUIRE(ctx, H % r == 0 && W % r == 0, DFE_E_SHAPE,
                     "%s: frame %dx%d is not a multiple of ratio %d (opticalflow_model_multiscale.lua:238-243)", entry, H, W, r);
         sc.Hs = H / r; sc.Ws = W / r; sc.Hp = sc.Hs + hp; sc.Wp = sc.Ws + wp;
-        const size_t np = (size_t)C * sc.Hp * sc.Wp, nv = (size_t)sc.Hs * sc.Ws * N;
-        // learned filters: four feature buffers per scale (ping-pong per frame), each the largest layer output
-        sc.fbuf = a.filt ? ((size_t)maxplanes * sc.Hp * sc.Wp * sizeof(float) + 255) / 256 * 256 : 0;
-        sc.feat = P.total; P.total += 4 * sc.fbuf;
-        sc.frames = P.total; P.total += (2 * np * sizeof(float) + 255) / 256 * 256;
-        sc.cost = P.total; P.total += (nv * sizeof(float) + 255) / 256 * 256;
-        sc.prob = P.total; P.total += (nv * sizeof(float) + 255) / 256 * 256;
-        sc.best = P.total; P.total += ((size_t)sc.Hs * sc.Ws * sizeof(float2) + 255) / 256 * 256;
     }
-    P.idx_tmp = P.total;
-    if (a.subpixel && !a.idx) P.total += ((size_t)H * W * sizeof(int64_t) + 255) / 256 * 256;
     P.mg.maxh = maxh; P.mg.maxw = maxw; P.mg.nratios = nratios;
     P.frame_max = 0;
     for (int s = 0; s < nratios; ++s) {
@@ -1158,18 +1146,23 @@ static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
     return DFE_OK;
 }
 
-static void ms_bufs(const MsPlan &P, void *scr, MsBufs *bufs) {
-    MsBufs &B = *bufs;
-    char *base = (char *)scr;
-    for (int s = 0; s < P.a.nratios; ++s) {
+// The arena's layout, the one place that places the plan's buffers: sizes on a carver without a base, pointers on the arena.
+// frames_only: the padded scale frames alone (the stand-alone refinement needs no volumes)
+static MsBufs ms_bufs(const MsPlan &P, DfeCarve &c, bool frames_only = false) {
+    MsBufs B{};
+    const MsArgs &a = P.a;
+    for (int s = 0; s < a.nratios; ++s) {
         const MsScale &sc = P.sc[s];
-        B.p0[s] = (float *)(base + sc.frames);
-        B.p1[s] = B.p0[s] + (size_t)P.a.C * sc.Hp * sc.Wp;
-        B.cost[s] = (float *)(base + sc.cost);
-        B.prob[s] = (float *)(base + sc.prob);
-        B.best[s] = (float2 *)(base + sc.best);
-        for (int j = 0; j < 4; ++j) B.feat[s][j] = (float *)(base + sc.feat + j * sc.fbuf);
+        const size_t np = (size_t)a.C * sc.Hp * sc.Wp, nv = frames_only ? 0 : (size_t)sc.Hs * sc.Ws * P.N;
+        for (float *&f : B.feat[s]) f = c.take<float>(a.filt && !frames_only ? (size_t)P.maxplanes * sc.Hp * sc.Wp : 0);
+        B.p0[s] = c.take<float>(2 * np);
+        B.p1[s] = B.p0[s] ? B.p0[s] + np : nullptr;
+        B.cost[s] = c.take<float>(nv);
+        B.prob[s] = c.take<float>(nv);
+        B.best[s] = c.take<float2>(frames_only ? 0 : (size_t)sc.Hs * sc.Ws);
     }
+    B.idx_tmp = c.take<int64_t>(a.subpixel && !a.idx ? (size_t)a.H * a.W : 0);
+    return B;
 }
 
 // stage "filter" of the raw-patch pyramid: every scale's padded frames from the float or uint8 frames in one launch
@@ -1494,8 +1487,10 @@ static int multiscale_flow_pair(dfe_ctx *ctx, const float *I0, const float *I1, 
     if (rc) return rc;
     // the per-scale cost volumes use the same arena for their own temporaries only through cv_frames_dispatch, which
     // needs none; one allocation up front keeps every stage's buffers alive until the cascade has read them
+    DfeCarve sizes;
+    ms_bufs(P, sizes);
     void *scr = nullptr;
-    rc = dfe_scratch(ctx, P.total, &scr, filt != nullptr);   // (learned filters: the convolutions' arena, see dfe_scratch)
+    rc = dfe_scratch(ctx, sizes.off, &scr, filt != nullptr);   // (learned filters: the convolutions' arena, see dfe_scratch)
     if (rc) return rc;
     // the same call again (same buffers, shapes and arena): replay its launches as a graph
     struct { const void *I0, *I1, *flow, *idx, *scr; int C, H, W, k, maxh, maxw, nratios, ratios[DFE_MAX_RATIOS]; float f16, u8; int subpixel; } gkey;
@@ -1509,9 +1504,9 @@ static int multiscale_flow_pair(dfe_ctx *ctx, const float *I0, const float *I1, 
         ctx->last_kernel = "multiscale graph";
         return DFE_OK;
     }
-    MsBufs B;
-    ms_bufs(P, scr, &B);
-    if (subpixel && !idx) P.a.idx = (int64_t *)((char *)scr + P.idx_tmp);   // (the refinement reads the class map)
+    DfeCarve arena(scr);
+    const MsBufs B = ms_bufs(P, arena);
+    if (subpixel && !idx) P.a.idx = B.idx_tmp;   // (the refinement reads the class map)
     rc = ms_run(ctx, P, B);
     if (!rc && subpixel) rc = ms_subpixel(ctx, P, B, P.a.idx);
     return gmode == 1 ? dfe_graph_finish(ctx, ctx->ms_graph, rc) : rc;
@@ -1538,19 +1533,9 @@ int dfe_multiscale_refine_subpixel_f32(dfe_ctx *ctx, const float *I0, const floa
     MsPlan P;
     int rc = ms_plan(ctx, a, &P);
     if (rc) return rc;
-    size_t off[DFE_MAX_RATIOS], total = 0;
-    for (int s = 0; s < nratios; ++s) {
-        off[s] = total;
-        total += (2 * (size_t)C * P.sc[s].Hp * P.sc[s].Wp * sizeof(float) + 255) / 256 * 256;
-    }
-    void *scr = nullptr;
-    rc = dfe_scratch(ctx, total, &scr);
+    MsBufs B;
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { B = ms_bufs(P, c, true); });
     if (rc) return rc;
-    MsBufs B{};
-    for (int s = 0; s < nratios; ++s) {
-        B.p0[s] = (float *)((char *)scr + off[s]);
-        B.p1[s] = B.p0[s] + (size_t)C * P.sc[s].Hp * P.sc[s].Wp;
-    }
     rc = ms_prep_raw(ctx, P, B);
     if (rc) return rc;
     return ms_subpixel(ctx, P, B, idx);

@@ -153,11 +153,10 @@ int dfe_postprocess_image_f32(dfe_ctx *ctx, const float *flow, const float *mask
         DFE_LAUNCH_CHECK(ctx);
         return DFE_OK;
     }
-    void *scr = nullptr;
-    int rc = dfe_scratch(ctx, 2 * HW * sizeof(float) + 64, &scr);
+    float *R;   // the rounded flow
+    int *mm;    // its minimum and maximum
+    int rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { R = c.take<float>(2 * HW); mm = c.take<int>(2); });
     if (rc) return rc;
-    float *R = (float *)scr;
-    int *mm = (int *)((char *)scr + 2 * HW * sizeof(float));
     const int init[2] = {0x7fffffff, (int)0x80000000};
     DFE_HIP(ctx, hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(round_minmax_kernel, dim3(dfe_grid1d(2 * HW)), dim3(256), 0, ctx->stream, flow, 2 * HW, R, mm);

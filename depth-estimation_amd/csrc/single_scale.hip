@@ -119,23 +119,22 @@ static int ss_flow_pair(dfe_ctx *ctx, const char *fn, bool mean, const float *I0
     // arena: cropped frame 0 | two ping-pong feature buffers per branch | (fallback) contiguous in1 | volume | probabilities | index | scores
     // ('mean' fallback: imaxs | scores | x | y | row marginals in place of index and scores)
     const int Hc = H1 + hk - 1, Wc = W1 + wk - 1;                   // the part of frame 0 the narrowed features come from
-    auto al = [](size_t f) { return (f + 63) / 64 * 64; };
     const size_t f_c0 = nlayers ? (size_t)C * Hc * Wc : 0;
     const size_t f_fa = nlayers ? (size_t)maxplanes * Hc * Wc : 0, f_fb = nlayers ? (size_t)maxplanes * H * W : 0;
     const size_t f_in1 = (!lean && !nlayers) ? (size_t)K * P1 : 0;
     const size_t f_vol = lean ? 0 : (size_t)P1 * N;
-    const size_t f_idx = (lean || index || mean) ? 0 : (size_t)P1 * 2, f_sc = (lean || scores || !use_threshold || mean) ? 0 : (size_t)P1;
+    const size_t n_idx = (lean || index || mean) ? 0 : (size_t)P1, f_sc = (lean || scores || !use_threshold || mean) ? 0 : (size_t)P1;
     const size_t f_mean = (lean || !mean) ? 0 : (size_t)P1 * (5 + maxh);
-    void *scr = nullptr;
-    rc = dfe_scratch(ctx, (al(f_c0) + 2 * al(f_fa) + 2 * al(f_fb) + al(f_in1) + 2 * al(f_vol) + al(f_idx) + al(f_sc) + al(f_mean)) * sizeof(float), &scr, nlayers > 0);
+    float *c0, *fa[2], *fb[2], *in1c, *vol, *prob, *sc_s, *mean_s;
+    long long *idx_s;
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
+        c0 = c.take<float>(f_c0);
+        for (float *&f : fa) f = c.take<float>(f_fa);
+        for (float *&f : fb) f = c.take<float>(f_fb);
+        in1c = c.take<float>(f_in1); vol = c.take<float>(f_vol); prob = c.take<float>(f_vol);
+        idx_s = c.take<long long>(n_idx); sc_s = c.take<float>(f_sc); mean_s = c.take<float>(f_mean);
+    }, nlayers > 0);
     if (rc) return rc;
-    float *c0 = (float *)scr;
-    float *fa[2] = {c0 + al(f_c0), c0 + al(f_c0) + al(f_fa)};
-    float *fb[2] = {fa[1] + al(f_fa), fa[1] + al(f_fa) + al(f_fb)};
-    float *in1c = fb[1] + al(f_fb), *vol = in1c + al(f_in1), *prob = vol + al(f_vol);
-    long long *idx_s = (long long *)(prob + al(f_vol));
-    float *sc_s = (float *)idx_s + al(f_idx);
-    float *mean_s = sc_s + al(f_sc);
     const float *in1 = nullptr, *in2 = nullptr;
     int pitch1 = W1;
     long long plane1 = P1;
@@ -272,12 +271,12 @@ extern "C" int dfe_spatial_matching_strided_f32(dfe_ctx *ctx, const float *in1, 
     bool done = false;
     int rc = dfe_feat_matching_flat_strided(ctx, in1, in1_pitch, in1_plane, in2, K, H1, W1, maxh, maxw, out, &done);
     if (rc || done) return rc;
-    void *scr = nullptr;
-    rc = dfe_scratch(ctx, (size_t)K * H1 * W1 * sizeof(float), &scr);
+    float *scr = nullptr;
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { scr = c.take<float>((size_t)K * H1 * W1); });
     if (rc) return rc;
     // (a view with rows pitch apart inside planes plane apart: the crop kernel's (plane, W) pair)
     hipLaunchKernelGGL(ss_crop_kernel, dim3(dfe_grid1d((long long)K * H1 * W1, 256, 16384)), dim3(256), 0, ctx->stream, in1, (long long)in1_plane, in1_pitch, 0, 0, H1, W1,
-                       (long long)K * H1 * W1, (float *)scr);
+                       (long long)K * H1 * W1, scr);
     DFE_LAUNCH_CHECK(ctx);
-    return dfe_spatial_matching_dispatch(ctx, (const float *)scr, in2, K, H1, W1, maxh, maxw, out);
+    return dfe_spatial_matching_dispatch(ctx, scr, in2, K, H1, W1, maxh, maxw, out);
 }

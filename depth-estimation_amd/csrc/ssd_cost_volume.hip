@@ -2090,18 +2090,17 @@ static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, i
     const int Ho = H - K + 1 - hWin + 1, Wo = W - K + 1 - wWin + 1;
     const long long P = (long long)Ho * Wo;
     if (Wo < 8 || P >= (1ll << 31) || (pd && (long long)pd->H * pd->W >= (1ll << 31))) return DFE_OK;   // (the finalize's 32-bit pixel arithmetic)
-    const size_t rec_bytes = ((size_t)dfe_cdiv(Wo, 8) * Ho * DFE_REC * sizeof(float) + 255) / 256 * 256;   // [tile column][output row][DFE_REC]
-    const size_t fb_bytes = (size_t)dfe_cdiv(Wo, 8) * Ho * 8 * DFE_FB * sizeof(float);                     // [tile column][output row][8][DFE_FB]
-    void *scr = nullptr;
-    int rc = dfe_scratch(ctx, rec_bytes + fb_bytes, &scr);
-    if (rc) return rc;
+    const size_t nrec = (size_t)dfe_cdiv(Wo, 8) * Ho;   // tile-row records
     CvFuseArgs fa{};
-    fa.rec = (float *)scr;
+    CvNovolArgs nv;
+    int rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
+        fa.rec = c.take<float>(nrec * DFE_REC);       // [tile column][output row][DFE_REC]
+        nv.fb = c.take<float>(nrec * 8 * DFE_FB);     // [tile column][output row][8][DFE_FB]
+    });
+    if (rc) return rc;
     fa.rec_rows = Ho;
     fa.row_off = 0;
     fa.Ptot = P;
-    CvNovolArgs nv;
-    nv.fb = (float *)((char *)scr + rec_bytes);
     nv.thr = float_at_or_below(thr);
     nv.M = thr < 0.2 ? 8 : 4;   // extract_output.cpp:83-85
     bool handled = false;
@@ -2116,7 +2115,7 @@ static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, i
                            pad_t, pad_l, scores_padded, pd, fa.rec, Ho, nv.fb);
     if (pd && pd_done) *pd_done = true;
 #if DFE_TL
-    if (const char *path = getenv("DFE_TIMELINE_OUT"); path && !rc && fb_bytes >= 2 * DFE_TL_WORDS * sizeof(unsigned)) {
+    if (const char *path = getenv("DFE_TIMELINE_OUT"); path && !rc && nrec * 8 * DFE_FB * sizeof(float) >= 2 * DFE_TL_WORDS * sizeof(unsigned)) {
         static unsigned host[2 * DFE_TL_WORDS];
         if (hipStreamSynchronize(ctx->stream) == hipSuccess && hipMemcpy(host, nv.fb, sizeof(host), hipMemcpyDeviceToHost) == hipSuccess)
             if (FILE *f = fopen(path, "wb")) {
@@ -2151,22 +2150,18 @@ static int flow_pipeline(dfe_ctx *ctx, const float *I0, const float *I1, int C, 
     const long long P = (long long)Ho * Wo;
     const int elem = f16_scale != 0.f ? 2 : 4;
     const int band = band_rows(ctx, Ho, Wo, D, elem);
-    const size_t vol_bytes = ((size_t)band * Wo * D * elem + 255) / 256 * 256;
-    const size_t part_bytes = ((size_t)nch * P * sizeof(float2) + 255) / 256 * 256;
-    const size_t cen_bytes = ((size_t)P * sizeof(float) + 255) / 256 * 256;
-    const size_t lead_bytes = ((size_t)P * DFE_LEAD * sizeof(float) + 255) / 256 * 256;
     // per-pixel records of the role-split row-image kernels (one whole 128-B line per pixel instead of entries in the three planes)
     const bool want_rec = kh == kw && kh == 7 && rowimg_writes_records(C, hWin, wWin);
-    const size_t rec_bytes = want_rec ? (size_t)dfe_cdiv(Wo, 8) * Ho * DFE_REC * sizeof(float) : 0;   // [tile column][output row][DFE_REC]
-    void *scr = nullptr;
-    int rc = dfe_scratch(ctx, vol_bytes + part_bytes + cen_bytes + lead_bytes + rec_bytes, &scr);
-    if (rc) return rc;
-    float *vol = (float *)scr;
+    float *vol;
     CvFuseArgs fa{};
-    fa.part = (float2 *)((char *)scr + vol_bytes);
-    fa.centre = (float *)((char *)scr + vol_bytes + part_bytes);
-    fa.lead = (float *)((char *)scr + vol_bytes + part_bytes + cen_bytes);
-    fa.rec = want_rec ? (float *)((char *)scr + vol_bytes + part_bytes + cen_bytes + lead_bytes) : nullptr;
+    int rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
+        vol = (float *)c.take<char>((size_t)band * Wo * D * elem);
+        fa.part = c.take<float2>((size_t)nch * P);
+        fa.centre = c.take<float>((size_t)P);
+        fa.lead = c.take<float>((size_t)P * DFE_LEAD);
+        fa.rec = c.take<float>(want_rec ? (size_t)dfe_cdiv(Wo, 8) * Ho * DFE_REC : 0);   // [tile column][output row][DFE_REC]
+    });
+    if (rc) return rc;
     fa.rec_rows = Ho;
     fa.Ptot = P;
     {

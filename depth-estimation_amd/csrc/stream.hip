@@ -53,8 +53,6 @@ int stream_shapes(dfe_ctx *ctx, const char *fn, const dfe_stream_params *p, Stre
     return DFE_OK;
 }
 
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 
 struct dfe_stream {
@@ -66,7 +64,7 @@ struct dfe_stream {
     double Ksmall[9];
     bool primed = false;
     int cur = 0;                        // the slot this push writes; 1 - cur holds the previous frame
-    void *block = nullptr;
+    DfeBuf block;                       // the stream's own device memory (dfe_grow once, freed by dfe_stream_destroy)
     float *full[2], *scaled[2], *feat[2];   // (nlayers == 0: feat[i] IS scaled[i])
     float *raw = nullptr;               // has_dist: the converted uint8 frame in front of the undistortion
     float *pp[2];                       // the filter stack's intermediate layers
@@ -248,31 +246,26 @@ int dfe_stream_create(dfe_ctx *ctx, const dfe_stream_params *p, dfe_stream **out
     // K_small = diag(wImg / Wsrc, hImg / Hsrc, 1) K: the reference's Khalf (depth_estimation_api.lua:50-51) at one half
     const double sx = (double)p->wImg / (double)p->Wsrc, sy = (double)p->hImg / (double)p->Hsrc;
     for (int j = 0; j < 3; ++j) { s->Ksmall[j] = sx * p->K[j]; s->Ksmall[3 + j] = sy * p->K[3 + j]; s->Ksmall[6 + j] = p->K[6 + j]; }
-    const size_t nimg = (size_t)p->hImg * p->wImg, b_full = up256((size_t)p->C * p->Hsrc * p->Wsrc * 4), b_scaled = up256((size_t)p->C * nimg * 4),
-                 b_feat = p->nlayers ? up256((size_t)sh.K * sh.Hf * sh.Wf * 4) : 0, b_pp = p->nlayers > 1 ? up256((size_t)sh.maxplanes * nimg * 4) : 0,
-                 b_raw = p->has_dist ? b_full : 0, b_wimg = p->rectify == 1 ? b_scaled : 0, b_warp = (p->rectify == 0 || p->nlayers) ? up256((size_t)sh.K * sh.Hf * sh.Wf * 4) : 0,
-                 b_plane = up256(nimg * 4);
-    const size_t total = 2 * b_full + 2 * b_scaled + 2 * b_feat + 2 * b_pp + b_raw + b_wimg + b_warp + 6 * b_plane;
-    hipError_t e = hipMalloc(&s->block, total);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        delete s;
-        return dfe_fail(ctx, DFE_E_ALLOC, "dfe_stream_create: hipMalloc(%zu): %s", total, hipGetErrorString(e));
-    }
-    char *q = (char *)s->block;
-    auto take = [&q](size_t b) { float *r = b ? (float *)q : nullptr; q += b; return r; };
-    for (int i = 0; i < 2; ++i) s->full[i] = take(b_full);
-    for (int i = 0; i < 2; ++i) s->scaled[i] = take(b_scaled);
-    for (int i = 0; i < 2; ++i) s->feat[i] = p->nlayers ? take(b_feat) : s->scaled[i];
-    for (int i = 0; i < 2; ++i) s->pp[i] = take(b_pp);
-    s->raw = take(b_raw);
-    s->warped_img = take(b_wimg);
-    s->warped = take(b_warp);
-    s->rmask = take(b_plane);            // (at most hImg x wImg)
-    s->conf = take(b_plane);
-    s->flow_i = take(2 * b_plane);
-    s->mask_i = take(b_plane);
-    s->spare = take(b_plane);
+    const size_t nimg = (size_t)p->hImg * p->wImg, n_full = (size_t)p->C * p->Hsrc * p->Wsrc, n_feat = (size_t)sh.K * sh.Hf * sh.Wf;
+    auto lay = [&](DfeCarve c) {
+        for (float *&f : s->full) f = c.take<float>(n_full);
+        for (float *&f : s->scaled) f = c.take<float>(p->C * nimg);
+        for (int i = 0; i < 2; ++i) s->feat[i] = p->nlayers ? c.take<float>(n_feat) : s->scaled[i];
+        for (float *&f : s->pp) f = c.take<float>(p->nlayers > 1 ? sh.maxplanes * nimg : 0);
+        s->raw = c.take<float>(p->has_dist ? n_full : 0);
+        s->warped_img = c.take<float>(p->rectify == 1 ? p->C * nimg : 0);
+        s->warped = c.take<float>((p->rectify == 0 || p->nlayers) ? n_feat : 0);
+        s->rmask = c.take<float>(nimg);            // (at most hImg x wImg)
+        s->conf = c.take<float>(nimg);
+        s->flow_i = c.take<float>(nimg);           // [2][hImg][wImg], contiguous, in the space of two rounded planes: the second
+        c.take<float>(nimg);                       // take keeps what follows where the stream's first layout put it
+        s->mask_i = c.take<float>(nimg);
+        s->spare = c.take<float>(nimg);
+        return c.off;
+    };
+    rc = dfe_grow(ctx, s->block, lay(DfeCarve()), "dfe_stream_create");
+    if (rc) { delete s; return rc; }
+    lay(DfeCarve(s->block.p));
     *out = s;
     return DFE_OK;
 }
@@ -304,7 +297,7 @@ void dfe_stream_destroy(dfe_stream *s) {
     {
         DfeDeviceGuard guard(s->ctx);
         (void)hipStreamSynchronize(s->ctx->stream);   // nothing of this ctx may still be writing there
-        if (s->block) (void)hipFree(s->block);
+        if (s->block.p) (void)hipFree(s->block.p);
     }
     delete s;
 }

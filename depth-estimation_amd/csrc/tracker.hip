@@ -161,11 +161,18 @@ __global__ __launch_bounds__(1024) void sel_top_kernel(const unsigned *__restric
     }
 }
 
-size_t sel_ws_bytes(int H, int W) { return 256 + (size_t)H * W * 8; }
+// the selection's workspace: the list's head and one key per pixel
+struct SelWs { unsigned *head; unsigned long long *keys; };
+SelWs sel_layout(DfeCarve &c, int H, int W) {
+    SelWs ws;
+    ws.head = c.take<unsigned>(1);
+    ws.keys = c.take<unsigned long long>((size_t)H * W);
+    return ws;
+}
 
-int select_run(dfe_ctx *ctx, const float *resp, int H, int W, float quality, float min_dist, int max_points, float *pts, float *resp_out, int *n_out, void *ws) {
-    unsigned *head = (unsigned *)ws;
-    unsigned long long *keys = (unsigned long long *)((char *)ws + 256);
+int select_run(dfe_ctx *ctx, const float *resp, int H, int W, float quality, float min_dist, int max_points, float *pts, float *resp_out, int *n_out, const SelWs &ws) {
+    unsigned *head = ws.head;
+    unsigned long long *keys = ws.keys;
     // floor(min_dist^2) as the integer the kernel compares with, capped at the frame's diagonal (a larger disc holds the same pixels)
     const double diag2 = (double)(H - 1) * (H - 1) + (double)(W - 1) * (W - 1);
     const double md2 = floor((double)min_dist * (double)min_dist);
@@ -358,16 +365,18 @@ __global__ __launch_bounds__(256) void lk_track_kernel(const LkArgs A) {
     }
 }
 
-// floats of the pyramid levels 1 .. levels - 1 of ONE frame
-size_t lk_pyr_floats(int H, int W, int levels) {
-    size_t n = 0;
-    for (int L = 1; L < levels; ++L) {
-        H = (H + 1) / 2; W = (W + 1) / 2;
-        n += ((size_t)H * W + 63) / 64 * 64;
-    }
-    return n;
+// the tracker's workspace: the pyramid levels 1 .. levels - 1 of both frames
+struct LkWs { float *lev[2][LK_MAX_LEVELS]; };
+LkWs lk_layout(DfeCarve &c, int H, int W, int levels) {
+    LkWs ws{};
+    for (int k = 0; k < 2; ++k)
+        for (int L = 1, h = H, w = W; L < levels; ++L) {
+            h = (h + 1) / 2; w = (w + 1) / 2;
+            ws.lev[k][L] = c.take<float>((size_t)h * w);
+        }
+    c.take<char>(256);   // (slack behind the last level, as the first layout had it)
+    return ws;
 }
-size_t lk_ws_bytes(int H, int W, int levels) { return 2 * lk_pyr_floats(H, W, levels) * 4 + 256; }
 
 int lk_check_params(dfe_ctx *ctx, const dfe_tracker_params *p, const char *who) {
     DFE_REQUIRE(ctx, p, DFE_E_ARG, "%s: params is NULL", who);
@@ -379,20 +388,18 @@ int lk_check_params(dfe_ctx *ctx, const dfe_tracker_params *p, const char *who) 
 
 // wts (or NULL): status as float weights, what dfe_ego_motion_from_points_f32 takes
 int track_run(dfe_ctx *ctx, const float *Y0, const float *Y1, int H, int W, const float *pts0, int N, const dfe_tracker_params *p, float *pts1, int *status,
-              float *err, float *wts, void *ws) {
+              float *err, float *wts, const LkWs &ws) {
     LkArgs A;
     memset(&A, 0, sizeof(A));
-    float *f = (float *)ws;
     const float *src[2] = {Y0, Y1};
     for (int k = 0; k < 2; ++k) {
         int h = H, w = W;
         const float *prev = src[k];
         for (int L = 0; L < p->levels; ++L) {
             if (L > 0) {
-                pyr_down_run(ctx, prev, h, w, f);
-                prev = f;
+                pyr_down_run(ctx, prev, h, w, ws.lev[k][L]);
+                prev = ws.lev[k][L];
                 h = (h + 1) / 2; w = (w + 1) / 2;
-                f += ((size_t)h * w + 63) / 64 * 64;
             }
             (k == 0 ? A.y0 : A.y1)[L] = prev;
             A.H[L] = h; A.W[L] = w;
@@ -416,8 +423,6 @@ void corner_response_run(dfe_ctx *ctx, const float *Y, int H, int W, float *resp
     hipLaunchKernelGGL(corner_response_kernel, dim3(dfe_cdiv(W, CR_TW), dfe_cdiv(H, CR_TH)), dim3(CR_TW, CR_TH), 0, ctx->stream, Y, H, W, resp);
 }
 
-inline size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 
 extern "C" {
@@ -437,8 +442,8 @@ int dfe_select_corners_f32(dfe_ctx *ctx, const float *resp, int H, int W, float 
     DFE_REQUIRE(ctx, H > 0 && W > 0 && H <= 32768 && W <= 32768 && (long long)H * W < (1ll << 31), DFE_E_SHAPE, "dfe_select_corners_f32: %dx%d", H, W);
     int rc = check_select_args(ctx, quality, min_dist, max_points, "dfe_select_corners_f32");
     if (rc) return rc;
-    void *ws = nullptr;
-    rc = dfe_scratch(ctx, sel_ws_bytes(H, W), &ws);
+    SelWs ws;
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { ws = sel_layout(c, H, W); });
     if (rc) return rc;
     return select_run(ctx, resp, H, W, quality, min_dist, max_points, pts, resp_out, n_out, ws);
 }
@@ -461,8 +466,8 @@ int dfe_track_points_lk_f32(dfe_ctx *ctx, const float *Y0, const float *Y1, int 
     if (N == 0) return DFE_OK;
     DFE_REQUIRE(ctx, Y0 && Y1 && pts0 && pts1 && status, DFE_E_ARG, "dfe_track_points_lk_f32: NULL argument");
     DFE_REQUIRE(ctx, H > 0 && W > 0 && H < (1 << 24) && W < (1 << 24) && dfe_cdiv((H + 1) / 2, 4) <= 65535, DFE_E_SHAPE, "dfe_track_points_lk_f32: %dx%d", H, W);
-    void *ws = nullptr;
-    rc = dfe_scratch(ctx, lk_ws_bytes(H, W, params->levels), &ws);
+    LkWs ws;
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { ws = lk_layout(c, H, W, params->levels); });
     if (rc) return rc;
     return track_run(ctx, Y0, Y1, H, W, pts0, N, params, pts1, status, err, nullptr, ws);
 }
@@ -481,30 +486,34 @@ int dfe_ego_motion_from_images_f32(dfe_ctx *ctx, const float *im0, const float *
     DFE_REQUIRE(ctx, iterations >= 1 && iterations <= 65536 && ransac_max_dist > 0, DFE_E_ARG, "dfe_ego_motion_from_images_f32: iterations=%d (1..65536) ransac_max_dist=%g",
                 iterations, ransac_max_dist);
     const int mp = params->max_points;
-    const size_t plane = up256((size_t)H * W * 4);
     // arena: luminance of both frames (C = 3), the response, the selection's list, the pyramids.  The point lists live in the side
     // buffer: the pose step lays its own data out from the arena's start.
-    const size_t off_resp = C == 3 ? 2 * plane : 0, off_sel = off_resp + plane, off_lk = off_sel + up256(sel_ws_bytes(H, W));
-    void *scr = nullptr, *aux = nullptr;
-    rc = dfe_scratch(ctx, off_lk + lk_ws_bytes(H, W, params->levels), &scr);
+    const size_t HW = (size_t)H * W;
+    float *y0, *y1, *resp;
+    SelWs sel;
+    LkWs lk;
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
+        y0 = c.take<float>(C == 3 ? HW : 0); y1 = c.take<float>(C == 3 ? HW : 0); resp = c.take<float>(HW);
+        sel = sel_layout(c, H, W);
+        lk = lk_layout(c, H, W, params->levels);
+    });
     if (rc) return rc;
+    void *aux = nullptr;
     rc = dfe_aux_scratch(ctx, (size_t)mp * 24, &aux);
     if (rc) return rc;
     float *p0 = (float *)aux, *p1 = p0 + 2 * (size_t)mp, *wts = p1 + 2 * (size_t)mp;
     int *status = (int *)(wts + mp);
     const float *Y0 = im0, *Y1 = im1;
     if (C == 3) {
-        float *y0 = (float *)scr, *y1 = (float *)((char *)scr + plane);
         rc = dfe_rgb2y_f32(ctx, im0, H, W, y0);
         if (rc) return rc;
         rc = dfe_rgb2y_f32(ctx, im1, H, W, y1);
         if (rc) return rc;
         Y0 = y0; Y1 = y1;
     }
-    float *resp = (float *)((char *)scr + off_resp);
     corner_response_run(ctx, Y0, H, W, resp);
     int n = 0;
-    rc = select_run(ctx, resp, H, W, params->quality, params->min_dist, mp, p0, nullptr, &n, (char *)scr + off_sel);
+    rc = select_run(ctx, resp, H, W, params->quality, params->min_dist, mp, p0, nullptr, &n, sel);
     if (rc) return rc;
     // dfe_stream_push_* (stream.hip) tells the two "fewer than 8" refusals below from an argument error by the counts: *n_corners and
     // *n_found are written BEFORE the refusal they explain, every argument error returns before *n_corners is written, and nothing
@@ -512,7 +521,7 @@ int dfe_ego_motion_from_images_f32(dfe_ctx *ctx, const float *im0, const float *
     if (n_corners) *n_corners = n;
     if (n_found) *n_found = 0;
     DFE_REQUIRE(ctx, n >= 8, DFE_E_ARG, "dfe_ego_motion_from_images_f32: only %d corners", n);
-    rc = track_run(ctx, Y0, Y1, H, W, p0, n, params, p1, status, nullptr, wts, (char *)scr + off_lk);
+    rc = track_run(ctx, Y0, Y1, H, W, p0, n, params, p1, status, nullptr, wts, lk);
     if (rc) return rc;
     std::vector<int> hs(n);
     DFE_HIP(ctx, hipMemcpyAsync(hs.data(), status, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
