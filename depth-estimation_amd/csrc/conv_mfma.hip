@@ -15,6 +15,7 @@
 //   MFMA.  Zero-padded weights multiply finite tile values (the tile is zero-filled past the frame), so padding adds
 //   exact zeros to the chain.
 #include "dfe_internal.h"
+#include "dfe_wave.h"
 
 #ifndef DFE_CM_STAMPS
 #define DFE_CM_STAMPS 0

@@ -7,6 +7,7 @@
 // TX x TY pixels and deals its TY * ceil(D/64) (row, chunk) tasks to 8 waves, which keep the 8 accumulators of each of their
 // tasks in registers across the slabs.  Stores are the tiled kernel's 256-B pieces (same store-pattern bound).
 #include "dfe_internal.h"
+#include "cv_fine_epilogue.h"
 
 namespace {
 
@@ -199,7 +200,7 @@ struct FmBatch {
 };
 constexpr int F64_TY = 16;
 // MODE 0: the volume is stored.  MODE 1 / 2 (8 x 8 windows, one pair): the task rows -- 8 pixels x 64 cells, lane <-> cell, exactly the
-// tiled SSD kernel's -- go through fine_epilogue (dfe_internal.h) instead: the finest pyramid scale (1) or a scale between (2) without
+// tiled SSD kernel's -- go through fine_epilogue (cv_fine_epilogue.h) instead: the finest pyramid scale (1) or a scale between (2) without
 // its volume, as in ssd_cv_tiled_fine_kernel.  F16: the costs are rounded as the stored fp16 volume would hold them.
 template <int MODE, bool F16>
 __device__ __forceinline__ void feat_matching_win64_body(const FmBatch &fb, int K, int maxh, int maxw, int pitch, float f16_scale, int nt, const CvFineArgs *fine) {

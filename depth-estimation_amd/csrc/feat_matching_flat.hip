@@ -25,6 +25,8 @@
 //     EXTRA task, row 16 for the 16 pixels of lanes 4w .. 4w+3 (lane <-> (pixel, 4-cell group): 5 accumulators, 15 vector
 //     instructions a plane next to the main task's 204) -- the seventeenth row costs 7 % instead of a second round.
 #include "dfe_internal.h"
+#include "cv_records.h"   // dfe_sort8
+#include "dfe_wave.h"
 #include <algorithm>
 #include <type_traits>
 

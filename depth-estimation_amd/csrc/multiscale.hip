@@ -7,6 +7,8 @@
 // H x W x 64 temporaries; here volumes stay at native scale and one kernel per finest pixel gathers its
 // window from each scale, cascades and ring-selects in LDS, writing only the H x W x nclasses result.
 #include "dfe_internal.h"
+#include "cv_fine_epilogue.h"
+#include "dfe_wave.h"
 #include <cstring>
 #include <type_traits>
 #include <cmath>
@@ -519,7 +521,7 @@ __global__ __launch_bounds__(kWaves * 64) void cascade_argmax_kernel(CascadeGeom
         // index arithmetic in 32 bits (a 64-bit divide per pixel cost more than the whole cascade), x / r through a float
         // reciprocal (exact: (x + 0.5) / r is never within 1/(2r) of an integer); class -> displacement from a table
         // built once per block instead of divisions per pixel.
-        // Eight pixels per step: their wave reductions share one halving butterfly (dfe_internal.h: wave_min8, ~40 VALU for 8
+        // Eight pixels per step: their wave reductions share one halving butterfly (dfe_wave.h: wave_min8, ~40 VALU for 8
         // columns instead of 8 x 12 dependent DPP steps), on keys that order like the floats (sign-folded bits, inverted so
         // that the minimum is the maximum value); the smallest class among the lanes holding a column's maximum comes
         // from a second butterfly; lanes 0..7 then finish one pixel each and store together.

@@ -2,6 +2,7 @@
 // tie-break, A7/A8 extractOutput(+Marginalized), A9/A10 class-id decode.  All of them stream the
 // [P][N] volume once (one wave per pixel, 256-B coalesced reads) or are elementwise over [P].
 #include "dfe_internal.h"
+#include "cv_records.h"
 #include <cmath>
 
 namespace {
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void argbest_kernel(const floa
 // replaces: extract_output.cpp:63-155 / :157-255.  The reference scans the N values of a pixel in
 // index order and keeps the first M that exceed the threshold; a wave does the same 64 values at a
 // time with a ballot, so the kept set and its order are identical.
-// sorting networks: dfe_sort4 / dfe_sort8 in dfe_internal.h (extract_output.cpp:17-61)
+// sorting networks: dfe_sort4 / dfe_sort8 in cv_records.h (extract_output.cpp:17-61)
 #define sort4 dfe_sort4
 #define sort8 dfe_sort8
 
@@ -170,7 +171,7 @@ __global__ void x2yx_multi_compat_kernel(CompatGeom g, const long long *__restri
 
 // ---- fused single-scale tail: A6 (min + centre tie-break) + A7 + A9 in one pass over the volume ----
 // replaces: radial/radial_opticalflow_groundtruth.lua:87-105 (min(3), tie-break, decode, extractOutput)
-// (TailOut, pair_depth_px and the record path of the finalize -- dfe_finalize_rec_pixel -- live in dfe_internal.h: the fused sweep
+// (TailOut, pair_depth_px and the record path of the finalize -- dfe_finalize_rec_pixel -- live in cv_records.h: the fused sweep
 //  finishes its own pixels with the same code)
 
 // Finishes what the fused cost-volume epilogue started; one thread per pixel, everything it normally reads is compact
@@ -486,27 +487,15 @@ int fill_geom(dfe_ctx *ctx, MultiGeom &g, int maxh, int maxw, const int *ratios,
 
 }  // namespace
 
-void dfe_make_tailout(TailOut *po, int64_t *idx, float *best, float *fy, float *fx, float *scores, int64_t *imaxs, int Wo, int pitch, int pad_t, int pad_l,
-                      int scores_padded, int row_off, const DfePairDepth *pd) {
-    TailOut &o = *po;
-    o.frame_H = 0; o.frame_W = 0; o.depth = nullptr; o.conf = nullptr; o.mw = o.mh = o.infty = 0.f;
+int dfe_flow_finalize(dfe_ctx *ctx, const CvFuseArgs &fa, bool recs, int nchunks, const float *vol, const CvNovolArgs *nv, double threshold, int rows,
+                      int hWin, int wWin, const TailOut &out, const DfePairDepth *pd) {
+    TailOut o = out;
     if (pd) {   // frame mode: this call owns the whole frame (one band), fy / fx / scores are full-frame planes
         o.frame_H = pd->H; o.frame_W = pd->W; o.depth = pd->depth; o.conf = pd->conf;
         o.mw = pd->cx; o.mh = pd->cy; o.infty = (float)((double)pd->W / 2);   // test_opticalflow.lua:148 geometry.wImg/2
     }
-    o.idx = (long long *)idx; o.best = best; o.fy = fy; o.fx = fx; o.scores = scores; o.imaxs = (long long *)imaxs;
-    o.Wo = Wo; o.pitch = pitch; o.pad_t = pad_t; o.pad_l = pad_l; o.padded = scores_padded;
-    o.p_off = (long long)row_off * Wo; o.row_off = row_off;
-}
-
-int dfe_flow_finalize(dfe_ctx *ctx, const float2 *part, const float *centre, const float *lead, int nchunks, long long Ptot,
-                      const float *vol, double threshold, int rows, int Wo, int hWin, int wWin, int row_off, int64_t *idx, float *best,
-                      float *fy, float *fx, float *scores, int64_t *imaxs, int pitch, int pad_t, int pad_l, int scores_padded,
-                      const DfePairDepth *pd, const float *rec, int rec_rows, const float *fb) {
-    if (rec) nchunks = 1;
-    TailOut o;
-    dfe_make_tailout(&o, idx, best, fy, fx, scores, imaxs, Wo, pitch, pad_t, pad_l, scores_padded, row_off, pd);
-    const long long Pb = (long long)rows * Wo;
+    const float *rec = recs ? fa.rec : nullptr, *fb = nv ? nv->fb : nullptr;
+    const long long Pb = (long long)rows * o.Wo;
     const int N = hWin * wWin;
     const int middle = dfe_window_middle(hWin, wWin);
     const int grid = dfe_grid1d(pd ? (long long)pd->H * pd->W : Pb, 256);
@@ -515,18 +504,18 @@ int dfe_flow_finalize(dfe_ctx *ctx, const float2 *part, const float *centre, con
         DFE_REQUIRE(ctx, Pb < (1ll << 31), DFE_E_SHAPE, "flow finalize: %lld pixels in one band", Pb);   // (32-bit pixel arithmetic in the record path)
         DFE_REQUIRE(ctx, !pd || (long long)pd->H * pd->W < (1ll << 31), DFE_E_SHAPE, "flow finalize: frame of %d x %d pixels", pd ? pd->H : 0, pd ? pd->W : 0);
         if (threshold < 0.2)   // extract_output.cpp:83-85
-            hipLaunchKernelGGL(flow_finalize_rec_kernel<8>, dim3(grid), dim3(256), 0, ctx->stream, vol, Pb, N, hWin, wWin, middle, threshold, o, rec, rec_rows, fb);
+            hipLaunchKernelGGL(flow_finalize_rec_kernel<8>, dim3(grid), dim3(256), 0, ctx->stream, vol, Pb, N, hWin, wWin, middle, threshold, o, rec, fa.rec_rows, fb);
         else
-            hipLaunchKernelGGL(flow_finalize_rec_kernel<4>, dim3(grid), dim3(256), 0, ctx->stream, vol, Pb, N, hWin, wWin, middle, threshold, o, rec, rec_rows, fb);
+            hipLaunchKernelGGL(flow_finalize_rec_kernel<4>, dim3(grid), dim3(256), 0, ctx->stream, vol, Pb, N, hWin, wWin, middle, threshold, o, rec, fa.rec_rows, fb);
         DFE_LAUNCH_CHECK(ctx);
         return DFE_OK;
     }
     if (threshold < 0.2)   // extract_output.cpp:83-85
-        hipLaunchKernelGGL(flow_finalize_kernel<8>, dim3(grid), dim3(256), 0, ctx->stream, part, centre, lead, nchunks, Ptot, vol, Pb, N,
-                           hWin, wWin, middle, threshold, o, rec, rec_rows);
+        hipLaunchKernelGGL(flow_finalize_kernel<8>, dim3(grid), dim3(256), 0, ctx->stream, fa.part, fa.centre, fa.lead,
+                           nchunks, fa.Ptot, vol, Pb, N, hWin, wWin, middle, threshold, o, rec, fa.rec_rows);
     else
-        hipLaunchKernelGGL(flow_finalize_kernel<4>, dim3(grid), dim3(256), 0, ctx->stream, part, centre, lead, nchunks, Ptot, vol, Pb, N,
-                           hWin, wWin, middle, threshold, o, rec, rec_rows);
+        hipLaunchKernelGGL(flow_finalize_kernel<4>, dim3(grid), dim3(256), 0, ctx->stream, fa.part, fa.centre, fa.lead,
+                           nchunks, fa.Ptot, vol, Pb, N, hWin, wWin, middle, threshold, o, rec, fa.rec_rows);
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
@@ -689,17 +678,13 @@ int64_t dfe_yx2x_multi(int maxh, int maxw, const int *ratios, int nratios, doubl
     return (long long)maxw * maxh + (long long)(i - 1) * (2ll * d * maxw + 2ll * (maxh - 2 * d) * d) + it;
 }
 
-int dfe_flow_tail(dfe_ctx *ctx, const float *vol, int rows, int Wo, int hWin, int wWin, double threshold, int row_off,
-                  int64_t *idx, float *best, float *fy, float *fx, float *scores, int64_t *imaxs, int pitch, int pad_t,
-                  int pad_l, int scores_padded) {
-    DFE_ENTER(ctx);
-    DFE_REQUIRE(ctx, vol && rows >= 0 && Wo > 0 && hWin > 0 && wWin > 0, DFE_E_ARG, "dfe_flow_tail: bad argument");
-    if (rows == 0) return DFE_OK;
-    TailOut o;
-    o.idx = (long long *)idx; o.best = best; o.fy = fy; o.fx = fx; o.scores = scores; o.imaxs = (long long *)imaxs;
-    o.Wo = Wo; o.pitch = pitch; o.pad_t = pad_t; o.pad_l = pad_l; o.padded = scores_padded;
-    o.p_off = (long long)row_off * Wo; o.row_off = row_off;
-    const long long Pb = (long long)rows * Wo;
+}  // extern "C"
+
+// the full pass over a band's volume: dfe_flow_tail behind its argument checks, and flow_pipeline's fallback (ssd_cost_volume.hip)
+// (it stands here, between two extern "C" blocks, and not beside dfe_flow_finalize: a kernel template is emitted where it is first used, and
+//  flow_tail_kernel's place in the code object is behind the entries above)
+int dfe_flow_tail_run(dfe_ctx *ctx, const float *vol, int rows, int hWin, int wWin, double threshold, const TailOut &o) {
+    const long long Pb = (long long)rows * o.Wo;
     const int N = hWin * wWin;
     const int middle = dfe_window_middle(hWin, wWin);
     DFE_REQUIRE(ctx, N <= 64 * 36, DFE_E_UNSUPPORTED, "dfe_flow_tail: window %dx%d has more than 2304 cells", hWin, wWin);
@@ -713,6 +698,20 @@ int dfe_flow_tail(dfe_ctx *ctx, const float *vol, int rows, int Wo, int hWin, in
 #undef DFE_TAIL
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
+}
+
+extern "C" {
+
+int dfe_flow_tail(dfe_ctx *ctx, const float *vol, int rows, int Wo, int hWin, int wWin, double threshold, int row_off,
+                  int64_t *idx, float *best, float *fy, float *fx, float *scores, int64_t *imaxs, int pitch, int pad_t,
+                  int pad_l, int scores_padded) {
+    DFE_ENTER(ctx);
+    DFE_REQUIRE(ctx, vol && rows >= 0 && Wo > 0 && hWin > 0 && wWin > 0, DFE_E_ARG, "dfe_flow_tail: bad argument");
+    if (rows == 0) return DFE_OK;
+    TailOut o = dfe_tailout(idx, best, fy, fx, scores, imaxs, Wo, pitch, pad_t, pad_l, scores_padded);
+    o.row_off = row_off;
+    o.p_off = (long long)row_off * Wo;
+    return dfe_flow_tail_run(ctx, vol, rows, hWin, wWin, threshold, o);
 }
 
 int dfe_flow_to_depth_cartesian(dfe_ctx *ctx, const float *flow, int H, int W, float cx, float cy, int fix_dot, float *depth,

@@ -28,6 +28,9 @@
 //                       Summation order is fixed relative to the output pixel (independent of the
 //                       tile), so results do not depend on the launch geometry.
 #include "dfe_internal.h"
+#include "cv_records.h"
+#include "cv_fine_epilogue.h"
+#include "dfe_wave.h"
 #include <type_traits>
 #include <memory>
 #include <cmath>
@@ -328,7 +331,7 @@ __device__ __forceinline__ int wave_min1(int c) {
     return min((int)q[0], (int)q[1]);
 }
 
-// (wave_reduce8_transposed and fine_epilogue -- the fused pyramid scales' epilogue, shared with the feature matcher -- live in dfe_internal.h)
+// (wave_reduce8_transposed and fine_epilogue -- the fused pyramid scales' epilogue, shared with the feature matcher -- live in dfe_wave.h and cv_fine_epilogue.h)
 
 // Rows are swept in groups of U (the unroll that makes every ring index static):
 //   K == 7: U = 6, vertical sum as the fixed tree ((H0+H1)+(H2+H3))+((H4+H5)+H6) kept as a ring of six
@@ -2082,9 +2085,8 @@ static float float_at_or_below(double t) {
 // The flow step without its cost volume (option "cv_novol", default on): the volume-free fused sweep leaves records and, for the rare
 // pixels whose lead cells hold fewer than M hits, the fallback plane; one launch for the whole pair (no bands: 112 B of scratch per
 // pixel instead of 4356), then the record finalize.  Returns DFE_OK with *done = false where the sweep does not apply.
-static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, int hWin, int wWin, double thr, int64_t *idx,
-                               float *best, float *fy, float *fx, float *scores, int64_t *imaxs, int pitch, int pad_t, int pad_l,
-                               int scores_padded, const DfePairDepth *pd, bool *pd_done, bool *done) {
+static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, int hWin, int wWin, double thr, const TailOut &out,
+                               const DfePairDepth *pd, bool *pd_done, bool *done) {
     constexpr int K = 7;
     *done = false;
     const int Ho = H - K + 1 - hWin + 1, Wo = W - K + 1 - wWin + 1;
@@ -2111,8 +2113,7 @@ static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, i
     }
     *done = true;
     DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
-    rc = dfe_flow_finalize(ctx, nullptr, nullptr, nullptr, 2, P, nullptr, thr, Ho, Wo, hWin, wWin, 0, idx, best, fy, fx, scores, imaxs, pitch,
-                           pad_t, pad_l, scores_padded, pd, fa.rec, Ho, nv.fb);
+    rc = dfe_flow_finalize(ctx, fa, true, 1, nullptr, &nv, thr, Ho, hWin, wWin, out, pd);
     if (pd && pd_done) *pd_done = true;
 #if DFE_TL
     if (const char *path = getenv("DFE_TIMELINE_OUT"); path && !rc && nrec * 8 * DFE_FB * sizeof(float) >= 2 * DFE_TL_WORDS * sizeof(unsigned)) {
@@ -2132,17 +2133,16 @@ static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, i
 // reads only those; it goes back to the volume only for pixels whose first 16 cells hold fewer than M values above
 // the extractOutput threshold.
 // Fallback (shapes without a fused instantiation): build, then the full pass dfe_flow_tail.
+// out: where the results go (dfe_tailout, Wo = this pair's); each band gets its row_off / p_off here.
 static int flow_pipeline(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int kh, int kw, int hWin, int wWin,
-                         double thr, int64_t *idx, float *best, float *fy, float *fx, float *scores, int64_t *imaxs, int pitch,
-                         int pad_t, int pad_l, int scores_padded, const DfePairDepth *pd = nullptr, bool *pd_done = nullptr, float f16_scale = 0.f) {
+                         double thr, const TailOut &out, const DfePairDepth *pd = nullptr, bool *pd_done = nullptr, float f16_scale = 0.f) {
     // f16_scale != 0: the volume is materialised as fp16 (cost * f16_scale); arg-min, centre and lead cells still come from
     // the fp32 sums in the kernel, so indices and minima are those of the fp32 path.  No extractOutput scores then (its
     // rare fall-back reads the volume).
     if (kh == kw && kh == 7 && f16_scale == 0.f && rowimg_writes_records(C, hWin, wWin) && ctx->opt_bool(DFE_OPT_CV_NOVOL, true) &&
         (ctx->cv_mode == 0 || ctx->cv_mode == 3) && (ctx->cv_tyq == 0 || ctx->cv_tyq == 1)) {   // (forced static tiles: the volume path)
         bool done = false;
-        int rc = flow_pipeline_novol(ctx, I0, I1, H, W, hWin, wWin, thr, idx, best, fy, fx, scores, imaxs, pitch, pad_t, pad_l, scores_padded, pd,
-                                     pd_done, &done);
+        int rc = flow_pipeline_novol(ctx, I0, I1, H, W, hWin, wWin, thr, out, pd, pd_done, &done);
         if (rc || done) return rc;
     }
     const int Ho = H - kh + 1 - hWin + 1, Wo = W - kw + 1 - wWin + 1;
@@ -2169,9 +2169,12 @@ static int flow_pipeline(dfe_ctx *ctx, const float *I0, const float *I1, int C, 
         fa.cmid = (middle - 1) >> 6; fa.lmid = (middle - 1) & 63;
     }
     const int nb = band_count(Ho, band);
+    TailOut o = out;
     for (int bi = 0; bi < nb; ++bi) {
         const int r0 = (int)((long long)bi * Ho / nb), nr = (int)((long long)(bi + 1) * Ho / nb) - r0;   // (nr <= band)
         const int Hb = nr + kh - 1 + hWin - 1;
+        o.row_off = r0;
+        o.p_off = (long long)r0 * Wo;
         const float *b0 = I0 + (long long)r0 * W, *b1 = I1 + (long long)r0 * W;
         bool fused = false, recs = false;
         int nparts = nch;
@@ -2192,15 +2195,14 @@ static int flow_pipeline(dfe_ctx *ctx, const float *I0, const float *I1, int C, 
             DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
             // one band: the finalize launch also zeroes the frame border and makes depth (pair step: 2 launches instead of 3)
             const bool frame_mode = pd && nr == Ho;
-            rc = dfe_flow_finalize(ctx, fa.part, fa.centre, fa.lead, nparts, P, vol, thr, nr, Wo, hWin, wWin, r0, idx, best, fy, fx, scores,
-                                   imaxs, pitch, pad_t, pad_l, scores_padded, frame_mode ? pd : nullptr, (recs && fused) ? fa.rec : nullptr, Ho);
+            rc = dfe_flow_finalize(ctx, fa, recs, nparts, vol, nullptr, thr, nr, hWin, wWin, o, frame_mode ? pd : nullptr);
             if (frame_mode && pd_done) *pd_done = true;
         } else {
             rc = cv_frames_dispatch(ctx, b0, b1, C, Hb, W, (long long)H * W, kh, kw, hWin, wWin, vol);
             if (rc) return rc;
             match_scope.reset();
             DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
-            rc = dfe_flow_tail(ctx, vol, nr, Wo, hWin, wWin, thr, r0, idx, best, fy, fx, scores, imaxs, pitch, pad_t, pad_l, scores_padded);
+            rc = dfe_flow_tail_run(ctx, vol, nr, hWin, wWin, thr, o);
         }
         if (rc) return rc;
     }
@@ -2218,8 +2220,8 @@ int dfe_ssd_flow_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int 
     DFE_REQUIRE(ctx, Ho > 0 && Wo > 0, DFE_E_SHAPE, "dfe_ssd_flow_f32: frame %dx%d too small for kernel %dx%d + window %dx%d",
                 H, W, kh, kw, hWin, wWin);
     DFE_REQUIRE(ctx, (scores == nullptr) == (imaxs == nullptr), DFE_E_ARG, "dfe_ssd_flow_f32: scores and imaxs go together");
-    return flow_pipeline(ctx, I0, I1, C, H, W, kh, kw, hWin, wWin, extract_threshold, idx, best, flow_y, flow_x, scores, imaxs, Wo, 0,
-                         0, 0);
+    return flow_pipeline(ctx, I0, I1, C, H, W, kh, kw, hWin, wWin, extract_threshold,
+                         dfe_tailout(idx, best, flow_y, flow_x, scores, imaxs, Wo, /*pitch*/ Wo, /*pad_t*/ 0, /*pad_l*/ 0, /*scores_padded*/ 0));
 }
 
 int dfe_flow_depth_pair_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin,
@@ -2241,8 +2243,8 @@ int dfe_flow_depth_pair_f32(dfe_ctx *ctx, const float *I0, const float *I1, int 
     // the pipeline writes every interior pixel of flow / scores; one pass afterwards zeroes the border and makes depth
     const DfePairDepth pd{H, W, foe_x, foe_y, depth, depth_conf};
     bool pd_done = false;
-    int rc = flow_pipeline(ctx, I0, I1, C, H, W, k, k, hWin, wWin, extract_threshold, nullptr, nullptr, flow, flow + HW, scores, nullptr,
-                           W, pad_t, pad_l, 1, &pd, &pd_done);
+    int rc = flow_pipeline(ctx, I0, I1, C, H, W, k, k, hWin, wWin, extract_threshold,
+                           dfe_tailout(nullptr, nullptr, flow, flow + HW, scores, nullptr, Wo, /*pitch*/ W, pad_t, pad_l, /*scores_padded*/ 1), &pd, &pd_done);
     if (rc || pd_done) return rc;
     // several bands, or no fused build for this shape: one pass afterwards zeroes the border and makes depth
     DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
@@ -2299,8 +2301,8 @@ int dfe_flow_depth_pair_f16(dfe_ctx *ctx, const float *I0, const float *I1, int 
     const DfePairDepth pd{H, W, foe_x, foe_y, depth, depth_conf};
     bool pd_done = false;
     // (idx / best are [Ho][Wo], like dfe_ssd_flow_f32's; flow is the centre-pasted [2][H][W])
-    int rc = flow_pipeline(ctx, I0, I1, C, H, W, k, k, hWin, wWin, 0.0, idx, best, flow, flow + HW, nullptr, nullptr, W, pad_t, pad_l, 1, &pd, &pd_done,
-                           scale);
+    int rc = flow_pipeline(ctx, I0, I1, C, H, W, k, k, hWin, wWin, 0.0,
+                           dfe_tailout(idx, best, flow, flow + HW, nullptr, nullptr, Wo, /*pitch*/ W, pad_t, pad_l, /*scores_padded*/ 1), &pd, &pd_done, scale);
     if (rc || pd_done) return rc;
     DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
     return dfe_pair_border_depth(ctx, flow, nullptr, H, W, pad_t, pad_l, Ho, Wo, foe_x, foe_y, depth, depth_conf);

@@ -11,6 +11,7 @@
 // pixels share their flow, which is most of a frame.  The five costs share their reads and are the bit patterns of
 // dfe_ssd_cost_volume_f32's reference kernel (subpixel_costs.h).
 #include "dfe_internal.h"
+#include "cv_records.h"        // pair_depth_px
 #include "subpixel_offset.h"   // the parabola's vertex on one axis (include/dfe.h: this order, IEEE division)
 #include "subpixel_costs.h"    // the five costs, from the frames
 

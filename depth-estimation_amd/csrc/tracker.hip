@@ -13,6 +13,7 @@
 // Every image read goes through a clamped index; every loop is bounded by a constant or by a checked argument; no block waits
 // on another.
 #include "dfe_internal.h"
+#include "dfe_wave.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>

@@ -615,6 +615,33 @@ def test_flow_depth_pair_matches_oracle(dfe, cuda, H, W, win, C, thr):
     ctx.check(dfe.lib().dfe_flow_depth_pair_f32(ctx.handle, t0.data_ptr(), t1.data_ptr(), C, H, W, k, win, win, cx, cy, thr,
                                                flow2.data_ptr(), None, None, None))
     assert torch.equal(flow2, flow)
+    # several row bands (the volume path: the volume-free sweep has none): full-frame-addressed scores at row_off > 0, border and depth
+    # by the pass behind the pipeline -- bit-equal to the one-band outputs above.  A third of the volume: fused bands with records or
+    # planes; the 1 MiB floor: bands of 2-5 rows of a 33 x 33 window, below the smallest tile -> the reference-order kernel and the tail pass
+    Ho, Wo = H - k + 1 - win + 1, W - k + 1 - win + 1
+    row_bytes = Wo * win * win * 4
+    try:
+        with ctx.options(cv_novol=0):
+            for limit in sorted({max(Ho * row_bytes // 3, 1 << 20), 1 << 20}, reverse=True):
+                band = max(limit // row_bytes, 1)   # rows of a band before they are dealt evenly
+                if band >= Ho:   # one band
+                    continue
+                ctx.check(dfe.lib().dfe_set_scratch_limit(ctx.handle, limit))
+                flow_b = torch.full((2, H, W), 7.0, device=cuda)
+                scores_b = torch.full((H, W), -3.0, device=cuda)
+                depth_b = torch.full((H, W), -1.0, device=cuda)
+                conf_b = torch.full((H, W), -1.0, device=cuda)
+                ctx.check(dfe.lib().dfe_flow_depth_pair_f32(ctx.handle, t0.data_ptr(), t1.data_ptr(), C, H, W, k, win, win, cx, cy, thr,
+                                                           flow_b.data_ptr(), scores_b.data_ptr(), depth_b.data_ptr(), conf_b.data_ptr()))
+                # the last band's build says which path ran: a fused band (records or planes, then the finalize), or -- the 33 x 33 shapes
+                # at the floor, 2-5 rows, below every tile -- the reference-order kernel with the tail pass behind it.  Never the sweep
+                name_b = ctx.last_kernel()
+                fused = "ssd_cv_rowimg_kernel+fused_tail" if win == 33 else "ssd_cv_tiled_kernel+fused_tail"
+                assert name_b == ("ssd_cv_ref_kernel" if band <= 5 else fused), (limit, band, name_b)
+                for got, one_band in ((flow_b, flow), (scores_b, scores), (depth_b, depth), (conf_b, conf)):
+                    assert torch.equal(got.view(torch.int32), one_band.view(torch.int32)), limit
+    finally:
+        ctx.check(dfe.lib().dfe_set_scratch_limit(ctx.handle, 16 << 30))
 
 
 @pytest.mark.parametrize("K,H1,W1,mh,mw", [(3, 9, 11, 5, 4), (30, 20, 26, 7, 9), (1, 6, 70, 17, 17), (8, 33, 5, 1, 1)])
