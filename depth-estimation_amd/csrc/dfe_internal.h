@@ -8,6 +8,7 @@
 #include <hip/hip_ext.h>
 #include "../../include/dfe.h"
 #include "dfe_carve.h"
+#include "fm_select.h"
 
 // Behaviour switches of the launchers (dfe_set_option / dfe_get_option, include/dfe.h).  -1 = automatic: the launcher's own choice
 // per shape.  The environment is read ONCE, in dfe_ctx_create (tuning scripts), never inside a launcher.
@@ -290,16 +291,6 @@ struct MsSubpixelArgs {
     const long long *idx;       // [H][W], 1-based class ids
     float *fy, *fx;             // [H][W] each, written where idx is a class id
 };
-// what getModel's tail + processOutput leave per pair (opticalflow_model.lua:201-252): the centre-pasted full-frame flow and confidences,
-// optionally the per-pixel class index and extractOutput score over the model's own output region
-struct DfeSoftOut {
-    int use_threshold;             // 0: processOutput(geometry, out, true, nil);  1: ...(geometry, out, true, threshold)
-    float threshold;
-    int hFull, wFull;              // geometry.hImg, geometry.wImg
-    float *full, *full_conf;       // [2][hFull][wFull] (plane 0 = y), [hFull][wFull]: ZEROED by the caller; the kernel writes the pasted region
-    long long *index;              // [H1][W1] or NULL
-    float *scores;                 // [H1][W1] or NULL
-};
 // one description of a learned filter stack (filters.hip), the one rule of every entry that takes dfe_filter_layer[]: every layer complete
 // (DFE_E_ARG); layer 0 reads the frames' C planes, a full layer the planes of the layer before it, a connection-table layer at most those
 // (DFE_E_SHAPE).  nlayers == 0: {1, 1, C, C}
@@ -350,8 +341,7 @@ int cv_frames_dispatch_fused(dfe_ctx *ctx, const float *I0, const float *I1, int
 int cv_frames_finest_fused(dfe_ctx *ctx, const float *I0p, const float *I1p, int C, int Hp, int Wp, int k, int maxh, int maxw, const CvFineArgs &fine,
                            bool *handled);
 bool cv_finest_plan_ok(dfe_ctx *ctx, int Hp, int Wp, int maxh, int maxw);   // cv_frames_finest_fused (with a parent scale) would take this frame
-// nn.SpatialMatching on feature maps, fast kernels or the reference-order one
-int dfe_spatial_matching_dispatch(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int maxh, int maxw, float *out);
+int dfe_fm_launch_ref(dfe_ctx *ctx, const FmJob &j);   // the reference-order kernel on feature maps (FM_K_REF)
 
 // postops.hip
 // Finishes `rows` rows of a fused build from what it left in fa: the tile-row records (recs; part / centre / lead are ignored then) or the
@@ -365,36 +355,27 @@ int dfe_flow_tail_run(dfe_ctx *ctx, const float *vol, int rows, int hWin, int wW
 int dfe_pair_border_depth(dfe_ctx *ctx, float *flow, float *scores, int H, int W, int pad_t, int pad_l, int Ho, int Wo, float cx,
                           float cy, float *depth, float *conf);
 
-// feat_matching.hip
-int dfe_feat_matching_fast(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int maxh, int maxw, float *out,
-                           bool *handled);
+// feat_matching_dispatch.hip -- nn.SpatialMatching on feature maps.  The one rule: a kernel is chosen by fm_select (fm_select.h); a launcher
+// (dfe_fm_launch_*, one per kernel family, geometry from the FmPick) never declines
+static inline FmEnv dfe_fm_env(const dfe_ctx *c) {
+    return FmEnv{c->cv_mode, c->opt[DFE_OPT_FM_FLAT], c->opt[DFE_OPT_FM64], c->opt[DFE_OPT_FM_ROWS], c->opt[DFE_OPT_FM_MFMA], c->opt[DFE_OPT_FM_SPLIT]};
+}
+// fm_select on the job, then the pick's launch.  FM_K_NONE launches nothing: with `picked` the caller sees it there (and goes through a
+// contiguous copy or the volume), without it the call fails
+int dfe_fm_run(dfe_ctx *ctx, const FmJob &j, FmPick *picked = nullptr);
+// the volume of contiguous maps behind dfe_spatial_matching_f32's argument checks
+int dfe_spatial_matching_dispatch(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int maxh, int maxw, float *out);
+
+// feat_matching.hip, feat_matching_flat.hip, feat_matching_mfma.hip
+int dfe_fm_launch_win64(dfe_ctx *ctx, const FmJob &j, const FmPick &pk);
+int dfe_fm_launch_rows(dfe_ctx *ctx, const FmJob &j, const FmPick &pk);
+int dfe_fm_launch_chunk(dfe_ctx *ctx, const FmJob &j, const FmPick &pk);
+int dfe_fm_launch_flat(dfe_ctx *ctx, const FmJob &j, const FmPick &pk);
+int dfe_fm_launch_mfma(dfe_ctx *ctx, const FmJob &j, const FmPick &pk);
+// the one-chunk matcher on n pairs (pyramid scales) in one launch, or on one pair through the fused pyramid epilogue (fine)
 bool dfe_feat_matching_win64_ok(const dfe_ctx *ctx, int K, int maxh, int maxw);   // the ctx / window conditions of the launcher below
 int dfe_feat_matching_win64_batch(dfe_ctx *ctx, int n, const float *const *in1, const float *const *in2, int K, const int *H1, const int *W1, int maxh,
                                   int maxw, float *const *out, float f16_scale, bool *handled, const CvFineArgs *fine = nullptr);
-
-// feat_matching_flat.hip -- 16- / 17-wide windows on feature maps: flat tiles, persistent blocks, LDS-DMA staging
-int dfe_feat_matching_flat(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int maxh, int maxw, float *out, bool *handled);
-int dfe_feat_matching_flat_argmin(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int maxh, int maxw, long long *idx, float *xflow,
-                                  float *yflow, bool *handled);
-bool dfe_feat_matching_flat_argmin_takes(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw);
-int dfe_feat_matching_flat_strided(dfe_ctx *ctx, const float *in1, int pitch1, long long plane1, const float *in2, int K, int H1, int W1, int maxh, int maxw,
-                                   float *out, bool *handled);
-// whether the one-kernel flat matcher takes in1 as a view -- rows pitch1, planes plane1 floats apart: the arena planners leave the volume
-// out only where it does
-bool dfe_feat_matching_flat_view_takes(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw, int pitch1, long long plane1);
-int dfe_feat_matching_flat_soft(dfe_ctx *ctx, const float *in1, int pitch1, long long plane1, const float *in2, int K, int H1, int W1, int maxh, int maxw,
-                                const DfeSoftOut *soft, bool *handled);
-// ... and its soft-max epilogue with processOutput's 'mean' branch (soft arg-max, row-marginal confidence) behind it: full / full_conf /
-// index as DfeSoftOut describes them, y and x as floats; *handled stays false where the shape is not the kernel's
-int dfe_feat_matching_flat_mean(dfe_ctx *ctx, const float *in1, int pitch1, long long plane1, const float *in2, int K, int H1, int W1, int maxh, int maxw,
-                                const DfeSoftOut *soft, bool *handled);
-
-// feat_matching_mfma.hip -- the matcher as a banded GEMM on the matrix cores (option fm_mfma); norms: dfe_feat_matching_mfma_scratch floats
-bool dfe_feat_matching_mfma_takes(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw);
-size_t dfe_feat_matching_mfma_scratch(int H1, int W1, int maxh, int maxw);
-// norms_ready: `norms` already holds |a|^2 [H1][W1] | |b|^2 [H2][W2] (left there by the convolution that made the features)
-int dfe_feat_matching_mfma(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int maxh, int maxw, float *norms, float *out, long long *idx,
-                           float *xflow, float *yflow, bool *handled, bool norms_ready = false);
 
 // filters.hip
 int dfe_filter_stack_geom(dfe_ctx *ctx, const char *entry, const dfe_filter_layer *layers, int nlayers, int C, DfeStackGeom *g);

@@ -11,8 +11,7 @@
 
 namespace {
 
-constexpr int FM_TX = 8, FM_TY = 8, FM_NW = 8, FM_MAXT = 8;   // tile, waves, max tasks per wave
-
+// (FM_TX, FM_TY, FM_NW, FM_MAXT, F64_TY: fm_select.h, where the choice of a kernel reads them too)
 typedef const float __attribute__((address_space(4))) *fm_cfptr;
 typedef float fm_f8 __attribute__((ext_vector_type(8)));
 typedef fm_f8 fm_f8u __attribute__((aligned(4)));
@@ -198,7 +197,6 @@ struct FmBatch {
     float *out[DFE_MAX_RATIOS];
     int H1[DFE_MAX_RATIOS], W1[DFE_MAX_RATIOS];
 };
-constexpr int F64_TY = 16;
 // MODE 0: the volume is stored.  MODE 1 / 2 (8 x 8 windows, one pair): the task rows -- 8 pixels x 64 cells, lane <-> cell, exactly the
 // tiled SSD kernel's -- go through fine_epilogue (cv_fine_epilogue.h) instead: the finest pyramid scale (1) or a scale between (2) without
 // its volume, as in ssd_cv_tiled_fine_kernel.  F16: the costs are rounded as the stored fp16 volume would hold them.
@@ -360,17 +358,36 @@ __global__ __launch_bounds__(512) void feat_matching_win64_fine_kernel(FmBatch f
 
 }  // namespace
 
-// The ctx- and window-level conditions of dfe_feat_matching_win64_batch (everything but the per-pair sizes): the multiscale launcher
-// plans its fused scales with the SAME predicate the launcher applies, so a plan never meets a refusal (round-3 advisor: with
-// dfe_set_cost_volume_kernel(1) or fm64 = 0 the fused second scale was planned and then refused).
-bool dfe_feat_matching_win64_ok(const dfe_ctx *ctx, int K, int maxh, int maxw) {
-    if (maxh * maxw != 64 || K < 1 || K > 16 || ctx->cv_mode == 1 || ctx->opt[DFE_OPT_FM64] == 0) return false;
-    const int tcols = FM_TX + maxw - 1, trows = F64_TY + maxh - 1;
-    if (tcols > 16) return false;                          // (the staging deals 16 columns per tile row)
-    int pitch = tcols;
-    while ((pitch - maxw) % 32 != 0) ++pitch;
-    return (size_t)K * trows * pitch * sizeof(float) <= 64 * 1024;
+// the one-chunk matcher's launch: n pairs as the grid's z, or one pair through the fused pyramid epilogue (fine)
+static int win64_launch(dfe_ctx *ctx, const FmBatch &fb, int n, int gx, int gy, int K, int maxh, int maxw, int pitch, size_t lds, float f16_scale, size_t vol,
+                        const CvFineArgs *fine) {
+    if (fine) {
+        const bool h16 = fine->f16_scale != 0.f, mid = fine->casc != nullptr;
+        auto kern = mid ? (h16 ? feat_matching_win64_fine_kernel<2, true> : feat_matching_win64_fine_kernel<2, false>)
+                        : (h16 ? feat_matching_win64_fine_kernel<1, true> : feat_matching_win64_fine_kernel<1, false>);
+        DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        {
+            DfeProfScope prof(ctx);
+            hipLaunchKernelGGL(kern, dim3(gx, gy, 1), dim3(512), lds, ctx->stream, fb, K, pitch, *fine);
+        }
+        DFE_LAUNCH_CHECK(ctx);
+        ctx->last_kernel = mid ? (h16 ? "feat_matching_win64_mid_kernel_f16" : "feat_matching_win64_mid_kernel") : h16 ? "feat_matching_win64_fine_kernel_f16" : "feat_matching_win64_fine_kernel";
+        return DFE_OK;
+    }
+    DFE_HIP(ctx, hipFuncSetAttribute((const void *)feat_matching_win64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int nt = vol > ((size_t)160 << 20);              // (volumes that do not stay in the memory-side cache: non-temporal stores)
+    {
+        DfeProfScope prof(ctx);
+        hipLaunchKernelGGL(feat_matching_win64_kernel, dim3(gx, gy, n), dim3(512), lds, ctx->stream, fb, K, maxh, maxw, pitch, f16_scale, nt);
+    }
+    DFE_LAUNCH_CHECK(ctx);
+    ctx->last_kernel = f16_scale != 0.f ? "feat_matching_win64_kernel_f16" : "feat_matching_win64_kernel";
+    return DFE_OK;
 }
+
+// The ctx- and window-level conditions of dfe_feat_matching_win64_batch (everything but the per-pair sizes; fm_win64_geom): the multiscale
+// launcher plans its fused scales with the SAME function the launcher applies
+bool dfe_feat_matching_win64_ok(const dfe_ctx *ctx, int K, int maxh, int maxw) { return fm_win64_geom(dfe_fm_env(ctx), K, maxh, maxw, nullptr, nullptr); }
 
 // n pairs (pyramid scales) of K-plane features through one launch of the one-chunk matcher; out[i] [H1][W1][64] f32, or half volumes
 // (half(cost * f16_scale)) when f16_scale != 0.  *handled = false: not this kernel's shape (the caller launches pair by pair).
@@ -379,7 +396,9 @@ bool dfe_feat_matching_win64_ok(const dfe_ctx *ctx, int K, int maxh, int maxw) {
 int dfe_feat_matching_win64_batch(dfe_ctx *ctx, int n, const float *const *in1, const float *const *in2, int K, const int *H1, const int *W1, int maxh,
                                   int maxw, float *const *out, float f16_scale, bool *handled, const CvFineArgs *fine) {
     *handled = false;
-    if (!dfe_feat_matching_win64_ok(ctx, K, maxh, maxw) || n < 1 || n > DFE_MAX_RATIOS) return DFE_OK;
+    int pitch = 0;
+    size_t lds = 0;
+    if (!fm_win64_geom(dfe_fm_env(ctx), K, maxh, maxw, &pitch, &lds) || n < 1 || n > DFE_MAX_RATIOS) return DFE_OK;
     if (fine && (n != 1 || maxh != 8 || maxw != 8 || (fine->pcasc && ((H1[0] | W1[0]) & 1)))) return DFE_OK;
     FmBatch fb;
     int gx = 0, gy = 0;
@@ -392,96 +411,43 @@ int dfe_feat_matching_win64_batch(dfe_ctx *ctx, int n, const float *const *in1, 
         gy = gy > dfe_cdiv(H1[i], F64_TY) ? gy : dfe_cdiv(H1[i], F64_TY);
         vol += (size_t)H1[i] * W1[i] * 64 * (f16_scale != 0.f ? 2 : 4);
     }
-    const int tcols = FM_TX + maxw - 1, trows = F64_TY + maxh - 1;
-    if (tcols > 16) return DFE_OK;                         // (the staging deals 16 columns per tile row)
-    int pitch = tcols;
-    while ((pitch - maxw) % 32 != 0) ++pitch;              // pitch == maxw (mod 32): conflict-free for the lane <-> (dy, dx) reads
-    size_t lds = (size_t)K * trows * pitch * sizeof(float);
-    if (lds < (size_t)8 * FM_TX * 64 * sizeof(float)) lds = (size_t)8 * FM_TX * 64 * sizeof(float);   // the copy-out scratch reuses the tile
-    if (lds > 64 * 1024) return DFE_OK;
-    if (fine) {
-        const bool h16 = fine->f16_scale != 0.f, mid = fine->casc != nullptr;
-        auto kern = mid ? (h16 ? feat_matching_win64_fine_kernel<2, true> : feat_matching_win64_fine_kernel<2, false>)
-                        : (h16 ? feat_matching_win64_fine_kernel<1, true> : feat_matching_win64_fine_kernel<1, false>);
-        DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        {
-            DfeProfScope prof(ctx);
-            hipLaunchKernelGGL(kern, dim3(gx, gy, 1), dim3(512), lds, ctx->stream, fb, K, pitch, *fine);
-        }
-        DFE_LAUNCH_CHECK(ctx);
-        ctx->last_kernel = mid ? (h16 ? "feat_matching_win64_mid_kernel_f16" : "feat_matching_win64_mid_kernel") : h16 ? "feat_matching_win64_fine_kernel_f16" : "feat_matching_win64_fine_kernel";
-        *handled = true;
-        return DFE_OK;
-    }
-    DFE_HIP(ctx, hipFuncSetAttribute((const void *)feat_matching_win64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int nt = vol > ((size_t)160 << 20);              // (volumes that do not stay in the memory-side cache: non-temporal stores)
+    const int rc = win64_launch(ctx, fb, n, gx, gy, K, maxh, maxw, pitch, lds, f16_scale, vol, fine);
+    *handled = rc == DFE_OK;
+    return rc;
+}
+
+// ---- the single-pair launches fm_select picked (dfe_fm_run, feat_matching_dispatch.hip): geometry from the FmPick ----
+int dfe_fm_launch_win64(dfe_ctx *ctx, const FmJob &j, const FmPick &pk) {
+    FmBatch fb;
+    fb.in1[0] = j.in1; fb.in2[0] = j.in2; fb.out[0] = j.out; fb.H1[0] = j.H1; fb.W1[0] = j.W1;
+    return win64_launch(ctx, fb, 1, dfe_cdiv(j.W1, FM_TX), dfe_cdiv(j.H1, F64_TY), j.K, j.maxh, j.maxw, pk.pitch, pk.lds, 0.f, (size_t)j.H1 * j.W1 * 64 * 4, nullptr);
+}
+
+int dfe_fm_launch_rows(dfe_ctx *ctx, const FmJob &j, const FmPick &pk) {
+    FmArgs a{};
+    a.K = j.K; a.H1 = j.H1; a.W1 = j.W1; a.maxh = j.maxh; a.maxw = j.maxw; a.H2 = j.H1 + j.maxh - 1; a.W2 = j.W1 + j.maxw - 1;
+    dim3 grid(dfe_cdiv(j.W1, 256), j.H1);
+    auto kern = j.maxw == 16 ? feat_matching_rows_kernel<16> : feat_matching_rows_kernel<8>;
+    DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk.lds));
     {
         DfeProfScope prof(ctx);
-        hipLaunchKernelGGL(feat_matching_win64_kernel, dim3(gx, gy, n), dim3(512), lds, ctx->stream, fb, K, maxh, maxw, pitch, f16_scale, nt);
+        hipLaunchKernelGGL(kern, grid, dim3(64 * j.maxh), pk.lds, ctx->stream, j.in1, j.in2, j.out, a);
     }
     DFE_LAUNCH_CHECK(ctx);
-    ctx->last_kernel = f16_scale != 0.f ? "feat_matching_win64_kernel_f16" : "feat_matching_win64_kernel";
-    *handled = true;
     return DFE_OK;
 }
 
-// *handled stays false when the shape has no fast instantiation (the caller falls back to the reference-order kernel)
-int dfe_feat_matching_fast(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int maxh, int maxw, float *out,
-                           bool *handled) {
-    *handled = false;
-    const int D = maxh * maxw, nchunks = (D + 63) / 64;
-    if (ctx->cv_mode == 1) return DFE_OK;
-    if (maxh * maxw == 64 && K <= 16 && ctx->cv_mode != 2) {   // one-chunk windows (the pyramid's 8 x 8): the prefetching, transposing matcher
-        int rc = dfe_feat_matching_win64_batch(ctx, 1, &in1, &in2, K, &H1, &W1, maxh, maxw, &out, 0.f, handled);
-        if (rc != DFE_OK || *handled) return rc;
-    }
-    {   // 16- / 17-wide windows on frames at least 253 pixels wide: the flat-tile kernel (feat_matching_flat.hip)
-        int rc = dfe_feat_matching_flat(ctx, in1, in2, K, H1, W1, maxh, maxw, out, handled);
-        if (rc != DFE_OK || *handled) return rc;
-    }
-    // The row kernel pays a barrier and a tile refill per plane and only fills its 256-column blocks on wide frames: measured
-    // 625 x 465, 16 x 16: K = 32 0.37 ms against 0.55 ms for the chunk kernel below, K = 10 0.168 against 0.194 (with the next plane's
-    // loads in flight behind the arithmetic; 0.46 / 0.23 before); K = 10, 293 x 153: 0.064 against 0.039 ms.
-    // (W1 == 1: the patch-mode call of the trainers, any K -- the chunk kernel needs 8 x 8 pixels.)
-    bool rows_pays = (K >= 8 && W1 >= 400) || W1 < FM_TX || H1 < FM_TY;
-    rows_pays = ctx->opt_bool(DFE_OPT_FM_ROWS, rows_pays);   // tuning
-    if (rows_pays && (maxw == 16 || maxw == 8) && maxh >= 4 && maxh <= 16 && ctx->cv_mode != 2 && ((uintptr_t)out & 15) == 0) {
-        FmArgs a{};
-        a.K = K; a.H1 = H1; a.W1 = W1; a.maxh = maxh; a.maxw = maxw; a.H2 = H1 + maxh - 1; a.W2 = W1 + maxw - 1;
-        const int TC = 256 + maxw;
-        const size_t lds = ((size_t)2 * maxh * TC + 2 * 256 + (size_t)64 * maxh * maxw) * sizeof(float);
-        dim3 grid(dfe_cdiv(W1, 256), H1);
-        auto kern = maxw == 16 ? feat_matching_rows_kernel<16> : feat_matching_rows_kernel<8>;
-        DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        {
-            DfeProfScope prof(ctx);
-            hipLaunchKernelGGL(kern, grid, dim3(64 * maxh), lds, ctx->stream, in1, in2, out, a);
-        }
-        DFE_LAUNCH_CHECK(ctx);
-        ctx->last_kernel = "feat_matching_rows_kernel";
-        *handled = true;
-        return DFE_OK;
-    }
-    if (W1 < FM_TX || H1 < FM_TY || FM_TY * nchunks > FM_MAXT * FM_NW) return DFE_OK;
-    if (((uintptr_t)in1 & 3) != 0) return DFE_OK;
+int dfe_fm_launch_chunk(dfe_ctx *ctx, const FmJob &j, const FmPick &pk) {
     FmArgs a;
-    a.K = K; a.H1 = H1; a.W1 = W1; a.maxh = maxh; a.maxw = maxw; a.H2 = H1 + maxh - 1; a.W2 = W1 + maxw - 1;
-    a.trows = FM_TY + maxh - 1; a.tcols = FM_TX + maxw - 1;
-    a.pitch = a.tcols | 1;                                  // odd pitch: the lanes behind a dy-row jump land on other banks
-    a.nchunks = nchunks;
-    const size_t per_plane = (size_t)a.trows * a.pitch * sizeof(float);
-    int kb = (int)((48 * 1024) / per_plane);
-    if (kb < 1) return DFE_OK;
-    a.KB = kb < K ? kb : K;
-    const size_t lds = (size_t)a.KB * per_plane;
-    DFE_HIP(ctx, hipFuncSetAttribute((const void *)feat_matching_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    dim3 grid(dfe_cdiv(W1, FM_TX), dfe_cdiv(H1, FM_TY));
+    a.K = j.K; a.H1 = j.H1; a.W1 = j.W1; a.maxh = j.maxh; a.maxw = j.maxw; a.H2 = j.H1 + j.maxh - 1; a.W2 = j.W1 + j.maxw - 1;
+    a.trows = FM_TY + j.maxh - 1; a.tcols = FM_TX + j.maxw - 1;
+    a.pitch = pk.pitch; a.nchunks = (j.maxh * j.maxw + 63) / 64; a.KB = pk.KB;
+    DFE_HIP(ctx, hipFuncSetAttribute((const void *)feat_matching_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk.lds));
+    dim3 grid(dfe_cdiv(j.W1, FM_TX), dfe_cdiv(j.H1, FM_TY));
     {
         DfeProfScope prof(ctx);
-        hipLaunchKernelGGL(feat_matching_kernel, grid, dim3(FM_NW * 64), lds, ctx->stream, in1, in2, out, a);
+        hipLaunchKernelGGL(feat_matching_kernel, grid, dim3(FM_NW * 64), pk.lds, ctx->stream, j.in1, j.in2, j.out, a);
     }
     DFE_LAUNCH_CHECK(ctx);
-    ctx->last_kernel = "feat_matching_kernel";
-    *handled = true;
     return DFE_OK;
 }

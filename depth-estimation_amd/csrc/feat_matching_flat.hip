@@ -27,13 +27,11 @@
 #include "dfe_internal.h"
 #include "cv_records.h"   // dfe_sort8
 #include "dfe_wave.h"
-#include <algorithm>
 #include <type_traits>
 
 namespace {
 
-constexpr int FF_PX = 4;                     // pixels per lane
-constexpr int FF_GROUPS = 64;                // groups (lanes) per tile
+// (FF_PX, FF_GROUPS, FfGeom and ff_wnp: fm_select.h, where the choice of a kernel reads them too)
 #define FF_ST_FLAGS " nt"                    // cache policy of the copy-out stores
 constexpr int FF_BATCH = 8;                  // (pixel, cell) pairs whose differences / squares / adds are issued as three groups
 template <int I, int N, class F> __device__ __forceinline__ void static_for_q(F &&f) {
@@ -74,23 +72,10 @@ struct FfArgs {
     long long fullplane;               // hFull * wFull
     float *full, *full_conf, *scores;  // [2][hFull][wFull] (plane 0 = y), [hFull][wFull], [H1][W1]; each may be NULL (idx above: [H1][W1])
 };
-enum { FF_VOLUME = 0, FF_ARGMIN = 1, FF_SOFT = 2, FF_MEAN = 3 };
+enum { FF_VOLUME = FM_VOLUME, FF_ARGMIN = FM_ARGMIN, FF_SOFT = FM_SOFT, FF_MEAN = FM_MEAN };
 constexpr float FF_TIE = 1e-6f;   // FF_SOFT without a threshold: cells this close to a window's minimum may share its maximal probability
 
-template <int MW> struct FfGeom {
-    static constexpr int PITCH = (64 * FF_PX + 2 * (MW - 1) + 8 + 3) / 4 * 4;   // floats per LDS tile row (piece A | piece B)
-    static constexpr int NLOAD = (PITCH + 63) / 64;                             // LDS-DMA loads per tile row
-    static constexpr int NB4 = (FF_PX + MW - 1 + 3) / 4;                        // b128 reads of a lane's window row
-};
-
 extern __shared__ __attribute__((aligned(128))) float ff_smem[];
-
-// floats per window slot of the copy-out image: a multiple of 4 with room for the alignment shift (<= 3 floats) of a window whose
-// place in the output is not 16-B aligned, and not a multiple of 8 (the 64 lanes' 16-B writes then fall on different banks)
-__host__ __device__ inline int ff_wnp(int WN) {
-    int w = (WN + 3 + 3) & ~3;
-    return (w & 7) ? w : w + 4;
-}
 
 // One LDS-DMA load of 64 floats: lane l fetches the float at sbase + voff (bytes; its own offset) into LDS at lds_dst + 4 l.
 // Written as assembly for the addressing form: scalar base + 32-bit vector offset -- through the builtin the compiler built a 64-bit
@@ -752,50 +737,17 @@ __global__ __launch_bounds__(1024) void feat_matching_flat_mean_kernel(FfArgs p)
 
 }  // namespace
 
-// the shapes this kernel takes (the pointers' alignment apart): 16- / 17-wide windows of 4 .. 17 rows on frames at least 64 groups wide
-static bool ff_shape_ok(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw) {
-    if (ctx->cv_mode == 1 || ctx->cv_mode == 2 || ctx->opt[DFE_OPT_FM_FLAT] == 0) return false;
-    if (maxw != 16 && maxw != 17) return false;
-    if (maxh < 4 || maxh > 17 || (maxh == 17 && maxw != 17)) return false;
-    const int G = dfe_cdiv(W1, FF_PX);
-    if (G < FF_GROUPS || K < 1 || H1 < 1) return false;                    // (a tile must not touch more than two image rows)
-    const long long NGl = (long long)H1 * G;
-    if (NGl > (1ll << 30) || (long long)H1 * W1 * maxh * maxw >= (1ll << 40)) return false;
-    return true;
-}
-
-// ... and in1 as a view (rows pitch1 floats apart, planes plane1 floats apart): everything ff_launch can decline on but the pointers'
-// alignment (the LDS budget holds for every shape ff_shape_ok takes: 158 KiB at most, 17 x 17 soft-max)
-static bool ff_view_ok(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw, int pitch1, long long plane1) {
-    if (!ff_shape_ok(ctx, K, H1, W1, maxh, maxw)) return false;
-    return pitch1 >= W1 && plane1 >= (long long)(H1 - 1) * pitch1 + W1 && plane1 < (1ll << 29);
-}
-
-// whether dfe_feat_matching_flat_argmin / _soft will take the shape (4-byte aligned feature maps assumed): the one-call models decide with
-// it whether the volume needs a place in the scratch arena at all -- a decline behind a `true` here would leave them without a volume
-bool dfe_feat_matching_flat_argmin_takes(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw) {
-    return ff_view_ok(ctx, K, H1, W1, maxh, maxw, W1, (long long)H1 * W1);
-}
-bool dfe_feat_matching_flat_view_takes(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw, int pitch1, long long plane1) {
-    return ff_view_ok(ctx, K, H1, W1, maxh, maxw, pitch1, plane1);
-}
-
-// *handled stays false when the shape is not this kernel's (the caller goes on to the round-3 kernels)
-static int ff_launch(dfe_ctx *ctx, const float *in1, int pitch1, long long plane1, const float *in2, int K, int H1, int W1, int maxh, int maxw, float *out,
-                     long long *idx, float *xflow, float *yflow, const DfeSoftOut *soft, bool *handled, bool mean = false) {
-    const int mode = soft ? (mean ? FF_MEAN : FF_SOFT) : out ? FF_VOLUME : FF_ARGMIN;
-    const bool argmin = mode == FF_ARGMIN;
-    *handled = false;
-    if (!ff_view_ok(ctx, K, H1, W1, maxh, maxw, pitch1, plane1)) return DFE_OK;
-    const int G = dfe_cdiv(W1, FF_PX);
-    if (((uintptr_t)in1 | (uintptr_t)in2 | (uintptr_t)out) & 3) return DFE_OK;
-    const long long NGl = (long long)H1 * G;
+// the flat-tile launch fm_select picked for the job (every form; FmPick: S, nd, LDS bytes)
+int dfe_fm_launch_flat(dfe_ctx *ctx, const FmJob &j, const FmPick &pk) {
+    const int K = j.K, H1 = j.H1, W1 = j.W1, maxh = j.maxh, maxw = j.maxw, mode = j.form;
+    const DfeSoftOut *soft = mode >= FF_SOFT ? j.soft : nullptr;
+    const long long NGl = (long long)H1 * dfe_cdiv(W1, FF_PX);
     FfArgs a{};
-    a.in1 = in1; a.in2 = in2; a.out = out;
-    a.pitch1 = pitch1; a.plane1 = plane1;
+    a.in1 = j.in1; a.in2 = j.in2; a.out = mode == FF_VOLUME ? j.out : nullptr;
+    a.pitch1 = j.pitch1; a.plane1 = j.plane1;
     a.K = K; a.H1 = H1; a.W1 = W1; a.maxh = maxh; a.H2 = H1 + maxh - 1; a.W2 = W1 + maxw - 1;
-    a.G = G; a.NG = (int)NGl; a.ntiles = dfe_cdiv(NGl, FF_GROUPS);
-    a.idx = idx; a.xflow = xflow; a.yflow = yflow;
+    a.G = dfe_cdiv(W1, FF_PX); a.NG = (int)NGl; a.ntiles = dfe_cdiv(NGl, FF_GROUPS);
+    if (mode == FF_ARGMIN) { a.idx = j.idx; a.xflow = j.xflow; a.yflow = j.yflow; }
     a.lWin = dfe_window_lead(maxw); a.tWin = dfe_window_lead(maxh);
     if (soft) {
         a.middle = dfe_window_middle(maxh, maxw);
@@ -803,88 +755,23 @@ static int ff_launch(dfe_ctx *ctx, const float *in1, int pitch1, long long plane
         a.wFull = soft->wFull; a.fullplane = (long long)soft->hFull * soft->wFull;
         a.ho = (soft->hFull - H1) / 2; a.wo = (soft->wFull - W1) / 2;    // processOutput: floor((hImg - h) / 2), :228-230
         a.full = soft->full; a.full_conf = soft->full_conf; a.scores = soft->scores; a.idx = soft->index;
-        if ((soft->full || soft->full_conf) && (soft->hFull < H1 || soft->wFull < W1)) return DFE_OK;
     }
-    const bool extra = maxh == 17;
-    // two half blocks per tile and CU where the window's rows split evenly into halves of >= 4 waves (the arg-min and soft-max forms need
-    // the whole window in one block; 17 rows = 17 waves do not fit a CU's registers as 9 + 8)
-    // (option fm_split: 0 whole tiles, 1 / 2 halves, 4 quarters; the launcher's own choice: quarters for few planes -- the copy-out is
-    //  then a larger share of a tile, K = 10: 0.102 -> 0.098 ms, time_matching.lua's shape 0.024 -> 0.022 -- else halves, which cost
-    //  less staging: profiles/r04_ao_fm_quarters.txt)
-    const int want = ctx->opt[DFE_OPT_FM_SPLIT] < 0 ? (K <= 16 ? 4 : 2) : ctx->opt[DFE_OPT_FM_SPLIT] == 1 ? 2 : ctx->opt[DFE_OPT_FM_SPLIT];
-    const bool can = mode == FF_VOLUME && !extra;
-    a.S = can && want >= 4 && maxh == 16 ? 4 : can && want >= 2 && maxh >= 8 && maxh % 2 == 0 ? 2 : 1;
-    a.nd = extra ? 16 : maxh / a.S;
-    const int NW = a.nd;
-    const int PITCH = maxw == 17 ? FfGeom<17>::PITCH : FfGeom<16>::PITCH;
-    const int WNP = ff_wnp((extra ? 17 : a.nd) * maxw);
-    // the copy-out image [64][WNP]; the arg-min form keeps its candidates there instead -- cv[256][NC] and ci[256][NC], NC = 16 (20 with
-    // the extra task) whatever the window's height: larger than the image of a window of fewer than 8 rows; the soft-max form reads its
-    // windows in 16-B pieces up to cell 4 * 16 * ceil(WN / 64) of the last window and keeps extractOutput's candidates [64][16] behind
-    const size_t img_floats = mode >= FF_SOFT ? (size_t)64 * WNP + 64 * 16 + 64
-                                              : std::max((size_t)64 * WNP, argmin ? (size_t)2 * 256 * (extra ? 20 : 16) : (size_t)0);
-    const size_t lds = ((size_t)3 * (extra ? 18 : a.nd + 1) * PITCH + 3 * 64 * FF_PX + 64 + img_floats) * sizeof(float);
-    if (lds * a.S > 160 * 1024) return DFE_OK;
+    a.S = pk.S; a.nd = pk.nd;
+    const bool extra = pk.extra;
     void (*kern)(FfArgs);
     if (mode == FF_MEAN) kern = maxw == 17 ? (extra ? feat_matching_flat_mean_kernel<17, true> : feat_matching_flat_mean_kernel<17, false>)
                                            : feat_matching_flat_mean_kernel<16, false>;
     else if (mode == FF_SOFT) kern = maxw == 17 ? (extra ? feat_matching_flat_kernel<17, true, FF_SOFT> : feat_matching_flat_kernel<17, false, FF_SOFT>)
                                            : feat_matching_flat_kernel<16, false, FF_SOFT>;
-    else if (argmin) kern = maxw == 17 ? (extra ? feat_matching_flat_kernel<17, true, FF_ARGMIN> : feat_matching_flat_kernel<17, false, FF_ARGMIN>)
-                                       : feat_matching_flat_kernel<16, false, FF_ARGMIN>;
+    else if (mode == FF_ARGMIN) kern = maxw == 17 ? (extra ? feat_matching_flat_kernel<17, true, FF_ARGMIN> : feat_matching_flat_kernel<17, false, FF_ARGMIN>)
+                                                  : feat_matching_flat_kernel<16, false, FF_ARGMIN>;
     else kern = maxw == 17 ? (extra ? feat_matching_flat_kernel<17, true> : feat_matching_flat_kernel<17, false>) : feat_matching_flat_kernel<16, false>;
-    DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk.lds));
     const int nblk = (a.ntiles < ctx->ncu ? a.ntiles : ctx->ncu) * a.S;
     {
         DfeProfScope prof(ctx);
-        hipLaunchKernelGGL(kern, dim3(nblk), dim3(64 * NW), lds, ctx->stream, a);
+        hipLaunchKernelGGL(kern, dim3(nblk), dim3(64 * a.nd), pk.lds, ctx->stream, a);
     }
     DFE_LAUNCH_CHECK(ctx);
-    ctx->last_kernel = mode == FF_MEAN ? "feat_matching_flat_mean_kernel" : mode == FF_SOFT ? "feat_matching_flat_kernel+softmax" : argmin ? "feat_matching_flat_kernel+argmin" : "feat_matching_flat_kernel";
-    *handled = true;
     return DFE_OK;
-}
-
-int dfe_feat_matching_flat(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int maxh, int maxw, float *out, bool *handled) {
-    *handled = false;
-    if (!out) return DFE_OK;
-    return ff_launch(ctx, in1, W1, (long long)H1 * W1, in2, K, H1, W1, maxh, maxw, out, nullptr, nullptr, nullptr, nullptr, handled);
-}
-
-// in1 as a view: rows pitch1 floats apart, planes plane1 floats apart (prepareInput's narrow of a feature map, opticalflow_model.lua:147-149)
-int dfe_feat_matching_flat_strided(dfe_ctx *ctx, const float *in1, int pitch1, long long plane1, const float *in2, int K, int H1, int W1, int maxh, int maxw,
-                                   float *out, bool *handled) {
-    *handled = false;
-    if (!out) return DFE_OK;
-    return ff_launch(ctx, in1, pitch1, plane1, in2, K, H1, W1, maxh, maxw, out, nullptr, nullptr, nullptr, nullptr, handled);
-}
-
-// nn.SpatialMatching(maxh, maxw) + `min` over the window + the decode of version2/test.lua:45-51, without the volume
-int dfe_feat_matching_flat_argmin(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int maxh, int maxw, long long *idx, float *xflow,
-                                  float *yflow, bool *handled) {
-    if (dfe_feat_matching_mfma_takes(ctx, K, H1, W1, maxh, maxw)) {   // opt-in (fm_mfma = 1): the banded GEMM on the matrix cores
-        void *nrm = nullptr;
-        int rc = dfe_aux_scratch(ctx, dfe_feat_matching_mfma_scratch(H1, W1, maxh, maxw) * sizeof(float), &nrm);
-        if (rc) return rc;
-        rc = dfe_feat_matching_mfma(ctx, in1, in2, K, H1, W1, maxh, maxw, (float *)nrm, nullptr, idx, xflow, yflow, handled);
-        if (rc != DFE_OK || *handled) return rc;
-    }
-    return ff_launch(ctx, in1, W1, (long long)H1 * W1, in2, K, H1, W1, maxh, maxw, nullptr, idx, xflow, yflow, nullptr, handled);
-}
-
-// nn.SpatialMatching -> nn.Minus -> SoftMax over the window -> processOutput, without the volume (the FF_SOFT epilogue)
-int dfe_feat_matching_flat_soft(dfe_ctx *ctx, const float *in1, int pitch1, long long plane1, const float *in2, int K, int H1, int W1, int maxh, int maxw,
-                                const DfeSoftOut *soft, bool *handled) {
-    *handled = false;
-    if (!soft) return DFE_OK;
-    return ff_launch(ctx, in1, pitch1, plane1, in2, K, H1, W1, maxh, maxw, nullptr, nullptr, nullptr, nullptr, soft, handled);
-}
-
-// nn.SpatialMatching -> nn.Minus -> SoftMax over the window -> processOutput's 'mean' branch, without the volume (the FF_MEAN epilogue;
-// soft->use_threshold, threshold and scores are not read)
-int dfe_feat_matching_flat_mean(dfe_ctx *ctx, const float *in1, int pitch1, long long plane1, const float *in2, int K, int H1, int W1, int maxh, int maxw,
-                                const DfeSoftOut *soft, bool *handled) {
-    *handled = false;
-    if (!soft) return DFE_OK;
-    return ff_launch(ctx, in1, pitch1, plane1, in2, K, H1, W1, maxh, maxw, nullptr, nullptr, nullptr, nullptr, soft, handled, true);
 }

@@ -34,8 +34,7 @@ template <int I, int N, class F> __device__ __forceinline__ void fmm_static_for(
 
 typedef float f4v __attribute__((ext_vector_type(4)));
 
-constexpr int FMM_R = 8;     // output rows per block (= waves)
-constexpr int FMM_KC = 8;    // planes per stage (two MFMA k-steps); the arg-min form takes 16 where K % 16 == 0
+// (FMM_R, FMM_KC: fm_select.h, where the choice of a kernel reads them too)
 constexpr int FMM_T = FMM_R * 64;
 
 struct FmmArgs {
@@ -325,52 +324,34 @@ __global__ __launch_bounds__(FMM_T) void fmm_kernel(FmmArgs p) {
 
 }  // namespace
 
-// floats of scratch the launcher needs for the two norm planes
-size_t dfe_feat_matching_mfma_scratch(int H1, int W1, int maxh, int maxw) { return (size_t)H1 * W1 + (size_t)(H1 + maxh - 1) * (W1 + maxw - 1); }
-
-bool dfe_feat_matching_mfma_takes(const dfe_ctx *ctx, int K, int H1, int W1, int maxh, int maxw) {
-    if (ctx->opt[DFE_OPT_FM_MFMA] <= 0 || ctx->cv_mode == 1) return false;
-    if (!((maxh == 17 && maxw == 17) || (maxh == 16 && maxw == 16))) return false;
-    if (K < 1 || K > 256 || H1 < 1 || W1 < 1) return false;
-    // the LDS-DMA requests address in2 as 32-bit BYTE offsets 4 * (k plane2 + row W2 + col) from the map's base: below 2^30 floats they do
-    // not wrap (in1 and the norm planes are smaller)
-    return (long long)K * (H1 + maxh - 1) * (W1 + maxw - 1) < (1ll << 30);
-}
-
-// out != NULL: the volume; else the first-minimum decode (idx / xflow / yflow).  norms: dfe_feat_matching_mfma_scratch floats.
-int dfe_feat_matching_mfma(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int maxh, int maxw, float *norms, float *out, long long *idx,
-                           float *xflow, float *yflow, bool *handled, bool norms_ready) {
-    *handled = false;
-    if (!dfe_feat_matching_mfma_takes(ctx, K, H1, W1, maxh, maxw) || !norms) return DFE_OK;
+// the matrix-core launch fm_select picked: the volume (FM_VOLUME) or the first-minimum decode (FM_ARGMIN).  j.norms: fm_mfma_scratch floats
+int dfe_fm_launch_mfma(dfe_ctx *ctx, const FmJob &j, const FmPick &pk) {
+    const int K = j.K, H1 = j.H1, W1 = j.W1, maxh = j.maxh, maxw = j.maxw;
+    const bool volume = j.form == FM_VOLUME;
     const int H2 = H1 + maxh - 1, W2 = W1 + maxw - 1;
-    float *na = norms, *nb = norms + (size_t)H1 * W1;
+    float *na = j.norms, *nb = j.norms + (size_t)H1 * W1;
     const long long P1 = (long long)H1 * W1, P2 = (long long)H2 * W2;
-    if (!norms_ready) {
-        hipLaunchKernelGGL(fmm_norm_kernel, dim3((unsigned)std::min<long long>((P1 + 255) / 256, 4096)), dim3(256), 0, ctx->stream, in1, K, P1, na);
-        hipLaunchKernelGGL(fmm_norm_kernel, dim3((unsigned)std::min<long long>((P2 + 255) / 256, 4096)), dim3(256), 0, ctx->stream, in2, K, P2, nb);
+    if (!j.norms_ready) {
+        hipLaunchKernelGGL(fmm_norm_kernel, dim3((unsigned)std::min<long long>((P1 + 255) / 256, 4096)), dim3(256), 0, ctx->stream, j.in1, K, P1, na);
+        hipLaunchKernelGGL(fmm_norm_kernel, dim3((unsigned)std::min<long long>((P2 + 255) / 256, 4096)), dim3(256), 0, ctx->stream, j.in2, K, P2, nb);
         DFE_LAUNCH_CHECK(ctx);
     }
     FmmArgs a{};
-    a.in1 = in1; a.in2 = in2; a.na = na; a.nb = nb; a.out = out; a.idx = idx; a.xflow = xflow; a.yflow = yflow;
+    a.in1 = j.in1; a.in2 = j.in2; a.na = na; a.nb = nb;
+    if (volume) a.out = j.out;
+    else { a.idx = j.idx; a.xflow = j.xflow; a.yflow = j.yflow; }
     a.K = K; a.H1 = H1; a.W1 = W1; a.H2 = H2; a.W2 = W2;
     a.gx = dfe_cdiv(W1, 16); a.ntiles = a.gx * dfe_cdiv(H1, FMM_R);
     a.lWin = dfe_window_lead(maxw); a.tWin = dfe_window_lead(maxh);
-    const int BROWS = (FMM_R + maxh - 1 + 3) & ~3;
-    // the arg-min form stages 16 planes at a time where K allows it: three of four k-steps then have their operands requested behind MFMAs
-    const bool kc16 = !out && K % 16 == 0;
-    const int KC = kc16 ? 16 : FMM_KC;
-    const size_t lds = ((size_t)2 * (KC * (BROWS * 32 + 16) + KC * (FMM_R * 16)) + (size_t)2 * BROWS * 32) * sizeof(float);
-    void (*kern)(FmmArgs) = out      ? (maxh == 17 ? fmm_kernel<17, 17, false> : fmm_kernel<16, 16, false>)
-                            : kc16 ? (maxh == 17 ? fmm_kernel<17, 17, true, 16> : fmm_kernel<16, 16, true, 16>)
-                                   : (maxh == 17 ? fmm_kernel<17, 17, true> : fmm_kernel<16, 16, true>);
-    DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    void (*kern)(FmmArgs) = volume        ? (maxh == 17 ? fmm_kernel<17, 17, false> : fmm_kernel<16, 16, false>)
+                            : pk.KC == 16 ? (maxh == 17 ? fmm_kernel<17, 17, true, 16> : fmm_kernel<16, 16, true, 16>)
+                                          : (maxh == 17 ? fmm_kernel<17, 17, true> : fmm_kernel<16, 16, true>);
+    DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk.lds));
     const int nblk = a.ntiles < ctx->ncu ? a.ntiles : ctx->ncu;
     {
         DfeProfScope prof(ctx);
-        hipLaunchKernelGGL(kern, dim3(nblk), dim3(FMM_T), lds, ctx->stream, a);
+        hipLaunchKernelGGL(kern, dim3(nblk), dim3(FMM_T), pk.lds, ctx->stream, a);
     }
     DFE_LAUNCH_CHECK(ctx);
-    ctx->last_kernel = out ? "fmm_kernel" : "fmm_kernel+argmin";
-    *handled = true;
     return DFE_OK;
 }

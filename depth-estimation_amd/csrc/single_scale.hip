@@ -112,10 +112,16 @@ static int ss_flow_pair(dfe_ctx *ctx, const char *fn, bool mean, const float *I0
     const int ny = dfe_window_lead(maxh), nx = dfe_window_lead(maxw);   // prepareInput's narrow: first row / column of patch 1
     const int N = maxh * maxw;
     const long long P1 = (long long)H1 * W1;
-    // the matcher reads the narrowed in1 in place when the caller ran the filter (prefilter: rows W, planes H W floats apart), else a
-    // contiguous map of the arena; the predicate sees that view and the frames' alignment, so that it declines what the launcher would
-    const bool lean = nlayers ? dfe_feat_matching_flat_argmin_takes(ctx, K, H1, W1, maxh, maxw)
-                              : dfe_feat_matching_flat_view_takes(ctx, K, H1, W1, maxh, maxw, W, (long long)H * W) && !(((uintptr_t)I0 | (uintptr_t)I1) & 3);
+    // The job of the matcher with the per-pixel tail in its epilogue.  It reads the narrowed in1 in place when the caller ran the filter
+    // (prefilter: a view of frame 0, rows W, planes H W floats apart, with the frames' own alignment), else contiguous maps of the arena to
+    // come; fm_select sees exactly what will run, so the volume is planned wherever that kernel is not the pick
+    DfeSoftOut so{};
+    so.use_threshold = use_threshold ? 1 : 0; so.threshold = (float)threshold;
+    so.hFull = hImg; so.wFull = wImg; so.full = full; so.full_conf = full_conf; so.index = (long long *)index; so.scores = scores;
+    FmJob job = fm_job(mean ? FM_MEAN : FM_SOFT, nullptr, nullptr, K, H1, W1, maxh, maxw);
+    job.soft = &so;
+    if (!nlayers) { job.in1 = I0 + (long long)ny * W + nx; job.pitch1 = W; job.plane1 = (long long)H * W; job.in2 = I1; }
+    const bool lean = fm_select(dfe_fm_env(ctx), job).kernel != FM_K_NONE;
     // arena: cropped frame 0 | two ping-pong feature buffers per branch | (fallback) contiguous in1 | volume | probabilities | index | scores
     // ('mean' fallback: imaxs | scores | x | y | row marginals in place of index and scores)
     const int Hc = H1 + hk - 1, Wc = W1 + wk - 1;                   // the part of frame 0 the narrowed features come from
@@ -135,9 +141,7 @@ static int ss_flow_pair(dfe_ctx *ctx, const char *fn, bool mean, const float *I0
         idx_s = c.take<long long>(n_idx); sc_s = c.take<float>(f_sc); mean_s = c.take<float>(f_mean);
     }, nlayers > 0);
     if (rc) return rc;
-    const float *in1 = nullptr, *in2 = nullptr;
-    int pitch1 = W1;
-    long long plane1 = P1;
+    const float *in1 = job.in1, *in2 = job.in2;   // (prefilter: patch 1's narrow is a view of the caller's map, depth_estimation_opticalflow.lua:66-75)
     if (nlayers) {
         DfeStageScope st(ctx, DFE_STAGE_FILTER);
         // the first branch filters only what the narrow keeps: a convolution is 'valid' and shift-invariant, so the features of the cropped
@@ -171,10 +175,6 @@ static int ss_flow_pair(dfe_ctx *ctx, const char *fn, bool mean, const float *I0
         }
         DFE_REQUIRE(ctx, ha == H1 && wa == W1 && hb == Hf && wb == Wf, DFE_E_SHAPE, "%s: internal shape mismatch", fn);
         in1 = ia; in2 = ib;
-    } else {
-        // geometry.prefilter: the caller ran the filter (depth_estimation_opticalflow.lua:66-75) -- patch 1's narrow is a view of its map
-        in1 = I0 + (long long)ny * W + nx; pitch1 = W; plane1 = (long long)H * W;
-        in2 = I1;
     }
     const int ho = (hImg - H1) / 2, wo = (wImg - W1) / 2;
     if ((full || full_conf) && (hImg > H1 || wImg > W1)) {
@@ -183,14 +183,8 @@ static int ss_flow_pair(dfe_ctx *ctx, const char *fn, bool mean, const float *I0
     }
     if (lean) {
         DfeStageScope st(ctx, DFE_STAGE_MATCH);
-        DfeSoftOut so{};
-        so.use_threshold = use_threshold ? 1 : 0; so.threshold = (float)threshold;
-        so.hFull = hImg; so.wFull = wImg; so.full = full; so.full_conf = full_conf; so.index = (long long *)index; so.scores = scores;
-        bool done = false;
-        rc = mean ? dfe_feat_matching_flat_mean(ctx, in1, pitch1, plane1, in2, K, H1, W1, maxh, maxw, &so, &done)
-                  : dfe_feat_matching_flat_soft(ctx, in1, pitch1, plane1, in2, K, H1, W1, maxh, maxw, &so, &done);
-        if (rc || done) return rc;
-        return dfe_fail(ctx, DFE_E_UNSUPPORTED, "%s: the matcher declined a shape its predicate took", fn);
+        job.in1 = in1; job.in2 = in2;
+        return dfe_fm_run(ctx, job);
     }
     if (!nlayers) {
         hipLaunchKernelGGL(ss_crop_kernel, dim3(dfe_grid1d((long long)K * P1, 256, 16384)), dim3(256), 0, ctx->stream, I0, (long long)H * W, W, ny, nx, H1, W1, (long long)K * P1, in1c);
@@ -267,10 +261,11 @@ extern "C" int dfe_spatial_matching_strided_f32(dfe_ctx *ctx, const float *in1, 
                 W1, maxh, maxw);
     DFE_REQUIRE(ctx, in1_pitch >= W1 && in1_plane >= (int64_t)(H1 - 1) * in1_pitch + W1, DFE_E_SHAPE, "dfe_spatial_matching_strided_f32: pitch %d / plane %lld too small for %dx%d",
                 in1_pitch, (long long)in1_plane, H1, W1);
-    if (in1_pitch == W1 && in1_plane == (int64_t)H1 * W1) return dfe_spatial_matching_dispatch(ctx, in1, in2, K, H1, W1, maxh, maxw, out);
-    bool done = false;
-    int rc = dfe_feat_matching_flat_strided(ctx, in1, in1_pitch, in1_plane, in2, K, H1, W1, maxh, maxw, out, &done);
-    if (rc || done) return rc;
+    FmJob job = fm_job(FM_VOLUME, in1, in2, K, H1, W1, maxh, maxw);
+    job.pitch1 = in1_pitch; job.plane1 = in1_plane; job.out = out;
+    FmPick pk;
+    int rc = dfe_fm_run(ctx, job, &pk);
+    if (rc || pk.kernel != FM_K_NONE) return rc;
     float *scr = nullptr;
     rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { scr = c.take<float>((size_t)K * H1 * W1); });
     if (rc) return rc;

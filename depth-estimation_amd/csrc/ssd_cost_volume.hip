@@ -2315,29 +2315,13 @@ int dfe_spatial_matching_f32(dfe_ctx *ctx, const float *in1, const float *in2, i
 }
 }  // extern "C"
 
-int dfe_spatial_matching_dispatch(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int maxh, int maxw, float *out) {
-    DFE_REQUIRE(ctx, in1 && in2 && out, DFE_E_ARG, "dfe_spatial_matching_f32: NULL tensor");
-    DFE_REQUIRE(ctx, K > 0 && H1 > 0 && W1 > 0 && maxh > 0 && maxw > 0, DFE_E_SHAPE,
-                "dfe_spatial_matching_f32: K=%d H1=%d W1=%d maxh=%d maxw=%d must be positive", K, H1, W1, maxh, maxw);
-    if (dfe_feat_matching_mfma_takes(ctx, K, H1, W1, maxh, maxw)) {   // opt-in (fm_mfma = 1): the banded GEMM on the matrix cores, costs to 1e-5
-        void *nrm = nullptr;
-        int rc = dfe_aux_scratch(ctx, dfe_feat_matching_mfma_scratch(H1, W1, maxh, maxw) * sizeof(float), &nrm);
-        if (rc) return rc;
-        bool handled = false;
-        rc = dfe_feat_matching_mfma(ctx, in1, in2, K, H1, W1, maxh, maxw, (float *)nrm, out, nullptr, nullptr, nullptr, &handled);
-        if (rc != DFE_OK || handled) return rc;
-    }
-    {
-        bool handled = false;   // lane <-> cell kernel with the feature tile in LDS (feat_matching.hip), bit-identical results
-        int rc = dfe_feat_matching_fast(ctx, in1, in2, K, H1, W1, maxh, maxw, out, &handled);
-        if (rc != DFE_OK || handled) return rc;
-    }
+int dfe_fm_launch_ref(dfe_ctx *ctx, const FmJob &j) {
     CvRefArgs a;
-    a.a = in1; a.a_plane = (long long)H1 * W1; a.a_pitch = W1; a.a_oy = 0; a.a_ox = 0;
-    a.b = in2; a.b_plane = (long long)(H1 + maxh - 1) * (W1 + maxw - 1); a.b_pitch = W1 + maxw - 1;
-    a.C = K; a.kh = 1; a.kw = 1; a.Wo = W1; a.hWin = maxh; a.wWin = maxw;
-    a.total = (long long)H1 * W1 * maxh * maxw;
-    a.out = out;
+    a.a = j.in1; a.a_plane = (long long)j.H1 * j.W1; a.a_pitch = j.W1; a.a_oy = 0; a.a_ox = 0;
+    a.b = j.in2; a.b_plane = (long long)(j.H1 + j.maxh - 1) * (j.W1 + j.maxw - 1); a.b_pitch = j.W1 + j.maxw - 1;
+    a.C = j.K; a.kh = 1; a.kw = 1; a.Wo = j.W1; a.hWin = j.maxh; a.wWin = j.maxw;
+    a.total = (long long)j.H1 * j.W1 * j.maxh * j.maxw;
+    a.out = j.out;
     return launch_cv_ref(ctx, a);
 }
 

@@ -42,6 +42,24 @@ __global__ __launch_bounds__(256) void v2_argmin_decode_kernel(const float *__re
 
 }  // namespace
 
+// the matcher into a volume, then the first-minimum decode of it (idx / xflow / yflow, each may be NULL; none: the volume only)
+static int v2_volume_argmin(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int hWin, int wWin, float *vol, long long *idx, float *xflow,
+                            float *yflow) {
+    {
+        DfeStageScope st(ctx, DFE_STAGE_MATCH);
+        int rc = dfe_spatial_matching_dispatch(ctx, in1, in2, K, H1, W1, hWin, wWin, vol);
+        if (rc) return rc;
+    }
+    DfeStageScope st(ctx, DFE_STAGE_EXTRACT);
+    if (xflow || yflow || idx) {
+        const long long P1 = (long long)H1 * W1;
+        hipLaunchKernelGGL(v2_argmin_decode_kernel, dim3(dfe_grid1d(P1, 4, 65535 * 16)), dim3(256), 0, ctx->stream, vol, P1, hWin * wWin, wWin, dfe_window_lead(wWin),
+                           dfe_window_lead(hWin), idx, xflow, yflow);
+        DFE_LAUNCH_CHECK(ctx);
+    }
+    return DFE_OK;
+}
+
 extern "C" int dfe_version2_flow_pair_f32(dfe_ctx *ctx, const float *prev, const float *cur, int C, int H, int W, const float *norm_kernel_host,
                                           int norm_k, float threshold, float thresval, const dfe_filter_layer *layers, int nlayers, int hWin,
                                           int wWin, float *xflow, float *yflow, int64_t *idx, float *volume) {
@@ -62,14 +80,18 @@ extern "C" int dfe_version2_flow_pair_f32(dfe_ctx *ctx, const float *prev, const
     // arena: normalisation scratch | normalised cur | cropped normalised prev | two ping-pong feature buffers per branch | volume (unless the caller gave one)
     const size_t f_cn = ((size_t)C + 3) * P, f_n = (size_t)C * P, f_c = (size_t)C * Hc * Wc;
     const size_t f_fa = (size_t)maxplanes * Hc * Wc, f_fb = (size_t)maxplanes * P;
-    // (the volume needs a place in the arena only when nobody gave one AND the matcher + arg-min kernel will not take the shape:
-    //  316 MB at VGA, 2.4 GB at 1080p that the lean path never touches)
-    const bool lean = !volume && (xflow || yflow || idx) && dfe_feat_matching_flat_argmin_takes(ctx, K, H1, W1, hWin, wWin);
+    // nobody asked for the volume: matcher and decode in one kernel where fm_select has one for the shape (bit-identical to the volume
+    // path: the same sums, the same first minimum).  The job is the one that runs below, its maps arena buffers to come
+    FmJob job = fm_job(FM_ARGMIN, nullptr, nullptr, K, H1, W1, hWin, wWin);
+    job.idx = (long long *)idx; job.xflow = xflow; job.yflow = yflow;
+    const FmPick plan = (!volume && (xflow || yflow || idx)) ? fm_select(dfe_fm_env(ctx), job) : FmPick{};
+    // (the volume needs a place in the arena only when nobody gave one AND no such kernel takes the shape: 316 MB at VGA, 2.4 GB at 1080p
+    //  that the lean path never touches)
+    const bool lean = plan.kernel != FM_K_NONE;
     const size_t f_vol = (volume || lean) ? 0 : (size_t)P1 * N;
     // both matrix-core options on: the last layer's convolution leaves the features' squared norms for the matcher (no pass of its own)
-    const bool mm_both = ctx->opt[DFE_OPT_CONV_MFMA] > 0 && dfe_feat_matching_mfma_takes(ctx, K, H1, W1, hWin, wWin) && layers[nlayers - 1].nOut <= 32 &&
-                         !layers[nlayers - 1].conn;
-    const size_t f_nrm = mm_both ? dfe_feat_matching_mfma_scratch(H1, W1, hWin, wWin) : 0;
+    const bool mm_both = ctx->opt[DFE_OPT_CONV_MFMA] > 0 && plan.kernel == FM_K_MFMA && layers[nlayers - 1].nOut <= 32 && !layers[nlayers - 1].conn;
+    const size_t f_nrm = mm_both ? fm_mfma_scratch(job) : 0;
     float *s_cn, *n1, *c0, *fa[2], *fb[2], *vol, *nrm;            // nrm: |a|^2 [H1][W1] | |b|^2 [H2][W2]
     rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
         s_cn = c.take<float>(f_cn); n1 = c.take<float>(f_n); c0 = c.take<float>(f_c);
@@ -108,32 +130,12 @@ extern "C" int dfe_version2_flow_pair_f32(dfe_ctx *ctx, const float *prev, const
         }
         DFE_REQUIRE(ctx, ha == H1 && wa == W1 && hb == H1 + hWin - 1 && wb == W1 + wWin - 1, DFE_E_SHAPE, "dfe_version2_flow_pair_f32: internal shape mismatch");
     }
-    if (!volume && (xflow || yflow || idx)) {
-        // nobody asked for the volume: matcher and decode in one kernel where the flat-tile matcher takes the shape (bit-identical to the
-        // volume path: the same sums, the same first minimum)
+    if (lean) {
         DfeStageScope st(ctx, DFE_STAGE_MATCH);
-        bool done = false;
-        if (norms_ready) {
-            rc = dfe_feat_matching_mfma(ctx, ia, ib, K, H1, W1, hWin, wWin, nrm, nullptr, (long long *)idx, xflow, yflow, &done, true);
-            if (rc || done) return rc;
-        }
-        rc = dfe_feat_matching_flat_argmin(ctx, ia, ib, K, H1, W1, hWin, wWin, (long long *)idx, xflow, yflow, &done);
-        if (rc || done) return rc;
-        DFE_REQUIRE(ctx, !lean, DFE_E_UNSUPPORTED, "dfe_version2_flow_pair_f32: the matcher declined a shape its predicate took");
+        job.in1 = ia; job.in2 = ib; job.norms = norms_ready ? nrm : nullptr; job.norms_ready = norms_ready;
+        return dfe_fm_run(ctx, job);
     }
-    {
-        DfeStageScope st(ctx, DFE_STAGE_MATCH);
-        rc = dfe_spatial_matching_dispatch(ctx, ia, ib, K, H1, W1, hWin, wWin, vol);
-        if (rc) return rc;
-    }
-    {
-        DfeStageScope st(ctx, DFE_STAGE_EXTRACT);
-        if (xflow || yflow || idx) {
-            hipLaunchKernelGGL(v2_argmin_decode_kernel, dim3(dfe_grid1d(P1, 4, 65535 * 16)), dim3(256), 0, ctx->stream, vol, P1, N, wWin, lWin, tWin, (long long *)idx, xflow, yflow);
-            DFE_LAUNCH_CHECK(ctx);
-        }
-    }
-    return DFE_OK;
+    return v2_volume_argmin(ctx, ia, ib, K, H1, W1, hWin, wWin, vol, (long long *)idx, xflow, yflow);
 }
 
 // nn.SpatialMatching(maxh, maxw) followed by `output:min(3)` and the decode of version2/test.lua:45-51 (radial_opticalflow_groundtruth.lua:88-100
@@ -145,25 +147,16 @@ extern "C" int dfe_spatial_matching_argmin_f32(dfe_ctx *ctx, const float *in1, c
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, in1 && in2 && (idx || xflow || yflow), DFE_E_ARG, "dfe_spatial_matching_argmin_f32: NULL argument");
     DFE_REQUIRE(ctx, K > 0 && H1 > 0 && W1 > 0 && maxh > 0 && maxw > 0, DFE_E_ARG, "dfe_spatial_matching_argmin_f32: K=%d %dx%d window %dx%d", K, H1, W1, maxh, maxw);
-    const int lWin = dfe_window_lead(maxw), tWin = dfe_window_lead(maxh);
-    bool done = false;
+    FmJob job = fm_job(FM_ARGMIN, in1, in2, K, H1, W1, maxh, maxw);
+    job.idx = (long long *)idx; job.xflow = xflow; job.yflow = yflow;
     {
         DfeStageScope st(ctx, DFE_STAGE_MATCH);
-        int rc = dfe_feat_matching_flat_argmin(ctx, in1, in2, K, H1, W1, maxh, maxw, (long long *)idx, xflow, yflow, &done);
-        if (rc || done) return rc;
+        FmPick pk;
+        int rc = dfe_fm_run(ctx, job, &pk);
+        if (rc || pk.kernel != FM_K_NONE) return rc;
     }
-    const long long P1 = (long long)H1 * W1;
-    const int N = maxh * maxw;
     void *scr = nullptr;
-    int rc = dfe_scratch(ctx, (size_t)P1 * N * sizeof(float), &scr);
+    int rc = dfe_scratch(ctx, (size_t)H1 * W1 * maxh * maxw * sizeof(float), &scr);
     if (rc) return rc;
-    {
-        DfeStageScope st(ctx, DFE_STAGE_MATCH);
-        rc = dfe_spatial_matching_dispatch(ctx, in1, in2, K, H1, W1, maxh, maxw, (float *)scr);
-        if (rc) return rc;
-    }
-    DfeStageScope st(ctx, DFE_STAGE_EXTRACT);
-    hipLaunchKernelGGL(v2_argmin_decode_kernel, dim3(dfe_grid1d(P1, 4, 65535 * 16)), dim3(256), 0, ctx->stream, (const float *)scr, P1, N, maxw, lWin, tWin, (long long *)idx, xflow, yflow);
-    DFE_LAUNCH_CHECK(ctx);
-    return DFE_OK;
+    return v2_volume_argmin(ctx, in1, in2, K, H1, W1, maxh, maxw, (float *)scr, (long long *)idx, xflow, yflow);
 }

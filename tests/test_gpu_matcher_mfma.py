@@ -63,7 +63,7 @@ def _first_min_index(vol):
 
 
 def _mfma_kernel(K, mh, volume):
-    """the instantiation dfe_feat_matching_mfma launches (feat_matching_mfma.hip): the volume form stages 8 planes, the arg-min form 16 where K % 16 == 0"""
+    """the instantiation dfe_fm_launch_mfma launches (feat_matching_mfma.hip): the volume form stages 8 planes, the arg-min form 16 where K % 16 == 0"""
     if volume:
         return "fmm_kernel<%d,%d,false>" % (mh, mh)
     return "fmm_kernel<%d,%d,true,%d>" % (mh, mh, 16 if K % 16 == 0 else 8)
@@ -179,7 +179,7 @@ LIMIT = [
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("K,H1,W1,takes", LIMIT)
 def test_matrix_core_matcher_size_limit(dfe, cuda, K, H1, W1, takes):
-    """dfe_feat_matching_mfma_takes admits K H2 W2 < 2^30 floats of in2 (the LDS-DMA requests are 32-bit byte offsets from the map's base;
+    """fm_try_mfma (csrc/fm_select.h) admits K H2 W2 < 2^30 floats of in2 (the LDS-DMA requests are 32-bit byte offsets from the map's base;
     the guard once admitted 2^31, where they wrap inside the buffer: wrong costs, no fault).  On both sides of the limit, one arg-min launch:
     the kernel named, and the index against the float64 first minimum on the first and the last output rows (whose planes lie furthest
     into in2).  About 4.3 GB per map; freed at the end."""
