@@ -141,7 +141,7 @@ PROTOTYPES = {
     "dfe_cascading_add_backward_f32": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_i32p, C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "dfe_cascade_ring_f32": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_i32p] + [C.c_int] * 5 + [C.c_void_p]),
     "dfe_polar_grid_c2p_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
-    "dfe_polar_grid_p2c_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_float] * 4 + [C.c_void_p]),
+    "dfe_polar_grid_p2c_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_float] * 2 + [C.c_double, C.c_float, C.c_void_p]),   # rmax: a double
     "dfe_warp_bilinear_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dfe_flow_to_depth_radial": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "dfe_marginal_sum_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),

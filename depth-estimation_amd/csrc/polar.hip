@@ -147,13 +147,13 @@ int dfe_polar_grid_c2p_f32(dfe_ctx *ctx, int wsrc, int hsrc, int wdst, int hdst,
     return DFE_OK;
 }
 
-int dfe_polar_grid_p2c_f32(dfe_ctx *ctx, int wsrc, int hsrc, int wdst, int hdst, float xcenter, float ycenter, float rmax,
+int dfe_polar_grid_p2c_f32(dfe_ctx *ctx, int wsrc, int hsrc, int wdst, int hdst, float xcenter, float ycenter, double rmax,
                            float alpha, float *mask) {
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, mask && wdst > 0 && hdst > 0 && rmax > 0 && alpha > 0, DFE_E_ARG, "dfe_polar_grid_p2c_f32: bad argument");
     const float pi2 = (float)(2 * M_PI);                                                   // :58
     const float kx = (float)((double)wsrc / (2 * M_PI));                                   // :59
-    const float ky = (float)((double)hsrc / pow((double)rmax, 1.0 / (double)alpha));       // :60
+    const float ky = (float)((double)hsrc / pow(rmax, 1.0 / (double)alpha));               // :59 (rmax a Lua number: a double up to here)
     const float invalpha = (float)(1.0 / (double)alpha) * 0.5f;                            // :70
     hipLaunchKernelGGL(p2c_kernel, dim3(dfe_grid1d((long long)hdst * wdst)), dim3(256), 0, ctx->stream, wdst, hdst, xcenter, ycenter, kx, ky,
                        pi2, invalpha, mask);

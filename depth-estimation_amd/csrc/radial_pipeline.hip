@@ -552,6 +552,8 @@ static int radial_flow_depth_pair(dfe_ctx *ctx, const char *fn, bool sub, const 
     stage.reset(new DfeStageScope(ctx, DFE_STAGE_EXTRACT));
     {   // 4. polar flow -> cartesian -> depth (getP2CMaskOF + flow2depth with center2 = e2 * getKOutput)
         const double kOut = (double)hm / (double)H;
+        // newRMax stays a double up to ky, as in the reference (a Lua number: polar.lua:25, cartesian2polar.lua:59; only the finished ky
+        // is narrowed to float, :67) -- dfe_polar_grid_p2c_f32 takes it as a double for the same reason
         const double nrmax = rmax * kOut;
         const float pi2 = (float)(2 * M_PI);
         const float kx = (float)((double)W / (2 * M_PI));

@@ -468,9 +468,11 @@ int dfe_cascade_ring_f32(dfe_ctx *ctx, const float *const *prob, const int *rati
 int dfe_polar_grid_c2p_f32(dfe_ctx *ctx, int wsrc, int hsrc, int wdst, int hdst, float xcenter,
                            float ycenter, int lpadding, int rpadding, float rmax, float alpha,
                            float *mask);
-/* replaces: getP2CMask radial/cartesian2polar.lua:51-89.  mask [2][hdst][wdst]. */
+/* replaces: getP2CMask radial/cartesian2polar.lua:51-89.  mask [2][hdst][wdst].  rmax is a double: the reference computes
+ *   ky = hsrc / rmax^(1/alpha) in Lua numbers (:59) and getP2CMaskOF hands it a scaled, non-integer radius (polar.lua:25);
+ *   only the finished ky becomes a float. */
 int dfe_polar_grid_p2c_f32(dfe_ctx *ctx, int wsrc, int hsrc, int wdst, int hdst, float xcenter,
-                           float ycenter, float rmax, float alpha, float *mask);
+                           float ycenter, double rmax, float alpha, float *mask);
 /* replaces: cartesian2polar(img, mask) = image.warp(img, mask, 'bilinear', false)
  *   radial/cartesian2polar.lua:91-93.  img [C][H][W], mask [2][Hd][Wd] (plane 0 = y, 1 = x, absolute,
  *   0-based), out [C][Hd][Wd]; coordinates outside the image are clamped. */

@@ -902,12 +902,13 @@ void orc_polar_grid_c2p(int wsrc, int hsrc, int wdst, int hdst, float xc, float 
         }
     }
 }
-void orc_polar_grid_p2c(int wsrc, int hsrc, int wdst, int hdst, float xc, float yc, float rmax,
+void orc_polar_grid_p2c(int wsrc, int hsrc, int wdst, int hdst, float xc, float yc, double rmax,
                         float alpha, float *mask) {
-    /* ref: radial/cartesian2polar.lua:51-89 */
+    /* ref: radial/cartesian2polar.lua:51-89.  kx and ky are computed in Lua numbers (:58-59: rmax, scaled and non-integer when it
+     * comes from getP2CMaskOF, stays a double) and narrowed to float by the inline C (:66-67) */
     float pi2 = (float)(2 * M_PI);
     float kx = (float)((double)wsrc / (2 * M_PI));
-    float ky = (float)((double)hsrc / pow((double)rmax, 1.0 / (double)alpha));
+    float ky = (float)((double)hsrc / pow(rmax, 1.0 / (double)alpha));
     float invalpha = (float)(1.0 / (double)alpha) * 0.5f;
     float *m0 = mask, *m1 = mask + (size_t)hdst * wdst;
     for (int i = 0; i < hdst; ++i)

@@ -169,7 +169,7 @@ void orc_flow_to_depth_ardrone(const float *xflow, const float *mask, int H, int
 void orc_polar_grid_c2p(int wsrc, int hsrc, int wdst, int hdst, float xc, float yc,
                         int lpad, int rpad, float rmax, float alpha, float *mask /*[2][hdst][wdst+lpad+rpad]*/);
 void orc_polar_grid_p2c(int wsrc, int hsrc, int wdst, int hdst, float xc, float yc,
-                        float rmax, float alpha, float *mask /*[2][hdst][wdst]*/);
+                        double rmax /* a Lua number up to ky (:59) */, float alpha, float *mask /*[2][hdst][wdst]*/);
 /* A14 absolute-coordinate bilinear warp (image.warp(img,mask,'bilinear',false)).
  * ref: radial/cartesian2polar.lua:91-93.  Border policy is un-vendored: this restatement
  * clamps coordinates to the image (parity unpinned). */

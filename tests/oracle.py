@@ -73,7 +73,7 @@ def lib():
             "orc_flow_to_depth_ardrone": (None, [f32p, f32p, C.c_int, C.c_int, C.c_float, f32p, f32p]),
             "orc_marginal_sum": (None, [f32p, C.c_int64, C.c_int, C.c_int, f32p]),
             "orc_polar_grid_c2p": (None, [C.c_int] * 4 + [C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.c_float, f32p]),
-            "orc_polar_grid_p2c": (None, [C.c_int] * 4 + [C.c_float] * 4 + [f32p]),
+            "orc_polar_grid_p2c": (None, [C.c_int] * 4 + [C.c_float] * 2 + [C.c_double, C.c_float, f32p]),
             "orc_warp_bilinear": (None, [f32p] + [C.c_int] * 3 + [f32p, C.c_int, C.c_int, f32p]),
             "orc_postprocess_image": (C.c_int, [f32p, f32p] + [C.c_int] * 4 + [f32p]),
             "orc_enlarge_mask": (None, [f32p] + [C.c_int] * 4),
