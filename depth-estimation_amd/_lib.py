@@ -12,7 +12,7 @@ DFE_MAX_RATIOS = 10
 # keys of dfe_set_option / dfe_get_option (include/dfe.h)
 OPTION_KEYS = ("cascade_px", "fine_fuse", "mid_fuse", "fine_nq", "mid_nq", "prep_tiles", "xpose", "xpose_nt", "soft_epilogue", "conv_batch", "conv_nt10",
                "fm64", "fm_rows", "sweep_ovh", "sweep_blocks", "debug_arena", "fm_flat", "fm_split", "conv_narrow", "conv_mfma", "fm_mfma", "arena_contig", "graphs",
-               "cv_novol", "conv_nt")
+               "cv_novol", "conv_nt", "cv_i8")
 
 c_f32p = C.POINTER(C.c_float)
 c_i64p = C.POINTER(C.c_int64)
@@ -74,6 +74,7 @@ PROTOTYPES = {
     "dfe_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "dfe_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
     "dfe_last_kernel": (C.c_char_p, [C.c_void_p]),
+    "dfe_flow_last_path": (C.c_int, [C.c_void_p, c_i32p]),
     "dfe_ssd_cost_volume_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]),
     "dfe_ssd_cost_volume_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_float, C.c_void_p]),
     "dfe_flow_depth_pair_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 5),

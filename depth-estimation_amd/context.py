@@ -65,6 +65,12 @@ class Context:
     def last_kernel(self):
         return lib().dfe_last_kernel(self.handle).decode()
 
+    def flow_last_path_i8(self):
+        """True if the int8 matrix-core kernel produced the last single-scale flow step's result (synchronises)."""
+        v = C.c_int()
+        self.check(lib().dfe_flow_last_path(self.handle, C.byref(v)))
+        return bool(v.value)
+
     def close(self):
         if self.handle:
             lib().dfe_ctx_destroy(self.handle)

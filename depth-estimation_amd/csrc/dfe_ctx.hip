@@ -15,6 +15,7 @@ const DfeOptName dfe_opt_names[DFE_NOPT] = {
     {"debug_arena", "DFE_DEBUG_ARENA", false}, {"fm_flat", "DFE_FM_FLAT", false},             {"fm_split", "DFE_FM_SPLIT", false},
     {"conv_narrow", "DFE_CONV_NARROW", false}, {"conv_mfma", "DFE_CONV_MFMA", false},         {"fm_mfma", "DFE_FM_MFMA", false},
     {"arena_contig", "DFE_ARENA_CONTIG", false}, {"cv_novol", "DFE_CV_NOVOL", false},       {"conv_nt", "DFE_CONV_NT", false},
+    {"cv_i8", "DFE_CV_I8", false},
 };
 
 int dfe_fail(dfe_ctx *ctx, int code, const char *fmt, ...) {
@@ -192,7 +193,7 @@ void dfe_ctx_destroy(dfe_ctx *ctx) {
     if (ctx->ms_graph.exec) (void)hipGraphExecDestroy(ctx->ms_graph.exec);
     for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
     for (const dfe_ctx::StageEvent &e : ctx->stage_events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    for (DfeBuf *b : {&ctx->scratch, &ctx->scratch_plain, &ctx->cn_coef, &ctx->ingest, &ctx->aux})
+    for (DfeBuf *b : {&ctx->scratch, &ctx->scratch_plain, &ctx->cn_coef, &ctx->ingest, &ctx->aux, &ctx->i8_verdict})
         if (b->p) (void)hipFree(b->p);
     for (int i = 0; i < DFE_NSLOT; ++i) {
         if (ctx->slot[i].p) (void)hipFree(ctx->slot[i].p);
@@ -298,6 +299,18 @@ int dfe_set_cost_volume_tile(dfe_ctx *ctx, int tyq) {
 }
 
 const char *dfe_last_kernel(const dfe_ctx *ctx) { return ctx ? ctx->last_kernel : ""; }
+
+int dfe_flow_last_path(dfe_ctx *ctx, int *i8_taken) {
+    DFE_ENTER(ctx);
+    DFE_REQUIRE(ctx, i8_taken, DFE_E_ARG, "dfe_flow_last_path: i8_taken is NULL");
+    *i8_taken = 0;
+    DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (!ctx->i8_last || !ctx->i8_verdict.p) return DFE_OK;
+    unsigned v = 1u;
+    DFE_HIP(ctx, hipMemcpy(&v, (const unsigned *)ctx->i8_verdict.p + ctx->i8_seq % 3, sizeof(v), hipMemcpyDeviceToHost));
+    *i8_taken = v ? 0 : 1;
+    return DFE_OK;
+}
 
 static int dfe_opt_find(const char *key) {
     if (!key) return -1;

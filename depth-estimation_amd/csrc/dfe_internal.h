@@ -37,6 +37,7 @@ enum DfeOpt {
     DFE_OPT_ARENA_CONTIG,     // scratch arena from physically contiguous memory (hipDeviceMallocContiguous; 0: plain hipMalloc)
     DFE_OPT_CV_NOVOL,         // single-scale flow step without its cost volume (volume-free sweep; 0: build the volume, finalize reads it)
     DFE_OPT_CONV_NT,          // batched convolution: n > 0 = n output planes per thread where nOut % n == 0 and <kW, n> is instantiated (tests)
+    DFE_OPT_CV_I8,            // volume-free flow step on the int8 matrix cores where the frames turn out byte-valued (ssd_flow_i8.hip; 0: the float sweep only)
     DFE_NOPT
 };
 struct DfeOptName { const char *key; const char *env; bool env_presence_means_zero; };
@@ -78,6 +79,11 @@ struct dfe_ctx {
     int cn_key[4] = {0, 0, 0, 0};     // H, W, C, k of the plane that is there (k = 0: none)
     float cn_key_kn[33] = {};
     int *dflag = nullptr;             // one device int for error flags raised by kernels
+    DfeBuf i8_verdict;                // three device words taken in turn: word (i8_seq % 3) != 0 = the frames of int8 flow step i8_seq were NOT byte-valued
+                                      // (ssd_flow_i8.hip; a step's pack kernel clears the next step's word, so no launch resets them); the ctx's
+                                      // own, so that dfe_flow_last_path can read it whatever has carved the arena since
+    unsigned i8_seq = 0;              // number of the last int8 flow step
+    bool i8_last = false;             // the last flow step launched the int8 kernel (and the gated float sweep behind it)
     char err[512] = {0};
     // optional per-launch timing of the cost-volume kernel (dfe_profile_enable)
     bool profile = false;
@@ -324,6 +330,22 @@ template <class L> int dfe_scratch_carve(dfe_ctx *ctx, L &&lay, bool plain = fal
     lay(c);
     return DFE_OK;
 }
+
+// ssd_flow_i8.hip
+// device buffers of the int8 flow step: packed frames and patch-sum planes (carved by the caller), this call's verdict word and the next one's
+struct DfeFlowI8Bufs {
+    unsigned *pk0, *pk1, *verdict, *verdict_next;
+    int *s0, *s1k;
+    size_t px;            // elements of each of pk0, pk1, s0, s1k
+    int Wp, nstrips;
+};
+struct CvFuseArgs;
+struct CvNovolArgs;
+// the sizes for an H x W frame (k = 7, 33 x 33) into *b; 0 = the kernel does not take this shape
+size_t dfe_flow_i8_plan(int H, int W, DfeFlowI8Bufs *b);
+// pack + patch sums + the int8 sweep: records and fallback plane as the float sweep leaves them IF the frames are byte-valued (else
+// nothing: *b.verdict says so to the gated float sweep that the caller launches behind it)
+int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const DfeFlowI8Bufs &b, const CvFuseArgs &fa, const CvNovolArgs &nv);
 
 // ssd_cost_volume.hip
 // cost volume of raw frames into `out`; H = rows visible to this call, plane = channel stride

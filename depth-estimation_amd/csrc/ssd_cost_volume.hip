@@ -2040,6 +2040,55 @@ int cv_frames_dispatch(dfe_ctx *ctx, const float *I0, const float *I1, int C, in
     return launch_cv_ref(ctx, a);
 }
 
+// The float sweep behind the int8 kernel (ssd_flow_i8.hip): ssd_cv_rowimg_flow_kernel's body behind a gate -- every block returns at entry
+// unless the pack kernel found a value that is not an integer in 0..255.  A kernel of its own, so that the ungated sweep's code is what it
+// was (its register allocation sits on the edge: tests/test_novol_guard_cpu.py).
+template <int C, int K, int TX>
+__global__ __launch_bounds__(1024) void ssd_cv_rowimg_flow_gated_kernel(const float *__restrict__ I0, const float *__restrict__ I1, CvTiledArgs p,
+                                                                        CvFuseArgs fa, CvNovolArgs nv, const unsigned *__restrict__ verdict) {
+    if (!*verdict) return;   // (block-uniform, in front of the first barrier)
+    rowimg_body<C, K, TX, true, true, true, 1089, false, true>(I0, I1, nullptr, p, fa, nv);
+}
+// its plan and launch: the geometry of launch_cv_rowimg_sweep's volume-free branch (3 channels, k = 7, 33 x 33; the tuning options included)
+struct FlowSweepGatedPlan { CvTiledArgs a; int nblk; size_t lds_bytes; };
+static bool plan_flow_sweep_gated(const dfe_ctx *ctx, int H, int W, FlowSweepGatedPlan *pl) {
+    using G = RowimgGeom<3, 7, 8>;
+    const int Ho = H - 38, Wo = W - 38;
+    if (Ho < 1 || Wo < 8 || DFE_TL) return false;
+    CvTiledArgs &a = pl->a;
+    a.plane = (long long)H * W;
+    a.H = H; a.W = W; a.hWin = 33; a.wWin = 33; a.Ho = Ho; a.Wo = Wo;
+    a.lrows = G::R;
+    a.lcols = G::lcols33;
+    a.pitch = G::pitch33;
+    const int ncols = dfe_cdiv(Wo, 8);
+    a.seg_rows = 0;
+    a.scale = 1.f;
+    a.sw_ovh = kSweepOvh; a.sw_min = kSweepMin;
+    pl->nblk = sweep_blocks(ctx, ncols, Ho);
+    if (ctx->opt[DFE_OPT_SWEEP_OVH] >= 0) a.sw_ovh = ctx->opt[DFE_OPT_SWEEP_OVH];
+    if (ctx->opt[DFE_OPT_SWEEP_BLOCKS] >= 0) pl->nblk = ctx->opt[DFE_OPT_SWEEP_BLOCKS];
+    if (pl->nblk < 1 || (long long)(Ho + a.sw_ovh) * ncols * pl->nblk >= (1ll << 31)) return false;
+    a.tile0_off = G::sweep_tile0_off;
+    a.stage_off = G::sweep_stage_off;
+    a.stage_len = G::stage_len33;
+    a.chunk0 = 0;
+    pl->lds_bytes = a.stage_off + (size_t)2 * a.stage_len * sizeof(float) + 2 * DFE_REC * sizeof(float);
+    return pl->lds_bytes <= 160 * 1024;
+}
+static int launch_flow_sweep_gated(dfe_ctx *ctx, const float *I0, const float *I1, const FlowSweepGatedPlan &pl, const CvFuseArgs &fa,
+                                   const CvNovolArgs &nv, const unsigned *verdict) {
+    auto kern = ssd_cv_rowimg_flow_gated_kernel<3, 7, 8>;
+    DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
+    {
+        DfeProfScope prof(ctx, true);
+        hipExtLaunchKernelGGL(kern, dim3(pl.nblk, 1), dim3(1024), pl.lds_bytes, ctx->stream, prof.a, prof.b, 0, I0, I1, pl.a, fa, nv, verdict);
+    }
+    DFE_LAUNCH_CHECK(ctx);
+    ctx->last_kernel = "ssd_cv_rowimg_kernel+fused_tail+novol";
+    return DFE_OK;
+}
+
 extern "C" {
 // Bumped whenever a change can alter what the cost-volume kernels read or write: profiles/traffic_*.json carries the revision
 // its PMC counters were taken with, and bench.py reports `traffic` only when the two agree.
@@ -2085,19 +2134,42 @@ static float float_at_or_below(double t) {
 // The flow step without its cost volume (option "cv_novol", default on): the volume-free fused sweep leaves records and, for the rare
 // pixels whose lead cells hold fewer than M hits, the fallback plane; one launch for the whole pair (no bands: 112 B of scratch per
 // pixel instead of 4356), then the record finalize.  Returns DFE_OK with *done = false where the sweep does not apply.
+// Option "cv_i8" (default on): the frames are packed to bytes and checked on the device; the int8 matrix-core kernel (ssd_flow_i8.hip)
+// leaves the same records if every value is an integer in 0..255 and the gated float sweep, launched behind it, if not -- one of the
+// two returns at entry, and no host round trip decides.
 static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, int hWin, int wWin, double thr, const TailOut &out,
                                const DfePairDepth *pd, bool *pd_done, bool *done) {
     constexpr int K = 7;
     *done = false;
+    ctx->i8_last = false;
     const int Ho = H - K + 1 - hWin + 1, Wo = W - K + 1 - wWin + 1;
     const long long P = (long long)Ho * Wo;
     if (Wo < 8 || P >= (1ll << 31) || (pd && (long long)pd->H * pd->W >= (1ll << 31))) return DFE_OK;   // (the finalize's 32-bit pixel arithmetic)
     const size_t nrec = (size_t)dfe_cdiv(Wo, 8) * Ho;   // tile-row records
+    DfeFlowI8Bufs ib{};
+    FlowSweepGatedPlan gp;
+    const bool i8 = hWin == 33 && wWin == 33 && ctx->opt_bool(DFE_OPT_CV_I8, true) && dfe_flow_i8_plan(H, W, &ib) != 0 && plan_flow_sweep_gated(ctx, H, W, &gp);
+    if (i8) {
+        if (!ctx->i8_verdict.p) {
+            int rc = dfe_grow(ctx, ctx->i8_verdict, 256, "i8 verdict");
+            if (rc) return rc;
+            DFE_HIP(ctx, hipMemsetAsync(ctx->i8_verdict.p, 0, 256, ctx->stream));
+        }
+        ++ctx->i8_seq;
+        ib.verdict = (unsigned *)ctx->i8_verdict.p + ctx->i8_seq % 3;
+        ib.verdict_next = (unsigned *)ctx->i8_verdict.p + (ctx->i8_seq + 1) % 3;
+    }
     CvFuseArgs fa{};
     CvNovolArgs nv;
     int rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
         fa.rec = c.take<float>(nrec * DFE_REC);       // [tile column][output row][DFE_REC]
         nv.fb = c.take<float>(nrec * 8 * DFE_FB);     // [tile column][output row][8][DFE_FB]
+        if (i8) {
+            ib.pk0 = c.take<unsigned>(ib.px);
+            ib.pk1 = c.take<unsigned>(ib.px);
+            ib.s0 = c.take<int>(ib.px);
+            ib.s1k = c.take<int>(ib.px);
+        }
     });
     if (rc) return rc;
     fa.rec_rows = Ho;
@@ -2108,8 +2180,17 @@ static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, i
     bool handled = false;
     {
         DfeStageScope match(ctx, DFE_STAGE_MATCH);
-        rc = launch_cv_rowimg_sweep<3, 7, 8, true>(ctx, I0, I1, H, W, (long long)H * W, hWin, wWin, nullptr, &fa, &handled, &nv);
-        if (rc || !handled) return rc;
+        if (i8) {
+            rc = dfe_flow_i8_launch(ctx, I0, I1, H, W, ib, fa, nv);
+            if (rc) return rc;
+            rc = launch_flow_sweep_gated(ctx, I0, I1, gp, fa, nv, ib.verdict);
+            if (rc) return rc;
+            ctx->i8_last = true;
+            handled = true;
+        } else {
+            rc = launch_cv_rowimg_sweep<3, 7, 8, true>(ctx, I0, I1, H, W, (long long)H * W, hWin, wWin, nullptr, &fa, &handled, &nv);
+            if (rc || !handled) return rc;
+        }
     }
     *done = true;
     DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);

@@ -1,0 +1,396 @@
+// ssd_flow_i8.hip -- the single-scale flow step's sweep on the int8 matrix cores, for byte-valued frames (C = 3, k = 7, 33 x 33).
+//
+// For frames whose values are integers in 0..255 every partial sum of the SSD is an integer below 2^24: the float sweep
+// (ssd_cv_rowimg_flow_kernel) is exact on them and any exact integer evaluation gives the same bits.  With a' = a - 128, b' = b - 128
+//     cost(x, d) = S0(x) + S1(x + d) - 2 a'.b'
+// where a'.b' is a dot product over the 147 taps of the patch: v_mfma_i32_16x16x64_i8.
+//
+// Layout.  A frame is packed to 4 bytes per pixel (three channels - 128, one zero byte), row pitch Wp pixels, zero (a' = 0) beyond the
+// frame's width; the patch sums S0 / S1 are planes of the same pitch (the pack kernel makes both).  One wave owns a strip of 16 pixels (MFMA N side) of R
+// consecutive output rows; the 48 candidate columns q = n + dx of a displacement row are three tiles of 16 on the M side.  A lane (n, g)
+// of a result tile holds candidates q = 16 T + 4 g + i, i = 0..3, of ONE pixel n, so the running arg-min is lane-local.
+// K = 256 = 4 MFMAs: lane groups 0, 1 hold patch rows 0..3 (one per MFMA; left / right four pixels of the row), groups 2, 3 hold rows 3..6;
+// the frame-0 operand, which stays in registers for the whole strip, is zero in the duplicate row 3 and in the eighth pixel.  A frame-1
+// fragment of image rows (r .. r+3) at displacement row dy is the fragment of rows (r-1 .. r+2) at dy + 1: the four fragments of a tile
+// rotate through registers (the sweep is unrolled by four) and every step loads ONE new 16-byte piece per lane and tile.  With R = 2 the
+// same frame-1 fragments serve (row y, dy) and (row y + 1, dy - 1).
+//
+// Arg-min.  A lane keeps two running keys (i = 0, 1 and i = 2, 3): key = ((2 a'.b' - S1) << 8) + tiebreak, maximised; the plane holds
+// -(S1 << 8) + (1 - (q & 1)), so a key is ONE v_lshl_add of the MFMA result; the (dy, T) part of the tiebreak is relative: the running key
+// gains 2 after every tile, so an earlier candidate wins a tie.  |2 a'.b' - S1| < 2^23, 99 tiles x 2: the key fits 32 bits.  Candidates
+// outside 0 <= q - n <= 32 (first and third tile) are masked.  The four lane groups of a pixel are combined once, on (cost, index).
+//
+// What it leaves is what the float sweep leaves (cv_records.h): tile-row records, and for a pixel with fewer than M lead cells above the
+// threshold its first M hits in index order in the fallback plane -- found by a second sweep of that strip row which ranks the hits of
+// a tile with ballots and stops when every flagged pixel has M.
+//
+// The gate.  A block of the pack kernel that meets a value that is not an integer in 0..255 raises the step's verdict word; this kernel
+// returns at entry when it is set, the gated float sweep (ssd_cost_volume.hip) when it is clear.  A ctx has three such words, taken in
+// turn: the pack kernel of step i clears the word of step i + 1, so nothing has to be reset between calls.
+#include "dfe_internal.h"
+#include "cv_records.h"
+#include <climits>
+
+typedef int i8x16_t __attribute__((ext_vector_type(4)));   // 16 bytes of an MFMA operand / four i32 results
+
+struct I8Args {
+    const unsigned *pk0, *pk1;   // packed frames [H][Wp]
+    const int *s0, *s1k;         // patch sums of frame 0 (plain) and frame 1 (as the key's addend) [H][Wp]
+    const unsigned *verdict;     // != 0: the frames are not byte-valued
+    float *rec, *fb;             // records and fallback plane (cv_records.h)
+    float thr;
+    int M;
+    int Ho, Wo, Wp, nstrips, nrp, ncols;
+};
+
+constexpr int kI8Waves = 4;
+
+// ------------------------------------------------------------------------------------------
+// pack: float planes -> (c0 - 128, c1 - 128, c2 - 128, 0) per pixel and the 7 x 7 x 3 sums of squares, one 64 x 16 tile per block (read with
+// its 6-pixel halo); a block that meets a value that is not an integer in 0..255 raises the call's verdict word
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool i8_byte(float v, unsigned *b) {
+    const bool ok = v >= 0.f && v <= 255.f && v == truncf(v);   // (NaN fails every comparison; -0.0 is 0)
+    *b = ok ? (unsigned)((int)v - 128) & 255u : 0u;
+    return ok;
+}
+__device__ __forceinline__ int i8_sq(unsigned p) {
+    const int a = (int)(p << 24) >> 24, b = (int)(p << 16) >> 24, c = (int)(p << 8) >> 24;
+    return a * a + b * b + c * c;
+}
+constexpr int kPackW = 64, kPackH = 16, kPackLW = kPackW + 6, kPackLH = kPackH + 6;
+__global__ __launch_bounds__(256) void flow_i8_pack_kernel(const float *__restrict__ I0, const float *__restrict__ I1, int H, int W, long long plane, int Wp,
+                                                           unsigned *__restrict__ pk0, unsigned *__restrict__ pk1, int *__restrict__ s0, int *__restrict__ s1k,
+                                                           unsigned *__restrict__ verdict, unsigned *__restrict__ verdict_next) {
+    __shared__ int sq[kPackLH][kPackLW + 1];
+    __shared__ int hs[kPackLH][kPackW];
+    const float *I = blockIdx.z ? I1 : I0;
+    unsigned *pk = blockIdx.z ? pk1 : pk0;
+    const int tx0 = blockIdx.x * kPackW, ty0 = blockIdx.y * kPackH;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *verdict_next = 0u;   // (the NEXT call's word: no reset launch)
+    bool bad = false;
+    for (int e = threadIdx.x; e < kPackLH * kPackLW; e += 256) {
+        const int ly = e / kPackLW, lx = e - ly * kPackLW;
+        const int gy = ty0 + ly, gx = tx0 + lx;
+        unsigned p = 0u;
+        if (gy < H && gx < W) {
+            const float *s = I + (long long)gy * W + gx;
+            unsigned b0, b1, b2;
+            bad |= !i8_byte(s[0], &b0);
+            bad |= !i8_byte(s[plane], &b1);
+            bad |= !i8_byte(s[2 * plane], &b2);
+            p = b0 | (b1 << 8) | (b2 << 16);
+        }
+        if (ly < kPackH && lx < kPackW && gy < H && gx < Wp) pk[(long long)gy * Wp + gx] = p;
+        sq[ly][lx] = i8_sq(p);
+    }
+    const int any = __syncthreads_or(bad ? 1 : 0);
+    if (any && threadIdx.x == 0) atomicOr(verdict, 1u);
+    for (int e = threadIdx.x; e < kPackLH * kPackW; e += 256) {
+        const int ly = e / kPackW, lx = e - ly * kPackW;
+        hs[ly][lx] = sq[ly][lx] + sq[ly][lx + 1] + sq[ly][lx + 2] + sq[ly][lx + 3] + sq[ly][lx + 4] + sq[ly][lx + 5] + sq[ly][lx + 6];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < kPackH * kPackW; e += 256) {
+        const int ly = e / kPackW, lx = e - ly * kPackW;
+        const int gy = ty0 + ly, X = tx0 + lx;
+        if (gy >= H || X >= Wp) continue;
+        const int v = hs[ly][lx] + hs[ly + 1][lx] + hs[ly + 2][lx] + hs[ly + 3][lx] + hs[ly + 4][lx] + hs[ly + 5][lx] + hs[ly + 6][lx];
+        const long long o = (long long)gy * Wp + X;
+        if (blockIdx.z) s1k[o] = -(v << 8) + (1 - (X & 1));
+        else s0[o] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// the sweep of one strip (16 pixels) over R output rows
+// ------------------------------------------------------------------------------------------
+constexpr int kCostPitch = 33;   // floats per pixel of the wave's lead-cell image in LDS (32 candidates, odd pitch)
+template <int R> struct I8Lds {
+    float cost[R][16][kCostPitch];   // displacement row 0, tiles 0 and 1: cost[n][q]
+    float rec[R][2][DFE_REC];        // the strip's two tile-row records
+};
+
+template <int R, bool FB> struct I8Sweep {
+    static constexpr int NS = 33 + R - 1;
+    const I8Args &a;
+    const int lane, n, g, x0, y0;
+    i8x16_t A[3][4], B[R][4];
+    int best[R][2];
+    int sa[R];
+    int pen0[4], pen2[4];   // INT_MAX where the first / third tile's candidate 4 g + i lies inside 0 <= q - n <= 32, else INT_MIN
+    // FB
+    int cnt;
+    bool flagged;
+    float *fbp;
+    I8Lds<(FB ? 1 : R)> *lds;
+
+    __device__ __forceinline__ I8Sweep(const I8Args &a_, int lane_, int x0_, int y0_)
+        : a(a_), lane(lane_), n(lane_ & 15), g(lane_ >> 4), x0(x0_), y0(y0_) {}
+
+    __device__ __forceinline__ void load_operands() {
+        const int h = g & 1, up = g >> 1;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            pen0[i] = 4 * g + i >= n ? INT_MAX : INT_MIN;
+            pen2[i] = 4 * g + i <= n ? INT_MAX : INT_MIN;
+        }
+        // frame 0: patch rows (0..3 | 3..6) of pixel n, zero in the duplicate row 3 and in the eighth pixel
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const unsigned *p = a.pk0 + (y0 + r + 16 + t + 3 * up) * a.Wp + x0 + n + 16 + 4 * h;
+                i8x16_t v = *reinterpret_cast<const i8x16_t *>(p);
+                if (h) v[3] = 0;
+                if (up && t == 0) v = i8x16_t{0, 0, 0, 0};
+                B[r][t] = v;
+            }
+        // frame 1: the fragments of displacement row 0
+#pragma unroll
+        for (int T = 0; T < 3; ++T)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) A[T][t] = *reinterpret_cast<const i8x16_t *>(a.pk1 + (y0 + t + 3 * up) * a.Wp + x0 + 16 * T + n + 4 * h);
+    }
+
+    // one step: frame-1 rows y0 + s ..; PH = s mod 4, the rotation of the fragment registers
+    template <int PH> __device__ __forceinline__ void step(int s) {
+        const int h = g & 1, up = g >> 1;
+        const bool more = s + 1 < NS;
+        i8x16_t nx[3];
+        if (more) {   // the one new row of the next step's fragments (rows s + 4 | s + 7)
+#pragma unroll
+            for (int T = 0; T < 3; ++T) nx[T] = *reinterpret_cast<const i8x16_t *>(a.pk1 + (y0 + s + 4 + 3 * up) * a.Wp + x0 + 16 * T + n + 4 * h);
+        }
+        i8x16_t P[3];
+#pragma unroll
+        for (int T = 0; T < 3; ++T) P[T] = *reinterpret_cast<const i8x16_t *>(a.s1k + (y0 + s) * a.Wp + x0 + 16 * T + 4 * g);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int dy = s - r;
+            if ((unsigned)dy > 32u) continue;
+#pragma unroll
+            for (int T = 0; T < 3; ++T) {
+                i8x16_t D = {0, 0, 0, 0};
+#pragma unroll
+                for (int t = 0; t < 4; ++t) D = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][(t + PH) & 3], B[r][t], D, 0, 0, 0);
+                if constexpr (!FB) {
+                    int k[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        k[i] = (int)((unsigned)D[i] << 9) + P[T][i];
+                        if (T == 0) k[i] = min(k[i], pen0[i]);
+                        if (T == 2) k[i] = min(k[i], pen2[i]);
+                    }
+                    best[r][0] = max(max(best[r][0], k[0]), k[1]) + 2;
+                    best[r][1] = max(max(best[r][1], k[2]), k[3]) + 2;
+                    if (T < 2 && dy == 0) {   // the lead cells' row
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) lds->cost[r][n][16 * T + 4 * g + i] = (float)(sa[r] - (P[T][i] >> 8) - 2 * D[i]);
+                    }
+                    if (T == 1 && dy == 16) {   // the centre cell: dx = 16, q = 16 + n
+#pragma unroll
+                        for (int i = 0; i < 4; ++i)
+                            if (4 * g + i == n) {
+                                const int x = x0 + n;
+                                lds->rec[r][(x >> 3) & 1][DFE_REC_CENTRE + (x & 7)] = (float)(sa[r] - (P[T][i] >> 8) - 2 * D[i]);
+                            }
+                    }
+                } else {
+                    // rank this tile's hits of every flagged pixel in candidate order: lane groups below mine, then my own earlier ones
+                    bool hit[4];
+                    float cv[4];
+                    unsigned long long bal[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int m = 4 * g + i;
+                        cv[i] = (float)(sa[0] - (P[T][i] >> 8) - 2 * D[i]);
+                        bool valid = flagged;
+                        if (T == 0) valid = valid && m >= n;
+                        if (T == 2) valid = valid && m <= n;
+                        hit[i] = valid && cv[i] > a.thr;
+                        bal[i] = __builtin_amdgcn_ballot_w64(hit[i]);
+                    }
+                    const unsigned long long mine = 0x0001000100010001ull << n;
+                    const unsigned long long below = mine & ((1ull << (16 * g)) - 1ull);
+                    int k = cnt, tot = 0;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        k += __builtin_popcountll(bal[i] & below);
+                        tot += __builtin_popcountll(bal[i] & mine);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        if (hit[i]) {
+                            if (k < a.M) {
+                                fbp[2 * k] = cv[i];
+                                fbp[2 * k + 1] = (float)(dy * 33 + 16 * T + 4 * g + i - n + 1);
+                            }
+                            ++k;
+                        }
+                    }
+                    cnt += tot;
+                }
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int T = 0; T < 3; ++T) A[T][PH & 3] = nx[T];
+        }
+    }
+
+    __device__ __forceinline__ bool fb_done() const { return FB && __builtin_amdgcn_ballot_w64(flagged && cnt < a.M) == 0ull; }
+
+    __device__ __forceinline__ void run() {
+        for (int s = 0; s < NS; s += 4) {
+            if (fb_done()) break;
+            step<0>(s);
+            if (s + 1 >= NS) break;
+            step<1>(s + 1);
+            if (s + 2 >= NS) break;
+            step<2>(s + 2);
+            if (s + 3 >= NS) break;
+            step<3>(s + 3);
+        }
+    }
+};
+
+__device__ __forceinline__ void i8_lds_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+template <int R>
+__global__ __launch_bounds__(kI8Waves * 64) void ssd_flow_i8_kernel(I8Args a) {
+    if (*a.verdict) return;   // not byte-valued: the gated float sweep behind this launch does the step
+    __shared__ I8Lds<R> lds_all[kI8Waves];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int item = blockIdx.x * kI8Waves + wave;
+    if (item >= a.nstrips * a.nrp) return;   // (no block-wide barrier below: a wave works alone)
+    const int strip = item / a.nrp, rp = item - strip * a.nrp;
+    const int x0 = strip * 16, y0 = min(rp * R, a.Ho - R);   // (a short last group of rows is shifted upwards; it stores only its own rows)
+    const int n = lane & 15, g = lane >> 4;
+    I8Lds<R> *lds = &lds_all[wave];
+
+    I8Sweep<R, false> sw(a, lane, x0, y0);
+    sw.lds = lds;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        sw.best[r][0] = sw.best[r][1] = INT_MIN;
+        sw.sa[r] = a.s0[(y0 + r + 16) * a.Wp + x0 + n + 16];
+    }
+    for (int i = lane; i < R * 2 * DFE_REC; i += 64) (&lds->rec[0][0][0])[i] = 0.f;
+    i8_lds_fence();
+    sw.load_operands();
+    sw.run();
+    i8_lds_fence();
+
+    const int x = x0 + n;
+    const bool xin = x < a.Wo;
+    // the pixel's record slot: its tile column (the last one shifted inwards), position inside it
+    const int gi = x >> 3, xb = gi == a.ncols - 1 ? a.Wo - 8 : gi << 3, pos = x - xb, slot = gi & 1;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        // (cost, index) of the lane's two running keys, then of the pixel's four lane groups
+        long long kb = LLONG_MIN;
+#pragma unroll
+        for (int sl = 0; sl < 2; ++sl) {
+            const int bt = sw.best[r][sl] + (254 - 2 * 99);
+            const int u = 255 - (bt & 255), j = u >> 1, ib = u & 1;
+            const int dy = j / 3, T = j - 3 * dy;
+            const int d = dy * 33 + 16 * T + 4 * g + 2 * sl + ib - n;
+            const long long k64 = ((long long)(bt >> 8) << 12) | (long long)(4095 - d);
+            kb = k64 > kb ? k64 : kb;
+        }
+        {
+            long long o = __shfl_xor(kb, 16);
+            kb = o > kb ? o : kb;
+            o = __shfl_xor(kb, 32);
+            kb = o > kb ? o : kb;
+        }
+        const int E = (int)(kb >> 12), d = 4095 - (int)(kb & 4095);
+        // lead cells: lane l takes cells 2 (l & 3), + 1 of pixel l >> 2
+        const int pn = lane >> 2, pk = (lane & 3) * 2;
+        const float l0 = lds->cost[r][pn][pn + pk], l1 = lds->cost[r][pn][pn + pk + 1];
+        const unsigned long long m0 = __builtin_amdgcn_ballot_w64(l0 > a.thr), m1 = __builtin_amdgcn_ballot_w64(l1 > a.thr);
+        const int nl = __builtin_popcount((unsigned)(m0 >> (4 * n)) & 15u) + __builtin_popcount((unsigned)(m1 >> (4 * n)) & 15u);
+        const bool flag = xin && nl < a.M;
+        {
+            const int px = x0 + pn, pgi = px >> 3, pxb = pgi == a.ncols - 1 ? a.Wo - 8 : pgi << 3;
+            if (px < a.Wo) {
+                float *lp = &lds->rec[r][pgi & 1][DFE_REC_LEAD + (px - pxb) * DFE_REC_NLEAD + pk];
+                lp[0] = l0;
+                lp[1] = l1;
+            }
+        }
+        if (g == 0 && xin) {
+            float *rb = lds->rec[r][slot];
+            rb[2 * pos] = (float)(sw.sa[r] - E);
+            rb[2 * pos + 1] = __int_as_float(d);
+            rb[DFE_REC_FLAG + pos] = flag ? 1.f : 0.f;
+        }
+        // the centre cost was left at (x & 7) of its slot: move it to the pixel's position (differs only in a shifted last tile column)
+        i8_lds_fence();
+        float cen = 0.f;
+        if (g == 0 && xin) cen = lds->rec[r][slot][DFE_REC_CENTRE + (x & 7)];
+        i8_lds_fence();
+        if (g == 0 && xin) lds->rec[r][slot][DFE_REC_CENTRE + pos] = cen;
+        i8_lds_fence();
+        const int y = y0 + r;
+        if (y >= rp * R) {
+            for (int i = lane; i < 2 * DFE_REC; i += 64) {
+                const int sl = i >= DFE_REC ? 1 : 0, gg = 2 * strip + sl;
+                if (gg < a.ncols) a.rec[((long long)gg * a.Ho + y) * DFE_REC + (i - sl * DFE_REC)] = lds->rec[r][sl][i - sl * DFE_REC];
+            }
+            if (__builtin_amdgcn_ballot_w64(flag)) {   // rare: rank the hits of the flagged pixels over the whole window
+                I8Sweep<1, true> fs(a, lane, x0, y);
+                fs.sa[0] = sw.sa[r];
+                fs.cnt = 0;
+                fs.flagged = flag;
+                fs.fbp = a.fb + (((long long)gi * a.Ho + y) * 8 + pos) * DFE_FB;
+                fs.lds = nullptr;
+                fs.load_operands();
+                fs.run();
+                if (flag && g == 0)
+                    for (int j = 2 * min(fs.cnt, a.M); j < 2 * a.M; ++j) fs.fbp[j] = 0.f;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// host
+// ------------------------------------------------------------------------------------------
+size_t dfe_flow_i8_plan(int H, int W, DfeFlowI8Bufs *b) {
+    const int Ho = H - 38, Wo = W - 38;
+    DfeFlowI8Bufs p{};
+    if (Ho < 1 || Wo < 8) return 0;
+    p.nstrips = dfe_cdiv(Wo, 16);
+    p.Wp = 16 * p.nstrips + 64;   // candidate columns reach x0 + 54, frame-0 columns x0 + 38
+    if ((long long)(H + 1) * p.Wp >= (1ll << 29)) return 0;   // (32-bit offsets in the sweep)
+    p.px = (size_t)(H + 1) * p.Wp;
+    if (b) *b = p;
+    return p.px;
+}
+
+int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const DfeFlowI8Bufs &b, const CvFuseArgs &fa, const CvNovolArgs &nv) {
+    const int Ho = H - 38, Wo = W - 38;
+    hipLaunchKernelGGL(flow_i8_pack_kernel, dim3(dfe_cdiv(b.Wp, kPackW), dfe_cdiv(H, kPackH), 2), dim3(256), 0, ctx->stream, I0, I1, H, W, (long long)H * W,
+                       b.Wp, b.pk0, b.pk1, b.s0, b.s1k, b.verdict, b.verdict_next);
+    DFE_LAUNCH_CHECK(ctx);
+    I8Args a;
+    a.pk0 = b.pk0; a.pk1 = b.pk1; a.s0 = b.s0; a.s1k = b.s1k; a.verdict = b.verdict;
+    a.rec = fa.rec; a.fb = nv.fb; a.thr = nv.thr; a.M = nv.M;
+    a.Ho = Ho; a.Wo = Wo; a.Wp = b.Wp; a.nstrips = b.nstrips; a.ncols = dfe_cdiv(Wo, 8);
+    const int R = Ho >= 2 ? 2 : 1;
+    a.nrp = dfe_cdiv(Ho, R);
+    const int nblk = dfe_cdiv((long long)a.nstrips * a.nrp, kI8Waves);
+    {
+        DfeProfScope prof(ctx, true);
+        if (R == 2) hipExtLaunchKernelGGL(ssd_flow_i8_kernel<2>, dim3(nblk), dim3(kI8Waves * 64), 0, ctx->stream, prof.a, prof.b, 0, a);
+        else hipExtLaunchKernelGGL(ssd_flow_i8_kernel<1>, dim3(nblk), dim3(kI8Waves * 64), 0, ctx->stream, prof.a, prof.b, 0, a);
+    }
+    DFE_LAUNCH_CHECK(ctx);
+    ctx->last_kernel = "ssd_flow_i8_kernel";
+    return DFE_OK;
+}
