@@ -20,6 +20,8 @@ no CPU fallback -- a missing library or device raises.
     version2.getNetwork, getTrainerNetwork, decodeFlow, flowPair   (version2/network.lua, version2/test.lua)
     flowDepthPair, refineFlowSubpixel                   (not in the reference: the single-scale step in one call, and its
                                                         opt-in sub-pixel flow -- subpixel.py)
+    flowDepthPair(..., consistency=tol, gate=False), flowConsistency   (not in the reference: the step in both directions with a
+                                                        forward-backward occlusion mask, and that check on any two flow fields -- subpixel.py)
     radialFlowDepth(..., subpixel=True), refineRadialFlowSubpixel   (not in the reference: sub-pixel radial flow -- radial.py)
     getModel(geometry).forwardFlow                      (a trained single-scale model per frame pair in one call,
                                                         output_extraction_method 'max' or 'mean' -- network.py)
@@ -48,7 +50,7 @@ from .opticalflow_model import (  # noqa: F401
     rgb2y,
 )
 from . import version2  # noqa: F401
-from .subpixel import flowDepthPair, refineFlowSubpixel  # noqa: F401
+from .subpixel import flowDepthPair, refineFlowSubpixel, flowConsistency  # noqa: F401
 from .multiscale import CascadingAddTable, MultiscaleModel, MultiscalePrefilter, getModelMultiscale, getMultiscalePrefilter  # noqa: F401
 from .network import getFilter, getFilterRadial, getModel, tables_random  # noqa: F401
 from .radial import (getRMax, getC2PMask, getP2CMask, cartesian2polar, flow2depth, getKOutput, getP2CMaskOF,  # noqa: F401

@@ -377,6 +377,13 @@ int dfe_flow_tail_run(dfe_ctx *ctx, const float *vol, int rows, int hWin, int wW
 int dfe_pair_border_depth(dfe_ctx *ctx, float *flow, float *scores, int H, int W, int pad_t, int pad_l, int Ho, int Wo, float cx,
                           float cy, float *depth, float *conf);
 
+// consistency.hip
+// the pair step forwards (subpixel != 0: its refined form), the backward flow (flow_bw, or the ctx's side buffer when NULL) and the
+// consistency kernel behind them: dfe_flow_depth_pair_fb_f32 behind its device guard, and _fb_u8 on the frames it has converted once
+int dfe_flow_pair_fb_run(dfe_ctx *ctx, const char *fn, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x,
+                         float foe_y, double extract_threshold, int subpixel, float tol, int gate, float *flow, float *scores, float *depth,
+                         float *depth_conf, float *flow_bw, float *mask, float *err);
+
 // feat_matching_dispatch.hip -- nn.SpatialMatching on feature maps.  The one rule: a kernel is chosen by fm_select (fm_select.h); a launcher
 // (dfe_fm_launch_*, one per kernel family, geometry from the FmPick) never declines
 static inline FmEnv dfe_fm_env(const dfe_ctx *c) {

@@ -185,6 +185,21 @@ int dfe_flow_depth_pair_subpixel_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8
     return dfe_flow_depth_pair_subpixel_f32(ctx, f0, f1, C, H, W, k, hWin, wWin, foe_x, foe_y, extract_threshold, flow, scores, depth, depth_conf);
 }
 
+// the pair step in both directions with their consistency (consistency.hip): each frame is converted ONCE, both directions read the float planes
+int dfe_flow_depth_pair_fb_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x,
+                              float foe_y, double extract_threshold, float scale, int subpixel, float tol, int gate, float *flow, float *scores,
+                              float *depth, float *depth_conf, float *flow_bw, float *mask, float *err) {
+    DFE_ENTER(ctx);
+    DFE_REQUIRE(ctx, I0 && I1, DFE_E_ARG, "dfe_flow_depth_pair_fb_u8: NULL frame");
+    DFE_REQUIRE(ctx, C > 0 && H > 0 && W > 0 && scale > 0, DFE_E_ARG, "dfe_flow_depth_pair_fb_u8: C=%d %dx%d scale=%g", C, H, W, (double)scale);
+    DFE_REQUIRE(ctx, mask && tol >= 0.f, DFE_E_ARG, "dfe_flow_depth_pair_fb_u8: mask %s, tol=%g must be >= 0", mask ? "given" : "is NULL", (double)tol);
+    float *f0 = nullptr, *f1 = nullptr;
+    int rc = ingest_pair(ctx, I0, I1, (long long)C * H * W, scale, &f0, &f1);
+    if (rc) return rc;
+    return dfe_flow_pair_fb_run(ctx, "dfe_flow_depth_pair_fb_u8", f0, f1, C, H, W, k, hWin, wWin, foe_x, foe_y, extract_threshold, subpixel, tol, gate, flow,
+                                scores, depth, depth_conf, flow_bw, mask, err);
+}
+
 // ---- pipelined ingest: host frames of pair i+1 travel while pair i computes -------------------------------------------------------
 // What the measurements on this stack say (tools/pipe_probe.py, pipe_probe2.py; profiles/r05_n_*):
 //   * asynchronous copies from pinned host memory on a second stream run on the copy engines BESIDE the sweep: 258 us per step

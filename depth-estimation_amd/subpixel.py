@@ -1,7 +1,10 @@
 """The single-scale raw-patch step as one call, with its opt-in sub-pixel flow (not in the reference: include/dfe.h).
 
-    flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0)
-        dfe_flow_depth_pair_f32 / _u8, or their _subpixel_ forms: frames -> flow, extractOutput scores, depth, depth confidence
+    flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False)
+        dfe_flow_depth_pair_f32 / _u8, or their _subpixel_ forms: frames -> flow, extractOutput scores, depth, depth confidence;
+        consistency=tol: dfe_flow_depth_pair_fb_f32 / _u8, both directions and the forward-backward mask
+    flowConsistency(fw, bw, tol, region=None)
+        dfe_flow_consistency_f32: the forward-backward mask and residual of any two flow fields
     refineFlowSubpixel(img1, img2, idx, hKer, wKer, hWin, wWin)
         dfe_flow_refine_subpixel_f32: the sub-pixel flow of an arg-min index map (dfe_ssd_flow_f32's 1-based idx)
 """
@@ -21,11 +24,14 @@ def _frames(img1, img2, name):
     return img1.contiguous(), img2.contiguous()
 
 
-def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0):
+def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False):
     """One frame pair through the single-scale step: C x H x W frames (float32, or uint8 read as float(byte) * scale), a k x k patch,
     an hWin x wWin search window, foe = (x, y) focus of expansion.  Returns dict(flow [2][H][W] (y, x), scores, depth, depth_conf [H][W]),
     zero outside the centre-pasted output region.  subpixel=True: the flow is refined to sub-pixel precision and depth follows it;
-    scores are the same either way."""
+    scores are the same either way.
+    consistency=tol (pixels): the step also runs from img2 to img1 and the dict gains flow_bw [2][H][W], consistent [H][W] (1 where following
+    the forward flow and then the backward flow found there returns within tol, else 0) and consistency_err [H][W] (that residual; +Inf
+    where the forward flow leaves the output region or a flow is not finite).  gate=True multiplies scores and depth_conf by consistent."""
     a, b = _frames(img1, img2, "flowDepthPair")
     C, H, W = a.shape
     flow = torch.empty((2, H, W), dtype=torch.float32, device=a.device)
@@ -35,6 +41,17 @@ def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False
     ctx = get_ctx(a)
     fx, fy = float(foe[0]), float(foe[1])
     l = lib()
+    if consistency is not None:
+        bw = torch.empty_like(flow)
+        mask = torch.empty_like(scores)
+        err = torch.empty_like(scores)
+        tail = (int(bool(subpixel)), float(consistency), int(bool(gate)), ptr(flow), ptr(scores), ptr(depth), ptr(conf), ptr(bw), ptr(mask), ptr(err))
+        if a.dtype == torch.uint8:
+            rc = l.dfe_flow_depth_pair_fb_u8(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, threshold, float(scale), *tail)
+        else:
+            rc = l.dfe_flow_depth_pair_fb_f32(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, threshold, *tail)
+        ctx.check(rc)
+        return {"flow": flow, "scores": scores, "depth": depth, "depth_conf": conf, "flow_bw": bw, "consistent": mask, "consistency_err": err}
     if a.dtype == torch.uint8:
         fn = l.dfe_flow_depth_pair_subpixel_u8 if subpixel else l.dfe_flow_depth_pair_u8
         rc = fn(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, threshold, float(scale), ptr(flow), ptr(scores), ptr(depth), ptr(conf))
@@ -43,6 +60,25 @@ def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False
         rc = fn(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, threshold, ptr(flow), ptr(scores), ptr(depth), ptr(conf))
     ctx.check(rc)
     return {"flow": flow, "scores": scores, "depth": depth, "depth_conf": conf}
+
+
+def flowConsistency(fw, bw, tol, region=None):
+    """Forward-backward check of two float32 flow fields [2][H][W] (plane 0 = y, plane 1 = x; fw from frame 0 to frame 1, bw back) over
+    region = (y0, x0, Ho, Wo), the whole frame by default (include/dfe.h: dfe_flow_consistency_f32).  Returns (mask, err), float32 [H][W]:
+    mask 1 where |fw(p) + bw(p + fw(p))| <= tol, err that residual (+Inf where p + fw(p) leaves the region or a flow is not finite); both 0
+    outside the region."""
+    if not (fw.is_cuda and bw.is_cuda) or fw.dtype != torch.float32 or bw.dtype != torch.float32:
+        raise TypeError("flowConsistency: two float32 CUDA tensors expected")
+    if fw.dim() != 3 or fw.shape[0] != 2 or fw.shape != bw.shape or fw.device != bw.device:
+        raise ValueError("flowConsistency: two 2 x H x W flows of one shape expected, got %s and %s" % (tuple(fw.shape), tuple(bw.shape)))
+    fw, bw = fw.contiguous(), bw.contiguous()
+    _, H, W = fw.shape
+    y0, x0, Ho, Wo = (0, 0, H, W) if region is None else (int(v) for v in region)
+    mask = torch.empty((H, W), dtype=torch.float32, device=fw.device)
+    err = torch.empty_like(mask)
+    ctx = get_ctx(fw)
+    ctx.check(lib().dfe_flow_consistency_f32(ctx.handle, ptr(fw), ptr(bw), H, W, y0, x0, Ho, Wo, float(tol), ptr(mask), ptr(err)))
+    return mask, err
 
 
 def refineFlowSubpixel(img1, img2, idx, hKer, wKer, hWin, wWin):

@@ -571,6 +571,36 @@ int dfe_flow_depth_pair_subpixel_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8
                                     float *depth, float *depth_conf);
 int dfe_flow_refine_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int kh, int kw, int hWin,
                                  int wWin, const int64_t *idx, float *fy, float *fx, int pitch, int pad_t, int pad_l);
+/* ---- forward-backward flow consistency: an occlusion mask (NOT in the reference) ------------------------------ */
+/* fw, bw [2][H][W] (plane 0 = y, plane 1 = x: the layout of dfe_flow_depth_pair_f32's flow): fw maps frame 0 to frame 1, bw frame 1 to
+ * frame 0.  The valid region R = rows y0 .. y0+Ho-1, columns x0 .. x0+Wo-1 must lie inside the frame (DFE_E_SHAPE); tol >= 0, not NaN
+ * (DFE_E_ARG).  mask, err [H][W]; err may be NULL.  Per pixel p = (y, x), everything in fp32 without fused multiply-adds:
+ *   p outside R: mask = 0, err = 0.
+ *   q = p + fw(p).  A component of fw(p) not finite: mask = 0, err = +Inf (decided before any float -> int conversion of q).
+ *   Reach: fy = floor(q.y), cy = ceil(q.y), fx = floor(q.x), cx = ceil(q.x) (an integral coordinate has floor = ceil).  One of the four
+ *     taps (fy|cy, fx|cx) outside R: mask = 0, err = +Inf.  So a q exactly on R's last row or column is inside, a fraction beyond is not.
+ *   b = bilinear sample of bw at q: wy = q.y - fy, wx = q.x - fx, uy = 1 - wy, ux = 1 - wx;
+ *     b = (uy ux) bw(fy, fx) + (uy wx) bw(fy, cx) + (wy ux) bw(cy, fx) + (wy wx) bw(cy, cx), summed in this order from 0, where a tap
+ *     with a factor that is exactly 0 is NOT read and adds nothing: an integral q reads one pixel, and a NaN under a zero weight does
+ *     not poison the sum.  A component of b not finite: mask = 0, err = +Inf.
+ *   Residual e = fw(p) + b; d2 = e.y e.y + e.x e.x; err = sqrtf(d2); mask = d2 <= tol tol ? 1 : 0 (the squares are compared: integer-valued
+ *     flows give an exact mask).
+ * One launch, one thread per pixel of the frame (the border zeros included).
+ * dfe_flow_depth_pair_fb_f32 / _u8: the pair step in both directions and their consistency in one call.  With gate == 0, flow, scores,
+ *   depth, depth_conf (same NULL rules) are bit-identical to dfe_flow_depth_pair_f32 / _u8 -- subpixel != 0: to the _subpixel_ forms;
+ *   flow_bw [2][H][W] is the flow of that entry with I0 and I1 swapped (NULL: kept in the ctx's own scratch); mask (required) and err
+ *   (may be NULL) are dfe_flow_consistency_f32(flow, flow_bw, H, W, pad_t, pad_l, Ho, Wo, tol) with R the step's centre-pasted region,
+ *   Ho = H - k + 1 - hWin + 1, Wo alike, pad_t = (H - Ho) / 2, pad_l = (W - Wo) / 2.  gate != 0: scores and depth_conf (where given)
+ *   are multiplied by mask inside R; flow and depth stay.  The backward direction makes its two flow planes only (no extractOutput,
+ *   no depth); the _u8 form converts each frame once for both directions. */
+int dfe_flow_consistency_f32(dfe_ctx *ctx, const float *fw, const float *bw, int H, int W, int y0, int x0, int Ho, int Wo, float tol,
+                             float *mask, float *err);
+int dfe_flow_depth_pair_fb_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin,
+                               float foe_x, float foe_y, double extract_threshold, int subpixel, float tol, int gate, float *flow,
+                               float *scores, float *depth, float *depth_conf, float *flow_bw, float *mask, float *err);
+int dfe_flow_depth_pair_fb_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin,
+                              float foe_x, float foe_y, double extract_threshold, float scale, int subpixel, float tol, int gate,
+                              float *flow, float *scores, float *depth, float *depth_conf, float *flow_bw, float *mask, float *err);
 
 /* replaces: image.rgb2y as prepareInput calls it (opticalflow_model.lua:136-138; un-vendored `image`, restated: parity unpinned).
  *   rgb [3][H][W] -> y [1][H][W] = 0.299 R + 0.587 G + 0.114 B, accumulated in that order with separately rounded products and sums. */
