@@ -38,6 +38,7 @@ enum DfeOpt {
     DFE_OPT_CV_NOVOL,         // single-scale flow step without its cost volume (volume-free sweep; 0: build the volume, finalize reads it)
     DFE_OPT_CONV_NT,          // batched convolution: n > 0 = n output planes per thread where nOut % n == 0 and <kW, n> is instantiated (tests)
     DFE_OPT_CV_I8,            // volume-free flow step on the int8 matrix cores where the frames turn out byte-valued (ssd_flow_i8.hip; 0: the float sweep only)
+    DFE_OPT_I8_SLOTS,         // int8 flow sweep: the number of waves its item plan takes the device to hold at once (tests; automatic: from the device)
     DFE_NOPT
 };
 struct DfeOptName { const char *key; const char *env; bool env_presence_means_zero; };
@@ -83,6 +84,7 @@ struct dfe_ctx {
                                       // (ssd_flow_i8.hip; a step's pack kernel clears the next step's word, so no launch resets them); the ctx's
                                       // own, so that dfe_flow_last_path can read it whatever has carved the arena since
     unsigned i8_seq = 0;              // number of the last int8 flow step
+    int i8_slots = 0;                 // waves of the int8 sweep that the device holds at once (0: not asked yet)
     bool i8_last = false;             // the last flow step launched the int8 kernel (and the gated float sweep behind it)
     char err[512] = {0};
     // optional per-launch timing of the cost-volume kernel (dfe_profile_enable)

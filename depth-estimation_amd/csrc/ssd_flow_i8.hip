@@ -15,10 +15,18 @@
 // rotate through registers (the sweep is unrolled by four) and every step loads ONE new 16-byte piece per lane and tile.  With R = 2 the
 // same frame-1 fragments serve (row y, dy) and (row y + 1, dy - 1).
 //
-// Arg-min.  A lane keeps two running keys (i = 0, 1 and i = 2, 3): key = ((2 a'.b' - S1) << 8) + tiebreak, maximised; the plane holds
-// -(S1 << 8) + (1 - (q & 1)), so a key is ONE v_lshl_add of the MFMA result; the (dy, T) part of the tiebreak is relative: the running key
-// gains 2 after every tile, so an earlier candidate wins a tie.  |2 a'.b' - S1| < 2^23, 99 tiles x 2: the key fits 32 bits.  Candidates
-// outside 0 <= q - n <= 32 (first and third tile) are masked.  The four lane groups of a pixel are combined once, on (cost, index).
+// Arg-min.  A lane keeps two running keys (i = 0, 1 and i = 2, 3): key = ((2 a'.b' - S1) << 8) + tiebreak, maximised; the plane cell of
+// frame-1 row y1, column q holds -(S1 << 8) + (1 - (q & 1)) - 6 y1 - 2 (q >> 4), so a key is ONE v_lshl_add of the MFMA result and nothing
+// else is kept per tile: for the item's row y0 + r the candidate j = 3 dy + T (sweep order) lies in row y1 = y0 + r + dy and column block
+// x0 / 16 + T, where the plane's term is -2 j - base, base = 6 (y0 + r) + x0 / 8 the same for all of the row's candidates.  An earlier
+// candidate has the larger term and wins a tie; the terms of two candidates of one pixel differ by at most 2 * 98 + 1 < 256, so the term
+// never outweighs a difference of the costs and need not be reduced.  The decode adds base back.  Range: 2 a'.b' - S1 lies in
+// [-7187712, 2408448] (147 taps of 2 * 127 * -128 - 128^2 .. 2 * 128 * 128 - 128^2), times 256 that is -1.840e9 .. 0.617e9; dfe_flow_i8_plan admits
+// (H + 1) Wp < 2^29 with Wp >= 80, so 6 y1 + 2 (q >> 4) < 6 * 2^29 / 80 + 2^29 / (40 * 8) < 4.2e7: every key, and base + 255 added
+// to one, stays inside 32 bits.  Candidates outside 0 <= q - n <= 32 (first and third tile) are masked by lane masks that live in
+// scalar registers.  The four lane groups of a pixel are combined once, on (cost, index).
+//
+// Items.  flow_i8_items.h splits the rows into two-row and one-row wave items from the number of waves the device holds at once.
 //
 // What it leaves is what the float sweep leaves (cv_records.h): tile-row records, and for a pixel with fewer than M lead cells above the
 // threshold its first M hits in index order in the fallback plane -- found by a second sweep of that strip row which ranks the hits of
@@ -29,6 +37,7 @@
 // turn: the pack kernel of step i clears the word of step i + 1, so nothing has to be reset between calls.
 #include "dfe_internal.h"
 #include "cv_records.h"
+#include "flow_i8_items.h"
 #include <climits>
 
 typedef int i8x16_t __attribute__((ext_vector_type(4)));   // 16 bytes of an MFMA operand / four i32 results
@@ -41,6 +50,7 @@ struct I8Args {
     float thr;
     int M;
     int Ho, Wo, Wp, nstrips, nrp, ncols;
+    int n2, row0, nitems;        // flow_i8_items.h
 };
 
 constexpr int kI8Waves = 4;
@@ -97,7 +107,7 @@ __global__ __launch_bounds__(256) void flow_i8_pack_kernel(const float *__restri
         if (gy >= H || X >= Wp) continue;
         const int v = hs[ly][lx] + hs[ly + 1][lx] + hs[ly + 2][lx] + hs[ly + 3][lx] + hs[ly + 4][lx] + hs[ly + 5][lx] + hs[ly + 6][lx];
         const long long o = (long long)gy * Wp + X;
-        if (blockIdx.z) s1k[o] = -(v << 8) + (1 - (X & 1));
+        if (blockIdx.z) s1k[o] = -(v << 8) + (1 - (X & 1)) - 6 * gy - 2 * (X >> 4);
         else s0[o] = v;
     }
 }
@@ -118,7 +128,7 @@ template <int R, bool FB> struct I8Sweep {
     i8x16_t A[3][4], B[R][4];
     int best[R][2];
     int sa[R];
-    int pen0[4], pen2[4];   // INT_MAX where the first / third tile's candidate 4 g + i lies inside 0 <= q - n <= 32, else INT_MIN
+    bool in0[4], in2[4];   // the first / third tile's candidate 4 g + i lies inside 0 <= q - n <= 32 (loop-invariant lane masks)
     // FB
     int cnt;
     bool flagged;
@@ -132,8 +142,8 @@ template <int R, bool FB> struct I8Sweep {
         const int h = g & 1, up = g >> 1;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            pen0[i] = 4 * g + i >= n ? INT_MAX : INT_MIN;
-            pen2[i] = 4 * g + i <= n ? INT_MAX : INT_MIN;
+            in0[i] = 4 * g + i >= n;
+            in2[i] = 4 * g + i <= n;
         }
         // frame 0: patch rows (0..3 | 3..6) of pixel n, zero in the duplicate row 3 and in the eighth pixel
 #pragma unroll
@@ -157,6 +167,7 @@ template <int R, bool FB> struct I8Sweep {
     template <int PH> __device__ __forceinline__ void step(int s) {
         const int h = g & 1, up = g >> 1;
         const bool more = s + 1 < NS;
+        const int pb = 6 * (y0 + s) + (x0 >> 3);   // the plane's order term of tile 0 of this row, taken off where S1 itself is wanted
         i8x16_t nx[3];
         if (more) {   // the one new row of the next step's fragments (rows s + 4 | s + 7)
 #pragma unroll
@@ -179,21 +190,21 @@ template <int R, bool FB> struct I8Sweep {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         k[i] = (int)((unsigned)D[i] << 9) + P[T][i];
-                        if (T == 0) k[i] = min(k[i], pen0[i]);
-                        if (T == 2) k[i] = min(k[i], pen2[i]);
+                        if (T == 0) k[i] = in0[i] ? k[i] : INT_MIN;
+                        if (T == 2) k[i] = in2[i] ? k[i] : INT_MIN;
                     }
-                    best[r][0] = max(max(best[r][0], k[0]), k[1]) + 2;
-                    best[r][1] = max(max(best[r][1], k[2]), k[3]) + 2;
+                    best[r][0] = max(max(best[r][0], k[0]), k[1]);
+                    best[r][1] = max(max(best[r][1], k[2]), k[3]);
                     if (T < 2 && dy == 0) {   // the lead cells' row
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) lds->cost[r][n][16 * T + 4 * g + i] = (float)(sa[r] - (P[T][i] >> 8) - 2 * D[i]);
+                        for (int i = 0; i < 4; ++i) lds->cost[r][n][16 * T + 4 * g + i] = (float)(sa[r] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[i]);
                     }
                     if (T == 1 && dy == 16) {   // the centre cell: dx = 16, q = 16 + n
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
                             if (4 * g + i == n) {
                                 const int x = x0 + n;
-                                lds->rec[r][(x >> 3) & 1][DFE_REC_CENTRE + (x & 7)] = (float)(sa[r] - (P[T][i] >> 8) - 2 * D[i]);
+                                lds->rec[r][(x >> 3) & 1][DFE_REC_CENTRE + (x & 7)] = (float)(sa[r] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[i]);
                             }
                     }
                 } else {
@@ -204,7 +215,7 @@ template <int R, bool FB> struct I8Sweep {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int m = 4 * g + i;
-                        cv[i] = (float)(sa[0] - (P[T][i] >> 8) - 2 * D[i]);
+                        cv[i] = (float)(sa[0] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[i]);
                         bool valid = flagged;
                         if (T == 0) valid = valid && m >= n;
                         if (T == 2) valid = valid && m <= n;
@@ -260,17 +271,10 @@ __device__ __forceinline__ void i8_lds_fence() {
     __builtin_amdgcn_wave_barrier();
 }
 
-template <int R>
-__global__ __launch_bounds__(kI8Waves * 64) void ssd_flow_i8_kernel(I8Args a) {
-    if (*a.verdict) return;   // not byte-valued: the gated float sweep behind this launch does the step
-    __shared__ I8Lds<R> lds_all[kI8Waves];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int item = blockIdx.x * kI8Waves + wave;
-    if (item >= a.nstrips * a.nrp) return;   // (no block-wide barrier below: a wave works alone)
-    const int strip = item / a.nrp, rp = item - strip * a.nrp;
-    const int x0 = strip * 16, y0 = min(rp * R, a.Ho - R);   // (a short last group of rows is shifted upwards; it stores only its own rows)
+// one wave item: strip `strip`, rows y0 .. y0 + R - 1, of which it stores those from ylo on
+template <int R> __device__ __forceinline__ void i8_item(const I8Args &a, I8Lds<R> *lds, int lane, int strip, int y0, int ylo) {
+    const int x0 = strip * 16;
     const int n = lane & 15, g = lane >> 4;
-    I8Lds<R> *lds = &lds_all[wave];
 
     I8Sweep<R, false> sw(a, lane, x0, y0);
     sw.lds = lds;
@@ -295,7 +299,7 @@ __global__ __launch_bounds__(kI8Waves * 64) void ssd_flow_i8_kernel(I8Args a) {
         long long kb = LLONG_MIN;
 #pragma unroll
         for (int sl = 0; sl < 2; ++sl) {
-            const int bt = sw.best[r][sl] + (254 - 2 * 99);
+            const int bt = sw.best[r][sl] + (6 * (y0 + r) + (x0 >> 3) + 254);   // (E << 8) + 254 - 2 j + (1 - ib)
             const int u = 255 - (bt & 255), j = u >> 1, ib = u & 1;
             const int dy = j / 3, T = j - 3 * dy;
             const int d = dy * 33 + 16 * T + 4 * g + 2 * sl + ib - n;
@@ -337,7 +341,7 @@ __global__ __launch_bounds__(kI8Waves * 64) void ssd_flow_i8_kernel(I8Args a) {
         if (g == 0 && xin) lds->rec[r][slot][DFE_REC_CENTRE + pos] = cen;
         i8_lds_fence();
         const int y = y0 + r;
-        if (y >= rp * R) {
+        if (y >= ylo) {
             for (int i = lane; i < 2 * DFE_REC; i += 64) {
                 const int sl = i >= DFE_REC ? 1 : 0, gg = 2 * strip + sl;
                 if (gg < a.ncols) a.rec[((long long)gg * a.Ho + y) * DFE_REC + (i - sl * DFE_REC)] = lds->rec[r][sl][i - sl * DFE_REC];
@@ -356,6 +360,26 @@ __global__ __launch_bounds__(kI8Waves * 64) void ssd_flow_i8_kernel(I8Args a) {
             }
         }
     }
+}
+
+// Three waves per SIMD: 168 registers, the MFMA results in VGPRs (left to itself the compiler takes 188 with the accumulators in AGPRs,
+// two waves per SIMD, and reads every result back with v_accvgpr_read).
+template <int R>
+__global__ __launch_bounds__(kI8Waves * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void ssd_flow_i8_kernel(I8Args a) {
+    if (*a.verdict) return;   // not byte-valued: the gated float sweep behind this launch does the step
+    __shared__ I8Lds<R> lds_all[kI8Waves];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int item = blockIdx.x * kI8Waves + wave;
+    if (item >= a.nitems) return;   // (no block-wide barrier below: a wave works alone)
+    if constexpr (R == 2) {
+        if (item < a.n2) {
+            const int strip = item / a.nrp, rp = item - strip * a.nrp;
+            i8_item<2>(a, &lds_all[wave], lane, strip, min(2 * rp, a.Ho - 2), 2 * rp);   // (the last pair of an odd Ho is shifted upwards)
+            return;
+        }
+    }
+    const int row = a.row0 + (item - a.n2), strip = row / a.Ho, y = row - strip * a.Ho;
+    i8_item<1>(a, reinterpret_cast<I8Lds<1> *>(&lds_all[wave]), lane, strip, y, y);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -383,8 +407,14 @@ int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, in
     a.rec = fa.rec; a.fb = nv.fb; a.thr = nv.thr; a.M = nv.M;
     a.Ho = Ho; a.Wo = Wo; a.Wp = b.Wp; a.nstrips = b.nstrips; a.ncols = dfe_cdiv(Wo, 8);
     const int R = Ho >= 2 ? 2 : 1;
-    a.nrp = dfe_cdiv(Ho, R);
-    const int nblk = dfe_cdiv((long long)a.nstrips * a.nrp, kI8Waves);
+    if (!ctx->i8_slots) {   // waves resident at once: CUs x blocks of the kernel that a CU holds x waves of a block
+        int nb = 0;
+        DFE_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ssd_flow_i8_kernel<2>, kI8Waves * 64, 0));
+        ctx->i8_slots = ctx->ncu * (nb > 0 ? nb : 1) * kI8Waves;
+    }
+    const I8ItemPlan ip = flow_i8_item_plan(Ho, a.nstrips, ctx->opt[DFE_OPT_I8_SLOTS] > 0 ? ctx->opt[DFE_OPT_I8_SLOTS] : ctx->i8_slots);
+    a.nrp = ip.nrp; a.n2 = (int)ip.n2; a.row0 = (int)ip.row0; a.nitems = (int)(ip.n2 + ip.n1);
+    const int nblk = dfe_cdiv(a.nitems, kI8Waves);
     {
         DfeProfScope prof(ctx, true);
         if (R == 2) hipExtLaunchKernelGGL(ssd_flow_i8_kernel<2>, dim3(nblk), dim3(kI8Waves * 64), 0, ctx->stream, prof.a, prof.b, 0, a);

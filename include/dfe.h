@@ -78,7 +78,7 @@ int dfe_set_cost_volume_tile(dfe_ctx *ctx, int tyq);
 /* Behaviour switches of the launchers (tuning and tests; none is needed for correct results -- every choice has a parity test or is
  * a pure scheduling choice).  value >= 0 forces, -1 restores the launcher's own choice per shape.  Keys: "cascade_px", "fine_fuse",
  * "mid_fuse", "fine_nq", "mid_nq", "prep_tiles", "xpose", "xpose_nt", "soft_epilogue", "conv_batch", "conv_nt10", "fm64", "fm_rows",
- * "sweep_ovh", "sweep_blocks", "debug_arena", "fm_flat", "fm_split", "conv_narrow", "conv_mfma", "fm_mfma", "arena_contig", "graphs", "cv_novol", "conv_nt", "cv_i8".  The library reads the environment ONCE, in dfe_ctx_create
+ * "sweep_ovh", "sweep_blocks", "debug_arena", "fm_flat", "fm_split", "conv_narrow", "conv_mfma", "fm_mfma", "arena_contig", "graphs", "cv_novol", "conv_nt", "cv_i8", "i8_slots".  The library reads the environment ONCE, in dfe_ctx_create
  * (DFE_<KEY> variables of the tuning scripts) -- never inside an op, so an op's behaviour depends on its ctx only.
  * Two keys trade the exact arithmetic for the matrix cores, both OFF unless set to 1: "conv_mfma" (the one-call models' filter layers as
  * implicit GEMMs, v_mfma_f32_16x16x4_f32: the reference's (input plane, ky, kx) order with FUSED multiply-adds, <= 1e-5 relative to
@@ -94,7 +94,9 @@ int dfe_set_cost_volume_tile(dfe_ctx *ctx, int tyq);
  * automatic choice.  "cv_i8" (default 1; only where "cv_novol" applies): the volume-free step packs both float frames to bytes on the
  * device, checking every value; frames that hold nothing but integers in 0..255 are matched by an int8 matrix-core kernel (exact integer
  * arithmetic: the float sweep's bits), any other frame by the float sweep, decided on the device without a host round trip
- * (dfe_flow_last_path tells which); 0 runs the float sweep alone.  Unknown key: DFE_E_ARG. */
+ * (dfe_flow_last_path tells which); 0 runs the float sweep alone.  "i8_slots" (tests): the number of waves that the int8
+ * kernel's split of the rows into two-row and one-row wave items takes the device to hold at once (automatic: compute units x resident
+ * blocks x 4, from the device); a pure scheduling choice.  Unknown key: DFE_E_ARG. */
 int dfe_set_option(dfe_ctx *ctx, const char *key, int value);
 int dfe_get_option(dfe_ctx *ctx, const char *key, int *value);
 /* name of the kernel the last cost-volume call launched (static string) */

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Tuning only: VGPRs / scratch / SGPR spills of every kernel in a .hip file (default: the cost-volume kernels).
+"""Tuning only: VGPRs / scratch / SGPR spills / AGPRs / occupancy of every kernel in a .hip file (default: the cost-volume kernels).
 usage: kres.py [file.hip] [substring] [-Dmacro=value ...]"""
 import re, subprocess, sys, os
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,7 +12,7 @@ out = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--of
                      capture_output=True, text=True).stderr
 cur = None
 for line in out.splitlines():
-    m = re.search(r"remark: (?:\s*)(Function Name|VGPRs|ScratchSize \[bytes/lane\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\S+)", line)
+    m = re.search(r"remark: (?:\s*)(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\S+)", line)
     if not m:
         if "error" in line: print(line)
         continue
@@ -26,4 +26,6 @@ for line in out.splitlines():
             n = n.replace("(anonymous namespace)::", "")
             short = re.sub(r"^void ", "", n)
             short = short[: short.rindex("(")] if "(" in short else short
-            print("%-70s VGPR %s scratch %s sgpr-spill %s" % (short[-70:], cur.get("VGPRs"), cur.get("ScratchSize [bytes/lane]"), cur.get("SGPRs Spill")))
+            # (architectural VGPRs; a wave's registers are VGPRs + AGPRs, and the occupancy follows from that sum)
+            print("%-70s VGPR %s scratch %s sgpr-spill %s agpr %s occupancy %s" % (short[-70:], cur.get("VGPRs"), cur.get("ScratchSize [bytes/lane]"), cur.get("SGPRs Spill"),
+                                                                                   cur.get("AGPRs"), cur.get("Occupancy [waves/SIMD]")))
