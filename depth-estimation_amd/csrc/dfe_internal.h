@@ -207,6 +207,19 @@ static inline int dfe_grid1d(long long n, int per_block = 256, int cap = 256 * 3
     const long long b = (n + per_block - 1) / per_block;
     return (int)(b < 1 ? 1 : b > cap ? cap : b);
 }
+// rows of the output volume that fit one scratch band (ctx->scratch_limit, 16 GiB by default:
+// one launch per pair up to 1080p/33x33; 288 GB of HBM make the whole volume the natural unit)
+static inline int band_rows(const dfe_ctx *ctx, int Ho, int Wo, int D, int elem = (int)sizeof(float)) {
+    long long row_bytes = (long long)Wo * D * elem;
+    long long band = (long long)ctx->scratch_limit / row_bytes;
+    if (band < 1) band = 1;
+    if (band > Ho) band = Ho;
+    // balanced: the same number of bands, rows dealt evenly (band i = rows [i Ho / nb, (i+1) Ho / nb)), so that no short last
+    // band is left over -- the fast kernels need at least a tile of rows, and the fp16 pipeline has no other kernel to fall back to
+    const long long nb = (Ho + band - 1) / band;
+    return (int)((Ho + nb - 1) / nb);
+}
+static inline int band_count(int Ho, int band) { return (Ho + band - 1) / band; }
 // 0-based offset of the centre in a window side of n cells, ceil(n / 2) - 1: datap.lWin / tWin (version2/test.lua:18-21), and the first
 // row / column that prepareInput's narrow(2, ceil(maxh / 2), ..) keeps of patch 1 (opticalflow_model.lua)
 static inline int dfe_window_lead(int n) { return (n + 1) / 2 - 1; }
@@ -305,6 +318,9 @@ struct MsSubpixelArgs {
 struct DfeStackGeom { int hk, wk, K, maxplanes; };   // receptive field, planes of the last layer, the widest layer (>= C)
 
 // ---- the cross-file launchers, by the file that defines them ----
+// kept out of libdfe.so's dynamic symbol table, which is the C ABI's: every cross-file function added from now on (the older ones are
+// still exported under their mangled names)
+#define DFE_HIDDEN __attribute__((visibility("hidden")))
 
 // dfe_ctx.hip
 // key = the bytes of a POD describing the call; returns 0 = launch directly, 1 = capture this call, 2 = replay slot.exec
@@ -333,26 +349,48 @@ template <class L> int dfe_scratch_carve(dfe_ctx *ctx, L &&lay, bool plain = fal
     return DFE_OK;
 }
 
-// ssd_flow_i8.hip
+// rows and columns that the volume-free flow step (k = 7, 33 x 33: the float sweep, its gated copy, the int8 sweep) takes off a frame
+constexpr int DFE_FLOW_MARGIN = 7 - 1 + 33 - 1;
+
+// ssd_flow_i8.hip -- the int8 flow step's kernels and its host state (the ctx's verdict ring); flow_step.hip carves the buffers and calls
 // device buffers of the int8 flow step: packed frames and patch-sum planes (carved by the caller), this call's verdict word and the next one's
 struct DfeFlowI8Bufs {
     unsigned *pk0, *pk1, *verdict, *verdict_next;
     int *s0, *s1k;
     size_t px;            // elements of each of pk0, pk1, s0, s1k
     int Wp, nstrips;
+    void take(DfeCarve &c) {
+        pk0 = c.take<unsigned>(px);
+        pk1 = c.take<unsigned>(px);
+        s0 = c.take<int>(px);
+        s1k = c.take<int>(px);
+    }
 };
-struct CvFuseArgs;
-struct CvNovolArgs;
 // the sizes for an H x W frame (k = 7, 33 x 33) into *b; 0 = the kernel does not take this shape
 size_t dfe_flow_i8_plan(int H, int W, DfeFlowI8Bufs *b);
+// one more int8 step on this ctx: the verdict ring (ctx->i8_verdict, allocated and cleared at first use) turns, b->verdict / verdict_next
+// are this step's word and the next one's
+DFE_HIDDEN int dfe_flow_i8_turn(dfe_ctx *ctx, DfeFlowI8Bufs *b);
 // pack + patch sums + the int8 sweep: records and fallback plane as the float sweep leaves them IF the frames are byte-valued (else
-// nothing: *b.verdict says so to the gated float sweep that the caller launches behind it)
+// nothing: *b.verdict says so to the gated float sweep that the caller launches behind it).  Sets ctx->i8_last
 int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const DfeFlowI8Bufs &b, const CvFuseArgs &fa, const CvNovolArgs &nv);
 
-// ssd_cost_volume.hip
+// ssd_cost_volume.hip -- the raw-frame cost-volume kernels, their planners and launchers; the host pipeline of the flow step that
+// calls them is flow_step.hip
 // cost volume of raw frames into `out`; H = rows visible to this call, plane = channel stride
 int cv_frames_dispatch(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, long long plane, int kh,
                        int kw, int hWin, int wWin, float *out);
+// the fp16 volume (cost * scale) of raw frames, with the fused epilogue's results beside it when fa != NULL; *handled = false: no fast kernel
+int cv_frames_dispatch_f16(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, long long plane, int k, int hWin, int wWin,
+                           float scale, void *out, const CvFuseArgs *fa, bool *handled, bool *recs);
+// the fused builds of this shape leave per-pixel RECORDS (fa.rec) instead of the three planes
+DFE_HIDDEN bool cv_writes_records(int C, int hWin, int wWin);
+// The volume-free flow sweep (3 channels, k = 7, 33 x 33): records into fa.rec, the fallback plane into nv.fb, no volume.
+// cv_flow_sweep_gated_ok: the gated form takes an H x W frame (a caller asks before it launches the int8 kernel in front of it).
+// verdict == NULL: the plain sweep; else its gated copy, which returns at entry unless *verdict != 0.  *handled = false: no launch
+DFE_HIDDEN bool cv_flow_sweep_gated_ok(const dfe_ctx *ctx, int H, int W);
+DFE_HIDDEN int cv_flow_sweep(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const CvFuseArgs &fa, const CvNovolArgs &nv,
+                             const unsigned *verdict, bool *handled);
 // the volumes of n independent pairs (pyramid scales) in one launch where a common block shape exists (*handled)
 // prob (may be NULL): per pair, non-null = leave soft-min probabilities there instead of the costs in out[i] -- if the
 // launcher finds that worthwhile for the shape (*prob_used)

@@ -680,7 +680,7 @@ int64_t dfe_yx2x_multi(int maxh, int maxw, const int *ratios, int nratios, doubl
 
 }  // extern "C"
 
-// the full pass over a band's volume: dfe_flow_tail behind its argument checks, and flow_pipeline's fallback (ssd_cost_volume.hip)
+// the full pass over a band's volume: dfe_flow_tail behind its argument checks, and flow_pipeline's fallback (flow_step.hip)
 // (it stands here, between two extern "C" blocks, and not beside dfe_flow_finalize: a kernel template is emitted where it is first used, and
 //  flow_tail_kernel's place in the code object is behind the entries above)
 int dfe_flow_tail_run(dfe_ctx *ctx, const float *vol, int rows, int hWin, int wWin, double threshold, const TailOut &o) {

@@ -2053,7 +2053,7 @@ __global__ __launch_bounds__(1024) void ssd_cv_rowimg_flow_gated_kernel(const fl
 struct FlowSweepGatedPlan { CvTiledArgs a; int nblk; size_t lds_bytes; };
 static bool plan_flow_sweep_gated(const dfe_ctx *ctx, int H, int W, FlowSweepGatedPlan *pl) {
     using G = RowimgGeom<3, 7, 8>;
-    const int Ho = H - 38, Wo = W - 38;
+    const int Ho = H - DFE_FLOW_MARGIN, Wo = W - DFE_FLOW_MARGIN;
     if (Ho < 1 || Wo < 8 || DFE_TL) return false;
     CvTiledArgs &a = pl->a;
     a.plane = (long long)H * W;
@@ -2089,6 +2089,39 @@ static int launch_flow_sweep_gated(dfe_ctx *ctx, const float *I0, const float *I
     return DFE_OK;
 }
 
+// What flow_step.hip, the host pipeline of the flow step, reaches of the code above: plain functions, so that no template or kernel
+// of this file is instantiated anywhere else
+bool cv_writes_records(int C, int hWin, int wWin) { return rowimg_writes_records(C, hWin, wWin); }
+bool cv_flow_sweep_gated_ok(const dfe_ctx *ctx, int H, int W) {
+    FlowSweepGatedPlan pl;
+    return plan_flow_sweep_gated(ctx, H, W, &pl);
+}
+int cv_flow_sweep(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const CvFuseArgs &fa, const CvNovolArgs &nv, const unsigned *verdict,
+                  bool *handled) {
+    *handled = false;
+    int rc = DFE_OK;
+    FlowSweepGatedPlan pl;
+    if (!verdict) {
+        rc = launch_cv_rowimg_sweep<3, 7, 8, true>(ctx, I0, I1, H, W, (long long)H * W, 33, 33, nullptr, &fa, handled, &nv);
+    } else if (plan_flow_sweep_gated(ctx, H, W, &pl)) {
+        rc = launch_flow_sweep_gated(ctx, I0, I1, pl, fa, nv, verdict);
+        *handled = rc == DFE_OK;
+    }
+#if DFE_TL
+    // (tuning build: the stamps that blocks 0 and 1 left at the start of the fallback plane, in front of the finalize that reads the plane)
+    const size_t fb_bytes = (size_t)dfe_cdiv(W - DFE_FLOW_MARGIN, 8) * (H - DFE_FLOW_MARGIN) * 8 * DFE_FB * sizeof(float);
+    if (const char *path = getenv("DFE_TIMELINE_OUT"); path && !rc && *handled && fb_bytes >= 2 * DFE_TL_WORDS * sizeof(unsigned)) {
+        static unsigned host[2 * DFE_TL_WORDS];
+        if (hipStreamSynchronize(ctx->stream) == hipSuccess && hipMemcpy(host, nv.fb, sizeof(host), hipMemcpyDeviceToHost) == hipSuccess)
+            if (FILE *f = fopen(path, "wb")) {
+                fwrite(host, 1, sizeof(host), f);
+                fclose(f);
+            }
+    }
+#endif
+    return rc;
+}
+
 extern "C" {
 // Bumped whenever a change can alter what the cost-volume kernels read or write: profiles/traffic_*.json carries the revision
 // its PMC counters were taken with, and bench.py reports `traffic` only when the two agree.
@@ -2104,232 +2137,6 @@ int dfe_ssd_cost_volume_f32(dfe_ctx *ctx, const float *I0, const float *I1, int 
     DFE_REQUIRE(ctx, Ho > 0 && Wo > 0, DFE_E_SHAPE,
                 "dfe_ssd_cost_volume_f32: frame %dx%d too small for kernel %dx%d + window %dx%d", H, W, kh, kw, hWin, wWin);
     return cv_frames_dispatch(ctx, I0, I1, C, H, W, (long long)H * W, kh, kw, hWin, wWin, out);
-}
-
-// rows of the output volume that fit one scratch band (ctx->scratch_limit, 16 GiB by default:
-// one launch per pair up to 1080p/33x33; 288 GB of HBM make the whole volume the natural unit)
-static int band_rows(const dfe_ctx *ctx, int Ho, int Wo, int D, int elem = (int)sizeof(float)) {
-    long long row_bytes = (long long)Wo * D * elem;
-    long long band = (long long)ctx->scratch_limit / row_bytes;
-    if (band < 1) band = 1;
-    if (band > Ho) band = Ho;
-    // balanced: the same number of bands, rows dealt evenly (band i = rows [i Ho / nb, (i+1) Ho / nb)), so that no short last
-    // band is left over -- the fast kernels need at least a tile of rows, and the fp16 pipeline has no other kernel to fall back to
-    const long long nb = (Ho + band - 1) / band;
-    return (int)((Ho + nb - 1) / nb);
-}
-static int band_count(int Ho, int band) { return (Ho + band - 1) / band; }
-
-// the largest float <= t (NaN stays NaN): for every float v, v > float_at_or_below(t) <=> (double)v > t -- a hit strictly above a float
-// f <= t is at least the next float, which lies above t -- so the kernel compares in fp32 exactly as the finalize does in fp64
-static float float_at_or_below(double t) {
-    if (std::isnan(t)) return std::numeric_limits<float>::quiet_NaN();
-    if (t >= (double)std::numeric_limits<float>::max()) return std::isinf(t) ? std::numeric_limits<float>::infinity() : std::numeric_limits<float>::max();
-    if (t < -(double)std::numeric_limits<float>::max()) return -std::numeric_limits<float>::infinity();
-    float f = (float)t;
-    if ((double)f > t) f = std::nextafter(f, -std::numeric_limits<float>::infinity());
-    return f;
-}
-
-// The flow step without its cost volume (option "cv_novol", default on): the volume-free fused sweep leaves records and, for the rare
-// pixels whose lead cells hold fewer than M hits, the fallback plane; one launch for the whole pair (no bands: 112 B of scratch per
-// pixel instead of 4356), then the record finalize.  Returns DFE_OK with *done = false where the sweep does not apply.
-// Option "cv_i8" (default on): the frames are packed to bytes and checked on the device; the int8 matrix-core kernel (ssd_flow_i8.hip)
-// leaves the same records if every value is an integer in 0..255 and the gated float sweep, launched behind it, if not -- one of the
-// two returns at entry, and no host round trip decides.
-static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, int hWin, int wWin, double thr, const TailOut &out,
-                               const DfePairDepth *pd, bool *pd_done, bool *done) {
-    constexpr int K = 7;
-    *done = false;
-    ctx->i8_last = false;
-    const int Ho = H - K + 1 - hWin + 1, Wo = W - K + 1 - wWin + 1;
-    const long long P = (long long)Ho * Wo;
-    if (Wo < 8 || P >= (1ll << 31) || (pd && (long long)pd->H * pd->W >= (1ll << 31))) return DFE_OK;   // (the finalize's 32-bit pixel arithmetic)
-    const size_t nrec = (size_t)dfe_cdiv(Wo, 8) * Ho;   // tile-row records
-    DfeFlowI8Bufs ib{};
-    FlowSweepGatedPlan gp;
-    const bool i8 = hWin == 33 && wWin == 33 && ctx->opt_bool(DFE_OPT_CV_I8, true) && dfe_flow_i8_plan(H, W, &ib) != 0 && plan_flow_sweep_gated(ctx, H, W, &gp);
-    if (i8) {
-        if (!ctx->i8_verdict.p) {
-            int rc = dfe_grow(ctx, ctx->i8_verdict, 256, "i8 verdict");
-            if (rc) return rc;
-            DFE_HIP(ctx, hipMemsetAsync(ctx->i8_verdict.p, 0, 256, ctx->stream));
-        }
-        ++ctx->i8_seq;
-        ib.verdict = (unsigned *)ctx->i8_verdict.p + ctx->i8_seq % 3;
-        ib.verdict_next = (unsigned *)ctx->i8_verdict.p + (ctx->i8_seq + 1) % 3;
-    }
-    CvFuseArgs fa{};
-    CvNovolArgs nv;
-    int rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
-        fa.rec = c.take<float>(nrec * DFE_REC);       // [tile column][output row][DFE_REC]
-        nv.fb = c.take<float>(nrec * 8 * DFE_FB);     // [tile column][output row][8][DFE_FB]
-        if (i8) {
-            ib.pk0 = c.take<unsigned>(ib.px);
-            ib.pk1 = c.take<unsigned>(ib.px);
-            ib.s0 = c.take<int>(ib.px);
-            ib.s1k = c.take<int>(ib.px);
-        }
-    });
-    if (rc) return rc;
-    fa.rec_rows = Ho;
-    fa.row_off = 0;
-    fa.Ptot = P;
-    nv.thr = float_at_or_below(thr);
-    nv.M = thr < 0.2 ? 8 : 4;   // extract_output.cpp:83-85
-    bool handled = false;
-    {
-        DfeStageScope match(ctx, DFE_STAGE_MATCH);
-        if (i8) {
-            rc = dfe_flow_i8_launch(ctx, I0, I1, H, W, ib, fa, nv);
-            if (rc) return rc;
-            rc = launch_flow_sweep_gated(ctx, I0, I1, gp, fa, nv, ib.verdict);
-            if (rc) return rc;
-            ctx->i8_last = true;
-            handled = true;
-        } else {
-            rc = launch_cv_rowimg_sweep<3, 7, 8, true>(ctx, I0, I1, H, W, (long long)H * W, hWin, wWin, nullptr, &fa, &handled, &nv);
-            if (rc || !handled) return rc;
-        }
-    }
-    *done = true;
-    DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
-    rc = dfe_flow_finalize(ctx, fa, true, 1, nullptr, &nv, thr, Ho, hWin, wWin, out, pd);
-    if (pd && pd_done) *pd_done = true;
-#if DFE_TL
-    if (const char *path = getenv("DFE_TIMELINE_OUT"); path && !rc && nrec * 8 * DFE_FB * sizeof(float) >= 2 * DFE_TL_WORDS * sizeof(unsigned)) {
-        static unsigned host[2 * DFE_TL_WORDS];
-        if (hipStreamSynchronize(ctx->stream) == hipSuccess && hipMemcpy(host, nv.fb, sizeof(host), hipMemcpyDeviceToHost) == hipSuccess)
-            if (FILE *f = fopen(path, "wb")) {
-                fwrite(host, 1, sizeof(host), f);
-                fclose(f);
-            }
-    }
-#endif
-    return rc;
-}
-
-// One pair through build + flow extraction.  Preferred: the fused build (per-chunk minimum + first index, the centre
-// cell and the pixel's first 16 cells leave the kernel with the volume, ~210 compact bytes per pixel) + a finalize that
-// reads only those; it goes back to the volume only for pixels whose first 16 cells hold fewer than M values above
-// the extractOutput threshold.
-// Fallback (shapes without a fused instantiation): build, then the full pass dfe_flow_tail.
-// out: where the results go (dfe_tailout, Wo = this pair's); each band gets its row_off / p_off here.
-static int flow_pipeline(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int kh, int kw, int hWin, int wWin,
-                         double thr, const TailOut &out, const DfePairDepth *pd = nullptr, bool *pd_done = nullptr, float f16_scale = 0.f) {
-    // f16_scale != 0: the volume is materialised as fp16 (cost * f16_scale); arg-min, centre and lead cells still come from
-    // the fp32 sums in the kernel, so indices and minima are those of the fp32 path.  No extractOutput scores then (its
-    // rare fall-back reads the volume).
-    if (kh == kw && kh == 7 && f16_scale == 0.f && rowimg_writes_records(C, hWin, wWin) && ctx->opt_bool(DFE_OPT_CV_NOVOL, true) &&
-        (ctx->cv_mode == 0 || ctx->cv_mode == 3) && (ctx->cv_tyq == 0 || ctx->cv_tyq == 1)) {   // (forced static tiles: the volume path)
-        bool done = false;
-        int rc = flow_pipeline_novol(ctx, I0, I1, H, W, hWin, wWin, thr, out, pd, pd_done, &done);
-        if (rc || done) return rc;
-    }
-    const int Ho = H - kh + 1 - hWin + 1, Wo = W - kw + 1 - wWin + 1;
-    const int D = hWin * wWin, nch = (D + 63) / 64;
-    const long long P = (long long)Ho * Wo;
-    const int elem = f16_scale != 0.f ? 2 : 4;
-    const int band = band_rows(ctx, Ho, Wo, D, elem);
-    // per-pixel records of the role-split row-image kernels (one whole 128-B line per pixel instead of entries in the three planes)
-    const bool want_rec = kh == kw && kh == 7 && rowimg_writes_records(C, hWin, wWin);
-    float *vol;
-    CvFuseArgs fa{};
-    int rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
-        vol = (float *)c.take<char>((size_t)band * Wo * D * elem);
-        fa.part = c.take<float2>((size_t)nch * P);
-        fa.centre = c.take<float>((size_t)P);
-        fa.lead = c.take<float>((size_t)P * DFE_LEAD);
-        fa.rec = c.take<float>(want_rec ? (size_t)dfe_cdiv(Wo, 8) * Ho * DFE_REC : 0);   // [tile column][output row][DFE_REC]
-    });
-    if (rc) return rc;
-    fa.rec_rows = Ho;
-    fa.Ptot = P;
-    {
-        const int middle = dfe_window_middle(hWin, wWin);
-        fa.cmid = (middle - 1) >> 6; fa.lmid = (middle - 1) & 63;
-    }
-    const int nb = band_count(Ho, band);
-    TailOut o = out;
-    for (int bi = 0; bi < nb; ++bi) {
-        const int r0 = (int)((long long)bi * Ho / nb), nr = (int)((long long)(bi + 1) * Ho / nb) - r0;   // (nr <= band)
-        const int Hb = nr + kh - 1 + hWin - 1;
-        o.row_off = r0;
-        o.p_off = (long long)r0 * Wo;
-        const float *b0 = I0 + (long long)r0 * W, *b1 = I1 + (long long)r0 * W;
-        bool fused = false, recs = false;
-        int nparts = nch;
-        std::unique_ptr<DfeStageScope> match_scope(new DfeStageScope(ctx, DFE_STAGE_MATCH));   // (closed in front of the finalize / tail pass below)
-        if (kh == kw && f16_scale != 0.f) {
-            fa.row_off = r0;
-            rc = cv_frames_dispatch_f16(ctx, b0, b1, C, Hb, W, (long long)H * W, kh, hWin, wWin, f16_scale, vol, &fa, &fused, &recs);
-            if (rc) return rc;
-            nparts = 2;
-            if (!fused) return dfe_fail(ctx, DFE_E_UNSUPPORTED, "no fused fp16 cost-volume kernel for C=%d k=%d win=%dx%d out=%dx%d (band of %d rows)", C, kh, hWin, wWin, Ho, Wo, nr);
-        } else if (kh == kw) {
-            fa.row_off = r0;
-            rc = cv_frames_dispatch_fused(ctx, b0, b1, C, Hb, W, (long long)H * W, kh, hWin, wWin, vol, fa, &fused, &nparts, &recs);
-            if (rc) return rc;
-        }
-        if (fused) {
-            match_scope.reset();
-            DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
-            // one band: the finalize launch also zeroes the frame border and makes depth (pair step: 2 launches instead of 3)
-            const bool frame_mode = pd && nr == Ho;
-            rc = dfe_flow_finalize(ctx, fa, recs, nparts, vol, nullptr, thr, nr, hWin, wWin, o, frame_mode ? pd : nullptr);
-            if (frame_mode && pd_done) *pd_done = true;
-        } else {
-            rc = cv_frames_dispatch(ctx, b0, b1, C, Hb, W, (long long)H * W, kh, kw, hWin, wWin, vol);
-            if (rc) return rc;
-            match_scope.reset();
-            DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
-            rc = dfe_flow_tail_run(ctx, vol, nr, hWin, wWin, thr, o);
-        }
-        if (rc) return rc;
-    }
-    return DFE_OK;
-}
-
-int dfe_ssd_flow_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int kh, int kw, int hWin,
-                     int wWin, double extract_threshold, int64_t *idx, float *best, float *flow_y, float *flow_x,
-                     float *scores, int64_t *imaxs) {
-    DFE_ENTER(ctx);
-    DFE_REQUIRE(ctx, I0 && I1, DFE_E_ARG, "dfe_ssd_flow_f32: NULL frame");
-    DFE_REQUIRE(ctx, C > 0 && kh > 0 && kw > 0 && hWin > 0 && wWin > 0, DFE_E_ARG,
-                "dfe_ssd_flow_f32: C=%d k=%dx%d win=%dx%d must be positive", C, kh, kw, hWin, wWin);
-    const int Ho = H - kh + 1 - hWin + 1, Wo = W - kw + 1 - wWin + 1;
-    DFE_REQUIRE(ctx, Ho > 0 && Wo > 0, DFE_E_SHAPE, "dfe_ssd_flow_f32: frame %dx%d too small for kernel %dx%d + window %dx%d",
-                H, W, kh, kw, hWin, wWin);
-    DFE_REQUIRE(ctx, (scores == nullptr) == (imaxs == nullptr), DFE_E_ARG, "dfe_ssd_flow_f32: scores and imaxs go together");
-    return flow_pipeline(ctx, I0, I1, C, H, W, kh, kw, hWin, wWin, extract_threshold,
-                         dfe_tailout(idx, best, flow_y, flow_x, scores, imaxs, Wo, /*pitch*/ Wo, /*pad_t*/ 0, /*pad_l*/ 0, /*scores_padded*/ 0));
-}
-
-int dfe_flow_depth_pair_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin,
-                            float foe_x, float foe_y, double extract_threshold, float *flow, float *scores, float *depth,
-                            float *depth_conf) {
-    DFE_ENTER(ctx);
-    DFE_REQUIRE(ctx, I0 && I1 && flow, DFE_E_ARG, "dfe_flow_depth_pair_f32: NULL tensor");
-    DFE_REQUIRE(ctx, C > 0 && k > 0 && hWin > 0 && wWin > 0, DFE_E_ARG, "dfe_flow_depth_pair_f32: C=%d k=%d win=%dx%d", C, k,
-                hWin, wWin);
-    DFE_REQUIRE(ctx, (depth == nullptr) == (depth_conf == nullptr), DFE_E_ARG,
-                "dfe_flow_depth_pair_f32: depth and depth_conf go together");
-    const int Ho = H - k + 1 - hWin + 1, Wo = W - k + 1 - wWin + 1;
-    DFE_REQUIRE(ctx, Ho > 0 && Wo > 0, DFE_E_SHAPE, "dfe_flow_depth_pair_f32: frame %dx%d too small for kernel %d + window %dx%d",
-                H, W, k, hWin, wWin);
-    const long long HW = (long long)H * W;
-    // centre-paste offsets: opticalflow_model.lua:228-230 floor((hImg-h)/2)
-    //   == radial/radial_opticalflow_groundtruth.lua:27-32 floor((hWin-1)/2)+floor((k-1)/2)
-    const int pad_t = (H - Ho) / 2, pad_l = (W - Wo) / 2;
-    // the pipeline writes every interior pixel of flow / scores; one pass afterwards zeroes the border and makes depth
-    const DfePairDepth pd{H, W, foe_x, foe_y, depth, depth_conf};
-    bool pd_done = false;
-    int rc = flow_pipeline(ctx, I0, I1, C, H, W, k, k, hWin, wWin, extract_threshold,
-                           dfe_tailout(nullptr, nullptr, flow, flow + HW, scores, nullptr, Wo, /*pitch*/ W, pad_t, pad_l, /*scores_padded*/ 1), &pd, &pd_done);
-    if (rc || pd_done) return rc;
-    // several bands, or no fused build for this shape: one pass afterwards zeroes the border and makes depth
-    DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
-    return dfe_pair_border_depth(ctx, flow, scores, H, W, pad_t, pad_l, Ho, Wo, foe_x, foe_y, depth, depth_conf);
 }
 
 int dfe_ssd_cost_volume_f16(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int kh, int kw, int hWin, int wWin,
@@ -2366,27 +2173,6 @@ int dfe_ssd_cost_volume_f16(dfe_ctx *ctx, const float *I0, const float *I1, int 
         DFE_LAUNCH_CHECK(ctx);
     }
     return DFE_OK;
-}
-
-int dfe_flow_depth_pair_f16(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x,
-                            float foe_y, float scale, int64_t *idx, float *best, float *flow, float *depth, float *depth_conf) {
-    DFE_ENTER(ctx);
-    DFE_REQUIRE(ctx, I0 && I1 && flow, DFE_E_ARG, "dfe_flow_depth_pair_f16: NULL tensor");
-    DFE_REQUIRE(ctx, C > 0 && k > 0 && hWin > 0 && wWin > 0 && scale > 0, DFE_E_ARG, "dfe_flow_depth_pair_f16: C=%d k=%d win=%dx%d scale=%g", C, k, hWin,
-                wWin, (double)scale);
-    DFE_REQUIRE(ctx, (depth == nullptr) == (depth_conf == nullptr), DFE_E_ARG, "dfe_flow_depth_pair_f16: depth and depth_conf go together");
-    const int Ho = H - k + 1 - hWin + 1, Wo = W - k + 1 - wWin + 1;
-    DFE_REQUIRE(ctx, Ho > 0 && Wo > 0, DFE_E_SHAPE, "dfe_flow_depth_pair_f16: frame %dx%d too small for kernel %d + window %dx%d", H, W, k, hWin, wWin);
-    const long long HW = (long long)H * W;
-    const int pad_t = (H - Ho) / 2, pad_l = (W - Wo) / 2;
-    const DfePairDepth pd{H, W, foe_x, foe_y, depth, depth_conf};
-    bool pd_done = false;
-    // (idx / best are [Ho][Wo], like dfe_ssd_flow_f32's; flow is the centre-pasted [2][H][W])
-    int rc = flow_pipeline(ctx, I0, I1, C, H, W, k, k, hWin, wWin, 0.0,
-                           dfe_tailout(idx, best, flow, flow + HW, nullptr, nullptr, Wo, /*pitch*/ W, pad_t, pad_l, /*scores_padded*/ 1), &pd, &pd_done, scale);
-    if (rc || pd_done) return rc;
-    DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
-    return dfe_pair_border_depth(ctx, flow, nullptr, H, W, pad_t, pad_l, Ho, Wo, foe_x, foe_y, depth, depth_conf);
 }
 
 int dfe_spatial_matching_f32(dfe_ctx *ctx, const float *in1, const float *in2, int K, int H1, int W1, int maxh,

@@ -386,7 +386,7 @@ __global__ __launch_bounds__(kI8Waves * 64) __attribute__((amdgpu_waves_per_eu(3
 // host
 // ------------------------------------------------------------------------------------------
 size_t dfe_flow_i8_plan(int H, int W, DfeFlowI8Bufs *b) {
-    const int Ho = H - 38, Wo = W - 38;
+    const int Ho = H - DFE_FLOW_MARGIN, Wo = W - DFE_FLOW_MARGIN;
     DfeFlowI8Bufs p{};
     if (Ho < 1 || Wo < 8) return 0;
     p.nstrips = dfe_cdiv(Wo, 16);
@@ -397,8 +397,21 @@ size_t dfe_flow_i8_plan(int H, int W, DfeFlowI8Bufs *b) {
     return p.px;
 }
 
+// the verdict ring: step i8_seq takes word i8_seq % 3 and has its pack kernel clear word (i8_seq + 1) % 3 for the step after it
+int dfe_flow_i8_turn(dfe_ctx *ctx, DfeFlowI8Bufs *b) {
+    if (!ctx->i8_verdict.p) {
+        int rc = dfe_grow(ctx, ctx->i8_verdict, 256, "i8 verdict");
+        if (rc) return rc;
+        DFE_HIP(ctx, hipMemsetAsync(ctx->i8_verdict.p, 0, 256, ctx->stream));
+    }
+    ++ctx->i8_seq;
+    b->verdict = (unsigned *)ctx->i8_verdict.p + ctx->i8_seq % 3;
+    b->verdict_next = (unsigned *)ctx->i8_verdict.p + (ctx->i8_seq + 1) % 3;
+    return DFE_OK;
+}
+
 int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const DfeFlowI8Bufs &b, const CvFuseArgs &fa, const CvNovolArgs &nv) {
-    const int Ho = H - 38, Wo = W - 38;
+    const int Ho = H - DFE_FLOW_MARGIN, Wo = W - DFE_FLOW_MARGIN;
     hipLaunchKernelGGL(flow_i8_pack_kernel, dim3(dfe_cdiv(b.Wp, kPackW), dfe_cdiv(H, kPackH), 2), dim3(256), 0, ctx->stream, I0, I1, H, W, (long long)H * W,
                        b.Wp, b.pk0, b.pk1, b.s0, b.s1k, b.verdict, b.verdict_next);
     DFE_LAUNCH_CHECK(ctx);
@@ -422,5 +435,6 @@ int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, in
     }
     DFE_LAUNCH_CHECK(ctx);
     ctx->last_kernel = "ssd_flow_i8_kernel";
+    ctx->i8_last = true;
     return DFE_OK;
 }
