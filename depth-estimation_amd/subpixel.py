@@ -1,10 +1,13 @@
 """The single-scale raw-patch step as one call, with its opt-in sub-pixel flow (not in the reference: include/dfe.h).
 
-    flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False)
+    flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False, fill=None)
         dfe_flow_depth_pair_f32 / _u8, or their _subpixel_ forms: frames -> flow, extractOutput scores, depth, depth confidence;
         consistency=tol: dfe_flow_depth_pair_fb_f32 / _u8, both directions and the forward-backward mask
+        fill=True: the rejected pixels filled from the kept ones, flow_dense / filled / depth_dense
     flowConsistency(fw, bw, tol, region=None)
         dfe_flow_consistency_f32: the forward-backward mask and residual of any two flow fields
+    fillHoles(values, weight, region=None, levels=0)
+        dfe_fill_holes_f32: a dense field from the confident pixels of a sparse one (confidence-weighted push-pull)
     refineFlowSubpixel(img1, img2, idx, hKer, wKer, hWin, wWin)
         dfe_flow_refine_subpixel_f32: the sub-pixel flow of an arg-min index map (dfe_ssd_flow_f32's 1-based idx)
 """
@@ -24,14 +27,36 @@ def _frames(img1, img2, name):
     return img1.contiguous(), img2.contiguous()
 
 
-def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False):
+def _with_fill(res, fill, k, hWin, wWin, fx, fy):
+    """the three keys of flowDepthPair(..., fill=...) from the step's own outputs, which stay as they are"""
+    if fill is None or fill is False:
+        return res
+    flow, scores = res["flow"], res["scores"]
+    _, H, W = flow.shape
+    Ho, Wo = H - k + 1 - hWin + 1, W - k + 1 - wWin + 1
+    wgt = (scores > 0).to(torch.float32)          # a pixel that extractOutput rejected carries score 0 (and so does one the gate removed)
+    if "consistent" in res:
+        wgt = wgt * res["consistent"]
+    dense, filled = fillHoles(flow, wgt, ((H - Ho) // 2, (W - Wo) // 2, Ho, Wo), 0 if fill is True else int(fill))
+    depth = torch.empty_like(scores)
+    conf = torch.empty_like(scores)
+    ctx = get_ctx(flow)
+    ctx.check(lib().dfe_flow_to_depth_cartesian(ctx.handle, ptr(dense), H, W, fx, fy, 0, ptr(depth), ptr(conf)))
+    res.update(flow_dense=dense, filled=filled, depth_dense=depth)
+    return res
+
+
+def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False, fill=None):
     """One frame pair through the single-scale step: C x H x W frames (float32, or uint8 read as float(byte) * scale), a k x k patch,
     an hWin x wWin search window, foe = (x, y) focus of expansion.  Returns dict(flow [2][H][W] (y, x), scores, depth, depth_conf [H][W]),
     zero outside the centre-pasted output region.  subpixel=True: the flow is refined to sub-pixel precision and depth follows it;
     scores are the same either way.
     consistency=tol (pixels): the step also runs from img2 to img1 and the dict gains flow_bw [2][H][W], consistent [H][W] (1 where following
     the forward flow and then the backward flow found there returns within tol, else 0) and consistency_err [H][W] (that residual; +Inf
-    where the forward flow leaves the output region or a flow is not finite).  gate=True multiplies scores and depth_conf by consistent."""
+    where the forward flow leaves the output region or a flow is not finite).  gate=True multiplies scores and depth_conf by consistent.
+    fill=True (or an int: the `levels` of fillHoles): the dict gains flow_dense [2][H][W] = fillHoles(flow, wgt, R, levels) with R the
+    output region and wgt 1 where scores > 0 (and, with consistency, where consistent is 1 as well), filled [H][W] (1 where a value was
+    found), and depth_dense [H][W], the depth of flow_dense (dfe_flow_to_depth_cartesian, fix_dot = 0).  The other keys are unchanged."""
     a, b = _frames(img1, img2, "flowDepthPair")
     C, H, W = a.shape
     flow = torch.empty((2, H, W), dtype=torch.float32, device=a.device)
@@ -51,7 +76,8 @@ def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False
         else:
             rc = l.dfe_flow_depth_pair_fb_f32(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, threshold, *tail)
         ctx.check(rc)
-        return {"flow": flow, "scores": scores, "depth": depth, "depth_conf": conf, "flow_bw": bw, "consistent": mask, "consistency_err": err}
+        return _with_fill({"flow": flow, "scores": scores, "depth": depth, "depth_conf": conf, "flow_bw": bw, "consistent": mask, "consistency_err": err},
+                          fill, k, hWin, wWin, fx, fy)
     if a.dtype == torch.uint8:
         fn = l.dfe_flow_depth_pair_subpixel_u8 if subpixel else l.dfe_flow_depth_pair_u8
         rc = fn(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, threshold, float(scale), ptr(flow), ptr(scores), ptr(depth), ptr(conf))
@@ -59,7 +85,7 @@ def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False
         fn = l.dfe_flow_depth_pair_subpixel_f32 if subpixel else l.dfe_flow_depth_pair_f32
         rc = fn(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, threshold, ptr(flow), ptr(scores), ptr(depth), ptr(conf))
     ctx.check(rc)
-    return {"flow": flow, "scores": scores, "depth": depth, "depth_conf": conf}
+    return _with_fill({"flow": flow, "scores": scores, "depth": depth, "depth_conf": conf}, fill, k, hWin, wWin, fx, fy)
 
 
 def flowConsistency(fw, bw, tol, region=None):
@@ -79,6 +105,28 @@ def flowConsistency(fw, bw, tol, region=None):
     ctx = get_ctx(fw)
     ctx.check(lib().dfe_flow_consistency_f32(ctx.handle, ptr(fw), ptr(bw), H, W, y0, x0, Ho, Wo, float(tol), ptr(mask), ptr(err)))
     return mask, err
+
+
+def fillHoles(values, weight, region=None, levels=0):
+    """Dense field from the confident pixels of a sparse one (include/dfe.h: dfe_fill_holes_f32): values float32 [C][H][W], 1 <= C <= 4,
+    weight float32 [H][W] (>= 1 fully trusted, below 1e-6 or not finite a hole), region = (y0, x0, Ho, Wo), the whole frame by default;
+    levels = 0 fills from any distance, n > 0 from at most n pyramid levels (holes farther than about 2^n pixels from every valid pixel
+    stay unfilled).  Returns (out [C][H][W], filled [H][W]): pixels of weight >= 1 keep their bits, the others are blended with / replaced
+    by the confidence-weighted push-pull interpolation; filled is 1 where a value was found; both 0 outside the region."""
+    if values.dim() != 3 or not 1 <= values.shape[0] <= 4 or weight.dim() != 2 or tuple(weight.shape) != tuple(values.shape[1:]):
+        raise ValueError("fillHoles: values C x H x W (C = 1 .. 4) and weight H x W expected, got %s and %s" % (tuple(values.shape), tuple(weight.shape)))
+    if not (values.is_cuda and weight.is_cuda) or values.dtype != torch.float32 or weight.dtype != torch.float32:
+        raise TypeError("fillHoles: two float32 CUDA tensors expected")
+    if values.device != weight.device:
+        raise ValueError("fillHoles: values on %s, weight on %s" % (values.device, weight.device))
+    values, weight = values.contiguous(), weight.contiguous()
+    C, H, W = values.shape
+    y0, x0, Ho, Wo = (0, 0, H, W) if region is None else (int(v) for v in region)
+    out = torch.empty_like(values)
+    filled = torch.empty((H, W), dtype=torch.float32, device=values.device)
+    ctx = get_ctx(values)
+    ctx.check(lib().dfe_fill_holes_f32(ctx.handle, ptr(values), C, H, W, ptr(weight), y0, x0, Ho, Wo, int(levels), ptr(out), ptr(filled)))
+    return out, filled
 
 
 def refineFlowSubpixel(img1, img2, idx, hKer, wKer, hWin, wWin):

@@ -78,7 +78,7 @@ int dfe_set_cost_volume_tile(dfe_ctx *ctx, int tyq);
 /* Behaviour switches of the launchers (tuning and tests; none is needed for correct results -- every choice has a parity test or is
  * a pure scheduling choice).  value >= 0 forces, -1 restores the launcher's own choice per shape.  Keys: "cascade_px", "fine_fuse",
  * "mid_fuse", "fine_nq", "mid_nq", "prep_tiles", "xpose", "xpose_nt", "soft_epilogue", "conv_batch", "conv_nt10", "fm64", "fm_rows",
- * "sweep_ovh", "sweep_blocks", "debug_arena", "fm_flat", "fm_split", "conv_narrow", "conv_mfma", "fm_mfma", "arena_contig", "graphs", "cv_novol", "conv_nt", "cv_i8", "i8_slots".  The library reads the environment ONCE, in dfe_ctx_create
+ * "sweep_ovh", "sweep_blocks", "debug_arena", "fm_flat", "fm_split", "conv_narrow", "conv_mfma", "fm_mfma", "arena_contig", "graphs", "cv_novol", "conv_nt", "cv_i8", "i8_slots", "fill_apex".  The library reads the environment ONCE, in dfe_ctx_create
  * (DFE_<KEY> variables of the tuning scripts) -- never inside an op, so an op's behaviour depends on its ctx only.
  * Two keys trade the exact arithmetic for the matrix cores, both OFF unless set to 1: "conv_mfma" (the one-call models' filter layers as
  * implicit GEMMs, v_mfma_f32_16x16x4_f32: the reference's (input plane, ky, kx) order with FUSED multiply-adds, <= 1e-5 relative to
@@ -96,7 +96,10 @@ int dfe_set_cost_volume_tile(dfe_ctx *ctx, int tyq);
  * arithmetic: the float sweep's bits), any other frame by the float sweep, decided on the device without a host round trip
  * (dfe_flow_last_path tells which); 0 runs the float sweep alone.  "i8_slots" (tests): the number of waves that the int8
  * kernel's split of the rows into two-row and one-row wave items takes the device to hold at once (automatic: compute units x resident
- * blocks x 4, from the device); a pure scheduling choice.  Unknown key: DFE_E_ARG. */
+ * blocks x 4, from the device); a pure scheduling choice.  "fill_apex" (dfe_fill_holes_f32): automatic = the upper pyramid levels, from
+ * the first one whose levels up to the top fit the 160 KB of LDS, run in one workgroup's single launch; 0 = a launch per level and
+ * direction only; n > 0 (tests) = the apex takes over at the first level of at most n cells (that also fits).  The same bits either way.
+ * Unknown key: DFE_E_ARG. */
 int dfe_set_option(dfe_ctx *ctx, const char *key, int value);
 int dfe_get_option(dfe_ctx *ctx, const char *key, int *value);
 /* name of the kernel the last cost-volume call launched (static string) */
@@ -603,6 +606,29 @@ int dfe_flow_depth_pair_fb_f32(dfe_ctx *ctx, const float *I0, const float *I1, i
 int dfe_flow_depth_pair_fb_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin,
                               float foe_x, float foe_y, double extract_threshold, float scale, int subpixel, float tol, int gate,
                               float *flow, float *scores, float *depth, float *depth_conf, float *flow_bw, float *mask, float *err);
+/* ---- hole filling: a dense field from the confident pixels (NOT in the reference) ---------------------------- */
+/* A confidence-weighted push-pull.  v, out [C][H][W], 1 <= C <= 4 (DFE_E_ARG); w [H][W]; filled [H][W], may be NULL; out may be v itself.
+ * The region R = rows y0 .. y0+Ho-1, columns x0 .. x0+Wo-1 must lie inside the frame (DFE_E_SHAPE); levels >= 0 and no NULL tensor
+ * (DFE_E_ARG).  Everything in fp32 without fused multiply-adds, sums taken from 0 in the stated order, IEEE division.
+ *   Outside R: out = 0, filled = 0.  Every level below is a grid relative to R's origin.
+ *   Level 0 (Ho x Wo): a0 = min(w, 1) where w is finite, w >= 1e-6f (the fp32 constant) and every channel of v is finite; else a0 = 0.
+ *     Where a0 = 0 the value is never read into arithmetic: a NaN in a hole or under a zero weight does not leak.
+ *   Levels: H_{l+1} = (H_l + 1) / 2, W alike; Lfull = the halvings until the grid is 1 x 1; L = Lfull if levels == 0, else
+ *     min(levels, Lfull).
+ *   Push, l = 0 .. L-1, per coarse cell (i, j): the children (2i + dy, 2j + dx) in the order (0,0) (0,1) (1,0) (1,1), those outside the
+ *     level-l grid or with a = 0 skipped; s = sum a, n_c = sum a v_c.  s > 0: v_{l+1,c} = n_c / s, a_{l+1} = min(s, 1); else both 0.
+ *   Top: f_L = v_L, g_L = (a_L > 0).
+ *   Pull, l = L-1 .. 0, per level-l pixel (y, x): parent (i, j) = (y >> 1, x >> 1), i' = i + (y & 1 ? 1 : -1), j' alike; the taps
+ *     (i, j) 9/16, (i, j') 3/16, (i', j) 3/16, (i', j') 1/16 in this order, those outside the level-(l+1) grid or with g = 0 skipped;
+ *     S = sum t, U_c = sum t f_c.  S > 0: u_c = U_c / S, g_l = 1 and f_{l,c} = a_l v_{l,c} + (1 - a_l) u_c -- a_l == 1 copies v_{l,c}
+ *     (a fully trusted pixel keeps its bits), a_l == 0 copies u_c (the value under it is not read).  S == 0: f = 0, g = 0 (only with
+ *     a limited `levels`, or when nothing in R is valid).
+ *   out = f_0, filled = g_0.
+ * Launches: a push and a pull kernel per level, and from the first level whose pyramid fits LDS one workgroup's apex kernel for all
+ * levels above (option "fill_apex"); both run the same per-cell code and give the same bits.  Pyramid levels live in the ctx's side
+ * buffer: nothing is allocated per call once it has grown. */
+int dfe_fill_holes_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, int y0, int x0, int Ho, int Wo, int levels,
+                       float *out, float *filled);
 
 /* replaces: image.rgb2y as prepareInput calls it (opticalflow_model.lua:136-138; un-vendored `image`, restated: parity unpinned).
  *   rgb [3][H][W] -> y [1][H][W] = 0.299 R + 0.587 G + 0.114 B, accumulated in that order with separately rounded products and sums. */
