@@ -12,8 +12,10 @@
 // K = 256 = 4 MFMAs: lane groups 0, 1 hold patch rows 0..3 (one per MFMA; left / right four pixels of the row), groups 2, 3 hold rows 3..6;
 // the frame-0 operand, which stays in registers for the whole strip, is zero in the duplicate row 3 and in the eighth pixel.  A frame-1
 // fragment of image rows (r .. r+3) at displacement row dy is the fragment of rows (r-1 .. r+2) at dy + 1: the four fragments of a tile
-// rotate through registers (the sweep is unrolled by four) and every step loads ONE new 16-byte piece per lane and tile.  With R = 2 the
-// same frame-1 fragments serve (row y, dy) and (row y + 1, dy - 1).
+// rotate through registers (the sweep runs in rounds of four steps) and every step loads ONE new 16-byte piece per lane and tile, into the
+// registers of the oldest fragment, right after the step's MFMAs that read it: after a round every fragment is back where it started and
+// nothing is copied.  With R = 2 the same frame-1 fragments serve (row y, dy) and (row y + 1, dy - 1).  The row addresses are scalar; a
+// lane adds one 64-bit base per frame-1 row and per plane row, made once per item.
 //
 // Arg-min.  A lane keeps two running keys (i = 0, 1 and i = 2, 3): key = ((2 a'.b' - S1) << 8) + tiebreak, maximised; the plane cell of
 // frame-1 row y1, column q holds -(S1 << 8) + (1 - (q & 1)) - 6 y1 - 2 (q >> 4), so a key is ONE v_lshl_add of the MFMA result and nothing
@@ -24,7 +26,9 @@
 // [-7187712, 2408448] (147 taps of 2 * 127 * -128 - 128^2 .. 2 * 128 * 128 - 128^2), times 256 that is -1.840e9 .. 0.617e9; dfe_flow_i8_plan admits
 // (H + 1) Wp < 2^29 with Wp >= 80, so 6 y1 + 2 (q >> 4) < 6 * 2^29 / 80 + 2^29 / (40 * 8) < 4.2e7: every key, and base + 255 added
 // to one, stays inside 32 bits.  Candidates outside 0 <= q - n <= 32 (first and third tile) are masked by lane masks that live in
-// scalar registers.  The four lane groups of a pixel are combined once, on (cost, index).
+// scalar registers.  Per tile that is 4 v_lshl_add_u32 and 2 v_max3_i32, and 4 v_cndmask_b32 in a masked tile (i8_max3 keeps the compiler
+// from selecting after each max: 8 in place of 6); with the two row addresses a two-row step issues 54 vector instructions beside its 24
+// MFMAs, a one-row step 28 beside 12.  The four lane groups of a pixel are combined once, on (cost, index).
 //
 // Items.  flow_i8_items.h splits the rows into two-row and one-row wave items from the number of waves the device holds at once.
 //
@@ -55,8 +59,15 @@ struct I8Args {
 
 constexpr int kI8Waves = 4;
 
+// max(a, b, c) the compiler cannot take apart: given max(max(best, m0 ? k0 : INT_MIN), m1 ? k1 : INT_MIN) it selects after each max instead
+__device__ __forceinline__ int i8_max3(int a, int b, int c) {
+    int r;
+    asm("v_max3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
 // ------------------------------------------------------------------------------------------
-// pack: float planes -> (c0 - 128, c1 - 128, c2 - 128, 0) per pixel and the 7 x 7 x 3 sums of squares, one 64 x 16 tile per block (read with
+// pack: float planes -> (c0 - 128, c1 - 128, c2 - 128, 0) per pixel and the 7 x 7 x 3 sums of squares, one 32 x 32 tile per block (read with
 // its 6-pixel halo); a block that meets a value that is not an integer in 0..255 raises the call's verdict word
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool i8_byte(float v, unsigned *b) {
@@ -68,7 +79,7 @@ __device__ __forceinline__ int i8_sq(unsigned p) {
     const int a = (int)(p << 24) >> 24, b = (int)(p << 16) >> 24, c = (int)(p << 8) >> 24;
     return a * a + b * b + c * c;
 }
-constexpr int kPackW = 64, kPackH = 16, kPackLW = kPackW + 6, kPackLH = kPackH + 6;
+constexpr int kPackW = 32, kPackH = 32, kPackLW = kPackW + 6, kPackLH = kPackH + 6;
 __global__ __launch_bounds__(256) void flow_i8_pack_kernel(const float *__restrict__ I0, const float *__restrict__ I1, int H, int W, long long plane, int Wp,
                                                            unsigned *__restrict__ pk0, unsigned *__restrict__ pk1, int *__restrict__ s0, int *__restrict__ s1k,
                                                            unsigned *__restrict__ verdict, unsigned *__restrict__ verdict_next) {
@@ -79,20 +90,31 @@ __global__ __launch_bounds__(256) void flow_i8_pack_kernel(const float *__restri
     const int tx0 = blockIdx.x * kPackW, ty0 = blockIdx.y * kPackH;
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *verdict_next = 0u;   // (the NEXT call's word: no reset launch)
     bool bad = false;
-    for (int e = threadIdx.x; e < kPackLH * kPackLW; e += 256) {
+    // every load of the thread is issued before the first is used: one memory latency, not one per trip.  The addresses are clamped into the
+    // frame, so no load hangs on a branch; what lies outside the tile's image or outside the frame is dropped afterwards
+    constexpr int NT = (kPackLH * kPackLW + 255) / 256;
+    float v[NT][3];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int e = threadIdx.x + 256 * j;
+        const int ly = e / kPackLW, lx = e - ly * kPackLW;
+        const float *s = I + (long long)min(ty0 + ly, H - 1) * W + min(tx0 + lx, W - 1);
+        v[j][0] = s[0];
+        v[j][1] = s[plane];
+        v[j][2] = s[2 * plane];
+    }
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int e = threadIdx.x + 256 * j;
         const int ly = e / kPackLW, lx = e - ly * kPackLW;
         const int gy = ty0 + ly, gx = tx0 + lx;
-        unsigned p = 0u;
-        if (gy < H && gx < W) {
-            const float *s = I + (long long)gy * W + gx;
-            unsigned b0, b1, b2;
-            bad |= !i8_byte(s[0], &b0);
-            bad |= !i8_byte(s[plane], &b1);
-            bad |= !i8_byte(s[2 * plane], &b2);
-            p = b0 | (b1 << 8) | (b2 << 16);
-        }
+        unsigned b0, b1, b2;
+        const bool ok0 = i8_byte(v[j][0], &b0), ok1 = i8_byte(v[j][1], &b1), ok2 = i8_byte(v[j][2], &b2);
+        const bool in = gy < H && gx < W;   // (beyond the halo image, e >= kPackLH * kPackLW, nothing is written either)
+        bad |= in && !(ok0 && ok1 && ok2);
+        const unsigned p = in ? b0 | (b1 << 8) | (b2 << 16) : 0u;
         if (ly < kPackH && lx < kPackW && gy < H && gx < Wp) pk[(long long)gy * Wp + gx] = p;
-        sq[ly][lx] = i8_sq(p);
+        if (ly < kPackLH) sq[ly][lx] = i8_sq(p);
     }
     const int any = __syncthreads_or(bad ? 1 : 0);
     if (any && threadIdx.x == 0) atomicOr(verdict, 1u);
@@ -128,6 +150,7 @@ template <int R, bool FB> struct I8Sweep {
     i8x16_t A[3][4], B[R][4];
     int best[R][2];
     int sa[R];
+    unsigned lo1, lop;     // the lane's byte offsets inside a row of the packed frame 1 and of the S1 plane
     bool in0[4], in2[4];   // the first / third tile's candidate 4 g + i lies inside 0 <= q - n <= 32 (loop-invariant lane masks)
     // FB
     int cnt;
@@ -156,55 +179,79 @@ template <int R, bool FB> struct I8Sweep {
                 if (up && t == 0) v = i8x16_t{0, 0, 0, 0};
                 B[r][t] = v;
             }
-        // frame 1: the fragments of displacement row 0
+        // frame 1: the fragments of displacement row 0.  A lane's byte offset from (row, x0) is the same for the whole item: fragment rows
+        // (+ 0 | + 3 rows, pixel n + 4 h) and plane cells (4 g); at most 4 (3 Wp + 19) < 2^32 as (H + 1) Wp < 2^29, the tile's 64 T an immediate
+        lo1 = 4u * (unsigned)(3 * up * a.Wp + n + 4 * h);
+        lop = 16u * (unsigned)g;
 #pragma unroll
-        for (int T = 0; T < 3; ++T)
+        for (int t = 0; t < 4; ++t) {
+            const char *frow = reinterpret_cast<const char *>(a.pk1 + (y0 + t) * a.Wp + x0);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) A[T][t] = *reinterpret_cast<const i8x16_t *>(a.pk1 + (y0 + t + 3 * up) * a.Wp + x0 + 16 * T + n + 4 * h);
+            for (int T = 0; T < 3; ++T) A[T][t] = *reinterpret_cast<const i8x16_t *>(frow + lo1 + 64 * T);
+        }
     }
 
-    // one step: frame-1 rows y0 + s ..; PH = s mod 4, the rotation of the fragment registers
-    template <int PH> __device__ __forceinline__ void step(int s) {
-        const int h = g & 1, up = g >> 1;
-        const bool more = s + 1 < NS;
+    // one step: frame-1 rows y0 + s ..; PH = s mod 4, the rotation of the fragment registers.  S is the step's number where the step is one of
+    // the peeled ones (the lead cells' rows, the centre cells' rows, the two edge steps of a two-row item, the last step), -1 in the steady state,
+    // which tests nothing.  The fallback sweep (R = 1: every step is a displacement row) takes all of it at run time.
+    template <int PH, int S> __device__ __forceinline__ void step(int s) {
+        const bool more = FB ? s + 1 < NS : S != NS - 1;
         const int pb = 6 * (y0 + s) + (x0 >> 3);   // the plane's order term of tile 0 of this row, taken off where S1 itself is wanted
-        i8x16_t nx[3];
-        if (more) {   // the one new row of the next step's fragments (rows s + 4 | s + 7)
-#pragma unroll
-            for (int T = 0; T < 3; ++T) nx[T] = *reinterpret_cast<const i8x16_t *>(a.pk1 + (y0 + s + 4 + 3 * up) * a.Wp + x0 + 16 * T + n + 4 * h);
-        }
+        // the rows' addresses live in scalar registers; a lane adds its offset (load_operands; the compiler keeps it as a 64-bit base and adds
+        // the scalar row with one v_lshl_add_u64) and the tile's 64 T bytes
+        const char *prow = reinterpret_cast<const char *>(a.s1k + (y0 + s) * a.Wp + x0);
+        const char *frow = reinterpret_cast<const char *>(a.pk1 + (y0 + s + 4) * a.Wp + x0);   // the one new row of the next step's fragments (rows s + 4 | s + 7)
+        const unsigned lo1 = this->lo1, lop = this->lop;
         i8x16_t P[3];
 #pragma unroll
-        for (int T = 0; T < 3; ++T) P[T] = *reinterpret_cast<const i8x16_t *>(a.s1k + (y0 + s) * a.Wp + x0 + 16 * T + 4 * g);
+        for (int T = 0; T < 3; ++T) P[T] = *reinterpret_cast<const i8x16_t *>(prow + lop + 64 * T);
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int dy = s - r;
-            if ((unsigned)dy > 32u) continue;
+        for (int T = 0; T < 3; ++T) {
+            i8x16_t D[R];
+            bool on[R];
 #pragma unroll
-            for (int T = 0; T < 3; ++T) {
-                i8x16_t D = {0, 0, 0, 0};
+            for (int r = 0; r < R; ++r) {
+                on[r] = FB || S < 0 || (unsigned)(S - r) <= 32u;
+                D[r] = i8x16_t{0, 0, 0, 0};
+                if (on[r]) D[r] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][PH & 3], B[r][0], D[r], 0, 0, 0);
+            }
+            // the fragment of the oldest row has been read by the step's last MFMA that needs it: the new row is loaded into its registers, a
+            // renaming and no copy.  The barrier keeps the scheduler from hoisting the load above those MFMAs, which costs spare fragments
+            // (18 VGPRs more with R = 2, 28 with R = 1) and measured slower
+            if (more) {
+                __builtin_amdgcn_sched_barrier(0);
+                A[T][PH & 3] = *reinterpret_cast<const i8x16_t *>(frow + lo1 + 64 * T);
+            }
 #pragma unroll
-                for (int t = 0; t < 4; ++t) D = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][(t + PH) & 3], B[r][t], D, 0, 0, 0);
+            for (int r = 0; r < R; ++r) {
+                if (!on[r]) continue;
+#pragma unroll
+                for (int t = 1; t < 4; ++t) D[r] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][(t + PH) & 3], B[r][t], D[r], 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if (!on[r]) continue;
+                const int dy = s - r;
                 if constexpr (!FB) {
                     int k[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        k[i] = (int)((unsigned)D[i] << 9) + P[T][i];
+                        k[i] = (int)((unsigned)D[r][i] << 9) + P[T][i];
                         if (T == 0) k[i] = in0[i] ? k[i] : INT_MIN;
                         if (T == 2) k[i] = in2[i] ? k[i] : INT_MIN;
                     }
-                    best[r][0] = max(max(best[r][0], k[0]), k[1]);
-                    best[r][1] = max(max(best[r][1], k[2]), k[3]);
-                    if (T < 2 && dy == 0) {   // the lead cells' row
+                    best[r][0] = i8_max3(best[r][0], k[0], k[1]);
+                    best[r][1] = i8_max3(best[r][1], k[2], k[3]);
+                    if (T < 2 && S - r == 0) {   // the lead cells' row
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) lds->cost[r][n][16 * T + 4 * g + i] = (float)(sa[r] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[i]);
+                        for (int i = 0; i < 4; ++i) lds->cost[r][n][16 * T + 4 * g + i] = (float)(sa[r] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[r][i]);
                     }
-                    if (T == 1 && dy == 16) {   // the centre cell: dx = 16, q = 16 + n
+                    if (T == 1 && S - r == 16) {   // the centre cell: dx = 16, q = 16 + n
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
                             if (4 * g + i == n) {
                                 const int x = x0 + n;
-                                lds->rec[r][(x >> 3) & 1][DFE_REC_CENTRE + (x & 7)] = (float)(sa[r] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[i]);
+                                lds->rec[r][(x >> 3) & 1][DFE_REC_CENTRE + (x & 7)] = (float)(sa[r] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[r][i]);
                             }
                     }
                 } else {
@@ -215,7 +262,7 @@ template <int R, bool FB> struct I8Sweep {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int m = 4 * g + i;
-                        cv[i] = (float)(sa[0] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[i]);
+                        cv[i] = (float)(sa[0] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[r][i]);
                         bool valid = flagged;
                         if (T == 0) valid = valid && m >= n;
                         if (T == 2) valid = valid && m <= n;
@@ -244,24 +291,42 @@ template <int R, bool FB> struct I8Sweep {
                 }
             }
         }
-        if (more) {
-#pragma unroll
-            for (int T = 0; T < 3; ++T) A[T][PH & 3] = nx[T];
-        }
+    }
+
+    // four steps from step s on: S0 is the first one's number where the round holds peeled steps, -1 in the steady state
+    template <int S0> __device__ __forceinline__ void round(int s) {
+        step<0, S0 < 0 ? -1 : S0>(s);
+        step<1, S0 < 0 ? -1 : S0 + 1>(s + 1);
+        step<2, S0 < 0 ? -1 : S0 + 2>(s + 2);
+        step<3, S0 < 0 ? -1 : S0 + 3>(s + 3);
     }
 
     __device__ __forceinline__ bool fb_done() const { return FB && __builtin_amdgcn_ballot_w64(flagged && cnt < a.M) == 0ull; }
 
+    // The sweep proper runs whole rounds of four steps, after which every fragment is back in the registers it started in, and has no exit
+    // inside a round; the lead cells' rows (steps 0 .. R - 1) lie in round 0, the centre cells' rows (16 .. 16 + R - 1) in round 4, and the
+    // one or two steps past the eighth round stand alone.  The fallback sweep leaves as soon as every flagged pixel has its M hits.
     __device__ __forceinline__ void run() {
-        for (int s = 0; s < NS; s += 4) {
-            if (fb_done()) break;
-            step<0>(s);
-            if (s + 1 >= NS) break;
-            step<1>(s + 1);
-            if (s + 2 >= NS) break;
-            step<2>(s + 2);
-            if (s + 3 >= NS) break;
-            step<3>(s + 3);
+        if constexpr (FB) {
+            for (int s = 0; s < NS; s += 4) {
+                if (fb_done()) break;
+                step<0, -1>(s);
+                if (s + 1 >= NS) break;
+                step<1, -1>(s + 1);
+                if (s + 2 >= NS) break;
+                step<2, -1>(s + 2);
+                if (s + 3 >= NS) break;
+                step<3, -1>(s + 3);
+            }
+        } else {
+            round<0>(0);
+#pragma nounroll
+            for (int s = 4; s < 16; s += 4) round<-1>(s);
+            round<16>(16);
+#pragma nounroll
+            for (int s = 20; s < 32; s += 4) round<-1>(s);
+            step<0, 32>(32);
+            if constexpr (R == 2) step<1, 33>(33);
         }
     }
 };
