@@ -1,13 +1,16 @@
 """The single-scale raw-patch step as one call, with its opt-in sub-pixel flow (not in the reference: include/dfe.h).
 
-    flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False, fill=None)
+    flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False, fill=None, median=None)
         dfe_flow_depth_pair_f32 / _u8, or their _subpixel_ forms: frames -> flow, extractOutput scores, depth, depth confidence;
         consistency=tol: dfe_flow_depth_pair_fb_f32 / _u8, both directions and the forward-backward mask
         fill=True: the rejected pixels filled from the kept ones, flow_dense / filled / depth_dense
+        median=k or (k, sigma): flow (or flow_dense) through the guided weighted median, flow_median / median_valid / depth_median
     flowConsistency(fw, bw, tol, region=None)
         dfe_flow_consistency_f32: the forward-backward mask and residual of any two flow fields
     fillHoles(values, weight, region=None, levels=0)
         dfe_fill_holes_f32: a dense field from the confident pixels of a sparse one (confidence-weighted push-pull)
+    weightedMedian(values, weight=None, guide=None, k=7, sigma=0.0, region=None)
+        dfe_weighted_median_f32: per channel the lower weighted median of the k x k window, weights from a confidence plane and a guide image
     refineFlowSubpixel(img1, img2, idx, hKer, wKer, hWin, wWin)
         dfe_flow_refine_subpixel_f32: the sub-pixel flow of an arg-min index map (dfe_ssd_flow_f32's 1-based idx)
 """
@@ -27,26 +30,55 @@ def _frames(img1, img2, name):
     return img1.contiguous(), img2.contiguous()
 
 
-def _with_fill(res, fill, k, hWin, wWin, fx, fy):
-    """the three keys of flowDepthPair(..., fill=...) from the step's own outputs, which stay as they are"""
-    if fill is None or fill is False:
+def _kept_weight(res):
+    """1 where the step kept the pixel: extractOutput's score above 0 (a rejected pixel carries score 0, and so does one the gate removed)
+    and, with consistency, the forward-backward mask"""
+    wgt = (res["scores"] > 0).to(torch.float32)
+    if "consistent" in res:
+        wgt = wgt * res["consistent"]
+    return wgt
+
+
+def _median_arg(median):
+    """median=k or (k, sigma) of flowDepthPair -> (k, sigma), or None"""
+    if median is None or median is False:
+        return None
+    k, sigma = median if isinstance(median, (tuple, list)) and len(median) == 2 else (median, 0.0)
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= 15 or k % 2 == 0 or not isinstance(sigma, (int, float)):
+        raise ValueError("flowDepthPair: median=%r: an odd window 1 .. 15, or (window, sigma), expected" % (median,))
+    return k, float(sigma)
+
+
+def _with_fill(res, fill, median, guide, k, hWin, wWin, fx, fy):
+    """the keys of flowDepthPair(..., fill=..., median=...) from the step's own outputs, which stay as they are"""
+    want_fill = not (fill is None or fill is False)
+    if not want_fill and median is None:
         return res
     flow, scores = res["flow"], res["scores"]
     _, H, W = flow.shape
     Ho, Wo = H - k + 1 - hWin + 1, W - k + 1 - wWin + 1
-    wgt = (scores > 0).to(torch.float32)          # a pixel that extractOutput rejected carries score 0 (and so does one the gate removed)
-    if "consistent" in res:
-        wgt = wgt * res["consistent"]
-    dense, filled = fillHoles(flow, wgt, ((H - Ho) // 2, (W - Wo) // 2, Ho, Wo), 0 if fill is True else int(fill))
-    depth = torch.empty_like(scores)
-    conf = torch.empty_like(scores)
+    R = ((H - Ho) // 2, (W - Wo) // 2, Ho, Wo)
+    wgt = _kept_weight(res)
     ctx = get_ctx(flow)
-    ctx.check(lib().dfe_flow_to_depth_cartesian(ctx.handle, ptr(dense), H, W, fx, fy, 0, ptr(depth), ptr(conf)))
-    res.update(flow_dense=dense, filled=filled, depth_dense=depth)
+
+    def depth_of(field):
+        depth = torch.empty_like(scores)
+        conf = torch.empty_like(scores)
+        ctx.check(lib().dfe_flow_to_depth_cartesian(ctx.handle, ptr(field), H, W, fx, fy, 0, ptr(depth), ptr(conf)))
+        return depth
+
+    src = flow
+    if want_fill:
+        dense, filled = fillHoles(flow, wgt, R, 0 if fill is True else int(fill))
+        res.update(flow_dense=dense, filled=filled, depth_dense=depth_of(dense))
+        src, wgt = dense, torch.where(wgt > 0, filled, 0.25 * filled)   # a filled value votes, but weighs less than a measured one
+    if median is not None:
+        med, valid = weightedMedian(src, wgt, guide.to(torch.float32), median[0], median[1], R)
+        res.update(flow_median=med, median_valid=valid, depth_median=depth_of(med))
     return res
 
 
-def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False, fill=None):
+def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False, fill=None, median=None):
     """One frame pair through the single-scale step: C x H x W frames (float32, or uint8 read as float(byte) * scale), a k x k patch,
     an hWin x wWin search window, foe = (x, y) focus of expansion.  Returns dict(flow [2][H][W] (y, x), scores, depth, depth_conf [H][W]),
     zero outside the centre-pasted output region.  subpixel=True: the flow is refined to sub-pixel precision and depth follows it;
@@ -56,7 +88,12 @@ def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False
     where the forward flow leaves the output region or a flow is not finite).  gate=True multiplies scores and depth_conf by consistent.
     fill=True (or an int: the `levels` of fillHoles): the dict gains flow_dense [2][H][W] = fillHoles(flow, wgt, R, levels) with R the
     output region and wgt 1 where scores > 0 (and, with consistency, where consistent is 1 as well), filled [H][W] (1 where a value was
-    found), and depth_dense [H][W], the depth of flow_dense (dfe_flow_to_depth_cartesian, fix_dot = 0).  The other keys are unchanged."""
+    found), and depth_dense [H][W], the depth of flow_dense (dfe_flow_to_depth_cartesian, fix_dot = 0).  The other keys are unchanged.
+    median=k or (k, sigma): the dict gains flow_median [2][H][W], median_valid [H][W] = weightedMedian(src, wgt, img1 as float32, k, sigma, R)
+    and depth_median [H][W], the depth of flow_median made as depth_dense is.  Without fill, src = flow and wgt is the plane above; with
+    fill, src = flow_dense and wgt = filled, 0.25 where the pixel was a hole.  sigma is in the frame's own units (bytes for uint8 frames);
+    0, the default, is the unguided median.  Frames of more than 4 channels cannot guide (ValueError).  The other keys are unchanged."""
+    median = _median_arg(median)
     a, b = _frames(img1, img2, "flowDepthPair")
     C, H, W = a.shape
     flow = torch.empty((2, H, W), dtype=torch.float32, device=a.device)
@@ -77,7 +114,7 @@ def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False
             rc = l.dfe_flow_depth_pair_fb_f32(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, threshold, *tail)
         ctx.check(rc)
         return _with_fill({"flow": flow, "scores": scores, "depth": depth, "depth_conf": conf, "flow_bw": bw, "consistent": mask, "consistency_err": err},
-                          fill, k, hWin, wWin, fx, fy)
+                          fill, median, a, k, hWin, wWin, fx, fy)
     if a.dtype == torch.uint8:
         fn = l.dfe_flow_depth_pair_subpixel_u8 if subpixel else l.dfe_flow_depth_pair_u8
         rc = fn(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, threshold, float(scale), ptr(flow), ptr(scores), ptr(depth), ptr(conf))
@@ -85,7 +122,7 @@ def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False
         fn = l.dfe_flow_depth_pair_subpixel_f32 if subpixel else l.dfe_flow_depth_pair_f32
         rc = fn(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, threshold, ptr(flow), ptr(scores), ptr(depth), ptr(conf))
     ctx.check(rc)
-    return _with_fill({"flow": flow, "scores": scores, "depth": depth, "depth_conf": conf}, fill, k, hWin, wWin, fx, fy)
+    return _with_fill({"flow": flow, "scores": scores, "depth": depth, "depth_conf": conf}, fill, median, a, k, hWin, wWin, fx, fy)
 
 
 def flowConsistency(fw, bw, tol, region=None):
@@ -127,6 +164,37 @@ def fillHoles(values, weight, region=None, levels=0):
     ctx = get_ctx(values)
     ctx.check(lib().dfe_fill_holes_f32(ctx.handle, ptr(values), C, H, W, ptr(weight), y0, x0, Ho, Wo, int(levels), ptr(out), ptr(filled)))
     return out, filled
+
+
+def weightedMedian(values, weight=None, guide=None, k=7, sigma=0.0, region=None):
+    """Guided weighted median (include/dfe.h: dfe_weighted_median_f32): values float32 [C][H][W], 1 <= C <= 4; weight float32 [H][W] or None
+    (all ones; below 1e-6 or not finite: the sample does not exist; above 1 counts as 1); guide float32 [Cg][H][W], Cg <= 4, or None;
+    k odd in 1 .. 15; sigma > 0 with a guide: a sample weighs max(0, 1 - |guide(p) - guide(q)|^2 / sigma^2) times its weight, else the
+    weight alone; region = (y0, x0, Ho, Wo), the whole frame by default.  Returns (out [C][H][W], filtered [H][W]): per channel the lower
+    weighted median of the k x k window clipped to the region (the bits of an input sample), filtered 1 where the window held a sample
+    of positive weight, else both 0; both 0 outside the region."""
+    if values.dim() != 3 or not 1 <= values.shape[0] <= 4:
+        raise ValueError("weightedMedian: values C x H x W (C = 1 .. 4) expected, got %s" % (tuple(values.shape),))
+    if weight is not None and (weight.dim() != 2 or tuple(weight.shape) != tuple(values.shape[1:])):
+        raise ValueError("weightedMedian: weight H x W expected, got %s for values %s" % (tuple(weight.shape), tuple(values.shape)))
+    if guide is not None and (guide.dim() != 3 or not 1 <= guide.shape[0] <= 4 or tuple(guide.shape[1:]) != tuple(values.shape[1:])):
+        raise ValueError("weightedMedian: guide Cg x H x W (Cg = 1 .. 4) expected, got %s for values %s" % (tuple(guide.shape), tuple(values.shape)))
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= 15 or k % 2 == 0:
+        raise ValueError("weightedMedian: k=%r must be odd, 1 .. 15" % (k,))
+    planes = [t for t in (values, weight, guide) if t is not None]
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in planes):
+        raise TypeError("weightedMedian: float32 CUDA tensors expected")
+    if any(t.device != values.device for t in planes):
+        raise ValueError("weightedMedian: tensors on different devices")
+    values, weight, guide = (None if t is None else t.contiguous() for t in (values, weight, guide))
+    C, H, W = values.shape
+    y0, x0, Ho, Wo = (0, 0, H, W) if region is None else (int(v) for v in region)
+    out = torch.empty_like(values)
+    filtered = torch.empty((H, W), dtype=torch.float32, device=values.device)
+    ctx = get_ctx(values)
+    ctx.check(lib().dfe_weighted_median_f32(ctx.handle, ptr(values), C, H, W, None if weight is None else ptr(weight), None if guide is None else ptr(guide),
+                                            0 if guide is None else guide.shape[0], float(sigma), k, y0, x0, Ho, Wo, ptr(out), ptr(filtered)))
+    return out, filtered
 
 
 def refineFlowSubpixel(img1, img2, idx, hKer, wKer, hWin, wWin):

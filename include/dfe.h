@@ -629,6 +629,32 @@ int dfe_flow_depth_pair_fb_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1
  * buffer: nothing is allocated per call once it has grown. */
 int dfe_fill_holes_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, int y0, int x0, int Ho, int Wo, int levels,
                        float *out, float *filled);
+/* ---- guided weighted median: outliers out, motion boundaries kept (NOT in the reference) --------------------- */
+/* Per channel the lower weighted median of the k x k window, the weights from a confidence plane and, optionally, from a guide image.
+ * v, out [C][H][W], 1 <= C <= 4; w [H][W] or NULL (all ones); guide [Cg][H][W], 0 <= Cg <= 4, or NULL / Cg = 0: no range term; k odd in
+ * 1 .. 15; filtered [H][W] or NULL (DFE_E_ARG for each, and for v or out NULL).  The region R = rows y0 .. y0+Ho-1, columns
+ * x0 .. x0+Wo-1 must be non-empty and lie inside the frame (DFE_E_SHAPE).  Neighbours are read: out and filtered must not overlap v, w,
+ * guide or each other (DFE_E_ARG).  Asynchronous on the ctx's stream; allocates nothing.
+ *   Validity (dfe_fill_holes_f32's rule): a(q) = min(w(q), 1) where w(q) is finite, w(q) >= 1e-6f (the fp32 constant) and every channel
+ *     of v(q) is finite; else a(q) = 0.  With w == NULL, w(q) = 1.
+ *   Range term, in fp32 without fused multiply-adds, no division and no exp on the device: with a guide and sigma > 0 the host forms
+ *     inv_s2 = 1.0f / (sigma * sigma) in float; d2 = sum_c (g_c(p) - g_c(q))^2 in channel order starting from the first square;
+ *     r = max(0, 1 - d2 * inv_s2); an r that is not finite counts as 0.  Without a guide, or with sigma <= 0 (or NaN): r = 1.
+ *   Integer sample weight: wt(p, q) = (uint32)((a(q) * r) * 4096.0f + 0.5f), and wt(p, q) = 0 where a(q) = 0.  Everything behind this
+ *     is integer arithmetic: the sums do not depend on their order and the result is exact whatever the kernel's schedule.
+ *   Window: the k x k pixels centred on p, clipped to R -- samples outside R do not exist.
+ *   Per pixel p of R: T = sum_q wt(p, q).  T == 0: out = 0 in every channel, filtered = 0.  Else filtered = 1 and, per channel
+ *     separately, out_c(p) = the sample value v_c(q*) with the smallest key such that 2 S >= T, S = the sum of wt(p, q) over the samples
+ *     whose key is at most that key: the LOWER weighted median.  Keys are the order-preserving integer image of the float's bits
+ *     (u = bits; key = u with the sign bit set if it was clear, ~u if it was set), so -0 sorts below +0; the output's bits are those of
+ *     an input sample.
+ *   Outside R: out = 0, filtered = 0, written by the same launch.
+ * Consequences: k = 1 copies v where wt > 0; unit weights and a full window give the plain median; a NaN or Inf under a = 0 never
+ * leaks; a NaN in the guide at p gives T = 0.
+ * One launch: a workgroup per 4 x 64 tile of the frame with its halo in LDS, a thread per pixel bisecting the key interval of its
+ * window, all channels in one pass. */
+int dfe_weighted_median_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, const float *guide, int Cg, float sigma,
+                            int k, int y0, int x0, int Ho, int Wo, float *out, float *filtered);
 
 /* replaces: image.rgb2y as prepareInput calls it (opticalflow_model.lua:136-138; un-vendored `image`, restated: parity unpinned).
  *   rgb [3][H][W] -> y [1][H][W] = 0.299 R + 0.587 G + 0.114 B, accumulated in that order with separately rounded products and sums. */
