@@ -26,6 +26,9 @@ no CPU fallback -- a missing library or device raises.
                                                         confidence-weighted push-pull, and that operator on any planes -- subpixel.py)
     flowDepthPair(..., median=k | (k, sigma)), weightedMedian   (not in the reference: the flow through a confidence-weighted median
                                                         guided by the first frame, and that operator on any planes -- subpixel.py)
+    guidedUpsample                                      (not in the reference: a flow or depth field back at the camera's resolution by joint
+                                                        bilateral upsampling with a confidence plane, holes skipped, motion boundaries
+                                                        kept by the frame itself -- subpixel.py)
     radialFlowDepth(..., subpixel=True), refineRadialFlowSubpixel   (not in the reference: sub-pixel radial flow -- radial.py)
     getModel(geometry).forwardFlow                      (a trained single-scale model per frame pair in one call,
                                                         output_extraction_method 'max' or 'mean' -- network.py)
@@ -54,7 +57,7 @@ from .opticalflow_model import (  # noqa: F401
     rgb2y,
 )
 from . import version2  # noqa: F401
-from .subpixel import flowDepthPair, refineFlowSubpixel, flowConsistency, fillHoles, weightedMedian  # noqa: F401
+from .subpixel import flowDepthPair, refineFlowSubpixel, flowConsistency, fillHoles, weightedMedian, guidedUpsample  # noqa: F401
 from .multiscale import CascadingAddTable, MultiscaleModel, MultiscalePrefilter, getModelMultiscale, getMultiscalePrefilter  # noqa: F401
 from .network import getFilter, getFilterRadial, getModel, tables_random  # noqa: F401
 from .radial import (getRMax, getC2PMask, getP2CMask, cartesian2polar, flow2depth, getKOutput, getP2CMaskOF,  # noqa: F401

@@ -71,6 +71,8 @@ PROTOTYPES = {
     "dfe_fill_holes_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
     "dfe_weighted_median_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int, C.c_float] + [C.c_int] * 5
                                 + [C.c_void_p, C.c_void_p]),
+    "dfe_guided_upsample_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int,
+                                          C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dfe_flow_depth_pair_fb_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_float, C.c_double, C.c_int, C.c_float, C.c_int]
                                    + [C.c_void_p] * 7),
     "dfe_flow_depth_pair_fb_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_float, C.c_double, C.c_float, C.c_int, C.c_float,

@@ -100,6 +100,7 @@ int dfe_flow_depth_pair_fb_f32(dfe_ctx *ctx, const float *I0, const float *I1, i
 int dfe_flow_depth_pair_fb_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x, float foe_y, double extract_threshold, float scale, int subpixel, float tol, int gate, float *flow, float *scores, float *depth, float *depth_conf, float *flow_bw, float *mask, float *err);
 int dfe_fill_holes_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, int y0, int x0, int Ho, int Wo, int levels, float *out, float *filled);
 int dfe_weighted_median_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, const float *guide, int Cg, float sigma, int k, int y0, int x0, int Ho, int Wo, float *out, float *filtered);
+int dfe_guided_upsample_f32(dfe_ctx *ctx, const float *v, int C, int Hl, int Wl, const float *w, const float *guide_hi, const float *guide_lo, int Cg, float sigma, int r, const float *gain, int Hh, int Wh, float *out, float *valid);
 int dfe_rgb2y_f32(dfe_ctx *ctx, const float *rgb, int H, int W, float *y);
 int dfe_min_dim0_f32(dfe_ctx *ctx, const float *in, int n, int64_t M, float *val, int64_t *idx);
 int dfe_flow_depth_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x, float foe_y, double extract_threshold, float scale, float *flow, float *scores, float *depth, float *depth_conf);

@@ -11,9 +11,14 @@
         dfe_fill_holes_f32: a dense field from the confident pixels of a sparse one (confidence-weighted push-pull)
     weightedMedian(values, weight=None, guide=None, k=7, sigma=0.0, region=None)
         dfe_weighted_median_f32: per channel the lower weighted median of the k x k window, weights from a confidence plane and a guide image
+    guidedUpsample(values, size=None, weight=None, guide=None, guide_lo=None, r=2, sigma=0.0, gain=None)
+        dfe_guided_upsample_f32: a field at a higher resolution, the mean of the low-resolution samples around each pixel weighted by a tent,
+        a confidence plane and the agreement of the frame at both resolutions (joint bilateral upsampling)
     refineFlowSubpixel(img1, img2, idx, hKer, wKer, hWin, wWin)
         dfe_flow_refine_subpixel_f32: the sub-pixel flow of an arg-min index map (dfe_ssd_flow_f32's 1-based idx)
 """
+import ctypes
+
 import torch
 
 from ._lib import lib
@@ -195,6 +200,74 @@ def weightedMedian(values, weight=None, guide=None, k=7, sigma=0.0, region=None)
     ctx.check(lib().dfe_weighted_median_f32(ctx.handle, ptr(values), C, H, W, None if weight is None else ptr(weight), None if guide is None else ptr(guide),
                                             0 if guide is None else guide.shape[0], float(sigma), k, y0, x0, Ho, Wo, ptr(out), ptr(filtered)))
     return out, filtered
+
+
+def guidedUpsample(values, size=None, weight=None, guide=None, guide_lo=None, r=2, sigma=0.0, gain=None):
+    """Guided upsampling (include/dfe.h: dfe_guided_upsample_f32): values float32 [C][Hl][Wl], 1 <= C <= 4, to size = (Hh, Wh) >= (Hl, Wl),
+    by default the guide's; weight float32 [Hl][Wl] or None (all ones; below 1e-6 or not finite: the sample does not exist; above 1 counts
+    as 1); guide float32 [Cg][Hh][Wh] or [Hh][Wh] (one channel), Cg <= 4, or None; guide_lo the same frame at [Cg][Hl][Wl], by default
+    imageScale(guide, Wl, Hl); r in 1 .. 4: 2r x 2r low-resolution samples around each pixel under a tent of radius r; sigma > 0 with a
+    guide: a sample also weighs max(0, 1 - |guide(p) - guide_lo(q)|^2 / sigma^2); gain None, C numbers, or "flow" for C = 2 planes (y, x):
+    (Hh / Hl, Wh / Wl), so that vectors stay in pixels of the grid they are on.  Returns (out [C][Hh][Wh], valid [Hh][Wh]): the weighted
+    mean times gain and 1 where a sample was found, else both 0."""
+    if values.dim() != 3 or not 1 <= values.shape[0] <= 4:
+        raise ValueError("guidedUpsample: values C x Hl x Wl (C = 1 .. 4) expected, got %s" % (tuple(values.shape),))
+    C, Hl, Wl = values.shape
+    if weight is not None and (weight.dim() != 2 or tuple(weight.shape) != (Hl, Wl)):
+        raise ValueError("guidedUpsample: weight Hl x Wl expected, got %s for values %s" % (tuple(weight.shape), tuple(values.shape)))
+    if guide is None and guide_lo is not None:
+        raise ValueError("guidedUpsample: guide_lo without a guide")
+    if guide is not None:
+        if guide.dim() == 2:
+            guide = guide.unsqueeze(0)
+        if guide.dim() != 3 or not 1 <= guide.shape[0] <= 4:
+            raise ValueError("guidedUpsample: guide Cg x Hh x Wh (Cg = 1 .. 4) or Hh x Wh expected, got %s" % (tuple(guide.shape),))
+        if size is None:
+            size = tuple(guide.shape[1:])
+    if size is None:
+        raise ValueError("guidedUpsample: without a guide the size = (Hh, Wh) must be given")
+    if not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(n, int) and not isinstance(n, bool) for n in size)):
+        raise ValueError("guidedUpsample: size=%r: (Hh, Wh) expected" % (size,))
+    Hh, Wh = size
+    if not (Hl <= Hh <= 32768 and Wl <= Wh <= 32768 and Hl >= 1 and Wl >= 1):
+        raise ValueError("guidedUpsample: size %d x %d for values %d x %d: every size 1 .. 32768, and none may shrink" % (Hh, Wh, Hl, Wl))
+    if guide is not None and tuple(guide.shape[1:]) != (Hh, Wh):
+        raise ValueError("guidedUpsample: guide %s for the size %d x %d" % (tuple(guide.shape), Hh, Wh))
+    if guide_lo is not None:
+        if guide_lo.dim() == 2:
+            guide_lo = guide_lo.unsqueeze(0)
+        if tuple(guide_lo.shape) != (guide.shape[0], Hl, Wl):
+            raise ValueError("guidedUpsample: guide_lo %d x %d x %d expected, got %s" % (guide.shape[0], Hl, Wl, tuple(guide_lo.shape)))
+    if not isinstance(r, int) or isinstance(r, bool) or not 1 <= r <= 4:
+        raise ValueError("guidedUpsample: r=%r must be 1 .. 4" % (r,))
+    if isinstance(gain, str):
+        if gain != "flow" or C != 2:
+            raise ValueError("guidedUpsample: gain=%r: \"flow\" is for C = 2 planes (y, x)" % (gain,))
+        gain = (Hh / Hl, Wh / Wl)
+    if gain is not None:
+        try:
+            gain = [float(g) for g in gain]
+        except TypeError:
+            raise ValueError("guidedUpsample: gain=%r: None, %d numbers or \"flow\" expected" % (gain, C)) from None
+        if len(gain) != C or not all(g == g and abs(g) != float("inf") for g in gain):
+            raise ValueError("guidedUpsample: gain=%r: %d finite numbers expected" % (gain, C))
+    planes = [t for t in (values, weight, guide, guide_lo) if t is not None]
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in planes):
+        raise TypeError("guidedUpsample: float32 CUDA tensors expected")
+    if any(t.device != values.device for t in planes):
+        raise ValueError("guidedUpsample: tensors on different devices")
+    if guide is not None and guide_lo is None:
+        from .stream import imageScale
+
+        guide_lo = imageScale(guide, Wl, Hl)
+    values, weight, guide, guide_lo = (None if t is None else t.contiguous() for t in (values, weight, guide, guide_lo))
+    out = torch.empty((C, Hh, Wh), dtype=torch.float32, device=values.device)
+    valid = torch.empty((Hh, Wh), dtype=torch.float32, device=values.device)
+    ctx = get_ctx(values)
+    ctx.check(lib().dfe_guided_upsample_f32(ctx.handle, ptr(values), C, Hl, Wl, None if weight is None else ptr(weight), None if guide is None else ptr(guide),
+                                            None if guide_lo is None else ptr(guide_lo), 0 if guide is None else guide.shape[0], float(sigma), r,
+                                            None if gain is None else (ctypes.c_float * C)(*gain), Hh, Wh, ptr(out), ptr(valid)))
+    return out, valid
 
 
 def refineFlowSubpixel(img1, img2, idx, hKer, wKer, hWin, wWin):

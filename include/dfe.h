@@ -655,6 +655,39 @@ int dfe_fill_holes_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const 
  * window, all channels in one pass. */
 int dfe_weighted_median_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, const float *guide, int Cg, float sigma,
                             int k, int y0, int x0, int Ho, int Wo, float *out, float *filtered);
+/* ---- guided upsampling: a field back at the camera's resolution, holes skipped, motion boundaries kept (NOT in the reference; DESIGN
+ * section 4.28) -------------------------------------------------------------------------------------------------------------------- */
+/* Joint bilateral upsampling (Kopf et al. 2007) with a confidence plane: each full-resolution pixel p takes the mean of the (2r)^2
+ * low-resolution samples q around it, weighted by a tent in each axis, by the sample's confidence and by how much the full-resolution
+ * frame at p looks like the low-resolution frame at q.
+ * v [C][Hl][Wl], out [C][Hh][Wh], 1 <= C <= 4; w [Hl][Wl] or NULL (all ones); guide_hi [Cg][Hh][Wh] and guide_lo [Cg][Hl][Wl],
+ * 0 <= Cg <= 4: both given when Cg > 0, both NULL when Cg = 0 (no range term); r in 1 .. 4; valid [Hh][Wh] or NULL; gain C finite HOST
+ * floats or NULL (ones) -- DFE_E_ARG for each, and for v or out NULL.  Every size in 1 .. 32768 with Hl <= Hh and Wl <= Wh (it is an
+ * upsampler; equal sizes are allowed), else DFE_E_SHAPE.  out and valid must not overlap an input or each other (DFE_E_ARG).
+ * Asynchronous on the ctx's stream; allocates nothing.
+ * Everything in fp32 without fused multiply-adds, the products rounded separately in the grouping written here, IEEE division.
+ *   Validity (dfe_fill_holes_f32's rule): a(q) = min(w(q), 1) where w(q) is finite, w(q) >= 1e-6f (the fp32 constant) and every channel
+ *     of v(q) is finite; else a(q) = 0, and v(q) is never read into arithmetic.
+ *   Coordinates (dfe_image_scale_f32's mapping), per axis in exact int64 (x shown; y alike with Hl, Hh): num = (2 x + 1) Wl - Wh,
+ *     den = 2 Wh; j0 = floor(num / den) (-1 for a negative num); the taps j = j0 - r + 1 .. j0 + r; n_j = r den - |num - j den|.  A tap
+ *     with j outside [0, Wl) or with n_j = 0 does not exist: edge taps are dropped, not clamped, and the normalisation makes up for
+ *     them.  tx_j = float32(double(n_j) / double(r den)): the tent 1 - |u - j| / r at u = num / den.
+ *   Range term (dfe_weighted_median_f32's rule): with a guide and sigma > 0 the host forms inv_s2 = 1.0f / (sigma * sigma) in float;
+ *     d2 = sum_c (guide_hi_c(p) - guide_lo_c(q))^2 in channel order starting from the first square; rr = max(0, 1 - d2 * inv_s2); an rr
+ *     that is not finite counts as 0.  Without a guide, or with sigma <= 0 (or NaN): rr = 1.
+ *   Sample weight: wt = (a(q) * rr) * (ty_i * tx_j).  A sample with a(q) = 0 or wt = 0 does not exist.
+ *   Sums over the existing samples, rows ascending and columns ascending within a row, each started from its first term (not from 0:
+ *     -0 survives): S = sum wt, N_c = sum wt * v_c(q).
+ *   At least one sample: out_c(p) = gain_c * (N_c / S), valid(p) = 1.  None: out_c(p) = 0, valid(p) = 0.
+ * Consequences: equal sizes, r = 1, no guide and w NULL give a bit copy times gain; r = 1 without guide or holes is
+ * dfe_image_scale_f32's bilinear interpolation up to rounding (a dropped edge tap equals a clamped one); a NaN or Inf under a = 0 never
+ * leaks; a NaN in guide_hi at p gives valid(p) = 0.  For a flow field gain = (Hh / Hl, Wh / Wl) keeps the vectors in pixels of the
+ * grid they are on.
+ * One launch: a workgroup per 8 x 64 tile of the output stages the tile's low-resolution footprint, at most (7 + 2r) x (63 + 2r)
+ * samples, and the tents of its rows and columns in LDS; a thread per output pixel. */
+int dfe_guided_upsample_f32(dfe_ctx *ctx, const float *v, int C, int Hl, int Wl, const float *w, const float *guide_hi,
+                            const float *guide_lo, int Cg, float sigma, int r, const float *gain, int Hh, int Wh, float *out,
+                            float *valid);
 
 /* replaces: image.rgb2y as prepareInput calls it (opticalflow_model.lua:136-138; un-vendored `image`, restated: parity unpinned).
  *   rgb [3][H][W] -> y [1][H][W] = 0.299 R + 0.587 G + 0.114 B, accumulated in that order with separately rounded products and sums. */
