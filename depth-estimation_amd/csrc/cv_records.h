@@ -96,6 +96,7 @@ inline TailOut dfe_tailout(int64_t *idx, float *best, float *fy, float *fx, floa
 // flow -> depth of one pixel (i, j) with displacement (dy, dx): the quirk-preserving cartesian formula of
 // test_opticalflow.lua:143-216 (same arithmetic as flow_to_depth_cartesian_kernel)
 __device__ __forceinline__ void pair_depth_px(int i, int j, float dy, float dx, float mw, float mh, float infty, float *r_out, float *c_out) {
+#pragma clang fp contract(off)   // products rounded one by one, as the reference's C (and the oracle) do
     const float py = (float)i - mh, px = (float)j - mw;
     const float pn = (float)sqrt((double)(px * px + py * py));
     const float dn = (float)sqrt((double)(dx * dx + dy * dy));

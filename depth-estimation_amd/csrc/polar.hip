@@ -3,8 +3,11 @@
 //             cartesian2polar = image.warp(.., 'bilinear', false)   radial/cartesian2polar.lua:91-93
 //             flow2depth (inline C do_depths)          radial/radial_opticalflow_display.lua:6-58
 // The reference's inline C keeps `float` variables but calls the double libm functions (pow, sin, cos,
-// atan2, fmod, sqrt) on them; the kernels do the same promotions so results agree to the last float bit
-// wherever the device libm is correctly rounded.
+// atan2, fmod, sqrt) on them; the kernels do the same promotions and round every product by itself
+// (`fp contract(off)`: hipcc fuses a * a + b * b into a multiply and an fma otherwise, gcc's build of the
+// inline C and of the oracle does not), so flow2depth agrees with the oracle to the last float bit (sqrt of
+// a double and division are correctly rounded) and the grids wherever the device's pow / sin / cos / atan2
+// round as glibc's do (tests/test_gpu_postfilters.py: within one float ulp).
 #include "dfe_internal.h"
 #include <cmath>
 
@@ -12,6 +15,7 @@ namespace {
 
 __global__ void c2p_kernel(int wdst, int hdst, int Wp, int lpad, float xc, float yc, float kr, float ktheta, float alpha,
                            float *__restrict__ mask) {
+#pragma clang fp contract(off)   // products rounded one by one, as the reference's C (and the oracle) do
     const long long total = (long long)hdst * wdst;
     float *m0 = mask, *m1 = mask + (long long)hdst * Wp;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
@@ -39,6 +43,7 @@ __global__ void c2p_pad_kernel(int wdst, int hdst, int Wp, int lpad, int rpad, f
 
 __global__ void p2c_kernel(int wdst, int hdst, float xc, float yc, float kx, float ky, float pi2, float invalpha,
                            float *__restrict__ mask) {
+#pragma clang fp contract(off)   // products rounded one by one, as the reference's C (and the oracle) do
     const long long total = (long long)hdst * wdst;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
         int i = (int)(e / wdst), j = (int)(e - (long long)i * wdst);
@@ -56,8 +61,8 @@ __global__ void warp_bilinear_kernel(const float *__restrict__ img, int C, int H
     const long long P = (long long)Hd * Wd;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < P; e += (long long)gridDim.x * blockDim.x) {
         float fy = mask[e], fx = mask[P + e];
-        fy = fy < 0 ? 0 : (fy > (float)(H - 1) ? (float)(H - 1) : fy);
-        fx = fx < 0 ? 0 : (fx > (float)(W - 1) ? (float)(W - 1) : fx);
+        fy = fy >= 0 ? fminf(fy, (float)(H - 1)) : 0;   // (NaN -> 0: a NaN passes `fy < 0 ? .. : fy > H-1 ? ..` unclamped)
+        fx = fx >= 0 ? fminf(fx, (float)(W - 1)) : 0;
         int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
         int y1 = y0 + 1 < H ? y0 + 1 : H - 1, x1 = x0 + 1 < W ? x0 + 1 : W - 1;
         float wy = fy - (float)y0, wx = fx - (float)x0;
@@ -72,6 +77,7 @@ __global__ void warp_bilinear_kernel(const float *__restrict__ img, int C, int H
 
 __global__ void flow_to_depth_radial_kernel(const float *__restrict__ rflow, int H, int W, float xc, float yc, float infty,
                                             float *__restrict__ depth, float *__restrict__ conf) {
+#pragma clang fp contract(off)   // products rounded one by one, as the reference's C (and the oracle) do
     const long long P = (long long)H * W;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < P; e += (long long)gridDim.x * blockDim.x) {
         int i = (int)(e / W), j = (int)(e - (long long)i * W);
@@ -135,6 +141,8 @@ int dfe_polar_grid_c2p_f32(dfe_ctx *ctx, int wsrc, int hsrc, int wdst, int hdst,
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, mask && wdst > 0 && hdst > 0 && lpadding >= 0 && rpadding >= 0 && lpadding <= wdst && rpadding <= wdst,
                 DFE_E_ARG, "dfe_polar_grid_c2p_f32: bad argument");
+    // (alpha < 0: pow(0, alpha) = inf in row 0, inf * sin(0) = NaN coordinates)
+    DFE_REQUIRE(ctx, rmax > 0 && alpha > 0, DFE_E_ARG, "dfe_polar_grid_c2p_f32: rmax=%g alpha=%g must be positive", (double)rmax, (double)alpha);
     const int Wp = wdst + lpadding + rpadding;
     const float kr = (float)((double)rmax / pow((double)hdst, (double)alpha));   // cartesian2polar.lua:13
     const float ktheta = (float)(2 * M_PI / wdst);                                 // :14

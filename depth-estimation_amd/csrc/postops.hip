@@ -427,6 +427,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64) void flow_tail_kernel(const fl
 // ---- A12 (i): flow -> depth, replaces the inline-C `radial` of test_opticalflow.lua:143-189 ----
 __global__ void flow_to_depth_cart_kernel(const float *__restrict__ flow, int H, int W, float mw, float mh, float infty,
                                           int fix_dot, float *__restrict__ depth, float *__restrict__ conf) {
+#pragma clang fp contract(off)   // products rounded one by one, as the reference's C (and the oracle) do
     const long long P = (long long)H * W;
     for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < P; p += (long long)gridDim.x * blockDim.x) {
         int i = (int)(p / W), j = (int)(p - (long long)i * W);

@@ -31,8 +31,8 @@ namespace {
 
 __device__ __forceinline__ float bilinear_at(const float *__restrict__ p, int H, int W, float fy, float fx) {
 #pragma clang fp contract(off)
-    fy = fy < 0 ? 0 : (fy > (float)(H - 1) ? (float)(H - 1) : fy);
-    fx = fx < 0 ? 0 : (fx > (float)(W - 1) ? (float)(W - 1) : fx);
+    fy = fy >= 0 ? fminf(fy, (float)(H - 1)) : 0;   // (NaN -> 0: a NaN passes `fy < 0 ? .. : fy > H-1 ? ..` unclamped)
+    fx = fx >= 0 ? fminf(fx, (float)(W - 1)) : 0;
     const int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
     const int y1 = y0 + 1 < H ? y0 + 1 : H - 1, x1 = x0 + 1 < W ? x0 + 1 : W - 1;
     const float wy = fy - (float)y0, wx = fx - (float)x0;
@@ -68,8 +68,8 @@ __global__ __launch_bounds__(256) void interleave_pair_kernel(const float *__res
 
 __device__ __forceinline__ float4 bilinear4_at(const float4 *__restrict__ p, int H, int W, float fy, float fx) {
 #pragma clang fp contract(off)
-    fy = fy < 0 ? 0 : (fy > (float)(H - 1) ? (float)(H - 1) : fy);
-    fx = fx < 0 ? 0 : (fx > (float)(W - 1) ? (float)(W - 1) : fx);
+    fy = fy >= 0 ? fminf(fy, (float)(H - 1)) : 0;   // (NaN -> 0: a NaN passes `fy < 0 ? .. : fy > H-1 ? ..` unclamped)
+    fx = fx >= 0 ? fminf(fx, (float)(W - 1)) : 0;
     const int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
     const int y1 = y0 + 1 < H ? y0 + 1 : H - 1, x1 = x0 + 1 < W ? x0 + 1 : W - 1;
     const float wy = fy - (float)y0, wx = fx - (float)x0;
@@ -86,6 +86,7 @@ __global__ __launch_bounds__(256) void polar_warp_pair_kernel(const float *__res
                                                              int wdst, int hdst, int Wp, int lpad, float xc, float yc, const float *__restrict__ rt,
                                                              const double *__restrict__ sn, const double *__restrict__ cs, float *__restrict__ o0,
                                                              float *__restrict__ o1) {
+#pragma clang fp contract(off)   // r * sin + yc in doubles rounded one by one, as c2p_kernel (polar.hip): the staged path's grid, bit for bit
     // A block = a patch of 8 radii x 32 angles of the polar image: its 1024 taps fall into a compact piece of the frame (an arc of ~50
     // pixels, 8 deep: ~60 cache lines), where 256 consecutive angles of ONE radius -- the first version -- ran along 400 pixels of a
     // circle, nearly every tap its own line (176 MB gathered for 45 MB written, 76 % of the wave-cycles waiting: profiles/r04_af).  The
@@ -360,6 +361,7 @@ __global__ __launch_bounds__(256) void p2c_flow_depth_kernel(const float *__rest
                                                             float yc, float kx, float ky, float pi2, float invalpha, float cx2, float cy2,
                                                             float infty, float *__restrict__ cart, float *__restrict__ depth,
                                                             float *__restrict__ conf) {
+#pragma clang fp contract(off)   // products rounded one by one, as the reference's C (and the oracle) do
     const long long total = (long long)hdst * wdst;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
         const int i = (int)(e / wdst), j = (int)(e - (long long)i * wdst);

@@ -475,7 +475,8 @@ int dfe_cascade_ring_f32(dfe_ctx *ctx, const float *const *prob, const int *rati
                          int H, int W, int maxh, int maxw, float *out);
 
 /* ---- A13 / A14: polar grids and bilinear warp ------------------------------------------------ */
-/* replaces: getC2PMask radial/cartesian2polar.lua:4-49.  mask [2][hdst][wdst+lpadding+rpadding]. */
+/* replaces: getC2PMask radial/cartesian2polar.lua:4-49.  mask [2][hdst][wdst+lpadding+rpadding].  rmax > 0 and alpha > 0, as for
+ *   the P2C grid (else DFE_E_ARG, nothing is written): alpha < 0 makes row 0 pow(0, alpha) * sin(0) = inf * 0 = NaN coordinates. */
 int dfe_polar_grid_c2p_f32(dfe_ctx *ctx, int wsrc, int hsrc, int wdst, int hdst, float xcenter,
                            float ycenter, int lpadding, int rpadding, float rmax, float alpha,
                            float *mask);
@@ -486,7 +487,7 @@ int dfe_polar_grid_p2c_f32(dfe_ctx *ctx, int wsrc, int hsrc, int wdst, int hdst,
                            float ycenter, double rmax, float alpha, float *mask);
 /* replaces: cartesian2polar(img, mask) = image.warp(img, mask, 'bilinear', false)
  *   radial/cartesian2polar.lua:91-93.  img [C][H][W], mask [2][Hd][Wd] (plane 0 = y, 1 = x, absolute,
- *   0-based), out [C][Hd][Wd]; coordinates outside the image are clamped. */
+ *   0-based), out [C][Hd][Wd]; coordinates outside the image are clamped, a NaN coordinate samples row / column 0. */
 int dfe_warp_bilinear_f32(dfe_ctx *ctx, const float *img, int C, int H, int W, const float *mask,
                           int Hd, int Wd, float *out);
 

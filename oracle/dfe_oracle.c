@@ -926,8 +926,10 @@ void orc_warp_bilinear(const float *img, int C, int H, int W, const float *mask,
     for (int i = 0; i < Hd; ++i)
         for (int j = 0; j < Wd; ++j) {
             float fy = my[(size_t)i * Wd + j], fx = mx[(size_t)i * Wd + j];
-            fy = fy < 0 ? 0 : (fy > (float)(H - 1) ? (float)(H - 1) : fy);
-            fx = fx < 0 ? 0 : (fx > (float)(W - 1) ? (float)(W - 1) : fx);
+            /* written so that a NaN coordinate goes to 0 (both comparisons of `fy < 0 ? 0 : fy > H-1 ? H-1 : fy` are false
+             * for NaN, and (int)floorf(NaN) indexes out of the image) */
+            fy = fy >= 0 ? (fy < (float)(H - 1) ? fy : (float)(H - 1)) : 0;
+            fx = fx >= 0 ? (fx < (float)(W - 1) ? fx : (float)(W - 1)) : 0;
             int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
             int y1 = y0 + 1 < H ? y0 + 1 : H - 1, x1 = x0 + 1 < W ? x0 + 1 : W - 1;
             float wy = fy - (float)y0, wx = fx - (float)x0;
