@@ -30,6 +30,9 @@ no CPU fallback -- a missing library or device raises.
                                                         bilateral upsampling with a confidence plane, holes skipped, motion boundaries
                                                         kept by the frame itself -- subpixel.py)
     radialFlowDepth(..., subpixel=True), refineRadialFlowSubpixel   (not in the reference: sub-pixel radial flow -- radial.py)
+    radialFlowDepth(..., sgm=(P1, P2)), semiGlobalAggregate         (not in the reference: the radial cost volume summed along 4 or 8 image
+                                                        directions under two label-change penalties before the arg-min, the polar columns
+                                                        a ring -- radial.py)
     getModel(geometry).forwardFlow                      (a trained single-scale model per frame pair in one call,
                                                         output_extraction_method 'max' or 'mean' -- network.py)
     imageScale, DepthEstimationAPI(...).nextFrameDepth  (image.scale; depth_estimation_api.lua:134-198, video -> depth per camera
@@ -61,7 +64,8 @@ from .subpixel import flowDepthPair, refineFlowSubpixel, flowConsistency, fillHo
 from .multiscale import CascadingAddTable, MultiscaleModel, MultiscalePrefilter, getModelMultiscale, getMultiscalePrefilter  # noqa: F401
 from .network import getFilter, getFilterRadial, getModel, tables_random  # noqa: F401
 from .radial import (getRMax, getC2PMask, getP2CMask, cartesian2polar, flow2depth, getKOutput, getP2CMaskOF,  # noqa: F401
-                     computeDepthMapFromFlow, getTesterNetwork, getTrainerNetwork, getMatcher, radialFlowDepth, radial_out_shape, refineRadialFlowSubpixel)
+                     computeDepthMapFromFlow, getTesterNetwork, getTrainerNetwork, getMatcher, radialFlowDepth, radial_out_shape, refineRadialFlowSubpixel,
+                     semiGlobalAggregate)
 from .glue import SmartReshape, FunctionWrapper, Mul2, Log2, OutputExtractor, postProcessImage, enlargeMask  # noqa: F401
 from . import stream  # noqa: F401
 from .stream import imageScale, DepthEstimationAPI  # noqa: F401

@@ -170,6 +170,9 @@ PROTOTYPES = {
     "dfe_radial_match_subpixel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int]),
     "dfe_radial_refine_subpixel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "dfe_radial_flow_depth_pair_subpixel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 9),
+    "dfe_sgm_aggregate_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_float, C.c_float, C.c_uint, C.c_int, C.c_void_p, C.c_void_p]),
+    "dfe_radial_flow_depth_pair_sgm_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 4
+                                           + [C.c_float, C.c_float, C.c_uint, C.c_int, C.c_int] + [C.c_void_p] * 6),
     "dfe_corner_response_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dfe_select_corners_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "dfe_pyr_down_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

@@ -471,6 +471,15 @@ int dfe_contrastive_normalization_run2(dfe_ctx *ctx, const float *in0, const flo
 int dfe_conv_mfma_res_batch(dfe_ctx *ctx, int n, const float *const *in, const int *H, const int *W, const int *in_pitch, const long long *in_plane,
                             const dfe_filter_layer &L, float *const *out, bool *handled, float *const *nrm = nullptr);
 
+// sgm.hip -- semi-global aggregation of a [H][W][D] volume
+// dfe_sgm_aggregate_f32's checks of the sizes and parameters (fn: the entry's name for the message)
+DFE_HIDDEN int dfe_sgm_check(dfe_ctx *ctx, const char *fn, int H, int W, int D, float P1, float P2, unsigned paths, int ring);
+// ... and its launches behind them, for a caller that has carved the arena itself.  work: dfe_sgm_work_planes(paths, agg != NULL) planes of
+// H * W * D floats (one per direction; none when the only direction goes straight to agg); agg [H][W][D] or NULL; flow [H][W] or NULL
+DFE_HIDDEN size_t dfe_sgm_work_planes(unsigned paths, bool agg_given);
+DFE_HIDDEN int dfe_sgm_run(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *work, float *agg,
+                           float *flow);
+
 // multiscale.hip, multiscale_subpixel.hip
 // the raw-patch pyramid on uint8 frames, converted inside its preparation kernels (f16_scale 0 = fp32 volumes)
 // subpixel: the sub-pixel refinement behind the matcher (dfe_multiscale_flow_pair_subpixel_u8)

@@ -22,6 +22,9 @@
 //                            on the costs in registers
 //   radial_refine_subpixel_kernel   the same offset from a stored volume and an integer flow (the staged path)
 //   p2c_flow_depth_kernel    P2C grid in place + bilinear sample of the polar flow + flow2depth
+// dfe_radial_flow_depth_pair_sgm_f32 puts the semi-global aggregation (sgm.hip) between the matcher and the P2C sample: the
+// matcher for its volume, dfe_sgm_run, radial_refine_subpixel_kernel on the aggregate, the last row by a memset -- no kernel of this file
+// changes for it
 #include "dfe_internal.h"
 #include "subpixel_offset.h"
 #include <memory>
@@ -490,10 +493,14 @@ static int radial_match(dfe_ctx *ctx, const char *fn, bool sub, const float *in1
     return DFE_OK;
 }
 
-// dfe_radial_flow_depth_pair_f32 (sub = false) / dfe_radial_flow_depth_pair_subpixel_f32 (sub = true)
+// the semi-global aggregation between the matcher and the P2C sample (dfe_radial_flow_depth_pair_sgm_f32): dfe_sgm_aggregate_f32's
+// parameters, the refinement of the aggregate's minimum, and where the caller wants the aggregate (or NULL)
+struct RadialSgm { float P1, P2; unsigned paths; int ring, subpixel; float *agg; };
+
+// dfe_radial_flow_depth_pair_f32 (sub = false) / dfe_radial_flow_depth_pair_subpixel_f32 (sub = true) / _sgm_f32 (sg != NULL, sub = false)
 static int radial_flow_depth_pair(dfe_ctx *ctx, const char *fn, bool sub, const dfe_radial_params *p, const float *prev, const float *cur, double e2x,
                                   double e2y, const float *w1, const float *b1, const float *w2, const float *b2, float *volume,
-                                  float *polar_flow, float *cart_flow, float *depth, float *conf) {
+                                  float *polar_flow, float *cart_flow, float *depth, float *conf, const RadialSgm *sg = nullptr) {
     DFE_REQUIRE(ctx, p && prev && cur && w1 && w2, DFE_E_ARG, "%s: NULL argument", fn);
     DFE_REQUIRE(ctx, p->C > 0 && p->hImg > 0 && p->wImg > 0 && p->hInput > 0 && p->wInput > 0 && p->n1 > 0 && p->n2 > 0 && p->kW1 > 0 && p->kH2 > 0 &&
                          p->hWin > 0 && p->alpha_polar > 0 && p->kinfty > 0,
@@ -505,10 +512,17 @@ static int radial_flow_depth_pair(dfe_ctx *ctx, const char *fn, bool sub, const 
     DFE_REQUIRE(ctx, lpad <= p->wInput && rpad <= p->wInput, DFE_E_SHAPE, "%s: wInput %d below the kernel width", fn, p->wInput);
     const int Wp = p->wInput + lpad + rpad, H = p->hInput, W = p->wInput;
     const int Hf2 = H - (p->kH2 - 1);                                        // feature rows of a full polar frame
+    // the aggregate is stored where it is read again: by the caller, or by the refinement of its minimum
+    const bool sg_keep = sg && (sg->agg || sg->subpixel);
+    if (sg) {
+        const int rc = dfe_sgm_check(ctx, fn, hm, W, p->hWin, sg->P1, sg->P2, sg->paths, sg->ring);
+        if (rc) return rc;
+        DFE_REQUIRE(ctx, !volume || sg->agg != volume, DFE_E_ARG, "%s: agg_volume must not be the volume", fn);
+    }
     // scratch: two polar frames, one row-filter buffer, two feature maps, the polar flow
     const bool il = p->C <= 4;   // (planar taps measured with the patch mapping too: 0.194 against 0.185 ms at 720p)
     const size_t n_pol = (size_t)p->C * H * Wp, n_feat = (size_t)p->n2 * Hf2 * W, n_il = il ? (size_t)p->hImg * p->wImg : 0;
-    float *pol0, *pol1, *tmp, *feat1, *feat2, *pflow, *rt;
+    float *pol0, *pol1, *tmp, *feat1, *feat2, *pflow, *rt, *svol, *sagg, *swork;
     double *sn, *cs;
     float4 *i0, *i1;
     int rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
@@ -516,6 +530,9 @@ static int radial_flow_depth_pair(dfe_ctx *ctx, const char *fn, bool sub, const 
         feat1 = c.take<float>(n_feat); feat2 = c.take<float>(n_feat); pflow = c.take<float>((size_t)hm * W);
         rt = c.take<float>(H); sn = c.take<double>(W); cs = c.take<double>(W);   // the warp's tables
         i0 = c.take<float4>(n_il); i1 = c.take<float4>(n_il);                    // ... and its interleaved frames
+        svol = c.take<float>(sg && !volume ? (size_t)hm * W * p->hWin : 0);      // the aggregation's volume and aggregate, where the
+        sagg = c.take<float>(sg_keep && !sg->agg ? (size_t)hm * W * p->hWin : 0); // caller keeps neither,
+        swork = c.take<float>(sg ? dfe_sgm_work_planes(sg->paths, sg_keep) * hm * W * p->hWin : 0);   // and its directions' planes
     });
     if (rc) return rc;
     if (polar_flow) pflow = polar_flow;
@@ -548,8 +565,22 @@ static int radial_flow_depth_pair(dfe_ctx *ctx, const char *fn, bool sub, const 
     stage.reset(new DfeStageScope(ctx, DFE_STAGE_MATCH));
     // 3. matcher + arg-min (+ the volume when asked for); the last flow row zeroed only on request (train_radial:178-180 does
     //    it for its display; test_radial:204-207, the path this call replaces, does not)
-    rc = radial_match(ctx, fn, sub, feat1, Hf2, feat2, p->n2, hm, W, p->hWin, volume, pflow, p->zero_last_row != 0);
-    if (rc) return rc;
+    if (!sg) {
+        rc = radial_match(ctx, fn, sub, feat1, Hf2, feat2, p->n2, hm, W, p->hWin, volume, pflow, p->zero_last_row != 0);
+        if (rc) return rc;
+    } else {   // the matcher for its volume (its own arg-min is overwritten), the aggregate and its first minimum, the refinement, the last row
+        float *vol = volume ? volume : svol, *abuf = sg->agg ? sg->agg : sagg;   // (abuf: NULL unless sg_keep)
+        rc = radial_match(ctx, fn, false, feat1, Hf2, feat2, p->n2, hm, W, p->hWin, vol, pflow, 0);
+        if (rc) return rc;
+        rc = dfe_sgm_run(ctx, vol, hm, W, p->hWin, sg->P1, sg->P2, sg->paths, sg->ring, swork, abuf, pflow);
+        if (rc) return rc;
+        if (sg->subpixel) {
+            hipLaunchKernelGGL(radial_refine_subpixel_kernel, dim3(dfe_grid1d((long long)hm * W)), dim3(256), 0, ctx->stream, abuf, pflow, (long long)hm * W,
+                               p->hWin, pflow);
+            DFE_LAUNCH_CHECK(ctx);
+        }
+        if (p->zero_last_row) DFE_HIP(ctx, hipMemsetAsync(pflow + (size_t)(hm - 1) * W, 0, (size_t)W * sizeof(float), ctx->stream));
+    }
     stage.reset();
     stage.reset(new DfeStageScope(ctx, DFE_STAGE_EXTRACT));
     {   // 4. polar flow -> cartesian -> depth (getP2CMaskOF + flow2depth with center2 = e2 * getKOutput)
@@ -615,6 +646,15 @@ int dfe_radial_flow_depth_pair_subpixel_f32(dfe_ctx *ctx, const dfe_radial_param
     DFE_ENTER(ctx);
     return radial_flow_depth_pair(ctx, "dfe_radial_flow_depth_pair_subpixel_f32", true, p, prev, cur, e2x, e2y, w1, b1, w2, b2, volume, polar_flow,
                                   cart_flow, depth, conf);
+}
+
+int dfe_radial_flow_depth_pair_sgm_f32(dfe_ctx *ctx, const dfe_radial_params *p, const float *prev, const float *cur, double e2x, double e2y,
+                                       const float *w1, const float *b1, const float *w2, const float *b2, float P1, float P2, unsigned paths, int ring,
+                                       int subpixel, float *volume, float *agg_volume, float *polar_flow, float *cart_flow, float *depth, float *conf) {
+    DFE_ENTER(ctx);
+    const RadialSgm sg{P1, P2, paths, ring, subpixel, agg_volume};
+    return radial_flow_depth_pair(ctx, "dfe_radial_flow_depth_pair_sgm_f32", false, p, prev, cur, e2x, e2y, w1, b1, w2, b2, volume, polar_flow, cart_flow,
+                                  depth, conf, &sg);
 }
 
 }  // extern "C"

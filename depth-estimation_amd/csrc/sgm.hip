@@ -1,0 +1,260 @@
+// sgm.hip -- semi-global aggregation (Hirschmueller's path sums) of a cost volume with a one-dimensional label axis: the radial
+// matcher's [H][W][D] volume, D <= 32 (NOT in the reference, whose matchers are all winner-takes-all).
+// The definition -- directions, the step, the ring, the order of the sum, the first-minimum flow -- is in include/dfe.h and restated
+// in numpy in tests/sgm_ref.py; the device is tested against that bit for bit.
+//   sgm_path_kernel<LPL>   ONE launch for all the directions asked for (blockIdx.y), each into a plane of its own.  A chain is a
+//       sequence of dependent steps of some 60 instructions, and one direction has only H or W chains, 4 to a wave: 320 waves for the
+//       1280 columns of the 720p polar image, on 1024 SIMDs.  One direction after the other took 0.17 - 0.21 ms EACH at 720p, every wave
+//       alone on its SIMD at one instruction per four or five cycles; side by side the directions share the SIMDs.
+//       A LINE is the chain of pixels a path walks: a row for the horizontal directions; for the others the W chains that start on the
+//       top (or bottom) row and, on a ring, wind round it -- on the plane a chain that leaves through a side comes back in through the
+//       other one and STARTS AGAIN there (L = C), which is the definition's "the predecessor lies outside the plane" for every pixel of
+//       the side columns, so every direction has H or W lines of equal length and nothing is ragged.  A line belongs to one 16-lane DPP
+//       row, the labels across its lanes (LPL = 1: label = lane, D <= 16; LPL = 2: labels 2 lane and 2 lane + 1, D <= 32), the label
+//       axis padded with +Inf cells, which change no bit of a real cell and stay +Inf.  Per step: min_k L by four DPP row steps,
+//       L(d -+ 1) by one row shift each (a lane without a neighbour keeps the +Inf it is given as `old`), six more VALU operations,
+//       nothing through LDS.  The loads of the next kSgmAhead steps are in flight (a chain's addresses are known from its first step).
+//   sgm_sum_kernel<LPL, FLOW>   agg = ((L_a + L_b) + L_c) + ... in ascending direction order, 16 lanes a pixel as above; the first
+//       minimum over the labels by a row reduction on (value, label); the aggregate is stored only if somebody reads it.
+#include "dfe_internal.h"
+#include <cmath>
+#include <climits>
+
+namespace {
+
+constexpr int kSgmAhead = 8;   // steps of a line whose loads are in flight
+
+struct SgmJob {
+    const float *C;      // [H][W][D]
+    float *L[8];         // [H][W][D] each: L of the n directions asked for, in ascending bit order
+    int dy[8], dx[8];    // their directions: p's predecessor is p - (dy, dx)
+    int n;
+    int H, W, D;
+    int ring;            // G: 0 = plane
+    float P1, P2;
+};
+
+// the smallest value of a 16-lane DPP row in every lane of it (no NaNs: path costs, +Inf in the padding lanes) -- the float form of the
+// reductions in dfe_wave.h, in their step order
+__device__ __forceinline__ float sgm_row_min(float v) {
+#define DFE_STEP(ctrl) v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, false)))
+    DFE_STEP(0x128); DFE_STEP(0x124); DFE_STEP(0x4E); DFE_STEP(0xB1);   // row_ror:8, row_ror:4, quad_perm [2,3,0,1], [1,0,3,2]
+#undef DFE_STEP
+    return v;
+}
+__device__ __forceinline__ float sgm_row_shr1(float v, float edge) {   // lane j: lane j - 1's v; lane 0 of the row: edge
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x111, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float sgm_row_shl1(float v, float edge) {   // lane j: lane j + 1's v; lane 15 of the row: edge
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x101, 0xf, 0xf, false));
+}
+
+template <int LPL>
+__global__ __launch_bounds__(64) void sgm_path_kernel(const SgmJob a) {
+#pragma clang fp contract(off)
+    const float inf = __builtin_inff();
+    const int k = blockIdx.y;                    // which of the directions
+    const int dy = a.dy[k], dx = a.dx[k];
+    float *__restrict__ out = a.L[k];
+    const bool horizontal = dy == 0;
+    const int nlines = horizontal ? a.H : a.W;   // lines of this direction
+    const int warm = horizontal ? a.ring : 0;    // leading steps of a horizontal line on a ring that are walked and not kept
+    const int nsteps = horizontal ? a.W + a.ring : a.H;   // (run in whole groups of kSgmAhead: a short line wastes up to 7 of 8 steps, a row
+                                                          //  beyond the last line all of them -- in-bounds loads, no store)
+    if ((int)blockIdx.x * 4 >= nlines) return;   // (the grid is sized for the longer side)
+    const int lane = threadIdx.x & 15;
+    const int line = blockIdx.x * 4 + (int)(threadIdx.x >> 4);
+    const bool live = line < nlines;             // a row beyond the last line walks the last line again and stores nothing
+    const int ln = live ? line : nlines - 1;
+    const int d0 = lane * LPL;
+    bool in[LPL];
+    int dc[LPL];                                 // a padding lane loads the last real label (and takes +Inf): no load under a branch
+#pragma unroll
+    for (int j = 0; j < LPL; ++j) {
+        in[j] = d0 + j < a.D;
+        dc[j] = in[j] ? d0 + j : a.D - 1;
+    }
+
+    // the fetch cursor: the pixel of step `fs`, and whether the chain starts (again) there.  Past the last step it stays on the last
+    // pixel: the step loop runs whole groups of kSgmAhead steps, and the surplus ones of the last group keep nothing.
+    int fy, fx, fs = 0;
+    bool fstart = true;
+    if (horizontal) {
+        fy = ln;
+        fx = dx > 0 ? (a.W - a.ring) % a.W : (a.ring + a.W - 1) % a.W;
+    } else {
+        fy = dy > 0 ? 0 : a.H - 1;
+        fx = ln;
+    }
+    float cb[kSgmAhead][LPL];
+    int pixb[kSgmAhead];
+    bool stb[kSgmAhead];
+    auto fetch = [&](int slot) {
+        const int pix = fy * a.W + fx;
+        const long long e = (long long)pix * a.D;
+#pragma unroll
+        for (int j = 0; j < LPL; ++j) cb[slot][j] = a.C[e + dc[j]];
+        pixb[slot] = pix;
+        stb[slot] = fstart;
+        ++fs;
+        if (fs < nsteps) {                       // (wave-uniform; integer work only)
+            fy += dy;
+            fx += dx;
+            const bool wrapped = fx < 0 || fx >= a.W;
+            fx = fx < 0 ? a.W - 1 : (fx >= a.W ? 0 : fx);
+            fstart = wrapped && a.ring == 0;
+        }
+    };
+#pragma unroll
+    for (int u = 0; u < kSgmAhead; ++u) fetch(u);
+
+    float l[LPL];
+#pragma unroll
+    for (int j = 0; j < LPL; ++j) l[j] = 0.f;
+    for (int s = 0; s < nsteps; s += kSgmAhead) {
+#pragma unroll
+        for (int u = 0; u < kSgmAhead; ++u) {
+            float c[LPL];
+#pragma unroll
+            for (int j = 0; j < LPL; ++j) c[j] = in[j] ? cb[u][j] : inf;
+            const int pix = pixb[u];
+            const bool start = stb[u];
+            fetch(u);
+            // L_r(p, d) = C(p, d) + (min(L(q, d), L(q, d - 1) + P1, L(q, d + 1) + P1, m + P2) - m), m = min_k L(q, k)
+            float m = l[0];
+            if constexpr (LPL == 2) m = fminf(m, l[1]);
+            m = sgm_row_min(m);
+            const float far = m + a.P2;
+            float lo[LPL], hi[LPL];              // L(q, d - 1), L(q, d + 1)
+            if constexpr (LPL == 1) {
+                lo[0] = sgm_row_shr1(l[0], inf);
+                hi[0] = sgm_row_shl1(l[0], inf);
+            } else {
+                lo[0] = sgm_row_shr1(l[1], inf);
+                hi[0] = l[1];
+                lo[1] = l[0];
+                hi[1] = sgm_row_shl1(l[0], inf);
+            }
+#pragma unroll
+            for (int j = 0; j < LPL; ++j) {
+                const float t = fminf(fminf(fminf(l[j], lo[j] + a.P1), hi[j] + a.P1), far);
+                const float n = c[j] + (t - m);
+                l[j] = start ? c[j] : n;
+            }
+            const bool keep = live && s + u >= warm && s + u < nsteps;
+#pragma unroll
+            for (int j = 0; j < LPL; ++j)
+                if (keep && in[j]) out[(long long)pix * a.D + d0 + j] = l[j];
+        }
+    }
+}
+
+// agg = the n planes summed in order; flow = its first minimum.  16 lanes a pixel, 16 pixels a block
+template <int LPL, bool FLOW>
+__global__ __launch_bounds__(256) void sgm_sum_kernel(const SgmJob a, float *__restrict__ agg, float *__restrict__ flow) {
+#pragma clang fp contract(off)
+    const int P = a.H * a.W;
+    const int lane = threadIdx.x & 15;
+    const int px = blockIdx.x * 16 + (int)(threadIdx.x >> 4);
+    const bool live = px < P;                    // a row beyond the last pixel sums the last pixel again and stores nothing
+    const long long e = (long long)(live ? px : P - 1) * a.D;
+    const int d0 = lane * LPL;
+    float v[LPL];
+#pragma unroll
+    for (int j = 0; j < LPL; ++j) {
+        const bool in = d0 + j < a.D;
+        const long long ej = e + (in ? d0 + j : a.D - 1);
+        float t = a.L[0][ej];
+        for (int k = 1; k < a.n; ++k) t = t + a.L[k][ej];
+        v[j] = in ? t : __builtin_inff();
+        if (agg && live && in) agg[ej] = t;
+    }
+    if constexpr (FLOW) {                        // the first minimum: the smallest value, and among equal ones the smallest label
+        float b = v[0];
+        int bi = d0;
+        if constexpr (LPL == 2)
+            if (v[1] < b) { b = v[1]; bi = d0 + 1; }
+#define DFE_STEP(ctrl)                                                                                                  \
+    {                                                                                                                   \
+        const float ob = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(b), ctrl, 0xf, 0xf, false));      \
+        const int oi = __builtin_amdgcn_update_dpp(0, bi, ctrl, 0xf, 0xf, false);                                       \
+        const bool take = (ob < b) | ((ob == b) & (oi < bi));                                                           \
+        b = take ? ob : b;                                                                                              \
+        bi = take ? oi : bi;                                                                                            \
+    }
+        DFE_STEP(0x128); DFE_STEP(0x124); DFE_STEP(0x4E); DFE_STEP(0xB1);   // row_ror:8, row_ror:4, quad_perm [2,3,0,1], [1,0,3,2]
+#undef DFE_STEP
+        if (live && lane == 0) flow[px] = (float)bi;
+    }
+}
+
+}  // namespace
+
+// planes of H * W * D floats that dfe_sgm_run takes as `work`: one per direction, unless the only direction goes straight to agg
+size_t dfe_sgm_work_planes(unsigned paths, bool agg_given) {
+    const int n = __builtin_popcount(paths & 255u);
+    return n == 1 && agg_given ? 0 : (size_t)n;
+}
+
+// The launches of dfe_sgm_aggregate_f32 behind its argument checks.  work: dfe_sgm_work_planes(paths, agg != NULL) planes;
+// agg [H][W][D] or NULL; flow [H][W] or NULL.
+int dfe_sgm_run(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *work, float *agg,
+                float *flow) {
+    static const int dirs[8][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, 1}, {-1, -1}, {1, -1}, {-1, 1}};   // (dy, dx) of bit r
+    const bool direct = dfe_sgm_work_planes(paths, agg != nullptr) == 0;   // one direction, and its L is the aggregate the caller wants
+    SgmJob a{};
+    a.C = volume;
+    a.H = H; a.W = W; a.D = D;
+    a.ring = ring;
+    a.P1 = P1; a.P2 = P2;
+    for (int r = 0; r < 8; ++r) {
+        if (!(paths >> r & 1u)) continue;
+        a.L[a.n] = direct ? agg : work + (size_t)a.n * H * W * D;
+        a.dy[a.n] = dirs[r][0]; a.dx[a.n] = dirs[r][1];
+        ++a.n;
+    }
+    DfeProfScope prof(ctx);
+    const dim3 grid((unsigned)dfe_cdiv(H > W ? H : W, 4), (unsigned)a.n);
+    if (D <= 16) hipLaunchKernelGGL(sgm_path_kernel<1>, grid, dim3(64), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(sgm_path_kernel<2>, grid, dim3(64), 0, ctx->stream, a);
+    DFE_LAUNCH_CHECK(ctx);
+    float *aout = direct ? nullptr : agg;
+    if (aout || flow) {
+        const dim3 sgrid((unsigned)dfe_cdiv((long long)H * W, 16));
+#define DFE_SGM_SUM(LPL, FLOW) hipLaunchKernelGGL((sgm_sum_kernel<LPL, FLOW>), sgrid, dim3(256), 0, ctx->stream, a, aout, flow)
+        if (D <= 16) { if (flow) DFE_SGM_SUM(1, true); else DFE_SGM_SUM(1, false); }
+        else { if (flow) DFE_SGM_SUM(2, true); else DFE_SGM_SUM(2, false); }
+#undef DFE_SGM_SUM
+        DFE_LAUNCH_CHECK(ctx);
+    }
+    ctx->last_kernel = "sgm_path_kernel";
+    return DFE_OK;
+}
+
+int dfe_sgm_check(dfe_ctx *ctx, const char *fn, int H, int W, int D, float P1, float P2, unsigned paths, int ring) {
+    DFE_REQUIRE(ctx, H >= 1 && W >= 1 && D >= 1 && (long long)H * W <= INT_MAX, DFE_E_SHAPE, "%s: H=%d W=%d D=%d", fn, H, W, D);
+    DFE_REQUIRE(ctx, D <= 32, DFE_E_UNSUPPORTED, "%s: D=%d labels (32 at most)", fn, D);
+    DFE_REQUIRE(ctx, paths >= 1u && paths <= 255u, DFE_E_ARG, "%s: paths=0x%x must be 1 .. 255 (bit r = direction r)", fn, paths);
+    DFE_REQUIRE(ctx, std::isfinite(P1) && std::isfinite(P2) && P1 >= 0.f && P1 <= P2, DFE_E_ARG, "%s: P1=%g P2=%g must be finite with 0 <= P1 <= P2", fn,
+                (double)P1, (double)P2);
+    DFE_REQUIRE(ctx, ring >= 0 && ring <= W, DFE_E_ARG, "%s: ring=%d must be 0 .. W=%d", fn, ring, W);
+    return DFE_OK;
+}
+
+extern "C" {
+
+int dfe_sgm_aggregate_f32(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *agg,
+                          float *flow) {
+    DFE_ENTER(ctx);
+    DFE_REQUIRE(ctx, volume && (agg || flow), DFE_E_ARG, "dfe_sgm_aggregate_f32: %s", volume ? "agg and flow are both NULL" : "volume is NULL");
+    DFE_REQUIRE(ctx, agg != volume, DFE_E_ARG, "dfe_sgm_aggregate_f32: agg must not be the volume (every direction reads it)");
+    int rc = dfe_sgm_check(ctx, "dfe_sgm_aggregate_f32", H, W, D, P1, P2, paths, ring);
+    if (rc) return rc;
+    float *work = nullptr;
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { work = c.take<float>(dfe_sgm_work_planes(paths, agg != nullptr) * H * W * D); });
+    if (rc) return rc;
+    DfeStageScope st(ctx, DFE_STAGE_MATCH);
+    return dfe_sgm_run(ctx, volume, H, W, D, P1, P2, paths, ring, work, agg, flow);
+}
+
+}  // extern "C"

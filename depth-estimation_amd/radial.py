@@ -260,8 +260,45 @@ def refineRadialFlowSubpixel(volume, flow):
     return out
 
 
+def _sgm_params(P1, P2, paths, ring, W, who):
+    """dfe_sgm_aggregate_f32's parameter rules, raised as ValueError before any device work"""
+    if isinstance(paths, bool) or not isinstance(paths, int) or not 1 <= paths <= 255:
+        raise ValueError("%s: paths=%r must be 1 .. 255 (bit r = direction r)" % (who, paths))
+    if isinstance(ring, bool) or not isinstance(ring, int) or not 0 <= ring <= W:
+        raise ValueError("%s: ring=%r must be 0 .. W=%d" % (who, ring, W))
+    try:
+        P1, P2 = float(P1), float(P2)
+    except (TypeError, ValueError):
+        raise ValueError("%s: P1=%r, P2=%r: two numbers expected" % (who, P1, P2))
+    if not (math.isfinite(P1) and math.isfinite(P2) and 0 <= P1 <= P2):
+        raise ValueError("%s: P1=%r, P2=%r must be finite with 0 <= P1 <= P2" % (who, P1, P2))
+    return P1, P2
+
+
+def semiGlobalAggregate(volume, P1, P2, paths=0x0f, ring=0, want_volume=True):
+    """Not in the reference: semi-global aggregation of a matcher volume [H][W][D] (D <= 32, float32) along the
+    directions whose bits `paths` has set -- 0 (0, +1), 1 (0, -1), 2 (+1, 0), 3 (-1, 0), 4 (+1, +1), 5 (-1, -1), 6 (+1, -1), 7 (-1, +1) as
+    (dy, dx) -- with the penalty P1 for a label change of one and P2 for any other; ring = G > 0: the columns are a ring and a horizontal
+    path warms up over G columns (include/dfe.h: dfe_sgm_aggregate_f32).  Returns (flow [H][W] = the first minimum of the aggregate as
+    float, aggregate [H][W][D] or None without want_volume: the aggregate then never leaves the library's scratch)."""
+    if volume.dim() != 3 or min(volume.shape) < 1:
+        raise ValueError("semiGlobalAggregate: volume H x W x D expected, got %s" % (tuple(volume.shape),))
+    H, W, D = volume.shape
+    if D > 32:
+        raise ValueError("semiGlobalAggregate: D=%d labels (32 at most)" % D)
+    P1, P2 = _sgm_params(P1, P2, paths, ring, W, "semiGlobalAggregate")
+    if not volume.is_cuda or volume.dtype != torch.float32:
+        raise TypeError("semiGlobalAggregate: a float32 CUDA tensor expected")
+    volume = volume.contiguous()
+    ctx = get_ctx(volume)
+    flow = torch.empty((H, W), dtype=torch.float32, device=volume.device)
+    agg = torch.empty_like(volume) if want_volume else None
+    ctx.check(lib().dfe_sgm_aggregate_f32(ctx.handle, ptr(volume), H, W, D, P1, P2, paths, ring, ptr(agg) if want_volume else None, ptr(flow)))
+    return flow, agg
+
+
 def radialFlowDepth(networkp, network, prev_img, img, e2, kinfty=0.65, alpha_polar=1.0, one_call=True, want_volume=False, zero_last_row=False,
-                    subpixel=False):
+                    subpixel=False, sgm=None):
     """radial/test_radial_opticalflow.lua:186-225 for one frame pair: polar warps of both frames around the epipole e2,
     getTesterNetwork:forward, min(3) - 1, back to cartesian through getP2CMaskOF, flow2depth.  prev_img is the previous
     frame after the caller's ego-motion correction (sfm2.removeEgoMotion: `sfm2.removeEgoMotion` of this package, or the caller's own).  Returns a dict
@@ -272,7 +309,10 @@ def radialFlowDepth(networkp, network, prev_img, img, e2, kinfty=0.65, alpha_pol
     `test:sub(h,h,1,w):zero()`); test_radial:204-207 -- the default here -- does not.
     subpixel (not in the reference): the polar flow is the first-minimum index plus the vertex of the parabola
     through the costs around it (dfe_radial_flow_depth_pair_subpixel_f32; staged: dfe_radial_refine_subpixel_f32 after the arg-min);
-    everything after it is unchanged and sees a fractional polar flow."""
+    everything after it is unchanged and sees a fractional polar flow.
+    sgm (not in the reference): None, (P1, P2) or dict(P1=, P2=, paths=0x0f, ring=hWin) -- the matcher's volume goes
+    through semiGlobalAggregate before the arg-min (ring defaults to hWin: the polar columns are a ring); subpixel then refines on the
+    aggregate, and want_volume also returns it as `aggregate` (dfe_radial_flow_depth_pair_sgm_f32; staged: the same public calls)."""
     hK, wK = networkp_kernel_size(networkp)
     prev_img, img = prev_img.contiguous(), img.contiguous()
     Cc, hImg, wImg = img.shape
@@ -281,6 +321,12 @@ def radialFlowDepth(networkp, network, prev_img, img, e2, kinfty=0.65, alpha_pol
     hm, hOut, wOut = radial_out_shape(networkp)
     if hm < 1:
         raise ValueError("radialFlowDepth: hInput %d too small for kernel %d + window %d" % (networkp["hInput"], hK, networkp["hWin"]))
+    if sgm is not None:
+        sg = dict(sgm) if isinstance(sgm, dict) else dict(zip(("P1", "P2"), sgm)) if isinstance(sgm, (tuple, list)) and len(sgm) == 2 else None
+        if sg is None or not {"P1", "P2"} <= set(sg) <= {"P1", "P2", "paths", "ring"}:
+            raise ValueError("radialFlowDepth: sgm=%r: None, (P1, P2) or dict(P1=, P2=, paths=, ring=) expected" % (sgm,))
+        sg_paths, sg_ring = sg.get("paths", 0x0f), sg.get("ring", min(networkp["hWin"], networkp["wInput"]))
+        sg_P1, sg_P2 = _sgm_params(sg["P1"], sg["P2"], sg_paths, sg_ring, networkp["wInput"], "radialFlowDepth(sgm=)")
     sep = _separable_weights(network, networkp) if one_call else None
     dev = img.device
     ret = {}
@@ -292,9 +338,18 @@ def radialFlowDepth(networkp, network, prev_img, img, e2, kinfty=0.65, alpha_pol
         pf = torch.empty((hm, networkp["wInput"]), dtype=torch.float32, device=dev)
         cart, depth, conf = (torch.empty((hOut, wOut), dtype=torch.float32, device=dev) for _ in range(3))
         ctx = get_ctx(img)
-        entry = lib().dfe_radial_flow_depth_pair_subpixel_f32 if subpixel else lib().dfe_radial_flow_depth_pair_f32
-        ctx.check(entry(ctx.handle, C.byref(prm), ptr(prev_img), ptr(img), float(e2[0]), float(e2[1]), ptr(w1), ptr(b1),
-                        ptr(w2), ptr(b2), ptr(vol) if want_volume else None, ptr(pf), ptr(cart), ptr(depth), ptr(conf)))
+        if sgm is not None:
+            agg = torch.empty_like(vol) if want_volume else None
+            ctx.check(lib().dfe_radial_flow_depth_pair_sgm_f32(ctx.handle, C.byref(prm), ptr(prev_img), ptr(img), float(e2[0]), float(e2[1]), ptr(w1), ptr(b1),
+                                                               ptr(w2), ptr(b2), sg_P1, sg_P2, sg_paths, sg_ring, 1 if subpixel else 0,
+                                                               ptr(vol) if want_volume else None, ptr(agg) if want_volume else None, ptr(pf), ptr(cart),
+                                                               ptr(depth), ptr(conf)))
+            if want_volume:
+                ret["aggregate"] = agg
+        else:
+            entry = lib().dfe_radial_flow_depth_pair_subpixel_f32 if subpixel else lib().dfe_radial_flow_depth_pair_f32
+            ctx.check(entry(ctx.handle, C.byref(prm), ptr(prev_img), ptr(img), float(e2[0]), float(e2[1]), ptr(w1), ptr(b1),
+                            ptr(w2), ptr(b2), ptr(vol) if want_volume else None, ptr(pf), ptr(cart), ptr(depth), ptr(conf)))
         ret.update(polar_flow=pf, flow=cart, depth=depth, confs=conf)
         if want_volume:
             ret["output"] = vol
@@ -304,12 +359,18 @@ def radialFlowDepth(networkp, network, prev_img, img, e2, kinfty=0.65, alpha_pol
     polar_prev, polar_img = cartesian2polar(prev_img, mask), cartesian2polar(img, mask)
     output = network.forward([polar_prev, polar_img])
     H1, Wi, hW = output.shape
-    imin = torch.empty((H1, Wi), dtype=torch.int64, device=dev)
     ctx = get_ctx(output)
-    ctx.check(lib().dfe_argbest_center(ctx.handle, ptr(output), H1 * Wi, hW, 0, 0, ptr(imin), None))   # output:min(3): first minimum, no centre rule
-    idx = (imin - 1).to(torch.float32)                   # idx:add(-1), test_radial:207
+    costs = output                                       # the volume whose minimum is the flow
+    if sgm is not None:
+        idx, costs = semiGlobalAggregate(output.contiguous(), sg_P1, sg_P2, sg_paths, sg_ring, want_volume=want_volume or subpixel)
+        if want_volume:
+            ret["aggregate"] = costs
+    else:
+        imin = torch.empty((H1, Wi), dtype=torch.int64, device=dev)
+        ctx.check(lib().dfe_argbest_center(ctx.handle, ptr(output), H1 * Wi, hW, 0, 0, ptr(imin), None))   # output:min(3): first minimum, no centre rule
+        idx = (imin - 1).to(torch.float32)               # idx:add(-1), test_radial:207
     if subpixel:
-        ctx.check(lib().dfe_radial_refine_subpixel_f32(ctx.handle, ptr(output), ptr(idx), H1 * Wi, hW, ptr(idx)))   # in place
+        ctx.check(lib().dfe_radial_refine_subpixel_f32(ctx.handle, ptr(costs), ptr(idx), H1 * Wi, hW, ptr(idx)))   # in place
     if zero_last_row:
         idx[-1].zero_()                                  # train_radial:178-180 (the trainer's display path only)
     np2 = dict(networkp, hKernel=hK, wKernel=wK)

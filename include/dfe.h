@@ -249,6 +249,42 @@ int dfe_radial_flow_depth_pair_subpixel_f32(dfe_ctx *ctx, const dfe_radial_param
                                             const float *b2, float *volume, float *polar_flow, float *cart_flow, float *depth,
                                             float *conf);
 
+/* ---- semi-global aggregation of a cost volume with one label axis: a smoothed polar flow (NOT in the reference, whose matchers
+ * are all winner-takes-all) ------------------------------------------------------------------------------- */
+/* Hirschmueller's path aggregation.  volume [H][W][D] (dfe_radial_matching_f32's layout, D = hWin), agg [H][W][D] or NULL,
+ * flow [H][W] or NULL.  With C = volume, every operation fp32, separately rounded, in exactly this order:
+ *   Directions: bit r of `paths` is the direction (dy, dx): 0 (0, +1), 1 (0, -1), 2 (+1, 0), 3 (-1, 0), 4 (+1, +1), 5 (-1, -1),
+ *     6 (+1, -1), 7 (-1, +1).
+ *   Step: for a pixel p with predecessor q = p - r and m = min_k L_r(q, k), cells outside 0 .. D-1 taken as +Inf:
+ *     t = min(min(min(L_r(q, d), L_r(q, d-1) + P1), L_r(q, d+1) + P1), m + P2);   L_r(p, d) = C(p, d) + (t - m).
+ *   Start: L_r(p, .) = C(p, .) where q lies outside the plane.
+ *   ring = G > 0: the columns are a ring, as the polar image's angle is.  The predecessor's column is taken modulo W, so a diagonal
+ *     path only ever starts on the top or bottom row.  Direction 0 of a row starts at column W - G with L = C, walks the G warm-up
+ *     columns up to W - 1 and then the columns 0 .. W - 1: only this second stretch is its L_0.  Direction 1 is the mirror image:
+ *     it starts at G - 1, goes down to 0, then W - 1 .. 0.  G = 0 is the plane.
+ *   Sum: agg = L_r of the lowest set bit, then agg = agg + L_r for each further set bit in ascending r.
+ *   flow = the first minimum of agg over d, by strict `<` scan from 0, as a float (the matcher's rule).
+ * 1 <= D <= 32 (a larger D: DFE_E_UNSUPPORTED); H, W >= 1 with H * W < 2^31 (DFE_E_SHAPE); paths in 1 .. 255, P1 and P2 finite
+ * with 0 <= P1 <= P2, 0 <= ring <= W, agg and flow not both NULL, agg != volume, volume not NULL (DFE_E_ARG).  The volume must be
+ * finite; for anything else (NaN, Inf, sums that overflow) the result is unspecified.
+ * Two launches.  All directions at once, each into a plane of its own in the ctx's scratch arena (H * W * D floats per set bit): a
+ * path's chain runs in one 16-lane DPP row, the labels across the lanes (two per lane above 16), the label axis padded with +Inf
+ * cells, which change no bit of a real cell.  Then the planes are summed in order and the first minimum taken; with agg == NULL
+ * the aggregate is never stored.  (A single direction with agg given writes its L straight there.)  Asynchronous on the ctx's
+ * stream; runs under DFE_STAGE_MATCH. */
+int dfe_sgm_aggregate_f32(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring,
+                          float *agg, float *flow);
+/* dfe_radial_flow_depth_pair_f32 with the aggregation between the matcher and the P2C sample.  Same arguments and outputs, plus
+ * P1, P2, paths, ring (dfe_sgm_aggregate_f32's; 0 <= ring <= wInput), subpixel (non-zero: dfe_radial_refine_subpixel_f32's rule on the
+ * AGGREGATE) and agg_volume [hMatch][wInput][hWin] or NULL.  Order of work: the matcher writes the volume (to scratch when `volume` is
+ * NULL); dfe_sgm_aggregate_f32 gives the aggregate and polar_flow = its first minimum; with subpixel the refinement; with
+ * p->zero_last_row the last polar flow row is zeroed; the unchanged P2C sample and flow2depth.  hWin in {8, 12, 15, 16}.
+ * Bit-identical to the same steps as staged public calls. */
+int dfe_radial_flow_depth_pair_sgm_f32(dfe_ctx *ctx, const dfe_radial_params *p, const float *prev, const float *cur, double e2x,
+                                       double e2y, const float *w1, const float *b1, const float *w2, const float *b2, float P1,
+                                       float P2, unsigned paths, int ring, int subpixel, float *volume, float *agg_volume,
+                                       float *polar_flow, float *cart_flow, float *depth, float *conf);
+
 /* ---- N2: gradients of the two matchers (training drivers call model:backward through them) ------- */
 /* replaces: nn.SpatialMatching:updateGradInput / nn.SpatialRadialMatching:updateGradInput (un-vendored nnx), reached
  *   from radial/train_radial_opticalflow.lua:228-252 and opticalflow.lua:296-338.  gradOut has the forward output's
