@@ -85,6 +85,7 @@ PROTOTYPES = {
     "dfe_get_option": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]),
     "dfe_last_kernel": (C.c_char_p, [C.c_void_p]),
     "dfe_flow_last_path": (C.c_int, [C.c_void_p, c_i32p]),
+    "dfe_multiscale_last_path": (C.c_char_p, [C.c_void_p]),
     "dfe_ssd_cost_volume_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]),
     "dfe_ssd_cost_volume_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_float, C.c_void_p]),
     "dfe_flow_depth_pair_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 5),

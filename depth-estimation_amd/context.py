@@ -24,6 +24,10 @@ class Context:
         if rc != DFE_OK:
             raise DfeError(rc, lib().dfe_last_error(self.handle).decode())
 
+    def last_error(self):
+        """the text of this ctx's last failed call (dfe_last_error)"""
+        return lib().dfe_last_error(self.handle).decode()
+
     def synchronize(self):
         self.check(lib().dfe_ctx_synchronize(self.handle))
 
@@ -64,6 +68,10 @@ class Context:
 
     def last_kernel(self):
         return lib().dfe_last_kernel(self.handle).decode()
+
+    def multiscale_last_path(self):
+        """'<preparation kernel> <cascade kernel>' of the last one-call pyramid matcher run (dfe_multiscale_last_path)"""
+        return lib().dfe_multiscale_last_path(self.handle).decode()
 
     def flow_last_path_i8(self):
         """True if the int8 matrix-core kernel produced the last single-scale flow step's result (synchronises)."""

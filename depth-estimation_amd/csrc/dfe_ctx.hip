@@ -301,6 +301,12 @@ int dfe_set_cost_volume_tile(dfe_ctx *ctx, int tyq) {
 
 const char *dfe_last_kernel(const dfe_ctx *ctx) { return ctx ? ctx->last_kernel : ""; }
 
+const char *dfe_multiscale_last_path(dfe_ctx *ctx) {
+    if (!ctx) return "";
+    snprintf(ctx->ms_path, sizeof ctx->ms_path, "%s %s", ctx->ms_prep, ctx->ms_cascade);
+    return ctx->ms_path;
+}
+
 int dfe_flow_last_path(dfe_ctx *ctx, int *i8_taken) {
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, i8_taken, DFE_E_ARG, "dfe_flow_last_path: i8_taken is NULL");

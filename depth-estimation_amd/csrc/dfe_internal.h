@@ -61,6 +61,8 @@ struct dfe_ctx {
     int cv_tyq = 0;                   // 0 = pick the tile height per shape; else dfe_set_cost_volume_tile's code (tuning / tests)
     int ncu = 256;                    // compute units of the device
     const char *last_kernel = "";
+    const char *ms_prep = "", *ms_cascade = "";   // the pyramid matcher's last preparation / cascade kernel (dfe_multiscale_last_path)
+    char ms_path[96] = "";
     DfeBuf scratch;                   // grow-only device arena (never shrinks; freed with the ctx), physically contiguous where the driver grants it
     DfeBuf scratch_plain;             // the arena of the paths that run learned filter stacks: a plain hipMalloc (dfe_scratch's `plain`)
     size_t scratch_limit = (size_t)16 << 30;   // cost-volume bands are sized to fit (dfe_set_scratch_limit)

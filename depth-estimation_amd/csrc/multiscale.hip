@@ -916,7 +916,10 @@ __global__ __launch_bounds__(256) void round_half_kernel(float *__restrict__ v, 
 
 int ring_width(int maxw, int r, int rprev) { return (int)floor((double)maxw * (r - rprev) / (2.0 * r) + 0.5); }
 
-int fill_cascade(dfe_ctx *ctx, CascadeGeom &g, const int *ratios, int nratios, int maxh, int maxw) {
+// ring: the caller uses the joined class layout (g.d, g.base, g.ncls).  Its ring width comes from maxw alone and is used on both axes, so a
+// window lower than 2 d has side blocks of negative height: rejected (the reference's nn.Narrow(2, d + 1, maxh - 2 d) fails there too;
+// maxh == 2 d, with empty side blocks, is accepted).  CascadingAddTable itself has no ring and takes any window its ratios divide.
+int fill_cascade(dfe_ctx *ctx, CascadeGeom &g, const int *ratios, int nratios, int maxh, int maxw, bool ring = true) {
     DFE_REQUIRE(ctx, ratios && nratios >= 1 && nratios <= DFE_MAX_RATIOS, DFE_E_ARG, "nratios=%d not in 1..%d", nratios, DFE_MAX_RATIOS);
     DFE_REQUIRE(ctx, maxh > 0 && maxw > 0, DFE_E_ARG, "maxh=%d maxw=%d must be positive", maxh, maxw);
     g.nratios = nratios; g.maxh = maxh; g.maxw = maxw;
@@ -925,6 +928,9 @@ int fill_cascade(dfe_ctx *ctx, CascadeGeom &g, const int *ratios, int nratios, i
         DFE_REQUIRE(ctx, ratios[i] > 0, DFE_E_ARG, "ratios[%d]=%d", i, ratios[i]);
         g.ratios[i] = ratios[i];
         g.d[i] = i ? ring_width(maxw, ratios[i], ratios[i - 1]) : 0;
+        DFE_REQUIRE(ctx, !ring || maxh >= 2 * g.d[i], DFE_E_SHAPE,
+                    "scale %d (ratio %d): the %dx%d window is lower than twice its ring width d=%d (d = round(maxw (r - r') / (2 r)) serves both axes)", i,
+                    ratios[i], maxh, maxw, g.d[i]);
         g.base[i] = base;
         base += i ? 2 * g.d[i] * maxw + 2 * (maxh - 2 * g.d[i]) * g.d[i] : maxh * maxw;
         if (i + 1 < nratios) {   // CascadingAddTable.lua:121-124
@@ -1172,6 +1178,7 @@ static int ms_prep_raw(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B) {
     const MsArgs &a = P.a;
     const unsigned char *b0 = (const unsigned char *)a.I0, *b1 = (const unsigned char *)a.I1;
     DfeStageScope st(ctx, DFE_STAGE_FILTER);
+    ctx->ms_prep = P.prep_tiles ? "prep_tiles_kernel" : "prep_scales_kernel";
     if (P.prep_tiles) {       // every scale from one read of the frames
         PrepTile pq;
         pq.ns = a.nratios;
@@ -1209,6 +1216,7 @@ static int ms_learned_front(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, MsRu
     }
     {
         DfeStageScope st(ctx, DFE_STAGE_FILTER);
+        ctx->ms_prep = "prep_frames_kernel";
         hipLaunchKernelGGL(prep_frames_kernel, dim3(dfe_grid1d(P.frame_max, 256 * 8), 2 * nratios), dim3(256), 0, ctx->stream, a.C, a.H, a.W, pf);
     }
     DFE_LAUNCH_CHECK(ctx);
@@ -1359,7 +1367,7 @@ static int ms_cascade_px(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const M
             bool fine_done = false;
             rc = ms_fused_scale(ctx, P, B, R, 0, fine, &fine_done);
             if (rc) return rc;
-            if (fine_done) break;
+            if (fine_done) { ctx->ms_cascade = ctx->last_kernel; break; }   // (the fused kernel's launcher has just named itself)
             // no plan for this frame: the scale-1 volume after all (fp32; rounded in place for the fp16 entry), then the px kernel
             if (a.filt) rc = dfe_spatial_matching_dispatch(ctx, R.feat[0][0], R.feat[0][1], P.fK, a.H, a.W, a.maxh, a.maxw, B.cost[0]);
             else rc = cv_frames_dispatch(ctx, B.p0[0], B.p1[0], a.C, P.sc[0].Hp, P.sc[0].Wp, (long long)P.sc[0].Hp * P.sc[0].Wp, a.k, a.k, a.maxh, a.maxw, B.cost[0]);
@@ -1393,6 +1401,7 @@ static int ms_cascade_px(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const M
             ca.fx = P.fx;
         }
         launch_cascade_px(ctx, s == 0, inl, h16, ca, dt);
+        ctx->ms_cascade = "cascade_px_kernel";
     }
     DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
@@ -1430,6 +1439,7 @@ static int ms_cascade_cell(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const
     }
     DecodeTab dt;
     fill_decode_tab(P.mg, g.ncls, dt);
+    ctx->ms_cascade = P.fast ? "cascade_argmax_kernel<fast>" : "cascade_argmax_kernel<slow>";
     if (P.fast) {
         fill_cell_maps(g, dt);
         hipLaunchKernelGGL(cascade_argmax_kernel<true>, cascade_fast_grid(a.H, a.W), dim3(kWaves * 64), P.lds, ctx->stream, g, P.mg, P.middle, (long long *)a.idx,
@@ -1631,7 +1641,7 @@ int dfe_cascading_add_f32(dfe_ctx *ctx, const float *const *in, const int *ratio
                           float *const *out) {
     DFE_ENTER(ctx);
     CascadeGeom g;
-    int rc = fill_cascade(ctx, g, ratios, nratios, maxh, maxw);
+    int rc = fill_cascade(ctx, g, ratios, nratios, maxh, maxw, false);
     if (rc) return rc;
     DFE_REQUIRE(ctx, in && out && P >= 0, DFE_E_ARG, "dfe_cascading_add_f32: bad argument");
     if (P == 0) return DFE_OK;
@@ -1653,7 +1663,7 @@ int dfe_cascading_add_backward_f32(dfe_ctx *ctx, const float *const *gradOut, co
                                    int maxw, float *const *gradIn) {
     DFE_ENTER(ctx);
     CascadeGeom g;
-    int rc = fill_cascade(ctx, g, ratios, nratios, maxh, maxw);
+    int rc = fill_cascade(ctx, g, ratios, nratios, maxh, maxw, false);
     if (rc) return rc;
     DFE_REQUIRE(ctx, gradOut && gradIn && P >= 0, DFE_E_ARG, "dfe_cascading_add_backward_f32: bad argument");
     if (P == 0) return DFE_OK;

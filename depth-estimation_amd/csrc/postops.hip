@@ -482,8 +482,19 @@ int fill_geom(dfe_ctx *ctx, MultiGeom &g, int maxh, int maxw, const int *ratios,
         DFE_REQUIRE(ctx, ratios[i] > 0, DFE_E_ARG, "ratios[%d]=%d must be positive", i, ratios[i]);
         g.ratios[i] = ratios[i];
         g.d[i] = i ? ring_d(maxw, ratios[i], ratios[i - 1]) : 0;
+        // the ring's side blocks have maxh - 2 d rows (d comes from maxw alone): fill_cascade (multiscale.hip) rejects the same windows
+        DFE_REQUIRE(ctx, maxh >= 2 * g.d[i], DFE_E_SHAPE,
+                    "scale %d (ratio %d): the %dx%d window is lower than twice its ring width d=%d (d = round(maxw (r - r') / (2 r)) serves both axes)", i,
+                    ratios[i], maxh, maxw, g.d[i]);
     }
     return DFE_OK;
+}
+
+// the same for the entries without a context: the first scale whose ring does not fit the window's height, or 0
+int ring_bad_scale(int maxh, int maxw, const int *ratios, int nratios) {
+    for (int i = 1; i < nratios; ++i)
+        if (maxh < 2 * ring_d(maxw, ratios[i], ratios[i - 1])) return i;
+    return 0;
 }
 
 }  // namespace
@@ -634,6 +645,7 @@ int dfe_x2yx_multi(dfe_ctx *ctx, int maxh, int maxw, const int *ratios, int nrat
 
 int64_t dfe_multi_nclasses(int maxh, int maxw, const int *ratios, int nratios) {
     if (!ratios || nratios < 1 || nratios > DFE_MAX_RATIOS) return -1;
+    if (ring_bad_scale(maxh, maxw, ratios, nratios)) return -1;   // (no ring layout for this window: fill_geom)
     int64_t n = (int64_t)maxh * maxw;
     for (int i = 1; i < nratios; ++i) {
         int d = ring_d(maxw, ratios[i], ratios[i - 1]);
@@ -644,6 +656,7 @@ int64_t dfe_multi_nclasses(int maxh, int maxw, const int *ratios, int nratios) {
 
 int dfe_x2yx_multi_number(int maxh, int maxw, const int *ratios, int nratios, int64_t id, int64_t *y, int64_t *x) {
     if (!ratios || !y || !x || nratios < 1 || nratios > DFE_MAX_RATIOS) return DFE_E_ARG;
+    if (ring_bad_scale(maxh, maxw, ratios, nratios)) return DFE_E_SHAPE;
     MultiGeom g;
     g.maxh = maxh; g.maxw = maxw; g.nratios = nratios;
     for (int i = 0; i < nratios; ++i) { g.ratios[i] = ratios[i]; g.d[i] = i ? ring_d(maxw, ratios[i], ratios[i - 1]) : 0; }
@@ -656,6 +669,7 @@ int dfe_x2yx_multi_number(int maxh, int maxw, const int *ratios, int nratios, in
 int64_t dfe_yx2x_multi(int maxh, int maxw, const int *ratios, int nratios, double y, double x) {
     // replaces: yx2xMulti opticalflow_model_multiscale.lua:10-52 (host scalar, used for middleIndex)
     if (!ratios || nratios < 1 || nratios > DFE_MAX_RATIOS) return -1;
+    if (ring_bad_scale(maxh, maxw, ratios, nratios)) return -1;
     x = floor(x + 0.5);
     y = floor(y + 0.5);
     auto is_in = [](double size, double v) { return (v >= -ceil(size / 2) + 1) && (v <= floor(size / 2)); };

@@ -31,6 +31,7 @@ int dfe_set_cost_volume_tile(dfe_ctx *ctx, int tyq);
 int dfe_set_option(dfe_ctx *ctx, const char *key, int value);
 int dfe_get_option(dfe_ctx *ctx, const char *key, int *value);
 const char *dfe_last_kernel(const dfe_ctx *ctx);
+const char *dfe_multiscale_last_path(dfe_ctx *ctx);
 int dfe_flow_last_path(dfe_ctx *ctx, int *i8_taken);
 int dfe_set_scratch_limit(dfe_ctx *ctx, size_t bytes);
 int dfe_device_alloc(dfe_ctx *ctx, size_t bytes, void **ptr, int *contiguous);

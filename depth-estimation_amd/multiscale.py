@@ -306,7 +306,7 @@ class MultiscaleModel(Module):
         self.probs = self._probs(self.volumes)
         ctx = get_ctx(self.volumes[0])
         rr, n = ratios_array(self.ratios)
-        ncls = lib().dfe_multi_nclasses(maxh, maxw, rr, n)
+        ncls = _nclasses(maxh, maxw, self.ratios)
         out = torch.empty((H, W, ncls), dtype=torch.float32, device=self.volumes[0].device)
         ctx.check(lib().dfe_cascade_ring_f32(ctx.handle, _ptr_array(self.probs), rr, n, H, W, maxh, maxw, ptr(out)))
         self.output = out
@@ -368,7 +368,7 @@ class MultiscaleModel(Module):
                 ctx.check(lib().dfe_ssd_cost_volume_f32(ctx.handle, ptr(c0), ptr(c1), Cc, hp + 1, wp + 1, kh, kw, maxh, maxw, ptr(vol)))
             probs.append(self._probs([vol])[0])
         rr, n = ratios_array(self.ratios)
-        ncls = lib().dfe_multi_nclasses(maxh, maxw, rr, n)
+        ncls = _nclasses(maxh, maxw, self.ratios)
         # the cascade of a single pixel: every scale's window is "the" pixel's ([P = 1][maxh][maxw] per scale)
         outs = self.cascad.forward([p.reshape(1, maxh, maxw) for p in probs])
         out = _ring_join(outs, self.ratios, maxh, maxw).reshape(1, 1, ncls)
@@ -464,13 +464,35 @@ class MultiscaleModel(Module):
         return ret
 
 
+def _ring_widths(ratios, maxh, maxw):
+    """d of every scale (0 for scale 1): round(maxw (r - r') / (2 r)), from maxw alone and used on both axes
+    (opticalflow_model_multiscale.lua:296).  The ring's side blocks have maxh - 2 d rows: a window lower than 2 d has no ring layout
+    (the reference's nn.Narrow fails there), maxh == 2 d has one with empty side blocks."""
+    ds = [0] + [int(math.floor(maxw * (ratios[i] - ratios[i - 1]) / (2.0 * ratios[i]) + 0.5)) for i in range(1, len(ratios))]
+    for s, d in enumerate(ds):
+        if maxh < 2 * d:
+            raise ValueError("multiscale: scale %d (ratio %d): the %dx%d window is lower than twice its ring width d=%d" % (s, ratios[s], maxh, maxw, d))
+    return ds
+
+
+def _nclasses(maxh, maxw, ratios):
+    """length of the joined class vector (dfe_multi_nclasses), after the ring-geometry check"""
+    _ring_widths(ratios, maxh, maxw)
+    rr, n = ratios_array(ratios)
+    ncls = lib().dfe_multi_nclasses(maxh, maxw, rr, n)
+    if ncls < 0:
+        raise ValueError("multiscale: no class layout for ratios %r and a %dx%d window" % (list(ratios), maxh, maxw))
+    return ncls
+
+
 def _ring_join(outs, ratios, maxh, maxw):
     """the "middle remover" + JoinTable(2) on per-pixel windows [P][maxh][maxw] (opticalflow_model_multiscale.lua:293-324):
     scale 1 whole, then per coarser scale the ring blocks top, left, right, bottom."""
     P = outs[0].shape[0]
     parts = [outs[0].reshape(P, -1)]
+    ds = _ring_widths(ratios, maxh, maxw)
     for i in range(1, len(ratios)):
-        d = int(math.floor(maxw * (ratios[i] - ratios[i - 1]) / (2.0 * ratios[i]) + 0.5))
+        d = ds[i]
         o = outs[i]
         parts += [o[:, :d, :].reshape(P, -1), o[:, d : maxh - d, :d].reshape(P, -1), o[:, d : maxh - d, maxw - d :].reshape(P, -1),
                   o[:, maxh - d :, :].reshape(P, -1)]

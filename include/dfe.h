@@ -104,6 +104,11 @@ int dfe_set_option(dfe_ctx *ctx, const char *key, int value);
 int dfe_get_option(dfe_ctx *ctx, const char *key, int *value);
 /* name of the kernel the last cost-volume call launched (static string) */
 const char *dfe_last_kernel(const dfe_ctx *ctx);
+/* the preparation and cascade kernels of the last one-call pyramid matcher run on this ctx, "<prep> <cascade>" -- prep_scales_kernel or
+ * prep_tiles_kernel (prep_frames_kernel with learned filters); cascade_px_kernel, cascade_argmax_kernel<fast> (one cell per lane) or
+ * cascade_argmax_kernel<slow>, or the fused volume kernel's name where the finest scale has no launch of its own.  A graph replay
+ * keeps the names of its capture.  The string lives in the ctx and is rewritten by this call.  For tests and tuning. */
+const char *dfe_multiscale_last_path(dfe_ctx *ctx);
 /* which kernel produced the last single-scale flow step's result: *i8_taken = 1 the int8 matrix-core kernel (option "cv_i8": the frames
  * were byte-valued), 0 the float kernels.  Synchronises the ctx stream.  For tests and tuning. */
 int dfe_flow_last_path(dfe_ctx *ctx, int *i8_taken);
@@ -329,6 +334,11 @@ int dfe_x2yx(dfe_ctx *ctx, const int64_t *idx, int64_t P, int maxh, int maxw, in
  *   flag is read back, so this call synchronises). */
 int dfe_x2yx_multi(dfe_ctx *ctx, int maxh, int maxw, const int *ratios, int nratios,
                    const int64_t *idx, int64_t P, int64_t *y, int64_t *x, int compat_c);
+/* The ring layout: scale s >= 1 contributes the blocks top, left, right, bottom of its window, of width
+ *   d = round(maxw (r_s - r_{s-1}) / (2 r_s)) on BOTH axes (:296); the side blocks have maxh - 2 d rows.  Every entry
+ *   that uses the layout -- the three below, dfe_x2yx_multi, dfe_cascade_ring_f32, dfe_cascade_flow_f32 and the one-call
+ *   pyramid matchers -- rejects maxh < 2 d (DFE_E_SHAPE; -1 from the two that return an id or a count).  maxh == 2 d
+ *   (empty side blocks) is accepted, which the reference's nn.Narrow is not. */
 /* host-side scalar codec (no device work): yx2xMulti :10-52, x2yxMultiNumber :83-132 */
 int64_t dfe_yx2x_multi(int maxh, int maxw, const int *ratios, int nratios, double y, double x);
 int dfe_x2yx_multi_number(int maxh, int maxw, const int *ratios, int nratios, int64_t id,

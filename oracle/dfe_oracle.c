@@ -488,7 +488,18 @@ static int ring_d(int maxw, const int *ratios, int i) { /* i: 0-based scale inde
     /* ref: opticalflow_model_multiscale.lua:94-95 / :296 round(maxw*(r_i-r_{i-1})/(2 r_i)) */
     return (int)lua_round((double)maxw * (ratios[i] - ratios[i - 1]) / (2.0 * ratios[i]));
 }
+/* The ring width comes from maxw alone and serves both axes: the side blocks have maxh - 2 d rows.  A window lower than 2 d has no
+ * ring layout (ref: :301-315, nn.Narrow(2, d+1, maxh-2*d) fails); maxh == 2 d, empty side blocks, has.  Returns the first bad scale or 0. */
+static int ring_bad_scale(int maxh, int maxw, const int *ratios, int nratios) {
+    if (maxh < 1 || maxw < 1 || nratios < 1) return -1;
+    for (int i = 0; i < nratios; ++i)
+        if (ratios[i] < 1) return -1;
+    for (int i = 1; i < nratios; ++i)
+        if (maxh < 2 * ring_d(maxw, ratios, i)) return i;
+    return 0;
+}
 int64_t orc_multi_nclasses(int maxh, int maxw, const int *ratios, int nratios) {
+    if (ring_bad_scale(maxh, maxw, ratios, nratios)) return -1;
     int64_t n = (int64_t)maxh * maxw;
     for (int i = 1; i < nratios; ++i) {
         int d = ring_d(maxw, ratios, i);
@@ -501,6 +512,7 @@ static int is_in(double size, double v) { /* ref: :13-15 */
 }
 int64_t orc_yx2x_multi(int maxh, int maxw, const int *ratios, int nratios, double y, double x) {
     /* ref: opticalflow_model_multiscale.lua:10-52 */
+    if (ring_bad_scale(maxh, maxw, ratios, nratios)) return -1;
     x = lua_round(x);
     y = lua_round(y);
     int i = 0;
@@ -531,6 +543,7 @@ int orc_x2yx_multi_number(int maxh, int maxw, const int *ratios, int nratios, in
     /* ref: opticalflow_model_multiscale.lua:83-132 */
     int chh = iceil_div2(maxh), chw = iceil_div2(maxw);
     int64_t x = id;
+    if (ring_bad_scale(maxh, maxw, ratios, nratios)) return -2;
     if (x < 1) return -1;
     if (x <= (int64_t)maxh * maxw) {
         int64_t ty = (x - 1) / maxw + 1, tx = (x - 1) % maxw + 1;
@@ -569,6 +582,7 @@ int orc_x2yx_multi_number(int maxh, int maxw, const int *ratios, int nratios, in
 int orc_x2yx_multi(int maxh, int maxw, const int *ratios, int nratios, const int64_t *idx,
                    int64_t P, int64_t *y, int64_t *x) {
     int rc = 0;
+    if (ring_bad_scale(maxh, maxw, ratios, nratios)) return -2;
     for (int64_t p = 0; p < P; ++p)
         if (orc_x2yx_multi_number(maxh, maxw, ratios, nratios, idx[p], &y[p], &x[p])) rc = -1;
     return rc;
@@ -753,7 +767,8 @@ int orc_cascading_add_backward(const float *const *gradOut, int nratios, const i
 }
 int orc_cascade_ring(const float *const *prob, int nratios, const int *ratios, int H, int W,
                      int maxh, int maxw, float *out) {
-    if (cascade_check(nratios, ratios, maxh, maxw) || nratios > ORC_MAX_RATIOS) return -1;
+    if (nratios < 1 || nratios > ORC_MAX_RATIOS || cascade_check(nratios, ratios, maxh, maxw)) return -1;
+    if (ring_bad_scale(maxh, maxw, ratios, nratios)) return -2;
     int N = maxh * maxw;
     int64_t ncls = orc_multi_nclasses(maxh, maxw, ratios, nratios);
     float *buf = (float *)malloc(sizeof(float) * (size_t)N * nratios);

@@ -108,7 +108,10 @@ void orc_extract_output_marginalized(const float *input, int64_t P, int N, doubl
 void orc_x2yx(const int64_t *idx, int64_t P, int maxh, int maxw, int64_t *y, int64_t *x);
 
 /* A10 multiscale codec, Lua scalar semantics.
- * ref: opticalflow_model_multiscale.lua:10-52 (yx2xMulti), :83-132 (x2yxMultiNumber) */
+ * ref: opticalflow_model_multiscale.lua:10-52 (yx2xMulti), :83-132 (x2yxMultiNumber)
+ * The ring width d = round(maxw (r - r') / (2 r)) serves both axes (:296): a window with maxh < 2 d for some scale has no ring
+ * layout (the reference's nn.Narrow fails).  Then orc_multi_nclasses and orc_yx2x_multi return -1, orc_x2yx_multi_number,
+ * orc_x2yx_multi and orc_cascade_ring a non-zero code, and nothing is written.  maxh == 2 d (empty side blocks) is accepted. */
 int64_t orc_yx2x_multi(int maxh, int maxw, const int *ratios, int nratios, double y, double x);
 int orc_x2yx_multi_number(int maxh, int maxw, const int *ratios, int nratios, int64_t id,
                           int64_t *y, int64_t *x);

@@ -246,6 +246,9 @@ def cascade_ring(probs, ratios, H, W, maxh, maxw):
     probs = [_f(p) for p in probs]
     r = _r(ratios)
     ncls = multi_nclasses(maxh, maxw, ratios)
+    if ncls < 0:   # no ring layout for this window (maxh < 2 d): the C function's own answer, with nothing to write into
+        arr = (C.c_void_p * len(probs))(*[p.ctypes.data for p in probs])
+        return lib().orc_cascade_ring(arr, len(probs), r, H, W, maxh, maxw, np.full(1, -7, np.float32)), None
     out = np.empty((H, W, ncls), np.float32)
     arr = (C.c_void_p * len(probs))(*[p.ctypes.data for p in probs])
     rc = lib().orc_cascade_ring(arr, len(probs), r, H, W, maxh, maxw, out)

@@ -122,13 +122,55 @@ def test_cascading_add_table_errors(dfe, cuda):
         m.forward([torch.zeros((4, 2, 2), device=cuda), torch.zeros((4, 2, 2), device=cuda)])
 
 
-@pytest.mark.parametrize("ratios,mh,mw", [([1, 2, 4], 8, 8), ([1, 2, 4, 8], 4, 4)])
-def test_cascade_ring_bit_exact_and_layout(dfe, cuda, ratios, mh, mw):
+# the staged cascade entries off the square power-of-two corner (tests/pyramid_cases.py has the one-call rows of the same geometries): maxh == 2 d,
+# a tall window, ratio 3 with an odd W, 8 x 8 with d = 3, 64 and 96 cells in a non-square window, steps 2 and 3 mixed, six scales
+STAGED_GEOMETRIES = [
+    ([1, 2], 4, 8, 24, 42),
+    ([1, 2], 8, 4, 24, 42),
+    ([1, 3], 9, 6, 18, 33),
+    ([1, 4], 8, 8, 16, 44),
+    ([1, 2, 4], 16, 4, 16, 44),
+    ([1, 2, 4], 12, 8, 16, 44),
+    ([1, 2, 6], 12, 12, 24, 42),
+    ([1, 2, 4, 8, 16, 32], 8, 8, 64, 96),
+]
+
+
+def _plant_scale_winners(probs, ratios, mh, mw, H, W):
+    """One pixel per scale whose only non-zero input is a 1.0 in cell (0, 0) of that scale's window: the cell lies in the ring's top block
+    and outside the crop the finer scales read (dh, dw >= 1), so the pixel's arg-max is that scale's first class.  The pixels sit in
+    different blocks of the coarsest ratio, so that no planted window is shared."""
+    rmax = ratios[-1]
+    assert (H // rmax) * (W // rmax) >= len(ratios)
+    for s in range(len(ratios)):
+        by, bx = divmod(s, W // rmax)
+        y, x = by * rmax, bx * rmax
+        for t, r in enumerate(ratios):
+            probs[t][y // r, x // r] = 0.0
+        probs[s][y // ratios[s], x // ratios[s], 0, 0] = 1.0
+
+
+def _assert_reaches_every_scale(idx, ratios, mh, mw):
+    from tests import pyramid_cases as pc
+
+    won = np.bincount(pc.scale_of(idx, ratios, mh, mw).ravel(), minlength=len(ratios))
+    assert (won > 0).all(), "the oracle's arg-max never lands in scale(s) %s" % np.flatnonzero(won == 0).tolist()
+
+
+@pytest.mark.parametrize("ratios,mh,mw,H,W", [pytest.param([1, 2, 4], 8, 8, 16, 24, id="ratios0-8-8"), pytest.param([1, 2, 4, 8], 4, 4, 16, 24, id="ratios1-4-4")]
+                         + STAGED_GEOMETRIES)
+def test_cascade_ring_bit_exact_and_layout(dfe, cuda, ratios, mh, mw, H, W):
     rng = np.random.default_rng(mh)
-    H, W = 16, 24
     probs = [rng.random((H // r, W // r, mh, mw), dtype=np.float32) for r in ratios]
+    staged = (ratios, mh, mw, H, W) in STAGED_GEOMETRIES
+    if staged:
+        # the geometries above: quantised probabilities (every sum is exact) and one planted winner per scale
+        probs = [(rng.integers(0, 6, (H // r, W // r, mh, mw)) / 8.0).astype(np.float32) for r in ratios]
+        _plant_scale_winners(probs, ratios, mh, mw, H, W)
     rc, ref = orc.cascade_ring(probs, ratios, H, W, mh, mw)
     assert rc == 0
+    if staged:
+        _assert_reaches_every_scale(orc.argbest_center(ref, orc.yx2x_multi(mh, mw, ratios, 0, 0), True)[0], ratios, mh, mw)
     ctx = dfe.get_ctx(0)
     tp = [T(p, cuda) for p in probs]
     out = torch.empty(ref.shape, device=cuda)
@@ -176,13 +218,16 @@ def test_multiscale_model_end_to_end(dfe, cuda):
     assert ok[inner].mean() > 0.9
 
 
-@pytest.mark.parametrize("ratios,mh,mw,H,W", [([1, 2, 4], 8, 8, 96, 128), ([1, 2], 8, 8, 40, 56), ([1, 2, 4, 8], 16, 16, 64, 64), ([1], 8, 8, 33, 47)])
+@pytest.mark.parametrize("ratios,mh,mw,H,W", [([1, 2, 4], 8, 8, 96, 128), ([1, 2], 8, 8, 40, 56), ([1, 2, 4, 8], 16, 16, 64, 64), ([1], 8, 8, 33, 47)] + STAGED_GEOMETRIES)
 def test_cascade_flow_fused_equals_ring_argmax_decode(dfe, cuda, ratios, mh, mw, H, W):
     """dfe_cascade_flow_f32 (A4+A5+A6+A10 in one pass) == dfe_cascade_ring_f32 -> dfe_argbest_center(max) -> dfe_x2yx_multi,
     bit for bit, including ties (quantised probabilities) and the centre tie-break; and == the oracle composition."""
     rng = np.random.default_rng(H + len(ratios))
     probs = [(rng.integers(0, 6, (H // r, W // r, mh, mw)) / 8.0).astype(np.float32) for r in ratios]   # many exact ties
     probs[0][3, 5] = 0.0                                                # an all-zero window at the finest scale: the centre ties with everything
+    staged = (ratios, mh, mw, H, W) in STAGED_GEOMETRIES
+    if staged:
+        _plant_scale_winners(probs, ratios, mh, mw, H, W)
     ctx = dfe.get_ctx(0)
     lib = dfe.lib()
     from depth_estimation_amd._lib import ratios_array
@@ -207,6 +252,8 @@ def test_cascade_flow_fused_equals_ring_argmax_decode(dfe, cuda, ratios, mh, mw,
     rc, oj = orc.cascade_ring(probs, ratios, H, W, mh, mw)
     oi, _ = orc.argbest_center(oj, middle, True)
     assert np.array_equal(idx.cpu().numpy(), oi)
+    if staged:
+        _assert_reaches_every_scale(oi, ratios, mh, mw)
     assert idx[3, 5].item() == middle or len(ratios) == 1 or True   # (the zero window still receives the coarser scales' mass)
 
 

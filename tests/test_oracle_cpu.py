@@ -456,3 +456,54 @@ def test_patch_mode_matching_argmax_is_block_matching_ground_truth():
         m = int((-out).reshape(-1).argmax()) + 1                   # 1-based class, as torch's max
         target = (fy + math.ceil(maxh / 2) - 1) * maxh + fx + math.ceil(maxh / 2)   # yx2x(centered2onebased(fy, fx)), opticalflow_model.lua:12-34
         assert m == target and out.reshape(-1)[m - 1] == 0
+
+
+# --- ring geometry: d comes from maxw alone and serves both axes (opticalflow_model_multiscale.lua:296) ---------------------------
+@pytest.mark.parametrize("ratios,maxh,maxw", [([1, 2], 4, 12), ([1, 3], 3, 6), ([1, 2, 4], 4, 16)])
+def test_window_lower_than_twice_its_ring_width_is_an_error(ratios, maxh, maxw):
+    """maxh < 2 d: the ring's side blocks would have maxh - 2 d < 0 rows (the reference's nn.Narrow(2, d+1, maxh-2*d) fails).  Every
+    function that uses the ring layout answers with an error and writes nothing; the whole chain raises instead of corrupting the heap
+    (it used to abort in malloc at [1,3] 3 x 6 and [1,2] 4 x 12 and to return 256 classes of nonsense at [1,2,4] 4 x 16)."""
+    H, W = 2 * ratios[-1], 6 * ratios[-1]
+    assert orc.multi_nclasses(maxh, maxw, ratios) < 0
+    assert orc.yx2x_multi(maxh, maxw, ratios, 0, 0) < 0
+    assert orc.x2yx_multi_number(maxh, maxw, ratios, 1)[0] != 0
+    ids = np.arange(1, 9, dtype=np.int64)
+    lib = orc.lib()
+    r = np.ascontiguousarray(ratios, np.int32)
+    y, x = np.full(8, -7, np.int64), np.full(8, -7, np.int64)
+    assert lib.orc_x2yx_multi(maxh, maxw, r, len(r), ids, 8, y, x) != 0
+    assert (y == -7).all() and (x == -7).all()
+    probs = [np.full((H // q, W // q, maxh, maxw), 0.25, np.float32) for q in ratios]
+    rc, out = orc.cascade_ring(probs, ratios, H, W, maxh, maxw)
+    assert rc != 0 and out is None
+    f0, f1, _, _ = rp.synth_pair(H, W, C=1, seed=1, max_flow=2)
+    with pytest.raises(AssertionError):
+        rp.multiscale_flow_oracle(f0, f1, 3, maxh, maxw, ratios)
+    # CascadingAddTable has no ring: as permissive as CascadingAddTable.lua (its own divisibility rule holds for these windows)
+    ins = [np.full((3, maxh, maxw), float(s + 1), np.float32) for s in range(len(ratios))]
+    rc, outs = orc.cascading_add(ins, ratios, maxh, maxw)
+    assert rc == 0 and np.array_equal(outs[0], np.full((3, maxh, maxw), sum(range(1, len(ratios) + 1)), np.float32))
+
+
+@pytest.mark.parametrize("ratios,maxh,maxw", [([1, 2], 4, 8), ([1, 3], 6, 9)])
+def test_window_of_exactly_twice_its_ring_width_has_empty_side_blocks(ratios, maxh, maxw):
+    """maxh == 2 d stays legal (an extension over the reference): top and bottom blocks cover the window, the side blocks are empty.  The
+    codec round-trips over every class and cascade_ring emits the coarse window whole, in row order."""
+    n = orc.multi_nclasses(maxh, maxw, ratios)
+    assert n == 2 * maxh * maxw
+    seen = set()
+    for i in range(1, n + 1):
+        rc, y, x = orc.x2yx_multi_number(maxh, maxw, ratios, i)
+        assert rc == 0
+        seen.add((i > maxh * maxw, y, x))
+        if i <= maxh * maxw:
+            assert orc.yx2x_multi(maxh, maxw, ratios, y, x) == i
+    assert len(seen) == n
+    assert orc.x2yx_multi_number(maxh, maxw, ratios, n + 1)[0] != 0
+    H, W = ratios[1], 2 * ratios[1]
+    rng = np.random.default_rng(maxh)
+    probs = [rng.integers(0, 6, (H // q, W // q, maxh, maxw)).astype(np.float32) / 8 for q in ratios]
+    rc, out = orc.cascade_ring(probs, ratios, H, W, maxh, maxw)
+    assert rc == 0 and out.shape == (H, W, n)
+    assert np.array_equal(out[..., maxh * maxw :].reshape(H, W, maxh, maxw), np.repeat(np.repeat(probs[1], ratios[1], 0), ratios[1], 1))
