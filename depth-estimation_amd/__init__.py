@@ -33,6 +33,9 @@ no CPU fallback -- a missing library or device raises.
     radialFlowDepth(..., sgm=(P1, P2)), semiGlobalAggregate         (not in the reference: the radial cost volume summed along 4 or 8 image
                                                         directions under two label-change penalties before the arg-min, the polar columns
                                                         a ring -- radial.py)
+    censusTransform, censusCostVolume, censusFlow, censusFlowDepthPair   (not in the reference: the census matching cost -- patch
+                                                        signatures, Hamming distances summed over a small box, the first minimum -- for
+                                                        frame pairs whose exposure differs; the one call returns flowDepthPair's keys -- census.py)
     getModel(geometry).forwardFlow                      (a trained single-scale model per frame pair in one call,
                                                         output_extraction_method 'max' or 'mean' -- network.py)
     imageScale, DepthEstimationAPI(...).nextFrameDepth  (image.scale; depth_estimation_api.lua:134-198, video -> depth per camera
@@ -61,6 +64,7 @@ from .opticalflow_model import (  # noqa: F401
 )
 from . import version2  # noqa: F401
 from .subpixel import flowDepthPair, refineFlowSubpixel, flowConsistency, fillHoles, weightedMedian, guidedUpsample  # noqa: F401
+from .census import censusTransform, censusCostVolume, censusFlow, censusFlowDepthPair  # noqa: F401
 from .multiscale import CascadingAddTable, MultiscaleModel, MultiscalePrefilter, getModelMultiscale, getMultiscalePrefilter  # noqa: F401
 from .network import getFilter, getFilterRadial, getModel, tables_random  # noqa: F401
 from .radial import (getRMax, getC2PMask, getP2CMask, cartesian2polar, flow2depth, getKOutput, getP2CMaskOF,  # noqa: F401

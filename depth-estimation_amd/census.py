@@ -1,0 +1,165 @@
+"""The census matching cost: an exposure-robust single-scale matcher (not in the reference: include/dfe.h).
+
+    censusTransform(img, k=7)
+        dfe_census_transform_f32 / _u8: the signature of every k x k (or kh x kw) patch, its cells compared with its centre
+    censusCostVolume(sig0, sig1, hWin, wWin, agg=3)
+        dfe_census_cost_volume_f32: Hamming distances summed over the channels and an agg x agg box, as a float volume (the staged route)
+    censusFlow(sig0, sig1, nbits, hWin, wWin, agg=3)
+        dfe_census_flow_f32: the first minimum of that cost with the centre rule, its match score and the decoded flow; no volume
+    censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consistency=None, gate=False, fill=None, median=None)
+        dfe_census_flow_depth_pair_f32 / _u8: frames -> flow, match score, depth, depth confidence, with flowDepthPair's keys
+"""
+import torch
+
+from ._lib import lib
+from .context import get_ctx, ptr
+from .subpixel import _frames, _median_arg, _with_fill, flowConsistency
+
+MAX_CELLS = 1096   # window cells: the single-scale step's own ceiling
+
+
+def _patch(k, name):
+    kh, kw = k if isinstance(k, (tuple, list)) and len(k) == 2 else (k, k)
+    ok = all(isinstance(n, int) and not isinstance(n, bool) and n >= 3 and n % 2 == 1 for n in (kh, kw))
+    if not ok or kh * kw > 64:
+        raise ValueError("%s: k=%r: odd sides of at least 3 with at most 64 cells expected" % (name, k))
+    return kh, kw
+
+
+def _region(name, C, Hp, Wp, hWin, wWin, agg):
+    """(Ha, Wa) of the aggregated cost, after the checks of the window, agg and the channel count"""
+    if not all(isinstance(n, int) and not isinstance(n, bool) for n in (hWin, wWin)) or hWin < 1 or wWin < 1:
+        raise ValueError("%s: window %r x %r" % (name, hWin, wWin))
+    if hWin * wWin > MAX_CELLS:
+        raise ValueError("%s: window %d x %d has more than %d cells" % (name, hWin, wWin, MAX_CELLS))
+    if not isinstance(agg, int) or isinstance(agg, bool) or agg not in (1, 3, 5):
+        raise ValueError("%s: agg=%r must be 1, 3 or 5" % (name, agg))
+    if not 1 <= C <= 4:
+        raise ValueError("%s: %d channels (1 .. 4)" % (name, C))
+    Ha, Wa = Hp - hWin + 1 - agg + 1, Wp - wWin + 1 - agg + 1
+    if Ha < 1 or Wa < 1:
+        raise ValueError("%s: %d x %d patch positions leave no pixel for a %d x %d window summed over %d x %d" % (name, Hp, Wp, hWin, wWin, agg, agg))
+    return Ha, Wa
+
+
+def _sigs(sig0, sig1, name):
+    if not (isinstance(sig0, torch.Tensor) and isinstance(sig1, torch.Tensor)) or sig0.dtype != torch.int64 or sig1.dtype != torch.int64:
+        raise TypeError("%s: two int64 signature tensors expected" % name)
+    if sig0.dim() != 3 or sig0.shape != sig1.shape:
+        raise ValueError("%s: two C x Hp x Wp signature tensors of one shape expected, got %s and %s" % (name, tuple(sig0.shape), tuple(sig1.shape)))
+    return sig0, sig1
+
+
+def _on_device(name, *tensors):
+    if not all(t.is_cuda for t in tensors):
+        raise TypeError("%s: CUDA tensors expected" % name)
+    if any(t.device != tensors[0].device for t in tensors):
+        raise ValueError("%s: tensors on different devices" % name)
+    return [t.contiguous() for t in tensors]
+
+
+def censusTransform(img, k=7):
+    """Census signatures of a C x H x W frame (float32 or uint8, 1 <= C <= 4): int64 [C][Hp][Wp] holding the bits, Hp = H - kh + 1,
+    Wp = W - kw + 1, a patch indexed by its top-left corner.  k is an int or (kh, kw), odd sides of at least 3, kh kw <= 64.  Bit b is set
+    iff the b-th cell of the patch, row-major with the centre skipped, is strictly below the centre (include/dfe.h)."""
+    kh, kw = _patch(k, "censusTransform")
+    if not isinstance(img, torch.Tensor) or img.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("censusTransform: a float32 or uint8 frame expected")
+    if img.dim() != 3 or not 1 <= img.shape[0] <= 4:
+        raise ValueError("censusTransform: a C x H x W frame (C = 1 .. 4) expected, got %s" % (tuple(img.shape),))
+    C, H, W = img.shape
+    if H < kh or W < kw or H > 32768 or W > 32768:
+        raise ValueError("censusTransform: frame %d x %d for a %d x %d patch (up to 32768 a side)" % (H, W, kh, kw))
+    (img,) = _on_device("censusTransform", img)
+    sig = torch.empty((C, H - kh + 1, W - kw + 1), dtype=torch.int64, device=img.device)
+    ctx = get_ctx(img)
+    fn = lib().dfe_census_transform_u8 if img.dtype == torch.uint8 else lib().dfe_census_transform_f32
+    ctx.check(fn(ctx.handle, ptr(img), C, H, W, kh, kw, ptr(sig)))
+    return sig
+
+
+def censusCostVolume(sig0, sig1, hWin, wWin, agg=3):
+    """The aggregated census cost of two signature tensors [C][Hp][Wp]: float32 [Ha][Wa][hWin][wWin], the SSD volume's geometry and class
+    order, Ha = Hp - hWin + 1 - agg + 1 (include/dfe.h).  The staged route: censusFlow gives the same flow without the volume."""
+    sig0, sig1 = _sigs(sig0, sig1, "censusCostVolume")
+    C, Hp, Wp = sig0.shape
+    Ha, Wa = _region("censusCostVolume", C, Hp, Wp, hWin, wWin, agg)
+    sig0, sig1 = _on_device("censusCostVolume", sig0, sig1)
+    out = torch.empty((Ha, Wa, hWin, wWin), dtype=torch.float32, device=sig0.device)
+    ctx = get_ctx(sig0)
+    ctx.check(lib().dfe_census_cost_volume_f32(ctx.handle, ptr(sig0), ptr(sig1), C, Hp, Wp, hWin, wWin, agg, ptr(out)))
+    return out
+
+
+def censusFlow(sig0, sig1, nbits, hWin, wWin, agg=3):
+    """The fused sweep: dict(idx int64 (1-based class, first minimum, the centre wins an exact tie), best (the cost), match
+    (1 - best / (nbits C agg^2)), flow_y, flow_x), all [Ha][Wa].  nbits = kh kw - 1 of the transform that made the signatures."""
+    sig0, sig1 = _sigs(sig0, sig1, "censusFlow")
+    C, Hp, Wp = sig0.shape
+    if not isinstance(nbits, int) or isinstance(nbits, bool) or not 1 <= nbits <= 63:
+        raise ValueError("censusFlow: nbits=%r (1 .. 63: the patch's cells less its centre)" % (nbits,))
+    Ha, Wa = _region("censusFlow", C, Hp, Wp, hWin, wWin, agg)
+    sig0, sig1 = _on_device("censusFlow", sig0, sig1)
+    dev = sig0.device
+    res = {"idx": torch.empty((Ha, Wa), dtype=torch.int64, device=dev)}
+    for key in ("best", "match", "flow_y", "flow_x"):
+        res[key] = torch.empty((Ha, Wa), dtype=torch.float32, device=dev)
+    ctx = get_ctx(sig0)
+    ctx.check(lib().dfe_census_flow_f32(ctx.handle, ptr(sig0), ptr(sig1), C, Hp, Wp, nbits, hWin, wWin, agg, ptr(res["idx"]), ptr(res["best"]),
+                                        ptr(res["match"]), ptr(res["flow_y"]), ptr(res["flow_x"])))
+    return res
+
+
+def _pair(a, b, k, hWin, wWin, agg, fx, fy, scale):
+    C, H, W = a.shape
+    flow = torch.empty((2, H, W), dtype=torch.float32, device=a.device)
+    match = torch.empty((H, W), dtype=torch.float32, device=a.device)
+    depth = torch.empty_like(match)
+    conf = torch.empty_like(match)
+    ctx = get_ctx(a)
+    if a.dtype == torch.uint8:
+        rc = lib().dfe_census_flow_depth_pair_u8(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, scale, ptr(flow), ptr(match), ptr(depth),
+                                                 ptr(conf))
+    else:
+        rc = lib().dfe_census_flow_depth_pair_f32(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, ptr(flow), ptr(match), ptr(depth), ptr(conf))
+    ctx.check(rc)
+    return {"flow": flow, "scores": match, "depth": depth, "depth_conf": conf}
+
+
+def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consistency=None, gate=False, fill=None, median=None):
+    """One frame pair through the census matcher: C x H x W frames (float32 or uint8, 1 <= C <= 4), a k x k patch (k odd, 3 .. 7), an
+    hWin x wWin search window, the Hamming cost summed over an agg x agg box (1, 3 or 5), foe = (x, y) focus of expansion.  Returns the keys
+    of flowDepthPair: flow [2][H][W] (y, x), scores [H][W] = the match score 1 - best / ((k k - 1) C agg^2), depth, depth_conf, zero outside
+    the centre-pasted Ha x Wa region at ((H - Ha) // 2, (W - Wa) // 2), Ha = H - k + 1 - hWin + 1 - agg + 1.  scale is accepted for uint8
+    frames as flowDepthPair accepts it and changes no bit: the bytes are compared as they are.
+    consistency=tol: the call also runs from img2 to img1 and the dict gains flow_bw, consistent and consistency_err =
+    flowConsistency(flow, flow_bw, tol, region); gate=True multiplies scores and depth_conf by consistent.  fill and median: as in
+    flowDepthPair, over the region above, with weight 1 where scores > 0 (and consistent)."""
+    median = _median_arg(median)
+    for t in (img1, img2):
+        if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.uint8) or t.dtype != img1.dtype:
+            raise TypeError("censusFlowDepthPair: two float32 or two uint8 frames expected")
+    if img1.dim() != 3 or img1.shape != img2.shape:
+        raise ValueError("censusFlowDepthPair: two C x H x W frames of one shape expected, got %s and %s" % (tuple(img1.shape), tuple(img2.shape)))
+    a, b = img1, img2
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError("censusFlowDepthPair: k=%r: an odd int expected" % (k,))
+    _patch(k, "censusFlowDepthPair")
+    C, H, W = a.shape
+    if H < k or W < k or H > 32768 or W > 32768:
+        raise ValueError("censusFlowDepthPair: frame %d x %d for a %d x %d patch (up to 32768 a side)" % (H, W, k, k))
+    Ha, Wa = _region("censusFlowDepthPair", C, H - k + 1, W - k + 1, hWin, wWin, agg)
+    if not float(scale) > 0:
+        raise ValueError("censusFlowDepthPair: scale=%r must be positive" % (scale,))
+    a, b = _frames(a, b, "censusFlowDepthPair")   # (the device check comes last: every check above needs none)
+    R = ((H - Ha) // 2, (W - Wa) // 2, Ha, Wa)
+    fx, fy = float(foe[0]), float(foe[1])
+    res = _pair(a, b, k, hWin, wWin, agg, fx, fy, float(scale))
+    if consistency is not None:
+        bw = _pair(b, a, k, hWin, wWin, agg, fx, fy, float(scale))["flow"]
+        mask, err = flowConsistency(res["flow"], bw, float(consistency), R)
+        res.update(flow_bw=bw, consistent=mask, consistency_err=err)
+        if gate:
+            res["scores"] = res["scores"] * mask
+            res["depth_conf"] = res["depth_conf"] * mask
+    return _with_fill(res, fill, median, a, k, hWin, wWin, fx, fy, region=R)

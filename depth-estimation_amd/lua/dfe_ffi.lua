@@ -54,6 +54,12 @@ int dfe_radial_flow_depth_pair_f32(dfe_ctx *ctx, const dfe_radial_params *p, con
 int dfe_radial_flow_depth_pair_subpixel_f32(dfe_ctx *ctx, const dfe_radial_params *p, const float *prev, const float *cur, double e2x, double e2y, const float *w1, const float *b1, const float *w2, const float *b2, float *volume, float *polar_flow, float *cart_flow, float *depth, float *conf);
 int dfe_sgm_aggregate_f32(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *agg, float *flow);
 int dfe_radial_flow_depth_pair_sgm_f32(dfe_ctx *ctx, const dfe_radial_params *p, const float *prev, const float *cur, double e2x, double e2y, const float *w1, const float *b1, const float *w2, const float *b2, float P1, float P2, unsigned paths, int ring, int subpixel, float *volume, float *agg_volume, float *polar_flow, float *cart_flow, float *depth, float *conf);
+int dfe_census_transform_f32(dfe_ctx *ctx, const float *I, int C, int H, int W, int kh, int kw, uint64_t *sig);
+int dfe_census_transform_u8(dfe_ctx *ctx, const uint8_t *I, int C, int H, int W, int kh, int kw, uint64_t *sig);
+int dfe_census_cost_volume_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1, int C, int Hp, int Wp, int hWin, int wWin, int agg, float *out);
+int dfe_census_flow_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1, int C, int Hp, int Wp, int nbits, int hWin, int wWin, int agg, int64_t *idx, float *best, float *match, float *flow_y, float *flow_x);
+int dfe_census_flow_depth_pair_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float *flow, float *match, float *depth, float *depth_conf);
+int dfe_census_flow_depth_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float scale, float *flow, float *match, float *depth, float *depth_conf);
 int dfe_spatial_matching_backward_f32(dfe_ctx *ctx, const float *in1, const float *in2, const float *gradOut, int K, int H1, int W1, int maxh, int maxw, float *gradIn1, float *gradIn2);
 int dfe_radial_matching_backward_f32(dfe_ctx *ctx, const float *in1, const float *in2, const float *gradOut, int K, int H1, int W, int hWin, float *gradIn1, float *gradIn2);
 int dfe_argbest_center(dfe_ctx *ctx, const float *vol, int64_t P, int N, int middle, int take_max, int64_t *idx, float *best);

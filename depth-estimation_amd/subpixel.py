@@ -54,15 +54,16 @@ def _median_arg(median):
     return k, float(sigma)
 
 
-def _with_fill(res, fill, median, guide, k, hWin, wWin, fx, fy):
-    """the keys of flowDepthPair(..., fill=..., median=...) from the step's own outputs, which stay as they are"""
+def _with_fill(res, fill, median, guide, k, hWin, wWin, fx, fy, region=None):
+    """the keys of flowDepthPair(..., fill=..., median=...) from the step's own outputs, which stay as they are; region = (y0, x0, Ho, Wo)
+    of the step's output, by default the single-scale SSD step's"""
     want_fill = not (fill is None or fill is False)
     if not want_fill and median is None:
         return res
     flow, scores = res["flow"], res["scores"]
     _, H, W = flow.shape
     Ho, Wo = H - k + 1 - hWin + 1, W - k + 1 - wWin + 1
-    R = ((H - Ho) // 2, (W - Wo) // 2, Ho, Wo)
+    R = ((H - Ho) // 2, (W - Wo) // 2, Ho, Wo) if region is None else tuple(int(v) for v in region)
     wgt = _kept_weight(res)
     ctx = get_ctx(flow)
 

@@ -290,6 +290,51 @@ int dfe_radial_flow_depth_pair_sgm_f32(dfe_ctx *ctx, const dfe_radial_params *p,
                                        float P2, unsigned paths, int ring, int subpixel, float *volume, float *agg_volume,
                                        float *polar_flow, float *cart_flow, float *depth, float *conf);
 
+/* ---- the census matching cost: an exposure-robust single-scale matcher (NOT in the reference, whose raw-frame matchers all score
+ * by the sum of squared differences) ------------------------------------------------------------------------ */
+/* Integers only up to the match score, so every result below is exact.
+ *   Signature.  kh, kw odd, at least 3, kh kw <= 64.  Patch positions Hp = H - kh + 1 by Wp = W - kw + 1, a patch indexed by its
+ *     top-left corner as in dfe_ssd_cost_volume_f32.  S[c][y][x] is a uint64_t: walk the patch row-major over (i, j) and skip the
+ *     centre (floor(kh / 2), floor(kw / 2)); the b-th visited cell sets bit b iff I[c][y+i][x+j] < I[c][y+floor(kh/2)][x+floor(kw/2)].
+ *     The comparison is strict and on the stored values; with a NaN on either side it is false; the unused high bits are 0.  The
+ *     byte entry compares the bytes themselves: the bits of the float entry on float(byte) * scale for any scale > 0.
+ *   Hamming.  h[y][x][dy][dx] = sum_c popcount(S0[c][y+oy][x+ox] ^ S1[c][y+dy][x+dx]), oy = floor((hWin - 1) / 2),
+ *     ox = floor((wWin - 1) / 2), y < Ho = Hp - hWin + 1, x < Wo = Wp - wWin + 1: the geometry and class order of the SSD volume,
+ *     for odd and even windows alike.
+ *   Aggregated cost.  agg = a in {1, 3, 5}: cost[y][x][dy][dx] = sum_{u < a, v < a} h[y+u][x+v][dy][dx], Ha = Ho - a + 1 by
+ *     Wa = Wo - a + 1.  At most 63 C a^2, so exact in fp32: the volume is stored as float, and dfe_flow_tail, dfe_argbest_center and
+ *     dfe_extract_output read it as they read any other.
+ *   Flow.  The first minimum in class order (class = dy wWin + dx + 1); the centre class wins an exact tie with the best: the rule
+ *     and the middle index of dfe_ssd_flow_f32 / dfe_argbest_center (getMiddleIndex).  Decoded as dfe_x2yx decodes.
+ *   Match score.  match = 1.0f - (float)best / (float)(nbits C a^2), nbits = kh kw - 1: one rounded fp32 division, one rounded
+ *     subtraction.  Above 0 unless every bit disagrees.
+ *   Paste.  The full-frame outputs hold the Ha x Wa region at pad_t = (H - Ha) / 2, pad_l = (W - Wa) / 2 (integer divisions, the
+ *     single-scale step's rule) and 0 elsewhere; depth and depth_conf are made from the pasted flow as dfe_flow_depth_pair_f32
+ *     makes them (dfe_flow_to_depth_cartesian, fix_dot = 0).
+ * Limits: 1 <= C <= 4, kh / kw as above, agg in {1, 3, 5}, nbits in 1 .. 63, no NULL input (DFE_E_ARG); hWin wWin <= 1096
+ * (DFE_E_UNSUPPORTED); every frame side and Hp, Wp at most 32768 and Ha, Wa >= 1 (DFE_E_SHAPE).  Refused before any launch.
+ * Asynchronous on the ctx's stream.
+ * dfe_census_transform_*: I [C][H][W] -> sig [C][Hp][Wp].  One launch, a 4 x 64 tile of positions with its halo in LDS. */
+int dfe_census_transform_f32(dfe_ctx *ctx, const float *I, int C, int H, int W, int kh, int kw, uint64_t *sig);
+int dfe_census_transform_u8(dfe_ctx *ctx, const uint8_t *I, int C, int H, int W, int kh, int kw, uint64_t *sig);
+/* The staged route: out [Ha][Wa][hWin][wWin], for tests and for callers who want the volume.  A thread per cell. */
+int dfe_census_cost_volume_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1, int C, int Hp, int Wp, int hWin,
+                               int wWin, int agg, float *out);
+/* The fused route: no volume reaches memory.  idx (1-based class), best (the cost), match, flow_y, flow_x, all [Ha][Wa], any may be
+ * NULL.  Equal to dfe_census_cost_volume_f32 -> dfe_argbest_center(middle = getMiddleIndex) -> dfe_x2yx.  A workgroup stages
+ * frame 1's signatures of a band of window rows in LDS (at most 64 KB), a lane keeps frame 0's signatures of its column in
+ * registers and walks down it once per class; the box sum is DPP row shifts across and register adds down. */
+int dfe_census_flow_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1, int C, int Hp, int Wp, int nbits, int hWin,
+                        int wWin, int agg, int64_t *idx, float *best, float *match, float *flow_y, float *flow_x);
+/* The one call: two transforms (k x k patch) into the ctx's scratch arena, the fused sweep storing at the pasted positions, then
+ * the border and depth pass of the single-scale step.  flow [2][H][W] (y, x), match [H][W], depth / depth_conf [H][W] (both or
+ * neither).  Bit-identical to the staged public calls plus the paste.  scale only has to be positive: it changes no bit. */
+int dfe_census_flow_depth_pair_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin,
+                                   int agg, float foe_x, float foe_y, float *flow, float *match, float *depth, float *depth_conf);
+int dfe_census_flow_depth_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin,
+                                  int agg, float foe_x, float foe_y, float scale, float *flow, float *match, float *depth,
+                                  float *depth_conf);
+
 /* ---- N2: gradients of the two matchers (training drivers call model:backward through them) ------- */
 /* replaces: nn.SpatialMatching:updateGradInput / nn.SpatialRadialMatching:updateGradInput (un-vendored nnx), reached
  *   from radial/train_radial_opticalflow.lua:228-252 and opticalflow.lua:296-338.  gradOut has the forward output's
