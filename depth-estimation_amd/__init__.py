@@ -21,14 +21,14 @@ no CPU fallback -- a missing library or device raises.
     flowDepthPair, refineFlowSubpixel                   (not in the reference: the single-scale step in one call, and its
                                                         opt-in sub-pixel flow -- subpixel.py)
     flowDepthPair(..., consistency=tol, gate=False), flowConsistency   (not in the reference: the step in both directions with a
-                                                        forward-backward occlusion mask, and that check on any two flow fields -- subpixel.py)
+                                                        forward-backward occlusion mask (subpixel.py), and that check on any two flow fields (fields.py))
     flowDepthPair(..., fill=True), fillHoles            (not in the reference: the rejected pixels filled from the kept ones by a
-                                                        confidence-weighted push-pull, and that operator on any planes -- subpixel.py)
+                                                        confidence-weighted push-pull (subpixel.py), and that operator on any planes (fields.py))
     flowDepthPair(..., median=k | (k, sigma)), weightedMedian   (not in the reference: the flow through a confidence-weighted median
-                                                        guided by the first frame, and that operator on any planes -- subpixel.py)
+                                                        guided by the first frame (subpixel.py), and that operator on any planes (fields.py))
     guidedUpsample                                      (not in the reference: a flow or depth field back at the camera's resolution by joint
                                                         bilateral upsampling with a confidence plane, holes skipped, motion boundaries
-                                                        kept by the frame itself -- subpixel.py)
+                                                        kept by the frame itself -- fields.py)
     radialFlowDepth(..., subpixel=True), refineRadialFlowSubpixel   (not in the reference: sub-pixel radial flow -- radial.py)
     radialFlowDepth(..., sgm=(P1, P2)), semiGlobalAggregate         (not in the reference: the radial cost volume summed along 4 or 8 image
                                                         directions under two label-change penalties before the arg-min, the polar columns
@@ -63,7 +63,8 @@ from .opticalflow_model import (  # noqa: F401
     rgb2y,
 )
 from . import version2  # noqa: F401
-from .subpixel import flowDepthPair, refineFlowSubpixel, flowConsistency, fillHoles, weightedMedian, guidedUpsample  # noqa: F401
+from .subpixel import flowDepthPair, refineFlowSubpixel  # noqa: F401
+from .fields import flowConsistency, fillHoles, weightedMedian, guidedUpsample  # noqa: F401
 from .census import censusTransform, censusCostVolume, censusFlow, censusFlowDepthPair  # noqa: F401
 from .multiscale import CascadingAddTable, MultiscaleModel, MultiscalePrefilter, getModelMultiscale, getMultiscalePrefilter  # noqa: F401
 from .network import getFilter, getFilterRadial, getModel, tables_random  # noqa: F401

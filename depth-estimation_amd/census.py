@@ -13,7 +13,8 @@ import torch
 
 from ._lib import lib
 from .context import get_ctx, ptr
-from .subpixel import _frames, _median_arg, _with_fill, flowConsistency
+from .fields import _on_device, flowConsistency
+from .subpixel import _frames, _median_arg, _with_fill
 
 MAX_CELLS = 1096   # window cells: the single-scale step's own ceiling
 
@@ -50,14 +51,6 @@ def _sigs(sig0, sig1, name):
     return sig0, sig1
 
 
-def _on_device(name, *tensors):
-    if not all(t.is_cuda for t in tensors):
-        raise TypeError("%s: CUDA tensors expected" % name)
-    if any(t.device != tensors[0].device for t in tensors):
-        raise ValueError("%s: tensors on different devices" % name)
-    return [t.contiguous() for t in tensors]
-
-
 def censusTransform(img, k=7):
     """Census signatures of a C x H x W frame (float32 or uint8, 1 <= C <= 4): int64 [C][Hp][Wp] holding the bits, Hp = H - kh + 1,
     Wp = W - kw + 1, a patch indexed by its top-left corner.  k is an int or (kh, kw), odd sides of at least 3, kh kw <= 64.  Bit b is set
@@ -70,7 +63,7 @@ def censusTransform(img, k=7):
     C, H, W = img.shape
     if H < kh or W < kw or H > 32768 or W > 32768:
         raise ValueError("censusTransform: frame %d x %d for a %d x %d patch (up to 32768 a side)" % (H, W, kh, kw))
-    (img,) = _on_device("censusTransform", img)
+    (img,) = _on_device("censusTransform", (img,), dtype=None, expected="CUDA tensors expected")
     sig = torch.empty((C, H - kh + 1, W - kw + 1), dtype=torch.int64, device=img.device)
     ctx = get_ctx(img)
     fn = lib().dfe_census_transform_u8 if img.dtype == torch.uint8 else lib().dfe_census_transform_f32
@@ -84,7 +77,7 @@ def censusCostVolume(sig0, sig1, hWin, wWin, agg=3):
     sig0, sig1 = _sigs(sig0, sig1, "censusCostVolume")
     C, Hp, Wp = sig0.shape
     Ha, Wa = _region("censusCostVolume", C, Hp, Wp, hWin, wWin, agg)
-    sig0, sig1 = _on_device("censusCostVolume", sig0, sig1)
+    sig0, sig1 = _on_device("censusCostVolume", (sig0, sig1), dtype=None, expected="CUDA tensors expected")
     out = torch.empty((Ha, Wa, hWin, wWin), dtype=torch.float32, device=sig0.device)
     ctx = get_ctx(sig0)
     ctx.check(lib().dfe_census_cost_volume_f32(ctx.handle, ptr(sig0), ptr(sig1), C, Hp, Wp, hWin, wWin, agg, ptr(out)))
@@ -99,7 +92,7 @@ def censusFlow(sig0, sig1, nbits, hWin, wWin, agg=3):
     if not isinstance(nbits, int) or isinstance(nbits, bool) or not 1 <= nbits <= 63:
         raise ValueError("censusFlow: nbits=%r (1 .. 63: the patch's cells less its centre)" % (nbits,))
     Ha, Wa = _region("censusFlow", C, Hp, Wp, hWin, wWin, agg)
-    sig0, sig1 = _on_device("censusFlow", sig0, sig1)
+    sig0, sig1 = _on_device("censusFlow", (sig0, sig1), dtype=None, expected="CUDA tensors expected")
     dev = sig0.device
     res = {"idx": torch.empty((Ha, Wa), dtype=torch.int64, device=dev)}
     for key in ("best", "match", "flow_y", "flow_x"):

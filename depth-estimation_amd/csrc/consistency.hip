@@ -8,7 +8,7 @@
 // mask / err (and the in-place gate of scores / depth_conf) are whole 256-B runs; the zero border is written by the same launch.  The
 // (up to) four taps of bw are gathered through L1 / L2: displacements are bounded by the search window, so a wave's taps lie in a few
 // rows around its own.
-#include "dfe_internal.h"
+#include "dfe_field.h"
 
 namespace {
 
@@ -20,8 +20,6 @@ struct ConsistencyArgs {
     float *scores, *conf;          // [H][W] or null: multiplied in place by the mask inside R (the gate of the one-call)
 };
 
-__device__ __forceinline__ bool cons_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }   // (false for NaN)
-
 __global__ __launch_bounds__(256) void flow_consistency_kernel(ConsistencyArgs a) {
 #pragma clang fp contract(off)
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -32,7 +30,7 @@ __global__ __launch_bounds__(256) void flow_consistency_kernel(ConsistencyArgs a
     if (inR) {
         const float fy = a.fw[p], fx = a.fw[HW + p];
         e = __builtin_inff();
-        if (cons_finite(fy) && cons_finite(fx)) {
+        if (dfe_finite(fy) && dfe_finite(fx)) {
             const float qy = (float)y + fy, qx = (float)x + fx;
             const float fly = floorf(qy), cly = ceilf(qy), flx = floorf(qx), clx = ceilf(qx);
             // reach, decided on the floats: only coordinates inside R (inside the frame) are converted to int
@@ -46,7 +44,7 @@ __global__ __launch_bounds__(256) void flow_consistency_kernel(ConsistencyArgs a
                 if (uy != 0.f && wx != 0.f) { const float w = uy * wx; by += w * a.bw[r0 + c1]; bx += w * a.bw[HW + r0 + c1]; }
                 if (wy != 0.f && ux != 0.f) { const float w = wy * ux; by += w * a.bw[r1 + c0]; bx += w * a.bw[HW + r1 + c0]; }
                 if (wy != 0.f && wx != 0.f) { const float w = wy * wx; by += w * a.bw[r1 + c1]; bx += w * a.bw[HW + r1 + c1]; }
-                if (cons_finite(by) && cons_finite(bx)) {
+                if (dfe_finite(by) && dfe_finite(bx)) {
                     const float ey = fy + by, ex = fx + bx;
                     const float d2 = ey * ey + ex * ex;
                     e = sqrtf(d2);
@@ -59,14 +57,6 @@ __global__ __launch_bounds__(256) void flow_consistency_kernel(ConsistencyArgs a
     }
     a.mask[p] = m;
     if (a.err) a.err[p] = e;
-}
-
-// the argument rules of the operator under the caller's name; R inside the frame, tol >= 0 (false for NaN)
-int consistency_check(dfe_ctx *ctx, const char *fn, int H, int W, int y0, int x0, int Ho, int Wo, float tol) {
-    DFE_REQUIRE(ctx, tol >= 0.f, DFE_E_ARG, "%s: tol=%g must be >= 0", fn, (double)tol);
-    DFE_REQUIRE(ctx, H > 0 && W > 0 && Ho > 0 && Wo > 0 && y0 >= 0 && x0 >= 0 && (long long)y0 + Ho <= H && (long long)x0 + Wo <= W, DFE_E_SHAPE,
-                "%s: region %dx%d at (%d, %d) does not lie inside the %dx%d frame", fn, Ho, Wo, y0, x0, H, W);
-    return DFE_OK;
 }
 
 int launch_consistency(dfe_ctx *ctx, const float *fw, const float *bw, int H, int W, int y0, int x0, int Ho, int Wo, float tol, float *mask, float *err,
@@ -114,8 +104,8 @@ int dfe_flow_consistency_f32(dfe_ctx *ctx, const float *fw, const float *bw, int
                              float *err) {
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, fw && bw && mask, DFE_E_ARG, "dfe_flow_consistency_f32: NULL tensor");
-    int rc = consistency_check(ctx, "dfe_flow_consistency_f32", H, W, y0, x0, Ho, Wo, tol);
-    if (rc) return rc;
+    DFE_REQUIRE(ctx, tol >= 0.f, DFE_E_ARG, "dfe_flow_consistency_f32: tol=%g must be >= 0", (double)tol);   // (false for NaN)
+    if (int rc = dfe_region_check(ctx, "dfe_flow_consistency_f32", H, W, y0, x0, Ho, Wo)) return rc;
     return launch_consistency(ctx, fw, bw, H, W, y0, x0, Ho, Wo, tol, mask, err, nullptr, nullptr);
 }
 

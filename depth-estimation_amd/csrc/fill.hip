@@ -13,7 +13,7 @@
 //                       step: 3 MB), the cost is launch boundaries, and the upper levels are the ones with nothing to do per launch.
 // A level is C + 1 planes [h][w]: the values, then the weight a; its pull overwrites them in place with f and the mask g (a pull reads
 // the coarser level and the pixel's own cell only).  The top needs no pass: g = (a > 0) is what a tap's test `!= 0` reads off a.
-#include "dfe_internal.h"
+#include "dfe_field.h"
 
 #pragma clang fp contract(off)
 
@@ -34,8 +34,6 @@ struct FillFrame {
     int H, W, y0, x0, Ho, Wo;
 };
 
-__device__ __forceinline__ bool fill_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }   // (false for NaN)
-
 template <int C> __device__ __forceinline__ FillPx<C> fill_zero() {
     FillPx<C> r;
 #pragma unroll
@@ -44,21 +42,12 @@ template <int C> __device__ __forceinline__ FillPx<C> fill_zero() {
     return r;
 }
 
-// level 0 at (y, x) of R: a = min(w, 1) where w and every channel are finite and w >= 1e-6f, else a = 0 and the values read as 0 (what
-// is under a zero weight never enters arithmetic)
+// level 0 at (y, x) of R: the sample rule of dfe_field.h; where the sample does not exist the values read as 0 (what is under a zero
+// weight never enters arithmetic)
 template <int C> __device__ __forceinline__ FillPx<C> fill_read0(const FillFrame &f, int y, int x) {
-    const long long HW = (long long)f.H * f.W, p = (long long)(f.y0 + y) * f.W + f.x0 + x;
-    const float wv = f.w[p];
-    bool ok = fill_finite(wv) && wv >= 1e-6f;
     FillPx<C> r;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        r.v[c] = f.v[c * HW + p];
-        ok = ok && fill_finite(r.v[c]);
-    }
-    if (!ok) return fill_zero<C>();
-    r.a = fminf(wv, 1.f);
-    return r;
+    r.a = dfe_sample_read<C>(f.v, f.w, (long long)f.H * f.W, (long long)(f.y0 + y) * f.W + f.x0 + x, r.v);
+    return r.a != 0.f ? r : fill_zero<C>();
 }
 
 template <int C> __device__ __forceinline__ FillPx<C> fill_load(const float *p, long long plane, long long i) {
@@ -332,10 +321,9 @@ int dfe_fill_holes_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const 
                        float *filled) {
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, v && w && out, DFE_E_ARG, "dfe_fill_holes_f32: NULL tensor");
-    DFE_REQUIRE(ctx, C >= 1 && C <= 4, DFE_E_ARG, "dfe_fill_holes_f32: C=%d must be 1 .. 4", C);
+    if (int rc = dfe_channels_check(ctx, "dfe_fill_holes_f32", C)) return rc;
     DFE_REQUIRE(ctx, levels >= 0, DFE_E_ARG, "dfe_fill_holes_f32: levels=%d must be >= 0", levels);
-    DFE_REQUIRE(ctx, H > 0 && W > 0 && Ho > 0 && Wo > 0 && y0 >= 0 && x0 >= 0 && (long long)y0 + Ho <= H && (long long)x0 + Wo <= W, DFE_E_SHAPE,
-                "dfe_fill_holes_f32: region %dx%d at (%d, %d) does not lie inside the %dx%d frame", Ho, Wo, y0, x0, H, W);
+    if (int rc = dfe_region_check(ctx, "dfe_fill_holes_f32", H, W, y0, x0, Ho, Wo)) return rc;
     const FillPlan p = fill_plan(C, H, W, Ho, Wo, levels, ctx->opt[DFE_OPT_FILL_APEX]);
     float *scr = nullptr;
     if (p.floats) {   // the ctx's side buffer: grown once, then no allocation per call
@@ -345,12 +333,7 @@ int dfe_fill_holes_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const 
         scr = (float *)aux;
     }
     FillFrame f{v, w, out, filled, H, W, y0, x0, Ho, Wo};
-    switch (C) {
-    case 1: return fill_launch<1>(ctx, f, p, scr);
-    case 2: return fill_launch<2>(ctx, f, p, scr);
-    case 3: return fill_launch<3>(ctx, f, p, scr);
-    default: return fill_launch<4>(ctx, f, p, scr);
-    }
+    return dfe_dispatch_1to4(C, [&](auto c) { return fill_launch<decltype(c)::value>(ctx, f, p, scr); });
 }
 
 }  // extern "C"

@@ -22,7 +22,7 @@
 //                 signed zeros included, so the first term starts the sum as the definition asks), then gain_c (N_c / S).
 #include <cmath>
 
-#include "dfe_internal.h"
+#include "dfe_field.h"
 
 #pragma clang fp contract(off)
 
@@ -38,8 +38,6 @@ struct UpFrame {
     float inv_s2;
     float gain[4];
 };
-
-__device__ __forceinline__ bool up_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }   // (false for NaN)
 
 // j0 = floor(((2 x + 1) nl - nh) / (2 nh)) for 0 <= x and 1 <= nl <= nh <= 32768: (2 x + 1) nl <= 65535 * 32768 < 2^31 while x < nh, and
 // the tile's columns beyond the frame (x < nh + 64) are never used, only kept from overflowing
@@ -80,14 +78,7 @@ template <int C, int Cg> __global__ __launch_bounds__(512) void guided_upsample_
             for (int c = 0; c < Cg; ++c) g[c] = 0.f;
             if (row_in && xx >= 0 && xx < f.Wl) {
                 const long long q = (long long)yy * f.Wl + xx;
-                const float wv = f.w ? f.w[q] : 1.f;
-                bool ok = up_finite(wv) && wv >= 1e-6f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    val[c] = f.v[c * HWl + q];
-                    ok = ok && up_finite(val[c]);
-                }
-                a = ok ? fminf(wv, 1.f) : 0.f;
+                a = dfe_sample_read<C>(f.v, f.w, HWl, q, val);
 #pragma unroll
                 for (int c = 0; c < Cg; ++c) g[c] = f.guide_lo[c * HWl + q];
             }
@@ -123,15 +114,7 @@ template <int C, int Cg> __global__ __launch_bounds__(512) void guided_upsample_
             const int cell = base + i * fw + j;
             const float tent = ty * txp[j * kUpTileW + lane];
             float ar = ap[cell];
-            if constexpr (Cg > 0) {
-                float d2 = 0.f;
-#pragma unroll
-                for (int c = 0; c < Cg; ++c) {
-                    const float d = gc[c] - gp[c * cells + cell], s = d * d;
-                    d2 = c == 0 ? s : d2 + s;
-                }
-                ar = ar * fmaxf(0.f, 1.f - d2 * f.inv_s2);   // (NaN -> 0; +Inf cannot occur: d2 inv_s2 is >= 0 or NaN)
-            }
+            if constexpr (Cg > 0) ar = ar * dfe_range_weight<Cg>(gc, gp, cells, cell, f.inv_s2);
             const float wt = ar * tent;
             // a sample that exists: a > 0, rr > 0, both tents > 0 and no underflow to 0.  One that does not adds -0, which changes no sum
             // (the values are read either way: a load under the test would wait for LDS once more per tap)
@@ -164,22 +147,6 @@ template <int C, int Cg> int upsample_launch(dfe_ctx *ctx, const UpFrame &f) {
     return DFE_OK;
 }
 
-template <int C> int upsample_launch_c(dfe_ctx *ctx, const UpFrame &f, int Cg) {
-    switch (Cg) {
-    case 0: return upsample_launch<C, 0>(ctx, f);
-    case 1: return upsample_launch<C, 1>(ctx, f);
-    case 2: return upsample_launch<C, 2>(ctx, f);
-    case 3: return upsample_launch<C, 3>(ctx, f);
-    default: return upsample_launch<C, 4>(ctx, f);
-    }
-}
-
-// [a, a + na) and [b, b + nb) floats share a byte
-bool up_overlap(const float *a, long long na, const float *b, long long nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + (uintptr_t)nb * sizeof(float) && b0 < a0 + (uintptr_t)na * sizeof(float);
-}
-
 }  // namespace
 
 extern "C" {
@@ -188,8 +155,8 @@ int dfe_guided_upsample_f32(dfe_ctx *ctx, const float *v, int C, int Hl, int Wl,
                             float sigma, int r, const float *gain, int Hh, int Wh, float *out, float *valid) {
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, v && out, DFE_E_ARG, "dfe_guided_upsample_f32: NULL tensor");
-    DFE_REQUIRE(ctx, C >= 1 && C <= 4, DFE_E_ARG, "dfe_guided_upsample_f32: C=%d must be 1 .. 4", C);
-    DFE_REQUIRE(ctx, Cg >= 0 && Cg <= 4, DFE_E_ARG, "dfe_guided_upsample_f32: Cg=%d must be 0 .. 4", Cg);
+    if (int rc = dfe_channels_check(ctx, "dfe_guided_upsample_f32", C)) return rc;
+    if (int rc = dfe_guide_channels_check(ctx, "dfe_guided_upsample_f32", Cg)) return rc;
     DFE_REQUIRE(ctx, Cg > 0 ? guide_hi && guide_lo : !guide_hi && !guide_lo, DFE_E_ARG,
                 "dfe_guided_upsample_f32: Cg=%d takes %s", Cg, Cg > 0 ? "the guide at both resolutions" : "no guide (both NULL)");
     DFE_REQUIRE(ctx, r >= 1 && r <= kUpMaxR, DFE_E_ARG, "dfe_guided_upsample_f32: r=%d must be 1 .. %d", r, kUpMaxR);
@@ -200,20 +167,19 @@ int dfe_guided_upsample_f32(dfe_ctx *ctx, const float *v, int C, int Hl, int Wl,
     for (int i = 0; i < 2; ++i) {   // neighbours are read: no output over an input
         const float *o = i ? valid : out;
         const long long no = i ? HWh : C * HWh;
-        DFE_REQUIRE(ctx, !up_overlap(o, no, v, C * HWl) && !up_overlap(o, no, w, HWl) && !up_overlap(o, no, guide_hi, Cg * HWh) && !up_overlap(o, no, guide_lo, Cg * HWl),
+        DFE_REQUIRE(ctx, !dfe_overlap(o, no, v, C * HWl) && !dfe_overlap(o, no, w, HWl) && !dfe_overlap(o, no, guide_hi, Cg * HWh) && !dfe_overlap(o, no, guide_lo, Cg * HWl),
                     DFE_E_ARG, "dfe_guided_upsample_f32: %s overlaps an input", i ? "valid" : "out");
     }
-    DFE_REQUIRE(ctx, !up_overlap(out, C * HWh, valid, HWh), DFE_E_ARG, "dfe_guided_upsample_f32: out overlaps valid");
+    DFE_REQUIRE(ctx, !dfe_overlap(out, C * HWh, valid, HWh), DFE_E_ARG, "dfe_guided_upsample_f32: out overlaps valid");
     const bool guided = Cg > 0 && sigma > 0.f;
     UpFrame f{v, w, guided ? guide_hi : nullptr, guided ? guide_lo : nullptr, out, valid, Hl, Wl, Hh, Wh, r, guided ? 1.0f / (sigma * sigma) : 0.f, {1.f, 1.f, 1.f, 1.f}};
     for (int c = 0; gain && c < C; ++c) f.gain[c] = gain[c];
     const int cg = guided ? Cg : 0;
-    switch (C) {
-    case 1: return upsample_launch_c<1>(ctx, f, cg);
-    case 2: return upsample_launch_c<2>(ctx, f, cg);
-    case 3: return upsample_launch_c<3>(ctx, f, cg);
-    default: return upsample_launch_c<4>(ctx, f, cg);
-    }
+    return dfe_dispatch_1to4(C, [&](auto c) {
+        constexpr int Cc = decltype(c)::value;
+        if (cg == 0) return upsample_launch<Cc, 0>(ctx, f);
+        return dfe_dispatch_1to4(cg, [&](auto g) { return upsample_launch<Cc, decltype(g)::value>(ctx, f); });
+    });
 }
 
 }  // extern "C"

@@ -16,7 +16,7 @@
 //                 it in LDS, a u16 in a table [k k][256] (25 KB at k = 7), and the bisection passes read it back; above that the table
 //                 (62 KB at k = 11, 115 KB at k = 15) leaves one workgroup a CU and making the weight again in every pass is faster
 //                 (measured: DESIGN section 4.27).  Both forms are the same device code around `Table`.
-#include "dfe_internal.h"
+#include "dfe_field.h"
 
 #pragma clang fp contract(off)
 
@@ -36,7 +36,6 @@ struct WmedFrame {
     float inv_s2;
 };
 
-__device__ __forceinline__ bool wmed_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }   // (false for NaN)
 // the order-preserving integer image of a float's bits (-0 below +0) and back
 __device__ __forceinline__ unsigned wmed_key(float v) {
     const unsigned u = __float_as_uint(v);
@@ -81,14 +80,7 @@ template <int C, int Cg, bool Table> __global__ __launch_bounds__(256) void wmed
             for (int c = 0; c < Cg; ++c) g[c] = 0.f;
             if (row_in && xx >= f.x0 && xx < f.x0 + f.Wo) {
                 const long long q = (long long)yy * f.W + xx;
-                const float wv = f.w ? f.w[q] : 1.f;
-                bool ok = wmed_finite(wv) && wv >= 1e-6f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    val[c] = f.v[c * HW + q];
-                    ok = ok && wmed_finite(val[c]);
-                }
-                a = ok ? fminf(wv, 1.f) : 0.f;
+                a = dfe_sample_read<C>(f.v, f.w, HW, q, val);
 #pragma unroll
                 for (int c = 0; c < Cg; ++c) g[c] = f.guide[c * HW + q];
             }
@@ -117,13 +109,7 @@ template <int C, int Cg, bool Table> __global__ __launch_bounds__(256) void wmed
                 return ap[cell];
             } else {
                 const float a = __uint_as_float(ap[cell]);
-                float d2 = 0.f;
-#pragma unroll
-                for (int c = 0; c < Cg; ++c) {
-                    const float d = gc[c] - gp[c * cells + cell], s = d * d;
-                    d2 = c == 0 ? s : d2 + s;
-                }
-                const float r = fmaxf(0.f, 1.f - d2 * f.inv_s2);   // (NaN -> 0; +Inf cannot occur: d2 inv_s2 is >= 0 or NaN)
+                const float r = dfe_range_weight<Cg>(gc, gp, cells, cell, f.inv_s2);
                 return a != 0.f ? wmed_weight(a * r) : 0u;
             }
         };
@@ -201,22 +187,6 @@ template <int C, int Cg> int wmedian_launch(dfe_ctx *ctx, const WmedFrame &f) {
     return DFE_OK;
 }
 
-template <int C> int wmedian_launch_c(dfe_ctx *ctx, const WmedFrame &f, int Cg) {
-    switch (Cg) {
-    case 0: return wmedian_launch<C, 0>(ctx, f);
-    case 1: return wmedian_launch<C, 1>(ctx, f);
-    case 2: return wmedian_launch<C, 2>(ctx, f);
-    case 3: return wmedian_launch<C, 3>(ctx, f);
-    default: return wmedian_launch<C, 4>(ctx, f);
-    }
-}
-
-// [a, a + na) and [b, b + nb) floats share a byte
-bool wmed_overlap(const float *a, long long na, const float *b, long long nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + (uintptr_t)nb * sizeof(float) && b0 < a0 + (uintptr_t)na * sizeof(float);
-}
-
 }  // namespace
 
 extern "C" {
@@ -225,29 +195,27 @@ int dfe_weighted_median_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, c
                             int Ho, int Wo, float *out, float *filtered) {
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, v && out, DFE_E_ARG, "dfe_weighted_median_f32: NULL tensor");
-    DFE_REQUIRE(ctx, C >= 1 && C <= 4, DFE_E_ARG, "dfe_weighted_median_f32: C=%d must be 1 .. 4", C);
-    DFE_REQUIRE(ctx, Cg >= 0 && Cg <= 4, DFE_E_ARG, "dfe_weighted_median_f32: Cg=%d must be 0 .. 4", Cg);
+    if (int rc = dfe_channels_check(ctx, "dfe_weighted_median_f32", C)) return rc;
+    if (int rc = dfe_guide_channels_check(ctx, "dfe_weighted_median_f32", Cg)) return rc;
     DFE_REQUIRE(ctx, k >= 1 && k <= kWmedMaxK && (k & 1), DFE_E_ARG, "dfe_weighted_median_f32: k=%d must be odd, 1 .. %d", k, kWmedMaxK);
-    DFE_REQUIRE(ctx, H > 0 && W > 0 && Ho > 0 && Wo > 0 && y0 >= 0 && x0 >= 0 && (long long)y0 + Ho <= H && (long long)x0 + Wo <= W, DFE_E_SHAPE,
-                "dfe_weighted_median_f32: region %dx%d at (%d, %d) does not lie inside the %dx%d frame", Ho, Wo, y0, x0, H, W);
+    if (int rc = dfe_region_check(ctx, "dfe_weighted_median_f32", H, W, y0, x0, Ho, Wo)) return rc;
     DFE_REQUIRE(ctx, dfe_cdiv(H, kWmedTileH) <= 65535, DFE_E_SHAPE, "dfe_weighted_median_f32: H=%d above %d rows", H, 65535 * kWmedTileH);
     const long long HW = (long long)H * W;
     const bool guided = guide && Cg > 0 && sigma > 0.f;
     for (int i = 0; i < 2; ++i) {   // neighbours are read: no output over an input
         const float *o = i ? filtered : out;
         const long long no = i ? HW : C * HW;
-        DFE_REQUIRE(ctx, !wmed_overlap(o, no, v, C * HW) && !wmed_overlap(o, no, w, HW) && !(Cg > 0 && wmed_overlap(o, no, guide, Cg * HW)), DFE_E_ARG,
+        DFE_REQUIRE(ctx, !dfe_overlap(o, no, v, C * HW) && !dfe_overlap(o, no, w, HW) && !(Cg > 0 && dfe_overlap(o, no, guide, Cg * HW)), DFE_E_ARG,
                     "dfe_weighted_median_f32: %s overlaps an input", i ? "filtered" : "out");
     }
-    DFE_REQUIRE(ctx, !wmed_overlap(out, C * HW, filtered, HW), DFE_E_ARG, "dfe_weighted_median_f32: out overlaps filtered");
+    DFE_REQUIRE(ctx, !dfe_overlap(out, C * HW, filtered, HW), DFE_E_ARG, "dfe_weighted_median_f32: out overlaps filtered");
     WmedFrame f{v, w, guided ? guide : nullptr, out, filtered, H, W, y0, x0, Ho, Wo, k, guided ? 1.0f / (sigma * sigma) : 0.f};
     const int cg = guided ? Cg : 0;
-    switch (C) {
-    case 1: return wmedian_launch_c<1>(ctx, f, cg);
-    case 2: return wmedian_launch_c<2>(ctx, f, cg);
-    case 3: return wmedian_launch_c<3>(ctx, f, cg);
-    default: return wmedian_launch_c<4>(ctx, f, cg);
-    }
+    return dfe_dispatch_1to4(C, [&](auto c) {
+        constexpr int Cc = decltype(c)::value;
+        if (cg == 0) return wmedian_launch<Cc, 0>(ctx, f);
+        return dfe_dispatch_1to4(cg, [&](auto g) { return wmedian_launch<Cc, decltype(g)::value>(ctx, f); });
+    });
 }
 
 }  // extern "C"

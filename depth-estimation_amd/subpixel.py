@@ -5,24 +5,14 @@
         consistency=tol: dfe_flow_depth_pair_fb_f32 / _u8, both directions and the forward-backward mask
         fill=True: the rejected pixels filled from the kept ones, flow_dense / filled / depth_dense
         median=k or (k, sigma): flow (or flow_dense) through the guided weighted median, flow_median / median_valid / depth_median
-    flowConsistency(fw, bw, tol, region=None)
-        dfe_flow_consistency_f32: the forward-backward mask and residual of any two flow fields
-    fillHoles(values, weight, region=None, levels=0)
-        dfe_fill_holes_f32: a dense field from the confident pixels of a sparse one (confidence-weighted push-pull)
-    weightedMedian(values, weight=None, guide=None, k=7, sigma=0.0, region=None)
-        dfe_weighted_median_f32: per channel the lower weighted median of the k x k window, weights from a confidence plane and a guide image
-    guidedUpsample(values, size=None, weight=None, guide=None, guide_lo=None, r=2, sigma=0.0, gain=None)
-        dfe_guided_upsample_f32: a field at a higher resolution, the mean of the low-resolution samples around each pixel weighted by a tent,
-        a confidence plane and the agreement of the frame at both resolutions (joint bilateral upsampling)
     refineFlowSubpixel(img1, img2, idx, hKer, wKer, hWin, wWin)
         dfe_flow_refine_subpixel_f32: the sub-pixel flow of an arg-min index map (dfe_ssd_flow_f32's 1-based idx)
 """
-import ctypes
-
 import torch
 
 from ._lib import lib
 from .context import get_ctx, ptr
+from .fields import fillHoles, weightedMedian
 
 
 def _frames(img1, img2, name):
@@ -129,146 +119,6 @@ def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False
         rc = fn(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, threshold, ptr(flow), ptr(scores), ptr(depth), ptr(conf))
     ctx.check(rc)
     return _with_fill({"flow": flow, "scores": scores, "depth": depth, "depth_conf": conf}, fill, median, a, k, hWin, wWin, fx, fy)
-
-
-def flowConsistency(fw, bw, tol, region=None):
-    """Forward-backward check of two float32 flow fields [2][H][W] (plane 0 = y, plane 1 = x; fw from frame 0 to frame 1, bw back) over
-    region = (y0, x0, Ho, Wo), the whole frame by default (include/dfe.h: dfe_flow_consistency_f32).  Returns (mask, err), float32 [H][W]:
-    mask 1 where |fw(p) + bw(p + fw(p))| <= tol, err that residual (+Inf where p + fw(p) leaves the region or a flow is not finite); both 0
-    outside the region."""
-    if not (fw.is_cuda and bw.is_cuda) or fw.dtype != torch.float32 or bw.dtype != torch.float32:
-        raise TypeError("flowConsistency: two float32 CUDA tensors expected")
-    if fw.dim() != 3 or fw.shape[0] != 2 or fw.shape != bw.shape or fw.device != bw.device:
-        raise ValueError("flowConsistency: two 2 x H x W flows of one shape expected, got %s and %s" % (tuple(fw.shape), tuple(bw.shape)))
-    fw, bw = fw.contiguous(), bw.contiguous()
-    _, H, W = fw.shape
-    y0, x0, Ho, Wo = (0, 0, H, W) if region is None else (int(v) for v in region)
-    mask = torch.empty((H, W), dtype=torch.float32, device=fw.device)
-    err = torch.empty_like(mask)
-    ctx = get_ctx(fw)
-    ctx.check(lib().dfe_flow_consistency_f32(ctx.handle, ptr(fw), ptr(bw), H, W, y0, x0, Ho, Wo, float(tol), ptr(mask), ptr(err)))
-    return mask, err
-
-
-def fillHoles(values, weight, region=None, levels=0):
-    """Dense field from the confident pixels of a sparse one (include/dfe.h: dfe_fill_holes_f32): values float32 [C][H][W], 1 <= C <= 4,
-    weight float32 [H][W] (>= 1 fully trusted, below 1e-6 or not finite a hole), region = (y0, x0, Ho, Wo), the whole frame by default;
-    levels = 0 fills from any distance, n > 0 from at most n pyramid levels (holes farther than about 2^n pixels from every valid pixel
-    stay unfilled).  Returns (out [C][H][W], filled [H][W]): pixels of weight >= 1 keep their bits, the others are blended with / replaced
-    by the confidence-weighted push-pull interpolation; filled is 1 where a value was found; both 0 outside the region."""
-    if values.dim() != 3 or not 1 <= values.shape[0] <= 4 or weight.dim() != 2 or tuple(weight.shape) != tuple(values.shape[1:]):
-        raise ValueError("fillHoles: values C x H x W (C = 1 .. 4) and weight H x W expected, got %s and %s" % (tuple(values.shape), tuple(weight.shape)))
-    if not (values.is_cuda and weight.is_cuda) or values.dtype != torch.float32 or weight.dtype != torch.float32:
-        raise TypeError("fillHoles: two float32 CUDA tensors expected")
-    if values.device != weight.device:
-        raise ValueError("fillHoles: values on %s, weight on %s" % (values.device, weight.device))
-    values, weight = values.contiguous(), weight.contiguous()
-    C, H, W = values.shape
-    y0, x0, Ho, Wo = (0, 0, H, W) if region is None else (int(v) for v in region)
-    out = torch.empty_like(values)
-    filled = torch.empty((H, W), dtype=torch.float32, device=values.device)
-    ctx = get_ctx(values)
-    ctx.check(lib().dfe_fill_holes_f32(ctx.handle, ptr(values), C, H, W, ptr(weight), y0, x0, Ho, Wo, int(levels), ptr(out), ptr(filled)))
-    return out, filled
-
-
-def weightedMedian(values, weight=None, guide=None, k=7, sigma=0.0, region=None):
-    """Guided weighted median (include/dfe.h: dfe_weighted_median_f32): values float32 [C][H][W], 1 <= C <= 4; weight float32 [H][W] or None
-    (all ones; below 1e-6 or not finite: the sample does not exist; above 1 counts as 1); guide float32 [Cg][H][W], Cg <= 4, or None;
-    k odd in 1 .. 15; sigma > 0 with a guide: a sample weighs max(0, 1 - |guide(p) - guide(q)|^2 / sigma^2) times its weight, else the
-    weight alone; region = (y0, x0, Ho, Wo), the whole frame by default.  Returns (out [C][H][W], filtered [H][W]): per channel the lower
-    weighted median of the k x k window clipped to the region (the bits of an input sample), filtered 1 where the window held a sample
-    of positive weight, else both 0; both 0 outside the region."""
-    if values.dim() != 3 or not 1 <= values.shape[0] <= 4:
-        raise ValueError("weightedMedian: values C x H x W (C = 1 .. 4) expected, got %s" % (tuple(values.shape),))
-    if weight is not None and (weight.dim() != 2 or tuple(weight.shape) != tuple(values.shape[1:])):
-        raise ValueError("weightedMedian: weight H x W expected, got %s for values %s" % (tuple(weight.shape), tuple(values.shape)))
-    if guide is not None and (guide.dim() != 3 or not 1 <= guide.shape[0] <= 4 or tuple(guide.shape[1:]) != tuple(values.shape[1:])):
-        raise ValueError("weightedMedian: guide Cg x H x W (Cg = 1 .. 4) expected, got %s for values %s" % (tuple(guide.shape), tuple(values.shape)))
-    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= 15 or k % 2 == 0:
-        raise ValueError("weightedMedian: k=%r must be odd, 1 .. 15" % (k,))
-    planes = [t for t in (values, weight, guide) if t is not None]
-    if not all(t.is_cuda and t.dtype == torch.float32 for t in planes):
-        raise TypeError("weightedMedian: float32 CUDA tensors expected")
-    if any(t.device != values.device for t in planes):
-        raise ValueError("weightedMedian: tensors on different devices")
-    values, weight, guide = (None if t is None else t.contiguous() for t in (values, weight, guide))
-    C, H, W = values.shape
-    y0, x0, Ho, Wo = (0, 0, H, W) if region is None else (int(v) for v in region)
-    out = torch.empty_like(values)
-    filtered = torch.empty((H, W), dtype=torch.float32, device=values.device)
-    ctx = get_ctx(values)
-    ctx.check(lib().dfe_weighted_median_f32(ctx.handle, ptr(values), C, H, W, None if weight is None else ptr(weight), None if guide is None else ptr(guide),
-                                            0 if guide is None else guide.shape[0], float(sigma), k, y0, x0, Ho, Wo, ptr(out), ptr(filtered)))
-    return out, filtered
-
-
-def guidedUpsample(values, size=None, weight=None, guide=None, guide_lo=None, r=2, sigma=0.0, gain=None):
-    """Guided upsampling (include/dfe.h: dfe_guided_upsample_f32): values float32 [C][Hl][Wl], 1 <= C <= 4, to size = (Hh, Wh) >= (Hl, Wl),
-    by default the guide's; weight float32 [Hl][Wl] or None (all ones; below 1e-6 or not finite: the sample does not exist; above 1 counts
-    as 1); guide float32 [Cg][Hh][Wh] or [Hh][Wh] (one channel), Cg <= 4, or None; guide_lo the same frame at [Cg][Hl][Wl], by default
-    imageScale(guide, Wl, Hl); r in 1 .. 4: 2r x 2r low-resolution samples around each pixel under a tent of radius r; sigma > 0 with a
-    guide: a sample also weighs max(0, 1 - |guide(p) - guide_lo(q)|^2 / sigma^2); gain None, C numbers, or "flow" for C = 2 planes (y, x):
-    (Hh / Hl, Wh / Wl), so that vectors stay in pixels of the grid they are on.  Returns (out [C][Hh][Wh], valid [Hh][Wh]): the weighted
-    mean times gain and 1 where a sample was found, else both 0."""
-    if values.dim() != 3 or not 1 <= values.shape[0] <= 4:
-        raise ValueError("guidedUpsample: values C x Hl x Wl (C = 1 .. 4) expected, got %s" % (tuple(values.shape),))
-    C, Hl, Wl = values.shape
-    if weight is not None and (weight.dim() != 2 or tuple(weight.shape) != (Hl, Wl)):
-        raise ValueError("guidedUpsample: weight Hl x Wl expected, got %s for values %s" % (tuple(weight.shape), tuple(values.shape)))
-    if guide is None and guide_lo is not None:
-        raise ValueError("guidedUpsample: guide_lo without a guide")
-    if guide is not None:
-        if guide.dim() == 2:
-            guide = guide.unsqueeze(0)
-        if guide.dim() != 3 or not 1 <= guide.shape[0] <= 4:
-            raise ValueError("guidedUpsample: guide Cg x Hh x Wh (Cg = 1 .. 4) or Hh x Wh expected, got %s" % (tuple(guide.shape),))
-        if size is None:
-            size = tuple(guide.shape[1:])
-    if size is None:
-        raise ValueError("guidedUpsample: without a guide the size = (Hh, Wh) must be given")
-    if not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(n, int) and not isinstance(n, bool) for n in size)):
-        raise ValueError("guidedUpsample: size=%r: (Hh, Wh) expected" % (size,))
-    Hh, Wh = size
-    if not (Hl <= Hh <= 32768 and Wl <= Wh <= 32768 and Hl >= 1 and Wl >= 1):
-        raise ValueError("guidedUpsample: size %d x %d for values %d x %d: every size 1 .. 32768, and none may shrink" % (Hh, Wh, Hl, Wl))
-    if guide is not None and tuple(guide.shape[1:]) != (Hh, Wh):
-        raise ValueError("guidedUpsample: guide %s for the size %d x %d" % (tuple(guide.shape), Hh, Wh))
-    if guide_lo is not None:
-        if guide_lo.dim() == 2:
-            guide_lo = guide_lo.unsqueeze(0)
-        if tuple(guide_lo.shape) != (guide.shape[0], Hl, Wl):
-            raise ValueError("guidedUpsample: guide_lo %d x %d x %d expected, got %s" % (guide.shape[0], Hl, Wl, tuple(guide_lo.shape)))
-    if not isinstance(r, int) or isinstance(r, bool) or not 1 <= r <= 4:
-        raise ValueError("guidedUpsample: r=%r must be 1 .. 4" % (r,))
-    if isinstance(gain, str):
-        if gain != "flow" or C != 2:
-            raise ValueError("guidedUpsample: gain=%r: \"flow\" is for C = 2 planes (y, x)" % (gain,))
-        gain = (Hh / Hl, Wh / Wl)
-    if gain is not None:
-        try:
-            gain = [float(g) for g in gain]
-        except TypeError:
-            raise ValueError("guidedUpsample: gain=%r: None, %d numbers or \"flow\" expected" % (gain, C)) from None
-        if len(gain) != C or not all(g == g and abs(g) != float("inf") for g in gain):
-            raise ValueError("guidedUpsample: gain=%r: %d finite numbers expected" % (gain, C))
-    planes = [t for t in (values, weight, guide, guide_lo) if t is not None]
-    if not all(t.is_cuda and t.dtype == torch.float32 for t in planes):
-        raise TypeError("guidedUpsample: float32 CUDA tensors expected")
-    if any(t.device != values.device for t in planes):
-        raise ValueError("guidedUpsample: tensors on different devices")
-    if guide is not None and guide_lo is None:
-        from .stream import imageScale
-
-        guide_lo = imageScale(guide, Wl, Hl)
-    values, weight, guide, guide_lo = (None if t is None else t.contiguous() for t in (values, weight, guide, guide_lo))
-    out = torch.empty((C, Hh, Wh), dtype=torch.float32, device=values.device)
-    valid = torch.empty((Hh, Wh), dtype=torch.float32, device=values.device)
-    ctx = get_ctx(values)
-    ctx.check(lib().dfe_guided_upsample_f32(ctx.handle, ptr(values), C, Hl, Wl, None if weight is None else ptr(weight), None if guide is None else ptr(guide),
-                                            None if guide_lo is None else ptr(guide_lo), 0 if guide is None else guide.shape[0], float(sigma), r,
-                                            None if gain is None else (ctypes.c_float * C)(*gain), Hh, Wh, ptr(out), ptr(valid)))
-    return out, valid
 
 
 def refineFlowSubpixel(img1, img2, idx, hKer, wKer, hWin, wWin):

@@ -4,7 +4,7 @@ does, up to its division).  Plus the scene the feature is for: a zoom field with
 (no test in this file)."""
 import numpy as np
 
-W_MIN = np.float32(1e-6)   # the fp32 constant of the definition
+from tests.field_rule import validity
 
 
 def fill_level_sizes(Ho, Wo, levels=0):
@@ -73,10 +73,9 @@ def fill_holes_ref(v, w, region=None, levels=0, dtype=np.float64):
     y0, x0, Ho, Wo = (0, 0, H, W) if region is None else region
     assert Ho > 0 and Wo > 0 and y0 >= 0 and x0 >= 0 and y0 + Ho <= H and x0 + Wo <= W and levels >= 0
     vr, wr = v[:, y0 : y0 + Ho, x0 : x0 + Wo], w[y0 : y0 + Ho, x0 : x0 + Wo]
-    with np.errstate(invalid="ignore"):
-        ok = np.isfinite(wr) & (wr >= W_MIN) & np.isfinite(vr).all(axis=0)
-    a0 = np.where(ok, np.minimum(np.where(ok, wr, 0), np.float32(1)), 0).astype(dtype)
-    v0 = np.where(ok, vr, 0).astype(dtype)        # what lies under a zero weight is never read
+    a32 = validity(vr, wr)
+    a0 = a32.astype(dtype)
+    v0 = np.where(a32 > 0, vr, 0).astype(dtype)   # what lies under a zero weight is never read
     sizes = fill_level_sizes(Ho, Wo, levels)
     L = len(sizes) - 1
     lev = [(v0, a0)]

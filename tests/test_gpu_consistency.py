@@ -132,7 +132,7 @@ def test_argument_errors_launch_nothing(dfe, cuda):
     for reg in ((0, 0, H + 1, W), (0, 0, H, W + 1), (-1, 0, H, W), (0, -1, H, W), (1, 0, H, W), (0, 1, H, W), (0, 0, 0, W), (0, 0, H, 0), (0, 0, H, -3),
                 (2**31 - 1, 0, 1, 1), (0, 0, 1, 2**31 - 1)):
         assert fn(ctx.handle, f, f, H, W, *reg, 1.0, mp, ep) == DFE_E_SHAPE, reg
-        assert b"region" in lib.dfe_last_error(ctx.handle)
+        assert lib.dfe_last_error(ctx.handle).startswith(b"dfe_flow_consistency_f32: region")
     assert fn(ctx.handle, f, f, 0, W, 0, 0, 1, 1, 1.0, mp, ep) == DFE_E_SHAPE
     for tol in (-1e-3, float("nan"), -float("inf")):
         assert fn(ctx.handle, f, f, H, W, 0, 0, H, W, tol, mp, ep) == DFE_E_ARG, tol

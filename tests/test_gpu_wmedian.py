@@ -10,6 +10,8 @@ Each case is one (shape, k, C) and runs Cg = 0, 1, 3; the other inputs rotate wi
     guide     random floats (a contracted multiply-add would change d2, and with it a weight), byte-valued, or floats with a planted NaN
     sigma     small enough that many r are 0, or large enough that none is
     filtered  given, and (Cg = 0) NULL in a second call."""
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -163,12 +165,12 @@ def test_argument_errors_launch_nothing(dfe, cuda):
     for reg in ((0, 0, H + 1, W), (0, 0, H, W + 1), (-1, 0, H, W), (0, -1, H, W), (1, 0, H, W), (0, 1, H, W), (0, 0, 0, W), (0, 0, H, 0), (0, 0, H, -3),
                 (2**31 - 1, 0, 1, 1), (0, 0, 1, 2**31 - 1)):
         assert call(y0=reg[0], x0=reg[1], Ho=reg[2], Wo=reg[3]) == DFE_E_SHAPE, reg
-        assert b"region" in lib.dfe_last_error(ctx.handle)
+        assert lib.dfe_last_error(ctx.handle).startswith(b"dfe_weighted_median_f32: region")
     assert call(H=0, Ho=1) == DFE_E_SHAPE
     # aliasing: out over v (wholly, and by its last plane only), over w, over the guide; filtered over an input; out over filtered
     for kw in [dict(out=vp), dict(out=plane(1)), dict(out=plane(3)), dict(out=plane(4)), dict(out=plane(7)), dict(out=plane(7), C=1), dict(filtered=plane(1)),
                dict(filtered=wp), dict(filtered=plane(6)), dict(filtered=op), dict(filtered=out2.data_ptr() + 4 * HW), dict(out=plane(9), v=plane(8), C=2)]:
-        assert call(**kw) == DFE_E_ARG and b"overlaps" in lib.dfe_last_error(ctx.handle), kw
+        assert call(**kw) == DFE_E_ARG and re.match(rb"dfe_weighted_median_f32: \w+ overlaps", lib.dfe_last_error(ctx.handle)), kw
     torch.cuda.synchronize()
     assert (buf[9:] == FILL).all() and (buf[:9] == 1).all() and (out2 == FILL).all() and (filt == FILL).all(), "a refused call wrote"
     # neighbours in one buffer are fine: out right behind the guide

@@ -7,16 +7,9 @@ and loops over the (2r)^2 taps in the stated order.  dtype=np.float64 runs the s
 quotients): what the float32 result is held against."""
 import numpy as np
 
+from tests.field_rule import validity
+
 F = np.float32
-
-
-def validity(v, w, dtype=F):
-    """a [Hl][Wl]: min(w, 1) where w is finite, w >= 1e-6f and every channel of v is finite, else 0; w None: ones"""
-    v = np.asarray(v, F)
-    w = np.ones(v.shape[1:], F) if w is None else np.asarray(w, F)
-    with np.errstate(invalid="ignore"):
-        ok = np.isfinite(w) & (w >= F(1e-6)) & np.isfinite(v).all(axis=0)
-        return np.where(ok, np.minimum(w, F(1)), F(0)).astype(dtype)
 
 
 def axis_taps(nl, nh, r, dtype=F):
@@ -46,7 +39,7 @@ def guided_upsample_ref(v, size, w=None, guide_hi=None, guide_lo=None, sigma=0.0
     C, Hl, Wl = v.shape
     Hh, Wh = size
     assert 1 <= C <= 4 and 1 <= r <= 4 and 1 <= Hl <= Hh <= 32768 and 1 <= Wl <= Wh <= 32768
-    a = validity(v, w, dtype)
+    a = validity(v, w).astype(dtype)
     with np.errstate(invalid="ignore"):
         vz = np.where(a[None] > 0, v, F(0)).astype(dtype)                   # what is under a = 0 is never read into arithmetic
     inv_s2 = inv_sigma2(guide_hi, sigma)

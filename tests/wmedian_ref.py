@@ -7,6 +7,8 @@ for bit.  Two forms: wmedian_pixel is the definition read literally for one pixe
 weighted_median_ref does all pixels of R at once on [k * k][Ho][Wo] stacks, and the CPU tests hold the two against each other."""
 import numpy as np
 
+from tests.field_rule import validity
+
 F = np.float32
 
 
@@ -14,15 +16,6 @@ def keys_of(v):
     """order-preserving integer image of the float32 bits (-0 below +0), as int64"""
     u = np.ascontiguousarray(v, F).view(np.uint32)
     return np.where(u >> 31 != 0, ~u, u | np.uint32(0x80000000)).astype(np.int64)
-
-
-def validity(v, w):
-    """a [H][W] float32: min(w, 1) where w is finite, w >= 1e-6f and every channel of v is finite, else 0; w None: ones"""
-    v = np.asarray(v, F)
-    w = np.ones(v.shape[1:], F) if w is None else np.asarray(w, F)
-    with np.errstate(invalid="ignore"):
-        ok = np.isfinite(w) & (w >= F(1e-6)) & np.isfinite(v).all(axis=0)
-        return np.where(ok, np.minimum(w, F(1)), F(0)).astype(F)
 
 
 def sample_weight(a_q, g_p, g_q, inv_s2):
