@@ -88,7 +88,8 @@ struct dfe_ctx {
                                       // own, so that dfe_flow_last_path can read it whatever has carved the arena since
     unsigned i8_seq = 0;              // number of the last int8 flow step
     int i8_slots = 0;                 // waves of the int8 sweep that the device holds at once (0: not asked yet)
-    bool i8_last = false;             // the last flow step launched the int8 kernel (and the gated float sweep behind it)
+    int flow_gated_lds = 0;           // dynamic LDS that the gated float sweep has been allowed on this ctx (set when a step needs more)
+    bool i8_last = false;            // the last flow step launched the int8 kernel (and the gated float sweep behind it)
     char err[512] = {0};
     // optional per-launch timing of the cost-volume kernel (dfe_profile_enable)
     bool profile = false;
@@ -374,9 +375,14 @@ size_t dfe_flow_i8_plan(int H, int W, DfeFlowI8Bufs *b);
 // one more int8 step on this ctx: the verdict ring (ctx->i8_verdict, allocated and cleared at first use) turns, b->verdict / verdict_next
 // are this step's word and the next one's
 DFE_HIDDEN int dfe_flow_i8_turn(dfe_ctx *ctx, DfeFlowI8Bufs *b);
-// pack + patch sums + the int8 sweep: records and fallback plane as the float sweep leaves them IF the frames are byte-valued (else
-// nothing: *b.verdict says so to the gated float sweep that the caller launches behind it).  Sets ctx->i8_last
-int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const DfeFlowI8Bufs &b, const CvFuseArgs &fa, const CvNovolArgs &nv);
+// pack + patch sums + the int8 sweep, whose waves finish their own pixels into `out` (pd: frame mode, the interior of the pair's planes)
+// IF the frames are byte-valued (else nothing: *b.verdict says so to the gated float sweep that the caller launches behind it, and to
+// dfe_flow_i8_tail).  out: one band, the whole pair.  Sets ctx->i8_last
+int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const DfeFlowI8Bufs &b, const CvNovolArgs &nv, const TailOut &out,
+                       const DfePairDepth *pd);
+// the launch behind the two sweeps, gated on the same word: the record finalize if the float sweep ran, else the frame's border (frame mode)
+int dfe_flow_i8_tail(dfe_ctx *ctx, int H, int W, const DfeFlowI8Bufs &b, const CvFuseArgs &fa, const CvNovolArgs &nv, double threshold, const TailOut &out,
+                     const DfePairDepth *pd);
 
 // ssd_cost_volume.hip -- the raw-frame cost-volume kernels, their planners and launchers; the host pipeline of the flow step that
 // calls them is flow_step.hip

@@ -22,8 +22,8 @@ static float float_at_or_below(double t) {
 // pixels whose lead cells hold fewer than M hits, the fallback plane; one launch for the whole pair (no bands: 112 B of scratch per
 // pixel instead of 4356), then the record finalize.  Returns DFE_OK with *done = false where the sweep does not apply.
 // Option "cv_i8" (default on): the frames are packed to bytes and checked on the device; the int8 matrix-core kernel (ssd_flow_i8.hip)
-// leaves the same records if every value is an integer in 0..255 and the gated float sweep, launched behind it, if not -- one of the
-// two returns at entry, and no host round trip decides.
+// writes the results of its pixels itself if every value is an integer in 0..255, and the gated float sweep, launched behind it, leaves
+// its records if not -- one of the two returns at entry, the gated tail launch finishes whichever ran, and no host round trip decides.
 static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, int hWin, int wWin, double thr, const TailOut &out,
                                const DfePairDepth *pd, bool *pd_done, bool *done) {
     constexpr int K = 7;
@@ -53,7 +53,7 @@ static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, i
     {
         DfeStageScope match(ctx, DFE_STAGE_MATCH);
         if (i8) {
-            rc = dfe_flow_i8_launch(ctx, I0, I1, H, W, ib, fa, nv);
+            rc = dfe_flow_i8_launch(ctx, I0, I1, H, W, ib, nv, out, pd);
             if (rc) return rc;
         }
         bool handled = false;
@@ -62,7 +62,8 @@ static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, i
     }
     *done = true;
     DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
-    rc = dfe_flow_finalize(ctx, fa, true, 1, nullptr, &nv, thr, Ho, hWin, wWin, out, pd);
+    // behind the int8 kernel, whose waves finish their own pixels: the gated tail (the record finalize if the float sweep ran, else the frame's border)
+    rc = i8 ? dfe_flow_i8_tail(ctx, H, W, ib, fa, nv, thr, out, pd) : dfe_flow_finalize(ctx, fa, true, 1, nullptr, &nv, thr, Ho, hWin, wWin, out, pd);
     if (pd && pd_done) *pd_done = true;
     return rc;
 }

@@ -2079,7 +2079,10 @@ static bool plan_flow_sweep_gated(const dfe_ctx *ctx, int H, int W, FlowSweepGat
 static int launch_flow_sweep_gated(dfe_ctx *ctx, const float *I0, const float *I1, const FlowSweepGatedPlan &pl, const CvFuseArgs &fa,
                                    const CvNovolArgs &nv, const unsigned *verdict) {
     auto kern = ssd_cv_rowimg_flow_gated_kernel<3, 7, 8>;
-    DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
+    if ((int)pl.lds_bytes > ctx->flow_gated_lds) {   // (once per context, not per step: the plan's LDS does not depend on the frame)
+        DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
+        ctx->flow_gated_lds = (int)pl.lds_bytes;
+    }
     {
         DfeProfScope prof(ctx, true);
         hipExtLaunchKernelGGL(kern, dim3(pl.nblk, 1), dim3(1024), pl.lds_bytes, ctx->stream, prof.a, prof.b, 0, I0, I1, pl.a, fa, nv, verdict);

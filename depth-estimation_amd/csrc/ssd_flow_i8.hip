@@ -32,16 +32,21 @@
 //
 // Items.  flow_i8_items.h splits the rows into two-row and one-row wave items from the number of waves the device holds at once.
 //
-// What it leaves is what the float sweep leaves (cv_records.h): tile-row records, and for a pixel with fewer than M lead cells above the
-// threshold its first M hits in index order in the fallback plane -- found by a second sweep of that strip row which ranks the hits of
-// a tile with ballots and stops when every flagged pixel has M.
+// Finalize.  At the end of an item the wave holds all that the finalize of its 16 x R pixels wants -- the minimum and its first index in
+// registers, the centre cost and the lead cells in its LDS image -- so it writes their results itself (i8_finalize: the rules of
+// dfe_finalize_rec_pixel, cv_records.h), lane group r the pixels of row r; no record goes to memory and comes back.  For a pixel with
+// fewer than M lead cells above the threshold the first M hits in index order come from a second sweep of that strip row, which ranks
+// the hits of a tile with ballots, leaves them in LDS and stops when every flagged pixel has M.
 //
 // The gate.  A block of the pack kernel that meets a value that is not an integer in 0..255 raises the step's verdict word; this kernel
 // returns at entry when it is set, the gated float sweep (ssd_cost_volume.hip) when it is clear.  A ctx has three such words, taken in
-// turn: the pack kernel of step i clears the word of step i + 1, so nothing has to be reset between calls.
+// turn: the pack kernel of step i clears the word of step i + 1, so nothing has to be reset between calls.  The tail launch behind the
+// two sweeps (flow_i8_tail_kernel) reads the same word: the record finalize of the float sweep's records if it is set; and in either
+// case the frame's border, which no sweep writes.
 #include "dfe_internal.h"
 #include "cv_records.h"
 #include "flow_i8_items.h"
+#include <algorithm>
 #include <climits>
 
 typedef int i8x16_t __attribute__((ext_vector_type(4)));   // 16 bytes of an MFMA operand / four i32 results
@@ -50,10 +55,10 @@ struct I8Args {
     const unsigned *pk0, *pk1;   // packed frames [H][Wp]
     const int *s0, *s1k;         // patch sums of frame 0 (plain) and frame 1 (as the key's addend) [H][Wp]
     const unsigned *verdict;     // != 0: the frames are not byte-valued
-    float *rec, *fb;             // records and fallback plane (cv_records.h)
+    TailOut o;                   // where the wave's pixels go (cv_records.h)
     float thr;
-    int M;
-    int Ho, Wo, Wp, nstrips, nrp, ncols;
+    int M, middle;
+    int Ho, Wo, Wp, nstrips, nrp;
     int n2, row0, nitems;        // flow_i8_items.h
 };
 
@@ -140,7 +145,8 @@ __global__ __launch_bounds__(256) void flow_i8_pack_kernel(const float *__restri
 constexpr int kCostPitch = 33;   // floats per pixel of the wave's lead-cell image in LDS (32 candidates, odd pitch)
 template <int R> struct I8Lds {
     float cost[R][16][kCostPitch];   // displacement row 0, tiles 0 and 1: cost[n][q]
-    float rec[R][2][DFE_REC];        // the strip's two tile-row records
+    float cen[R][16];                // the centre cell's cost of pixel n
+    float fbh[R][16][DFE_FB];        // a flagged pixel's hits of the fall-back sweep: M (value, 1-based index) pairs, zero-padded
 };
 
 template <int R, bool FB> struct I8Sweep {
@@ -249,10 +255,7 @@ template <int R, bool FB> struct I8Sweep {
                     if (T == 1 && S - r == 16) {   // the centre cell: dx = 16, q = 16 + n
 #pragma unroll
                         for (int i = 0; i < 4; ++i)
-                            if (4 * g + i == n) {
-                                const int x = x0 + n;
-                                lds->rec[r][(x >> 3) & 1][DFE_REC_CENTRE + (x & 7)] = (float)(sa[r] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[r][i]);
-                            }
+                            if (4 * g + i == n) lds->cen[r][n] = (float)(sa[r] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[r][i]);
                     }
                 } else {
                     // rank this tile's hits of every flagged pixel in candidate order: lane groups below mine, then my own earlier ones
@@ -336,7 +339,54 @@ __device__ __forceinline__ void i8_lds_fence() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// one wave item: strip `strip`, rows y0 .. y0 + R - 1, of which it stores those from ylo on
+// The finalize of the lane's pixel (x, y) from what the wave holds: dfe_finalize_rec_pixel's rules (cv_records.h) for the 33 x 33 window,
+// without the record in between.  d: 0-based first index of the minimum `best`; cen: the centre cell's cost; lead: the pixel's eight lead
+// cells, hm: bit k set = lead cell k lies above the threshold; fbh: the hits of the fall-back sweep, read where `flag` is set.
+template <int M>
+__device__ __forceinline__ void i8_finalize(const TailOut &o, int middle, int y, int x, float best, float cen, int d, const float *lead, unsigned hm,
+                                            bool flag, const float *fbh) {
+    const long long pg = o.p_off + (y * o.Wo + x);                       // (Ho Wo < 2^31 and H W < 2^31: flow_pipeline_novol)
+    const int fo = (y + o.row_off + o.pad_t) * o.pitch + x + o.pad_l;
+    int id0 = d;
+    if (middle > 0 && best == cen) id0 = middle - 1;
+    if (o.idx) o.idx[pg] = (long long)id0 + 1;
+    if (o.best) o.best[pg] = best;
+    const int fl = id0 / 33;
+    const float dyf = (float)(fl - 16), dxf = (float)(id0 - fl * 33 - 16);
+    if (o.fy) o.fy[fo] = dyf;
+    if (o.fx) o.fx[fo] = dxf;
+    if (o.frame_H && o.depth) pair_depth_px(y + o.pad_t, x + o.pad_l, dyf, dxf, o.mw, o.mh, o.infty, &o.depth[fo], &o.conf[fo]);
+    if (o.scores) {
+        float hv[M], hi[M];
+        if (flag) {   // rare: fewer than M lead cells pass; the fall-back sweep left the first M hits of the whole window, zero-padded
+#pragma unroll
+            for (int j = 0; j < M; ++j) { hv[j] = fbh[2 * j]; hi[j] = fbh[2 * j + 1]; }
+        } else {      // the first M set bits of hm (at least M are set)
+            unsigned h = hm;
+#pragma unroll
+            for (int j = 0; j < M; ++j) {
+                const int k = __builtin_ctz(h | 0x100u);
+                h &= h - 1u;
+                hv[j] = lead[k];
+                hi[j] = (float)(k + 1);
+            }
+        }
+        if (hv[0] > 0) {
+            if (M == 4) dfe_sort4(hv, hi); else dfe_sort8(hv, hi);
+            if (o.imaxs) o.imaxs[pg] = (long long)hi[0];
+#pragma unroll
+            for (int j = 1; j < M; ++j) hv[j] += hv[j - 1];
+            double acc = 0;
+#pragma unroll
+            for (int j = 0; j < M; ++j) acc += hv[j];
+            if (o.padded) o.scores[fo] = (float)acc; else o.scores[pg] = (float)acc;
+        } else if (o.padded) {
+            o.scores[fo] = 0.f;
+        }
+    }
+}
+
+// one wave item: strip `strip`, rows y0 .. y0 + R - 1, of which it writes those from ylo on
 template <int R> __device__ __forceinline__ void i8_item(const I8Args &a, I8Lds<R> *lds, int lane, int strip, int y0, int ylo) {
     const int x0 = strip * 16;
     const int n = lane & 15, g = lane >> 4;
@@ -348,16 +398,16 @@ template <int R> __device__ __forceinline__ void i8_item(const I8Args &a, I8Lds<
         sw.best[r][0] = sw.best[r][1] = INT_MIN;
         sw.sa[r] = a.s0[(y0 + r + 16) * a.Wp + x0 + n + 16];
     }
-    for (int i = lane; i < R * 2 * DFE_REC; i += 64) (&lds->rec[0][0][0])[i] = 0.f;
-    i8_lds_fence();
     sw.load_operands();
     sw.run();
     i8_lds_fence();
 
     const int x = x0 + n;
     const bool xin = x < a.Wo;
-    // the pixel's record slot: its tile column (the last one shifted inwards), position inside it
-    const int gi = x >> 3, xb = gi == a.ncols - 1 ? a.Wo - 8 : gi << 3, pos = x - xb, slot = gi & 1;
+    // lane group r finishes the pixels of row r: what it needs of that row
+    int fE = 0, fd = 0, fsa = 0;
+    unsigned fhm = 0;
+    bool fflag = false;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         // (cost, index) of the lane's two running keys, then of the pixel's four lane groups
@@ -378,52 +428,34 @@ template <int R> __device__ __forceinline__ void i8_item(const I8Args &a, I8Lds<
             kb = o > kb ? o : kb;
         }
         const int E = (int)(kb >> 12), d = 4095 - (int)(kb & 4095);
-        // lead cells: lane l takes cells 2 (l & 3), + 1 of pixel l >> 2
-        const int pn = lane >> 2, pk = (lane & 3) * 2;
-        const float l0 = lds->cost[r][pn][pn + pk], l1 = lds->cost[r][pn][pn + pk + 1];
+        // lead cells: lane l takes cells (l & 3), + 4 of pixel l >> 2, so a pixel's eight verdicts are two nibbles of the ballots
+        const int pn = lane >> 2, pk = lane & 3;
+        const float l0 = lds->cost[r][pn][pn + pk], l1 = lds->cost[r][pn][pn + pk + 4];
         const unsigned long long m0 = __builtin_amdgcn_ballot_w64(l0 > a.thr), m1 = __builtin_amdgcn_ballot_w64(l1 > a.thr);
-        const int nl = __builtin_popcount((unsigned)(m0 >> (4 * n)) & 15u) + __builtin_popcount((unsigned)(m1 >> (4 * n)) & 15u);
-        const bool flag = xin && nl < a.M;
-        {
-            const int px = x0 + pn, pgi = px >> 3, pxb = pgi == a.ncols - 1 ? a.Wo - 8 : pgi << 3;
-            if (px < a.Wo) {
-                float *lp = &lds->rec[r][pgi & 1][DFE_REC_LEAD + (px - pxb) * DFE_REC_NLEAD + pk];
-                lp[0] = l0;
-                lp[1] = l1;
-            }
-        }
-        if (g == 0 && xin) {
-            float *rb = lds->rec[r][slot];
-            rb[2 * pos] = (float)(sw.sa[r] - E);
-            rb[2 * pos + 1] = __int_as_float(d);
-            rb[DFE_REC_FLAG + pos] = flag ? 1.f : 0.f;
-        }
-        // the centre cost was left at (x & 7) of its slot: move it to the pixel's position (differs only in a shifted last tile column)
-        i8_lds_fence();
-        float cen = 0.f;
-        if (g == 0 && xin) cen = lds->rec[r][slot][DFE_REC_CENTRE + (x & 7)];
-        i8_lds_fence();
-        if (g == 0 && xin) lds->rec[r][slot][DFE_REC_CENTRE + pos] = cen;
-        i8_lds_fence();
+        const unsigned hm = ((unsigned)(m0 >> (4 * n)) & 15u) | (((unsigned)(m1 >> (4 * n)) & 15u) << 4);
+        const bool flag = xin && __builtin_popcount(hm) < a.M;
+        if (g == r) { fE = E; fd = d; fsa = sw.sa[r]; fhm = hm; fflag = flag; }
         const int y = y0 + r;
-        if (y >= ylo) {
-            for (int i = lane; i < 2 * DFE_REC; i += 64) {
-                const int sl = i >= DFE_REC ? 1 : 0, gg = 2 * strip + sl;
-                if (gg < a.ncols) a.rec[((long long)gg * a.Ho + y) * DFE_REC + (i - sl * DFE_REC)] = lds->rec[r][sl][i - sl * DFE_REC];
-            }
-            if (__builtin_amdgcn_ballot_w64(flag)) {   // rare: rank the hits of the flagged pixels over the whole window
-                I8Sweep<1, true> fs(a, lane, x0, y);
-                fs.sa[0] = sw.sa[r];
-                fs.cnt = 0;
-                fs.flagged = flag;
-                fs.fbp = a.fb + (((long long)gi * a.Ho + y) * 8 + pos) * DFE_FB;
-                fs.lds = nullptr;
-                fs.load_operands();
-                fs.run();
-                if (flag && g == 0)
-                    for (int j = 2 * min(fs.cnt, a.M); j < 2 * a.M; ++j) fs.fbp[j] = 0.f;
-            }
+        if (y >= ylo && __builtin_amdgcn_ballot_w64(flag)) {   // rare: rank the hits of the flagged pixels over the whole window
+            I8Sweep<1, true> fs(a, lane, x0, y);
+            fs.sa[0] = sw.sa[r];
+            fs.cnt = 0;
+            fs.flagged = flag;
+            fs.fbp = &lds->fbh[r][n][0];
+            fs.lds = nullptr;
+            fs.load_operands();
+            fs.run();
+            if (flag && g == 0)
+                for (int j = 2 * min(fs.cnt, a.M); j < 2 * a.M; ++j) fs.fbp[j] = 0.f;
         }
+    }
+    i8_lds_fence();   // (the hits of the fall-back sweep came from all four lane groups)
+    const int fr = R == 2 ? g & 1 : 0, y = y0 + fr;
+    if (g < R && xin && y >= ylo) {
+        const float best = (float)(fsa - fE), cen = lds->cen[fr][n];
+        const float *lead = &lds->cost[fr][n][n], *fbh = &lds->fbh[fr][n][0];
+        if (a.M == 4) i8_finalize<4>(a.o, a.middle, y, x, best, cen, fd, lead, fhm, fflag, fbh);
+        else i8_finalize<8>(a.o, a.middle, y, x, best, cen, fd, lead, fhm, fflag, fbh);
     }
 }
 
@@ -445,6 +477,52 @@ __global__ __launch_bounds__(kI8Waves * 64) __attribute__((amdgpu_waves_per_eu(3
     }
     const int row = a.row0 + (item - a.n2), strip = row / a.Ho, y = row - strip * a.Ho;
     i8_item<1>(a, reinterpret_cast<I8Lds<1> *>(&lds_all[wave]), lane, strip, y, y);
+}
+
+// ------------------------------------------------------------------------------------------
+// the tail launch behind the two sweeps.  In frame mode it writes the frame's border, which is the same whichever sweep ran -- flow and
+// scores 0, depth of a pixel at rest -- enumerated directly: top rows, bottom rows, then the two side bands of the rows between.  Then,
+// verdict set (the float sweep left records and the fallback plane): the record finalize of the interior, what flow_finalize_rec_kernel
+// (postops.hip) does; verdict clear (the int8 waves wrote their pixels themselves): nothing.  The border comes first so that the clear
+// case does not wait for the verdict word: its load is in flight while the border is written.
+// ------------------------------------------------------------------------------------------
+template <int M>
+__global__ __launch_bounds__(256) void flow_i8_tail_kernel(const unsigned *__restrict__ verdict, int Ho, int N, int hWin, int wWin, int middle, double threshold,
+                                                           TailOut o, const float *__restrict__ rec, int rec_rows, const float *__restrict__ fb) {
+    // (an atomic load is a vector load: a scalar one would share its counter with the kernel arguments' loads, which the border waits for)
+    const unsigned set = __hip_atomic_load(verdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int tid = blockIdx.x * blockDim.x + threadIdx.x, nthr = gridDim.x * blockDim.x;   // (at most 2^21 threads: dfe_grid1d)
+    if (o.frame_H) {
+        const int W = o.frame_W, nbot = o.frame_H - o.pad_t - Ho, side = W - o.Wo;
+        const int nfull = (o.pad_t + nbot) * W, nborder = nfull + Ho * side;   // (H W < 2^31)
+        for (int q = tid; q < nborder; q += nthr) {
+            int fi, fj;
+            if (q < nfull) {
+                fi = (int)((unsigned)q / (unsigned)W);
+                fj = q - fi * W;
+                if (fi >= o.pad_t) fi += Ho;
+            } else {
+                const int e = q - nfull, iy = (int)((unsigned)e / (unsigned)side), c = e - iy * side;
+                fi = o.pad_t + iy;
+                fj = c < o.pad_l ? c : c + o.Wo;
+            }
+            const long long f = (long long)fi * W + fj;
+            o.fy[f] = 0.f;
+            o.fx[f] = 0.f;
+            if (o.scores) o.scores[f] = 0.f;
+            if (o.depth) pair_depth_px(fi, fj, 0.f, 0.f, o.mw, o.mh, o.infty, &o.depth[f], &o.conf[f]);
+        }
+    }
+    if (!set) return;
+    const int P = Ho * o.Wo;   // (< 2^31: flow_pipeline_novol)
+    for (long long p = tid; p < P; p += nthr) {
+        if (o.frame_H) {
+            const int iy = (int)((unsigned)p / (unsigned)o.Wo), ix = (int)((unsigned)p - (unsigned)iy * (unsigned)o.Wo);
+            dfe_finalize_rec_pixel<M>(rec, rec_rows, nullptr, p, N, hWin, wWin, middle, threshold, o, iy + o.pad_t, ix + o.pad_l, iy, ix, fb);
+        } else {
+            dfe_finalize_rec_pixel<M>(rec, rec_rows, nullptr, p, N, hWin, wWin, middle, threshold, o, 0, 0, -1, -1, fb);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -475,15 +553,27 @@ int dfe_flow_i8_turn(dfe_ctx *ctx, DfeFlowI8Bufs *b) {
     return DFE_OK;
 }
 
-int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const DfeFlowI8Bufs &b, const CvFuseArgs &fa, const CvNovolArgs &nv) {
+// where a step's results go, with the frame-mode fields of a pair call (as dfe_flow_finalize, postops.hip, sets them)
+static TailOut i8_tailout(const TailOut &out, const DfePairDepth *pd) {
+    TailOut o = out;
+    if (pd) {
+        o.frame_H = pd->H; o.frame_W = pd->W; o.depth = pd->depth; o.conf = pd->conf;
+        o.mw = pd->cx; o.mh = pd->cy; o.infty = (float)((double)pd->W / 2);   // test_opticalflow.lua:148 geometry.wImg/2
+    }
+    return o;
+}
+
+int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const DfeFlowI8Bufs &b, const CvNovolArgs &nv, const TailOut &out,
+                       const DfePairDepth *pd) {
     const int Ho = H - DFE_FLOW_MARGIN, Wo = W - DFE_FLOW_MARGIN;
+    DFE_REQUIRE(ctx, out.Wo == Wo && out.row_off == 0 && out.p_off == 0, DFE_E_ARG, "int8 flow sweep: one band of the whole pair");
     hipLaunchKernelGGL(flow_i8_pack_kernel, dim3(dfe_cdiv(b.Wp, kPackW), dfe_cdiv(H, kPackH), 2), dim3(256), 0, ctx->stream, I0, I1, H, W, (long long)H * W,
                        b.Wp, b.pk0, b.pk1, b.s0, b.s1k, b.verdict, b.verdict_next);
     DFE_LAUNCH_CHECK(ctx);
     I8Args a;
     a.pk0 = b.pk0; a.pk1 = b.pk1; a.s0 = b.s0; a.s1k = b.s1k; a.verdict = b.verdict;
-    a.rec = fa.rec; a.fb = nv.fb; a.thr = nv.thr; a.M = nv.M;
-    a.Ho = Ho; a.Wo = Wo; a.Wp = b.Wp; a.nstrips = b.nstrips; a.ncols = dfe_cdiv(Wo, 8);
+    a.o = i8_tailout(out, pd); a.thr = nv.thr; a.M = nv.M; a.middle = dfe_window_middle(33, 33);
+    a.Ho = Ho; a.Wo = Wo; a.Wp = b.Wp; a.nstrips = b.nstrips;
     const int R = Ho >= 2 ? 2 : 1;
     if (!ctx->i8_slots) {   // waves resident at once: CUs x blocks of the kernel that a CU holds x waves of a block
         int nb = 0;
@@ -501,5 +591,22 @@ int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, in
     DFE_LAUNCH_CHECK(ctx);
     ctx->last_kernel = "ssd_flow_i8_kernel";
     ctx->i8_last = true;
+    return DFE_OK;
+}
+
+int dfe_flow_i8_tail(dfe_ctx *ctx, int H, int W, const DfeFlowI8Bufs &b, const CvFuseArgs &fa, const CvNovolArgs &nv, double threshold, const TailOut &out,
+                     const DfePairDepth *pd) {
+    const int Ho = H - DFE_FLOW_MARGIN;
+    const TailOut o = i8_tailout(out, pd);
+    // The record finalize's grid, a thread per pixel, up to eight blocks per CU (a grid-stride loop from 1080p on).  The byte path, where
+    // only the border's blocks find work, measured the same with two blocks and with one block per CU; the float path lost 2.7 and 6.6 us
+    // of its 223 at VGA with those (EXPERIMENTS, round 11)
+    const int grid = std::min(dfe_grid1d(pd ? (long long)pd->H * pd->W : (long long)Ho * o.Wo, 256), 8 * std::max(ctx->ncu, 1));
+    const int middle = dfe_window_middle(33, 33);
+    if (threshold < 0.2)   // extract_output.cpp:83-85
+        hipLaunchKernelGGL(flow_i8_tail_kernel<8>, dim3(grid), dim3(256), 0, ctx->stream, b.verdict, Ho, 33 * 33, 33, 33, middle, threshold, o, fa.rec, fa.rec_rows, nv.fb);
+    else
+        hipLaunchKernelGGL(flow_i8_tail_kernel<4>, dim3(grid), dim3(256), 0, ctx->stream, b.verdict, Ho, 33 * 33, 33, 33, middle, threshold, o, fa.rec, fa.rec_rows, nv.fb);
+    DFE_LAUNCH_CHECK(ctx);
     return DFE_OK;
 }
