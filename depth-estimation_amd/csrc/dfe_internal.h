@@ -376,13 +376,18 @@ size_t dfe_flow_i8_plan(int H, int W, DfeFlowI8Bufs *b);
 // are this step's word and the next one's
 DFE_HIDDEN int dfe_flow_i8_turn(dfe_ctx *ctx, DfeFlowI8Bufs *b);
 // pack + patch sums + the int8 sweep, whose waves finish their own pixels into `out` (pd: frame mode, the interior of the pair's planes)
-// IF the frames are byte-valued (else nothing: *b.verdict says so to the gated float sweep that the caller launches behind it, and to
-// dfe_flow_i8_tail).  out: one band, the whole pair.  Sets ctx->i8_last
+// IF the frames are byte-valued (else nothing: *b.verdict says so to the gated float sweep that the caller launches behind it,
+// cv_flow_sweep_gated).  out: one band, the whole pair.  Sets ctx->i8_last
 int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const DfeFlowI8Bufs &b, const CvNovolArgs &nv, const TailOut &out,
                        const DfePairDepth *pd);
-// the launch behind the two sweeps, gated on the same word: the record finalize if the float sweep ran, else the frame's border (frame mode)
-int dfe_flow_i8_tail(dfe_ctx *ctx, int H, int W, const DfeFlowI8Bufs &b, const CvFuseArgs &fa, const CvNovolArgs &nv, double threshold, const TailOut &out,
-                     const DfePairDepth *pd);
+// the same on frames of bytes (the byte entries at scale 1): the pack kernel reads the bytes as they are, raises no verdict and writes the
+// frame's border (pd: required), so these two launches are the whole step
+int dfe_flow_i8_launch_bytes(dfe_ctx *ctx, const unsigned char *I0, const unsigned char *I1, int H, int W, const DfeFlowI8Bufs &b, const CvNovolArgs &nv,
+                             const TailOut &out, const DfePairDepth *pd);
+// flow_step.hip -- dfe_flow_depth_pair_f32 on frames of bytes without the float copy, where the step may take int8 (*done; else nothing
+// has been launched and the caller converts and goes the float way)
+int dfe_flow_depth_pair_bytes(dfe_ctx *ctx, const unsigned char *I0, const unsigned char *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x,
+                              float foe_y, double extract_threshold, float scale, float *flow, float *scores, float *depth, float *depth_conf, bool *done);
 
 // ssd_cost_volume.hip -- the raw-frame cost-volume kernels, their planners and launchers; the host pipeline of the flow step that
 // calls them is flow_step.hip
@@ -395,11 +400,14 @@ int cv_frames_dispatch_f16(dfe_ctx *ctx, const float *I0, const float *I1, int C
 // the fused builds of this shape leave per-pixel RECORDS (fa.rec) instead of the three planes
 DFE_HIDDEN bool cv_writes_records(int C, int hWin, int wWin);
 // The volume-free flow sweep (3 channels, k = 7, 33 x 33): records into fa.rec, the fallback plane into nv.fb, no volume.
+// cv_flow_sweep: the plain sweep; the caller finalizes its records (dfe_flow_finalize).  *handled = false: no launch.
 // cv_flow_sweep_gated_ok: the gated form takes an H x W frame (a caller asks before it launches the int8 kernel in front of it).
-// verdict == NULL: the plain sweep; else its gated copy, which returns at entry unless *verdict != 0.  *handled = false: no launch
+// cv_flow_sweep_gated: the ONE launch behind the int8 kernel -- the frame's border (pd: frame mode) whatever *verdict says, and, unless
+// *verdict == 0, the sweep and the finalize of its records into `out`, each block its own
 DFE_HIDDEN bool cv_flow_sweep_gated_ok(const dfe_ctx *ctx, int H, int W);
-DFE_HIDDEN int cv_flow_sweep(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const CvFuseArgs &fa, const CvNovolArgs &nv,
-                             const unsigned *verdict, bool *handled);
+DFE_HIDDEN int cv_flow_sweep(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const CvFuseArgs &fa, const CvNovolArgs &nv, bool *handled);
+DFE_HIDDEN int cv_flow_sweep_gated(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const CvFuseArgs &fa, const CvNovolArgs &nv,
+                                   const unsigned *verdict, double threshold, const TailOut &out, const DfePairDepth *pd);
 // the volumes of n independent pairs (pyramid scales) in one launch where a common block shape exists (*handled)
 // prob (may be NULL): per pair, non-null = leave soft-min probabilities there instead of the costs in out[i] -- if the
 // launcher finds that worthwhile for the shape (*prob_used)

@@ -18,12 +18,29 @@ static float float_at_or_below(double t) {
     return f;
 }
 
-// The flow step without its cost volume (option "cv_novol", default on): the volume-free fused sweep leaves records and, for the rare
+// Which route a step takes, asked by every caller of the same two functions.
+// flow_step_novol_ok: the volume-free sweep takes the step (3 channels, k = 7, a window that leaves records, fp32 volume semantics, no
+// forced static tiles; the finalize's 32-bit pixel arithmetic).
+static bool flow_step_novol_ok(const dfe_ctx *ctx, int C, int H, int W, int kh, int kw, int hWin, int wWin, float f16_scale, const DfePairDepth *pd) {
+    const int Ho = H - kh + 1 - hWin + 1, Wo = W - kw + 1 - wWin + 1;
+    if (!(kh == kw && kh == 7 && cv_writes_records(C, hWin, wWin) && f16_scale == 0.f)) return false;
+    if (!(ctx->opt_bool(DFE_OPT_CV_NOVOL, true) && (ctx->cv_mode == 0 || ctx->cv_mode == 3) && (ctx->cv_tyq == 0 || ctx->cv_tyq == 1))) return false;   // (forced static tiles: the volume path)
+    return Wo >= 8 && (long long)Ho * Wo < (1ll << 31) && !(pd && (long long)pd->H * pd->W >= (1ll << 31));
+}
+// flow_step_i8_ok: ... and it may take int8 (option "cv_i8", the 33 x 33 window, the int8 kernel's and the gated sweep's plans); *ib: the sizes
+static bool flow_step_i8_ok(const dfe_ctx *ctx, int C, int H, int W, int kh, int kw, int hWin, int wWin, float f16_scale, const DfePairDepth *pd,
+                            DfeFlowI8Bufs *ib) {
+    return flow_step_novol_ok(ctx, C, H, W, kh, kw, hWin, wWin, f16_scale, pd) && hWin == 33 && wWin == 33 && ctx->opt_bool(DFE_OPT_CV_I8, true) &&
+           dfe_flow_i8_plan(H, W, ib) != 0 && cv_flow_sweep_gated_ok(ctx, H, W);
+}
+
+// The flow step without its cost volume (option "cv_novol", default on; the caller has asked flow_step_novol_ok): the volume-free fused
+// sweep leaves records and, for the rare
 // pixels whose lead cells hold fewer than M hits, the fallback plane; one launch for the whole pair (no bands: 112 B of scratch per
-// pixel instead of 4356), then the record finalize.  Returns DFE_OK with *done = false where the sweep does not apply.
+// pixel instead of 4356), then the record finalize.
 // Option "cv_i8" (default on): the frames are packed to bytes and checked on the device; the int8 matrix-core kernel (ssd_flow_i8.hip)
-// writes the results of its pixels itself if every value is an integer in 0..255, and the gated float sweep, launched behind it, leaves
-// its records if not -- one of the two returns at entry, the gated tail launch finishes whichever ran, and no host round trip decides.
+// writes the results of its pixels itself if every value is an integer in 0..255; the launch behind it writes the frame's border and, if
+// not, runs the float sweep and finalizes its records -- three launches, and no host round trip decides.
 static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, int hWin, int wWin, double thr, const TailOut &out,
                                const DfePairDepth *pd, bool *pd_done, bool *done) {
     constexpr int K = 7;
@@ -31,10 +48,9 @@ static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, i
     ctx->i8_last = false;
     const int Ho = H - K + 1 - hWin + 1, Wo = W - K + 1 - wWin + 1;
     const long long P = (long long)Ho * Wo;
-    if (Wo < 8 || P >= (1ll << 31) || (pd && (long long)pd->H * pd->W >= (1ll << 31))) return DFE_OK;   // (the finalize's 32-bit pixel arithmetic)
     const size_t nrec = (size_t)dfe_cdiv(Wo, 8) * Ho;   // tile-row records
     DfeFlowI8Bufs ib{};
-    const bool i8 = hWin == 33 && wWin == 33 && ctx->opt_bool(DFE_OPT_CV_I8, true) && dfe_flow_i8_plan(H, W, &ib) != 0 && cv_flow_sweep_gated_ok(ctx, H, W);
+    const bool i8 = flow_step_i8_ok(ctx, 3, H, W, K, K, hWin, wWin, 0.f, pd, &ib);
     int rc = i8 ? dfe_flow_i8_turn(ctx, &ib) : DFE_OK;
     if (rc) return rc;
     CvFuseArgs fa{};
@@ -55,15 +71,18 @@ static int flow_pipeline_novol(dfe_ctx *ctx, const float *I0, const float *I1, i
         if (i8) {
             rc = dfe_flow_i8_launch(ctx, I0, I1, H, W, ib, nv, out, pd);
             if (rc) return rc;
+        } else {
+            bool handled = false;
+            rc = cv_flow_sweep(ctx, I0, I1, H, W, fa, nv, &handled);
+            if (rc || !handled) return rc;
         }
-        bool handled = false;
-        rc = cv_flow_sweep(ctx, I0, I1, H, W, fa, nv, i8 ? ib.verdict : nullptr, &handled);
-        if (rc || !handled) return rc;
     }
     *done = true;
     DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
-    // behind the int8 kernel, whose waves finish their own pixels: the gated tail (the record finalize if the float sweep ran, else the frame's border)
-    rc = i8 ? dfe_flow_i8_tail(ctx, H, W, ib, fa, nv, thr, out, pd) : dfe_flow_finalize(ctx, fa, true, 1, nullptr, &nv, thr, Ho, hWin, wWin, out, pd);
+    // behind the int8 kernel, whose waves finish their own pixels: ONE launch, the frame's border and -- only if the frames were not
+    // byte-valued -- the float sweep with the finalize of its records.  (The stage timers then count that sweep under `extract`:
+    // include/dfe.h.)
+    rc = i8 ? cv_flow_sweep_gated(ctx, I0, I1, H, W, fa, nv, ib.verdict, thr, out, pd) : dfe_flow_finalize(ctx, fa, true, 1, nullptr, &nv, thr, Ho, hWin, wWin, out, pd);
     if (pd && pd_done) *pd_done = true;
     return rc;
 }
@@ -81,8 +100,8 @@ static int flow_pipeline(dfe_ctx *ctx, const float *I0, const float *I1, int C, 
     // rare fall-back reads the volume).
     // per-pixel records of the role-split row-image kernels (one whole 128-B line per pixel instead of entries in the three planes)
     const bool want_rec = kh == kw && kh == 7 && cv_writes_records(C, hWin, wWin);
-    if (want_rec && f16_scale == 0.f && ctx->opt_bool(DFE_OPT_CV_NOVOL, true) && (ctx->cv_mode == 0 || ctx->cv_mode == 3) &&
-        (ctx->cv_tyq == 0 || ctx->cv_tyq == 1)) {   // (forced static tiles: the volume path)
+    ctx->i8_last = false;   // (dfe_flow_last_path speaks of THIS step)
+    if (flow_step_novol_ok(ctx, C, H, W, kh, kw, hWin, wWin, f16_scale, pd)) {
         bool done = false;
         int rc = flow_pipeline_novol(ctx, I0, I1, H, W, hWin, wWin, thr, out, pd, pd_done, &done);
         if (rc || done) return rc;
@@ -204,6 +223,37 @@ int dfe_flow_depth_pair_f32(dfe_ctx *ctx, const float *I0, const float *I1, int 
                            flow, scores, depth, depth_conf);
 }
 
+}  // extern "C"
+
+// The byte entries at scale 1 (ingest.hip): pack-from-bytes, which also writes the frame's border, and the int8 sweep -- no float copy of
+// the frames, no gated launch, nothing to extract.  Whatever flow_depth_pair would refuse, and every step that may not take int8, is
+// left to the caller's float route (*done = false, nothing launched).
+int dfe_flow_depth_pair_bytes(dfe_ctx *ctx, const unsigned char *I0, const unsigned char *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x,
+                              float foe_y, double extract_threshold, float scale, float *flow, float *scores, float *depth, float *depth_conf, bool *done) {
+    *done = false;
+    if (scale != 1.0f || !I0 || !I1 || !flow || C <= 0 || k <= 0 || hWin <= 0 || wWin <= 0 || (depth == nullptr) != (depth_conf == nullptr)) return DFE_OK;
+    const int Ho = H - k + 1 - hWin + 1, Wo = W - k + 1 - wWin + 1;
+    if (Ho <= 0 || Wo <= 0) return DFE_OK;
+    const DfePairDepth pd{H, W, foe_x, foe_y, depth, depth_conf};
+    DfeFlowI8Bufs ib{};
+    if (!flow_step_i8_ok(ctx, C, H, W, k, k, hWin, wWin, 0.f, &pd, &ib)) return DFE_OK;
+    ctx->i8_last = false;
+    int rc = dfe_flow_i8_turn(ctx, &ib);
+    if (rc) return rc;
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { ib.take(c); });
+    if (rc) return rc;
+    CvNovolArgs nv{};
+    nv.thr = float_at_or_below(extract_threshold);
+    nv.M = extract_threshold < 0.2 ? 8 : 4;   // extract_output.cpp:83-85
+    const int pad_t = (H - Ho) / 2, pad_l = (W - Wo) / 2;
+    const long long HW = (long long)H * W;
+    DfeStageScope match(ctx, DFE_STAGE_MATCH);
+    rc = dfe_flow_i8_launch_bytes(ctx, I0, I1, H, W, ib, nv, dfe_tailout(nullptr, nullptr, flow, flow + HW, scores, nullptr, Wo, /*pitch*/ W, pad_t, pad_l, /*scores_padded*/ 1), &pd);
+    *done = rc == DFE_OK;
+    return rc;
+}
+
+extern "C" {
 int dfe_flow_depth_pair_f16(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x,
                             float foe_y, float scale, int64_t *idx, float *best, float *flow, float *depth, float *depth_conf) {
     DFE_ENTER(ctx);

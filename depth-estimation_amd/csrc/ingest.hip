@@ -167,8 +167,12 @@ int dfe_flow_depth_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, i
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, I0 && I1, DFE_E_ARG, "dfe_flow_depth_pair_u8: NULL frame");
     DFE_REQUIRE(ctx, C > 0 && H > 0 && W > 0 && scale > 0, DFE_E_ARG, "dfe_flow_depth_pair_u8: C=%d %dx%d scale=%g", C, H, W, (double)scale);
+    // scale 1 and a step that may take int8: the pack kernel reads the bytes as they are (flow_step.hip), no float copy
+    bool done = false;
+    int rc = dfe_flow_depth_pair_bytes(ctx, I0, I1, C, H, W, k, hWin, wWin, foe_x, foe_y, extract_threshold, scale, flow, scores, depth, depth_conf, &done);
+    if (rc || done) return rc;
     float *f0 = nullptr, *f1 = nullptr;
-    int rc = ingest_pair(ctx, I0, I1, (long long)C * H * W, scale, &f0, &f1);
+    rc = ingest_pair(ctx, I0, I1, (long long)C * H * W, scale, &f0, &f1);
     if (rc) return rc;
     return dfe_flow_depth_pair_f32(ctx, f0, f1, C, H, W, k, hWin, wWin, foe_x, foe_y, extract_threshold, flow, scores, depth, depth_conf);
 }
@@ -251,10 +255,18 @@ int dfe_flow_depth_pair_u8_slot(dfe_ctx *ctx, int slot, int C, int H, int W, int
                 "dfe_flow_depth_pair_u8_slot: %dx%dx%d bytes (scale %g), the slot holds %zu", C, H, W, (double)scale, ctx->slot_bytes);
     DFE_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->copied[slot], 0));
     const uint8_t *d0 = (const uint8_t *)ctx->slot[slot].p, *d1 = d0 + ctx->slot_bytes;
+    // scale 1 and a step that may take int8: the pack kernel reads the slot's bytes in place (flow_step.hip); it is their only reader
+    bool done = false;
+    int rc = dfe_flow_depth_pair_bytes(ctx, d0, d1, C, H, W, k, hWin, wWin, foe_x, foe_y, extract_threshold, scale, flow, scores, depth, depth_conf, &done);
+    if (rc) return rc;
+    if (done) {
+        DFE_HIP(ctx, hipEventRecord(ctx->consumed[slot], ctx->stream));
+        return DFE_OK;
+    }
     // both frames converted by ONE launch (the serial entry's two conversion launches are 12 us of a 245-us step)
     const long long n = (long long)C * H * W;
     float *f0 = nullptr, *f1 = nullptr;
-    int rc = ingest_frames(ctx, n, &f0, &f1);
+    rc = ingest_frames(ctx, n, &f0, &f1);
     if (rc) return rc;
     {
         DfeStageScope st(ctx, DFE_STAGE_LOAD);

@@ -2007,6 +2007,8 @@ int cv_frames_dispatch_fused(dfe_ctx *ctx, const float *I0, const float *I1, int
 // ------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------
+#include "flow_border.h"
+#include <cstddef>
 // H is the number of frame rows visible to this call (a row band of a taller frame when plane > H*W)
 int cv_frames_dispatch(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, long long plane, int kh,
                               int kw, int hWin, int wWin, float *out) {
@@ -2040,14 +2042,84 @@ int cv_frames_dispatch(dfe_ctx *ctx, const float *I0, const float *I1, int C, in
     return launch_cv_ref(ctx, a);
 }
 
-// The float sweep behind the int8 kernel (ssd_flow_i8.hip): ssd_cv_rowimg_flow_kernel's body behind a gate -- every block returns at entry
-// unless the pack kernel found a value that is not an integer in 0..255.  A kernel of its own, so that the ungated sweep's code is what it
-// was (its register allocation sits on the edge: tests/test_novol_guard_cpu.py).
+// The launch behind the int8 kernel (ssd_flow_i8.hip).  In frame mode it first writes the frame's border, which is the same whichever
+// sweep ran (flow_border.h); the step's verdict word is loaded in front of the border and tested behind it, so the clear case never waits
+// for the word.  Verdict clear (byte-valued frames: the int8 waves wrote their pixels themselves): that is all.  Verdict set (the pack
+// kernel met a value that is not an integer in 0..255): ssd_cv_rowimg_flow_kernel's body, and then every block finalizes the pixels of
+// its own tile-row records -- the records of its range [sweep_cut(b), sweep_cut(b + 1)) of the column-major (tile column, output row)
+// sequence: write_record and fallback_walk of rowimg_body store rows [by, by + prows) of column bx for each piece, pos .. pos + prows of
+// that range, and nothing else -- with flow_finalize_rec_kernel's code (dfe_finalize_rec_pixel).  Record (bx, by) owns pixels
+// 8 bx .. min(8 bx + 8, Wo) - 1 of row by (the last tile column is shifted inwards; the finalize reads its record at x - (Wo - 8)).
+// A kernel of its own, so that the ungated sweep's code is what it was (its register allocation sits on the edge:
+// tests/test_novol_guard_cpu.py).  For the same reason the finalize phase takes nothing from the kernel's arguments as the compiler
+// loads them, at entry, which would keep ~40 more scalars alive across the sweep: it reads the kernarg segment again behind the body,
+// through a pointer the compiler cannot see through (FlowGatedKernargs mirrors the parameter list).
+struct FlowTailArgs { TailOut o; double threshold; int middle; };
+struct FlowGatedKernargs {
+    const float *I0, *I1;
+    CvTiledArgs p;
+    CvFuseArgs fa;
+    CvNovolArgs nv;
+    const unsigned *verdict;
+    FlowTailArgs t;
+};
+// (a kernarg segment lays the parameters out one behind the other, each at its own alignment, as a struct lays out its members: with
+//  every member 8-byte aligned and a multiple of 8 bytes long there is no padding on either side to differ in)
+static_assert(alignof(CvTiledArgs) == 8 && alignof(CvFuseArgs) == 8 && alignof(CvNovolArgs) == 8 && alignof(FlowTailArgs) == 8, "kernarg mirror");
+static_assert(offsetof(FlowGatedKernargs, t) == 16 + sizeof(CvTiledArgs) + sizeof(CvFuseArgs) + sizeof(CvNovolArgs) + 8, "kernarg mirror");
+// (byte offset of the stash in dynamic LDS: behind the two images and the two record buffers of the 33 x 33 sweep, plan_flow_sweep_gated)
+constexpr int kFlowGatedStashOff = RowimgGeom<3, 7, 8>::sweep_stage_off + 2 * RowimgGeom<3, 7, 8>::stage_len33 * (int)sizeof(float) + 2 * DFE_REC * (int)sizeof(float);
+template <int M>
+__device__ __forceinline__ void flow_finalize_own_records(const FlowGatedKernargs *ka, int blk, int nblk) {
+    const TailOut o = ka->t.o;
+    const float *rec = ka->fa.rec, *fb = ka->nv.fb;
+    const int rec_rows = ka->fa.rec_rows, Ho = ka->p.Ho, middle = ka->t.middle;
+    const double threshold = ka->t.threshold;
+    const int ncols = (ka->p.Wo + 7) / 8;
+    const int pos = sweep_cut(blk, nblk, ncols, Ho, ka->p.sw_ovh, ka->p.sw_min);
+    const int pend = sweep_cut(blk + 1, nblk, ncols, Ho, ka->p.sw_ovh, ka->p.sw_min);
+    // a thread per pixel of a record, 128 records a trip
+    for (int q = pos + (int)(threadIdx.x >> 3); q < pend; q += 128) {
+        const int bx = (int)((unsigned)q / (unsigned)Ho), iy = q - bx * Ho, ix = 8 * bx + (int)(threadIdx.x & 7);
+        if (ix >= o.Wo) continue;
+        const long long p = (long long)iy * o.Wo + ix;   // (Ho Wo < 2^31: flow_pipeline_novol)
+        if (o.frame_H) dfe_finalize_rec_pixel<M>(rec, rec_rows, nullptr, p, 33 * 33, 33, 33, middle, threshold, o, iy + o.pad_t, ix + o.pad_l, iy, ix, fb);
+        else dfe_finalize_rec_pixel<M>(rec, rec_rows, nullptr, p, 33 * 33, 33, 33, middle, threshold, o, 0, 0, -1, -1, fb);
+    }
+}
 template <int C, int K, int TX>
 __global__ __launch_bounds__(1024) void ssd_cv_rowimg_flow_gated_kernel(const float *__restrict__ I0, const float *__restrict__ I1, CvTiledArgs p,
-                                                                        CvFuseArgs fa, CvNovolArgs nv, const unsigned *__restrict__ verdict) {
-    if (!*verdict) return;   // (block-uniform, in front of the first barrier)
-    rowimg_body<C, K, TX, true, true, true, 1089, false, true>(I0, I1, nullptr, p, fa, nv);
+                                                                        CvFuseArgs fa, CvNovolArgs nv, const unsigned *__restrict__ verdict, FlowTailArgs t) {
+    // (an atomic load is a vector load: a scalar one would share its counter with the kernel arguments' loads, which the border waits for)
+    const unsigned word = __hip_atomic_load(verdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    constexpr unsigned kBorderBlocks = 1u << 20;   // (the border's thread index stays inside 31 bits whatever option "sweep_blocks" asks for)
+    if (t.o.frame_H && blockIdx.x < kBorderBlocks)
+        dfe_flow_border(t.o, p.Ho, (int)(blockIdx.x * 1024u + threadIdx.x), (int)(min(gridDim.x, kBorderBlocks) * 1024u));
+    if (!__builtin_amdgcn_readfirstlane(word)) return;   // (block-uniform, in front of the first barrier)
+    // what the finalize phase needs to find its arguments and its range -- the kernarg segment's address, the block's number and the
+    // grid's size -- waits in four words of LDS behind the body's: kept in scalar registers across the sweep it is two v_readlane more
+    // in every row (tools/isa_regions.py)
+    unsigned *stash = reinterpret_cast<unsigned *>(dfe_smem + kFlowGatedStashOff);
+    {   // (every thread the same words; ordered in front of the reads below by the body's barriers, and by the one here)
+        const unsigned long long kp = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+        stash[0] = (unsigned)kp;
+        stash[1] = (unsigned)(kp >> 32);
+        stash[2] = blockIdx.x;
+        stash[3] = gridDim.x;
+    }
+    rowimg_body<C, K, TX, true, true, true, 1089, false, true>(I0, I1, nullptr, p, fa, nv);   // (a block with an empty range comes straight back)
+    // the block's records and fallback entries, stored by its waves 0 .. 8 (the records by inline assembly the compiler keeps no count
+    // of), are read below by all of its waves and by no other block: a fence at WORKGROUP scope.  (__threadfence(), device scope, is a
+    // write-back and an invalidate of the XCD's L2 on this chip -- buffer_wbl2 sc1, buffer_inv sc1 -- issued by every block while the
+    // others still sweep: the VGA float path measured 0.2914 ms with it against the parent's 0.2233, profiles/r12_float_path.txt.)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __syncthreads();
+    const unsigned k0 = __builtin_amdgcn_readfirstlane(stash[0]), k1 = __builtin_amdgcn_readfirstlane(stash[1]);
+    const int blk = __builtin_amdgcn_readfirstlane(stash[2]), nblk = __builtin_amdgcn_readfirstlane(stash[3]);
+    const FlowGatedKernargs *ka = (const FlowGatedKernargs *)(const __attribute__((address_space(4))) FlowGatedKernargs *)((unsigned long long)k1 << 32 | k0);
+    if (ka->nv.M == 8) flow_finalize_own_records<8>(ka, blk, nblk);
+    else flow_finalize_own_records<4>(ka, blk, nblk);
 }
 // its plan and launch: the geometry of launch_cv_rowimg_sweep's volume-free branch (3 channels, k = 7, 33 x 33; the tuning options included)
 struct FlowSweepGatedPlan { CvTiledArgs a; int nblk; size_t lds_bytes; };
@@ -2073,11 +2145,12 @@ static bool plan_flow_sweep_gated(const dfe_ctx *ctx, int H, int W, FlowSweepGat
     a.stage_off = G::sweep_stage_off;
     a.stage_len = G::stage_len33;
     a.chunk0 = 0;
-    pl->lds_bytes = a.stage_off + (size_t)2 * a.stage_len * sizeof(float) + 2 * DFE_REC * sizeof(float);
+    pl->lds_bytes = (size_t)kFlowGatedStashOff + 4 * sizeof(unsigned);   // (the sweep's LDS and the kernel's four words behind it)
+    static_assert(kFlowGatedStashOff == G::sweep_stage_off + 2 * G::stage_len33 * (int)sizeof(float) + 2 * DFE_REC * (int)sizeof(float), "behind the sweep's LDS");
     return pl->lds_bytes <= 160 * 1024;
 }
 static int launch_flow_sweep_gated(dfe_ctx *ctx, const float *I0, const float *I1, const FlowSweepGatedPlan &pl, const CvFuseArgs &fa,
-                                   const CvNovolArgs &nv, const unsigned *verdict) {
+                                   const CvNovolArgs &nv, const unsigned *verdict, const FlowTailArgs &t) {
     auto kern = ssd_cv_rowimg_flow_gated_kernel<3, 7, 8>;
     if ((int)pl.lds_bytes > ctx->flow_gated_lds) {   // (once per context, not per step: the plan's LDS does not depend on the frame)
         DFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes));
@@ -2085,7 +2158,7 @@ static int launch_flow_sweep_gated(dfe_ctx *ctx, const float *I0, const float *I
     }
     {
         DfeProfScope prof(ctx, true);
-        hipExtLaunchKernelGGL(kern, dim3(pl.nblk, 1), dim3(1024), pl.lds_bytes, ctx->stream, prof.a, prof.b, 0, I0, I1, pl.a, fa, nv, verdict);
+        hipExtLaunchKernelGGL(kern, dim3(pl.nblk, 1), dim3(1024), pl.lds_bytes, ctx->stream, prof.a, prof.b, 0, I0, I1, pl.a, fa, nv, verdict, t);
     }
     DFE_LAUNCH_CHECK(ctx);
     ctx->last_kernel = "ssd_cv_rowimg_kernel+fused_tail+novol";
@@ -2099,17 +2172,19 @@ bool cv_flow_sweep_gated_ok(const dfe_ctx *ctx, int H, int W) {
     FlowSweepGatedPlan pl;
     return plan_flow_sweep_gated(ctx, H, W, &pl);
 }
-int cv_flow_sweep(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const CvFuseArgs &fa, const CvNovolArgs &nv, const unsigned *verdict,
-                  bool *handled) {
-    *handled = false;
-    int rc = DFE_OK;
+int cv_flow_sweep_gated(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const CvFuseArgs &fa, const CvNovolArgs &nv, const unsigned *verdict,
+                        double threshold, const TailOut &out, const DfePairDepth *pd) {
     FlowSweepGatedPlan pl;
-    if (!verdict) {
-        rc = launch_cv_rowimg_sweep<3, 7, 8, true>(ctx, I0, I1, H, W, (long long)H * W, 33, 33, nullptr, &fa, handled, &nv);
-    } else if (plan_flow_sweep_gated(ctx, H, W, &pl)) {
-        rc = launch_flow_sweep_gated(ctx, I0, I1, pl, fa, nv, verdict);
-        *handled = rc == DFE_OK;
-    }
+    if (!plan_flow_sweep_gated(ctx, H, W, &pl)) return dfe_fail(ctx, DFE_E_UNSUPPORTED, "gated flow sweep: no plan for a %dx%d frame", H, W);
+    FlowTailArgs t;
+    t.o = dfe_tailout_frame(out, pd);
+    t.threshold = threshold;
+    t.middle = dfe_window_middle(33, 33);
+    return launch_flow_sweep_gated(ctx, I0, I1, pl, fa, nv, verdict, t);
+}
+int cv_flow_sweep(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const CvFuseArgs &fa, const CvNovolArgs &nv, bool *handled) {
+    *handled = false;
+    int rc = launch_cv_rowimg_sweep<3, 7, 8, true>(ctx, I0, I1, H, W, (long long)H * W, 33, 33, nullptr, &fa, handled, &nv);
 #if DFE_TL
     // (tuning build: the stamps that blocks 0 and 1 left at the start of the fallback plane, in front of the finalize that reads the plane)
     const size_t fb_bytes = (size_t)dfe_cdiv(W - DFE_FLOW_MARGIN, 8) * (H - DFE_FLOW_MARGIN) * 8 * DFE_FB * sizeof(float);

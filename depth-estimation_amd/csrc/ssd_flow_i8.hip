@@ -39,13 +39,13 @@
 // the hits of a tile with ballots, leaves them in LDS and stops when every flagged pixel has M.
 //
 // The gate.  A block of the pack kernel that meets a value that is not an integer in 0..255 raises the step's verdict word; this kernel
-// returns at entry when it is set, the gated float sweep (ssd_cost_volume.hip) when it is clear.  A ctx has three such words, taken in
-// turn: the pack kernel of step i clears the word of step i + 1, so nothing has to be reset between calls.  The tail launch behind the
-// two sweeps (flow_i8_tail_kernel) reads the same word: the record finalize of the float sweep's records if it is set; and in either
-// case the frame's border, which no sweep writes.
+// returns at entry when it is set.  A ctx has three such words, taken in turn: the pack kernel of step i clears the word of step i + 1, so
+// nothing has to be reset between calls.  ONE launch follows (ssd_cv_rowimg_flow_gated_kernel, ssd_cost_volume.hip): it writes the
+// frame's border, which no sweep writes, and reads the same word -- clear: nothing more; set: the float sweep and the finalize of its records.
 #include "dfe_internal.h"
 #include "cv_records.h"
 #include "flow_i8_items.h"
+#include "flow_border.h"
 #include <algorithm>
 #include <climits>
 
@@ -72,25 +72,40 @@ __device__ __forceinline__ int i8_max3(int a, int b, int c) {
 }
 
 // ------------------------------------------------------------------------------------------
-// pack: float planes -> (c0 - 128, c1 - 128, c2 - 128, 0) per pixel and the 7 x 7 x 3 sums of squares, one 32 x 32 tile per block (read with
-// its 6-pixel halo); a block that meets a value that is not an integer in 0..255 raises the call's verdict word
+// pack: planes of floats or of bytes -> (c0 - 128, c1 - 128, c2 - 128, 0) per pixel and the 7 x 7 x 3 sums of squares, one 32 x 32 tile per
+// block (read with its 6-pixel halo).  Float planes: a block that meets a value that is not an integer in 0..255 raises the call's
+// verdict word.  Byte planes (the byte entries at scale 1: any address, any W) raise nothing; with BORDER the z = 0 blocks also write the
+// frame's border (flow_border.h), so that the int8 sweep is the only launch behind this one.  Both forms clear the NEXT call's word.
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool i8_byte(float v, unsigned *b) {
     const bool ok = v >= 0.f && v <= 255.f && v == truncf(v);   // (NaN fails every comparison; -0.0 is 0)
     *b = ok ? (unsigned)((int)v - 128) & 255u : 0u;
     return ok;
 }
+__device__ __forceinline__ bool i8_byte(unsigned char v, unsigned *b) {
+    *b = (unsigned)((int)v - 128) & 255u;
+    return true;
+}
 __device__ __forceinline__ int i8_sq(unsigned p) {
     const int a = (int)(p << 24) >> 24, b = (int)(p << 16) >> 24, c = (int)(p << 8) >> 24;
     return a * a + b * b + c * c;
 }
+template <bool BORDER> struct I8PackBorder {};
+template <> struct I8PackBorder<true> { TailOut o; int Ho; };
 constexpr int kPackW = 32, kPackH = 32, kPackLW = kPackW + 6, kPackLH = kPackH + 6;
-__global__ __launch_bounds__(256) void flow_i8_pack_kernel(const float *__restrict__ I0, const float *__restrict__ I1, int H, int W, long long plane, int Wp,
+template <typename T, bool BORDER>
+__global__ __launch_bounds__(256) void flow_i8_pack_kernel(const T *__restrict__ I0, const T *__restrict__ I1, int H, int W, long long plane, int Wp,
                                                            unsigned *__restrict__ pk0, unsigned *__restrict__ pk1, int *__restrict__ s0, int *__restrict__ s1k,
-                                                           unsigned *__restrict__ verdict, unsigned *__restrict__ verdict_next) {
+                                                           unsigned *__restrict__ verdict, unsigned *__restrict__ verdict_next, I8PackBorder<BORDER> bd) {
+    constexpr bool BYTES = sizeof(T) == 1;
+    static_assert(BYTES || !BORDER, "the border rides on the byte form");
     __shared__ int sq[kPackLH][kPackLW + 1];
     __shared__ int hs[kPackLH][kPackW];
-    const float *I = blockIdx.z ? I1 : I0;
+    if constexpr (BORDER) {   // (at most 2^21 blocks of a frame with H W < 2^31: the thread index stays inside 31 bits)
+        if (blockIdx.z == 0)
+            dfe_flow_border(bd.o, bd.Ho, (int)((blockIdx.y * gridDim.x + blockIdx.x) * 256u + threadIdx.x), (int)(gridDim.x * gridDim.y * 256u));
+    }
+    const T *I = blockIdx.z ? I1 : I0;
     unsigned *pk = blockIdx.z ? pk1 : pk0;
     const int tx0 = blockIdx.x * kPackW, ty0 = blockIdx.y * kPackH;
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) *verdict_next = 0u;   // (the NEXT call's word: no reset launch)
@@ -98,12 +113,12 @@ __global__ __launch_bounds__(256) void flow_i8_pack_kernel(const float *__restri
     // every load of the thread is issued before the first is used: one memory latency, not one per trip.  The addresses are clamped into the
     // frame, so no load hangs on a branch; what lies outside the tile's image or outside the frame is dropped afterwards
     constexpr int NT = (kPackLH * kPackLW + 255) / 256;
-    float v[NT][3];
+    T v[NT][3];
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
         const int e = threadIdx.x + 256 * j;
         const int ly = e / kPackLW, lx = e - ly * kPackLW;
-        const float *s = I + (long long)min(ty0 + ly, H - 1) * W + min(tx0 + lx, W - 1);
+        const T *s = I + (long long)min(ty0 + ly, H - 1) * W + min(tx0 + lx, W - 1);
         v[j][0] = s[0];
         v[j][1] = s[plane];
         v[j][2] = s[2 * plane];
@@ -121,8 +136,12 @@ __global__ __launch_bounds__(256) void flow_i8_pack_kernel(const float *__restri
         if (ly < kPackH && lx < kPackW && gy < H && gx < Wp) pk[(long long)gy * Wp + gx] = p;
         if (ly < kPackLH) sq[ly][lx] = i8_sq(p);
     }
-    const int any = __syncthreads_or(bad ? 1 : 0);
-    if (any && threadIdx.x == 0) atomicOr(verdict, 1u);
+    if constexpr (BYTES) {
+        __syncthreads();
+    } else {
+        const int any = __syncthreads_or(bad ? 1 : 0);
+        if (any && threadIdx.x == 0) atomicOr(verdict, 1u);
+    }
     for (int e = threadIdx.x; e < kPackLH * kPackW; e += 256) {
         const int ly = e / kPackW, lx = e - ly * kPackW;
         hs[ly][lx] = sq[ly][lx] + sq[ly][lx + 1] + sq[ly][lx + 2] + sq[ly][lx + 3] + sq[ly][lx + 4] + sq[ly][lx + 5] + sq[ly][lx + 6];
@@ -480,52 +499,6 @@ __global__ __launch_bounds__(kI8Waves * 64) __attribute__((amdgpu_waves_per_eu(3
 }
 
 // ------------------------------------------------------------------------------------------
-// the tail launch behind the two sweeps.  In frame mode it writes the frame's border, which is the same whichever sweep ran -- flow and
-// scores 0, depth of a pixel at rest -- enumerated directly: top rows, bottom rows, then the two side bands of the rows between.  Then,
-// verdict set (the float sweep left records and the fallback plane): the record finalize of the interior, what flow_finalize_rec_kernel
-// (postops.hip) does; verdict clear (the int8 waves wrote their pixels themselves): nothing.  The border comes first so that the clear
-// case does not wait for the verdict word: its load is in flight while the border is written.
-// ------------------------------------------------------------------------------------------
-template <int M>
-__global__ __launch_bounds__(256) void flow_i8_tail_kernel(const unsigned *__restrict__ verdict, int Ho, int N, int hWin, int wWin, int middle, double threshold,
-                                                           TailOut o, const float *__restrict__ rec, int rec_rows, const float *__restrict__ fb) {
-    // (an atomic load is a vector load: a scalar one would share its counter with the kernel arguments' loads, which the border waits for)
-    const unsigned set = __hip_atomic_load(verdict, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int tid = blockIdx.x * blockDim.x + threadIdx.x, nthr = gridDim.x * blockDim.x;   // (at most 2^21 threads: dfe_grid1d)
-    if (o.frame_H) {
-        const int W = o.frame_W, nbot = o.frame_H - o.pad_t - Ho, side = W - o.Wo;
-        const int nfull = (o.pad_t + nbot) * W, nborder = nfull + Ho * side;   // (H W < 2^31)
-        for (int q = tid; q < nborder; q += nthr) {
-            int fi, fj;
-            if (q < nfull) {
-                fi = (int)((unsigned)q / (unsigned)W);
-                fj = q - fi * W;
-                if (fi >= o.pad_t) fi += Ho;
-            } else {
-                const int e = q - nfull, iy = (int)((unsigned)e / (unsigned)side), c = e - iy * side;
-                fi = o.pad_t + iy;
-                fj = c < o.pad_l ? c : c + o.Wo;
-            }
-            const long long f = (long long)fi * W + fj;
-            o.fy[f] = 0.f;
-            o.fx[f] = 0.f;
-            if (o.scores) o.scores[f] = 0.f;
-            if (o.depth) pair_depth_px(fi, fj, 0.f, 0.f, o.mw, o.mh, o.infty, &o.depth[f], &o.conf[f]);
-        }
-    }
-    if (!set) return;
-    const int P = Ho * o.Wo;   // (< 2^31: flow_pipeline_novol)
-    for (long long p = tid; p < P; p += nthr) {
-        if (o.frame_H) {
-            const int iy = (int)((unsigned)p / (unsigned)o.Wo), ix = (int)((unsigned)p - (unsigned)iy * (unsigned)o.Wo);
-            dfe_finalize_rec_pixel<M>(rec, rec_rows, nullptr, p, N, hWin, wWin, middle, threshold, o, iy + o.pad_t, ix + o.pad_l, iy, ix, fb);
-        } else {
-            dfe_finalize_rec_pixel<M>(rec, rec_rows, nullptr, p, N, hWin, wWin, middle, threshold, o, 0, 0, -1, -1, fb);
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
 // host
 // ------------------------------------------------------------------------------------------
 size_t dfe_flow_i8_plan(int H, int W, DfeFlowI8Bufs *b) {
@@ -553,26 +526,29 @@ int dfe_flow_i8_turn(dfe_ctx *ctx, DfeFlowI8Bufs *b) {
     return DFE_OK;
 }
 
-// where a step's results go, with the frame-mode fields of a pair call (as dfe_flow_finalize, postops.hip, sets them)
-static TailOut i8_tailout(const TailOut &out, const DfePairDepth *pd) {
-    TailOut o = out;
-    if (pd) {
-        o.frame_H = pd->H; o.frame_W = pd->W; o.depth = pd->depth; o.conf = pd->conf;
-        o.mw = pd->cx; o.mh = pd->cy; o.infty = (float)((double)pd->W / 2);   // test_opticalflow.lua:148 geometry.wImg/2
-    }
-    return o;
-}
-
-int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const DfeFlowI8Bufs &b, const CvNovolArgs &nv, const TailOut &out,
-                       const DfePairDepth *pd) {
+// pack (T = float: the gate; T = unsigned char: no gate, and the frame's border) + the int8 sweep
+template <typename T>
+static int i8_launch(dfe_ctx *ctx, const T *I0, const T *I1, int H, int W, const DfeFlowI8Bufs &b, const CvNovolArgs &nv, const TailOut &out,
+                     const DfePairDepth *pd) {
+    constexpr bool BYTES = sizeof(T) == 1;
     const int Ho = H - DFE_FLOW_MARGIN, Wo = W - DFE_FLOW_MARGIN;
     DFE_REQUIRE(ctx, out.Wo == Wo && out.row_off == 0 && out.p_off == 0, DFE_E_ARG, "int8 flow sweep: one band of the whole pair");
-    hipLaunchKernelGGL(flow_i8_pack_kernel, dim3(dfe_cdiv(b.Wp, kPackW), dfe_cdiv(H, kPackH), 2), dim3(256), 0, ctx->stream, I0, I1, H, W, (long long)H * W,
-                       b.Wp, b.pk0, b.pk1, b.s0, b.s1k, b.verdict, b.verdict_next);
+    const dim3 pgrid(dfe_cdiv(b.Wp, kPackW), dfe_cdiv(H, kPackH), 2);
+    if constexpr (BYTES) {
+        DFE_REQUIRE(ctx, pd != nullptr, DFE_E_ARG, "int8 flow sweep on bytes: a pair step");
+        I8PackBorder<true> bd;
+        bd.o = dfe_tailout_frame(out, pd);
+        bd.Ho = Ho;
+        hipLaunchKernelGGL((flow_i8_pack_kernel<T, true>), pgrid, dim3(256), 0, ctx->stream, I0, I1, H, W, (long long)H * W, b.Wp, b.pk0, b.pk1, b.s0, b.s1k,
+                           b.verdict, b.verdict_next, bd);
+    } else {
+        hipLaunchKernelGGL((flow_i8_pack_kernel<T, false>), pgrid, dim3(256), 0, ctx->stream, I0, I1, H, W, (long long)H * W, b.Wp, b.pk0, b.pk1, b.s0, b.s1k,
+                           b.verdict, b.verdict_next, I8PackBorder<false>{});
+    }
     DFE_LAUNCH_CHECK(ctx);
     I8Args a;
     a.pk0 = b.pk0; a.pk1 = b.pk1; a.s0 = b.s0; a.s1k = b.s1k; a.verdict = b.verdict;
-    a.o = i8_tailout(out, pd); a.thr = nv.thr; a.M = nv.M; a.middle = dfe_window_middle(33, 33);
+    a.o = dfe_tailout_frame(out, pd); a.thr = nv.thr; a.M = nv.M; a.middle = dfe_window_middle(33, 33);
     a.Ho = Ho; a.Wo = Wo; a.Wp = b.Wp; a.nstrips = b.nstrips;
     const int R = Ho >= 2 ? 2 : 1;
     if (!ctx->i8_slots) {   // waves resident at once: CUs x blocks of the kernel that a CU holds x waves of a block
@@ -594,19 +570,11 @@ int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, in
     return DFE_OK;
 }
 
-int dfe_flow_i8_tail(dfe_ctx *ctx, int H, int W, const DfeFlowI8Bufs &b, const CvFuseArgs &fa, const CvNovolArgs &nv, double threshold, const TailOut &out,
-                     const DfePairDepth *pd) {
-    const int Ho = H - DFE_FLOW_MARGIN;
-    const TailOut o = i8_tailout(out, pd);
-    // The record finalize's grid, a thread per pixel, up to eight blocks per CU (a grid-stride loop from 1080p on).  The byte path, where
-    // only the border's blocks find work, measured the same with two blocks and with one block per CU; the float path lost 2.7 and 6.6 us
-    // of its 223 at VGA with those (EXPERIMENTS, round 11)
-    const int grid = std::min(dfe_grid1d(pd ? (long long)pd->H * pd->W : (long long)Ho * o.Wo, 256), 8 * std::max(ctx->ncu, 1));
-    const int middle = dfe_window_middle(33, 33);
-    if (threshold < 0.2)   // extract_output.cpp:83-85
-        hipLaunchKernelGGL(flow_i8_tail_kernel<8>, dim3(grid), dim3(256), 0, ctx->stream, b.verdict, Ho, 33 * 33, 33, 33, middle, threshold, o, fa.rec, fa.rec_rows, nv.fb);
-    else
-        hipLaunchKernelGGL(flow_i8_tail_kernel<4>, dim3(grid), dim3(256), 0, ctx->stream, b.verdict, Ho, 33 * 33, 33, 33, middle, threshold, o, fa.rec, fa.rec_rows, nv.fb);
-    DFE_LAUNCH_CHECK(ctx);
-    return DFE_OK;
+int dfe_flow_i8_launch(dfe_ctx *ctx, const float *I0, const float *I1, int H, int W, const DfeFlowI8Bufs &b, const CvNovolArgs &nv, const TailOut &out,
+                       const DfePairDepth *pd) {
+    return i8_launch<float>(ctx, I0, I1, H, W, b, nv, out, pd);
+}
+int dfe_flow_i8_launch_bytes(dfe_ctx *ctx, const unsigned char *I0, const unsigned char *I1, int H, int W, const DfeFlowI8Bufs &b, const CvNovolArgs &nv,
+                             const TailOut &out, const DfePairDepth *pd) {
+    return i8_launch<unsigned char>(ctx, I0, I1, H, W, b, nv, out, pd);
 }

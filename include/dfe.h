@@ -139,6 +139,10 @@ int dfe_profile_read_each(dfe_ctx *ctx, double *total_ms, int *launches, float *
  * padding, polar warps and the learned filter stacks (its `filter:forward`); match = cost volumes, soft-min and cascade
  * (`model:forward`); extract = arg-best / extractOutput / decode / border / depth passes (`processOutput`; where the arg-best
  * is fused into the matching kernel -- the multiscale cascade, the fused cost-volume build -- that part counts as match).
+ * The single-scale flow step with option "cv_i8" on: match = the pack kernel and the int8 sweep; the ONE launch behind them counts as
+ * extract.  On byte-valued frames that launch is the frame's border; on frames that fail the gate it is also the float sweep, which is
+ * then counted under extract ("cv_i8" = 0 gives the true split).  The byte entries at scale 1 (dfe_flow_depth_pair_u8, _u8_slot) on the
+ * int8 route launch nothing under load or extract: pack-from-bytes (with the border) and the sweep both count as match.
  * enable, run, read: ms[s] = summed GPU time of stage s, launches[s] = number of bracketed regions; read synchronises and resets. */
 #define DFE_STAGE_LOAD 0
 #define DFE_STAGE_FILTER 1

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The pair step on a VGA pair that is NOT byte-valued (bench.py's synthetic pair with one value set to 0.5): pack, the int8 kernel that
-returns at entry, the gated float sweep and the gated tail that runs the record finalize.  Libraries are timed in fresh child processes,
+returns at entry, and the gated launch behind it: the border, the float sweep and the per-block record finalize.  Libraries are timed in fresh child processes,
 interleaved, `--passes` times each; per-step ms from torch.cuda events over `--steps` steps.
 usage: time_flow_float_path.py [--steps N] [--passes P] [--log FILE] lib [lib ...]      (lib = path of a libdfe build, "-" = the product's)"""
 import argparse
