@@ -6,14 +6,16 @@
         dfe_census_cost_volume_f32: Hamming distances summed over the channels and an agg x agg box, as a float volume (the staged route)
     censusFlow(sig0, sig1, nbits, hWin, wWin, agg=3)
         dfe_census_flow_f32: the first minimum of that cost with the centre rule, its match score and the decoded flow; no volume
-    censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consistency=None, gate=False, fill=None, median=None)
-        dfe_census_flow_depth_pair_f32 / _u8: frames -> flow, match score, depth, depth confidence, with flowDepthPair's keys
+    censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consistency=None, gate=False, fill=None, median=None, sgm=None)
+        dfe_census_flow_depth_pair_f32 / _u8: frames -> flow, match score, depth, depth confidence, with flowDepthPair's keys;
+        sgm=(P1, P2): dfe_census_flow_depth_pair_sgm_f32 / _u8, the cost aggregated along image paths before the arg-min
 """
 import torch
 
 from ._lib import lib
 from .context import get_ctx, ptr
 from .fields import _on_device, flowConsistency
+from .sgm_plane import _sgm_arg
 from .subpixel import _frames, _median_arg, _with_fill
 
 MAX_CELLS = 1096   # window cells: the single-scale step's own ceiling
@@ -103,14 +105,22 @@ def censusFlow(sig0, sig1, nbits, hWin, wWin, agg=3):
     return res
 
 
-def _pair(a, b, k, hWin, wWin, agg, fx, fy, scale):
+def _pair(a, b, k, hWin, wWin, agg, fx, fy, scale, sgm=None):
     C, H, W = a.shape
     flow = torch.empty((2, H, W), dtype=torch.float32, device=a.device)
     match = torch.empty((H, W), dtype=torch.float32, device=a.device)
     depth = torch.empty_like(match)
     conf = torch.empty_like(match)
     ctx = get_ctx(a)
-    if a.dtype == torch.uint8:
+    if sgm is not None:
+        P1, P2, paths = sgm
+        if a.dtype == torch.uint8:
+            rc = lib().dfe_census_flow_depth_pair_sgm_u8(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, scale, P1, P2, paths, ptr(flow),
+                                                         ptr(match), ptr(depth), ptr(conf))
+        else:
+            rc = lib().dfe_census_flow_depth_pair_sgm_f32(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, P1, P2, paths, ptr(flow), ptr(match),
+                                                          ptr(depth), ptr(conf))
+    elif a.dtype == torch.uint8:
         rc = lib().dfe_census_flow_depth_pair_u8(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, scale, ptr(flow), ptr(match), ptr(depth),
                                                  ptr(conf))
     else:
@@ -119,7 +129,7 @@ def _pair(a, b, k, hWin, wWin, agg, fx, fy, scale):
     return {"flow": flow, "scores": match, "depth": depth, "depth_conf": conf}
 
 
-def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consistency=None, gate=False, fill=None, median=None):
+def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consistency=None, gate=False, fill=None, median=None, sgm=None):
     """One frame pair through the census matcher: C x H x W frames (float32 or uint8, 1 <= C <= 4), a k x k patch (k odd, 3 .. 7), an
     hWin x wWin search window, the Hamming cost summed over an agg x agg box (1, 3 or 5), foe = (x, y) focus of expansion.  Returns the keys
     of flowDepthPair: flow [2][H][W] (y, x), scores [H][W] = the match score 1 - best / ((k k - 1) C agg^2), depth, depth_conf, zero outside
@@ -127,8 +137,12 @@ def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consis
     frames as flowDepthPair accepts it and changes no bit: the bytes are compared as they are.
     consistency=tol: the call also runs from img2 to img1 and the dict gains flow_bw, consistent and consistency_err =
     flowConsistency(flow, flow_bw, tol, region); gate=True multiplies scores and depth_conf by consistent.  fill and median: as in
-    flowDepthPair, over the region above, with weight 1 where scores > 0 (and consistent)."""
+    flowDepthPair, over the region above, with weight 1 where scores > 0 (and consistent).
+    sgm: None, (P1, P2) or dict(P1=, P2=, paths=0x0f) -- the aggregated census cost goes through
+    semiGlobalAggregatePlane before the arg-min, in both directions of consistency= (dfe_census_flow_depth_pair_sgm_f32 / _u8); scores is
+    then the match score of the raw cost at the chosen class.  None leaves every bit and every launch as it is."""
     median = _median_arg(median)
+    sgm = _sgm_arg(sgm, "censusFlowDepthPair")
     for t in (img1, img2):
         if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.uint8) or t.dtype != img1.dtype:
             raise TypeError("censusFlowDepthPair: two float32 or two uint8 frames expected")
@@ -147,9 +161,9 @@ def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consis
     a, b = _frames(a, b, "censusFlowDepthPair")   # (the device check comes last: every check above needs none)
     R = ((H - Ha) // 2, (W - Wa) // 2, Ha, Wa)
     fx, fy = float(foe[0]), float(foe[1])
-    res = _pair(a, b, k, hWin, wWin, agg, fx, fy, float(scale))
+    res = _pair(a, b, k, hWin, wWin, agg, fx, fy, float(scale), sgm)
     if consistency is not None:
-        bw = _pair(b, a, k, hWin, wWin, agg, fx, fy, float(scale))["flow"]
+        bw = _pair(b, a, k, hWin, wWin, agg, fx, fy, float(scale), sgm)["flow"]
         mask, err = flowConsistency(res["flow"], bw, float(consistency), R)
         res.update(flow_bw=bw, consistent=mask, consistency_err=err)
         if gate:

@@ -60,6 +60,9 @@ int dfe_census_cost_volume_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_
 int dfe_census_flow_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1, int C, int Hp, int Wp, int nbits, int hWin, int wWin, int agg, int64_t *idx, float *best, float *match, float *flow_y, float *flow_x);
 int dfe_census_flow_depth_pair_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float *flow, float *match, float *depth, float *depth_conf);
 int dfe_census_flow_depth_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float scale, float *flow, float *match, float *depth, float *depth_conf);
+int dfe_sgm_plane_aggregate_f32(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, float *agg, int64_t *idx, float *flow_y, float *flow_x);
+int dfe_census_flow_depth_pair_sgm_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float P1, float P2, unsigned paths, float *flow, float *match, float *depth, float *depth_conf);
+int dfe_census_flow_depth_pair_sgm_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths, float *flow, float *match, float *depth, float *depth_conf);
 int dfe_spatial_matching_backward_f32(dfe_ctx *ctx, const float *in1, const float *in2, const float *gradOut, int K, int H1, int W1, int maxh, int maxw, float *gradIn1, float *gradIn2);
 int dfe_radial_matching_backward_f32(dfe_ctx *ctx, const float *in1, const float *in2, const float *gradOut, int K, int H1, int W, int hWin, float *gradIn1, float *gradIn2);
 int dfe_argbest_center(dfe_ctx *ctx, const float *vol, int64_t P, int N, int middle, int take_max, int64_t *idx, float *best);

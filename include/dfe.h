@@ -339,6 +339,48 @@ int dfe_census_flow_depth_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t
                                   int agg, float foe_x, float foe_y, float scale, float *flow, float *match, float *depth,
                                   float *depth_conf);
 
+/* ---- semi-global aggregation on a two-dimensional label plane: smoothed labels for the Cartesian matchers (NOT in the reference;
+ * DESIGN section 4.31) ------------------------------------------------------------------------------------------------------------ */
+/* dfe_sgm_aggregate_f32's path aggregation for the volumes whose label is a cell of a search window.  volume [H][W][hWin][wWin]: the
+ * geometry and class order of the SSD and census volumes, class = dy wWin + dx + 1.  agg [H][W][hWin][wWin] or NULL; idx [H][W]
+ * (int64, 1-based class), flow_y, flow_x [H][W], each or NULL.  With C = volume, every operation fp32, rounded on its own, not
+ * contracted, in exactly this order:
+ *   Labels: a label is a cell (dy, dx) of the window; its neighbours are the four cells at city-block distance 1; a cell outside
+ *     the window counts as +Inf.
+ *   Directions: bit r of `paths` is the direction (dy, dx) of dfe_sgm_aggregate_f32: 0 (0, +1), 1 (0, -1), 2 (+1, 0), 3 (-1, 0),
+ *     4 (+1, +1), 5 (-1, -1), 6 (+1, -1), 7 (-1, +1).  There is no ring: these are Cartesian frames.
+ *   Step: for a pixel p with predecessor q = p - r and m = the minimum of L_r(q, .) over all cells:
+ *     t = L_r(q, (dy, dx));
+ *     t = min(t, L_r(q, (dy, dx-1)) + P1);  t = min(t, L_r(q, (dy, dx+1)) + P1);
+ *     t = min(t, L_r(q, (dy-1, dx)) + P1);  t = min(t, L_r(q, (dy+1, dx)) + P1);
+ *     t = min(t, m + P2);   L_r(p, (dy, dx)) = C(p, (dy, dx)) + (t - m).
+ *   Start: L_r(p, .) = C(p, .) where q lies outside the plane.
+ *   Sum: agg = L_r of the lowest set bit, then agg = agg + L_r for each further set bit in ascending r.
+ *   Flow: idx = what dfe_argbest_center gives on agg with middle = getMiddleIndex: the first minimum in class order, the centre
+ *     class winning an exact tie; flow_y, flow_x decoded as dfe_x2yx decodes, as floats.
+ * hWin, wWin >= 1 with hWin wWin <= 1096, the single-scale step's ceiling (more: DFE_E_UNSUPPORTED); H, W >= 1 with H * W < 2^31
+ * (DFE_E_SHAPE, as a window side below 1); paths in 1 .. 255, P1 and P2 finite with 0 <= P1 <= P2, volume not NULL, outputs not all
+ * NULL, agg != volume (DFE_E_ARG).  Refused before any launch.  The volume must be finite; for anything else the result is unspecified.
+ * Two launches.  All directions at once, each into a plane of its own in the ctx's scratch arena (H * W * hWin * wWin floats per set
+ * bit): a line of pixels belongs to one wave, cell j 64 + lane in lane `lane`, the cell axis padded with +Inf cells, which change no
+ * bit of a real cell; L_r(q, .) is exchanged through a double-buffered LDS plane with a +Inf frame.  Then a wave a pixel sums the
+ * planes in order and takes the first minimum; with agg == NULL the aggregate is never stored.  (A single direction with agg given
+ * writes its L straight there.)  Asynchronous on the ctx's stream; runs under DFE_STAGE_MATCH. */
+int dfe_sgm_plane_aggregate_f32(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2,
+                                unsigned paths, float *agg, int64_t *idx, float *flow_y, float *flow_x);
+/* dfe_census_flow_depth_pair_* with the aggregation between the cost and the arg-min.  Same arguments and outputs, plus P1, P2, paths
+ * (dfe_sgm_plane_aggregate_f32's, on the Ha x Wa plane of the aggregated census cost).  Order of work: two transforms, the staged
+ * census volume (dfe_census_cost_volume_f32) into the scratch arena, the aggregation with no aggregate stored, the flow at the pasted
+ * positions, the border and depth pass of the single-scale step.  match = 1 - C(p, idx) / (nbits C agg^2): the census match score of the
+ * RAW cost at the chosen class, on the scale of dfe_census_flow_depth_pair_*'s.  Every argument is checked before any launch, with
+ * the codes of the two entries it joins.  Bit-identical to the staged public calls plus the paste. */
+int dfe_census_flow_depth_pair_sgm_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin,
+                                       int agg, float foe_x, float foe_y, float P1, float P2, unsigned paths, float *flow,
+                                       float *match, float *depth, float *depth_conf);
+int dfe_census_flow_depth_pair_sgm_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin,
+                                      int agg, float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths, float *flow,
+                                      float *match, float *depth, float *depth_conf);
+
 /* ---- N2: gradients of the two matchers (training drivers call model:backward through them) ------- */
 /* replaces: nn.SpatialMatching:updateGradInput / nn.SpatialRadialMatching:updateGradInput (un-vendored nnx), reached
  *   from radial/train_radial_opticalflow.lua:228-252 and opticalflow.lua:296-338.  gradOut has the forward output's
