@@ -39,6 +39,8 @@ no CPU fallback -- a missing library or device raises.
     semiGlobalAggregatePlane, censusFlowDepthPair(..., sgm=(P1, P2))     (not in the reference: the aggregation on the two-dimensional
                                                         label plane of a Cartesian matcher's [H][W][hWin][wWin] volume, its first customer
                                                         the census cost -- sgm_plane.py)
+    semiGlobalPick, flowDepthPair(..., sgm=(P1, P2))    (not in the reference: a uniqueness confidence and a sub-pixel flow read off the
+                                                        aggregate, and the SSD step through it in one call -- sgm_plane.py, subpixel.py)
     getModel(geometry).forwardFlow                      (a trained single-scale model per frame pair in one call,
                                                         output_extraction_method 'max' or 'mean' -- network.py)
     imageScale, DepthEstimationAPI(...).nextFrameDepth  (image.scale; depth_estimation_api.lua:134-198, video -> depth per camera
@@ -68,7 +70,7 @@ from .opticalflow_model import (  # noqa: F401
 from . import version2  # noqa: F401
 from .subpixel import flowDepthPair, refineFlowSubpixel  # noqa: F401
 from .fields import flowConsistency, fillHoles, weightedMedian, guidedUpsample  # noqa: F401
-from .sgm_plane import semiGlobalAggregatePlane  # noqa: F401
+from .sgm_plane import semiGlobalAggregatePlane, semiGlobalPick  # noqa: F401
 from .census import censusTransform, censusCostVolume, censusFlow, censusFlowDepthPair  # noqa: F401
 from .multiscale import CascadingAddTable, MultiscaleModel, MultiscalePrefilter, getModelMultiscale, getMultiscalePrefilter  # noqa: F401
 from .network import getFilter, getFilterRadial, getModel, tables_random  # noqa: F401

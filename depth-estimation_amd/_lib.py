@@ -183,6 +183,13 @@ PROTOTYPES = {
     "dfe_sgm_plane_aggregate_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_uint] + [C.c_void_p] * 4),
     "dfe_census_flow_depth_pair_sgm_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_float] * 4 + [C.c_uint] + [C.c_void_p] * 4),
     "dfe_census_flow_depth_pair_sgm_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_float] * 5 + [C.c_uint] + [C.c_void_p] * 4),
+    "dfe_sgm_plane_pick_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_uint, C.c_int, C.c_float] + [C.c_void_p] * 7),
+    "dfe_flow_depth_pair_sgm_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float] * 4 + [C.c_uint, C.c_int, C.c_float] + [C.c_void_p] * 4),
+    "dfe_flow_depth_pair_sgm_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float] * 5 + [C.c_uint, C.c_int, C.c_float] + [C.c_void_p] * 4),
+    "dfe_census_flow_depth_pair_sgm2_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_float] * 4 + [C.c_uint, C.c_int, C.c_float]
+                                            + [C.c_void_p] * 5),
+    "dfe_census_flow_depth_pair_sgm2_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_float] * 5 + [C.c_uint, C.c_int, C.c_float]
+                                           + [C.c_void_p] * 5),
     "dfe_corner_response_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dfe_select_corners_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "dfe_pyr_down_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

@@ -6,16 +6,18 @@
         dfe_census_cost_volume_f32: Hamming distances summed over the channels and an agg x agg box, as a float volume (the staged route)
     censusFlow(sig0, sig1, nbits, hWin, wWin, agg=3)
         dfe_census_flow_f32: the first minimum of that cost with the centre rule, its match score and the decoded flow; no volume
-    censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consistency=None, gate=False, fill=None, median=None, sgm=None)
+    censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consistency=None, gate=False, fill=None, median=None, sgm=None,
+                        subpixel=False)
         dfe_census_flow_depth_pair_f32 / _u8: frames -> flow, match score, depth, depth confidence, with flowDepthPair's keys;
-        sgm=(P1, P2): dfe_census_flow_depth_pair_sgm_f32 / _u8, the cost aggregated along image paths before the arg-min
+        sgm=(P1, P2): dfe_census_flow_depth_pair_sgm_f32 / _u8, the cost aggregated along image paths before the arg-min (DESIGN section 4.31);
+        with subpixel=True or min_unique in the dict: the _sgm2_ entries, which add the key unique
 """
 import torch
 
 from ._lib import lib
 from .context import get_ctx, ptr
 from .fields import _on_device, flowConsistency
-from .sgm_plane import _sgm_arg
+from .sgm_plane import _sgm_pick_arg
 from .subpixel import _frames, _median_arg, _with_fill
 
 MAX_CELLS = 1096   # window cells: the single-scale step's own ceiling
@@ -105,15 +107,25 @@ def censusFlow(sig0, sig1, nbits, hWin, wWin, agg=3):
     return res
 
 
-def _pair(a, b, k, hWin, wWin, agg, fx, fy, scale, sgm=None):
+def _pair(a, b, k, hWin, wWin, agg, fx, fy, scale, sgm=None, subpixel=False):
     C, H, W = a.shape
     flow = torch.empty((2, H, W), dtype=torch.float32, device=a.device)
     match = torch.empty((H, W), dtype=torch.float32, device=a.device)
     depth = torch.empty_like(match)
     conf = torch.empty_like(match)
     ctx = get_ctx(a)
+    if sgm is not None and (subpixel or sgm[4]):
+        P1, P2, paths, min_unique, _ = sgm
+        unique = torch.empty_like(match)
+        tail = (P1, P2, paths, int(bool(subpixel)), min_unique, ptr(flow), ptr(match), ptr(unique), ptr(depth), ptr(conf))
+        if a.dtype == torch.uint8:
+            rc = lib().dfe_census_flow_depth_pair_sgm2_u8(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, scale, *tail)
+        else:
+            rc = lib().dfe_census_flow_depth_pair_sgm2_f32(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, *tail)
+        ctx.check(rc)
+        return {"flow": flow, "scores": match, "unique": unique, "depth": depth, "depth_conf": conf}
     if sgm is not None:
-        P1, P2, paths = sgm
+        P1, P2, paths = sgm[:3]
         if a.dtype == torch.uint8:
             rc = lib().dfe_census_flow_depth_pair_sgm_u8(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, scale, P1, P2, paths, ptr(flow),
                                                          ptr(match), ptr(depth), ptr(conf))
@@ -129,7 +141,8 @@ def _pair(a, b, k, hWin, wWin, agg, fx, fy, scale, sgm=None):
     return {"flow": flow, "scores": match, "depth": depth, "depth_conf": conf}
 
 
-def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consistency=None, gate=False, fill=None, median=None, sgm=None):
+def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consistency=None, gate=False, fill=None, median=None, sgm=None,
+                        subpixel=False):
     """One frame pair through the census matcher: C x H x W frames (float32 or uint8, 1 <= C <= 4), a k x k patch (k odd, 3 .. 7), an
     hWin x wWin search window, the Hamming cost summed over an agg x agg box (1, 3 or 5), foe = (x, y) focus of expansion.  Returns the keys
     of flowDepthPair: flow [2][H][W] (y, x), scores [H][W] = the match score 1 - best / ((k k - 1) C agg^2), depth, depth_conf, zero outside
@@ -140,9 +153,15 @@ def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consis
     flowDepthPair, over the region above, with weight 1 where scores > 0 (and consistent).
     sgm: None, (P1, P2) or dict(P1=, P2=, paths=0x0f) -- the aggregated census cost goes through
     semiGlobalAggregatePlane before the arg-min, in both directions of consistency= (dfe_census_flow_depth_pair_sgm_f32 / _u8); scores is
-    then the match score of the raw cost at the chosen class.  None leaves every bit and every launch as it is."""
+    then the match score of the raw cost at the chosen class.  None leaves every bit and every launch as it is.
+    subpixel=True (with sgm only, else ValueError) or min_unique in the sgm dict: the
+    dfe_census_flow_depth_pair_sgm2_f32 / _u8 entries -- the flow moves by the per-axis parabola through the AGGREGATE, and the dict gains
+    unique [H][W], the uniqueness (second - best) / second of the aggregate gated by min_unique, 0 outside the region; scores keeps its
+    meaning, and fill and median still weigh by scores > 0."""
     median = _median_arg(median)
-    sgm = _sgm_arg(sgm, "censusFlowDepthPair")
+    sgm = _sgm_pick_arg(sgm, "censusFlowDepthPair")
+    if subpixel and sgm is None:
+        raise ValueError("censusFlowDepthPair: subpixel=True refines on the aggregate: it needs sgm=")
     for t in (img1, img2):
         if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.uint8) or t.dtype != img1.dtype:
             raise TypeError("censusFlowDepthPair: two float32 or two uint8 frames expected")
@@ -161,9 +180,9 @@ def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consis
     a, b = _frames(a, b, "censusFlowDepthPair")   # (the device check comes last: every check above needs none)
     R = ((H - Ha) // 2, (W - Wa) // 2, Ha, Wa)
     fx, fy = float(foe[0]), float(foe[1])
-    res = _pair(a, b, k, hWin, wWin, agg, fx, fy, float(scale), sgm)
+    res = _pair(a, b, k, hWin, wWin, agg, fx, fy, float(scale), sgm, subpixel)
     if consistency is not None:
-        bw = _pair(b, a, k, hWin, wWin, agg, fx, fy, float(scale), sgm)["flow"]
+        bw = _pair(b, a, k, hWin, wWin, agg, fx, fy, float(scale), sgm, subpixel)["flow"]
         mask, err = flowConsistency(res["flow"], bw, float(consistency), R)
         res.update(flow_bw=bw, consistent=mask, consistency_err=err)
         if gate:

@@ -496,6 +496,33 @@ DFE_HIDDEN size_t dfe_sgm_work_planes(unsigned paths, bool agg_given);
 DFE_HIDDEN int dfe_sgm_run(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *work, float *agg,
                            float *flow);
 
+// sgm_plane.hip -- semi-global aggregation of a [H][W][hWin][wWin] volume; sgm_pick.hip launches its path kernel through these
+struct SgmpJob {
+    const float *C;      // [H][W][cells]
+    float *L[8];         // [H][W][cells] each: L of the n directions asked for, in ascending bit order
+    int dy[8], dx[8];    // their directions: p's predecessor is p - (dy, dx)
+    int n;
+    int H, W, hWin, wWin, cells;
+    float P1, P2;
+};
+struct SgmpOut {
+    float *agg;            // [H][W][cells] or NULL
+    long long *idx;        // [H][W], 1-based; or NULL
+    float *fy, *fx;        // at [(y + pad_t) pitch + x + pad_l]; each or NULL
+    float *match;          // the same positions: 1 - raw(p, idx) / den; or NULL
+    const float *raw;      // the volume the match score reads (match != NULL)
+    float den;
+    int pitch, pad_t, pad_l;
+    int mid0;              // the centre class, 0-based
+};
+// dfe_sgm_plane_aggregate_f32's checks of the sizes and parameters (fn: the entry's name for the message)
+DFE_HIDDEN int sgmp_check(dfe_ctx *ctx, const char *fn, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths);
+// planes of H * W * cells floats that sgmp_run takes as `work`: one per direction, unless the only direction goes straight to agg
+DFE_HIDDEN size_t sgmp_work_planes(unsigned paths, bool agg_given);
+// the launches behind the checks: direction k (ascending bit order) into work + k planes, then the sum kernel for whatever `o` asks for
+// (an empty `o`: the path launch alone)
+DFE_HIDDEN int sgmp_run(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, float *work, SgmpOut o);
+
 // multiscale.hip, multiscale_subpixel.hip
 // the raw-patch pyramid on uint8 frames, converted inside its preparation kernels (f16_scale 0 = fp32 volumes)
 // subpixel: the sub-pixel refinement behind the matcher (dfe_multiscale_flow_pair_subpixel_u8)

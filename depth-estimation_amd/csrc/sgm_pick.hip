@@ -1,0 +1,329 @@
+// sgm_pick.hip -- what a caller reads off the aggregate of sgm_plane.hip besides its arg-min: a uniqueness confidence and a sub-pixel
+// flow taken on the surface that was minimised (NOT in the reference).  The definition -- the far cells, the
+// uniqueness ratio, the per-axis parabola with cost := A -- is in include/dfe.h and restated in numpy in tests/sgm_pick_ref.py; the
+// device is tested against that bit for bit.
+//   sgpk_pick_kernel<SUB>   sgmp_sum_kernel's shape: a wave a pixel, four pixels a block, agg = ((L_a + L_b) + L_c) + ... in ascending
+//       direction order, the first minimum in class order by a wave reduction on (value, class), the centre class winning an exact tie.
+//       A lane also leaves each sum in the wave's own LDS row (1096 floats a wave, 17.5 KB a block: the registers, not the LDS, bound
+//       the waves a CU holds), so the second pass -- the smallest sum outside the winner's 3 x 3 neighbourhood -- and the parabola's
+//       four neighbours read A itself: no plane is read twice and no sum is formed twice, so their bits are A's by construction.
+//   The path launch is sgm_plane.hip's, unchanged (sgmp_run with nothing to sum); paths == 0 skips it and A = the volume.
+//   The one calls: dfe_flow_depth_pair_sgm_f32 / _u8 (the SSD step) and dfe_census_flow_depth_pair_sgm2_f32 / _u8.
+#include "dfe_internal.h"
+#include "subpixel_offset.h"   // the parabola's vertex on one axis (include/dfe.h: this order, IEEE division)
+#include <cmath>
+#include <climits>
+
+namespace {
+
+constexpr int kSgpkMaxCells = 1096;   // sgm_plane.hip's ceiling (sgmp_check refuses more)
+
+struct SgpkJob {
+    const float *L[8];   // [H][W][cells] each: the planes to sum, in order (paths == 0: the volume alone)
+    int n;
+    int H, W, hWin, wWin, cells;
+    int mid0;            // the centre class, 0-based
+    float min_unique;
+};
+
+struct SgpkOut {
+    float *agg;            // [H][W][cells] or NULL
+    long long *idx;        // [H][W], 1-based; or NULL
+    // each of the following at [(y + pad_t) pitch + x + pad_l], or NULL
+    float *fy, *fx, *best, *second, *unique;
+    float *match;          // 1 - raw(p, idx) / den (the census one call)
+    const float *raw;      // the volume the match score reads (match != NULL)
+    float den;
+    int pitch, pad_t, pad_l;
+};
+
+template <bool SUB>
+__global__ __launch_bounds__(256) void sgpk_pick_kernel(const SgpkJob a, const SgpkOut o) {
+#pragma clang fp contract(off)
+    __shared__ float sums[4][kSgpkMaxCells];     // A(p, .) of the wave's pixel
+    const float inf = __builtin_inff();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float *A = sums[wave];
+    const long long P = (long long)a.H * a.W;
+    const long long px = (long long)blockIdx.x * 4 + wave;
+    const bool live = px < P;                    // (wave-uniform; a wave past the end still meets the barrier)
+    const size_t e = live ? (size_t)px * a.cells : 0;
+    float b = inf, cen = inf;
+    int bi = INT_MAX;
+    if (live) {
+        for (int c = lane; c < a.cells; c += 64) {
+            float t = a.L[0][e + c];
+            for (int k = 1; k < a.n; ++k) t = t + a.L[k][e + c];
+            if (o.agg) o.agg[e + c] = t;
+            A[c] = t;
+            if (t < b) { b = t; bi = c; }        // (a lane's classes ascend: strict `<` keeps its first minimum)
+            if (c == a.mid0) cen = t;
+        }
+    }
+    // the smallest value, and among equal ones the smallest class; the centre's value to every lane
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const float ob = __shfl_xor(b, d, 64);
+        const int oi = __shfl_xor(bi, d, 64);
+        const bool take = (ob < b) | ((ob == b) & (oi < bi));
+        b = take ? ob : b;
+        bi = take ? oi : bi;
+        cen = fminf(cen, __shfl_xor(cen, d, 64));
+    }
+    __syncthreads();                             // the wave's sums are in its row
+    if (!live) return;
+    if (cen == b || bi >= a.cells) bi = a.mid0;  // the centre wins an exact tie with the best (and a volume that is not finite reads in bounds)
+    const int r = bi / a.wWin, s = bi - r * a.wWin;
+    // the smallest sum at Chebyshev distance 2 or more from the winner: +Inf if the window has no such cell
+    float sec = inf;
+    if (o.second || o.unique) {
+        int cy = lane / a.wWin, cx = lane - cy * a.wWin;
+        const int sy = 64 / a.wWin, sx = 64 - sy * a.wWin;   // 64 cells further on
+        for (int c = lane; c < a.cells; c += 64) {
+            const int ey = cy > r ? cy - r : r - cy, ex = cx > s ? cx - s : s - cx;
+            const float t = A[c];
+            sec = ((ey >= 2) | (ex >= 2)) ? fminf(sec, t) : sec;
+            cy += sy; cx += sx;
+            if (cx >= a.wWin) { cx -= a.wWin; ++cy; }
+        }
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) sec = fminf(sec, __shfl_xor(sec, d, 64));
+    }
+    if (lane != 0) return;
+    const float c0 = A[bi];
+    const int y = (int)(px / a.W), x = (int)(px - (long long)y * a.W);
+    const size_t op = (size_t)(y + o.pad_t) * o.pitch + x + o.pad_l;
+    if (o.idx) o.idx[px] = bi + 1;
+    if (o.match) o.match[op] = 1.0f - o.raw[e + bi] / o.den;
+    if (o.best) o.best[op] = c0;
+    if (o.second) o.second[op] = sec;
+    if (o.unique) {
+        const float u = (sec == inf || !(sec > 0.f)) ? 0.f : (sec - c0) / sec;   // (not clamped)
+        o.unique[op] = u >= a.min_unique ? u : 0.f;
+    }
+    float fy = (float)(r - (a.hWin - 1) / 2), fx = (float)(s - (a.wWin - 1) / 2);   // dfe_x2yx
+    if constexpr (SUB) {
+        // a neighbour outside the window is not read: its cell is replaced by the winner's and the axis gives off = 0
+        const bool inx = s >= 1 && s + 1 < a.wWin, iny = r >= 1 && r + 1 < a.hWin;
+        const float cxm = A[inx ? bi - 1 : bi], cxp = A[inx ? bi + 1 : bi];
+        const float cym = A[iny ? bi - a.wWin : bi], cyp = A[iny ? bi + a.wWin : bi];
+        fy = fy + subpixel_offset(iny, cym, c0, cyp);
+        fx = fx + subpixel_offset(inx, cxm, c0, cxp);
+    }
+    if (o.fy) o.fy[op] = fy;
+    if (o.fx) o.fx[op] = fx;
+}
+
+// dfe_sgm_plane_pick_f32's parameter rules on top of sgmp_check's (paths == 0 allowed: P1 / P2 are checked all the same)
+int sgpk_check(dfe_ctx *ctx, const char *fn, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, float min_unique) {
+    int rc = sgmp_check(ctx, fn, H, W, hWin, wWin, P1, P2, paths ? paths : 1u);
+    if (rc) return rc;
+    DFE_REQUIRE(ctx, min_unique >= 0.f && min_unique <= 1.f, DFE_E_ARG, "%s: min_unique=%g must be in [0, 1]", fn, (double)min_unique);
+    return DFE_OK;
+}
+
+// planes of H * W * cells floats that sgpk_run takes as `work`
+size_t sgpk_work_planes(unsigned paths, bool agg_given) { return paths ? sgmp_work_planes(paths, agg_given) : 0; }
+
+// The launches behind the checks: sgm_plane.hip's path kernel (paths != 0), then the pick.  o: where the results go
+int sgpk_run(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, int subpixel, float min_unique,
+             float *work, SgpkOut o) {
+    SgpkJob a{};
+    a.H = H; a.W = W; a.hWin = hWin; a.wWin = wWin; a.cells = hWin * wWin;
+    a.mid0 = dfe_window_middle(hWin, wWin) - 1;
+    a.min_unique = min_unique;
+    if (paths == 0) {
+        a.L[0] = volume;
+        a.n = 1;
+    } else {
+        a.n = __builtin_popcount(paths & 255u);
+        const bool direct = sgmp_work_planes(paths, o.agg != nullptr) == 0;   // one direction, and its L is the aggregate the caller wants
+        SgmpOut so{};
+        so.agg = direct ? o.agg : nullptr;
+        int rc = sgmp_run(ctx, volume, H, W, hWin, wWin, P1, P2, paths, work, so);   // (nothing to sum: the path launch alone)
+        if (rc) return rc;
+        const size_t plane = (size_t)H * W * a.cells;
+        for (int k = 0; k < a.n; ++k) a.L[k] = direct ? o.agg : work + (size_t)k * plane;
+        if (direct) o.agg = nullptr;
+    }
+    DfeProfScope prof(ctx);
+    const dim3 grid((unsigned)dfe_cdiv((long long)H * W, 4));
+    if (subpixel) hipLaunchKernelGGL(sgpk_pick_kernel<true>, grid, dim3(256), 0, ctx->stream, a, o);
+    else hipLaunchKernelGGL(sgpk_pick_kernel<false>, grid, dim3(256), 0, ctx->stream, a, o);
+    DFE_LAUNCH_CHECK(ctx);
+    ctx->last_kernel = "sgpk_pick_kernel";
+    return DFE_OK;
+}
+
+// the SSD one call behind its device guard, on float frames
+int sgpk_ssd_pair(dfe_ctx *ctx, const char *fn, const float *I0, const float *I1, const uint8_t *B0, const uint8_t *B1, float scale, int C, int H, int W, int k,
+                  int hWin, int wWin, float foe_x, float foe_y, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *scores,
+                  float *depth, float *depth_conf) {
+    // the single-scale step's checks, in its order, then the aggregation's and the pick's: everything is refused before any launch
+    const bool bytes = B0 || B1;
+    DFE_REQUIRE(ctx, (bytes ? B0 && B1 : I0 && I1) && flow && scores, DFE_E_ARG, "%s: NULL tensor", fn);
+    DFE_REQUIRE(ctx, C > 0 && k > 0 && hWin > 0 && wWin > 0, DFE_E_ARG, "%s: C=%d k=%d win=%dx%d", fn, C, k, hWin, wWin);
+    DFE_REQUIRE(ctx, (depth == nullptr) == (depth_conf == nullptr), DFE_E_ARG, "%s: depth and depth_conf go together", fn);
+    const int Ho = H - k + 1 - hWin + 1, Wo = W - k + 1 - wWin + 1;
+    DFE_REQUIRE(ctx, Ho > 0 && Wo > 0, DFE_E_SHAPE, "%s: frame %dx%d too small for kernel %d + window %dx%d", fn, H, W, k, hWin, wWin);
+    DFE_REQUIRE(ctx, paths != 0u, DFE_E_ARG, "%s: paths=0x%x must be 1 .. 255 (bit r = direction r)", fn, paths);
+    int rc = sgpk_check(ctx, fn, Ho, Wo, hWin, wWin, P1, P2, paths, min_unique);
+    if (rc) return rc;
+    float *f0 = nullptr, *f1 = nullptr, *vol = nullptr, *work = nullptr;
+    const size_t n = (size_t)C * H * W, plane = (size_t)Ho * Wo * hWin * wWin;
+    // The whole volume: the vertical paths need every row, so there are no bands.  In the PLAIN arena: the volume and the n planes lie a
+    // fixed distance apart, and in physically contiguous memory the build and the path launch are slower for it (VGA, 17 x 17, 4 paths:
+    // the build 163 against 90 us, the paths 810 against 755 us; the call 1.41 against 1.06 ms -- DESIGN.md section 4.32)
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
+        if (bytes) { f0 = c.take<float>(n); f1 = c.take<float>(n); }
+        vol = c.take<float>(plane);
+        work = c.take<float>(sgpk_work_planes(paths, false) * plane);
+    }, /*plain*/ true);
+    if (rc) return rc;
+    if (bytes) {   // float(byte) * scale, as dfe_flow_depth_pair_u8 converts
+        DfeStageScope st(ctx, DFE_STAGE_LOAD);
+        rc = dfe_u8_to_f32(ctx, B0, (int64_t)n, scale, f0);
+        if (!rc) rc = dfe_u8_to_f32(ctx, B1, (int64_t)n, scale, f1);
+        if (rc) return rc;
+        I0 = f0; I1 = f1;
+    }
+    const int pad_t = (H - Ho) / 2, pad_l = (W - Wo) / 2;   // the rule of flow_step.hip
+    {   // the staged public call itself (it carves nothing): the same kernel, the same bits
+        DfeStageScope st(ctx, DFE_STAGE_MATCH);
+        rc = dfe_ssd_cost_volume_f32(ctx, I0, I1, C, H, W, k, k, hWin, wWin, vol);
+        if (rc) return rc;
+        SgpkOut o{};
+        o.fy = flow; o.fx = flow + (size_t)H * W;
+        o.unique = scores;
+        o.pitch = W; o.pad_t = pad_t; o.pad_l = pad_l;
+        rc = sgpk_run(ctx, vol, Ho, Wo, hWin, wWin, P1, P2, paths, subpixel, min_unique, work, o);
+        if (rc) return rc;
+    }
+    DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
+    return dfe_pair_border_depth(ctx, flow, scores, H, W, pad_t, pad_l, Ho, Wo, foe_x, foe_y, depth, depth_conf);
+}
+
+// the census one call behind its device guard: T = float or uint8_t
+template <class T>
+int sgpk_census_pair(dfe_ctx *ctx, const char *fn, const T *I0, const T *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y,
+                     float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *match, float *unique, float *depth,
+                     float *depth_conf) {
+    // dfe_census_flow_depth_pair_sgm_*'s checks, in their order, then the pick's: everything is refused before any launch
+    DFE_REQUIRE(ctx, I0 && I1 && flow && match, DFE_E_ARG, "%s: NULL tensor", fn);
+    DFE_REQUIRE(ctx, (depth == nullptr) == (depth_conf == nullptr), DFE_E_ARG, "%s: depth and depth_conf go together", fn);
+    DFE_REQUIRE(ctx, k >= 3 && (k & 1) && k * k <= 64, DFE_E_ARG, "%s: patch %dx%d: odd sides of at least 3 with at most 64 cells expected", fn, k, k);
+    DFE_REQUIRE(ctx, H >= 1 && W >= 1 && H <= 32768 && W <= 32768, DFE_E_SHAPE, "%s: frame %dx%d (1 .. 32768 each)", fn, H, W);
+    DFE_REQUIRE(ctx, H >= k && W >= k, DFE_E_SHAPE, "%s: frame %dx%d too small for a %dx%d patch", fn, H, W, k, k);
+    DFE_REQUIRE(ctx, C >= 1 && C <= 4, DFE_E_ARG, "%s: C=%d channels (1 .. 4)", fn, C);
+    DFE_REQUIRE(ctx, agg == 1 || agg == 3 || agg == 5, DFE_E_ARG, "%s: agg=%d must be 1, 3 or 5", fn, agg);
+    DFE_REQUIRE(ctx, hWin >= 1 && wWin >= 1, DFE_E_ARG, "%s: window %dx%d", fn, hWin, wWin);
+    DFE_REQUIRE(ctx, (long long)hWin * wWin <= kSgpkMaxCells, DFE_E_UNSUPPORTED, "%s: window %dx%d has more than %d cells", fn, hWin, wWin, kSgpkMaxCells);
+    const int Hp = H - k + 1, Wp = W - k + 1;
+    const int Ha = Hp - hWin + 1 - agg + 1, Wa = Wp - wWin + 1 - agg + 1;
+    DFE_REQUIRE(ctx, Ha >= 1 && Wa >= 1, DFE_E_SHAPE, "%s: %dx%d patch positions leave no pixel for a %dx%d window summed over %dx%d", fn, Hp, Wp, hWin, wWin,
+                agg, agg);
+    DFE_REQUIRE(ctx, paths != 0u, DFE_E_ARG, "%s: paths=0x%x must be 1 .. 255 (bit r = direction r)", fn, paths);
+    int rc = sgpk_check(ctx, fn, Ha, Wa, hWin, wWin, P1, P2, paths, min_unique);
+    if (rc) return rc;
+    uint64_t *sig0 = nullptr, *sig1 = nullptr;
+    float *vol = nullptr, *work = nullptr;
+    const size_t n = (size_t)C * Hp * Wp, plane = (size_t)Ha * Wa * hWin * wWin;
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
+        sig0 = c.take<uint64_t>(n);
+        sig1 = c.take<uint64_t>(n);
+        vol = c.take<float>(plane);
+        work = c.take<float>(sgpk_work_planes(paths, false) * plane);
+    });
+    if (rc) return rc;
+    {   // the staged public calls themselves (they carve nothing): the same kernels, the same bits
+        DfeStageScope st(ctx, DFE_STAGE_FILTER);
+        if constexpr (sizeof(T) == 1) {
+            rc = dfe_census_transform_u8(ctx, I0, C, H, W, k, k, sig0);
+            if (!rc) rc = dfe_census_transform_u8(ctx, I1, C, H, W, k, k, sig1);
+        } else {
+            rc = dfe_census_transform_f32(ctx, I0, C, H, W, k, k, sig0);
+            if (!rc) rc = dfe_census_transform_f32(ctx, I1, C, H, W, k, k, sig1);
+        }
+        if (rc) return rc;
+    }
+    const int pad_t = (H - Ha) / 2, pad_l = (W - Wa) / 2;   // the rule of flow_step.hip
+    {
+        DfeStageScope st(ctx, DFE_STAGE_MATCH);
+        rc = dfe_census_cost_volume_f32(ctx, sig0, sig1, C, Hp, Wp, hWin, wWin, agg, vol);
+        if (rc) return rc;
+        if (unique) DFE_HIP(ctx, hipMemsetAsync(unique, 0, (size_t)H * W * sizeof(float), ctx->stream));   // its border: 0, as match's
+        SgpkOut o{};
+        o.fy = flow; o.fx = flow + (size_t)H * W;
+        o.match = match; o.raw = vol;
+        o.den = (float)((k * k - 1) * C * agg * agg);
+        o.unique = unique;
+        o.pitch = W; o.pad_t = pad_t; o.pad_l = pad_l;
+        rc = sgpk_run(ctx, vol, Ha, Wa, hWin, wWin, P1, P2, paths, subpixel, min_unique, work, o);
+        if (rc) return rc;
+    }
+    DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
+    return dfe_pair_border_depth(ctx, flow, match, H, W, pad_t, pad_l, Ha, Wa, foe_x, foe_y, depth, depth_conf);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dfe_sgm_plane_pick_f32(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, int subpixel,
+                           float min_unique, float *agg, int64_t *idx, float *flow_y, float *flow_x, float *best, float *second, float *unique) {
+    DFE_ENTER(ctx);
+    const char *fn = "dfe_sgm_plane_pick_f32";
+    DFE_REQUIRE(ctx, volume && (agg || idx || flow_y || flow_x || best || second || unique), DFE_E_ARG, "%s: %s", fn,
+                volume ? "every output is NULL" : "volume is NULL");
+    DFE_REQUIRE(ctx, agg != volume, DFE_E_ARG, "%s: agg must not be the volume (every direction reads it)", fn);
+    int rc = sgpk_check(ctx, fn, H, W, hWin, wWin, P1, P2, paths, min_unique);
+    if (rc) return rc;
+    float *work = nullptr;
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { work = c.take<float>(sgpk_work_planes(paths, agg != nullptr) * H * W * (size_t)(hWin * wWin)); });
+    if (rc) return rc;
+    SgpkOut o{};
+    o.agg = agg;
+    o.idx = (long long *)idx; o.fy = flow_y; o.fx = flow_x;
+    o.best = best; o.second = second; o.unique = unique;
+    o.pitch = W;
+    DfeStageScope st(ctx, DFE_STAGE_MATCH);
+    return sgpk_run(ctx, volume, H, W, hWin, wWin, P1, P2, paths, subpixel, min_unique, work, o);
+}
+
+int dfe_flow_depth_pair_sgm_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x, float foe_y,
+                                float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *scores, float *depth,
+                                float *depth_conf) {
+    DFE_ENTER(ctx);
+    return sgpk_ssd_pair(ctx, "dfe_flow_depth_pair_sgm_f32", I0, I1, nullptr, nullptr, 1.f, C, H, W, k, hWin, wWin, foe_x, foe_y, P1, P2, paths, subpixel,
+                         min_unique, flow, scores, depth, depth_conf);
+}
+
+int dfe_flow_depth_pair_sgm_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x, float foe_y,
+                               float scale, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *scores, float *depth,
+                               float *depth_conf) {
+    DFE_ENTER(ctx);
+    const char *fn = "dfe_flow_depth_pair_sgm_u8";
+    DFE_REQUIRE(ctx, I0 && I1, DFE_E_ARG, "%s: NULL frame", fn);
+    DFE_REQUIRE(ctx, C > 0 && H > 0 && W > 0 && scale > 0, DFE_E_ARG, "%s: C=%d %dx%d scale=%g", fn, C, H, W, (double)scale);
+    return sgpk_ssd_pair(ctx, fn, nullptr, nullptr, I0, I1, scale, C, H, W, k, hWin, wWin, foe_x, foe_y, P1, P2, paths, subpixel, min_unique, flow, scores, depth,
+                         depth_conf);
+}
+
+int dfe_census_flow_depth_pair_sgm2_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x,
+                                        float foe_y, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *match,
+                                        float *unique, float *depth, float *depth_conf) {
+    DFE_ENTER(ctx);
+    return sgpk_census_pair(ctx, "dfe_census_flow_depth_pair_sgm2_f32", I0, I1, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, P1, P2, paths, subpixel, min_unique,
+                            flow, match, unique, depth, depth_conf);
+}
+
+int dfe_census_flow_depth_pair_sgm2_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, int agg,
+                                       float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow,
+                                       float *match, float *unique, float *depth, float *depth_conf) {
+    DFE_ENTER(ctx);
+    DFE_REQUIRE(ctx, scale > 0, DFE_E_ARG, "dfe_census_flow_depth_pair_sgm2_u8: scale=%g must be positive", (double)scale);
+    return sgpk_census_pair(ctx, "dfe_census_flow_depth_pair_sgm2_u8", I0, I1, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, P1, P2, paths, subpixel, min_unique,
+                            flow, match, unique, depth, depth_conf);
+}
+
+}  // extern "C"

@@ -23,26 +23,6 @@ namespace {
 constexpr int kSgmpMaxCells = 1096;   // the single-scale step's ceiling
 constexpr int kSgmpMaxJ = 18;         // cells a lane at that ceiling
 
-struct SgmpJob {
-    const float *C;      // [H][W][cells]
-    float *L[8];         // [H][W][cells] each: L of the n directions asked for, in ascending bit order
-    int dy[8], dx[8];    // their directions: p's predecessor is p - (dy, dx)
-    int n;
-    int H, W, hWin, wWin, cells;
-    float P1, P2;
-};
-
-struct SgmpOut {
-    float *agg;            // [H][W][cells] or NULL
-    long long *idx;        // [H][W], 1-based; or NULL
-    float *fy, *fx;        // at [(y + pad_t) pitch + x + pad_l]; each or NULL
-    float *match;          // the same positions: 1 - raw(p, idx) / den; or NULL
-    const float *raw;      // the volume the match score reads (match != NULL)
-    float den;
-    int pitch, pad_t, pad_l;
-    int mid0;              // the centre class, 0-based
-};
-
 // the smallest value of the wave in every lane of it (no NaNs: path costs, +Inf in the padding cells): four DPP steps inside each
 // 16-lane row -- the float form of the reductions in dfe_wave.h -- then the four rows' values through scalar registers
 __device__ __forceinline__ float sgmp_wave_min(float v) {
@@ -210,6 +190,9 @@ __global__ __launch_bounds__(256) void sgmp_sum_kernel(const SgmpJob a, const Sg
     }
 }
 
+}  // namespace
+
+// (declared in dfe_internal.h: sgm_pick.hip launches the path kernel through them)
 // planes of H * W * cells floats that sgmp_run takes as `work`: one per direction, unless the only direction goes straight to agg
 size_t sgmp_work_planes(unsigned paths, bool agg_given) {
     const int n = __builtin_popcount(paths & 255u);
@@ -265,6 +248,8 @@ int sgmp_run(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin
     ctx->last_kernel = "sgmp_path_kernel";
     return DFE_OK;
 }
+
+namespace {
 
 // the census one call behind its device guard: T = float or uint8_t
 template <class T>

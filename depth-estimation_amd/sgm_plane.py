@@ -4,6 +4,9 @@ DESIGN section 4.31).
     semiGlobalAggregatePlane(volume, P1, P2, paths=0x0f, want_volume=True)
         dfe_sgm_plane_aggregate_f32: an [H][W][hWin][wWin] cost volume (censusCostVolume's, the SSD volume's, nn.SpatialMatching's)
         summed along 4 or 8 image directions under two label-change penalties; the first minimum with the centre rule and its flow
+    semiGlobalPick(volume, P1=0.0, P2=0.0, paths=0, subpixel=False, min_unique=0.0, want_volume=False)
+        dfe_sgm_plane_pick_f32: the same aggregate (paths=0: the volume as it is) with the best and the second-best far cost, the
+        uniqueness confidence and, with subpixel, the parabola's flow on the aggregate
 """
 import math
 
@@ -42,6 +45,62 @@ def _sgm_arg(sgm, who):
         raise ValueError("%s: sgm=%r: None, (P1, P2) or dict(P1=, P2=, paths=) expected" % (who, sgm))
     P1, P2 = _plane_params(P1, P2, paths, who)
     return P1, P2, paths
+
+
+def _min_unique(v, who):
+    """min_unique of dfe_sgm_plane_pick_f32: a number in [0, 1]"""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v <= 1:
+        raise ValueError("%s: min_unique=%r must be a number in [0, 1]" % (who, v))
+    return float(v)
+
+
+def _sgm_pick_arg(sgm, who):
+    """_sgm_arg for the entries that pick with a confidence: None, or (P1, P2, paths, min_unique, gated) of (P1, P2) or
+    dict(P1=, P2=, paths=0x0f, min_unique=0.0); gated says whether min_unique was named"""
+    if not isinstance(sgm, dict) or "min_unique" not in sgm:
+        got = _sgm_arg(sgm, who)
+        return None if got is None else got + (0.0, False)
+    rest = {key: v for key, v in sgm.items() if key != "min_unique"}
+    mu = _min_unique(sgm["min_unique"], who)
+    return _sgm_arg(rest, who) + (mu, True)
+
+
+def _volume_arg(volume, who):
+    if not isinstance(volume, torch.Tensor) or volume.dim() != 4 or min(volume.shape) < 1:
+        raise ValueError("%s: volume H x W x hWin x wWin expected, got %s" % (who, tuple(getattr(volume, "shape", ())),))
+    H, W, hWin, wWin = volume.shape
+    if hWin * wWin > MAX_CELLS:
+        raise ValueError("%s: window %d x %d has more than %d cells" % (who, hWin, wWin, MAX_CELLS))
+    if H * W > 2 ** 31 - 1:
+        raise ValueError("%s: %d x %d pixels" % (who, H, W))
+    return H, W, hWin, wWin
+
+
+def semiGlobalPick(volume, P1=0.0, P2=0.0, paths=0, subpixel=False, min_unique=0.0, want_volume=False):
+    """Not in the reference: semiGlobalAggregatePlane with what else a caller reads off the aggregate A
+    (include/dfe.h: dfe_sgm_plane_pick_f32).  paths=0 (the default) aggregates nothing: A is the volume, P1 and P2 are checked and ignored.
+    Returns dict(idx, flow_y, flow_x, best, second, unique [H][W], aggregate [H][W][hWin][wWin] or None without want_volume):
+    best = A at the chosen cell; second = the smallest A at Chebyshev distance 2 or more from it, +Inf if there is no such cell;
+    unique = u if u >= min_unique else 0, u = (second - best) / second, 0 where second is +Inf or not above 0 -- u is not clamped, so costs
+    of mixed sign can give more than 1; subpixel=True: flow_y, flow_x move by the per-axis parabola through A (0 on an axis whose
+    neighbour lies outside the window or whose curvature is not positive), else they are semiGlobalAggregatePlane's bits."""
+    who = "semiGlobalPick"
+    H, W, hWin, wWin = _volume_arg(volume, who)
+    none = isinstance(paths, int) and not isinstance(paths, bool) and paths == 0
+    P1, P2 = _plane_params(P1, P2, 1 if none else paths, who)      # (no aggregation: P1 and P2 are checked all the same)
+    mu = _min_unique(min_unique, who)
+    if not volume.is_cuda or volume.dtype != torch.float32:
+        raise TypeError("%s: a float32 CUDA tensor expected" % who)
+    volume = volume.contiguous()
+    ctx = get_ctx(volume)
+    res = {"idx": torch.empty((H, W), dtype=torch.int64, device=volume.device)}
+    for key in ("flow_y", "flow_x", "best", "second", "unique"):
+        res[key] = torch.empty((H, W), dtype=torch.float32, device=volume.device)
+    res["aggregate"] = torch.empty_like(volume) if want_volume else None
+    ctx.check(lib().dfe_sgm_plane_pick_f32(ctx.handle, ptr(volume), H, W, hWin, wWin, P1, P2, paths, int(bool(subpixel)), mu,
+                                           ptr(res["aggregate"]) if want_volume else None, ptr(res["idx"]), ptr(res["flow_y"]), ptr(res["flow_x"]),
+                                           ptr(res["best"]), ptr(res["second"]), ptr(res["unique"])))
+    return res
 
 
 def semiGlobalAggregatePlane(volume, P1, P2, paths=0x0f, want_volume=True):

@@ -1,7 +1,10 @@
 """The single-scale raw-patch step as one call, with its opt-in sub-pixel flow (not in the reference: include/dfe.h).
 
-    flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False, fill=None, median=None)
+    flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False, fill=None, median=None,
+                  sgm=None)
         dfe_flow_depth_pair_f32 / _u8, or their _subpixel_ forms: frames -> flow, extractOutput scores, depth, depth confidence;
+        sgm=(P1, P2): dfe_flow_depth_pair_sgm_f32 / _u8, the SSD cost aggregated along image paths before the arg-min; scores are then the
+        uniqueness of the aggregate and subpixel refines on it
         consistency=tol: dfe_flow_depth_pair_fb_f32 / _u8, both directions and the forward-backward mask
         fill=True: the rejected pixels filled from the kept ones, flow_dense / filled / depth_dense
         median=k or (k, sigma): flow (or flow_dense) through the guided weighted median, flow_median / median_valid / depth_median
@@ -13,6 +16,7 @@ import torch
 from ._lib import lib
 from .context import get_ctx, ptr
 from .fields import fillHoles, weightedMedian
+from .sgm_plane import _sgm_pick_arg
 
 
 def _frames(img1, img2, name):
@@ -74,7 +78,8 @@ def _with_fill(res, fill, median, guide, k, hWin, wWin, fx, fy, region=None):
     return res
 
 
-def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False, fill=None, median=None):
+def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False, scale=1.0, consistency=None, gate=False, fill=None, median=None,
+                  sgm=None):
     """One frame pair through the single-scale step: C x H x W frames (float32, or uint8 read as float(byte) * scale), a k x k patch,
     an hWin x wWin search window, foe = (x, y) focus of expansion.  Returns dict(flow [2][H][W] (y, x), scores, depth, depth_conf [H][W]),
     zero outside the centre-pasted output region.  subpixel=True: the flow is refined to sub-pixel precision and depth follows it;
@@ -88,8 +93,15 @@ def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False
     median=k or (k, sigma): the dict gains flow_median [2][H][W], median_valid [H][W] = weightedMedian(src, wgt, img1 as float32, k, sigma, R)
     and depth_median [H][W], the depth of flow_median made as depth_dense is.  Without fill, src = flow and wgt is the plane above; with
     fill, src = flow_dense and wgt = filled, 0.25 where the pixel was a hole.  sigma is in the frame's own units (bytes for uint8 frames);
-    0, the default, is the unguided median.  Frames of more than 4 channels cannot guide (ValueError).  The other keys are unchanged."""
+    0, the default, is the unguided median.  Frames of more than 4 channels cannot guide (ValueError).  The other keys are unchanged.
+    sgm: None, (P1, P2) or dict(P1=, P2=, paths=0x0f, min_unique=0.0) -- the whole SSD volume goes through
+    semiGlobalPick before the arg-min (dfe_flow_depth_pair_sgm_f32 / _u8).  scores is then the uniqueness of the aggregate, (second - best) /
+    second gated by min_unique, and threshold is ignored; subpixel=True refines on the aggregate, not on the raw costs.  fill and median work
+    unchanged, through scores > 0.  consistency= together with sgm= raises ValueError.  None leaves every bit and every launch as it is."""
     median = _median_arg(median)
+    sgm = _sgm_pick_arg(sgm, "flowDepthPair")
+    if sgm is not None and consistency is not None:
+        raise ValueError("flowDepthPair: consistency= together with sgm= is not available")
     a, b = _frames(img1, img2, "flowDepthPair")
     C, H, W = a.shape
     flow = torch.empty((2, H, W), dtype=torch.float32, device=a.device)
@@ -99,6 +111,15 @@ def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False
     ctx = get_ctx(a)
     fx, fy = float(foe[0]), float(foe[1])
     l = lib()
+    if sgm is not None:
+        P1, P2, paths, min_unique, _ = sgm
+        tail = (P1, P2, paths, int(bool(subpixel)), min_unique, ptr(flow), ptr(scores), ptr(depth), ptr(conf))
+        if a.dtype == torch.uint8:
+            rc = l.dfe_flow_depth_pair_sgm_u8(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, float(scale), *tail)
+        else:
+            rc = l.dfe_flow_depth_pair_sgm_f32(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, *tail)
+        ctx.check(rc)
+        return _with_fill({"flow": flow, "scores": scores, "depth": depth, "depth_conf": conf}, fill, median, a, k, hWin, wWin, fx, fy)
     if consistency is not None:
         bw = torch.empty_like(flow)
         mask = torch.empty_like(scores)

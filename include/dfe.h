@@ -381,6 +381,55 @@ int dfe_census_flow_depth_pair_sgm_u8(dfe_ctx *ctx, const uint8_t *I0, const uin
                                       int agg, float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths, float *flow,
                                       float *match, float *depth, float *depth_conf);
 
+/* ---- what is read off the aggregate besides its arg-min: a uniqueness confidence and a sub-pixel flow (NOT in the reference; DESIGN
+ * section 4.32) ---------------------------------------------------------------------------------------------------------------------- */
+/* volume, H, W, hWin, wWin, P1, P2, paths, agg, idx: dfe_sgm_plane_aggregate_f32's.  paths == 0 is also accepted here and means no
+ * aggregation: A = volume, no path launch, P1 and P2 ignored but still checked -- uniqueness and the sub-pixel rule then serve any
+ * winner-takes-all volume.  flow_y, flow_x, best, second, unique: [H][W] floats, each or NULL; at least one output must be given.
+ * A is the aggregate exactly as dfe_sgm_plane_aggregate_f32 sums it and (r, s) the cell it picks, centre rule included.  Every
+ * operation is fp32, rounded on its own, not contracted:
+ *   best   = A(r, s).
+ *   second = the smallest A(r', s') over the cells with max(|r' - r|, |s' - s|) >= 2; +Inf if the window has no such cell.  (The
+ *     winner's 3 x 3 neighbourhood is left out because a true minimum drags its neighbours down with it.)
+ *   u      = (second == +Inf || !(second > 0)) ? 0 : (second - best) / second: one rounded subtraction, one IEEE division.  u is NOT
+ *     clamped: with costs of mixed sign (second > 0 > best) it exceeds 1.  unique = u >= min_unique ? u : 0, min_unique in [0, 1]
+ *     (else DFE_E_ARG).  idx and the flow are written whatever the gate says.
+ *   subpixel != 0: the per-axis parabola of dfe_flow_refine_subpixel_f32 with cost := A (x shown; y alike with r -+ 1):
+ *     c0 = A(r, s), cm = A(r, s-1), cp = A(r, s+1); off = 0 if s-1 < 0 or s+1 >= wWin; else den = (cm - c0) + (cp - c0),
+ *     off = den > 0 ? clamp((cm - cp) / (2 den), -0.5, 0.5) : 0;  flow_x = (float)dx + off_x, flow_y = (float)dy + off_y.
+ *   subpixel == 0: flow_y, flow_x have the bits of dfe_sgm_plane_aggregate_f32's; idx and agg have them always, for every non-zero paths.
+ * Errors: dfe_sgm_plane_aggregate_f32's, with paths in 0 .. 255.  Refused before any launch.
+ * The path launch is dfe_sgm_plane_aggregate_f32's; then a wave a pixel sums the planes in order, keeps the sums in LDS, takes the
+ * first minimum and, in a second reduction over the sums it has kept, the far minimum; the parabola reads the same sums.  With
+ * agg == NULL the aggregate is never stored.  Asynchronous on the ctx's stream; runs under DFE_STAGE_MATCH. */
+int dfe_sgm_plane_pick_f32(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths,
+                           int subpixel, float min_unique, float *agg, int64_t *idx, float *flow_y, float *flow_x, float *best,
+                           float *second, float *unique);
+/* The single-scale SSD step with the aggregation between the cost and the arg-min: the arguments of dfe_flow_depth_pair_f32 / _u8
+ * without extract_threshold, plus P1, P2, paths (1 .. 255), subpixel, min_unique (dfe_sgm_plane_pick_f32's, on the Ho x Wo plane).
+ * Order of work: the WHOLE SSD volume (dfe_ssd_cost_volume_f32) into the ctx's scratch arena -- no row bands, the vertical paths need
+ * every row; an arena that cannot be had returns the arena's own error --, the aggregation with no aggregate stored, the pick storing
+ * at the pasted positions: flow [2][H][W] (y, x), scores [H][W] = unique; then the border and depth pass of the single-scale step
+ * (depth / depth_conf both or neither).  The byte entry converts with float(byte) * scale, as dfe_flow_depth_pair_u8 does.  Every
+ * argument is refused before any launch, with the codes of the entries it joins.  Bit-identical to the staged public calls plus the
+ * paste. */
+int dfe_flow_depth_pair_sgm_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin,
+                                float foe_x, float foe_y, float P1, float P2, unsigned paths, int subpixel, float min_unique,
+                                float *flow, float *scores, float *depth, float *depth_conf);
+int dfe_flow_depth_pair_sgm_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin,
+                               float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths, int subpixel,
+                               float min_unique, float *flow, float *scores, float *depth, float *depth_conf);
+/* dfe_census_flow_depth_pair_sgm_* with subpixel and min_unique (dfe_sgm_plane_pick_f32's) and one more output: unique [H][W] or NULL,
+ * the uniqueness of the AGGREGATE at the pasted positions, 0 elsewhere.  match keeps its meaning (the raw cost at the chosen class).
+ * With subpixel == 0 and unique == NULL every output has the bits of dfe_census_flow_depth_pair_sgm_*'s. */
+int dfe_census_flow_depth_pair_sgm2_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin,
+                                        int agg, float foe_x, float foe_y, float P1, float P2, unsigned paths, int subpixel,
+                                        float min_unique, float *flow, float *match, float *unique, float *depth, float *depth_conf);
+int dfe_census_flow_depth_pair_sgm2_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin,
+                                       int wWin, int agg, float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths,
+                                       int subpixel, float min_unique, float *flow, float *match, float *unique, float *depth,
+                                       float *depth_conf);
+
 /* ---- N2: gradients of the two matchers (training drivers call model:backward through them) ------- */
 /* replaces: nn.SpatialMatching:updateGradInput / nn.SpatialRadialMatching:updateGradInput (un-vendored nnx), reached
  *   from radial/train_radial_opticalflow.lua:228-252 and opticalflow.lua:296-338.  gradOut has the forward output's
