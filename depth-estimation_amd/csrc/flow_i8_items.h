@@ -6,7 +6,8 @@
 // device holds `slots` waves at once, so a grid runs in rounds of `slots` items and a round that is nearly empty costs a whole one:
 // 1080p is 61478 two-row items, 20.01 rounds of 3072.  The plan keeps the whole rounds of two-row items (n2 of them) and gives the rows behind
 // them, in the same order, to one-row items where the model says that the step ends sooner: a one-row item runs the same 33 steps with
-// half the MFMAs and the same loads, kI8OneRowCost of a two-row item's time (0.61 measured at VGA: EXPERIMENTS.md, round 9).  A grid below one
+// 12 MFMAs per step against a two-row item's 15 (the two rows share the products of six image rows) and the same loads, kI8OneRowCost of
+// a two-row item's time (0.61 measured at VGA when a two-row step still took 24 MFMAs: EXPERIMENTS.md, rounds 9 and 13).  A grid below one
 // round of two-row items becomes one-row items for the same reason: twice the waves, each about half as long.
 #pragma once
 

@@ -14,8 +14,20 @@
 // fragment of image rows (r .. r+3) at displacement row dy is the fragment of rows (r-1 .. r+2) at dy + 1: the four fragments of a tile
 // rotate through registers (the sweep runs in rounds of four steps) and every step loads ONE new 16-byte piece per lane and tile, into the
 // registers of the oldest fragment, right after the step's MFMAs that read it: after a round every fragment is back where it started and
-// nothing is copied.  With R = 2 the same frame-1 fragments serve (row y, dy) and (row y + 1, dy - 1).  The row addresses are scalar; a
-// lane adds one 64-bit base per frame-1 row and per plane row, made once per item.
+// nothing is copied.  The row addresses are scalar; a lane adds one 64-bit base per frame-1 row and per plane row, made once per item.
+//
+// Two rows per item (R = 2).  At step s the fragments F_t = frame-1 rows (y0 + s + t | y0 + s + t + 3) serve row y0 at dy = s and row
+// y0 + 1 at dy = s - 1, which also share the S1-plane row y0 + s.  Both compare frame-0 image rows y0 + 17 .. y0 + 22 with the same six
+// frame-1 rows, one step apart: the product of frame-0 row Z with frame-1 row Z - 16 + dy is patch row Z - y0 - 16 of row y0 and patch
+// row Z - y0 - 17 of row y0 + 1.  So a step forms, per tile,
+//     C(s) = F_1.B[1] + F_2.B[2] + F_3.B[3]     (3 MFMAs)    B[t] = frame-0 rows (y0 + 16 + t | y0 + 19 + t), row y0's operands
+//     D0   = C(s) + F_0.B[0]                    (1 MFMA)     row y0, dy = s: its patch row 0 (the duplicate row 3 of B[0] is zero)
+//     D1   = C(s - 1) + F_3.Bbot                (1 MFMA)     row y0 + 1, dy = s - 1: its patch row 6, Bbot = (zero | frame-0 row y0 + 23)
+// 15 MFMAs per step against the 12 of a one-row item (two independent chains of four would be 24).  C(s - 1) is carried in 12 registers;
+// the round of four steps makes that a renaming, like the fragments.  Step 0 has no D1, step 33 nothing else.  D0's MFMA is the last to
+// read F_0, so the step's load goes into F_0's registers behind it: issuing F_0's product first into an accumulator of its own and
+// adding it to C with vector instructions keeps the load early but costs 4 v_add per tile, 24 v_mov_b64 on the back edge and 163 VGPRs
+// (288 vector instructions per four steps against 216; not shipped).
 //
 // Arg-min.  A lane keeps two running keys (i = 0, 1 and i = 2, 3): key = ((2 a'.b' - S1) << 8) + tiebreak, maximised; the plane cell of
 // frame-1 row y1, column q holds -(S1 << 8) + (1 - (q & 1)) - 6 y1 - 2 (q >> 4), so a key is ONE v_lshl_add of the MFMA result and nothing
@@ -27,7 +39,7 @@
 // (H + 1) Wp < 2^29 with Wp >= 80, so 6 y1 + 2 (q >> 4) < 6 * 2^29 / 80 + 2^29 / (40 * 8) < 4.2e7: every key, and base + 255 added
 // to one, stays inside 32 bits.  Candidates outside 0 <= q - n <= 32 (first and third tile) are masked by lane masks that live in
 // scalar registers.  Per tile that is 4 v_lshl_add_u32 and 2 v_max3_i32, and 4 v_cndmask_b32 in a masked tile (i8_max3 keeps the compiler
-// from selecting after each max: 8 in place of 6); with the two row addresses a two-row step issues 54 vector instructions beside its 24
+// from selecting after each max: 8 in place of 6); with the two row addresses a two-row step issues 54 vector instructions beside its 15
 // MFMAs, a one-row step 28 beside 12.  The four lane groups of a pixel are combined once, on (cost, index).
 //
 // Items.  flow_i8_items.h splits the rows into two-row and one-row wave items from the number of waves the device holds at once.
@@ -172,7 +184,8 @@ template <int R, bool FB> struct I8Sweep {
     static constexpr int NS = 33 + R - 1;
     const I8Args &a;
     const int lane, n, g, x0, y0;
-    i8x16_t A[3][4], B[R][4];
+    i8x16_t A[3][4], B[4];
+    i8x16_t Bbot, C[3];    // R == 2: frame-0 row y0 + 23 (row y0 + 1's own patch row) and the shared rows' products of the step before
     int best[R][2];
     int sa[R];
     unsigned lo1, lop;     // the lane's byte offsets inside a row of the packed frame 1 and of the S1 plane
@@ -193,17 +206,21 @@ template <int R, bool FB> struct I8Sweep {
             in0[i] = 4 * g + i >= n;
             in2[i] = 4 * g + i <= n;
         }
-        // frame 0: patch rows (0..3 | 3..6) of pixel n, zero in the duplicate row 3 and in the eighth pixel
+        // frame 0: patch rows (0..3 | 3..6) of row y0's pixel n, zero in the duplicate row 3 and in the eighth pixel.  R == 2: image rows
+        // y0 + 17 .. y0 + 22 of these are row y0 + 1's patch rows 0..5 as well; its patch row 6, image row y0 + 23, is Bbot's upper half
 #pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const unsigned *p = a.pk0 + (y0 + r + 16 + t + 3 * up) * a.Wp + x0 + n + 16 + 4 * h;
-                i8x16_t v = *reinterpret_cast<const i8x16_t *>(p);
-                if (h) v[3] = 0;
-                if (up && t == 0) v = i8x16_t{0, 0, 0, 0};
-                B[r][t] = v;
-            }
+        for (int t = 0; t < 4; ++t) {
+            const unsigned *p = a.pk0 + (y0 + 16 + t + 3 * up) * a.Wp + x0 + n + 16 + 4 * h;
+            i8x16_t v = *reinterpret_cast<const i8x16_t *>(p);
+            if (h) v[3] = 0;
+            if (up && t == 0) v = i8x16_t{0, 0, 0, 0};
+            B[t] = v;
+        }
+        if constexpr (R == 2) {
+            Bbot = *reinterpret_cast<const i8x16_t *>(a.pk0 + (y0 + 23) * a.Wp + x0 + n + 16 + 4 * h);
+            if (h) Bbot[3] = 0;
+            if (!up) Bbot = i8x16_t{0, 0, 0, 0};
+        }
         // frame 1: the fragments of displacement row 0.  A lane's byte offset from (row, x0) is the same for the whole item: fragment rows
         // (+ 0 | + 3 rows, pixel n + 4 h) and plane cells (4 g); at most 4 (3 Wp + 19) < 2^32 as (H + 1) Wp < 2^29, the tile's 64 T an immediate
         lo1 = 4u * (unsigned)(3 * up * a.Wp + n + 4 * h);
@@ -213,6 +230,29 @@ template <int R, bool FB> struct I8Sweep {
             const char *frow = reinterpret_cast<const char *>(a.pk1 + (y0 + t) * a.Wp + x0);
 #pragma unroll
             for (int T = 0; T < 3; ++T) A[T][t] = *reinterpret_cast<const i8x16_t *>(frow + lo1 + 64 * T);
+        }
+    }
+
+    // the keys of one result tile D of row y0 + r, and the row's lead cells (sr == 0) and centre cell (sr == 16) where the step is the peeled
+    // one that holds them: sr is the row's displacement row there, anything else in the steady state
+    __device__ __forceinline__ void take(int T, int r, int sr, const i8x16_t &D, const i8x16_t &P, int pb) {
+        int k[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            k[i] = (int)((unsigned)D[i] << 9) + P[i];
+            if (T == 0) k[i] = in0[i] ? k[i] : INT_MIN;
+            if (T == 2) k[i] = in2[i] ? k[i] : INT_MIN;
+        }
+        best[r][0] = i8_max3(best[r][0], k[0], k[1]);
+        best[r][1] = i8_max3(best[r][1], k[2], k[3]);
+        if (T < 2 && sr == 0) {   // the lead cells' row
+#pragma unroll
+            for (int i = 0; i < 4; ++i) lds->cost[r][n][16 * T + 4 * g + i] = (float)(sa[r] - ((P[i] + pb + 2 * T) >> 8) - 2 * D[i]);
+        }
+        if (T == 1 && sr == 16) {   // the centre cell: dx = 16, q = 16 + n
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (4 * g + i == n) lds->cen[r][n] = (float)(sa[r] - ((P[i] + pb + 2 * T) >> 8) - 2 * D[i]);
         }
     }
 
@@ -232,50 +272,39 @@ template <int R, bool FB> struct I8Sweep {
         for (int T = 0; T < 3; ++T) P[T] = *reinterpret_cast<const i8x16_t *>(prow + lop + 64 * T);
 #pragma unroll
         for (int T = 0; T < 3; ++T) {
-            i8x16_t D[R];
-            bool on[R];
+            if constexpr (R == 2) {
+                // Row y0 at dy = s and row y0 + 1 at dy = s - 1 compare frame-0 rows y0 + 17 .. y0 + 22 with the same six frame-1 rows, a
+                // step apart: C, the three MFMAs of fragments 1..3, is row y0's patch rows 1..6 now and row y0 + 1's patch rows 0..5 at the
+                // next step.  Each row adds the one patch row of its own: 5 MFMAs where two chains of four stood.  Step 0 has no row y0 + 1
+                // yet, step 33 nothing but its last patch row; C passes from step to step through the round's renaming, like the fragments
+                constexpr bool first = S == 0, last = S == NS - 1;
+                i8x16_t D0, D1;
+                if (!first) D1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][(3 + PH) & 3], Bbot, C[T], 0, 0, 0);
+                if (!last) {
+                    i8x16_t c{0, 0, 0, 0};
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                on[r] = FB || S < 0 || (unsigned)(S - r) <= 32u;
-                D[r] = i8x16_t{0, 0, 0, 0};
-                if (on[r]) D[r] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][PH & 3], B[r][0], D[r], 0, 0, 0);
-            }
-            // the fragment of the oldest row has been read by the step's last MFMA that needs it: the new row is loaded into its registers, a
-            // renaming and no copy.  The barrier keeps the scheduler from hoisting the load above those MFMAs, which costs spare fragments
-            // (18 VGPRs more with R = 2, 28 with R = 1) and measured slower
-            if (more) {
-                __builtin_amdgcn_sched_barrier(0);
-                A[T][PH & 3] = *reinterpret_cast<const i8x16_t *>(frow + lo1 + 64 * T);
-            }
+                    for (int t = 1; t < 4; ++t) c = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][(t + PH) & 3], B[t], c, 0, 0, 0);
+                    C[T] = c;
+                    D0 = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][PH & 3], B[0], c, 0, 0, 0);
+                    // D0's MFMA was the last reader of the oldest fragment: the new row is loaded into its registers, as in the one-row step
+                    __builtin_amdgcn_sched_barrier(0);
+                    A[T][PH & 3] = *reinterpret_cast<const i8x16_t *>(frow + lo1 + 64 * T);
+                    take(T, 0, S, D0, P[T], pb);
+                }
+                if (!first) take(T, 1, S - 1, D1, P[T], pb);
+            } else {
+                i8x16_t D = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][PH & 3], B[0], i8x16_t{0, 0, 0, 0}, 0, 0, 0);
+                // the fragment of the oldest row has been read by the step's last MFMA that needs it: the new row is loaded into its registers, a
+                // renaming and no copy.  The barrier keeps the scheduler from hoisting the load above those MFMAs, which costs spare fragments
+                // (18 VGPRs more with R = 2, 28 with R = 1) and measured slower
+                if (more) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    A[T][PH & 3] = *reinterpret_cast<const i8x16_t *>(frow + lo1 + 64 * T);
+                }
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (!on[r]) continue;
-#pragma unroll
-                for (int t = 1; t < 4; ++t) D[r] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][(t + PH) & 3], B[r][t], D[r], 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (!on[r]) continue;
-                const int dy = s - r;
+                for (int t = 1; t < 4; ++t) D = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][(t + PH) & 3], B[t], D, 0, 0, 0);
                 if constexpr (!FB) {
-                    int k[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        k[i] = (int)((unsigned)D[r][i] << 9) + P[T][i];
-                        if (T == 0) k[i] = in0[i] ? k[i] : INT_MIN;
-                        if (T == 2) k[i] = in2[i] ? k[i] : INT_MIN;
-                    }
-                    best[r][0] = i8_max3(best[r][0], k[0], k[1]);
-                    best[r][1] = i8_max3(best[r][1], k[2], k[3]);
-                    if (T < 2 && S - r == 0) {   // the lead cells' row
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) lds->cost[r][n][16 * T + 4 * g + i] = (float)(sa[r] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[r][i]);
-                    }
-                    if (T == 1 && S - r == 16) {   // the centre cell: dx = 16, q = 16 + n
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            if (4 * g + i == n) lds->cen[r][n] = (float)(sa[r] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[r][i]);
-                    }
+                    take(T, 0, S, D, P[T], pb);
                 } else {
                     // rank this tile's hits of every flagged pixel in candidate order: lane groups below mine, then my own earlier ones
                     bool hit[4];
@@ -284,7 +313,7 @@ template <int R, bool FB> struct I8Sweep {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int m = 4 * g + i;
-                        cv[i] = (float)(sa[0] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[r][i]);
+                        cv[i] = (float)(sa[0] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[i]);
                         bool valid = flagged;
                         if (T == 0) valid = valid && m >= n;
                         if (T == 2) valid = valid && m <= n;
@@ -304,7 +333,7 @@ template <int R, bool FB> struct I8Sweep {
                         if (hit[i]) {
                             if (k < a.M) {
                                 fbp[2 * k] = cv[i];
-                                fbp[2 * k + 1] = (float)(dy * 33 + 16 * T + 4 * g + i - n + 1);
+                                fbp[2 * k + 1] = (float)(s * 33 + 16 * T + 4 * g + i - n + 1);
                             }
                             ++k;
                         }
