@@ -17,10 +17,8 @@ import torch
 from ._lib import lib
 from .context import get_ctx, ptr
 from .fields import _on_device, flowConsistency
-from .sgm_plane import _sgm_pick_arg
+from .sgm_plane import MAX_CELLS, _sgm_pick_arg
 from .subpixel import _frames, _median_arg, _with_fill
-
-MAX_CELLS = 1096   # window cells: the single-scale step's own ceiling
 
 
 def _patch(k, name):
@@ -114,31 +112,22 @@ def _pair(a, b, k, hWin, wWin, agg, fx, fy, scale, sgm=None, subpixel=False):
     depth = torch.empty_like(match)
     conf = torch.empty_like(match)
     ctx = get_ctx(a)
+    res = {"flow": flow, "scores": match}
+    # the entry: plain, _sgm_ (P1, P2, paths) or, with subpixel or a named min_unique, _sgm2_ (... subpixel, min_unique, and unique behind match)
+    name, mid, outs = "dfe_census_flow_depth_pair_", (), (ptr(flow), ptr(match))
     if sgm is not None and (subpixel or sgm[4]):
-        P1, P2, paths, min_unique, _ = sgm
-        unique = torch.empty_like(match)
-        tail = (P1, P2, paths, int(bool(subpixel)), min_unique, ptr(flow), ptr(match), ptr(unique), ptr(depth), ptr(conf))
-        if a.dtype == torch.uint8:
-            rc = lib().dfe_census_flow_depth_pair_sgm2_u8(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, scale, *tail)
-        else:
-            rc = lib().dfe_census_flow_depth_pair_sgm2_f32(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, *tail)
-        ctx.check(rc)
-        return {"flow": flow, "scores": match, "unique": unique, "depth": depth, "depth_conf": conf}
-    if sgm is not None:
-        P1, P2, paths = sgm[:3]
-        if a.dtype == torch.uint8:
-            rc = lib().dfe_census_flow_depth_pair_sgm_u8(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, scale, P1, P2, paths, ptr(flow),
-                                                         ptr(match), ptr(depth), ptr(conf))
-        else:
-            rc = lib().dfe_census_flow_depth_pair_sgm_f32(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, P1, P2, paths, ptr(flow), ptr(match),
-                                                          ptr(depth), ptr(conf))
-    elif a.dtype == torch.uint8:
-        rc = lib().dfe_census_flow_depth_pair_u8(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, scale, ptr(flow), ptr(match), ptr(depth),
-                                                 ptr(conf))
+        res["unique"] = torch.empty_like(match)
+        name, mid, outs = name + "sgm2_", sgm[:3] + (int(bool(subpixel)), sgm[3]), outs + (ptr(res["unique"]),)
+    elif sgm is not None:
+        name, mid = name + "sgm_", sgm[:3]
+    head = (ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy)
+    if a.dtype == torch.uint8:
+        rc = getattr(lib(), name + "u8")(*head, scale, *mid, *outs, ptr(depth), ptr(conf))
     else:
-        rc = lib().dfe_census_flow_depth_pair_f32(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, agg, fx, fy, ptr(flow), ptr(match), ptr(depth), ptr(conf))
+        rc = getattr(lib(), name + "f32")(*head, *mid, *outs, ptr(depth), ptr(conf))
     ctx.check(rc)
-    return {"flow": flow, "scores": match, "depth": depth, "depth_conf": conf}
+    res.update(depth=depth, depth_conf=conf)
+    return res
 
 
 def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consistency=None, gate=False, fill=None, median=None, sgm=None,

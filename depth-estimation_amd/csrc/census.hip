@@ -28,7 +28,6 @@ constexpr int kNW = 4;                        // waves of a workgroup of the swe
 constexpr int kPitch = 128;                   // signatures of an LDS row of the sweep (a constant: a lane's row offsets are immediates)
 constexpr int kSweepLds = 40 * 1024;          // bytes of LDS a workgroup of the sweep stages into at most: four workgroups a CU
 constexpr int census_ty(int C) { return C <= 2 ? 8 : 4; }   // output rows of a workgroup (fewer where the channels fill the registers)
-constexpr int kMaxCells = 1096;               // window cells: the flow step's ceiling (and class ids fit the key's 11 bits)
 
 template <class T>
 __global__ __launch_bounds__(256) void census_transform_kernel(const T *__restrict__ I, int H, int W, int kh, int kw, int Hp, int Wp,
@@ -234,7 +233,8 @@ int census_geom(dfe_ctx *ctx, const char *fn, int C, int Hp, int Wp, int hWin, i
     DFE_REQUIRE(ctx, C >= 1 && C <= 4, DFE_E_ARG, "%s: C=%d channels (1 .. 4)", fn, C);
     DFE_REQUIRE(ctx, agg == 1 || agg == 3 || agg == 5, DFE_E_ARG, "%s: agg=%d must be 1, 3 or 5", fn, agg);
     DFE_REQUIRE(ctx, hWin >= 1 && wWin >= 1, DFE_E_ARG, "%s: window %dx%d", fn, hWin, wWin);
-    DFE_REQUIRE(ctx, (long long)hWin * wWin <= kMaxCells, DFE_E_UNSUPPORTED, "%s: window %dx%d has more than %d cells", fn, hWin, wWin, kMaxCells);
+    DFE_REQUIRE(ctx, (long long)hWin * wWin <= kDfeMaxWindowCells, DFE_E_UNSUPPORTED, "%s: window %dx%d has more than %d cells", fn, hWin, wWin,
+                kDfeMaxWindowCells);
     DFE_REQUIRE(ctx, Hp >= 1 && Wp >= 1 && Hp <= 32768 && Wp <= 32768, DFE_E_SHAPE, "%s: %dx%d patch positions (1 .. 32768 each)", fn, Hp, Wp);
     g->C = C; g->Hp = Hp; g->Wp = Wp; g->hWin = hWin; g->wWin = wWin; g->agg = agg;
     g->Ha = Hp - hWin + 1 - agg + 1;
@@ -315,18 +315,46 @@ int census_sweep_run(dfe_ctx *ctx, const CensusGeom &g, int nbits, int64_t *idx,
     return DFE_OK;
 }
 
-// the one call behind its device guard: T = float or uint8_t (the bytes compare as they are, whatever the scale)
-template <class T>
-int census_pair(dfe_ctx *ctx, const char *fn, const T *I0, const T *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y,
-                float *flow, float *match, float *depth, float *depth_conf) {
-    DFE_REQUIRE(ctx, I0 && I1 && flow && match, DFE_E_ARG, "%s: NULL tensor", fn);
-    DFE_REQUIRE(ctx, (depth == nullptr) == (depth_conf == nullptr), DFE_E_ARG, "%s: depth and depth_conf go together", fn);
+}  // namespace
+
+// (declared in dfe_internal.h: the one calls of sgm_pick.hip start with the same two steps)
+int dfe_census_pair_check(dfe_ctx *ctx, const char *fn, bool tensors, bool depth_pair, int C, int H, int W, int k, int hWin, int wWin, int agg, DfeCensusPair *p) {
+    DFE_REQUIRE(ctx, tensors, DFE_E_ARG, "%s: NULL tensor", fn);
+    DFE_REQUIRE(ctx, depth_pair, DFE_E_ARG, "%s: depth and depth_conf go together", fn);
     int rc = census_kernel_check(ctx, fn, k, k);
     if (rc) return rc;
     DFE_REQUIRE(ctx, H >= 1 && W >= 1 && H <= 32768 && W <= 32768, DFE_E_SHAPE, "%s: frame %dx%d (1 .. 32768 each)", fn, H, W);
     DFE_REQUIRE(ctx, H >= k && W >= k, DFE_E_SHAPE, "%s: frame %dx%d too small for a %dx%d patch", fn, H, W, k, k);
     CensusGeom g{};
     rc = census_geom(ctx, fn, C, H - k + 1, W - k + 1, hWin, wWin, agg, &g);
+    if (rc) return rc;
+    *p = {g.Hp, g.Wp, g.Ha, g.Wa, (H - g.Ha) / 2, (W - g.Wa) / 2};   // (the paste: the rule of flow_step.hip)
+    return DFE_OK;
+}
+
+// (the bytes compare as they are, whatever the scale)
+int dfe_census_pair_transforms(dfe_ctx *ctx, const void *I0, const void *I1, bool bytes, int C, int H, int W, int k, uint64_t *sig0, uint64_t *sig1) {
+    DfeStageScope st(ctx, DFE_STAGE_FILTER);
+    const void *I[2] = {I0, I1};
+    uint64_t *sig[2] = {sig0, sig1};
+    for (int f = 0; f < 2; ++f) {
+        const int rc = bytes ? census_transform_run(ctx, (const uint8_t *)I[f], C, H, W, k, k, (u64 *)sig[f])
+                             : census_transform_run(ctx, (const float *)I[f], C, H, W, k, k, (u64 *)sig[f]);
+        if (rc) return rc;
+    }
+    return DFE_OK;
+}
+
+namespace {
+
+// the one call behind its device guard
+int census_pair(dfe_ctx *ctx, const char *fn, const void *I0, const void *I1, bool bytes, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x,
+                float foe_y, float *flow, float *match, float *depth, float *depth_conf) {
+    DfeCensusPair p;
+    int rc = dfe_census_pair_check(ctx, fn, I0 && I1 && flow && match, (depth == nullptr) == (depth_conf == nullptr), C, H, W, k, hWin, wWin, agg, &p);
+    if (rc) return rc;
+    CensusGeom g{};
+    rc = census_geom(ctx, fn, C, p.Hp, p.Wp, hWin, wWin, agg, &g);   // (checked above: the sweep's form of it)
     if (rc) return rc;
     u64 *sig0 = nullptr, *sig1 = nullptr;
     const size_t n = (size_t)C * g.Hp * g.Wp;
@@ -336,22 +364,15 @@ int census_pair(dfe_ctx *ctx, const char *fn, const T *I0, const T *I1, int C, i
     });
     if (rc) return rc;
     g.s0 = sig0; g.s1 = sig1;
-    {
-        DfeStageScope st(ctx, DFE_STAGE_FILTER);
-        rc = census_transform_run(ctx, I0, C, H, W, k, k, sig0);
-        if (rc) return rc;
-        rc = census_transform_run(ctx, I1, C, H, W, k, k, sig1);
-        if (rc) return rc;
-    }
-    const int pad_t = (H - g.Ha) / 2, pad_l = (W - g.Wa) / 2;   // the rule of flow_step.hip
-    const long long HW = (long long)H * W;
+    rc = dfe_census_pair_transforms(ctx, I0, I1, bytes, C, H, W, k, (uint64_t *)sig0, (uint64_t *)sig1);
+    if (rc) return rc;
     {
         DfeStageScope st(ctx, DFE_STAGE_MATCH);
-        rc = census_sweep_run(ctx, g, k * k - 1, nullptr, nullptr, match, flow, flow + HW, W, pad_t, pad_l);
+        rc = census_sweep_run(ctx, g, k * k - 1, nullptr, nullptr, match, flow, flow + (long long)H * W, W, p.pad_t, p.pad_l);
         if (rc) return rc;
     }
     DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
-    return dfe_pair_border_depth(ctx, flow, match, H, W, pad_t, pad_l, g.Ha, g.Wa, foe_x, foe_y, depth, depth_conf);
+    return dfe_pair_border_depth(ctx, flow, match, H, W, p.pad_t, p.pad_l, g.Ha, g.Wa, foe_x, foe_y, depth, depth_conf);
 }
 
 }  // namespace
@@ -400,14 +421,14 @@ int dfe_census_flow_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1
 int dfe_census_flow_depth_pair_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x,
                                    float foe_y, float *flow, float *match, float *depth, float *depth_conf) {
     DFE_ENTER(ctx);
-    return census_pair(ctx, "dfe_census_flow_depth_pair_f32", I0, I1, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, flow, match, depth, depth_conf);
+    return census_pair(ctx, "dfe_census_flow_depth_pair_f32", I0, I1, false, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, flow, match, depth, depth_conf);
 }
 
 int dfe_census_flow_depth_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x,
                                   float foe_y, float scale, float *flow, float *match, float *depth, float *depth_conf) {
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, scale > 0, DFE_E_ARG, "dfe_census_flow_depth_pair_u8: scale=%g must be positive", (double)scale);
-    return census_pair(ctx, "dfe_census_flow_depth_pair_u8", I0, I1, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, flow, match, depth, depth_conf);
+    return census_pair(ctx, "dfe_census_flow_depth_pair_u8", I0, I1, true, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, flow, match, depth, depth_conf);
 }
 
 }  // extern "C"

@@ -230,6 +230,8 @@ static inline int dfe_window_lead(int n) { return (n + 1) / 2 - 1; }
 // 1-based class of the centre cell of an hWin x wWin window: getMiddleIndex = yx2x(centered2onebased(0, 0)) (opticalflow_model.lua:12-14,
 // 28-43), yx2xMulti(0, 0) of the pyramid, the centre override of radial/radial_opticalflow_groundtruth.lua:91
 static inline int dfe_window_middle(int hWin, int wWin) { return (wWin + 1) / 2 + wWin * dfe_window_lead(hWin); }
+// window cells the census and the semi-global entries take at the most: the single-scale step's ceiling (class ids fit census.hip's 11-bit key)
+constexpr int kDfeMaxWindowCells = 1096;
 // o = a b and o = m^-1 (false: singular) of row-major 3 x 3 matrices on the host (egomotion.hip, egopose.hip)
 static inline void dfe_mat3_mul(const double *a, const double *b, double *o) {
     for (int i = 0; i < 3; ++i)
@@ -496,32 +498,13 @@ DFE_HIDDEN size_t dfe_sgm_work_planes(unsigned paths, bool agg_given);
 DFE_HIDDEN int dfe_sgm_run(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *work, float *agg,
                            float *flow);
 
-// sgm_plane.hip -- semi-global aggregation of a [H][W][hWin][wWin] volume; sgm_pick.hip launches its path kernel through these
-struct SgmpJob {
-    const float *C;      // [H][W][cells]
-    float *L[8];         // [H][W][cells] each: L of the n directions asked for, in ascending bit order
-    int dy[8], dx[8];    // their directions: p's predecessor is p - (dy, dx)
-    int n;
-    int H, W, hWin, wWin, cells;
-    float P1, P2;
-};
-struct SgmpOut {
-    float *agg;            // [H][W][cells] or NULL
-    long long *idx;        // [H][W], 1-based; or NULL
-    float *fy, *fx;        // at [(y + pad_t) pitch + x + pad_l]; each or NULL
-    float *match;          // the same positions: 1 - raw(p, idx) / den; or NULL
-    const float *raw;      // the volume the match score reads (match != NULL)
-    float den;
-    int pitch, pad_t, pad_l;
-    int mid0;              // the centre class, 0-based
-};
-// dfe_sgm_plane_aggregate_f32's checks of the sizes and parameters (fn: the entry's name for the message)
-DFE_HIDDEN int sgmp_check(dfe_ctx *ctx, const char *fn, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths);
-// planes of H * W * cells floats that sgmp_run takes as `work`: one per direction, unless the only direction goes straight to agg
-DFE_HIDDEN size_t sgmp_work_planes(unsigned paths, bool agg_given);
-// the launches behind the checks: direction k (ascending bit order) into work + k planes, then the sum kernel for whatever `o` asks for
-// (an empty `o`: the path launch alone)
-DFE_HIDDEN int sgmp_run(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, float *work, SgmpOut o);
+// census.hip -- the front end of every census one call (census.hip's own, and the two that aggregate in sgm_pick.hip)
+struct DfeCensusPair { int Hp, Wp, Ha, Wa, pad_t, pad_l; };   // patch positions, the aggregated cost's region, where it is pasted
+// the one call's checks in their order -- tensors / depth_pair: what the entry found of its pointers -- and the geometry behind them
+DFE_HIDDEN int dfe_census_pair_check(dfe_ctx *ctx, const char *fn, bool tensors, bool depth_pair, int C, int H, int W, int k, int hWin, int wWin, int agg,
+                                     DfeCensusPair *g);
+// the two transforms under DFE_STAGE_FILTER: float frames, or bytes, into sig0 and sig1 ([C][Hp][Wp] each)
+DFE_HIDDEN int dfe_census_pair_transforms(dfe_ctx *ctx, const void *I0, const void *I1, bool bytes, int C, int H, int W, int k, uint64_t *sig0, uint64_t *sig1);
 
 // multiscale.hip, multiscale_subpixel.hip
 // the raw-patch pyramid on uint8 frames, converted inside its preparation kernels (f16_scale 0 = fp32 volumes)

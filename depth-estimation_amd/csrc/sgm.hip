@@ -13,12 +13,11 @@
 //       row, the labels across its lanes (LPL = 1: label = lane, D <= 16; LPL = 2: labels 2 lane and 2 lane + 1, D <= 32), the label
 //       axis padded with +Inf cells, which change no bit of a real cell and stay +Inf.  Per step: min_k L by four DPP row steps,
 //       L(d -+ 1) by one row shift each (a lane without a neighbour keeps the +Inf it is given as `old`), six more VALU operations,
-//       nothing through LDS.  The loads of the next kSgmAhead steps are in flight (a chain's addresses are known from its first step).
+//       nothing through LDS.  The loads of the next kSgmAhead steps are in flight (a chain's addresses are known from its first step:
+//       the walk is SgmCursor of sgm_common.h, which sgm_plane.hip's path kernel shares, as it does the row minimum).
 //   sgm_sum_kernel<LPL, FLOW>   agg = ((L_a + L_b) + L_c) + ... in ascending direction order, 16 lanes a pixel as above; the first
 //       minimum over the labels by a row reduction on (value, label); the aggregate is stored only if somebody reads it.
-#include "dfe_internal.h"
-#include <cmath>
-#include <climits>
+#include "sgm_common.h"
 
 namespace {
 
@@ -34,14 +33,6 @@ struct SgmJob {
     float P1, P2;
 };
 
-// the smallest value of a 16-lane DPP row in every lane of it (no NaNs: path costs, +Inf in the padding lanes) -- the float form of the
-// reductions in dfe_wave.h, in their step order
-__device__ __forceinline__ float sgm_row_min(float v) {
-#define DFE_STEP(ctrl) v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, false)))
-    DFE_STEP(0x128); DFE_STEP(0x124); DFE_STEP(0x4E); DFE_STEP(0xB1);   // row_ror:8, row_ror:4, quad_perm [2,3,0,1], [1,0,3,2]
-#undef DFE_STEP
-    return v;
-}
 __device__ __forceinline__ float sgm_row_shr1(float v, float edge) {   // lane j: lane j - 1's v; lane 0 of the row: edge
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x111, 0xf, 0xf, false));
 }
@@ -77,33 +68,20 @@ __global__ __launch_bounds__(64) void sgm_path_kernel(const SgmJob a) {
 
     // the fetch cursor: the pixel of step `fs`, and whether the chain starts (again) there.  Past the last step it stays on the last
     // pixel: the step loop runs whole groups of kSgmAhead steps, and the surplus ones of the last group keep nothing.
-    int fy, fx, fs = 0;
-    bool fstart = true;
-    if (horizontal) {
-        fy = ln;
-        fx = dx > 0 ? (a.W - a.ring) % a.W : (a.ring + a.W - 1) % a.W;
-    } else {
-        fy = dy > 0 ? 0 : a.H - 1;
-        fx = ln;
-    }
+    SgmCursor f(dy, dx, ln, a.H, a.W, a.ring);
+    int fs = 0;
     float cb[kSgmAhead][LPL];
     int pixb[kSgmAhead];
     bool stb[kSgmAhead];
     auto fetch = [&](int slot) {
-        const int pix = fy * a.W + fx;
+        const int pix = f.y * a.W + f.x;
         const long long e = (long long)pix * a.D;
 #pragma unroll
         for (int j = 0; j < LPL; ++j) cb[slot][j] = a.C[e + dc[j]];
         pixb[slot] = pix;
-        stb[slot] = fstart;
+        stb[slot] = f.start;
         ++fs;
-        if (fs < nsteps) {                       // (wave-uniform; integer work only)
-            fy += dy;
-            fx += dx;
-            const bool wrapped = fx < 0 || fx >= a.W;
-            fx = fx < 0 ? a.W - 1 : (fx >= a.W ? 0 : fx);
-            fstart = wrapped && a.ring == 0;
-        }
+        if (fs < nsteps) f.advance(dy, dx, a.W, a.ring);   // (wave-uniform; integer work only)
     };
 #pragma unroll
     for (int u = 0; u < kSgmAhead; ++u) fetch(u);
@@ -190,7 +168,8 @@ __global__ __launch_bounds__(256) void sgm_sum_kernel(const SgmJob a, float *__r
 
 }  // namespace
 
-// planes of H * W * D floats that dfe_sgm_run takes as `work`: one per direction, unless the only direction goes straight to agg
+// planes of H * W * D floats that dfe_sgm_run (and the plane family's jobs) take as `work`: one per direction, unless the only direction
+// goes straight to agg
 size_t dfe_sgm_work_planes(unsigned paths, bool agg_given) {
     const int n = __builtin_popcount(paths & 255u);
     return n == 1 && agg_given ? 0 : (size_t)n;
@@ -200,19 +179,14 @@ size_t dfe_sgm_work_planes(unsigned paths, bool agg_given) {
 // agg [H][W][D] or NULL; flow [H][W] or NULL.
 int dfe_sgm_run(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *work, float *agg,
                 float *flow) {
-    static const int dirs[8][2] = {{0, 1}, {0, -1}, {1, 0}, {-1, 0}, {1, 1}, {-1, -1}, {1, -1}, {-1, 1}};   // (dy, dx) of bit r
     const bool direct = dfe_sgm_work_planes(paths, agg != nullptr) == 0;   // one direction, and its L is the aggregate the caller wants
     SgmJob a{};
     a.C = volume;
     a.H = H; a.W = W; a.D = D;
     a.ring = ring;
     a.P1 = P1; a.P2 = P2;
-    for (int r = 0; r < 8; ++r) {
-        if (!(paths >> r & 1u)) continue;
-        a.L[a.n] = direct ? agg : work + (size_t)a.n * H * W * D;
-        a.dy[a.n] = dirs[r][0]; a.dx[a.n] = dirs[r][1];
-        ++a.n;
-    }
+    a.n = sgm_directions(paths, a.dy, a.dx);
+    for (int k = 0; k < a.n; ++k) a.L[k] = direct ? agg : work + (size_t)k * H * W * D;
     DfeProfScope prof(ctx);
     const dim3 grid((unsigned)dfe_cdiv(H > W ? H : W, 4), (unsigned)a.n);
     if (D <= 16) hipLaunchKernelGGL(sgm_path_kernel<1>, grid, dim3(64), 0, ctx->stream, a);
@@ -234,9 +208,8 @@ int dfe_sgm_run(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1
 int dfe_sgm_check(dfe_ctx *ctx, const char *fn, int H, int W, int D, float P1, float P2, unsigned paths, int ring) {
     DFE_REQUIRE(ctx, H >= 1 && W >= 1 && D >= 1 && (long long)H * W <= INT_MAX, DFE_E_SHAPE, "%s: H=%d W=%d D=%d", fn, H, W, D);
     DFE_REQUIRE(ctx, D <= 32, DFE_E_UNSUPPORTED, "%s: D=%d labels (32 at most)", fn, D);
-    DFE_REQUIRE(ctx, paths >= 1u && paths <= 255u, DFE_E_ARG, "%s: paths=0x%x must be 1 .. 255 (bit r = direction r)", fn, paths);
-    DFE_REQUIRE(ctx, std::isfinite(P1) && std::isfinite(P2) && P1 >= 0.f && P1 <= P2, DFE_E_ARG, "%s: P1=%g P2=%g must be finite with 0 <= P1 <= P2", fn,
-                (double)P1, (double)P2);
+    const int rc = sgm_params_check(ctx, fn, P1, P2, paths);
+    if (rc) return rc;
     DFE_REQUIRE(ctx, ring >= 0 && ring <= W, DFE_E_ARG, "%s: ring=%d must be 0 .. W=%d", fn, ring, W);
     return DFE_OK;
 }

@@ -2,45 +2,24 @@
 // flow taken on the surface that was minimised (NOT in the reference).  The definition -- the far cells, the
 // uniqueness ratio, the per-axis parabola with cost := A -- is in include/dfe.h and restated in numpy in tests/sgm_pick_ref.py; the
 // device is tested against that bit for bit.
-//   sgpk_pick_kernel<SUB>   sgmp_sum_kernel's shape: a wave a pixel, four pixels a block, agg = ((L_a + L_b) + L_c) + ... in ascending
-//       direction order, the first minimum in class order by a wave reduction on (value, class), the centre class winning an exact tie.
+//   sgpk_pick_kernel<SUB>   sgmp_sum_kernel's shape and its steps, the functions of sgm_common.h: a wave a pixel, four pixels a block,
+//       agg = ((L_a + L_b) + L_c) + ... in ascending direction order, the first minimum in class order by a wave reduction on
+//       (value, class), the centre class winning an exact tie.
 //       A lane also leaves each sum in the wave's own LDS row (1096 floats a wave, 17.5 KB a block: the registers, not the LDS, bound
 //       the waves a CU holds), so the second pass -- the smallest sum outside the winner's 3 x 3 neighbourhood -- and the parabola's
 //       four neighbours read A itself: no plane is read twice and no sum is formed twice, so their bits are A's by construction.
-//   The path launch is sgm_plane.hip's, unchanged (sgmp_run with nothing to sum); paths == 0 skips it and A = the volume.
-//   The one calls: dfe_flow_depth_pair_sgm_f32 / _u8 (the SSD step) and dfe_census_flow_depth_pair_sgm2_f32 / _u8.
-#include "dfe_internal.h"
+//   The path launch is sgm_plane.hip's, unchanged (sgmp_launch_paths on sgmp_job's job); paths == 0 skips it and A = the volume.
+//   The one calls: dfe_flow_depth_pair_sgm_f32 / _u8 (the SSD step) and, in ONE body on census.hip's front end, the census entries
+//   dfe_census_flow_depth_pair_sgm_f32 / _u8 (sgmp_run: the plain aggregate) and dfe_census_flow_depth_pair_sgm2_f32 / _u8 (sgpk_run).
+#include "sgm_common.h"
 #include "subpixel_offset.h"   // the parabola's vertex on one axis (include/dfe.h: this order, IEEE division)
-#include <cmath>
-#include <climits>
 
 namespace {
 
-constexpr int kSgpkMaxCells = 1096;   // sgm_plane.hip's ceiling (sgmp_check refuses more)
-
-struct SgpkJob {
-    const float *L[8];   // [H][W][cells] each: the planes to sum, in order (paths == 0: the volume alone)
-    int n;
-    int H, W, hWin, wWin, cells;
-    int mid0;            // the centre class, 0-based
-    float min_unique;
-};
-
-struct SgpkOut {
-    float *agg;            // [H][W][cells] or NULL
-    long long *idx;        // [H][W], 1-based; or NULL
-    // each of the following at [(y + pad_t) pitch + x + pad_l], or NULL
-    float *fy, *fx, *best, *second, *unique;
-    float *match;          // 1 - raw(p, idx) / den (the census one call)
-    const float *raw;      // the volume the match score reads (match != NULL)
-    float den;
-    int pitch, pad_t, pad_l;
-};
-
 template <bool SUB>
-__global__ __launch_bounds__(256) void sgpk_pick_kernel(const SgpkJob a, const SgpkOut o) {
+__global__ __launch_bounds__(256) void sgpk_pick_kernel(const SgmpJob a, const SgmpOut o) {
 #pragma clang fp contract(off)
-    __shared__ float sums[4][kSgpkMaxCells];     // A(p, .) of the wave's pixel
+    __shared__ float sums[4][kDfeMaxWindowCells];   // A(p, .) of the wave's pixel
     const float inf = __builtin_inff();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float *A = sums[wave];
@@ -50,29 +29,11 @@ __global__ __launch_bounds__(256) void sgpk_pick_kernel(const SgpkJob a, const S
     const size_t e = live ? (size_t)px * a.cells : 0;
     float b = inf, cen = inf;
     int bi = INT_MAX;
-    if (live) {
-        for (int c = lane; c < a.cells; c += 64) {
-            float t = a.L[0][e + c];
-            for (int k = 1; k < a.n; ++k) t = t + a.L[k][e + c];
-            if (o.agg) o.agg[e + c] = t;
-            A[c] = t;
-            if (t < b) { b = t; bi = c; }        // (a lane's classes ascend: strict `<` keeps its first minimum)
-            if (c == a.mid0) cen = t;
-        }
-    }
-    // the smallest value, and among equal ones the smallest class; the centre's value to every lane
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const float ob = __shfl_xor(b, d, 64);
-        const int oi = __shfl_xor(bi, d, 64);
-        const bool take = (ob < b) | ((ob == b) & (oi < bi));
-        b = take ? ob : b;
-        bi = take ? oi : bi;
-        cen = fminf(cen, __shfl_xor(cen, d, 64));
-    }
+    if (live) sgmp_lane_sum<true, true>(a, o.agg, e, lane, A, b, bi, cen);
+    sgmp_wave_first_min(b, bi, cen);
     __syncthreads();                             // the wave's sums are in its row
     if (!live) return;
-    if (cen == b || bi >= a.cells) bi = a.mid0;  // the centre wins an exact tie with the best (and a volume that is not finite reads in bounds)
+    bi = sgmp_centre_rule(a, b, bi, cen);
     const int r = bi / a.wWin, s = bi - r * a.wWin;
     // the smallest sum at Chebyshev distance 2 or more from the winner: +Inf if the window has no such cell
     float sec = inf;
@@ -91,15 +52,12 @@ __global__ __launch_bounds__(256) void sgpk_pick_kernel(const SgpkJob a, const S
     }
     if (lane != 0) return;
     const float c0 = A[bi];
-    const int y = (int)(px / a.W), x = (int)(px - (long long)y * a.W);
-    const size_t op = (size_t)(y + o.pad_t) * o.pitch + x + o.pad_l;
-    if (o.idx) o.idx[px] = bi + 1;
-    if (o.match) o.match[op] = 1.0f - o.raw[e + bi] / o.den;
+    const size_t op = sgmp_pasted(a, o, px);
     if (o.best) o.best[op] = c0;
     if (o.second) o.second[op] = sec;
     if (o.unique) {
         const float u = (sec == inf || !(sec > 0.f)) ? 0.f : (sec - c0) / sec;   // (not clamped)
-        o.unique[op] = u >= a.min_unique ? u : 0.f;
+        o.unique[op] = u >= o.min_unique ? u : 0.f;
     }
     float fy = (float)(r - (a.hWin - 1) / 2), fx = (float)(s - (a.wWin - 1) / 2);   // dfe_x2yx
     if constexpr (SUB) {
@@ -110,8 +68,7 @@ __global__ __launch_bounds__(256) void sgpk_pick_kernel(const SgpkJob a, const S
         fy = fy + subpixel_offset(iny, cym, c0, cyp);
         fx = fx + subpixel_offset(inx, cxm, c0, cxp);
     }
-    if (o.fy) o.fy[op] = fy;
-    if (o.fx) o.fx[op] = fx;
+    sgmp_store_winner(o, px, e, op, bi, fy, fx);
 }
 
 // dfe_sgm_plane_pick_f32's parameter rules on top of sgmp_check's (paths == 0 allowed: P1 / P2 are checked all the same)
@@ -122,29 +79,13 @@ int sgpk_check(dfe_ctx *ctx, const char *fn, int H, int W, int hWin, int wWin, f
     return DFE_OK;
 }
 
-// planes of H * W * cells floats that sgpk_run takes as `work`
-size_t sgpk_work_planes(unsigned paths, bool agg_given) { return paths ? sgmp_work_planes(paths, agg_given) : 0; }
-
-// The launches behind the checks: sgm_plane.hip's path kernel (paths != 0), then the pick.  o: where the results go
-int sgpk_run(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, int subpixel, float min_unique,
-             float *work, SgpkOut o) {
-    SgpkJob a{};
-    a.H = H; a.W = W; a.hWin = hWin; a.wWin = wWin; a.cells = hWin * wWin;
-    a.mid0 = dfe_window_middle(hWin, wWin) - 1;
-    a.min_unique = min_unique;
-    if (paths == 0) {
-        a.L[0] = volume;
-        a.n = 1;
-    } else {
-        a.n = __builtin_popcount(paths & 255u);
-        const bool direct = sgmp_work_planes(paths, o.agg != nullptr) == 0;   // one direction, and its L is the aggregate the caller wants
-        SgmpOut so{};
-        so.agg = direct ? o.agg : nullptr;
-        int rc = sgmp_run(ctx, volume, H, W, hWin, wWin, P1, P2, paths, work, so);   // (nothing to sum: the path launch alone)
+// The launches behind the checks: sgm_plane.hip's path kernel (paths != 0), then the pick.  work: dfe_sgm_work_planes(paths, o.agg != NULL)
+// planes; o: where the results go, and min_unique
+int sgpk_run(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, int subpixel, float *work, SgmpOut o) {
+    const SgmpJob a = sgmp_job(volume, H, W, hWin, wWin, P1, P2, paths, work, o.agg);
+    if (paths) {
+        int rc = sgmp_launch_paths(ctx, a);
         if (rc) return rc;
-        const size_t plane = (size_t)H * W * a.cells;
-        for (int k = 0; k < a.n; ++k) a.L[k] = direct ? o.agg : work + (size_t)k * plane;
-        if (direct) o.agg = nullptr;
     }
     DfeProfScope prof(ctx);
     const dim3 grid((unsigned)dfe_cdiv((long long)H * W, 4));
@@ -177,7 +118,7 @@ int sgpk_ssd_pair(dfe_ctx *ctx, const char *fn, const float *I0, const float *I1
     rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
         if (bytes) { f0 = c.take<float>(n); f1 = c.take<float>(n); }
         vol = c.take<float>(plane);
-        work = c.take<float>(sgpk_work_planes(paths, false) * plane);
+        work = c.take<float>(dfe_sgm_work_planes(paths, false) * plane);
     }, /*plain*/ true);
     if (rc) return rc;
     if (bytes) {   // float(byte) * scale, as dfe_flow_depth_pair_u8 converts
@@ -192,77 +133,56 @@ int sgpk_ssd_pair(dfe_ctx *ctx, const char *fn, const float *I0, const float *I1
         DfeStageScope st(ctx, DFE_STAGE_MATCH);
         rc = dfe_ssd_cost_volume_f32(ctx, I0, I1, C, H, W, k, k, hWin, wWin, vol);
         if (rc) return rc;
-        SgpkOut o{};
+        SgmpOut o{};
         o.fy = flow; o.fx = flow + (size_t)H * W;
-        o.unique = scores;
+        o.unique = scores; o.min_unique = min_unique;
         o.pitch = W; o.pad_t = pad_t; o.pad_l = pad_l;
-        rc = sgpk_run(ctx, vol, Ho, Wo, hWin, wWin, P1, P2, paths, subpixel, min_unique, work, o);
+        rc = sgpk_run(ctx, vol, Ho, Wo, hWin, wWin, P1, P2, paths, subpixel, work, o);
         if (rc) return rc;
     }
     DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
     return dfe_pair_border_depth(ctx, flow, scores, H, W, pad_t, pad_l, Ho, Wo, foe_x, foe_y, depth, depth_conf);
 }
 
-// the census one call behind its device guard: T = float or uint8_t
-template <class T>
-int sgpk_census_pair(dfe_ctx *ctx, const char *fn, const T *I0, const T *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y,
-                     float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *match, float *unique, float *depth,
-                     float *depth_conf) {
-    // dfe_census_flow_depth_pair_sgm_*'s checks, in their order, then the pick's: everything is refused before any launch
-    DFE_REQUIRE(ctx, I0 && I1 && flow && match, DFE_E_ARG, "%s: NULL tensor", fn);
-    DFE_REQUIRE(ctx, (depth == nullptr) == (depth_conf == nullptr), DFE_E_ARG, "%s: depth and depth_conf go together", fn);
-    DFE_REQUIRE(ctx, k >= 3 && (k & 1) && k * k <= 64, DFE_E_ARG, "%s: patch %dx%d: odd sides of at least 3 with at most 64 cells expected", fn, k, k);
-    DFE_REQUIRE(ctx, H >= 1 && W >= 1 && H <= 32768 && W <= 32768, DFE_E_SHAPE, "%s: frame %dx%d (1 .. 32768 each)", fn, H, W);
-    DFE_REQUIRE(ctx, H >= k && W >= k, DFE_E_SHAPE, "%s: frame %dx%d too small for a %dx%d patch", fn, H, W, k, k);
-    DFE_REQUIRE(ctx, C >= 1 && C <= 4, DFE_E_ARG, "%s: C=%d channels (1 .. 4)", fn, C);
-    DFE_REQUIRE(ctx, agg == 1 || agg == 3 || agg == 5, DFE_E_ARG, "%s: agg=%d must be 1, 3 or 5", fn, agg);
-    DFE_REQUIRE(ctx, hWin >= 1 && wWin >= 1, DFE_E_ARG, "%s: window %dx%d", fn, hWin, wWin);
-    DFE_REQUIRE(ctx, (long long)hWin * wWin <= kSgpkMaxCells, DFE_E_UNSUPPORTED, "%s: window %dx%d has more than %d cells", fn, hWin, wWin, kSgpkMaxCells);
-    const int Hp = H - k + 1, Wp = W - k + 1;
-    const int Ha = Hp - hWin + 1 - agg + 1, Wa = Wp - wWin + 1 - agg + 1;
-    DFE_REQUIRE(ctx, Ha >= 1 && Wa >= 1, DFE_E_SHAPE, "%s: %dx%d patch positions leave no pixel for a %dx%d window summed over %dx%d", fn, Hp, Wp, hWin, wWin,
-                agg, agg);
-    DFE_REQUIRE(ctx, paths != 0u, DFE_E_ARG, "%s: paths=0x%x must be 1 .. 255 (bit r = direction r)", fn, paths);
-    int rc = sgpk_check(ctx, fn, Ha, Wa, hWin, wWin, P1, P2, paths, min_unique);
+// The census one calls behind their device guard, on census.hip's front end: the staged volume, then the plain aggregate (pick == false:
+// sgmp_run) or the pick (sgpk_run).  Everything is refused before any launch: the census checks, then the aggregation's, then the pick's
+int sgm_census_pair(dfe_ctx *ctx, const char *fn, bool pick, const void *I0, const void *I1, bool bytes, int C, int H, int W, int k, int hWin, int wWin, int agg,
+                    float foe_x, float foe_y, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *match, float *unique,
+                    float *depth, float *depth_conf) {
+    DfeCensusPair g;
+    int rc = dfe_census_pair_check(ctx, fn, I0 && I1 && flow && match, (depth == nullptr) == (depth_conf == nullptr), C, H, W, k, hWin, wWin, agg, &g);
+    if (rc) return rc;
+    if (pick) DFE_REQUIRE(ctx, paths != 0u, DFE_E_ARG, "%s: paths=0x%x must be 1 .. 255 (bit r = direction r)", fn, paths);
+    rc = pick ? sgpk_check(ctx, fn, g.Ha, g.Wa, hWin, wWin, P1, P2, paths, min_unique) : sgmp_check(ctx, fn, g.Ha, g.Wa, hWin, wWin, P1, P2, paths);
     if (rc) return rc;
     uint64_t *sig0 = nullptr, *sig1 = nullptr;
     float *vol = nullptr, *work = nullptr;
-    const size_t n = (size_t)C * Hp * Wp, plane = (size_t)Ha * Wa * hWin * wWin;
+    const size_t n = (size_t)C * g.Hp * g.Wp, plane = (size_t)g.Ha * g.Wa * hWin * wWin;
     rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
         sig0 = c.take<uint64_t>(n);
         sig1 = c.take<uint64_t>(n);
         vol = c.take<float>(plane);
-        work = c.take<float>(sgpk_work_planes(paths, false) * plane);
+        work = c.take<float>(dfe_sgm_work_planes(paths, false) * plane);
     });
     if (rc) return rc;
-    {   // the staged public calls themselves (they carve nothing): the same kernels, the same bits
-        DfeStageScope st(ctx, DFE_STAGE_FILTER);
-        if constexpr (sizeof(T) == 1) {
-            rc = dfe_census_transform_u8(ctx, I0, C, H, W, k, k, sig0);
-            if (!rc) rc = dfe_census_transform_u8(ctx, I1, C, H, W, k, k, sig1);
-        } else {
-            rc = dfe_census_transform_f32(ctx, I0, C, H, W, k, k, sig0);
-            if (!rc) rc = dfe_census_transform_f32(ctx, I1, C, H, W, k, k, sig1);
-        }
-        if (rc) return rc;
-    }
-    const int pad_t = (H - Ha) / 2, pad_l = (W - Wa) / 2;   // the rule of flow_step.hip
+    rc = dfe_census_pair_transforms(ctx, I0, I1, bytes, C, H, W, k, sig0, sig1);
+    if (rc) return rc;
     {
         DfeStageScope st(ctx, DFE_STAGE_MATCH);
-        rc = dfe_census_cost_volume_f32(ctx, sig0, sig1, C, Hp, Wp, hWin, wWin, agg, vol);
+        rc = dfe_census_cost_volume_f32(ctx, sig0, sig1, C, g.Hp, g.Wp, hWin, wWin, agg, vol);   // the staged public call itself: the same kernel, the same bits
         if (rc) return rc;
         if (unique) DFE_HIP(ctx, hipMemsetAsync(unique, 0, (size_t)H * W * sizeof(float), ctx->stream));   // its border: 0, as match's
-        SgpkOut o{};
+        SgmpOut o{};
         o.fy = flow; o.fx = flow + (size_t)H * W;
         o.match = match; o.raw = vol;
         o.den = (float)((k * k - 1) * C * agg * agg);
-        o.unique = unique;
-        o.pitch = W; o.pad_t = pad_t; o.pad_l = pad_l;
-        rc = sgpk_run(ctx, vol, Ha, Wa, hWin, wWin, P1, P2, paths, subpixel, min_unique, work, o);
+        o.unique = unique; o.min_unique = min_unique;
+        o.pitch = W; o.pad_t = g.pad_t; o.pad_l = g.pad_l;
+        rc = pick ? sgpk_run(ctx, vol, g.Ha, g.Wa, hWin, wWin, P1, P2, paths, subpixel, work, o) : sgmp_run(ctx, vol, g.Ha, g.Wa, hWin, wWin, P1, P2, paths, work, o);
         if (rc) return rc;
     }
     DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
-    return dfe_pair_border_depth(ctx, flow, match, H, W, pad_t, pad_l, Ha, Wa, foe_x, foe_y, depth, depth_conf);
+    return dfe_pair_border_depth(ctx, flow, match, H, W, g.pad_t, g.pad_l, g.Ha, g.Wa, foe_x, foe_y, depth, depth_conf);
 }
 
 }  // namespace
@@ -279,15 +199,15 @@ int dfe_sgm_plane_pick_f32(dfe_ctx *ctx, const float *volume, int H, int W, int 
     int rc = sgpk_check(ctx, fn, H, W, hWin, wWin, P1, P2, paths, min_unique);
     if (rc) return rc;
     float *work = nullptr;
-    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { work = c.take<float>(sgpk_work_planes(paths, agg != nullptr) * H * W * (size_t)(hWin * wWin)); });
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { work = c.take<float>(dfe_sgm_work_planes(paths, agg != nullptr) * H * W * (size_t)(hWin * wWin)); });
     if (rc) return rc;
-    SgpkOut o{};
+    SgmpOut o{};
     o.agg = agg;
     o.idx = (long long *)idx; o.fy = flow_y; o.fx = flow_x;
-    o.best = best; o.second = second; o.unique = unique;
+    o.best = best; o.second = second; o.unique = unique; o.min_unique = min_unique;
     o.pitch = W;
     DfeStageScope st(ctx, DFE_STAGE_MATCH);
-    return sgpk_run(ctx, volume, H, W, hWin, wWin, P1, P2, paths, subpixel, min_unique, work, o);
+    return sgpk_run(ctx, volume, H, W, hWin, wWin, P1, P2, paths, subpixel, work, o);
 }
 
 int dfe_flow_depth_pair_sgm_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x, float foe_y,
@@ -309,12 +229,28 @@ int dfe_flow_depth_pair_sgm_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I
                          depth_conf);
 }
 
+int dfe_census_flow_depth_pair_sgm_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x,
+                                       float foe_y, float P1, float P2, unsigned paths, float *flow, float *match, float *depth, float *depth_conf) {
+    DFE_ENTER(ctx);
+    return sgm_census_pair(ctx, "dfe_census_flow_depth_pair_sgm_f32", false, I0, I1, false, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, P1, P2, paths, 0, 0.f, flow,
+                           match, nullptr, depth, depth_conf);
+}
+
+int dfe_census_flow_depth_pair_sgm_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x,
+                                      float foe_y, float scale, float P1, float P2, unsigned paths, float *flow, float *match, float *depth,
+                                      float *depth_conf) {
+    DFE_ENTER(ctx);
+    DFE_REQUIRE(ctx, scale > 0, DFE_E_ARG, "dfe_census_flow_depth_pair_sgm_u8: scale=%g must be positive", (double)scale);
+    return sgm_census_pair(ctx, "dfe_census_flow_depth_pair_sgm_u8", false, I0, I1, true, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, P1, P2, paths, 0, 0.f, flow,
+                           match, nullptr, depth, depth_conf);
+}
+
 int dfe_census_flow_depth_pair_sgm2_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x,
                                         float foe_y, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *match,
                                         float *unique, float *depth, float *depth_conf) {
     DFE_ENTER(ctx);
-    return sgpk_census_pair(ctx, "dfe_census_flow_depth_pair_sgm2_f32", I0, I1, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, P1, P2, paths, subpixel, min_unique,
-                            flow, match, unique, depth, depth_conf);
+    return sgm_census_pair(ctx, "dfe_census_flow_depth_pair_sgm2_f32", true, I0, I1, false, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, P1, P2, paths, subpixel,
+                           min_unique, flow, match, unique, depth, depth_conf);
 }
 
 int dfe_census_flow_depth_pair_sgm2_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, int agg,
@@ -322,8 +258,8 @@ int dfe_census_flow_depth_pair_sgm2_u8(dfe_ctx *ctx, const uint8_t *I0, const ui
                                        float *match, float *unique, float *depth, float *depth_conf) {
     DFE_ENTER(ctx);
     DFE_REQUIRE(ctx, scale > 0, DFE_E_ARG, "dfe_census_flow_depth_pair_sgm2_u8: scale=%g must be positive", (double)scale);
-    return sgpk_census_pair(ctx, "dfe_census_flow_depth_pair_sgm2_u8", I0, I1, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, P1, P2, paths, subpixel, min_unique,
-                            flow, match, unique, depth, depth_conf);
+    return sgm_census_pair(ctx, "dfe_census_flow_depth_pair_sgm2_u8", true, I0, I1, true, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, P1, P2, paths, subpixel,
+                           min_unique, flow, match, unique, depth, depth_conf);
 }
 
 }  // extern "C"

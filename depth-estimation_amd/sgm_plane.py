@@ -15,7 +15,7 @@ import torch
 from ._lib import lib
 from .context import get_ctx, ptr
 
-MAX_CELLS = 1096   # window cells: the single-scale step's own ceiling
+MAX_CELLS = 1096   # window cells: the single-scale step's own ceiling (kDfeMaxWindowCells of the library; census.py imports it)
 
 
 def _plane_params(P1, P2, paths, who):
@@ -110,16 +110,11 @@ def semiGlobalAggregatePlane(volume, P1, P2, paths=0x0f, want_volume=True):
     cells and P2 for any other (include/dfe.h: dfe_sgm_plane_aggregate_f32).  Returns dict(idx int64 [H][W] (1-based class: the first
     minimum of the aggregate, the centre class winning an exact tie), flow_y, flow_x [H][W], aggregate [H][W][hWin][wWin] or None without
     want_volume: the aggregate then never leaves the library's scratch)."""
-    if not isinstance(volume, torch.Tensor) or volume.dim() != 4 or min(volume.shape) < 1:
-        raise ValueError("semiGlobalAggregatePlane: volume H x W x hWin x wWin expected, got %s" % (tuple(getattr(volume, "shape", ())),))
-    H, W, hWin, wWin = volume.shape
-    if hWin * wWin > MAX_CELLS:
-        raise ValueError("semiGlobalAggregatePlane: window %d x %d has more than %d cells" % (hWin, wWin, MAX_CELLS))
-    if H * W > 2 ** 31 - 1:
-        raise ValueError("semiGlobalAggregatePlane: %d x %d pixels" % (H, W))
-    P1, P2 = _plane_params(P1, P2, paths, "semiGlobalAggregatePlane")
+    who = "semiGlobalAggregatePlane"
+    H, W, hWin, wWin = _volume_arg(volume, who)
+    P1, P2 = _plane_params(P1, P2, paths, who)
     if not volume.is_cuda or volume.dtype != torch.float32:
-        raise TypeError("semiGlobalAggregatePlane: a float32 CUDA tensor expected")
+        raise TypeError("%s: a float32 CUDA tensor expected" % who)
     volume = volume.contiguous()
     ctx = get_ctx(volume)
     idx = torch.empty((H, W), dtype=torch.int64, device=volume.device)
