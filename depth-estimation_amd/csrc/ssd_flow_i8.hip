@@ -29,18 +29,25 @@
 // adding it to C with vector instructions keeps the load early but costs 4 v_add per tile, 24 v_mov_b64 on the back edge and 163 VGPRs
 // (288 vector instructions per four steps against 216; not shipped).
 //
-// Arg-min.  A lane keeps two running keys (i = 0, 1 and i = 2, 3): key = ((2 a'.b' - S1) << 8) + tiebreak, maximised; the plane cell of
-// frame-1 row y1, column q holds -(S1 << 8) + (1 - (q & 1)) - 6 y1 - 2 (q >> 4), so a key is ONE v_lshl_add of the MFMA result and nothing
-// else is kept per tile: for the item's row y0 + r the candidate j = 3 dy + T (sweep order) lies in row y1 = y0 + r + dy and column block
-// x0 / 16 + T, where the plane's term is -2 j - base, base = 6 (y0 + r) + x0 / 8 the same for all of the row's candidates.  An earlier
-// candidate has the larger term and wins a tie; the terms of two candidates of one pixel differ by at most 2 * 98 + 1 < 256, so the term
-// never outweighs a difference of the costs and need not be reduced.  The decode adds base back.  Range: 2 a'.b' - S1 lies in
-// [-7187712, 2408448] (147 taps of 2 * 127 * -128 - 128^2 .. 2 * 128 * 128 - 128^2), times 256 that is -1.840e9 .. 0.617e9; dfe_flow_i8_plan admits
-// (H + 1) Wp < 2^29 with Wp >= 80, so 6 y1 + 2 (q >> 4) < 6 * 2^29 / 80 + 2^29 / (40 * 8) < 4.2e7: every key, and base + 255 added
-// to one, stays inside 32 bits.  Candidates outside 0 <= q - n <= 32 (first and third tile) are masked by lane masks that live in
-// scalar registers.  Per tile that is 4 v_lshl_add_u32 and 2 v_max3_i32, and 4 v_cndmask_b32 in a masked tile (i8_max3 keeps the compiler
-// from selecting after each max: 8 in place of 6); with the two row addresses a two-row step issues 54 vector instructions beside its 15
-// MFMAs, a one-row step 28 beside 12.  The four lane groups of a pixel are combined once, on (cost, index).
+// Arg-min.  A lane keeps four running keys, one per i: key = ((2 a'.b' - S1) << 7) + order, maximised; the plane cell of frame-1 row y1,
+// column q holds Z - (S1 << 7) - 3 y1 - (q >> 4), so a key is ONE v_lshl_add of the MFMA result, (D << 8) + P, and nothing else is kept
+// per tile: for the item's row y0 + r the candidate j = 3 dy + T (sweep order) lies in row y1 = y0 + r + dy and column block x0 / 16 + T,
+// where the plane's term is -j - base, base = 3 (y0 + r) + x0 / 16 the same for all of the row's candidates.  An earlier candidate has
+// the larger term and wins a tie; the terms of two candidates of one pixel differ by at most 98 < 128, so the term never outweighs a
+// difference of the costs and need not be reduced.  The decode adds base back; which of a pixel's candidates i (and lane groups g) comes
+// first is decided there, on (cost, index).
+// The window.  Candidates outside 0 <= q - n <= 32 (first and third tile) are never selected out: their dot product STARTS from a penalty.
+// The accumulator of the first / third tile starts from a per-lane quad (pen0 / pen2, made once per item) that holds kKeyPen = Q / 2 for a
+// masked (g, i, n) and 0 otherwise -- the MFMA's C operand, so no instruction -- and a masked key is the key of E + Q.  E = 2 a'.b' - S1
+// lies in [-7187712, 2408448] (147 taps of 2 * 127 * -128 - 128^2 .. 2 * 128 * 128 - 128^2) for masked candidates too (they read packed
+// bytes, or zero beyond the frame), a span of 9596160: with Q = -10485760 every masked key of a pixel lies below every valid one, and as
+// every running key sees tile 1, which is never masked, none ends on a masked candidate.  In a two-row item the penalty rides in C(s) and
+// so reaches D0 and the next step's D1, whose masks are the same.  Range, with Z = 2^30: valid keys lie in [Z - 0.920e9 - order,
+// Z + 0.308e9], masked ones from Z - 2.262e9 - order; dfe_flow_i8_plan admits (H + 1) Wp < 2^29 with Wp >= 80, so order = 3 y1 + (q >> 4)
+// + 98 < 3 * 2^29 / 80 + 2^29 / (40 * 16) < 2.2e7: every key, and the decode's base + 127 - Z added to a valid one, stays inside 32 bits
+// (tests/test_flow_i8_key7_cpu.py).  Per tile that is 4 v_lshl_add_u32 and 2 v_max3_i32 (the twelve keys of a row's step fold in six,
+// a tile's keys paired with the same i of the neighbouring tile); with the two row addresses a two-row step issues 38 vector instructions
+// beside its 15 MFMAs, a one-row step 20 beside 12.
 //
 // Items.  flow_i8_items.h splits the rows into two-row and one-row wave items from the number of waves the device holds at once.
 //
@@ -65,7 +72,7 @@ typedef int i8x16_t __attribute__((ext_vector_type(4)));   // 16 bytes of an MFM
 
 struct I8Args {
     const unsigned *pk0, *pk1;   // packed frames [H][Wp]
-    const int *s0, *s1k;         // patch sums of frame 0 (plain) and frame 1 (as the key's addend) [H][Wp]
+    const int *s0, *s1k;         // patch sums of frame 0 (plain) and frame 1 (as the key's addend: kKeyZ - (S1 << 7) - 3 y - (x >> 4)) [H][Wp]
     const unsigned *verdict;     // != 0: the frames are not byte-valued
     TailOut o;                   // where the wave's pixels go (cv_records.h)
     float thr;
@@ -75,8 +82,11 @@ struct I8Args {
 };
 
 constexpr int kI8Waves = 4;
+// the key (header: Arg-min): the plane's offset Z, and the start value of a masked candidate's accumulator, Q / 2 in units of a'.b'
+constexpr int kKeyZ = 1 << 30;
+constexpr int kKeyPen = -10485760 / 2;
 
-// max(a, b, c) the compiler cannot take apart: given max(max(best, m0 ? k0 : INT_MIN), m1 ? k1 : INT_MIN) it selects after each max instead
+// max(a, b, c) as ONE instruction, whatever the compiler would make of max(max(a, b), c)
 __device__ __forceinline__ int i8_max3(int a, int b, int c) {
     int r;
     asm("v_max3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
@@ -165,7 +175,7 @@ __global__ __launch_bounds__(256) void flow_i8_pack_kernel(const T *__restrict__
         if (gy >= H || X >= Wp) continue;
         const int v = hs[ly][lx] + hs[ly + 1][lx] + hs[ly + 2][lx] + hs[ly + 3][lx] + hs[ly + 4][lx] + hs[ly + 5][lx] + hs[ly + 6][lx];
         const long long o = (long long)gy * Wp + X;
-        if (blockIdx.z) s1k[o] = -(v << 8) + (1 - (X & 1)) - 6 * gy - 2 * (X >> 4);
+        if (blockIdx.z) s1k[o] = kKeyZ - (v << 7) - 3 * gy - (X >> 4);
         else s0[o] = v;
     }
 }
@@ -177,6 +187,7 @@ constexpr int kCostPitch = 33;   // floats per pixel of the wave's lead-cell ima
 template <int R> struct I8Lds {
     float cost[R][16][kCostPitch];   // displacement row 0, tiles 0 and 1: cost[n][q]
     float cen[R][16];                // the centre cell's cost of pixel n
+    int sa[R][16];                   // S0 of pixel n: wanted in the peeled steps and at the end only, so not held in a register
     float fbh[R][16][DFE_FB];        // a flagged pixel's hits of the fall-back sweep: M (value, 1-based index) pairs, zero-padded
 };
 
@@ -186,11 +197,12 @@ template <int R, bool FB> struct I8Sweep {
     const int lane, n, g, x0, y0;
     i8x16_t A[3][4], B[4];
     i8x16_t Bbot, C[3];    // R == 2: frame-0 row y0 + 23 (row y0 + 1's own patch row) and the shared rows' products of the step before
-    int best[R][2];
-    int sa[R];
+    i8x16_t pen0, pen2;    // the first / third tile's accumulators start here: kKeyPen where candidate 4 g + i lies outside 0 <= q - n <= 32, else 0
+    int best[R][4];        // the running key of candidates i, i = 0..3
+    int held[R][4];        // a tile's keys that wait for the next tile's, their partners in one v_max3
     unsigned lo1, lop;     // the lane's byte offsets inside a row of the packed frame 1 and of the S1 plane
-    bool in0[4], in2[4];   // the first / third tile's candidate 4 g + i lies inside 0 <= q - n <= 32 (loop-invariant lane masks)
     // FB
+    int sa[R];             // S0 of the lane's pixel (the sweep proper reads it from its LDS image)
     int cnt;
     bool flagged;
     float *fbp;
@@ -201,10 +213,12 @@ template <int R, bool FB> struct I8Sweep {
 
     __device__ __forceinline__ void load_operands() {
         const int h = g & 1, up = g >> 1;
+        if constexpr (!FB) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            in0[i] = 4 * g + i >= n;
-            in2[i] = 4 * g + i <= n;
+            for (int i = 0; i < 4; ++i) {
+                pen0[i] = 4 * g + i >= n ? 0 : kKeyPen;
+                pen2[i] = 4 * g + i <= n ? 0 : kKeyPen;
+            }
         }
         // frame 0: patch rows (0..3 | 3..6) of row y0's pixel n, zero in the duplicate row 3 and in the eighth pixel.  R == 2: image rows
         // y0 + 17 .. y0 + 22 of these are row y0 + 1's patch rows 0..5 as well; its patch row 6, image row y0 + 23, is Bbot's upper half
@@ -234,25 +248,29 @@ template <int R, bool FB> struct I8Sweep {
     }
 
     // the keys of one result tile D of row y0 + r, and the row's lead cells (sr == 0) and centre cell (sr == 16) where the step is the peeled
-    // one that holds them: sr is the row's displacement row there, anything else in the steady state
-    __device__ __forceinline__ void take(int T, int r, int sr, const i8x16_t &D, const i8x16_t &P, int pb) {
-        int k[4];
+    // one that holds them: sr is the row's displacement row there, anything else in the steady state.  A masked candidate's D carries
+    // kKeyPen, so its key lies below every valid key of the pixel and nothing selects.  The row's running keys take the tiles in pairs, one
+    // v_max3 per i and pair: tiles (0, 1) of an even displacement row (`odd` false), whose tile 2 waits in `held` for tile 0 of the odd row
+    // behind it, which pairs its own tiles (1, 2).  Displacement row 32 (sr == 32, even) has no row behind it: its tile 2 takes a v_max.
+    __device__ __forceinline__ void take(int T, int r, int sr, bool odd, const i8x16_t &D, const i8x16_t &P, int pb) {
+        const bool hold = odd ? T == 1 : T != 1, alone = sr == 32 && T == 2;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            k[i] = (int)((unsigned)D[i] << 9) + P[i];
-            if (T == 0) k[i] = in0[i] ? k[i] : INT_MIN;
-            if (T == 2) k[i] = in2[i] ? k[i] : INT_MIN;
+            const int k = (int)((unsigned)D[i] << 8) + P[i];
+            if (alone) best[r][i] = max(best[r][i], k);
+            else if (hold) held[r][i] = k;
+            else best[r][i] = i8_max3(best[r][i], held[r][i], k);
         }
-        best[r][0] = i8_max3(best[r][0], k[0], k[1]);
-        best[r][1] = i8_max3(best[r][1], k[2], k[3]);
+        // S1 back from the plane cell: P - Z + pb + T = -(S1 << 7) exactly.  In tile 0 the cells q < n hold the penalty: i8_item reads
+        // cost[n][q] at q = n + k, k = 0..7, only
         if (T < 2 && sr == 0) {   // the lead cells' row
 #pragma unroll
-            for (int i = 0; i < 4; ++i) lds->cost[r][n][16 * T + 4 * g + i] = (float)(sa[r] - ((P[i] + pb + 2 * T) >> 8) - 2 * D[i]);
+            for (int i = 0; i < 4; ++i) lds->cost[r][n][16 * T + 4 * g + i] = (float)(lds->sa[r][n] - ((P[i] + (pb - kKeyZ + T)) >> 7) - 2 * D[i]);
         }
-        if (T == 1 && sr == 16) {   // the centre cell: dx = 16, q = 16 + n
+        if (T == 1 && sr == 16) {   // the centre cell: dx = 16, q = 16 + n (tile 1: no penalty)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                if (4 * g + i == n) lds->cen[r][n] = (float)(sa[r] - ((P[i] + pb + 2 * T) >> 8) - 2 * D[i]);
+                if (4 * g + i == n) lds->cen[r][n] = (float)(lds->sa[r][n] - ((P[i] + (pb - kKeyZ + T)) >> 7) - 2 * D[i]);
         }
     }
 
@@ -261,7 +279,7 @@ template <int R, bool FB> struct I8Sweep {
     // which tests nothing.  The fallback sweep (R = 1: every step is a displacement row) takes all of it at run time.
     template <int PH, int S> __device__ __forceinline__ void step(int s) {
         const bool more = FB ? s + 1 < NS : S != NS - 1;
-        const int pb = 6 * (y0 + s) + (x0 >> 3);   // the plane's order term of tile 0 of this row, taken off where S1 itself is wanted
+        const int pb = 3 * (y0 + s) + (x0 >> 4);   // the plane's order term of tile 0 of this row, taken off where S1 itself is wanted
         // the rows' addresses live in scalar registers; a lane adds its offset (load_operands; the compiler keeps it as a 64-bit base and adds
         // the scalar row with one v_lshl_add_u64) and the tile's 64 T bytes
         const char *prow = reinterpret_cast<const char *>(a.s1k + (y0 + s) * a.Wp + x0);
@@ -272,6 +290,9 @@ template <int R, bool FB> struct I8Sweep {
         for (int T = 0; T < 3; ++T) P[T] = *reinterpret_cast<const i8x16_t *>(prow + lop + 64 * T);
 #pragma unroll
         for (int T = 0; T < 3; ++T) {
+            // the tile's accumulator starts from the window's penalty quad (the MFMA's C operand: no instruction); the fall-back sweep
+            // forms costs from D and tests `valid` itself: it starts from zero
+            const i8x16_t c0 = FB || T == 1 ? i8x16_t{0, 0, 0, 0} : T == 0 ? pen0 : pen2;
             if constexpr (R == 2) {
                 // Row y0 at dy = s and row y0 + 1 at dy = s - 1 compare frame-0 rows y0 + 17 .. y0 + 22 with the same six frame-1 rows, a
                 // step apart: C, the three MFMAs of fragments 1..3, is row y0's patch rows 1..6 now and row y0 + 1's patch rows 0..5 at the
@@ -281,7 +302,7 @@ template <int R, bool FB> struct I8Sweep {
                 i8x16_t D0, D1;
                 if (!first) D1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][(3 + PH) & 3], Bbot, C[T], 0, 0, 0);
                 if (!last) {
-                    i8x16_t c{0, 0, 0, 0};
+                    i8x16_t c = c0;   // in C(s), so in D0 and in the next step's D1: the two rows' masks are the same
 #pragma unroll
                     for (int t = 1; t < 4; ++t) c = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][(t + PH) & 3], B[t], c, 0, 0, 0);
                     C[T] = c;
@@ -289,11 +310,11 @@ template <int R, bool FB> struct I8Sweep {
                     // D0's MFMA was the last reader of the oldest fragment: the new row is loaded into its registers, as in the one-row step
                     __builtin_amdgcn_sched_barrier(0);
                     A[T][PH & 3] = *reinterpret_cast<const i8x16_t *>(frow + lo1 + 64 * T);
-                    take(T, 0, S, D0, P[T], pb);
+                    take(T, 0, S, PH & 1, D0, P[T], pb);
                 }
-                if (!first) take(T, 1, S - 1, D1, P[T], pb);
+                if (!first) take(T, 1, S - 1, (PH + 1) & 1, D1, P[T], pb);
             } else {
-                i8x16_t D = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][PH & 3], B[0], i8x16_t{0, 0, 0, 0}, 0, 0, 0);
+                i8x16_t D = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][PH & 3], B[0], c0, 0, 0, 0);
                 // the fragment of the oldest row has been read by the step's last MFMA that needs it: the new row is loaded into its registers, a
                 // renaming and no copy.  The barrier keeps the scheduler from hoisting the load above those MFMAs, which costs spare fragments
                 // (18 VGPRs more with R = 2, 28 with R = 1) and measured slower
@@ -304,7 +325,7 @@ template <int R, bool FB> struct I8Sweep {
 #pragma unroll
                 for (int t = 1; t < 4; ++t) D = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[T][(t + PH) & 3], B[t], D, 0, 0, 0);
                 if constexpr (!FB) {
-                    take(T, 0, S, D, P[T], pb);
+                    take(T, 0, S, PH & 1, D, P[T], pb);
                 } else {
                     // rank this tile's hits of every flagged pixel in candidate order: lane groups below mine, then my own earlier ones
                     bool hit[4];
@@ -313,7 +334,7 @@ template <int R, bool FB> struct I8Sweep {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int m = 4 * g + i;
-                        cv[i] = (float)(sa[0] - ((P[T][i] + pb + 2 * T) >> 8) - 2 * D[i]);
+                        cv[i] = (float)(sa[0] - ((P[T][i] + (pb - kKeyZ + T)) >> 7) - 2 * D[i]);
                         bool valid = flagged;
                         if (T == 0) valid = valid && m >= n;
                         if (T == 2) valid = valid && m <= n;
@@ -443,8 +464,8 @@ template <int R> __device__ __forceinline__ void i8_item(const I8Args &a, I8Lds<
     sw.lds = lds;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        sw.best[r][0] = sw.best[r][1] = INT_MIN;
-        sw.sa[r] = a.s0[(y0 + r + 16) * a.Wp + x0 + n + 16];
+        for (int i = 0; i < 4; ++i) sw.best[r][i] = INT_MIN;
+        lds->sa[r][n] = a.s0[(y0 + r + 16) * a.Wp + x0 + n + 16];
     }
     sw.load_operands();
     sw.run();
@@ -458,15 +479,16 @@ template <int R> __device__ __forceinline__ void i8_item(const I8Args &a, I8Lds<
     bool fflag = false;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        // (cost, index) of the lane's two running keys, then of the pixel's four lane groups
+        // (cost, index) of the lane's four running keys, then of the pixel's four lane groups.  Every running key has seen tile 1, which
+        // is never masked: each holds a valid candidate
         long long kb = LLONG_MIN;
 #pragma unroll
-        for (int sl = 0; sl < 2; ++sl) {
-            const int bt = sw.best[r][sl] + (6 * (y0 + r) + (x0 >> 3) + 254);   // (E << 8) + 254 - 2 j + (1 - ib)
-            const int u = 255 - (bt & 255), j = u >> 1, ib = u & 1;
+        for (int i = 0; i < 4; ++i) {
+            const int bt = sw.best[r][i] + (3 * (y0 + r) + (x0 >> 4) + 127 - kKeyZ);   // (E << 7) + 127 - j
+            const int j = 127 - (bt & 127);
             const int dy = j / 3, T = j - 3 * dy;
-            const int d = dy * 33 + 16 * T + 4 * g + 2 * sl + ib - n;
-            const long long k64 = ((long long)(bt >> 8) << 12) | (long long)(4095 - d);
+            const int d = dy * 33 + 16 * T + 4 * g + i - n;
+            const long long k64 = ((long long)(bt >> 7) << 12) | (long long)(4095 - d);
             kb = k64 > kb ? k64 : kb;
         }
         {
@@ -482,11 +504,11 @@ template <int R> __device__ __forceinline__ void i8_item(const I8Args &a, I8Lds<
         const unsigned long long m0 = __builtin_amdgcn_ballot_w64(l0 > a.thr), m1 = __builtin_amdgcn_ballot_w64(l1 > a.thr);
         const unsigned hm = ((unsigned)(m0 >> (4 * n)) & 15u) | (((unsigned)(m1 >> (4 * n)) & 15u) << 4);
         const bool flag = xin && __builtin_popcount(hm) < a.M;
-        if (g == r) { fE = E; fd = d; fsa = sw.sa[r]; fhm = hm; fflag = flag; }
+        if (g == r) { fE = E; fd = d; fsa = lds->sa[r][n]; fhm = hm; fflag = flag; }
         const int y = y0 + r;
         if (y >= ylo && __builtin_amdgcn_ballot_w64(flag)) {   // rare: rank the hits of the flagged pixels over the whole window
             I8Sweep<1, true> fs(a, lane, x0, y);
-            fs.sa[0] = sw.sa[r];
+            fs.sa[0] = lds->sa[r][n];
             fs.cnt = 0;
             fs.flagged = flag;
             fs.fbp = &lds->fbh[r][n][0];
