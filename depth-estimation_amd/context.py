@@ -36,7 +36,7 @@ class Context:
         self.check(lib().dfe_set_cost_volume_kernel(self.handle, int(mode)))
 
     def set_cost_volume_tile(self, tyq):
-        """0 = tile height chosen per shape; 2..5 forces it (tuning / tests)."""
+        """0 = tile height chosen per shape; 2..5 forces it, 1, 6, 7 and 100 + ty are row-image codes (include/dfe.h; tuning / tests)."""
         self.check(lib().dfe_set_cost_volume_tile(self.handle, int(tyq)))
 
     def set_option(self, key, value):

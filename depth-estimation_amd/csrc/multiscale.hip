@@ -1130,8 +1130,11 @@ static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
     // cascade launch): wherever the finest scale is fused and a coarser scale exists above it.  DFE_MID_FUSE=0 / 1 forces the choice.
     // Measured, finest scale fused -> both: 1080p 0.363 -> 0.346 ms, 4K 1.40 -> 1.29; 720p 0.179 -> 0.205 (230 k pixels: one partial round
     // of blocks, latency-bound); fp16 volumes (half the bytes to save) 4K 1.315 -> 1.320.
+    // (cv_finest_plan_ok plans the launcher's 4 row groups, an 18-row tile; mid_nq = 5 launches 24-row tiles, which a second scale of
+    //  18 .. 23 rows has no plan for: it keeps its volume then, instead of failing in ms_cascade_px)
     const bool mid_shape = nratios >= 3 && (a.filt ? (P.sc[1].Hs >= 16 && P.sc[1].Ws >= 8 && (P.sc[1].Hs | P.sc[1].Ws) % 2 == 0)
-                                                   : cv_finest_plan_ok(ctx, P.sc[1].Hp, P.sc[1].Wp, maxh, maxw));
+                                                   : (cv_finest_plan_ok(ctx, P.sc[1].Hp, P.sc[1].Wp, maxh, maxw) &&
+                                                      (ctx->opt[DFE_OPT_MID_NQ] != 5 || P.sc[1].Hs >= 24)));
     P.fuse_mid = P.fuse_fine && a.f16_scale == 0.f && (long long)H * W >= 1500000ll && mid_shape;
     if (ctx->opt[DFE_OPT_MID_FUSE] >= 0) P.fuse_mid = P.fuse_fine && ctx->opt[DFE_OPT_MID_FUSE] != 0 && mid_shape;
     P.s0 = P.fuse_mid ? 2 : P.fuse_fine ? 1 : 0;      // the first scale whose volume is materialised

@@ -81,8 +81,10 @@ def getNetwork(datap, device="cuda", generator=None):
     """version2/network.lua:5-39.  network.modules[0].modules = [filter1, filter2]; filter1.modules = [normalisation, SpatialPadding
     (crop), conv...]; filter2.modules = [normalisation, conv clones...]; network.modules[1] = SpatialMatching(hWin, wWin, false).
     The SpatialPadding takes its arguments in the order the script passes them -- (-lWin, -tWin, -rWin, -bWin) into
-    nn.SpatialPadding(pad_l, pad_r, pad_t, pad_b) -- which is the intended crop only for windows with lWin == tWin and rWin == bWin
-    (odd, square windows such as the script's 17 x 17); other windows fail in SpatialMatching's size check, as they would there."""
+    nn.SpatialPadding(pad_l, pad_r, pad_t, pad_b) -- which is the intended crop only for windows with tWin == rWin, i.e.
+    ceil(hWin / 2) - 1 == floor(wWin / 2) (the script's 17 x 17; not 16 x 16); other windows fail in SpatialMatching's size check, as they
+    would there (tests/test_gpu_parity.py::test_version2_one_call_equals_staged_and_oracle pins that).  dfe_version2_flow_pair_f32 crops as
+    intended for every window."""
     layers = _d(datap, "layers")
     network = Sequential()
     filters = ParallelTable()

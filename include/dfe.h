@@ -73,7 +73,11 @@ int dfe_host_free(dfe_ctx *ctx, void *hptr);
 int dfe_set_cost_volume_kernel(dfe_ctx *ctx, int mode);
 /* tile height of the tiled / row-image kernels: 0 = chosen per shape (default); 2..7 = force NQ (a tile sweeps
  * NQ groups of 6 image rows at k = 7: 6 NQ - 6 output rows); 100 + ty (101..164) = row-image tiles of ty output
- * rows (ty a multiple of 6 at k = 7); 1 = force the row-image kernel's column sweep (unfused build only).  For tuning and for testing. */
+ * rows (ty a multiple of 6 at k = 7); 1 = force the row-image kernel's column sweep (unfused build only).  For tuning and for testing.
+ * The row-image kernel takes every code.  The tiled kernels (the single-scale one, its fused build and the pyramid's merged volume
+ * launch) are built for NQ = 2..5 only: there 6, 7, 1 and 100 + ty mean 0, the launcher's own choice.  A forced height that does not
+ * fit the frame makes the tiled launcher decline: the next kernel in line builds the volume, the same values (with kernel mode 2,
+ * which leaves no other kernel, the op returns DFE_E_UNSUPPORTED). */
 int dfe_set_cost_volume_tile(dfe_ctx *ctx, int tyq);
 /* Behaviour switches of the launchers (tuning and tests; none is needed for correct results -- every choice has a parity test or is
  * a pure scheduling choice).  value >= 0 forces, -1 restores the launcher's own choice per shape.  Keys: "cascade_px", "fine_fuse",

@@ -45,6 +45,14 @@ CASES = [
 ]
 BY_NO = {c.no: c for c in CASES}
 
+# The corner itself -- 8 x 8, k = 7, C = 3, ratios 1, 2, 4 -- for the launcher switches of tests/test_gpu_pyramid_switches.py: W / 8 = 17
+# tiles, a coarsest scale of 24 x 34 (exactly one tile of 5 row groups high, one 32-pixel block and a tail wide), and a planted flow large
+# enough that every scale wins pixels, so that a wrong value in any scale's volume moves class ids.  Not a row of CASES: the shapes
+# suite does not run it.  `ties16`: the tie share under the fp16 rule of test_row_f16_equals_oracle_chain, as measured.
+SWITCH_ORACLE = Case(21, [1, 2, 4], 8, 8, 7, 3, 96, 136, 14, "launcher switches at the 8 x 8 corner", 0.0051, [7374, 4357, 1325])
+SWITCH_ORACLE.ties16 = 0.0345
+BY_NO[SWITCH_ORACLE.no] = SWITCH_ORACLE
+
 # prep_tiles_kernel off its 64-pixel tile grid (k = 7, 8 x 8 windows): (H, W, C, ratios, byte frames)
 PREP_CASES = [
     (1032, 1480, 1, [1, 2, 4, 8], False),        # both sides 8 mod 64: the last tiles are 8 wide and 8 high

@@ -72,9 +72,10 @@ def test_cost_volume_tiled_bit_exact_on_integer_frames(dfe, cuda, H, W, C, k, hW
     assert np.array_equal(gpu, cpu)
 
 
-@pytest.mark.parametrize("tyq", [2, 3, 4, 5])
+@pytest.mark.parametrize("tyq", [2, 3, 4, 5, 6, 7])
 def test_cost_volume_every_tile_height_bit_exact(dfe, cuda, tyq):
-    # every TYQ instantiation, on a frame whose last tile row/column is shifted (Ho, Wo not multiples)
+    # every TYQ instantiation, on a frame whose last tile row/column is shifted (Ho, Wo not multiples); 6 and 7 are row-image codes:
+    # the tiled launcher is built for 2..5 and takes its own choice there (include/dfe.h), the same bits
     H, W = 83, 71
     f0, f1, _, _ = rp.synth_pair(H, W, C=3, seed=tyq, max_flow=7)
     cpu = orc.ssd_cost_volume(f0, f1, 7, 7, 17, 17)
@@ -92,11 +93,11 @@ def test_cost_volume_every_tile_height_bit_exact(dfe, cuda, tyq):
     assert np.array_equal(out.cpu().numpy(), cpu)
 
 
-@pytest.mark.parametrize("nq", [0, 1, 3, 4, 5, 6, 106, 107, 142])
+@pytest.mark.parametrize("nq", [0, 1, 2, 3, 4, 5, 6, 7, 106, 107, 142])
 @pytest.mark.parametrize("H,W", [(80, 100), (75, 47), (131, 90), (230, 64)])
 def test_cost_volume_rowimg_kernel_bit_exact(dfe, cuda, nq, H, W):
     # the row-image kernel (all 1089 cells of a tile row in one block, LDS row image, aligned copy-out), 33x33 window, as a
-    # column sweep (nq = 1; (230, 64): several segments of a column) and with static tiles of many heights (0 = auto, 3..6 = 6n - 6
+    # column sweep (nq = 1; (230, 64): several segments of a column) and with static tiles of many heights (0 = auto, 2..7 = 6n - 6
     # rows, 100 + ty = ty rows: the height is a run-time value, a multiple of 6), on frames whose last tile row / column are shifted and whose
     # runs start at every alignment mod 128 B
     f0, f1, _, _ = rp.synth_pair(H, W, C=3, seed=H + nq, max_flow=9)
@@ -120,9 +121,9 @@ def test_cost_volume_rowimg_kernel_bit_exact(dfe, cuda, nq, H, W):
     assert np.array_equal(out.cpu().numpy(), cpu)
 
 
-@pytest.mark.parametrize("nq", [0, 1, 5])
+@pytest.mark.parametrize("nq", [0, 1, 2, 5, 7])
 def test_cost_volume_rowimg_kernel_luminance_bit_exact(dfe, cuda, nq):
-    # the row-image kernel's C = 1 instantiation (auto / column sweep / static 24-row tiles) against the oracle
+    # the row-image kernel's C = 1 instantiation (auto / column sweep / static 6-, 24- and 36-row tiles) against the oracle
     H, W = 131, 90
     f0, f1, _, _ = rp.synth_pair(H, W, C=1, seed=nq, max_flow=9)
     cpu = orc.ssd_cost_volume(f0, f1, 7, 7, 33, 33)
@@ -138,6 +139,72 @@ def test_cost_volume_rowimg_kernel_luminance_bit_exact(dfe, cuda, nq):
         ctx.set_cost_volume_kernel(0)
         ctx.set_cost_volume_tile(0)
     assert np.array_equal(out.cpu().numpy(), cpu)
+
+
+_SWEEP_REF = {}
+
+
+def _sweep_frames(H, W):
+    """the (H, W) frame pair of test_cost_volume_rowimg_kernel_bit_exact's column-sweep case and its oracle volume, computed once"""
+    if (H, W) not in _SWEEP_REF:
+        f0, f1, _, _ = rp.synth_pair(H, W, C=3, seed=H + 1, max_flow=9)
+        cpu = orc.ssd_cost_volume(f0, f1, 7, 7, 33, 33)
+        cpu.setflags(write=False)
+        _SWEEP_REF[(H, W)] = (f0, f1, cpu)
+    return _SWEEP_REF[(H, W)]
+
+
+@pytest.mark.parametrize("ovh", [0, 8, 64])
+@pytest.mark.parametrize("code", [1, 0])
+@pytest.mark.parametrize("H,W", [(131, 90), (230, 64)])
+def test_cost_volume_sweep_overhead_option_is_pure_scheduling(dfe, cuda, ovh, code, H, W):
+    """option sweep_ovh -- the cost of starting a piece in the column sweep's cut rule (sweep_cut) -- moves the cuts between the blocks'
+    ranges and nothing else: the row-image kernel's volume equals the oracle's bit for bit with the forced column sweep (tile code 1)
+    and with the launcher's own choice (code 0), for no overhead, one below the launcher's 9 and one that is most of a column."""
+    f0, f1, cpu = _sweep_frames(H, W)
+    ctx = dfe.get_ctx(0)
+    ctx.set_cost_volume_kernel(3)
+    ctx.set_cost_volume_tile(code)
+    try:
+        ctx.set_option("sweep_ovh", ovh)
+        out = torch.full(cpu.shape, -1.0, device=cuda)
+        t0, t1 = T(f0, cuda), T(f1, cuda)
+        ctx.check(dfe.lib().dfe_ssd_cost_volume_f32(ctx.handle, t0.data_ptr(), t1.data_ptr(), 3, H, W, 7, 7, 33, 33, out.data_ptr()))
+        assert ctx.last_kernel() == "ssd_cv_rowimg_kernel"
+    finally:
+        ctx.set_cost_volume_kernel(0)
+        ctx.set_cost_volume_tile(0)
+    assert np.array_equal(out.cpu().numpy(), cpu)
+
+
+def test_flow_step_sweep_overhead_option_is_pure_scheduling(dfe, cuda):
+    """sweep_ovh through the fused one call at 33 x 33 (dfe_flow_depth_pair_f32, the volume-free sweep): 50 x 70 output pixels are 9 tile
+    columns of 50 rows for 18 blocks, so ranges end inside columns and the overhead decides where.  Integer frames without int8
+    (the ungated sweep's launcher): flow and scores equal the oracle's, whatever the overhead.  One value that is no byte with int8 on (the
+    gated sweep's plan): every output equals the released run's, byte for byte."""
+    H, W, k, win = 88, 108, 7, 33
+    f0, f1, _, (cx, cy) = rp.synth_pair(H, W, C=3, seed=11, max_flow=10)
+    g0 = f0.copy()
+    g0[1, H // 2, W // 2] = 0.5
+    ref = rp.dense_flow_oracle(f0, f1, win, win, k, k)
+    ctx, lib = dfe.get_ctx(0), dfe.lib()
+
+    def run(a0, i8, ovh):
+        t0, t1 = T(a0, cuda), T(f1, cuda)
+        outs = [torch.full((2, H, W), -7.0, device=cuda)] + [torch.full((H, W), -7.0, device=cuda) for _ in range(3)]
+        with ctx.options(cv_i8=i8, sweep_ovh=ovh):
+            ctx.check(lib.dfe_flow_depth_pair_f32(ctx.handle, t0.data_ptr(), t1.data_ptr(), 3, H, W, k, win, win, cx, cy, 0.21, *[o.data_ptr() for o in outs]))
+            assert ctx.last_kernel() == "ssd_cv_rowimg_kernel+fused_tail+novol" and not ctx.flow_last_path_i8()
+        return [o.cpu().numpy() for o in outs]
+
+    for a0, i8 in ((f0, 0), (g0, 1)):
+        want = run(a0, i8, -1)
+        if i8 == 0:
+            assert np.array_equal(want[0], ref["flowp"][:2]) and np.array_equal(want[1], ref["flowp"][3])
+        for ovh in (0, 8, 64):
+            got = run(a0, i8, ovh)
+            for g, w in zip(got, want):
+                assert np.array_equal(g.view(np.uint8), w.view(np.uint8)), (i8, ovh)
 
 
 @pytest.mark.parametrize("H,W,C", [(75, 47, 3), (131, 90, 3), (90, 100, 1)])
@@ -292,6 +359,34 @@ def test_spatial_matching_flat_kernel_bit_exact(dfe, cuda, K, H1, W1, mh, mw):
             other = dfe.nn.SpatialMatching(mh, mw, False).forward([t1, t2])
             assert ctx.last_kernel() == "feat_matching_flat_kernel"
         assert torch.equal(other, out), split
+
+
+def test_spatial_matching_row_and_one_chunk_switches_bit_exact(dfe, cuda):
+    """options fm64 and fm_rows move a shape between the one-chunk, the row and the chunk kernel (tests/test_gpu_fm_select.py pins which):
+    either way nn.SpatialMatching equals the oracle bit for bit, and the kernel named is the forced one."""
+    ctx = dfe.get_ctx(0)
+    rng = np.random.default_rng(64)
+
+    def run(K, H1, W1, mh, mw):
+        out = dfe.nn.SpatialMatching(mh, mw, False).forward([t1, t2])
+        return out.cpu().numpy(), ctx.last_kernel()
+
+    for K, H1, W1, mh, mw, own in ((16, 16, 16, 8, 8, "feat_matching_win64_kernel"), (8, 8, 400, 4, 8, "feat_matching_rows_kernel"), (7, 8, 399, 4, 8, "feat_matching_kernel")):
+        in1 = rng.standard_normal((K, H1, W1)).astype(np.float32)
+        in2 = rng.standard_normal((K, H1 + mh - 1, W1 + mw - 1)).astype(np.float32)
+        t1, t2 = T(in1, cuda), T(in2, cuda)
+        ref = orc.spatial_matching(in1, in2, mh, mw)
+        got, name = run(K, H1, W1, mh, mw)
+        assert name == own and np.array_equal(got, ref), (name, own)
+        if mh * mw == 64:
+            with ctx.options(fm64=0):
+                got, name = run(K, H1, W1, mh, mw)
+            assert name == "feat_matching_kernel" and np.array_equal(got, ref), name
+        else:
+            for rows, forced in ((0, "feat_matching_kernel"), (1, "feat_matching_rows_kernel")):
+                with ctx.options(fm_rows=rows):
+                    got, name = run(K, H1, W1, mh, mw)
+                assert name == forced and np.array_equal(got, ref), (rows, name)
 
 
 @pytest.mark.parametrize("mh,mw", [(17, 17), (16, 16), (10, 16)])
@@ -1155,16 +1250,34 @@ def test_entry_points_run_on_their_ctx_device_and_leave_the_callers_alone(dfe, c
     (60, 300, [(3, 17, 17, 8)], 17),                 # the script's geometry with fewer planes: 17 x 17 kernel, 17 x 17 window (flat-tile matcher, extra row)
     (50, 330, [(3, 9, 9, 5)], 17),                  # ragged: W1 = 306 (not a multiple of 4), H1 = 26
     (48, 64, [(3, 5, 5, 4), (4, 3, 3, 6)], 9),      # two layers, small window (chunk matcher)
+    # windows whose crop has lead != trail and x != y (lWin, tWin, rWin, bWin below): a crop window swapped between x and y or off by one
+    # moves the first branch against the second.  W spans two 64-column tiles of the normalisation, H three 16-row tiles; normalization_k
+    # = 17 (the unrolled cn_fused_kernel<*, 17> with two frames and a crop) on two rows, 9 on the others
+    (45, 90, [(3, 5, 5, 4)], (16, 16, 17)),         # (7, 7, 8, 8)
+    (48, 91, [(3, 5, 5, 4)], (10, 17, 9)),          # (8, 4, 8, 5)
+    (46, 89, [(3, 5, 5, 4)], (17, 10, 17)),         # (4, 8, 5, 8)
+    (47, 92, [(3, 5, 5, 4)], (8, 16, 9)),           # (7, 3, 8, 4)
 ])
 def test_version2_one_call_equals_staged_and_oracle(dfe, cuda, H, W, layers, win):
     """version2/test.lua:40-51: getNetwork(datap), flat parameters loaded, forward on a frame pair, the dense decode.
     dfe_version2_flow_pair_f32 == the module-by-module host path bit for bit (volume, index, flows); both against the oracle
     composition (tests/refpath.version2_flow_oracle): the volume to 1e-4 relative (the normalisation divides by a device sqrt), the
-    arg-min wherever the oracle's two smallest costs are not within that band."""
+    arg-min wherever the oracle's two smallest costs are not within that band.  win: one number (square window, normalization_k = 9) or
+    (hWin, wWin, normalization_k).
+    getNetwork passes the crop as the script does, (l, t, r, b) into SpatialPadding(l, r, t, b): that is the intended crop only where tWin
+    == rWin (17 x 17), any other window stops in the matcher's size check, as in the reference.  For those rows that is pinned first; then
+    the staged network gets the crop in SpatialPadding's own order -- a torch slice, independent of the one call's crop window -- and the
+    comparison is the same.  (The oracle alone has clear.mean() == 1.0 on the four new rows.)"""
     v2 = dfe.version2
-    datap = v2.defaultDatap(wImg=W, hImg=H, normalization_k=9, layers=layers, wWin=win, hWin=win)
+    hWin, wWin, nk = win if isinstance(win, tuple) else (win, win, 9)
+    datap = v2.defaultDatap(wImg=W, hImg=H, normalization_k=nk, layers=layers, wWin=wWin, hWin=hWin)
     g = torch.Generator().manual_seed(H + W)
     net = v2.getNetwork(datap, device=cuda, generator=g)
+    if datap["tWin"] != datap["rWin"]:
+        with pytest.raises(ValueError, match="SpatialMatching"):
+            net.forward([torch.zeros((3, H, W), device=cuda), torch.zeros((3, H, W), device=cuda)])
+        assert type(net.modules[0].modules[0].modules[1]) is dfe.radial.SpatialPadding
+        net.modules[0].modules[0].modules[1] = dfe.radial.SpatialPadding(-datap["lWin"], -datap["rWin"], -datap["tWin"], -datap["bWin"])
     flat = (torch.rand(net.flatParameters().numel(), generator=g) - 0.5) * 0.2
     net.loadParameters(flat)                                               # parameters:copy(torch.load(...))
     assert torch.equal(net.flatParameters().cpu(), flat)
@@ -1180,7 +1293,7 @@ def test_version2_one_call_equals_staged_and_oracle(dfe, cuda, H, W, layers, win
     for k in ("volume", "index", "xflow", "yflow"):
         assert torch.equal(staged[k], one[k]), k
     lean = v2.flowPair(net, datap, tp, tc, one_call=True, want_volume=False)   # nobody reads the volume: matcher + first-min decode in one kernel
-    if win in (16, 17) and W - (win - 1) - (datap["wKernel"] - 1) >= 253:
+    if hWin == wWin and hWin in (16, 17) and W - (wWin - 1) - (datap["wKernel"] - 1) >= 253:
         assert dfe.get_ctx(0).last_kernel() == "feat_matching_flat_kernel+argmin"
     for k in ("index", "xflow", "yflow"):
         assert torch.equal(lean[k], one[k]), k

@@ -10,7 +10,7 @@ from tests import oracle as orc
 from tests import pyramid_cases as pc
 
 
-@pytest.mark.parametrize("c", pc.CASES, ids=[c.id for c in pc.CASES])
+@pytest.mark.parametrize("c", pc.CASES + [pc.SWITCH_ORACLE], ids=[c.id for c in pc.CASES + [pc.SWITCH_ORACLE]])
 def test_row_has_few_ties_and_reaches_its_scales(c):
     assert all(c.H % r == 0 and c.W % r == 0 for r in c.ratios)
     bases, ncls = pc.class_bases(c.ratios, c.mh, c.mw)
@@ -25,6 +25,20 @@ def test_row_has_few_ties_and_reaches_its_scales(c):
         for s, w in enumerate(c.wins):
             if w >= pc.MIN_WINS:
                 assert wins[s] >= pc.MIN_WINS, "scale %d wins %d pixels only (%d when the table was made)" % (s, wins[s], w)
+
+
+def test_switch_row_is_what_the_switch_suite_needs():
+    """row 21: the fp16 oracle chain has few fp32-rule ties too, the share of pixels the fp16 rule may excuse is the measured one (the rule
+    itself caps the pixels that differ at 2 %), every scale wins pixels, and the coarsest scale is one tile of 5 row groups high"""
+    c = pc.SWITCH_ORACLE
+    ref = pc.reference(c.no, 1.0)
+    top2 = ref["top2"]
+    share16 = float((top2[..., 1] - top2[..., 0] <= 2e-3 * np.maximum(top2[..., 1], 1e-6) + 1e-5).mean())
+    print("row %d, fp16 chain: fp32-rule tie share %.4f, fp16-rule share %.4f (table %.4f)" % (c.no, float(pc.tie_mask(ref).mean()), share16, c.ties16))
+    assert float(pc.tie_mask(ref).mean()) <= pc.TIE_CAP and abs(share16 - c.ties16) <= 0.005
+    assert all(w >= pc.MIN_WINS for w in c.wins)
+    assert c.H // c.ratios[-1] == 6 * 5 - 6 and (c.W // 8) % 4 == 1 and (c.W // c.ratios[-1]) % 32 == 2
+    assert (c.mh, c.mw, c.k, c.C) == (8, 8, 7, 3)
 
 
 def test_prep_tiles_oracle_row_has_few_ties():
