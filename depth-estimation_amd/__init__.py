@@ -41,6 +41,9 @@ no CPU fallback -- a missing library or device raises.
                                                         the census cost -- sgm_plane.py)
     semiGlobalPick, flowDepthPair(..., sgm=(P1, P2))    (not in the reference: a uniqueness confidence and a sub-pixel flow read off the
                                                         aggregate, and the SSD step through it in one call -- sgm_plane.py, subpixel.py)
+    censusRadialCostVolume, censusRadialFlow, censusRadialFlowDepth     (not in the reference: the census cost down the polar rows with a
+                                                        box whose columns are a ring -- the radial path for frame pairs whose exposure
+                                                        differs, with no trained weights -- census_radial.py)
     getModel(geometry).forwardFlow                      (a trained single-scale model per frame pair in one call,
                                                         output_extraction_method 'max' or 'mean' -- network.py)
     imageScale, DepthEstimationAPI(...).nextFrameDepth  (image.scale; depth_estimation_api.lua:134-198, video -> depth per camera
@@ -77,6 +80,7 @@ from .network import getFilter, getFilterRadial, getModel, tables_random  # noqa
 from .radial import (getRMax, getC2PMask, getP2CMask, cartesian2polar, flow2depth, getKOutput, getP2CMaskOF,  # noqa: F401
                      computeDepthMapFromFlow, getTesterNetwork, getTrainerNetwork, getMatcher, radialFlowDepth, radial_out_shape, refineRadialFlowSubpixel,
                      semiGlobalAggregate)
+from .census_radial import censusRadialCostVolume, censusRadialFlow, censusRadialFlowDepth  # noqa: F401
 from .glue import SmartReshape, FunctionWrapper, Mul2, Log2, OutputExtractor, postProcessImage, enlargeMask  # noqa: F401
 from . import stream  # noqa: F401
 from .stream import imageScale, DepthEstimationAPI  # noqa: F401

@@ -190,6 +190,10 @@ PROTOTYPES = {
                                             + [C.c_void_p] * 5),
     "dfe_census_flow_depth_pair_sgm2_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_float] * 5 + [C.c_uint, C.c_int, C.c_float]
                                            + [C.c_void_p] * 5),
+    "dfe_census_radial_cost_volume_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    "dfe_census_radial_flow_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p] * 4),
+    "dfe_census_radial_flow_depth_pair_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint,
+                                                        C.c_int, C.c_int] + [C.c_void_p] * 7),
     "dfe_corner_response_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dfe_select_corners_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "dfe_pyr_down_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -214,6 +218,12 @@ class RadialParams(C.Structure):
     _fields_ = [("C", C.c_int), ("hImg", C.c_int), ("wImg", C.c_int), ("hInput", C.c_int), ("wInput", C.c_int), ("hWin", C.c_int),
                 ("n1", C.c_int), ("kW1", C.c_int), ("n2", C.c_int), ("kH2", C.c_int), ("tanh_between", C.c_int),
                 ("alpha_polar", C.c_float), ("kinfty", C.c_double), ("zero_last_row", C.c_int)]
+
+
+class CensusRadialParams(C.Structure):
+    """dfe_census_radial_params (include/dfe.h)"""
+    _fields_ = [("C", C.c_int), ("hImg", C.c_int), ("wImg", C.c_int), ("hInput", C.c_int), ("wInput", C.c_int), ("hWin", C.c_int),
+                ("kh", C.c_int), ("kw", C.c_int), ("agg", C.c_int), ("alpha_polar", C.c_float), ("kinfty", C.c_double), ("zero_last_row", C.c_int)]
 
 
 class TrackerParams(C.Structure):

@@ -498,6 +498,19 @@ DFE_HIDDEN size_t dfe_sgm_work_planes(unsigned paths, bool agg_given);
 DFE_HIDDEN int dfe_sgm_run(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *work, float *agg,
                            float *flow);
 
+// radial_pipeline.hip -- the stages around the matcher that the radial one calls and the census radial one call (census_radial.hip) share
+// the warp's buffers: two polar frames [C][H][Wp], the radius table (H floats), the angle's sine and cosine (W doubles each), and the
+// channel-interleaved copies of the frames (hImg * wImg float4 each; i0 == NULL: the planar taps)
+struct DfeRadialWarpBufs { float *pol0, *pol1, *rt; double *sn, *cs; float4 *i0, *i1; };
+DFE_HIDDEN double dfe_radial_rmax(double h, double w, double ex, double ey);   // getRMax
+DFE_HIDDEN int dfe_radial_warp_pair(dfe_ctx *ctx, const float *prev, const float *cur, int C, int hImg, int wImg, int H, int W, int lpad, int Wp,
+                                    float alpha_polar, double e2x, double e2y, double rmax, const DfeRadialWarpBufs &b);
+// the P2C sample of the polar flow [hm][W] and flow2depth; kH2 = hKernel of getP2CMaskOF / getKOutput
+DFE_HIDDEN int dfe_radial_p2c_depth(dfe_ctx *ctx, const float *pflow, int hImg, int wImg, int H, int W, int hm, int kH2, int hWin, float alpha_polar,
+                                    double kinfty, double e2x, double e2y, double rmax, int hOut, int wOut, float *cart_flow, float *depth, float *conf);
+// dfe_radial_refine_subpixel_f32's launch behind its checks (fout may be fin)
+DFE_HIDDEN int dfe_radial_refine_run(dfe_ctx *ctx, const float *vol, const float *fin, long long P, int hWin, float *fout);
+
 // census.hip -- the front end of every census one call (census.hip's own, and the two that aggregate in sgm_pick.hip)
 struct DfeCensusPair { int Hp, Wp, Ha, Wa, pad_t, pad_l; };   // patch positions, the aggregated cost's region, where it is pasted
 // the one call's checks in their order -- tensors / depth_pair: what the entry found of its pointers -- and the geometry behind them

@@ -406,6 +406,55 @@ int launch_conv_rows(dfe_ctx *ctx, const float *in, const float *w, const float 
 
 }  // namespace
 
+// ---- the stages around the matcher, shared with the census radial one call (census_radial.hip); declared in dfe_internal.h ----
+double dfe_radial_rmax(double h, double w, double ex, double ey) { return lua_rmax(h, w, ex, ey); }
+
+// both frames to polar (getC2PMask's constants: cartesian2polar.lua:13-14); b.i0 == NULL: the planar taps
+int dfe_radial_warp_pair(dfe_ctx *ctx, const float *prev, const float *cur, int C, int hImg, int wImg, int H, int W, int lpad, int Wp, float alpha_polar,
+                         double e2x, double e2y, double rmax, const DfeRadialWarpBufs &b) {
+    const float kr = (float)(rmax / pow((double)H, (double)alpha_polar));
+    const float ktheta = (float)(2 * M_PI / W);
+    hipLaunchKernelGGL(polar_tables_kernel, dim3(dfe_cdiv(H > W ? H : W, 256)), dim3(256), 0, ctx->stream, W, H, kr, ktheta, alpha_polar, b.rt, b.sn, b.cs);
+    if (b.i0) {
+        hipLaunchKernelGGL(interleave_pair_kernel, dim3(dfe_grid1d((long long)hImg * wImg)), dim3(256), 0, ctx->stream, prev, cur, C, (long long)hImg * wImg,
+                           b.i0, b.i1);
+        hipLaunchKernelGGL(polar_warp_pair_kernel<true>, dim3(dfe_cdiv(H, 8) * dfe_cdiv(Wp, 32)), dim3(256), 0, ctx->stream, (const float *)b.i0,
+                           (const float *)b.i1, C, hImg, wImg, W, H, Wp, lpad, (float)e2x, (float)e2y, b.rt, b.sn, b.cs, b.pol0, b.pol1);
+    } else {
+        hipLaunchKernelGGL(polar_warp_pair_kernel<false>, dim3(dfe_cdiv(H, 8) * dfe_cdiv(Wp, 32)), dim3(256), 0, ctx->stream, prev, cur, C, hImg, wImg, W, H,
+                           Wp, lpad, (float)e2x, (float)e2y, b.rt, b.sn, b.cs, b.pol0, b.pol1);
+    }
+    DFE_LAUNCH_CHECK(ctx);
+    return DFE_OK;
+}
+
+// polar flow [hm][W] -> cartesian -> depth (getP2CMaskOF + flow2depth with center2 = e2 * getKOutput); kH2 = hKernel
+int dfe_radial_p2c_depth(dfe_ctx *ctx, const float *pflow, int hImg, int wImg, int H, int W, int hm, int kH2, int hWin, float alpha_polar, double kinfty,
+                         double e2x, double e2y, double rmax, int hOut, int wOut, float *cart_flow, float *depth, float *conf) {
+    const double kOut = (double)hm / (double)H;
+    // newRMax stays a double up to ky, as in the reference (a Lua number: polar.lua:25, cartesian2polar.lua:59; only the finished ky
+    // is narrowed to float, :67) -- dfe_polar_grid_p2c_f32 takes it as a double for the same reason
+    const double nrmax = rmax * kOut;
+    const float pi2 = (float)(2 * M_PI);
+    const float kx = (float)((double)W / (2 * M_PI));
+    const float ky = (float)((double)hm / pow(nrmax, 1.0 / (double)alpha_polar));
+    const float invalpha = (float)(1.0 / (double)alpha_polar) * 0.5f;
+    const double kOut2 = (double)(H - (kH2 - 1) / 2 - hWin + 1) / (double)H;           // getKOutput polar.lua:12-16 (sic: not kOut)
+    const double c2x = e2x * kOut2, c2y = e2y * kOut2;
+    const float infty = (float)(lua_rmax(hImg, wImg, c2x, c2y) * kinfty);
+    hipLaunchKernelGGL(p2c_flow_depth_kernel, dim3(dfe_grid1d((long long)hOut * wOut)), dim3(256), 0, ctx->stream, pflow, hm, W, wOut, hOut,
+                       (float)(e2x * kOut), (float)(e2y * kOut), kx, ky, pi2, invalpha, (float)c2x, (float)c2y, infty, cart_flow, depth, conf);
+    DFE_LAUNCH_CHECK(ctx);
+    return DFE_OK;
+}
+
+// radial_refine_subpixel_kernel behind the entry's checks
+int dfe_radial_refine_run(dfe_ctx *ctx, const float *vol, const float *fin, long long P, int hWin, float *fout) {
+    hipLaunchKernelGGL(radial_refine_subpixel_kernel, dim3(dfe_grid1d(P)), dim3(256), 0, ctx->stream, vol, fin, P, hWin, fout);
+    DFE_LAUNCH_CHECK(ctx);
+    return DFE_OK;
+}
+
 // separable stack: fast kernels for the shapes with an instantiation, the generic direct convolution otherwise (same sums)
 static int radial_filter(dfe_ctx *ctx, const dfe_radial_params *p, const float *polar, int H, int Wp, const float *w1, const float *b1,
                          const float *w2, const float *b2, float *tmp, float *feat) {
@@ -537,23 +586,12 @@ static int radial_flow_depth_pair(dfe_ctx *ctx, const char *fn, bool sub, const 
     if (rc) return rc;
     if (polar_flow) pflow = polar_flow;
 
-    const double rmax = lua_rmax(p->hImg, p->wImg, e2x, e2y);
+    const double rmax = dfe_radial_rmax(p->hImg, p->wImg, e2x, e2y);
     std::unique_ptr<DfeStageScope> stage(new DfeStageScope(ctx, DFE_STAGE_FILTER));   // polar warps + filters
-    {   // 1. both frames to polar (getC2PMask's constants: cartesian2polar.lua:13-14)
-        const float kr = (float)(rmax / pow((double)H, (double)p->alpha_polar));
-        const float ktheta = (float)(2 * M_PI / W);
-        hipLaunchKernelGGL(polar_tables_kernel, dim3(dfe_cdiv(H > W ? H : W, 256)), dim3(256), 0, ctx->stream, W, H, kr, ktheta, p->alpha_polar, rt, sn, cs);
-        if (il) {
-            hipLaunchKernelGGL(interleave_pair_kernel, dim3(dfe_grid1d((long long)p->hImg * p->wImg)), dim3(256), 0, ctx->stream, prev, cur, p->C,
-                               (long long)p->hImg * p->wImg, i0, i1);
-            hipLaunchKernelGGL(polar_warp_pair_kernel<true>, dim3(dfe_cdiv(H, 8) * dfe_cdiv(Wp, 32)), dim3(256), 0, ctx->stream, (const float *)i0,
-                               (const float *)i1, p->C, p->hImg, p->wImg, W, H, Wp, lpad, (float)e2x, (float)e2y, rt, sn, cs, pol0, pol1);
-        } else {
-            hipLaunchKernelGGL(polar_warp_pair_kernel<false>, dim3(dfe_cdiv(H, 8) * dfe_cdiv(Wp, 32)), dim3(256), 0, ctx->stream, prev, cur, p->C, p->hImg,
-                               p->wImg, W, H, Wp, lpad, (float)e2x, (float)e2y, rt, sn, cs, pol0, pol1);
-        }
-        DFE_LAUNCH_CHECK(ctx);
-    }
+    // 1. both frames to polar
+    rc = dfe_radial_warp_pair(ctx, prev, cur, p->C, p->hImg, p->wImg, H, W, lpad, Wp, p->alpha_polar, e2x, e2y, rmax,
+                              DfeRadialWarpBufs{pol0, pol1, rt, sn, cs, il ? i0 : nullptr, i1});
+    if (rc) return rc;
     // 2. shared filter on both polar frames.  The reference crops the previous frame's last hWin-1 rows BEFORE its filter
     //    (SpatialPadding(0,0,0,-hWin+1), network.lua:59); a valid correlation's surviving rows do not see the cropped ones, so
     //    the full frame is filtered and the matcher reads the first hm rows of each feature plane (plane pitch Hf2 rows).
@@ -575,31 +613,16 @@ static int radial_flow_depth_pair(dfe_ctx *ctx, const char *fn, bool sub, const 
         rc = dfe_sgm_run(ctx, vol, hm, W, p->hWin, sg->P1, sg->P2, sg->paths, sg->ring, swork, abuf, pflow);
         if (rc) return rc;
         if (sg->subpixel) {
-            hipLaunchKernelGGL(radial_refine_subpixel_kernel, dim3(dfe_grid1d((long long)hm * W)), dim3(256), 0, ctx->stream, abuf, pflow, (long long)hm * W,
-                               p->hWin, pflow);
-            DFE_LAUNCH_CHECK(ctx);
+            rc = dfe_radial_refine_run(ctx, abuf, pflow, (long long)hm * W, p->hWin, pflow);
+            if (rc) return rc;
         }
         if (p->zero_last_row) DFE_HIP(ctx, hipMemsetAsync(pflow + (size_t)(hm - 1) * W, 0, (size_t)W * sizeof(float), ctx->stream));
     }
     stage.reset();
     stage.reset(new DfeStageScope(ctx, DFE_STAGE_EXTRACT));
-    {   // 4. polar flow -> cartesian -> depth (getP2CMaskOF + flow2depth with center2 = e2 * getKOutput)
-        const double kOut = (double)hm / (double)H;
-        // newRMax stays a double up to ky, as in the reference (a Lua number: polar.lua:25, cartesian2polar.lua:59; only the finished ky
-        // is narrowed to float, :67) -- dfe_polar_grid_p2c_f32 takes it as a double for the same reason
-        const double nrmax = rmax * kOut;
-        const float pi2 = (float)(2 * M_PI);
-        const float kx = (float)((double)W / (2 * M_PI));
-        const float ky = (float)((double)hm / pow(nrmax, 1.0 / (double)p->alpha_polar));
-        const float invalpha = (float)(1.0 / (double)p->alpha_polar) * 0.5f;
-        const double kOut2 = (double)(H - (p->kH2 - 1) / 2 - p->hWin + 1) / (double)H;           // getKOutput polar.lua:12-16 (sic: not kOut)
-        const double c2x = e2x * kOut2, c2y = e2y * kOut2;
-        const float infty = (float)(lua_rmax(p->hImg, p->wImg, c2x, c2y) * p->kinfty);
-        hipLaunchKernelGGL(p2c_flow_depth_kernel, dim3(dfe_grid1d((long long)hOut * wOut)), dim3(256), 0, ctx->stream, pflow, hm, W, wOut, hOut,
-                           (float)(e2x * kOut), (float)(e2y * kOut), kx, ky, pi2, invalpha, (float)c2x, (float)c2y, infty,
-                           cart_flow, depth, conf);
-        DFE_LAUNCH_CHECK(ctx);
-    }
+    // 4. polar flow -> cartesian -> depth
+    rc = dfe_radial_p2c_depth(ctx, pflow, p->hImg, p->wImg, H, W, hm, p->kH2, p->hWin, p->alpha_polar, p->kinfty, e2x, e2y, rmax, hOut, wOut, cart_flow, depth, conf);
+    if (rc) return rc;
     ctx->last_kernel = "radial_match_kernel";
     return DFE_OK;
 }

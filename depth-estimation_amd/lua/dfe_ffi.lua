@@ -8,6 +8,7 @@ ffi.cdef[[
 typedef struct dfe_ctx dfe_ctx;
 typedef struct dfe_stream dfe_stream;
 typedef struct dfe_radial_params { int C, hImg, wImg; int hInput, wInput; int hWin; int n1, kW1; int n2, kH2; int tanh_between; float alpha_polar; double kinfty; int zero_last_row; } dfe_radial_params;
+typedef struct dfe_census_radial_params { int C, hImg, wImg; int hInput, wInput; int hWin; int kh, kw; int agg; float alpha_polar; double kinfty; int zero_last_row; } dfe_census_radial_params;
 typedef struct dfe_filter_layer { int nIn, nOut, kH, kW; const float *weight; const float *bias; const int32_t *conn; int nConn; int tanh_after; } dfe_filter_layer;
 typedef struct dfe_tracker_params { int max_points; float quality; float min_dist; int win; int levels; int max_iters; float eps; float min_eig; float max_err; } dfe_tracker_params;
 typedef struct dfe_stream_params { int C, Hsrc, Wsrc; int hImg, wImg; double K[9]; int has_dist; double dist[5]; const dfe_filter_layer *layers; int nlayers; int maxh, maxw; int extraction; double threshold; int rectify; int fix_mask_offset; dfe_tracker_params tracker; double ransac_max_dist; int iterations; unsigned seed; double min_inlier_ratio; } dfe_stream_params;
@@ -68,6 +69,9 @@ int dfe_flow_depth_pair_sgm_f32(dfe_ctx *ctx, const float *I0, const float *I1, 
 int dfe_flow_depth_pair_sgm_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *scores, float *depth, float *depth_conf);
 int dfe_census_flow_depth_pair_sgm2_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *match, float *unique, float *depth, float *depth_conf);
 int dfe_census_flow_depth_pair_sgm2_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *match, float *unique, float *depth, float *depth_conf);
+int dfe_census_radial_cost_volume_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1, int C, int Hp, int W, int hWin, int agg, float *out);
+int dfe_census_radial_flow_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1, int C, int Hp, int W, int nbits, int hWin, int agg, int subpixel, int zero_last_row, float *volume, float *flow, float *best, float *match);
+int dfe_census_radial_flow_depth_pair_f32(dfe_ctx *ctx, const dfe_census_radial_params *p, const float *prev, const float *cur, double e2x, double e2y, float P1, float P2, unsigned paths, int ring, int subpixel, float *volume, float *agg_volume, float *polar_flow, float *match, float *cart_flow, float *depth, float *conf);
 int dfe_spatial_matching_backward_f32(dfe_ctx *ctx, const float *in1, const float *in2, const float *gradOut, int K, int H1, int W1, int maxh, int maxw, float *gradIn1, float *gradIn2);
 int dfe_radial_matching_backward_f32(dfe_ctx *ctx, const float *in1, const float *in2, const float *gradOut, int K, int H1, int W, int hWin, float *gradIn1, float *gradIn2);
 int dfe_argbest_center(dfe_ctx *ctx, const float *vol, int64_t P, int N, int middle, int take_max, int64_t *idx, float *best);

@@ -434,6 +434,62 @@ int dfe_census_flow_depth_pair_sgm2_u8(dfe_ctx *ctx, const uint8_t *I0, const ui
                                        int subpixel, float min_unique, float *flow, float *match, float *unique, float *depth,
                                        float *depth_conf);
 
+/* ---- the census cost for the radial (polar) matcher: an exposure-robust polar flow that needs no trained weights (NOT in the
+ * reference, whose radial matcher scores learned features by the sum of squared differences) ---------------- */
+/* Integers only up to the score, so every result below is exact.  With W = wInput, lpad = (kw - 1) / 2 and rpad = kw - 1 - lpad (the
+ * filter stack's rule for wKernel):
+ *   Signatures.  S = dfe_census_transform_f32 of a polar frame [C][hInput][W + kw - 1], as the polar warp makes it with lpad wrap
+ *     columns on the left: [C][Hp = hInput - kh + 1][W], column x's patch centred on polar column x.
+ *   Hamming.  h[y][x][d] = sum_c popcount(S0[c][y][x] ^ S1[c][y + d][x]), y < H1 = Hp - hWin + 1, 0 <= d < hWin: the geometry of
+ *     dfe_radial_matching_f32 (frame 0 is not centred, d = 0 is no motion).
+ *   Box.  agg = a in {1, 3, 5}, a <= W: cost[y][x][d] = sum_{u < a} sum_{v < a} h[y + u][(x + v - floor(a / 2)) mod W][d].  The rows
+ *     shrink to Ha = H1 - a + 1, indexed from the top-left as the Cartesian census cost is; the columns are a ring, so all W survive.
+ *     At most 63 C a^2 <= 6300: stored as an exact float.
+ *   Flow.  The first minimum over d by a strict `<` scan from 0, as a float; no centre rule (dfe_radial_match_argmin_f32's rule).
+ *   Match score.  match = 1.0f - (float)best / (float)(nbits C a^2): one rounded fp32 division, one rounded subtraction.
+ *   Sub-pixel.  dfe_radial_refine_subpixel_f32's rule on the float costs.
+ *   zero_last_row.  As in the radial entries: the last flow row is stored as 0 (best, match and the volume keep their values).
+ * Limits: 1 <= C <= 4, agg in {1, 3, 5} and agg <= W, nbits in 1 .. 63, hWin >= 1, no NULL input (DFE_E_ARG); Hp, W in 1 .. 32768,
+ * hWin <= Hp and Ha >= 1 (DFE_E_SHAPE).  Refused before any launch.  Asynchronous on the ctx's stream, under DFE_STAGE_MATCH.
+ * There is no byte entry: the polar warp interpolates, so byte frames have no exactness to offer on this path.
+ * The staged route: out [Ha][W][hWin], any hWin >= 1, a thread per cell. */
+int dfe_census_radial_cost_volume_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1, int C, int Hp, int W, int hWin,
+                                      int agg, float *out);
+/* The fused matcher, one launch: flow [Ha][W]; volume [Ha][W][hWin], best (the cost at the first minimum) and match [Ha][W] may
+ * each be NULL, and no volume reaches memory unless asked for.  hWin in {8, 12, 15, 16} (anything else: DFE_E_UNSUPPORTED, use the
+ * staged route + dfe_argbest_center + dfe_radial_refine_subpixel_f32, as with dfe_radial_match_argmin_f32).  A workgroup of four
+ * waves stages frame 1's signatures of its tile's rows in LDS; a lane keeps frame 0's signatures of its column (x0 - floor(a / 2) +
+ * lane) mod W in registers; the labels are dealt to the waves; the box sum is register adds down and DPP row shifts across; the costs
+ * of the tile meet in LDS for the scan, the sub-pixel rule and whole-line stores of the volume. */
+int dfe_census_radial_flow_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1, int C, int Hp, int W, int nbits, int hWin,
+                               int agg, int subpixel, int zero_last_row, float *volume, float *flow, float *best, float *match);
+typedef struct dfe_census_radial_params {
+    int C, hImg, wImg;     /* cartesian frames [C][hImg][wImg] */
+    int hInput, wInput;    /* polar image size before the kw - 1 wrap-around columns */
+    int hWin;              /* radial search window */
+    int kh, kw;            /* census patch: odd sides of at least 3, kh kw <= 64 */
+    int agg;               /* box side a: 1, 3 or 5 */
+    float alpha_polar;     /* radial exponent of the polar grid (1 = linear) */
+    double kinfty;         /* flow2depth's infinity factor, as in dfe_radial_params */
+    int zero_last_row;     /* as in dfe_radial_params */
+} dfe_census_radial_params;
+/* The radial path in one call with the census matcher in the filter stack's and the matcher's place.  prev / cur [C][hImg][wImg],
+ * (e2x, e2y) the epipole.  Order of work: the polar warps of both frames (dfe_radial_flow_depth_pair_f32's kernels, lpad wrap
+ * columns on the left), two transforms into the ctx's scratch arena, the fused matcher, the unchanged P2C sample and flow2depth.
+ * Geometry: hMatch = hInput - (kh - 1) - (hWin - 1) - (a - 1), and every formula of dfe_radial_flow_depth_pair_f32's last step with
+ * kH2 = kh + a - 1 -- dfe_radial_out_shape with that kH2 gives hMatch, hOut and wOut.
+ * paths == 0: winner takes all.  paths in 1 .. 255: the matcher runs for its volume (to scratch when `volume` is NULL),
+ * dfe_sgm_aggregate_f32 (P1, P2, paths, ring) gives the aggregate and polar_flow = its first minimum, with subpixel the refinement
+ * runs on the AGGREGATE, and match is the census score of the RAW cost at the chosen integer label.
+ * Outputs (each may be NULL): volume, agg_volume [hMatch][wInput][hWin] (agg_volume only with paths != 0), polar_flow, match
+ * [hMatch][wInput], cart_flow / depth / conf [hOut][wOut].  hWin in {8, 12, 15, 16}.  Every argument is checked before any launch:
+ * the limits above, kh / kw as for dfe_census_transform_f32, dfe_sgm_aggregate_f32's rules, agg_volume != volume.  Bit-identical
+ * to the same steps as staged public calls. */
+int dfe_census_radial_flow_depth_pair_f32(dfe_ctx *ctx, const dfe_census_radial_params *p, const float *prev, const float *cur,
+                                          double e2x, double e2y, float P1, float P2, unsigned paths, int ring, int subpixel,
+                                          float *volume, float *agg_volume, float *polar_flow, float *match, float *cart_flow,
+                                          float *depth, float *conf);
+
 /* ---- N2: gradients of the two matchers (training drivers call model:backward through them) ------- */
 /* replaces: nn.SpatialMatching:updateGradInput / nn.SpatialRadialMatching:updateGradInput (un-vendored nnx), reached
  *   from radial/train_radial_opticalflow.lua:228-252 and opticalflow.lua:296-338.  gradOut has the forward output's
