@@ -194,7 +194,10 @@ PROTOTYPES = {
     "dfe_census_radial_flow_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p] * 4),
     "dfe_census_radial_flow_depth_pair_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint,
                                                         C.c_int, C.c_int] + [C.c_void_p] * 7),
-    "dfe_corner_response_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "dfe_census_pyramid_scale_volume_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_float, C.c_void_p]),
+    "dfe_multiscale_census_flow_pair_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [c_i32p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "dfe_multiscale_census_flow_pair_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [c_i32p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "dfe_corner_response_f32":(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dfe_select_corners_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "dfe_pyr_down_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dfe_track_points_lk_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

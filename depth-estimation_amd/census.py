@@ -11,6 +11,9 @@
         dfe_census_flow_depth_pair_f32 / _u8: frames -> flow, match score, depth, depth confidence, with flowDepthPair's keys;
         sgm=(P1, P2): dfe_census_flow_depth_pair_sgm_f32 / _u8, the cost aggregated along image paths before the arg-min (DESIGN section 4.31);
         with subpixel=True or min_unique in the dict: the _sgm2_ entries, which add the key unique
+    censusPyramidScaleVolume(i0, i1, r, k, maxh, maxw, agg=3, beta=None)
+        dfe_census_pyramid_scale_volume_f32: one scale of the census pyramid's volumes, staged (the matcher itself is
+        MultiscaleModel.forwardFlow(..., census=True), multiscale.py)
 """
 import torch
 
@@ -178,3 +181,44 @@ def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consis
             res["scores"] = res["scores"] * mask
             res["depth_conf"] = res["depth_conf"] * mask
     return _with_fill(res, fill, median, a, k, hWin, wWin, fx, fy, region=R)
+
+
+def _pyramid_args(name, C, k, agg, beta):
+    """(k, agg, beta) of a census pyramid call after its checks; beta=None: 0.25 / (C agg^2)"""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 3 or k % 2 == 0 or k * k > 64:
+        raise ValueError("%s: k=%r: an odd int of at least 3 with k k <= 64 expected" % (name, k))
+    if not isinstance(agg, int) or isinstance(agg, bool) or agg not in (1, 3, 5):
+        raise ValueError("%s: agg=%r must be 1, 3 or 5" % (name, agg))
+    if not 1 <= C <= 4:
+        raise ValueError("%s: %d channels (1 .. 4)" % (name, C))
+    if beta is None:
+        beta = 0.25 / (C * agg * agg)
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not (0.0 < float(beta) < float("inf")):
+        raise ValueError("%s: beta=%r must be finite and positive" % (name, beta))
+    return k, agg, float(beta)
+
+
+def censusPyramidScaleVolume(i0, i1, r, k, maxh, maxw, agg=3, beta=None):
+    """One scale of the census pyramid (include/dfe.h), staged: two float32 frames C x H x W (1 <= C <= 4), H and W
+    multiples of r, box down-sampled by r, zero-padded for the receptive field k + agg - 1, their k x k census signatures, the Hamming cost
+    summed over the channels and an agg x agg box for every cell of the maxh x maxw window, times beta (None: 0.25 / (C agg^2)).  float32
+    [H/r][W/r][maxh][maxw], the geometry and class order of dfe_pyramid_scale_volume_f32 (dfe_census_pyramid_scale_volume_f32)."""
+    name = "censusPyramidScaleVolume"
+    for t in (i0, i1):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError("%s: two float32 frames expected" % name)
+    if i0.dim() != 3 or i0.shape != i1.shape:
+        raise ValueError("%s: two C x H x W frames of one shape expected, got %s and %s" % (name, tuple(i0.shape), tuple(i1.shape)))
+    C, H, W = i0.shape
+    k, agg, beta = _pyramid_args(name, C, k, agg, beta)
+    if not all(isinstance(n, int) and not isinstance(n, bool) and n >= 1 for n in (r, maxh, maxw)):
+        raise ValueError("%s: r=%r, window %r x %r: positive ints expected" % (name, r, maxh, maxw))
+    if maxh * maxw > MAX_CELLS:
+        raise ValueError("%s: window %d x %d has more than %d cells" % (name, maxh, maxw, MAX_CELLS))
+    if H % r or W % r or H < r or W < r:
+        raise ValueError("%s: frame %d x %d is not a multiple of ratio %d" % (name, H, W, r))
+    i0, i1 = _on_device(name, (i0, i1), dtype=None, expected="CUDA tensors expected")
+    out = torch.empty((H // r, W // r, maxh, maxw), dtype=torch.float32, device=i0.device)
+    ctx = get_ctx(i0)
+    ctx.check(lib().dfe_census_pyramid_scale_volume_f32(ctx.handle, ptr(i0), ptr(i1), C, H, W, r, k, maxh, maxw, agg, beta, ptr(out)))
+    return out

@@ -303,7 +303,7 @@ const char *dfe_last_kernel(const dfe_ctx *ctx) { return ctx ? ctx->last_kernel 
 
 const char *dfe_multiscale_last_path(dfe_ctx *ctx) {
     if (!ctx) return "";
-    snprintf(ctx->ms_path, sizeof ctx->ms_path, "%s %s", ctx->ms_prep, ctx->ms_cascade);
+    snprintf(ctx->ms_path, sizeof ctx->ms_path, "%s %s%s%s", ctx->ms_prep, ctx->ms_cascade, *ctx->ms_census ? " " : "", ctx->ms_census);
     return ctx->ms_path;
 }
 

@@ -62,6 +62,7 @@ struct dfe_ctx {
     int ncu = 256;                    // compute units of the device
     const char *last_kernel = "";
     const char *ms_prep = "", *ms_cascade = "";   // the pyramid matcher's last preparation / cascade kernel (dfe_multiscale_last_path)
+    const char *ms_census = "";       // ... and its census volume kernel ("" where the last run scored by SSD)
     char ms_path[96] = "";
     DfeBuf scratch;                   // grow-only device arena (never shrinks; freed with the ctx), physically contiguous where the driver grants it
     DfeBuf scratch_plain;             // the arena of the paths that run learned filter stacks: a plain hipMalloc (dfe_scratch's `plain`)
@@ -525,3 +526,26 @@ DFE_HIDDEN int dfe_census_pair_transforms(dfe_ctx *ctx, const void *I0, const vo
 int dfe_multiscale_flow_pair_bytes(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int maxh, int maxw,
                                    const int *ratios, int nratios, float u8_scale, float f16_scale, float *flow, int64_t *idx, bool subpixel = false);
 int dfe_multiscale_subpixel_launch(dfe_ctx *ctx, const MsSubpixelArgs &a);
+// one scale's two frames, staged: box down-sample by r into d (2 * C * H/r * W/r floats; untouched for r = 1), zero-pad into p (2 * C * Hp * Wp)
+DFE_HIDDEN int dfe_pyramid_prep_scale(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int r, int pl, int pt, int Hp, int Wp, float *d,
+                                      float *p);
+// the one-call pyramid matcher in its census mode (dfe_multiscale_census_flow_pair_*); bytes: I0 / I1 are uint8 frames, taken as float(byte)
+DFE_HIDDEN int dfe_multiscale_census_pair(dfe_ctx *ctx, const void *I0, const void *I1, bool bytes, int C, int H, int W, int k, int maxh, int maxw,
+                                          const int *ratios, int nratios, int agg, float beta, float *flow, int64_t *idx, const char *entry);
+
+// census_pyramid.hip -- the census cost of the pyramid's scales, from the padded scale frames that ms_prep_raw leaves to the volumes the
+// cascade stages read
+struct DfeCensusPyramid {
+    int ns, C, k, maxh, maxw, agg;
+    float beta;
+    const float *p0[DFE_MAX_RATIOS], *p1[DFE_MAX_RATIOS];   // padded scale frames [C][Hp][Wp]
+    int Hp[DFE_MAX_RATIOS], Wp[DFE_MAX_RATIOS];
+    uint64_t *sig0[DFE_MAX_RATIOS], *sig1[DFE_MAX_RATIOS];  // signature planes [C][Hp - k + 1][Wp - k + 1]
+    float *cost[DFE_MAX_RATIOS];                            // volumes [Hs][Ws][maxh][maxw]
+};
+// k, C, agg and beta of every census pyramid entry (DFE_E_ARG)
+DFE_HIDDEN int dfe_census_pyramid_check(dfe_ctx *ctx, const char *fn, int C, int k, int agg, float beta);
+DFE_HIDDEN bool dfe_census_pyramid_fast(int maxh, int maxw);   // the window has the one-launch volume kernel
+DFE_HIDDEN int dfe_census_pyramid_signatures(dfe_ctx *ctx, const DfeCensusPyramid &a);   // every scale, both frames, one launch
+// every scale's volume: one launch where dfe_census_pyramid_fast, else the staged kernels scale by scale; names the route in ctx->ms_census
+DFE_HIDDEN int dfe_census_pyramid_volumes(dfe_ctx *ctx, const DfeCensusPyramid &a);

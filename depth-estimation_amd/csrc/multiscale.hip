@@ -946,6 +946,23 @@ int fill_cascade(dfe_ctx *ctx, CascadeGeom &g, const int *ratios, int nratios, i
 constexpr int PREP_EPT = 8;   // elements per thread of prep_scales_kernel (measured: EXPERIMENTS.md)
 }  // namespace
 
+// (declared in dfe_internal.h: the staged scale volumes of this file and of census_pyramid.hip start with it)
+int dfe_pyramid_prep_scale(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int r, int pl, int pt, int Hp, int Wp, float *d, float *p) {
+    const int Hs = H / r, Ws = W / r;
+    const size_t nd = (size_t)C * Hs * Ws, np = (size_t)C * Hp * Wp;
+    float *d0 = d, *d1 = d + nd, *p0 = p, *p1 = p + np;
+    const float *s0 = I0, *s1 = I1;
+    if (r > 1) {
+        hipLaunchKernelGGL(downsample_box_kernel, dim3(dfe_grid1d((long long)nd, 256)), dim3(256), 0, ctx->stream, I0, C, H, W, r, d0);
+        hipLaunchKernelGGL(downsample_box_kernel, dim3(dfe_grid1d((long long)nd, 256)), dim3(256), 0, ctx->stream, I1, C, H, W, r, d1);
+        s0 = d0; s1 = d1;
+    }
+    hipLaunchKernelGGL(zero_pad_kernel, dim3(dfe_grid1d((long long)np, 256)), dim3(256), 0, ctx->stream, s0, C, Hs, Ws, pl, pt, Hp, Wp, p0);
+    hipLaunchKernelGGL(zero_pad_kernel, dim3(dfe_grid1d((long long)np, 256)), dim3(256), 0, ctx->stream, s1, C, Hs, Ws, pl, pt, Hp, Wp, p1);
+    DFE_LAUNCH_CHECK(ctx);
+    return DFE_OK;
+}
+
 extern "C" {
 
 int dfe_downsample_box_f32(dfe_ctx *ctx, const float *img, int C, int H, int W, int r, float *out) {
@@ -972,16 +989,9 @@ int dfe_pyramid_scale_volume_f32(dfe_ctx *ctx, const float *I0, const float *I1,
     float *d, *p;   // both downsampled frames | both padded frames
     int rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { d = c.take<float>(2 * nd); p = c.take<float>(2 * np); });
     if (rc) return rc;
-    float *d0 = d, *d1 = d + nd, *p0 = p, *p1 = p + np;
-    const float *s0 = I0, *s1 = I1;
-    if (r > 1) {
-        hipLaunchKernelGGL(downsample_box_kernel, dim3(dfe_grid1d((long long)nd, 256)), dim3(256), 0, ctx->stream, I0, C, H, W, r, d0);
-        hipLaunchKernelGGL(downsample_box_kernel, dim3(dfe_grid1d((long long)nd, 256)), dim3(256), 0, ctx->stream, I1, C, H, W, r, d1);
-        s0 = d0; s1 = d1;
-    }
-    hipLaunchKernelGGL(zero_pad_kernel, dim3(dfe_grid1d((long long)np, 256)), dim3(256), 0, ctx->stream, s0, C, Hs, Ws, pl, pt, Hp, Wp, p0);
-    hipLaunchKernelGGL(zero_pad_kernel, dim3(dfe_grid1d((long long)np, 256)), dim3(256), 0, ctx->stream, s1, C, Hs, Ws, pl, pt, Hp, Wp, p1);
-    DFE_LAUNCH_CHECK(ctx);
+    rc = dfe_pyramid_prep_scale(ctx, I0, I1, C, H, W, r, pl, pt, Hp, Wp, d, p);
+    if (rc) return rc;
+    float *p0 = p, *p1 = p + np;
     // frame-0 crop floor/ceil((maxw-1)/2) (:198-202) is the oy/ox offset of the cost-volume op
     return cv_frames_dispatch(ctx, p0, p1, C, Hp, Wp, (long long)Hp * Wp, kh, kw, maxh, maxw, out);
 }
@@ -1003,6 +1013,10 @@ struct MsArgs {
     float u8_scale;
     bool subpixel;                 // the sub-pixel refinement behind the matcher (raw patches only; flow required)
     const char *entry;             // the C entry's name, for its error messages (NULL: dfe_multiscale_flow_pair_f32)
+    // census mode (census_agg != 0; raw frames, fp32 volumes, no refinement): every scale's volume is the aggregated census cost * census_beta
+    // (census_pyramid.hip), the receptive field k + census_agg - 1
+    int census_agg = 0;
+    float census_beta = 0.f;
 };
 // one scale's sizes
 struct MsScale {
@@ -1036,6 +1050,7 @@ struct MsBufs {
     float *prob[DFE_MAX_RATIOS];                      // soft-min probabilities (lane <-> cell) / cascaded windows (lane <-> pixel)
     float2 *best[DFE_MAX_RATIOS];                     // running best (lane <-> pixel)
     float *feat[DFE_MAX_RATIOS][4];                   // learned filters: four feature buffers (ping-pong per frame), each the largest layer output
+    uint64_t *sig0[DFE_MAX_RATIOS], *sig1[DFE_MAX_RATIOS];   // census mode: signature planes [C][Hp - k + 1][Wp - k + 1]
     int64_t *idx_tmp;                                 // sub-pixel entry called without idx: the class map the refinement reads
 };
 // what the launchers report back and a later stage depends on
@@ -1067,6 +1082,13 @@ static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
     DFE_REQUIRE(ctx, a.I0 && a.I1 && (a.flow || a.idx), DFE_E_ARG, "%s: NULL tensor", entry);
     DFE_REQUIRE(ctx, !a.subpixel || a.flow, DFE_E_ARG, "%s: flow is NULL", entry);
     DFE_REQUIRE(ctx, C > 0 && k > 0 && maxh > 0 && maxw > 0, DFE_E_ARG, "%s: bad size", entry);
+    const bool census = a.census_agg != 0;
+    if (census) {
+        const int crc = dfe_census_pyramid_check(ctx, entry, C, k, a.census_agg, a.census_beta);
+        if (crc) return crc;
+        DFE_REQUIRE(ctx, maxh * (long long)maxw <= kDfeMaxWindowCells, DFE_E_UNSUPPORTED, "%s: window %dx%d has more than %d cells", entry, maxh, maxw,
+                    kDfeMaxWindowCells);
+    }
     P.a = a;
     P.fx = a.flow ? a.flow + (size_t)H * W : nullptr;
     int rc = fill_cascade(ctx, P.g, ratios, nratios, maxh, maxw);
@@ -1075,7 +1097,7 @@ static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
     const int N = P.N = maxh * maxw;
     P.middle = dfe_window_middle(maxh, maxw);   // yx2xMulti(0, 0)
     int maxplanes = C;
-    P.hk = P.wk = k;
+    P.hk = P.wk = census ? k + a.census_agg - 1 : k;   // (census: the patch and the box behind it)
     if (a.filt) {
         rc = ms_filter_field(ctx, a, &P.hk, &P.wk, &maxplanes);
         if (rc) return rc;
@@ -1089,6 +1111,7 @@ static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
         DFE_REQUIRE(ctx, H % r == 0 && W % r == 0, DFE_E_SHAPE,
                     "%s: frame %dx%d is not a multiple of ratio %d (opticalflow_model_multiscale.lua:238-243)", entry, H, W, r);
         sc.Hs = H / r; sc.Ws = W / r; sc.Hp = sc.Hs + hp; sc.Wp = sc.Ws + wp;
+        DFE_REQUIRE(ctx, !census || (sc.Hp <= 32768 && sc.Wp <= 32768), DFE_E_SHAPE, "%s: padded scale %dx%d (up to 32768 a side)", entry, sc.Hp, sc.Wp);
     }
     P.mg.maxh = maxh; P.mg.maxw = maxw; P.mg.nratios = nratios;
     P.frame_max = 0;
@@ -1137,6 +1160,7 @@ static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
                                                       (ctx->opt[DFE_OPT_MID_NQ] != 5 || P.sc[1].Hs >= 24)));
     P.fuse_mid = P.fuse_fine && a.f16_scale == 0.f && (long long)H * W >= 1500000ll && mid_shape;
     if (ctx->opt[DFE_OPT_MID_FUSE] >= 0) P.fuse_mid = P.fuse_fine && ctx->opt[DFE_OPT_MID_FUSE] != 0 && mid_shape;
+    if (census) P.fuse_fine = P.fuse_mid = false;     // (census materialises every scale's volume: the fused epilogues score by SSD)
     P.s0 = P.fuse_mid ? 2 : P.fuse_fine ? 1 : 0;      // the first scale whose volume is materialised
     // where the coarsest scale is the parent of a fused scale it needs a launch of its own (it cannot be recomputed inside its child's)
     P.lone_parent = (P.fuse_mid && nratios == 3) || (P.fuse_fine && !P.fuse_mid && nratios == 2);
@@ -1171,6 +1195,9 @@ static MsBufs ms_bufs(const MsPlan &P, DfeCarve &c, bool frames_only = false) {
         B.cost[s] = c.take<float>(nv);
         B.prob[s] = c.take<float>(nv);
         B.best[s] = c.take<float2>(frames_only ? 0 : (size_t)sc.Hs * sc.Ws);
+        const size_t ng = a.census_agg ? (size_t)a.C * (sc.Hp - a.k + 1) * (sc.Wp - a.k + 1) : 0;
+        B.sig0[s] = c.take<uint64_t>(2 * ng);
+        B.sig1[s] = B.sig0[s] ? B.sig0[s] + ng : nullptr;
     }
     B.idx_tmp = c.take<int64_t>(a.subpixel && !a.idx ? (size_t)a.H * a.W : 0);
     return B;
@@ -1455,6 +1482,21 @@ static int ms_cascade_cell(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const
     return DFE_OK;
 }
 
+// census mode: every scale's signatures in one launch, every scale's volume in one more (census_pyramid.hip)
+static int ms_census_volumes(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B) {
+    const MsArgs &a = P.a;
+    DfeCensusPyramid cp{};
+    cp.ns = a.nratios; cp.C = a.C; cp.k = a.k; cp.maxh = a.maxh; cp.maxw = a.maxw; cp.agg = a.census_agg; cp.beta = a.census_beta;
+    for (int s = 0; s < a.nratios; ++s) {
+        cp.p0[s] = B.p0[s]; cp.p1[s] = B.p1[s]; cp.Hp[s] = P.sc[s].Hp; cp.Wp[s] = P.sc[s].Wp;
+        cp.sig0[s] = B.sig0[s]; cp.sig1[s] = B.sig1[s]; cp.cost[s] = B.cost[s];
+    }
+    int rc = dfe_census_pyramid_signatures(ctx, cp);
+    if (rc) return rc;
+    DfeStageScope st(ctx, DFE_STAGE_MATCH);
+    return dfe_census_pyramid_volumes(ctx, cp);
+}
+
 // every launch of one call, in order
 // the scales are independent until the cascade: one launch prepares every scale's frames, one per scale builds its
 // volume, one takes every soft-min (2 + nratios launches + the cascade instead of 3 nratios + 1)
@@ -1462,9 +1504,14 @@ static int ms_run(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B) {
     MsRun R{};
     int rc = P.a.filt ? ms_learned_front(ctx, P, B, R) : ms_prep_raw(ctx, P, B);
     if (rc) return rc;
+    ctx->ms_census = "";
+    if (P.a.census_agg) {
+        rc = ms_census_volumes(ctx, P, B);
+        if (rc) return rc;
+    }
     // stage "match": volumes, soft-min, cascade + fused arg-max (with learned filters it re-opens behind the per-scale filter / matching scopes)
     DfeStageScope st(ctx, DFE_STAGE_MATCH);
-    if (!P.a.filt) {
+    if (!P.a.filt && !P.a.census_agg) {
         rc = ms_raw_volumes(ctx, P, B, R);
         if (rc) return rc;
     }
@@ -1495,8 +1542,8 @@ static int ms_subpixel(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const int
 // holds the sub-pixel switch too: the two entries never replay each other's capture.
 static int multiscale_flow_pair(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw,
                                 const int *ratios, int nratios, float *flow, int64_t *idx, float f16_scale, const MsFilter *filt = nullptr,
-                                float u8_scale = 0.f, bool subpixel = false, const char *entry = nullptr) {
-    const MsArgs a{I0, I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, f16_scale, filt, u8_scale, subpixel, entry};
+                                float u8_scale = 0.f, bool subpixel = false, const char *entry = nullptr, int census_agg = 0, float census_beta = 0.f) {
+    const MsArgs a{I0, I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, f16_scale, filt, u8_scale, subpixel, entry, census_agg, census_beta};
     MsPlan P;
     int rc = ms_plan(ctx, a, &P);
     if (rc) return rc;
@@ -1508,10 +1555,11 @@ static int multiscale_flow_pair(dfe_ctx *ctx, const float *I0, const float *I1, 
     rc = dfe_scratch(ctx, sizes.off, &scr, filt != nullptr);   // (learned filters: the convolutions' arena, see dfe_scratch)
     if (rc) return rc;
     // the same call again (same buffers, shapes and arena): replay its launches as a graph
-    struct { const void *I0, *I1, *flow, *idx, *scr; int C, H, W, k, maxh, maxw, nratios, ratios[DFE_MAX_RATIOS]; float f16, u8; int subpixel; } gkey;
+    struct { const void *I0, *I1, *flow, *idx, *scr; int C, H, W, k, maxh, maxw, nratios, ratios[DFE_MAX_RATIOS]; float f16, u8; int subpixel; int agg; float beta; } gkey;
     memset(&gkey, 0, sizeof gkey);
     gkey.I0 = I0; gkey.I1 = I1; gkey.flow = flow; gkey.idx = idx; gkey.scr = scr;
     gkey.C = C; gkey.H = H; gkey.W = W; gkey.k = k; gkey.maxh = maxh; gkey.maxw = maxw; gkey.nratios = nratios; gkey.f16 = f16_scale; gkey.u8 = u8_scale; gkey.subpixel = subpixel;
+    gkey.agg = census_agg; gkey.beta = census_beta;
     for (int s = 0; s < nratios; ++s) gkey.ratios[s] = ratios[s];
     const int gmode = filt ? 0 : dfe_graph_lookup(ctx, ctx->ms_graph, &gkey, sizeof gkey);
     if (gmode == 2) {
@@ -1691,4 +1739,12 @@ int dfe_multiscale_flow_pair_bytes(dfe_ctx *ctx, const uint8_t *I0, const uint8_
                                    const int *ratios, int nratios, float u8_scale, float f16_scale, float *flow, int64_t *idx, bool subpixel) {
     return multiscale_flow_pair(ctx, (const float *)I0, (const float *)I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, f16_scale, nullptr, u8_scale,
                                 subpixel, subpixel ? "dfe_multiscale_flow_pair_subpixel_u8" : nullptr);
+}
+
+// the census mode behind dfe_multiscale_census_flow_pair_f32 / _u8 (census_pyramid.hip): bytes are taken as float(byte)
+int dfe_multiscale_census_pair(dfe_ctx *ctx, const void *I0, const void *I1, bool bytes, int C, int H, int W, int k, int maxh, int maxw, const int *ratios,
+                               int nratios, int agg, float beta, float *flow, int64_t *idx, const char *entry) {
+    DFE_REQUIRE(ctx, agg != 0, DFE_E_ARG, "%s: agg=%d must be 1, 3 or 5", entry, agg);   // (0 would select the SSD pyramid)
+    return multiscale_flow_pair(ctx, (const float *)I0, (const float *)I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, 0.f, nullptr, bytes ? 1.0f : 0.f,
+                                false, entry, agg, beta);
 }

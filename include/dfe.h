@@ -110,7 +110,9 @@ int dfe_get_option(dfe_ctx *ctx, const char *key, int *value);
 const char *dfe_last_kernel(const dfe_ctx *ctx);
 /* the preparation and cascade kernels of the last one-call pyramid matcher run on this ctx, "<prep> <cascade>" -- prep_scales_kernel or
  * prep_tiles_kernel (prep_frames_kernel with learned filters); cascade_px_kernel, cascade_argmax_kernel<fast> (one cell per lane) or
- * cascade_argmax_kernel<slow>, or the fused volume kernel's name where the finest scale has no launch of its own.  A graph replay
+ * cascade_argmax_kernel<slow>, or the fused volume kernel's name where the finest scale has no launch of its own.  After a census
+ * run (dfe_multiscale_census_flow_pair_*) a third word follows, "<prep> <cascade> <volume>": census_pyramid_volume_kernel (the
+ * one-launch kernel) or census_volume_kernel (the staged kernel, scale by scale).  A graph replay
  * keeps the names of its capture.  The string lives in the ctx and is rewritten by this call.  For tests and tuning. */
 const char *dfe_multiscale_last_path(dfe_ctx *ctx);
 /* which kernel produced the last single-scale flow step's result: *i8_taken = 1 the int8 matrix-core kernel (option "cv_i8": the frames
@@ -489,6 +491,40 @@ int dfe_census_radial_flow_depth_pair_f32(dfe_ctx *ctx, const dfe_census_radial_
                                           double e2x, double e2y, float P1, float P2, unsigned paths, int ring, int subpixel,
                                           float *volume, float *agg_volume, float *polar_flow, float *match, float *cart_flow,
                                           float *depth, float *conf);
+
+/* ---- the census cost in the pyramid matcher: an exposure-robust multiscale flow that needs no trained weights (NOT in the
+ * reference, whose pyramid scores raw patches by the sum of squared differences) ----------------------------- */
+/* Per scale with ratio r, for frames I0, I1 [C][H][W], H and W multiples of every ratio, k x k census patch, agg = a:
+ *   1. Down-sample.  Box down-sample by r with dfe_downsample_box_f32's bits; r = 1 is the frame itself.
+ *   2. Pad.  Zero-pad by hp = (maxh - 1) + (k - 1) + (a - 1) rows and wp = (maxw - 1) + (k - 1) + (a - 1) columns, pt = hp / 2 above
+ *      and pl = wp / 2 on the left (integer divisions), the rest below and on the right: the SSD pyramid's rule
+ *      (dfe_pyramid_scale_volume_f32) with the receptive field k + a - 1 in k's place.
+ *   3. Signatures.  dfe_census_transform_f32 with a k x k patch on both padded frames: [C][Hs + maxh - 1 + a - 1][Ws + maxw - 1 + a - 1],
+ *      Hs = H / r, Ws = W / r.  Strict comparison on the stored floats; the zero border compares like any value.
+ *   4. Cost.  dfe_census_cost_volume_f32(sig0, sig1, C, .., hWin = maxh, wWin = maxw, agg = a): the integer cost [Hs][Ws][maxh][maxw] in
+ *      the geometry and class order of the SSD scale volume (frame-0 offset floor((maxh - 1) / 2), floor((maxw - 1) / 2)); the a x a box
+ *      ends up centred on the pixel.
+ *   5. Stored value.  (float)cost * beta, one rounded fp32 multiply.  beta is the soft-min's temperature: a Hamming sum reaches
+ *      (k k - 1) C a^2, and unscaled the soft-min is one-hot, so that the cascade cannot weigh a scale against its parent.
+ *   6. Chain.  dfe_softmin_f32 per scale and dfe_cascade_flow_f32, as in dfe_multiscale_flow_pair_f32.
+ * Limits, refused before any launch: k odd, k >= 3, k k <= 64; 1 <= C <= 4; agg in {1, 3, 5}; beta finite and > 0; no NULL input
+ * (DFE_E_ARG); maxh maxw <= 1096 (DFE_E_UNSUPPORTED); every padded scale at most 32768 a side (DFE_E_SHAPE); and every ratio,
+ * ring-geometry and size rule of dfe_multiscale_flow_pair_f32.  Asynchronous on the ctx's stream.
+ * dfe_census_pyramid_scale_volume_f32: steps 1 - 5 for one scale, staged from the kernels of the entries named above plus the
+ *   multiply; out [H/r][W/r][maxh][maxw].  Any window.  For tests and for callers who want the volume. */
+int dfe_census_pyramid_scale_volume_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int r, int k, int maxh,
+                                        int maxw, int agg, float beta, float *out);
+/* The one call: flow [2][H][W] and / or idx [H][W] as dfe_multiscale_flow_pair_f32 gives them, bit-identical to
+ * dfe_census_pyramid_scale_volume_f32 per scale -> dfe_softmin_f32 -> dfe_cascade_flow_f32.  One launch prepares every scale's padded
+ * frames (the SSD pyramid's), one takes every scale's signatures, one builds every scale's volume (8 x 8 windows: frame 1's
+ * signatures of a tile in LDS, frame 0's of a lane's column in registers, the box sum by DPP row shifts and register adds, whole
+ * 128-byte lines stored; any other window: the staged volume kernel scale by scale), then the SSD pyramid's cascade launches.  Every
+ * scale's volume is materialised in the ctx's scratch arena.  dfe_multiscale_last_path names the volume kernel behind the other two.
+ * The _u8 entry takes byte frames and is the f32 entry on float(byte). */
+int dfe_multiscale_census_flow_pair_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw,
+                                        const int *ratios, int nratios, int agg, float beta, float *flow, int64_t *idx);
+int dfe_multiscale_census_flow_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int maxh,
+                                       int maxw, const int *ratios, int nratios, int agg, float beta, float *flow, int64_t *idx);
 
 /* ---- N2: gradients of the two matchers (training drivers call model:backward through them) ------- */
 /* replaces: nn.SpatialMatching:updateGradInput / nn.SpatialRadialMatching:updateGradInput (un-vendored nnx), reached
