@@ -29,6 +29,10 @@ no CPU fallback -- a missing library or device raises.
     guidedUpsample                                      (not in the reference: a flow or depth field back at the camera's resolution by joint
                                                         bilateral upsampling with a confidence plane, holes skipped, motion boundaries
                                                         kept by the frame itself -- fields.py)
+    forwardWarp, temporalFuse, temporalStep, TemporalFilter, DepthEstimationAPI(..., temporal=dict(tol=...))   (not in the reference: a
+                                                        depth field carried along its own flow to the next frame's grid under a z-buffer and
+                                                        fused with that frame's measurement, weights counting observations -- fields.py,
+                                                        temporal.py, stream.py)
     radialFlowDepth(..., subpixel=True), refineRadialFlowSubpixel   (not in the reference: sub-pixel radial flow -- radial.py)
     radialFlowDepth(..., sgm=(P1, P2)), semiGlobalAggregate         (not in the reference: the radial cost volume summed along 4 or 8 image
                                                         directions under two label-change penalties before the arg-min, the polar columns
@@ -75,7 +79,8 @@ from .opticalflow_model import (  # noqa: F401
 )
 from . import version2  # noqa: F401
 from .subpixel import flowDepthPair, refineFlowSubpixel  # noqa: F401
-from .fields import flowConsistency, fillHoles, weightedMedian, guidedUpsample  # noqa: F401
+from .fields import flowConsistency, fillHoles, weightedMedian, guidedUpsample, forwardWarp, temporalFuse, temporalStep  # noqa: F401
+from .temporal import TemporalFilter  # noqa: F401
 from .sgm_plane import semiGlobalAggregatePlane, semiGlobalPick  # noqa: F401
 from .census import censusTransform, censusCostVolume, censusFlow, censusFlowDepthPair, censusPyramidScaleVolume  # noqa: F401
 from .multiscale import CascadingAddTable, MultiscaleModel, MultiscalePrefilter, getModelMultiscale, getMultiscalePrefilter  # noqa: F401

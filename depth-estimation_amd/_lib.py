@@ -73,6 +73,11 @@ PROTOTYPES = {
                                 + [C.c_void_p, C.c_void_p]),
     "dfe_guided_upsample_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int,
                                           C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dfe_forward_warp_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int] * 4
+                             + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float] + [C.c_void_p] * 3),
+    "dfe_temporal_fuse_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_float, C.c_float] + [C.c_void_p] * 3),
+    "dfe_temporal_step_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int] * 4
+                              + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 6),
     "dfe_flow_depth_pair_fb_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_float, C.c_double, C.c_int, C.c_float, C.c_int]
                                    + [C.c_void_p] * 7),
     "dfe_flow_depth_pair_fb_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_float, C.c_double, C.c_float, C.c_int, C.c_float,

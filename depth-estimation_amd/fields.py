@@ -11,6 +11,12 @@ image [Cg][H][W], over a region of the frame.
     guidedUpsample(values, size=None, weight=None, guide=None, guide_lo=None, r=2, sigma=0.0, gain=None)
         dfe_guided_upsample_f32: a field at a higher resolution, the mean of the low-resolution samples around each pixel weighted by a tent,
         a confidence plane and the agreement of the frame at both resolutions (joint bilateral upsampling)
+    forwardWarp(values, weight, flow, key=None, region=None, gain=None, bias=None, decay=1.0)
+        dfe_forward_warp_f32: a field scattered along its own flow to the next frame's grid, a z-buffer on `key` deciding collisions
+    temporalFuse(prior, wprior, meas, wmeas, tol, wmax=8.0, region=None)
+        dfe_temporal_fuse_f32: a propagated prior and a new measurement fused pointwise, weights counting observations
+    temporalStep(state, wstate, flow, meas, wmeas, tol, wmax=8.0, key=None, region=None, gain=None, bias=None, decay=1.0, want_prior=False)
+        dfe_temporal_step_f32: the two in one call (the filter above them: temporal.py)
 """
 import ctypes
 
@@ -167,3 +173,116 @@ def guidedUpsample(values, size=None, weight=None, guide=None, guide_lo=None, r=
                                             None if guide_lo is None else ptr(guide_lo), 0 if guide is None else guide.shape[0], float(sigma), r,
                                             None if gain is None else (ctypes.c_float * C)(*gain), Hh, Wh, ptr(out), ptr(valid)))
     return out, valid
+
+
+def _check_flow_key(name, values, flow, key):
+    """ValueError unless flow is 2 x H x W and key (if given) H x W for values C x H x W"""
+    hw = tuple(values.shape[1:])
+    if flow.dim() != 3 or flow.shape[0] != 2 or tuple(flow.shape[1:]) != hw:
+        raise ValueError("%s: flow 2 x H x W expected, got %s for values %s" % (name, tuple(flow.shape), tuple(values.shape)))
+    if key is not None and (key.dim() != 2 or tuple(key.shape) != hw):
+        raise ValueError("%s: key H x W expected, got %s for values %s" % (name, tuple(key.shape), tuple(values.shape)))
+
+
+def _host_floats(name, what, v, C):
+    """None, or a ctypes array of the C finite numbers v (ValueError otherwise)"""
+    if v is None:
+        return None
+    try:
+        v = [float(g) for g in v]
+    except TypeError:
+        raise ValueError("%s: %s=%r: None or %d numbers expected" % (name, what, v, C)) from None
+    if len(v) != C or not all(g == g and abs(g) != float("inf") for g in v):
+        raise ValueError("%s: %s=%r: %d finite numbers expected" % (name, what, v, C))
+    return (ctypes.c_float * C)(*v)
+
+
+def _check_decay(name, decay):
+    decay = float(decay)
+    if not 0.0 < decay <= 1.0:
+        raise ValueError("%s: decay=%r must lie in (0, 1]" % (name, decay))
+    return decay
+
+
+def _check_tol_wmax(name, tol, wmax):
+    tol, wmax = float(tol), float(wmax)
+    if not tol >= 0.0:
+        raise ValueError("%s: tol=%r must be >= 0" % (name, tol))
+    if not 1e-6 <= wmax < float("inf"):
+        raise ValueError("%s: wmax=%r must be finite and >= 1e-6" % (name, wmax))
+    return tol, wmax
+
+
+def _optr(t):
+    return None if t is None else ptr(t)
+
+
+def forwardWarp(values, weight, flow, key=None, region=None, gain=None, bias=None, decay=1.0):
+    """Forward warp with a z-buffer (include/dfe.h: dfe_forward_warp_f32): values float32 [C][H][W], 1 <= C <= 4, and weight float32 [H][W]
+    (finite and >= 1e-6: the sample exists; NOT clipped at 1: it counts observations) scattered along flow float32 [2][H][W] (plane 0 = y,
+    plane 1 = x, from this grid to the next frame's) over region = (y0, x0, Ho, Wo), the whole frame by default.  Each source lands on the
+    nearest pixel (.5 rounds up); of the sources of one target the one with the smallest key [H][W] wins (pass depth: the nearer surface
+    covers the farther), for equal keys or key None the smallest index y W + x.  gain, bias: None or C numbers (out = gain v + bias);
+    decay in (0, 1] multiplies the weight.  Returns (out [C][H][W], wout [H][W], src int32 [H][W]): src the winner's index, -1 and zeros
+    where nothing landed and outside the region."""
+    _check_planes("forwardWarp", values, weight, joint=True)
+    _check_flow_key("forwardWarp", values, flow, key)
+    C, H, W = values.shape
+    gain, bias, decay = _host_floats("forwardWarp", "gain", gain, C), _host_floats("forwardWarp", "bias", bias, C), _check_decay("forwardWarp", decay)
+    values, weight, flow, key = _on_device("forwardWarp", (values, weight, flow, key))
+    y0, x0, Ho, Wo = _region_or_frame(region, H, W)
+    out = torch.empty_like(values)
+    wout = torch.empty((H, W), dtype=torch.float32, device=values.device)
+    src = torch.empty((H, W), dtype=torch.int32, device=values.device)
+    ctx = get_ctx(values)
+    ctx.check(lib().dfe_forward_warp_f32(ctx.handle, ptr(values), C, H, W, ptr(weight), ptr(flow), _optr(key), y0, x0, Ho, Wo, gain, bias, decay,
+                                         ptr(out), ptr(wout), ptr(src)))
+    return out, wout, src
+
+
+def temporalFuse(prior, wprior, meas, wmeas, tol, wmax=8.0, region=None):
+    """A propagated prior and a new measurement fused pointwise (include/dfe.h: dfe_temporal_fuse_f32): prior, meas float32 [C][H][W],
+    1 <= C <= 4, wprior, wmeas float32 [H][W] counting observations (capped at wmax; below 1e-6, not finite or over a value that is not
+    finite: a hole); region = (y0, x0, Ho, Wo), the whole frame by default.  Returns (out, wout, flag): where only one side exists its bits
+    and weight (flag 1: prior, 2: measurement); where |prior - meas| <= tol the mean weighted by the two weights, the weights summed (3);
+    else the heavier side's bits with the lighter side's weight taken off (4: the prior survives, 5: the measurement takes over; on a tie
+    the measurement with its weight); flag 0 and zeros where neither exists and outside the region."""
+    _check_planes("temporalFuse", prior, wprior, joint=True)
+    if tuple(meas.shape) != tuple(prior.shape) or tuple(wmeas.shape) != tuple(wprior.shape):
+        raise ValueError("temporalFuse: meas %s and wmeas %s expected, got %s and %s" % (tuple(prior.shape), tuple(wprior.shape), tuple(meas.shape), tuple(wmeas.shape)))
+    tol, wmax = _check_tol_wmax("temporalFuse", tol, wmax)
+    prior, wprior, meas, wmeas = _on_device("temporalFuse", (prior, wprior, meas, wmeas))
+    C, H, W = prior.shape
+    y0, x0, Ho, Wo = _region_or_frame(region, H, W)
+    out = torch.empty_like(prior)
+    wout = torch.empty((H, W), dtype=torch.float32, device=prior.device)
+    flag = torch.empty_like(wout)
+    ctx = get_ctx(prior)
+    ctx.check(lib().dfe_temporal_fuse_f32(ctx.handle, ptr(prior), ptr(wprior), ptr(meas), ptr(wmeas), C, H, W, y0, x0, Ho, Wo, tol, wmax, ptr(out), ptr(wout),
+                                          ptr(flag)))
+    return out, wout, flag
+
+
+def temporalStep(state, wstate, flow, meas, wmeas, tol, wmax=8.0, key=None, region=None, gain=None, bias=None, decay=1.0, want_prior=False):
+    """forwardWarp of (state, wstate) along flow, then temporalFuse of that prior with (meas, wmeas), in one call whose prior stays in
+    registers (include/dfe.h: dfe_temporal_step_f32); the same bits as the two calls.  Returns a dict: out, wout, flag, and with want_prior
+    also prior, wprior, src."""
+    _check_planes("temporalStep", state, wstate, joint=True)
+    _check_flow_key("temporalStep", state, flow, key)
+    if tuple(meas.shape) != tuple(state.shape) or tuple(wmeas.shape) != tuple(wstate.shape):
+        raise ValueError("temporalStep: meas %s and wmeas %s expected, got %s and %s" % (tuple(state.shape), tuple(wstate.shape), tuple(meas.shape), tuple(wmeas.shape)))
+    C, H, W = state.shape
+    gain, bias, decay = _host_floats("temporalStep", "gain", gain, C), _host_floats("temporalStep", "bias", bias, C), _check_decay("temporalStep", decay)
+    tol, wmax = _check_tol_wmax("temporalStep", tol, wmax)
+    state, wstate, flow, key, meas, wmeas = _on_device("temporalStep", (state, wstate, flow, key, meas, wmeas))
+    y0, x0, Ho, Wo = _region_or_frame(region, H, W)
+    r = dict(out=torch.empty_like(state), wout=torch.empty((H, W), dtype=torch.float32, device=state.device))
+    r["flag"] = torch.empty_like(r["wout"])
+    if want_prior:
+        r["prior"], r["wprior"] = torch.empty_like(state), torch.empty_like(r["wout"])
+        r["src"] = torch.empty((H, W), dtype=torch.int32, device=state.device)
+    ctx = get_ctx(state)
+    ctx.check(lib().dfe_temporal_step_f32(ctx.handle, ptr(state), C, H, W, ptr(wstate), ptr(flow), _optr(key), y0, x0, Ho, Wo, gain, bias, decay, ptr(meas),
+                                          ptr(wmeas), tol, wmax, ptr(r["out"]), ptr(r["wout"]), ptr(r["flag"]), _optr(r.get("prior")), _optr(r.get("wprior")),
+                                          _optr(r.get("src"))))
+    return r

@@ -91,14 +91,21 @@ class DepthEstimationAPI:
     or 'image' (test_opticalflow.lua:284); threshold: processOutput's, for 'max' (the script passes nil, :168); fixMaskOffset: paste the
     mask at the features' centre, not one pixel up and left of it as the script does (:177-179); minInlierRatio: the bad-image gate
     (:159); u8Scale: what a uint8 frame is multiplied by (1 / 255: image.load's range); calibration=, and the remaining keywords: the
-    tracker's and the RANSAC's, as sfm2.getEgoMotion2 takes them.  The stream is made when the first frame shows the camera's size."""
+    tracker's and the RANSAC's, as sfm2.getEgoMotion2 takes them.  The stream is made when the first frame shows the camera's size.
+    temporal: None, or dict(tol=, wmax=, decay=, gain=, bias=) for a TemporalFilter (temporal.py; not in the reference) that fuses the
+    depth of every push that was given imu_tx with what the earlier ones left (nextFrameDepth)."""
 
-    def __init__(self, geometry, filter, K, distP=None, calibration=None, rectify="features", u8Scale=1.0 / 255.0, **sfm):
+    def __init__(self, geometry, filter, K, distP=None, calibration=None, rectify="features", u8Scale=1.0 / 255.0, temporal=None, **sfm):
         self.geometry, self.filter, self.K, self.distP = geometry, filter, K, distP
         self.kw = dict(sfm, calibration=calibration, rectify=rectify)
         self.u8Scale = float(u8Scale)
         self.handle, self.ctx, self.shape, self.params, self._keep = None, None, None, None, None
         self.last = {}
+        self.temporal = None
+        if temporal is not None:
+            from .temporal import TemporalFilter
+
+            self.temporal = TemporalFilter(**temporal)
 
     def _open(self, frame):
         Cc, H, W = frame.shape
@@ -111,7 +118,10 @@ class DepthEstimationAPI:
     def nextFrameDepth(self, frame, imu_tx=None):
         """frame: float32 or uint8 C x H x W device tensor -> None for the first frame, else (im_scaled, xflow, mask) (:196).  self.last
         holds status (0 first frame, 1 result, 2 bad image: zero flow and mask), im_scaled, yflow, R, T, nFound, nInliers, and with imu_tx
-        depth / depth_conf (ARdroneAPI::computeDepthMapFromFlow on the x-flow and the mask)."""
+        depth / depth_conf (ARdroneAPI::computeDepthMapFromFlow on the x-flow and the mask).  With temporal= a result that was given imu_tx
+        also has depth_fused, depth_fused_weight, depth_fused_flag: the filter's push of depth[None], depth_conf and the flow planes with
+        rectify = (K_small, R), K_small = diag(wImg / Wsrc, hImg / Hsrc, 1) K; the first frame, a bad image (no usable pose: the grid cannot
+        be carried), a push without imu_tx (no depth) and reset() reset the filter."""
         if frame.dim() != 3 or frame.dtype not in (torch.float32, torch.uint8):
             raise TypeError("nextFrameDepth: a float32 or uint8 C x H x W tensor expected")
         frame = frame.contiguous()
@@ -134,17 +144,32 @@ class DepthEstimationAPI:
         else:
             self.ctx.check(lib().dfe_stream_push_f32(self.handle, ptr(frame), *tail))
         self.last = dict(status=st.value, im_scaled=ims, nFound=nf.value, nInliers=ni.value)
+        if self.temporal is not None and (st.value != 1 or imu_tx is None):   # nothing to carry the state with: it starts over
+            self.temporal.reset()
         if st.value == 0:
             return None
         self.last.update(yflow=flow[0], xflow=flow[1], mask=mask, R=torch.tensor(R[:], dtype=torch.float64).reshape(3, 3), T=torch.tensor(T[:], dtype=torch.float64))
         if imu_tx is not None:
             self.last.update(depth=depth, depth_conf=dconf)
+            if self.temporal is not None and st.value == 1:
+                fused, weight, flag = self.temporal.push(depth[None], dconf, flow, rectify=(self.K_small(), self.last["R"]))
+                self.last.update(depth_fused=fused[0], depth_fused_weight=weight, depth_fused_flag=flag)
         return ims, flow[1], mask
+
+    def K_small(self):
+        """diag(wImg / Wsrc, hImg / Hsrc, 1) K as a float64 3 x 3 tensor: the camera matrix at the session's working size (include/dfe.h)"""
+        p = self.params
+        k = torch.tensor(list(p.K), dtype=torch.float64).reshape(3, 3).clone()
+        k[0] *= float(p.wImg) / float(p.Wsrc)
+        k[1] *= float(p.hImg) / float(p.Hsrc)
+        return k
 
     def reset(self):
         """forget the previous frame: the next nextFrameDepth returns None again"""
         if self.handle is not None:
             self.ctx.check(lib().dfe_stream_reset(self.handle))
+        if self.temporal is not None:
+            self.temporal.reset()
         self.last = {}
 
     def close(self):

@@ -971,6 +971,63 @@ int dfe_weighted_median_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, c
 int dfe_guided_upsample_f32(dfe_ctx *ctx, const float *v, int C, int Hl, int Wl, const float *w, const float *guide_hi,
                             const float *guide_lo, int Cg, float sigma, int r, const float *gain, int Hh, int Wh, float *out,
                             float *valid);
+/* ---- temporal depth filter: a field carried along its own flow to the next frame's grid and fused with that frame's measurement (NOT
+ * in the reference) ----------------------------------------------------------------------------------------- */
+/* Forward warp with a z-buffer.  v, out [C][H][W], 1 <= C <= 4; w, wout [H][W]; flow [2][H][W], plane 0 = y, plane 1 = x (the layout of
+ * every flow this library returns), from this grid to the next frame's; key [H][W] or NULL; gain, bias C finite HOST floats or NULL;
+ * 0 < decay <= 1; src [H][W] or NULL; H W <= 2^31 - 1 (DFE_E_ARG for each, and for v, w, flow, out or wout NULL).  The region R = rows
+ * y0 .. y0+Ho-1, columns x0 .. x0+Wo-1 must be non-empty and lie inside the frame (DFE_E_SHAPE).  The winners are gathered from v and w
+ * while the outputs are written: out, wout and src must not overlap an input or each other (DFE_E_ARG).  Refused before any launch.
+ * Asynchronous on the ctx's stream; the z-buffer (8 bytes per pixel of R) lives in the ctx's side buffer: nothing is allocated per call
+ * once it has grown.  Everything in fp32 without fused multiply-adds.
+ *   A sample exists (dfe_fill_holes_f32's rule) where w is finite, w >= 1e-6f (the fp32 constant) and every channel of v is finite.
+ *     Unlike the other field operators the weight is NOT clipped at 1: here it counts observations.
+ *   Sources: a pixel p = (y, x) of R whose sample exists, whose two flow components are finite and, with a key, whose key(p) is finite.
+ *   Target of a source: q = (floorf((float(y) + f_y) + 0.5f), floorf((float(x) + f_x) + 0.5f)), each sum rounded to fp32 before the
+ *     next (a fraction of .5 rounds up).  q is compared with R's bounds as floats, before any conversion to an integer; a source whose
+ *     target lies outside R is dropped.
+ *   Winner of a target: among its sources the one with the smallest key + 0.0f (-0 counts as +0); for equal keys, or key == NULL, the
+ *     smallest source index s = y W + x.  The key is the occlusion rule: the caller passes depth, and the nearer surface covers the
+ *     farther one.
+ *   At a target q with winner s: out_c(q) = gain_c v_c(s) + bias_c, the product rounded, then the sum; a NULL gain or bias means no
+ *     arithmetic for that term, and with both NULL the bits are copied.  wout(q) = w(s) if decay == 1, else w(s) decay: the raw weight,
+ *     not clipped.  src(q) = s.
+ *   At a target with no source, and everywhere outside R: out = 0, wout = 0, src = -1.
+ * Launches: the z-buffer set to all-ones (a memset of the stream); the splat, a thread per pixel of R and one no-return 64-bit integer
+ * minimum of (ordered key << 32 | s) on the target's word (the ordered key is the order-preserving integer image of the float's bits:
+ * the sign bit flipped for non-negative values, every bit for negative ones) -- an integer minimum does not depend on the order of
+ * arrival, so the result is reproducible bit for bit; the resolve, a thread per pixel of the frame. */
+int dfe_forward_warp_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, const float *flow, const float *key, int y0,
+                         int x0, int Ho, int Wo, const float *gain, const float *bias, float decay, float *out, float *wout,
+                         int32_t *src);
+/* Fusion of a propagated prior and a new measurement, pointwise.  prior, meas, out [C][H][W], 1 <= C <= 4; wp, wm, wout [H][W]; flag
+ * [H][W] or NULL; tol >= 0 (not NaN); wmax finite and >= 1e-6 (DFE_E_ARG for each, and for another tensor NULL); the region as above
+ * (DFE_E_SHAPE).  out may be prior or meas and wout may be wp or wm (a pixel is read before it is written; no other overlap).  One
+ * launch, asynchronous on the ctx's stream; allocates nothing.  fp32 without fused multiply-adds, IEEE division.
+ *   Per pixel of R: a = min(wp, wmax) where the prior's sample exists (the rule above), else 0; b alike from the measurement.  What lies
+ *   under a zero weight is never read into arithmetic: a NaN in a hole does not leak.  With z the prior's values and m the measurement's:
+ *     a = 0 and b = 0:  out = 0, wout = 0, flag = 0
+ *     b = 0:            out = z (its bits), wout = a, flag = 1
+ *     a = 0:            out = m (its bits), wout = b, flag = 2
+ *     else d_c = z_c - m_c, d2 = sum_c d_c d_c in channel order starting from the first square, and
+ *       d2 <= tol tol (the product formed in fp32 by the host), they agree:  s = a + b, r = a / s, out_c = m_c + r d_c (the mean of
+ *                       the two weighted by the observations behind each), wout = min(s, wmax), flag = 3
+ *       a > b:          the prior survives, weakened by the dissent: out = z (its bits), wout = a - b, flag = 4
+ *       a <= b:         the measurement takes over: out = m (its bits), wout = b if a == b, else b - a, flag = 5
+ *   Outside R: out = 0, wout = 0, flag = 0.
+ * The squares are compared, so integer-valued fields with an integer tol give exact decisions.  A wout that falls below 1e-6 is a hole
+ * to the next call by the sample rule: intended.  wmax is the forgetting: a prior never outweighs wmax observations.  The vote of the
+ * last two rows removes isolated outliers without letting a wrong prior live forever. */
+int dfe_temporal_fuse_f32(dfe_ctx *ctx, const float *prior, const float *wp, const float *meas, const float *wm, int C, int H, int W,
+                          int y0, int x0, int Ho, int Wo, float tol, float wmax, float *out, float *wout, float *flag);
+/* Both in one call: dfe_forward_warp_f32 of the state (v, w) along flow with key, gain, bias and decay, then dfe_temporal_fuse_f32 of
+ * that prior with (meas, wm) -- the clear, the splat, and ONE resolve kernel that fuses in registers; the prior reaches memory only where
+ * it is asked for (prior [C][H][W], wprior [H][W], src [H][W]: each may be NULL, as may flag).  Every output is bit-identical to the two
+ * calls in a row.  Every bad argument is refused before any launch with the codes of the entries it joins; no output may overlap v, w,
+ * flow, key or another output, and flag, prior, wprior, src may not overlap meas or wm (out may be meas, wout may be wm). */
+int dfe_temporal_step_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, const float *flow, const float *key, int y0,
+                          int x0, int Ho, int Wo, const float *gain, const float *bias, float decay, const float *meas, const float *wm,
+                          float tol, float wmax, float *out, float *wout, float *flag, float *prior, float *wprior, int32_t *src);
 
 /* replaces: image.rgb2y as prepareInput calls it (opticalflow_model.lua:136-138; un-vendored `image`, restated: parity unpinned).
  *   rgb [3][H][W] -> y [1][H][W] = 0.299 R + 0.587 G + 0.114 B, accumulated in that order with separately rounded products and sums. */
