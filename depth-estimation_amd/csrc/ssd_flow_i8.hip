@@ -14,7 +14,19 @@
 // fragment of image rows (r .. r+3) at displacement row dy is the fragment of rows (r-1 .. r+2) at dy + 1: the four fragments of a tile
 // rotate through registers (the sweep runs in rounds of four steps) and every step loads ONE new 16-byte piece per lane and tile, into the
 // registers of the oldest fragment, right after the step's MFMAs that read it: after a round every fragment is back where it started and
-// nothing is copied.  The row addresses are scalar; a lane adds one 64-bit base per frame-1 row and per plane row, made once per item.
+// nothing is copied.  The row addresses are scalar; a lane adds one 64-bit base per frame-1 row, made once per item.
+//
+// The plane ring.  A step wants 48 cells (192 B) of ONE S1-plane row, the same for all sixteen lanes of a lane group: read from memory as
+// three 16-byte loads per lane that is three wave-loads of 1 KiB for 64 distinct bytes each.  So each wave keeps four plane rows in LDS
+// (I8Ring: 4 slots x 64 cells, 1 KiB per wave; the block's LDS goes from 26112 to 30208 B, still more than three blocks per CU need): slot
+// s & 3 holds plane row y0 + s, cells x0 .. x0 + 63 (x0 + 63 < Wp).  A step loads, per wave, ONE 256-byte row (buffer_load_dword: cell
+// x0 + lane of row y0 + s + 4, the plane as a buffer of (H + 1) Wp cells, the row a scalar offset) and the three fragment pieces, and reads
+// its three quads with broadcast ds_read_b128 at 16 g + 64 T + 256 (s & 3), immediates on one address register: 3.25 KiB through the vector
+// memory path per step where 6 KiB went.  The row rides one step in a register (stg) and is written to its slot, (s + 3) & 3, at the top
+// of the next step: the compiler counts that wait per register (s_waitcnt vmcnt(3): the three fragment loads issued behind it stay in
+// flight), which it does not do for an LDS-DMA load, whose every ring read it fences with vmcnt(0) (1 us gained at VGA where this form gains 6.7; EXPERIMENTS.md,
+// round 15).  Rows 0..3 are staged with the item's operands; no row beyond the last one a step consumes, y0 + 32 + R - 1, is loaded; the
+// fall-back sweep, rare, keeps its loads from memory.  What orders the slots' reads and refills: the comment at the ring, in `step`.
 //
 // Two rows per item (R = 2).  At step s the fragments F_t = frame-1 rows (y0 + s + t | y0 + s + t + 3) serve row y0 at dy = s and row
 // y0 + 1 at dy = s - 1, which also share the S1-plane row y0 + s.  Both compare frame-0 image rows y0 + 17 .. y0 + 22 with the same six
@@ -46,8 +58,8 @@
 // Z + 0.308e9], masked ones from Z - 2.262e9 - order; dfe_flow_i8_plan admits (H + 1) Wp < 2^29 with Wp >= 80, so order = 3 y1 + (q >> 4)
 // + 98 < 3 * 2^29 / 80 + 2^29 / (40 * 16) < 2.2e7: every key, and the decode's base + 127 - Z added to a valid one, stays inside 32 bits
 // (tests/test_flow_i8_key7_cpu.py).  Per tile that is 4 v_lshl_add_u32 and 2 v_max3_i32 (the twelve keys of a row's step fold in six,
-// a tile's keys paired with the same i of the neighbouring tile); with the two row addresses a two-row step issues 38 vector instructions
-// beside its 15 MFMAs, a one-row step 20 beside 12.
+// a tile's keys paired with the same i of the neighbouring tile); with the fragment row's address a two-row step issues 37 vector instructions
+// beside its 15 MFMAs, a one-row step 19 beside 12.
 //
 // Items.  flow_i8_items.h splits the rows into two-row and one-row wave items from the number of waves the device holds at once.
 //
@@ -191,6 +203,9 @@ template <int R> struct I8Lds {
     float fbh[R][16][DFE_FB];        // a flagged pixel's hits of the fall-back sweep: M (value, 1-based index) pairs, zero-padded
 };
 
+constexpr int kRingRow = 64;   // cells of a ring slot: the 48 a step reads and 16 that ride along in the 256-byte staging load
+struct I8Ring { int row[4][kRingRow]; } __attribute__((aligned(16)));
+
 template <int R, bool FB> struct I8Sweep {
     static constexpr int NS = 33 + R - 1;
     const I8Args &a;
@@ -200,7 +215,10 @@ template <int R, bool FB> struct I8Sweep {
     i8x16_t pen0, pen2;    // the first / third tile's accumulators start here: kKeyPen where candidate 4 g + i lies outside 0 <= q - n <= 32, else 0
     int best[R][4];        // the running key of candidates i, i = 0..3
     int held[R][4];        // a tile's keys that wait for the next tile's, their partners in one v_max3
-    unsigned lo1, lop;     // the lane's byte offsets inside a row of the packed frame 1 and of the S1 plane
+    unsigned lo1, lop;     // the lane's byte offsets inside a row of the packed frame 1 and of the S1 plane (FB) / of a ring slot
+    int *ring;             // !FB: the wave's four plane rows in LDS (the ring, below)
+    __amdgpu_buffer_rsrc_t prs;   // !FB: the S1 plane as a buffer, (H + 1) Wp cells: a staging load is row (scalar offset) + 4 lane, no address arithmetic
+    int stg;               // !FB: the plane row on its way into the ring: cell x0 + lane of row y0 + s + 3 at the top of step s
     // FB
     int sa[R];             // S0 of the lane's pixel (the sweep proper reads it from its LDS image)
     int cnt;
@@ -245,6 +263,13 @@ template <int R, bool FB> struct I8Sweep {
 #pragma unroll
             for (int T = 0; T < 3; ++T) A[T][t] = *reinterpret_cast<const i8x16_t *>(frow + lo1 + 64 * T);
         }
+        // the ring's first four rows: slot t = plane row y0 + t, cells x0 .. x0 + 63 (x0 + 63 < Wp: dfe_flow_i8_plan)
+        if constexpr (!FB) {
+            prs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int *>(a.s1k), 0, 4 * (a.Ho + DFE_FLOW_MARGIN + 1) * a.Wp, 0x00020000);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) ring[kRingRow * t + lane] = __builtin_amdgcn_raw_buffer_load_b32(prs, 4 * lane, 4 * ((y0 + t) * a.Wp + x0), 0);
+            __builtin_amdgcn_wave_barrier();
+        }
     }
 
     // the keys of one result tile D of row y0 + r, and the row's lead cells (sr == 0) and centre cell (sr == 16) where the step is the peeled
@@ -282,12 +307,33 @@ template <int R, bool FB> struct I8Sweep {
         const int pb = 3 * (y0 + s) + (x0 >> 4);   // the plane's order term of tile 0 of this row, taken off where S1 itself is wanted
         // the rows' addresses live in scalar registers; a lane adds its offset (load_operands; the compiler keeps it as a 64-bit base and adds
         // the scalar row with one v_lshl_add_u64) and the tile's 64 T bytes
-        const char *prow = reinterpret_cast<const char *>(a.s1k + (y0 + s) * a.Wp + x0);
         const char *frow = reinterpret_cast<const char *>(a.pk1 + (y0 + s + 4) * a.Wp + x0);   // the one new row of the next step's fragments (rows s + 4 | s + 7)
         const unsigned lo1 = this->lo1, lop = this->lop;
         i8x16_t P[3];
+        if constexpr (FB) {
+            const char *prow = reinterpret_cast<const char *>(a.s1k + (y0 + s) * a.Wp + x0);
 #pragma unroll
-        for (int T = 0; T < 3; ++T) P[T] = *reinterpret_cast<const i8x16_t *>(prow + lop + 64 * T);
+            for (int T = 0; T < 3; ++T) P[T] = *reinterpret_cast<const i8x16_t *>(prow + lop + 64 * T);
+        } else {
+            // The ring.  Slot PH holds plane row y0 + s: the step's three quads are broadcast reads at 16 g + 64 T, immediates on one address
+            // register.  The row on its way in (stg, loaded at the step before: row y0 + s + 3) goes to slot (PH + 3) & 3, which step s - 1
+            // read and whose next reader is step s + 3; then row y0 + s + 4 is loaded into stg.  The last rows a sweep consumes are
+            // y0 + NS - 1: the peeled steps past it load and write nothing, the steady ones (s <= 31) clamp the row, so the two or three
+            // loads past the end fetch row y0 + NS - 1 again, into a slot that no later step reads.
+            // Order.  (1) A slot's read stands behind the write that filled it: both are LDS instructions of ONE wave, which the LDS
+            // executes in issue order, and the compiler keeps the ds_write_b32 above the wave barrier and the ds_read_b128 below it; the
+            // write itself waits for its row with the s_waitcnt vmcnt(3) in front of it (counted: the three fragment loads issued behind
+            // stg's stay in flight; tools/i8_loop_hist.py prints the loops' waits).  (2) A slot's refill, that ds_write_b32, stands behind the
+            // slot's reads for the same reason, three steps later in issue order, and the reads' data is in registers (the s_waitcnt
+            // lgkmcnt in front of `take`'s v_lshl_add_u32) long before that.  No other wave touches the ring.
+            constexpr bool wr = S < 0 || (S >= 1 && S + 3 <= NS - 1), ld = S < 0 || S + 4 <= NS - 1;
+            if constexpr (wr) ring[kRingRow * ((PH + 3) & 3) + lane] = stg;
+            __builtin_amdgcn_wave_barrier();
+            if constexpr (ld) stg = __builtin_amdgcn_raw_buffer_load_b32(prs, 4 * lane, 4 * ((y0 + min(s + 4, NS - 1)) * a.Wp + x0), 0);
+            const char *slot = reinterpret_cast<const char *>(ring + kRingRow * (PH & 3));
+#pragma unroll
+            for (int T = 0; T < 3; ++T) P[T] = *reinterpret_cast<const i8x16_t *>(slot + lop + 64 * T);
+        }
 #pragma unroll
         for (int T = 0; T < 3; ++T) {
             // the tile's accumulator starts from the window's penalty quad (the MFMA's C operand: no instruction); the fall-back sweep
@@ -456,12 +502,13 @@ __device__ __forceinline__ void i8_finalize(const TailOut &o, int middle, int y,
 }
 
 // one wave item: strip `strip`, rows y0 .. y0 + R - 1, of which it writes those from ylo on
-template <int R> __device__ __forceinline__ void i8_item(const I8Args &a, I8Lds<R> *lds, int lane, int strip, int y0, int ylo) {
+template <int R> __device__ __forceinline__ void i8_item(const I8Args &a, I8Lds<R> *lds, I8Ring *ring, int lane, int strip, int y0, int ylo) {
     const int x0 = strip * 16;
     const int n = lane & 15, g = lane >> 4;
 
     I8Sweep<R, false> sw(a, lane, x0, y0);
     sw.lds = lds;
+    sw.ring = &ring->row[0][0];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         for (int i = 0; i < 4; ++i) sw.best[r][i] = INT_MIN;
@@ -513,6 +560,7 @@ template <int R> __device__ __forceinline__ void i8_item(const I8Args &a, I8Lds<
             fs.flagged = flag;
             fs.fbp = &lds->fbh[r][n][0];
             fs.lds = nullptr;
+            fs.ring = nullptr;
             fs.load_operands();
             fs.run();
             if (flag && g == 0)
@@ -535,18 +583,19 @@ template <int R>
 __global__ __launch_bounds__(kI8Waves * 64) __attribute__((amdgpu_waves_per_eu(3, 3))) void ssd_flow_i8_kernel(I8Args a) {
     if (*a.verdict) return;   // not byte-valued: the gated float sweep behind this launch does the step
     __shared__ I8Lds<R> lds_all[kI8Waves];
+    __shared__ I8Ring ring_all[kI8Waves];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int item = blockIdx.x * kI8Waves + wave;
     if (item >= a.nitems) return;   // (no block-wide barrier below: a wave works alone)
     if constexpr (R == 2) {
         if (item < a.n2) {
             const int strip = item / a.nrp, rp = item - strip * a.nrp;
-            i8_item<2>(a, &lds_all[wave], lane, strip, min(2 * rp, a.Ho - 2), 2 * rp);   // (the last pair of an odd Ho is shifted upwards)
+            i8_item<2>(a, &lds_all[wave], &ring_all[wave], lane, strip, min(2 * rp, a.Ho - 2), 2 * rp);   // (the last pair of an odd Ho is shifted upwards)
             return;
         }
     }
     const int row = a.row0 + (item - a.n2), strip = row / a.Ho, y = row - strip * a.Ho;
-    i8_item<1>(a, reinterpret_cast<I8Lds<1> *>(&lds_all[wave]), lane, strip, y, y);
+    i8_item<1>(a, reinterpret_cast<I8Lds<1> *>(&lds_all[wave]), &ring_all[wave], lane, strip, y, y);
 }
 
 // ------------------------------------------------------------------------------------------

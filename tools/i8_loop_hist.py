@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Tuning only: static instruction counts of the int8 flow sweep's loops.  Compiles ssd_flow_i8.hip for the device with the Makefile's
 flags, finds in each ssd_flow_i8_kernel instantiation every loop (a backward branch to an earlier label) that holds MFMAs, and prints
-per loop trip the MFMAs, scalar, memory and vector instructions and the vector ones by opcode; with them the compiler's resource report.
+per loop trip the MFMAs, scalar, memory and vector instructions, the vector and the memory ones by opcode and the operands of the loop's
+s_waitcnt (a counted vmcnt(n) leaves n loads in flight, vmcnt(0) drains them all); with them the compiler's resource report.
 usage: i8_loop_hist.py [source file, default csrc/ssd_flow_i8.hip] [-DX=Y ...]"""
 import collections, os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,7 +57,12 @@ for start, l in enumerate(lines):
         if not mf:
             continue
         valu = {k: v for k, v in c.items() if k.startswith("v_") and not k.startswith("v_mfma")}
-        mem = sum(v for k, v in c.items() if k.startswith(("global_", "buffer_", "ds_", "s_load", "s_buffer", "scratch_", "flat_")))
+        memops = {k: v for k, v in c.items() if k.startswith(("global_", "buffer_", "ds_", "s_load", "s_buffer", "scratch_", "flat_"))}
+        mem = sum(memops.values())
         sal = sum(v for k, v in c.items() if k.startswith("s_") and not k.startswith(("s_load", "s_buffer", "s_waitcnt", "s_nop")))
         print("  loop %s (%d lines): mfma %d  valu %d  scalar %d  memory %d  s_waitcnt %d  s_nop %d" % (tgt, i - labels[tgt], mf, sum(valu.values()), sal, mem, c["s_waitcnt"], c["s_nop"]))
         print("     " + ", ".join("%d %s" % (v, k) for k, v in sorted(valu.items(), key=lambda kv: -kv[1])))
+        # the memory instructions by opcode, and the waits as written: a counted vmcnt(n) leaves n loads in flight, vmcnt(0) drains them all
+        waits = collections.Counter(" ".join(x.split("//")[0].split(";")[0].split()[1:]) for x in body[labels[tgt]:i + 1] if x.strip().startswith("s_waitcnt"))
+        print("     memory: " + ", ".join("%d %s" % (v, k) for k, v in sorted(memops.items(), key=lambda kv: -kv[1])))
+        print("     waits:  " + ", ".join("%d x %s" % (v, k) for k, v in sorted(waits.items(), key=lambda kv: -kv[1])))
