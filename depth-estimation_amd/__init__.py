@@ -33,6 +33,9 @@ no CPU fallback -- a missing library or device raises.
                                                         depth field carried along its own flow to the next frame's grid under a z-buffer and
                                                         fused with that frame's measurement, weights counting observations -- fields.py,
                                                         temporal.py, stream.py)
+    forwardSplat, temporalStep(..., splat="bilinear"), TemporalFilter(..., splat="bilinear")   (not in the reference: the sub-pixel
+                                                        forward warp, every source spread over four pixels and summed in integers,
+                                                        reproducible bit for bit -- fields.py, temporal.py)
     radialFlowDepth(..., subpixel=True), refineRadialFlowSubpixel   (not in the reference: sub-pixel radial flow -- radial.py)
     radialFlowDepth(..., sgm=(P1, P2)), semiGlobalAggregate         (not in the reference: the radial cost volume summed along 4 or 8 image
                                                         directions under two label-change penalties before the arg-min, the polar columns
@@ -79,7 +82,7 @@ from .opticalflow_model import (  # noqa: F401
 )
 from . import version2  # noqa: F401
 from .subpixel import flowDepthPair, refineFlowSubpixel  # noqa: F401
-from .fields import flowConsistency, fillHoles, weightedMedian, guidedUpsample, forwardWarp, temporalFuse, temporalStep  # noqa: F401
+from .fields import flowConsistency, fillHoles, weightedMedian, guidedUpsample, forwardWarp, forwardSplat, temporalFuse, temporalStep  # noqa: F401
 from .temporal import TemporalFilter  # noqa: F401
 from .sgm_plane import semiGlobalAggregatePlane, semiGlobalPick  # noqa: F401
 from .census import censusTransform, censusCostVolume, censusFlow, censusFlowDepthPair, censusPyramidScaleVolume  # noqa: F401

@@ -12,7 +12,7 @@ DFE_MAX_RATIOS = 10
 # keys of dfe_set_option / dfe_get_option (include/dfe.h)
 OPTION_KEYS = ("cascade_px", "fine_fuse", "mid_fuse", "fine_nq", "mid_nq", "prep_tiles", "xpose", "xpose_nt", "soft_epilogue", "conv_batch", "conv_nt10",
                "fm64", "fm_rows", "sweep_ovh", "sweep_blocks", "debug_arena", "fm_flat", "fm_split", "conv_narrow", "conv_mfma", "fm_mfma", "arena_contig", "graphs",
-               "cv_novol", "conv_nt", "cv_i8", "i8_slots", "fill_apex")
+               "cv_novol", "conv_nt", "cv_i8", "i8_slots", "fill_apex", "splat_lds")
 
 c_f32p = C.POINTER(C.c_float)
 c_i64p = C.POINTER(C.c_int64)
@@ -78,6 +78,11 @@ PROTOTYPES = {
     "dfe_temporal_fuse_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_float, C.c_float] + [C.c_void_p] * 3),
     "dfe_temporal_step_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int] * 4
                               + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 6),
+    "dfe_forward_splat_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int] * 4
+                              + [C.POINTER(C.c_float), C.POINTER(C.c_float)] + [C.c_float] * 4 + [C.c_void_p] * 3),
+    "dfe_temporal_step_splat_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int] * 4
+                                    + [C.POINTER(C.c_float), C.POINTER(C.c_float)] + [C.c_float] * 4 + [C.c_void_p, C.c_void_p, C.c_float, C.c_float]
+                                    + [C.c_void_p] * 6),
     "dfe_flow_depth_pair_fb_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_float, C.c_double, C.c_int, C.c_float, C.c_int]
                                    + [C.c_void_p] * 7),
     "dfe_flow_depth_pair_fb_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float, C.c_float, C.c_double, C.c_float, C.c_int, C.c_float,

@@ -16,7 +16,7 @@ const DfeOptName dfe_opt_names[DFE_NOPT] = {
     {"conv_narrow", "DFE_CONV_NARROW", false}, {"conv_mfma", "DFE_CONV_MFMA", false},         {"fm_mfma", "DFE_FM_MFMA", false},
     {"arena_contig", "DFE_ARENA_CONTIG", false}, {"cv_novol", "DFE_CV_NOVOL", false},       {"conv_nt", "DFE_CONV_NT", false},
     {"cv_i8", "DFE_CV_I8", false},             {"i8_slots", "DFE_I8_SLOTS", false},
-    {"fill_apex", "DFE_FILL_APEX", false},
+    {"fill_apex", "DFE_FILL_APEX", false},     {"splat_lds", "DFE_SPLAT_LDS", false},
 };
 
 int dfe_fail(dfe_ctx *ctx, int code, const char *fmt, ...) {

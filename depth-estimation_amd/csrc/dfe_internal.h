@@ -40,6 +40,7 @@ enum DfeOpt {
     DFE_OPT_CV_I8,            // volume-free flow step on the int8 matrix cores where the frames turn out byte-valued (ssd_flow_i8.hip; 0: the float sweep only)
     DFE_OPT_I8_SLOTS,         // int8 flow sweep: the number of waves its item plan takes the device to hold at once (tests; automatic: from the device)
     DFE_OPT_FILL_APEX,        // hole filling: the one-workgroup apex kernel (fill.hip; 0: per-level kernels only; n > 0: its base level has at most n cells, tests)
+    DFE_OPT_SPLAT_LDS,        // four-tap temporal splat: the front and the accumulate pass with a workgroup's taps combined in LDS first (temporal_splat.hip; 0: every tap straight to global memory)
     DFE_NOPT
 };
 struct DfeOptName { const char *key; const char *env; bool env_presence_means_zero; };

@@ -15,8 +15,13 @@ image [Cg][H][W], over a region of the frame.
         dfe_forward_warp_f32: a field scattered along its own flow to the next frame's grid, a z-buffer on `key` deciding collisions
     temporalFuse(prior, wprior, meas, wmeas, tol, wmax=8.0, region=None)
         dfe_temporal_fuse_f32: a propagated prior and a new measurement fused pointwise, weights counting observations
-    temporalStep(state, wstate, flow, meas, wmeas, tol, wmax=8.0, key=None, region=None, gain=None, bias=None, decay=1.0, want_prior=False)
-        dfe_temporal_step_f32: the two in one call (the filter above them: temporal.py)
+    temporalStep(state, wstate, flow, meas, wmeas, tol, wmax=8.0, key=None, region=None, gain=None, bias=None, decay=1.0, want_prior=False,
+                 splat="nearest", ztol=0.0, quant=1024.0, min_cover=0.0)
+        dfe_temporal_step_f32: the two in one call (the filter above them: temporal.py); splat="bilinear":
+        dfe_temporal_step_splat_f32, forwardSplat in place of forwardWarp
+    forwardSplat(values, weight, flow, key=None, region=None, gain=None, bias=None, decay=1.0, ztol=0.0, quant=1024.0, min_cover=0.0)
+        dfe_forward_splat_f32: the sub-pixel forward warp, every source spread over the four pixels around where it lands, summed in
+        integers
 """
 import ctypes
 
@@ -263,25 +268,75 @@ def temporalFuse(prior, wprior, meas, wmeas, tol, wmax=8.0, region=None):
     return out, wout, flag
 
 
-def temporalStep(state, wstate, flow, meas, wmeas, tol, wmax=8.0, key=None, region=None, gain=None, bias=None, decay=1.0, want_prior=False):
+def _check_splat(name, ztol, quant, min_cover):
+    ztol, quant, min_cover = float(ztol), float(quant), float(min_cover)
+    if not 0.0 <= ztol < float("inf"):
+        raise ValueError("%s: ztol=%r must be finite and >= 0" % (name, ztol))
+    if not 0.0 < quant < float("inf"):
+        raise ValueError("%s: quant=%r must be finite and > 0" % (name, quant))
+    if not 0.0 <= min_cover <= 1.0:
+        raise ValueError("%s: min_cover=%r must lie in [0, 1]" % (name, min_cover))
+    return ztol, quant, min_cover
+
+
+def forwardSplat(values, weight, flow, key=None, region=None, gain=None, bias=None, decay=1.0, ztol=0.0, quant=1024.0, min_cover=0.0):
+    """Sub-pixel forward warp (include/dfe.h: dfe_forward_splat_f32): forwardWarp's arguments, but every source is spread over the four
+    pixels around where it lands with tent weights on a 1 / 128 grid, and a target is the mean of what reached it, weighted by tent weight
+    times source weight.  The sums are 64-bit integers (values on the 1 / quant grid, weights on the 1 / 256 grid, capped at 256), so the
+    result does not depend on the order of arrival: the same bits in every run.  Of the sources that reach a target only those whose key
+    lies within ztol of the smallest one contribute (pass depth: what the nearer surface covers does not leak through); key None: all.  A
+    target needs tent weights of at least min_cover in all (1 = one whole source).  Returns (out [C][H][W], wout [H][W], cover [H][W]):
+    wout the mean observation count, scaled down where cover < 1; cover the tent weights that arrived; zeros where nothing did and
+    outside the region.  Defined while at most 256 taps contribute to one target."""
+    _check_planes("forwardSplat", values, weight, joint=True)
+    _check_flow_key("forwardSplat", values, flow, key)
+    C, H, W = values.shape
+    gain, bias, decay = _host_floats("forwardSplat", "gain", gain, C), _host_floats("forwardSplat", "bias", bias, C), _check_decay("forwardSplat", decay)
+    ztol, quant, min_cover = _check_splat("forwardSplat", ztol, quant, min_cover)
+    values, weight, flow, key = _on_device("forwardSplat", (values, weight, flow, key))
+    y0, x0, Ho, Wo = _region_or_frame(region, H, W)
+    out = torch.empty_like(values)
+    wout = torch.empty((H, W), dtype=torch.float32, device=values.device)
+    cover = torch.empty_like(wout)
+    ctx = get_ctx(values)
+    ctx.check(lib().dfe_forward_splat_f32(ctx.handle, ptr(values), C, H, W, ptr(weight), ptr(flow), _optr(key), y0, x0, Ho, Wo, gain, bias, decay, ztol, quant,
+                                          min_cover, ptr(out), ptr(wout), ptr(cover)))
+    return out, wout, cover
+
+
+def temporalStep(state, wstate, flow, meas, wmeas, tol, wmax=8.0, key=None, region=None, gain=None, bias=None, decay=1.0, want_prior=False, splat="nearest",
+                 ztol=0.0, quant=1024.0, min_cover=0.0):
     """forwardWarp of (state, wstate) along flow, then temporalFuse of that prior with (meas, wmeas), in one call whose prior stays in
     registers (include/dfe.h: dfe_temporal_step_f32); the same bits as the two calls.  Returns a dict: out, wout, flag, and with want_prior
-    also prior, wprior, src."""
+    also prior, wprior, src.  splat="bilinear": forwardSplat with ztol, quant and min_cover in place of forwardWarp
+    (dfe_temporal_step_splat_f32); want_prior then adds prior, wprior, cover and no src."""
     _check_planes("temporalStep", state, wstate, joint=True)
     _check_flow_key("temporalStep", state, flow, key)
     if tuple(meas.shape) != tuple(state.shape) or tuple(wmeas.shape) != tuple(wstate.shape):
         raise ValueError("temporalStep: meas %s and wmeas %s expected, got %s and %s" % (tuple(state.shape), tuple(wstate.shape), tuple(meas.shape), tuple(wmeas.shape)))
+    if splat not in ("nearest", "bilinear"):
+        raise ValueError("temporalStep: splat=%r: \"nearest\" or \"bilinear\"" % (splat,))
     C, H, W = state.shape
     gain, bias, decay = _host_floats("temporalStep", "gain", gain, C), _host_floats("temporalStep", "bias", bias, C), _check_decay("temporalStep", decay)
     tol, wmax = _check_tol_wmax("temporalStep", tol, wmax)
+    if splat == "bilinear":
+        ztol, quant, min_cover = _check_splat("temporalStep", ztol, quant, min_cover)
     state, wstate, flow, key, meas, wmeas = _on_device("temporalStep", (state, wstate, flow, key, meas, wmeas))
     y0, x0, Ho, Wo = _region_or_frame(region, H, W)
     r = dict(out=torch.empty_like(state), wout=torch.empty((H, W), dtype=torch.float32, device=state.device))
     r["flag"] = torch.empty_like(r["wout"])
     if want_prior:
         r["prior"], r["wprior"] = torch.empty_like(state), torch.empty_like(r["wout"])
-        r["src"] = torch.empty((H, W), dtype=torch.int32, device=state.device)
+        if splat == "bilinear":
+            r["cover"] = torch.empty_like(r["wout"])
+        else:
+            r["src"] = torch.empty((H, W), dtype=torch.int32, device=state.device)
     ctx = get_ctx(state)
+    if splat == "bilinear":
+        ctx.check(lib().dfe_temporal_step_splat_f32(ctx.handle, ptr(state), C, H, W, ptr(wstate), ptr(flow), _optr(key), y0, x0, Ho, Wo, gain, bias, decay, ztol,
+                                                    quant, min_cover, ptr(meas), ptr(wmeas), tol, wmax, ptr(r["out"]), ptr(r["wout"]), ptr(r["flag"]),
+                                                    _optr(r.get("prior")), _optr(r.get("wprior")), _optr(r.get("cover"))))
+        return r
     ctx.check(lib().dfe_temporal_step_f32(ctx.handle, ptr(state), C, H, W, ptr(wstate), ptr(flow), _optr(key), y0, x0, Ho, Wo, gain, bias, decay, ptr(meas),
                                           ptr(wmeas), tol, wmax, ptr(r["out"]), ptr(r["wout"]), ptr(r["flag"]), _optr(r.get("prior")), _optr(r.get("wprior")),
                                           _optr(r.get("src"))))

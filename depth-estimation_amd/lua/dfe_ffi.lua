@@ -128,6 +128,8 @@ int dfe_guided_upsample_f32(dfe_ctx *ctx, const float *v, int C, int Hl, int Wl,
 int dfe_forward_warp_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, const float *flow, const float *key, int y0, int x0, int Ho, int Wo, const float *gain, const float *bias, float decay, float *out, float *wout, int32_t *src);
 int dfe_temporal_fuse_f32(dfe_ctx *ctx, const float *prior, const float *wp, const float *meas, const float *wm, int C, int H, int W, int y0, int x0, int Ho, int Wo, float tol, float wmax, float *out, float *wout, float *flag);
 int dfe_temporal_step_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, const float *flow, const float *key, int y0, int x0, int Ho, int Wo, const float *gain, const float *bias, float decay, const float *meas, const float *wm, float tol, float wmax, float *out, float *wout, float *flag, float *prior, float *wprior, int32_t *src);
+int dfe_forward_splat_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, const float *flow, const float *key, int y0, int x0, int Ho, int Wo, const float *gain, const float *bias, float decay, float ztol, float quant, float min_cover, float *out, float *wout, float *cover);
+int dfe_temporal_step_splat_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, const float *flow, const float *key, int y0, int x0, int Ho, int Wo, const float *gain, const float *bias, float decay, float ztol, float quant, float min_cover, const float *meas, const float *wm, float tol, float wmax, float *out, float *wout, float *flag, float *prior, float *wprior, float *cover);
 int dfe_rgb2y_f32(dfe_ctx *ctx, const float *rgb, int H, int W, float *y);
 int dfe_min_dim0_f32(dfe_ctx *ctx, const float *in, int n, int64_t M, float *val, int64_t *idx);
 int dfe_flow_depth_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x, float foe_y, double extract_threshold, float scale, float *flow, float *scores, float *depth, float *depth_conf);

@@ -92,7 +92,8 @@ class DepthEstimationAPI:
     mask at the features' centre, not one pixel up and left of it as the script does (:177-179); minInlierRatio: the bad-image gate
     (:159); u8Scale: what a uint8 frame is multiplied by (1 / 255: image.load's range); calibration=, and the remaining keywords: the
     tracker's and the RANSAC's, as sfm2.getEgoMotion2 takes them.  The stream is made when the first frame shows the camera's size.
-    temporal: None, or dict(tol=, wmax=, decay=, gain=, bias=) for a TemporalFilter (temporal.py; not in the reference) that fuses the
+    temporal: None, or dict(tol=, wmax=, decay=, gain=, bias=, key_channel=, splat=, ztol=, quant=, min_cover=), TemporalFilter's own
+    keywords passed through (temporal.py; not in the reference; splat="bilinear": the sub-pixel splat), for a filter that fuses the
     depth of every push that was given imu_tx with what the earlier ones left (nextFrameDepth)."""
 
     def __init__(self, geometry, filter, K, distP=None, calibration=None, rectify="features", u8Scale=1.0 / 255.0, temporal=None, **sfm):

@@ -82,7 +82,7 @@ int dfe_set_cost_volume_tile(dfe_ctx *ctx, int tyq);
 /* Behaviour switches of the launchers (tuning and tests; none is needed for correct results -- every choice has a parity test or is
  * a pure scheduling choice).  value >= 0 forces, -1 restores the launcher's own choice per shape.  Keys: "cascade_px", "fine_fuse",
  * "mid_fuse", "fine_nq", "mid_nq", "prep_tiles", "xpose", "xpose_nt", "soft_epilogue", "conv_batch", "conv_nt10", "fm64", "fm_rows",
- * "sweep_ovh", "sweep_blocks", "debug_arena", "fm_flat", "fm_split", "conv_narrow", "conv_mfma", "fm_mfma", "arena_contig", "graphs", "cv_novol", "conv_nt", "cv_i8", "i8_slots", "fill_apex".  The library reads the environment ONCE, in dfe_ctx_create
+ * "sweep_ovh", "sweep_blocks", "debug_arena", "fm_flat", "fm_split", "conv_narrow", "conv_mfma", "fm_mfma", "arena_contig", "graphs", "cv_novol", "conv_nt", "cv_i8", "i8_slots", "fill_apex", "splat_lds".  The library reads the environment ONCE, in dfe_ctx_create
  * (DFE_<KEY> variables of the tuning scripts) -- never inside an op, so an op's behaviour depends on its ctx only.
  * Two keys trade the exact arithmetic for the matrix cores, both OFF unless set to 1: "conv_mfma" (the one-call models' filter layers as
  * implicit GEMMs, v_mfma_f32_16x16x4_f32: the reference's (input plane, ky, kx) order with FUSED multiply-adds, <= 1e-5 relative to
@@ -103,6 +103,10 @@ int dfe_set_cost_volume_tile(dfe_ctx *ctx, int tyq);
  * blocks x 4, from the device); a pure scheduling choice.  "fill_apex" (dfe_fill_holes_f32): automatic = the upper pyramid levels, from
  * the first one whose levels up to the top fit the 160 KB of LDS, run in one workgroup's single launch; 0 = a launch per level and
  * direction only; n > 0 (tests) = the apex takes over at the first level of at most n cells (that also fits).  The same bits either way.
+ * "splat_lds" (dfe_forward_splat_f32, dfe_temporal_step_splat_f32): 1 = the front and the accumulate pass combine the taps of a
+ * workgroup's 8 x 64 sources that land in a 14 x 70 window around where the tile's centre goes in LDS and send every touched cell to
+ * global memory once; 0 = every tap straight to global memory; automatic = 1, the faster one at the VGA and the 1080p step's region
+ * (DESIGN section 4.36).  Integer minima and sums: the same bits.
  * Unknown key: DFE_E_ARG. */
 int dfe_set_option(dfe_ctx *ctx, const char *key, int value);
 int dfe_get_option(dfe_ctx *ctx, const char *key, int *value);
@@ -1028,6 +1032,47 @@ int dfe_temporal_fuse_f32(dfe_ctx *ctx, const float *prior, const float *wp, con
 int dfe_temporal_step_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, const float *flow, const float *key, int y0,
                           int x0, int Ho, int Wo, const float *gain, const float *bias, float decay, const float *meas, const float *wm,
                           float tol, float wmax, float *out, float *wout, float *flag, float *prior, float *wprior, int32_t *src);
+/* Forward warp with a sub-pixel (four-tap, bilinear) splat on INTEGER accumulators: every source is spread over the
+ * four pixels around where it lands, and a target is the weighted mean of what reached it.  The sums are integers, so they do not depend
+ * on the order of arrival: reproducible bit for bit, like the nearest-pixel entry above.  v, w, flow, key, the region, gain, bias, decay,
+ * out, wout, the sample rule, the sources, the overlap rule (out, wout, cover against the inputs and each other) and the error codes are
+ * dfe_forward_warp_f32's; there is no src.  ztol finite and >= 0, quant finite and > 0, 0 <= min_cover <= 1 (DFE_E_ARG); cover [H][W] or
+ * NULL.  fp32 without fused multiply-adds except for the integers.
+ *   Position: py = float(y) + f_y, px = float(x) + f_x, each rounded to fp32; by = floorf(py), ay = py - by (exact); x alike.
+ *   Tent weights on a grid of 1/128 per axis: uy1 = (int)floorf(ay * 128.0f + 0.5f), uy0 = 128 - uy1; x alike.  Tap (i, j), i, j in
+ *     {0, 1}, targets (by + float(i), bx + float(j)) with the integer weight u = uy_i ux_j: the four sum to 16384 exactly (a partition of
+ *     unity).  A tap with u == 0 does not exist.  A tap's target is compared with R's bounds as floats before any conversion; a tap
+ *     outside R is dropped, the source's other taps stay.
+ *   Fixed point: val_c = gain_c v_c + bias_c as above; V_c = (long long)rintf(val_c * quant); a source with any
+ *     !(|val_c * quant| <= 16777216.0f) is dropped whole.  wd = w if decay == 1, else w * decay; Wf = (long long)rintf(fminf(wd, 256.0f)
+ *     * 256.0f); a source with Wf == 0 is dropped whole.  A dropped source takes part in nothing below, the front included.
+ *   Front (the occlusion rule): Z(q) = the minimum of key(s) + 0.0f over the taps that reach q, held as the order-preserving 32-bit
+ *     integer image of the float (see above) and taken with an integer atomic minimum.  With key == NULL there is no front.
+ *   Accumulate: a tap of source s contributes to q iff key == NULL or (key(s) + 0.0f) - Z(q) <= ztol (one rounded subtraction).  With
+ *     omega = u Wf, three sums are kept in 64-bit integers by integer atomic adds: A_c(q) += omega V_c, B(q) += omega, U(q) += u.
+ *     omega |V_c| <= 2^14 2^16 2^24 = 2^54: the result is defined while AT MOST 256 TAPS contribute to one target (|A_c| <= 2^62);
+ *     beyond that the sums may wrap and the result is unspecified (never a fault).
+ *   Resolve: a target exists iff B > 0 and U >= max(1, (int)ceilf(min_cover * 16384.0f)).  There out_c = ((float)A_c / (float)B) / quant
+ *     (the conversions round to nearest even, the divisions are IEEE), wout = (float)B / (256.0f * (float)max(U, 16384)) and cover =
+ *     (float)U / 16384.0f: an under-covered target carries proportionally fewer observations, an over-covered one the mean count, not
+ *     the sum.  Everywhere else, and outside R: out = 0, wout = 0, cover = 0.
+ * Consequences: an integer flow without collisions, values on the 1 / quant grid with |V_c| Wf < 2^24, weights on the 1 / 256 grid and
+ * quant a power of two give dfe_forward_warp_f32's bits; a flow below half a pixel per frame moves the field (the nearest splat leaves
+ * it where it is); the position is quantised to 1 / 128 px and the values to 1 / quant per step.
+ * Launches: a clear of the accumulators ((C + 2) 64-bit words and one 32-bit front per pixel of R, in the ctx's side buffer: nothing is
+ * allocated per call once it has grown); the front pass (skipped with key == NULL); the accumulate pass (option "splat_lds": the two
+ * forms of both passes, the same bits); the resolve, a thread per pixel of the frame.  Asynchronous on the ctx's stream. */
+int dfe_forward_splat_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, const float *flow, const float *key, int y0,
+                          int x0, int Ho, int Wo, const float *gain, const float *bias, float decay, float ztol, float quant,
+                          float min_cover, float *out, float *wout, float *cover);
+/* dfe_temporal_step_f32 with dfe_forward_splat_f32 in place of the nearest warp: the clear, the front, the accumulate and ONE resolve
+ * kernel that divides and fuses in registers (the fusion's own device function).  cover [H][W] in place of src; prior, wprior, cover and
+ * flag may each be NULL.  Every output is bit-identical to dfe_forward_splat_f32 followed by dfe_temporal_fuse_f32; arguments, overlap
+ * rules and error codes are those of the entries it joins. */
+int dfe_temporal_step_splat_f32(dfe_ctx *ctx, const float *v, int C, int H, int W, const float *w, const float *flow, const float *key,
+                                int y0, int x0, int Ho, int Wo, const float *gain, const float *bias, float decay, float ztol,
+                                float quant, float min_cover, const float *meas, const float *wm, float tol, float wmax, float *out,
+                                float *wout, float *flag, float *prior, float *wprior, float *cover);
 
 /* replaces: image.rgb2y as prepareInput calls it (opticalflow_model.lua:136-138; un-vendored `image`, restated: parity unpinned).
  *   rgb [3][H][W] -> y [1][H][W] = 0.299 R + 0.587 G + 0.114 B, accumulated in that order with separately rounded products and sums. */
