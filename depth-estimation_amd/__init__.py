@@ -54,6 +54,9 @@ no CPU fallback -- a missing library or device raises.
     MultiscaleModel.forwardFlow(..., census=True), censusPyramidScaleVolume   (not in the reference: the census cost in the raw-patch pyramid
                                                         matcher -- multiscale flow for frame pairs whose exposure differs, with no trained
                                                         weights -- multiscale.py, census.py)
+    censusRefineSubpixel, censusFlow / censusFlowDepthPair(..., refine=True), forwardFlow(..., census=dict(refine=True))
+                                                        (not in the reference: sub-pixel flow on the raw census cost, the vee fit through
+                                                        the chosen cell's cost and its neighbours' -- census.py, multiscale.py)
     getModel(geometry).forwardFlow                      (a trained single-scale model per frame pair in one call,
                                                         output_extraction_method 'max' or 'mean' -- network.py)
     imageScale, DepthEstimationAPI(...).nextFrameDepth  (image.scale; depth_estimation_api.lua:134-198, video -> depth per camera
@@ -85,7 +88,7 @@ from .subpixel import flowDepthPair, refineFlowSubpixel  # noqa: F401
 from .fields import flowConsistency, fillHoles, weightedMedian, guidedUpsample, forwardWarp, forwardSplat, temporalFuse, temporalStep  # noqa: F401
 from .temporal import TemporalFilter  # noqa: F401
 from .sgm_plane import semiGlobalAggregatePlane, semiGlobalPick  # noqa: F401
-from .census import censusTransform, censusCostVolume, censusFlow, censusFlowDepthPair, censusPyramidScaleVolume  # noqa: F401
+from .census import censusTransform, censusCostVolume, censusFlow, censusFlowDepthPair, censusPyramidScaleVolume, censusRefineSubpixel  # noqa: F401
 from .multiscale import CascadingAddTable, MultiscaleModel, MultiscalePrefilter, getModelMultiscale, getMultiscalePrefilter  # noqa: F401
 from .network import getFilter, getFilterRadial, getModel, tables_random  # noqa: F401
 from .radial import (getRMax, getC2PMask, getP2CMask, cartesian2polar, flow2depth, getKOutput, getP2CMaskOF,  # noqa: F401

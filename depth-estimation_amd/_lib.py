@@ -207,6 +207,14 @@ PROTOTYPES = {
     "dfe_census_pyramid_scale_volume_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_float, C.c_void_p]),
     "dfe_multiscale_census_flow_pair_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [c_i32p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "dfe_multiscale_census_flow_pair_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [c_i32p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "dfe_census_refine_subpixel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 3 + [C.c_int] * 3),
+    "dfe_census_flow_depth_pair_subpixel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_float, C.c_float] + [C.c_void_p] * 4),
+    "dfe_census_flow_depth_pair_subpixel_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 4),
+    "dfe_multiscale_census_refine_subpixel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [c_i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dfe_multiscale_census_flow_pair_subpixel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [c_i32p, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                                              C.c_void_p]),
+    "dfe_multiscale_census_flow_pair_subpixel_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [c_i32p, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                                             C.c_void_p]),
     "dfe_corner_response_f32":(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "dfe_select_corners_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "dfe_pyr_down_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

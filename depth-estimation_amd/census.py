@@ -4,13 +4,16 @@
         dfe_census_transform_f32 / _u8: the signature of every k x k (or kh x kw) patch, its cells compared with its centre
     censusCostVolume(sig0, sig1, hWin, wWin, agg=3)
         dfe_census_cost_volume_f32: Hamming distances summed over the channels and an agg x agg box, as a float volume (the staged route)
-    censusFlow(sig0, sig1, nbits, hWin, wWin, agg=3)
+    censusFlow(sig0, sig1, nbits, hWin, wWin, agg=3, refine=False)
         dfe_census_flow_f32: the first minimum of that cost with the centre rule, its match score and the decoded flow; no volume
+    censusRefineSubpixel(sig0, sig1, hWin, wWin, idx, agg=3, flow_y=None, flow_x=None, pad_t=0, pad_l=0)
+        dfe_census_refine_subpixel_f32: the vee fit through the chosen cell's raw census cost and its neighbours' 
     censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consistency=None, gate=False, fill=None, median=None, sgm=None,
-                        subpixel=False)
+                        subpixel=False, refine=False)
         dfe_census_flow_depth_pair_f32 / _u8: frames -> flow, match score, depth, depth confidence, with flowDepthPair's keys;
         sgm=(P1, P2): dfe_census_flow_depth_pair_sgm_f32 / _u8, the cost aggregated along image paths before the arg-min (DESIGN section 4.31);
-        with subpixel=True or min_unique in the dict: the _sgm2_ entries, which add the key unique
+        with subpixel=True or min_unique in the dict: the _sgm2_ entries, which add the key unique (DESIGN section 4.32);
+        refine=True: dfe_census_flow_depth_pair_subpixel_f32 / _u8, the flow refined on the raw cost
     censusPyramidScaleVolume(i0, i1, r, k, maxh, maxw, agg=3, beta=None)
         dfe_census_pyramid_scale_volume_f32: one scale of the census pyramid's volumes, staged (the matcher itself is
         MultiscaleModel.forwardFlow(..., census=True), multiscale.py)
@@ -89,9 +92,50 @@ def censusCostVolume(sig0, sig1, hWin, wWin, agg=3):
     return out
 
 
-def censusFlow(sig0, sig1, nbits, hWin, wWin, agg=3):
+def censusRefineSubpixel(sig0, sig1, hWin, wWin, idx, agg=3, flow_y=None, flow_x=None, pad_t=0, pad_l=0):
+    """The sub-pixel refinement on the raw census cost, alone (dfe_census_refine_subpixel_f32; include/dfe.h): for
+    every pixel of idx [Ha][Wa] (int64, the 1-based class of censusFlow) the vee fit per axis through the aggregated cost of the class's
+    cell and its two neighbours', re-formed from the signatures.  Returns (flow_y, flow_x): the given float32 planes (one shape
+    [Hf][Wf], contiguous, Hf >= pad_t + Ha, Wf >= pad_l + Wa), written in place at [y + pad_t][x + pad_l], or new Ha x Wa planes of
+    zeros.  Pixels whose idx is outside 1 .. hWin wWin keep what the planes held.  Meant for agg >= 3 or several channels: one channel
+    without a box has too few bits to refine on."""
+    name = "censusRefineSubpixel"
+    sig0, sig1 = _sigs(sig0, sig1, name)
+    C, Hp, Wp = sig0.shape
+    Ha, Wa = _region(name, C, Hp, Wp, hWin, wWin, agg)
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64:
+        raise TypeError("%s: an int64 class map expected" % name)
+    if tuple(idx.shape) != (Ha, Wa):
+        raise ValueError("%s: idx %s, the region is %d x %d" % (name, tuple(idx.shape), Ha, Wa))
+    if not all(isinstance(n, int) and not isinstance(n, bool) and n >= 0 for n in (pad_t, pad_l)):
+        raise ValueError("%s: pads %r, %r: ints of at least 0 expected" % (name, pad_t, pad_l))
+    if (flow_y is None) != (flow_x is None):
+        raise ValueError("%s: flow_y and flow_x go together" % name)
+    if flow_y is not None:
+        for t in (flow_y, flow_x):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                raise TypeError("%s: float32 flow planes expected" % name)
+        if flow_y.dim() != 2 or flow_y.shape != flow_x.shape or not (flow_y.is_contiguous() and flow_x.is_contiguous()):
+            raise ValueError("%s: two contiguous planes of one shape expected" % name)
+        if flow_y.shape[0] < pad_t + Ha or flow_y.shape[1] < pad_l + Wa:
+            raise ValueError("%s: planes %s hold no %d x %d region at (%d, %d)" % (name, tuple(flow_y.shape), Ha, Wa, pad_t, pad_l))
+    sig0, sig1, idx = _on_device(name, (sig0, sig1, idx), dtype=None, expected="CUDA tensors expected")
+    if flow_y is None:
+        flow_y = torch.zeros((pad_t + Ha, pad_l + Wa), dtype=torch.float32, device=sig0.device)
+        flow_x = torch.zeros_like(flow_y)
+    elif flow_y.device != sig0.device or flow_x.device != sig0.device:
+        raise TypeError("%s: the flow planes are on another device" % name)
+    ctx = get_ctx(sig0)
+    ctx.check(lib().dfe_census_refine_subpixel_f32(ctx.handle, ptr(sig0), ptr(sig1), C, Hp, Wp, hWin, wWin, agg, ptr(idx), ptr(flow_y), ptr(flow_x),
+                                                   flow_y.shape[1], pad_t, pad_l))
+    return flow_y, flow_x
+
+
+def censusFlow(sig0, sig1, nbits, hWin, wWin, agg=3, refine=False):
     """The fused sweep: dict(idx int64 (1-based class, first minimum, the centre wins an exact tie), best (the cost), match
-    (1 - best / (nbits C agg^2)), flow_y, flow_x), all [Ha][Wa].  nbits = kh kw - 1 of the transform that made the signatures."""
+    (1 - best / (nbits C agg^2)), flow_y, flow_x), all [Ha][Wa].  nbits = kh kw - 1 of the transform that made the signatures.
+    refine=True: flow_y / flow_x are refined by censusRefineSubpixel behind the sweep; idx, best and match are untouched.  Meant for
+    agg >= 3 or several channels."""
     sig0, sig1 = _sigs(sig0, sig1, "censusFlow")
     C, Hp, Wp = sig0.shape
     if not isinstance(nbits, int) or isinstance(nbits, bool) or not 1 <= nbits <= 63:
@@ -105,10 +149,13 @@ def censusFlow(sig0, sig1, nbits, hWin, wWin, agg=3):
     ctx = get_ctx(sig0)
     ctx.check(lib().dfe_census_flow_f32(ctx.handle, ptr(sig0), ptr(sig1), C, Hp, Wp, nbits, hWin, wWin, agg, ptr(res["idx"]), ptr(res["best"]),
                                         ptr(res["match"]), ptr(res["flow_y"]), ptr(res["flow_x"])))
+    if refine:
+        ctx.check(lib().dfe_census_refine_subpixel_f32(ctx.handle, ptr(sig0), ptr(sig1), C, Hp, Wp, hWin, wWin, agg, ptr(res["idx"]), ptr(res["flow_y"]),
+                                                       ptr(res["flow_x"]), Wa, 0, 0))
     return res
 
 
-def _pair(a, b, k, hWin, wWin, agg, fx, fy, scale, sgm=None, subpixel=False):
+def _pair(a, b, k, hWin, wWin, agg, fx, fy, scale, sgm=None, subpixel=False, refine=False):
     C, H, W = a.shape
     flow = torch.empty((2, H, W), dtype=torch.float32, device=a.device)
     match = torch.empty((H, W), dtype=torch.float32, device=a.device)
@@ -116,9 +163,12 @@ def _pair(a, b, k, hWin, wWin, agg, fx, fy, scale, sgm=None, subpixel=False):
     conf = torch.empty_like(match)
     ctx = get_ctx(a)
     res = {"flow": flow, "scores": match}
-    # the entry: plain, _sgm_ (P1, P2, paths) or, with subpixel or a named min_unique, _sgm2_ (... subpixel, min_unique, and unique behind match)
+    # the entry: plain, _subpixel_ (refine: the plain arguments), _sgm_ (P1, P2, paths) or, with subpixel or a named min_unique, _sgm2_
+    # (... subpixel, min_unique, and unique behind match)
     name, mid, outs = "dfe_census_flow_depth_pair_", (), (ptr(flow), ptr(match))
-    if sgm is not None and (subpixel or sgm[4]):
+    if refine:
+        name += "subpixel_"
+    elif sgm is not None and (subpixel or sgm[4]):
         res["unique"] = torch.empty_like(match)
         name, mid, outs = name + "sgm2_", sgm[:3] + (int(bool(subpixel)), sgm[3]), outs + (ptr(res["unique"]),)
     elif sgm is not None:
@@ -134,7 +184,7 @@ def _pair(a, b, k, hWin, wWin, agg, fx, fy, scale, sgm=None, subpixel=False):
 
 
 def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consistency=None, gate=False, fill=None, median=None, sgm=None,
-                        subpixel=False):
+                        subpixel=False, refine=False):
     """One frame pair through the census matcher: C x H x W frames (float32 or uint8, 1 <= C <= 4), a k x k patch (k odd, 3 .. 7), an
     hWin x wWin search window, the Hamming cost summed over an agg x agg box (1, 3 or 5), foe = (x, y) focus of expansion.  Returns the keys
     of flowDepthPair: flow [2][H][W] (y, x), scores [H][W] = the match score 1 - best / ((k k - 1) C agg^2), depth, depth_conf, zero outside
@@ -149,11 +199,18 @@ def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consis
     subpixel=True (with sgm only, else ValueError) or min_unique in the sgm dict: the
     dfe_census_flow_depth_pair_sgm2_f32 / _u8 entries -- the flow moves by the per-axis parabola through the AGGREGATE, and the dict gains
     unique [H][W], the uniqueness (second - best) / second of the aggregate gated by min_unique, 0 outside the region; scores keeps its
-    meaning, and fill and median still weigh by scores > 0."""
+    meaning, and fill and median still weigh by scores > 0.
+    refine=True (without sgm, else ValueError): dfe_census_flow_depth_pair_subpixel_f32 / _u8 -- the step runs
+    unchanged, then its flow moves per axis by the vee fit through the RAW census cost of the chosen cell and its two neighbours'; depth and
+    depth_conf are made from the refined flow, scores and the border are the step's.  With consistency= both directions are refined; gate,
+    fill and median work as before on the refined flow.  Meant for agg >= 3 or several channels: one channel without a box has too few
+    bits to refine on, and the refined flow is then no better than the integer one."""
     median = _median_arg(median)
     sgm = _sgm_pick_arg(sgm, "censusFlowDepthPair")
     if subpixel and sgm is None:
         raise ValueError("censusFlowDepthPair: subpixel=True refines on the aggregate: it needs sgm=")
+    if refine and sgm is not None:
+        raise ValueError("censusFlowDepthPair: refine=True refines on the raw cost: with sgm= use subpixel=True, which refines on the aggregate")
     for t in (img1, img2):
         if not isinstance(t, torch.Tensor) or t.dtype not in (torch.float32, torch.uint8) or t.dtype != img1.dtype:
             raise TypeError("censusFlowDepthPair: two float32 or two uint8 frames expected")
@@ -172,9 +229,9 @@ def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consis
     a, b = _frames(a, b, "censusFlowDepthPair")   # (the device check comes last: every check above needs none)
     R = ((H - Ha) // 2, (W - Wa) // 2, Ha, Wa)
     fx, fy = float(foe[0]), float(foe[1])
-    res = _pair(a, b, k, hWin, wWin, agg, fx, fy, float(scale), sgm, subpixel)
+    res = _pair(a, b, k, hWin, wWin, agg, fx, fy, float(scale), sgm, subpixel, bool(refine))
     if consistency is not None:
-        bw = _pair(b, a, k, hWin, wWin, agg, fx, fy, float(scale), sgm, subpixel)["flow"]
+        bw = _pair(b, a, k, hWin, wWin, agg, fx, fy, float(scale), sgm, subpixel, bool(refine))["flow"]
         mask, err = flowConsistency(res["flow"], bw, float(consistency), R)
         res.update(flow_bw=bw, consistent=mask, consistency_err=err)
         if gate:

@@ -531,8 +531,10 @@ int dfe_multiscale_subpixel_launch(dfe_ctx *ctx, const MsSubpixelArgs &a);
 DFE_HIDDEN int dfe_pyramid_prep_scale(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int r, int pl, int pt, int Hp, int Wp, float *d,
                                       float *p);
 // the one-call pyramid matcher in its census mode (dfe_multiscale_census_flow_pair_*); bytes: I0 / I1 are uint8 frames, taken as float(byte)
+// refine: the vee fit on the raw census cost behind the matcher (census_subpixel.hip; flow required)
 DFE_HIDDEN int dfe_multiscale_census_pair(dfe_ctx *ctx, const void *I0, const void *I1, bool bytes, int C, int H, int W, int k, int maxh, int maxw,
-                                          const int *ratios, int nratios, int agg, float beta, float *flow, int64_t *idx, const char *entry);
+                                          const int *ratios, int nratios, int agg, float beta, float *flow, int64_t *idx, const char *entry,
+                                          bool refine = false);
 
 // census_pyramid.hip -- the census cost of the pyramid's scales, from the padded scale frames that ms_prep_raw leaves to the volumes the
 // cascade stages read
@@ -550,3 +552,15 @@ DFE_HIDDEN bool dfe_census_pyramid_fast(int maxh, int maxw);   // the window has
 DFE_HIDDEN int dfe_census_pyramid_signatures(dfe_ctx *ctx, const DfeCensusPyramid &a);   // every scale, both frames, one launch
 // every scale's volume: one launch where dfe_census_pyramid_fast, else the staged kernels scale by scale; names the route in ctx->ms_census
 DFE_HIDDEN int dfe_census_pyramid_volumes(dfe_ctx *ctx, const DfeCensusPyramid &a);
+
+// census_subpixel.hip -- the census pyramid's sub-pixel refinement: from the class map and every scale's signature planes to the refined flow
+struct DfeCenfitPyramid {
+    const uint64_t *s0[DFE_MAX_RATIOS], *s1[DFE_MAX_RATIOS];   // signature planes [C][Hg][Wg] (frame 0, frame 1)
+    int r[DFE_MAX_RATIOS], Hg[DFE_MAX_RATIOS], Wg[DFE_MAX_RATIOS];
+    int base[DFE_MAX_RATIOS];   // 0-based class id of the scale's first class in the joined vector
+    int d[DFE_MAX_RATIOS];      // ring width of scale s >= 1
+    int nratios, ncls, C, H, W, maxh, maxw, agg;
+    const long long *idx;       // [H][W], 1-based class ids
+    float *fy, *fx;             // [H][W] each, written where idx is a class id
+};
+DFE_HIDDEN int dfe_census_pyramid_subpixel_launch(dfe_ctx *ctx, const DfeCenfitPyramid &a);

@@ -1017,6 +1017,7 @@ struct MsArgs {
     // (census_pyramid.hip), the receptive field k + census_agg - 1
     int census_agg = 0;
     float census_beta = 0.f;
+    bool census_refine = false;    // census mode: the vee fit on the raw census cost behind the matcher (census_subpixel.hip; flow required)
 };
 // one scale's sizes
 struct MsScale {
@@ -1080,7 +1081,7 @@ static int ms_plan(dfe_ctx *ctx, const MsArgs &a, MsPlan *plan) {
     const int *ratios = a.ratios;
     const char *entry = a.entry ? a.entry : "dfe_multiscale_flow_pair_f32";
     DFE_REQUIRE(ctx, a.I0 && a.I1 && (a.flow || a.idx), DFE_E_ARG, "%s: NULL tensor", entry);
-    DFE_REQUIRE(ctx, !a.subpixel || a.flow, DFE_E_ARG, "%s: flow is NULL", entry);
+    DFE_REQUIRE(ctx, !(a.subpixel || a.census_refine) || a.flow, DFE_E_ARG, "%s: flow is NULL", entry);
     DFE_REQUIRE(ctx, C > 0 && k > 0 && maxh > 0 && maxw > 0, DFE_E_ARG, "%s: bad size", entry);
     const bool census = a.census_agg != 0;
     if (census) {
@@ -1199,7 +1200,7 @@ static MsBufs ms_bufs(const MsPlan &P, DfeCarve &c, bool frames_only = false) {
         B.sig0[s] = c.take<uint64_t>(2 * ng);
         B.sig1[s] = B.sig0[s] ? B.sig0[s] + ng : nullptr;
     }
-    B.idx_tmp = c.take<int64_t>(a.subpixel && !a.idx ? (size_t)a.H * a.W : 0);
+    B.idx_tmp = c.take<int64_t>((a.subpixel || a.census_refine) && !a.idx ? (size_t)a.H * a.W : 0);
     return B;
 }
 
@@ -1482,8 +1483,8 @@ static int ms_cascade_cell(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const
     return DFE_OK;
 }
 
-// census mode: every scale's signatures in one launch, every scale's volume in one more (census_pyramid.hip)
-static int ms_census_volumes(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B) {
+// census mode: the plan and the arena as census_pyramid.hip's launchers take them (cost: NULL where the arena holds the frames only)
+static DfeCensusPyramid ms_census_desc(const MsPlan &P, const MsBufs &B) {
     const MsArgs &a = P.a;
     DfeCensusPyramid cp{};
     cp.ns = a.nratios; cp.C = a.C; cp.k = a.k; cp.maxh = a.maxh; cp.maxw = a.maxw; cp.agg = a.census_agg; cp.beta = a.census_beta;
@@ -1491,6 +1492,12 @@ static int ms_census_volumes(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B) {
         cp.p0[s] = B.p0[s]; cp.p1[s] = B.p1[s]; cp.Hp[s] = P.sc[s].Hp; cp.Wp[s] = P.sc[s].Wp;
         cp.sig0[s] = B.sig0[s]; cp.sig1[s] = B.sig1[s]; cp.cost[s] = B.cost[s];
     }
+    return cp;
+}
+
+// census mode: every scale's signatures in one launch, every scale's volume in one more (census_pyramid.hip)
+static int ms_census_volumes(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B) {
+    const DfeCensusPyramid cp = ms_census_desc(P, B);
     int rc = dfe_census_pyramid_signatures(ctx, cp);
     if (rc) return rc;
     DfeStageScope st(ctx, DFE_STAGE_MATCH);
@@ -1537,13 +1544,28 @@ static int ms_subpixel(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const int
     return dfe_multiscale_subpixel_launch(ctx, sa);
 }
 
+// census mode: the vee fit of the class map `idx` into P.a.flow, on the integer census costs re-formed from the signature planes that
+// dfe_census_pyramid_signatures left in the arena (census_subpixel.hip)
+static int ms_census_subpixel(dfe_ctx *ctx, const MsPlan &P, const MsBufs &B, const int64_t *idx) {
+    DfeCenfitPyramid sa{};
+    for (int s = 0; s < P.a.nratios; ++s) {
+        sa.s0[s] = B.sig0[s]; sa.s1[s] = B.sig1[s];
+        sa.r[s] = P.sc[s].r; sa.Hg[s] = P.sc[s].Hp - P.a.k + 1; sa.Wg[s] = P.sc[s].Wp - P.a.k + 1;
+        sa.base[s] = P.g.base[s]; sa.d[s] = P.g.d[s];
+    }
+    sa.nratios = P.a.nratios; sa.ncls = P.g.ncls; sa.C = P.a.C; sa.H = P.a.H; sa.W = P.a.W; sa.maxh = P.a.maxh; sa.maxw = P.a.maxw; sa.agg = P.a.census_agg;
+    sa.idx = (const long long *)idx; sa.fy = P.a.flow; sa.fx = P.fx;
+    return dfe_census_pyramid_subpixel_launch(ctx, sa);
+}
+
 // Plan, allocate, look up the graph, run the stages.  The graph key holds the buffers and the shape, not the options (DFE_FINE_FUSE,
 // DFE_MID_FUSE, ... / the cost-volume mode): a replay keeps the plan it was captured with until a buffer or the shape changes.  It
 // holds the sub-pixel switch too: the two entries never replay each other's capture.
 static int multiscale_flow_pair(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw,
                                 const int *ratios, int nratios, float *flow, int64_t *idx, float f16_scale, const MsFilter *filt = nullptr,
-                                float u8_scale = 0.f, bool subpixel = false, const char *entry = nullptr, int census_agg = 0, float census_beta = 0.f) {
-    const MsArgs a{I0, I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, f16_scale, filt, u8_scale, subpixel, entry, census_agg, census_beta};
+                                float u8_scale = 0.f, bool subpixel = false, const char *entry = nullptr, int census_agg = 0, float census_beta = 0.f,
+                                bool census_refine = false) {
+    const MsArgs a{I0, I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, f16_scale, filt, u8_scale, subpixel, entry, census_agg, census_beta, census_refine};
     MsPlan P;
     int rc = ms_plan(ctx, a, &P);
     if (rc) return rc;
@@ -1558,7 +1580,7 @@ static int multiscale_flow_pair(dfe_ctx *ctx, const float *I0, const float *I1, 
     struct { const void *I0, *I1, *flow, *idx, *scr; int C, H, W, k, maxh, maxw, nratios, ratios[DFE_MAX_RATIOS]; float f16, u8; int subpixel; int agg; float beta; } gkey;
     memset(&gkey, 0, sizeof gkey);
     gkey.I0 = I0; gkey.I1 = I1; gkey.flow = flow; gkey.idx = idx; gkey.scr = scr;
-    gkey.C = C; gkey.H = H; gkey.W = W; gkey.k = k; gkey.maxh = maxh; gkey.maxw = maxw; gkey.nratios = nratios; gkey.f16 = f16_scale; gkey.u8 = u8_scale; gkey.subpixel = subpixel;
+    gkey.C = C; gkey.H = H; gkey.W = W; gkey.k = k; gkey.maxh = maxh; gkey.maxw = maxw; gkey.nratios = nratios; gkey.f16 = f16_scale; gkey.u8 = u8_scale; gkey.subpixel = (subpixel ? 1 : 0) | (census_refine ? 2 : 0);
     gkey.agg = census_agg; gkey.beta = census_beta;
     for (int s = 0; s < nratios; ++s) gkey.ratios[s] = ratios[s];
     const int gmode = filt ? 0 : dfe_graph_lookup(ctx, ctx->ms_graph, &gkey, sizeof gkey);
@@ -1569,9 +1591,10 @@ static int multiscale_flow_pair(dfe_ctx *ctx, const float *I0, const float *I1, 
     }
     DfeCarve arena(scr);
     const MsBufs B = ms_bufs(P, arena);
-    if (subpixel && !idx) P.a.idx = B.idx_tmp;   // (the refinement reads the class map)
+    if ((subpixel || census_refine) && !idx) P.a.idx = B.idx_tmp;   // (the refinement reads the class map)
     rc = ms_run(ctx, P, B);
     if (!rc && subpixel) rc = ms_subpixel(ctx, P, B, P.a.idx);
+    if (!rc && census_refine) rc = ms_census_subpixel(ctx, P, B, P.a.idx);
     return gmode == 1 ? dfe_graph_finish(ctx, ctx->ms_graph, rc) : rc;
 }
 
@@ -1602,6 +1625,28 @@ int dfe_multiscale_refine_subpixel_f32(dfe_ctx *ctx, const float *I0, const floa
     rc = ms_prep_raw(ctx, P, B);
     if (rc) return rc;
     return ms_subpixel(ctx, P, B, idx);
+}
+
+// the census pyramid's refinement alone: the plan's checks and geometry in census mode, an arena of the padded scale frames and their
+// signature planes (no volumes), ms_prep_raw, the signatures, the kernel
+int dfe_multiscale_census_refine_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw,
+                                              const int *ratios, int nratios, int agg, const int64_t *idx, float *flow) {
+    DFE_ENTER(ctx);
+    const char *fn = "dfe_multiscale_census_refine_subpixel_f32";
+    DFE_REQUIRE(ctx, idx && flow, DFE_E_ARG, "%s: NULL tensor", fn);
+    DFE_REQUIRE(ctx, agg != 0, DFE_E_ARG, "%s: agg=%d must be 1, 3 or 5", fn, agg);   // (0 would select the SSD pyramid)
+    const MsArgs a{I0, I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, nullptr, 0.f, nullptr, 0.f, false, fn, agg, 1.0f, true};   // (beta: unused)
+    MsPlan P;
+    int rc = ms_plan(ctx, a, &P);
+    if (rc) return rc;
+    MsBufs B;
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { B = ms_bufs(P, c, true); });
+    if (rc) return rc;
+    rc = ms_prep_raw(ctx, P, B);
+    if (rc) return rc;
+    rc = dfe_census_pyramid_signatures(ctx, ms_census_desc(P, B));
+    if (rc) return rc;
+    return ms_census_subpixel(ctx, P, B, idx);
 }
 
 int dfe_multiscale_flow_pair_f16(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw,
@@ -1743,8 +1788,8 @@ int dfe_multiscale_flow_pair_bytes(dfe_ctx *ctx, const uint8_t *I0, const uint8_
 
 // the census mode behind dfe_multiscale_census_flow_pair_f32 / _u8 (census_pyramid.hip): bytes are taken as float(byte)
 int dfe_multiscale_census_pair(dfe_ctx *ctx, const void *I0, const void *I1, bool bytes, int C, int H, int W, int k, int maxh, int maxw, const int *ratios,
-                               int nratios, int agg, float beta, float *flow, int64_t *idx, const char *entry) {
+                               int nratios, int agg, float beta, float *flow, int64_t *idx, const char *entry, bool refine) {
     DFE_REQUIRE(ctx, agg != 0, DFE_E_ARG, "%s: agg=%d must be 1, 3 or 5", entry, agg);   // (0 would select the SSD pyramid)
     return multiscale_flow_pair(ctx, (const float *)I0, (const float *)I1, C, H, W, k, maxh, maxw, ratios, nratios, flow, idx, 0.f, nullptr, bytes ? 1.0f : 0.f,
-                                false, entry, agg, beta);
+                                false, entry, agg, beta, refine);
 }

@@ -75,6 +75,12 @@ int dfe_census_radial_flow_depth_pair_f32(dfe_ctx *ctx, const dfe_census_radial_
 int dfe_census_pyramid_scale_volume_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int r, int k, int maxh, int maxw, int agg, float beta, float *out);
 int dfe_multiscale_census_flow_pair_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw, const int *ratios, int nratios, int agg, float beta, float *flow, int64_t *idx);
 int dfe_multiscale_census_flow_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int maxh, int maxw, const int *ratios, int nratios, int agg, float beta, float *flow, int64_t *idx);
+int dfe_census_refine_subpixel_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1, int C, int Hp, int Wp, int hWin, int wWin, int agg, const int64_t *idx, float *fy, float *fx, int pitch, int pad_t, int pad_l);
+int dfe_census_flow_depth_pair_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float *flow, float *match, float *depth, float *depth_conf);
+int dfe_census_flow_depth_pair_subpixel_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float scale, float *flow, float *match, float *depth, float *depth_conf);
+int dfe_multiscale_census_refine_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw, const int *ratios, int nratios, int agg, const int64_t *idx, float *flow);
+int dfe_multiscale_census_flow_pair_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh, int maxw, const int *ratios, int nratios, int agg, float beta, float *flow, int64_t *idx);
+int dfe_multiscale_census_flow_pair_subpixel_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int maxh, int maxw, const int *ratios, int nratios, int agg, float beta, float *flow, int64_t *idx);
 int dfe_spatial_matching_backward_f32(dfe_ctx *ctx, const float *in1, const float *in2, const float *gradOut, int K, int H1, int W1, int maxh, int maxw, float *gradIn1, float *gradIn2);
 int dfe_radial_matching_backward_f32(dfe_ctx *ctx, const float *in1, const float *in2, const float *gradOut, int K, int H1, int W, int hWin, float *gradIn1, float *gradIn2);
 int dfe_argbest_center(dfe_ctx *ctx, const float *vol, int64_t P, int N, int middle, int take_max, int64_t *idx, float *best);

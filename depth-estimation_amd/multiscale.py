@@ -378,7 +378,7 @@ class MultiscaleModel(Module):
         return out
 
     def _census_arg(self, census, input, f16_scale, subpixel):
-        """forwardFlow's census= after its checks: None (off), or (i0, i1, k, agg, beta) with the frames contiguous on one device"""
+        """forwardFlow's census= after its checks: None (off), or (i0, i1, k, agg, beta, refine) with the frames contiguous on one device"""
         from .census import _pyramid_args
         from .fields import _on_device
 
@@ -387,14 +387,18 @@ class MultiscaleModel(Module):
             return None
         if census is True:
             census = {}
-        if not isinstance(census, dict) or set(census) - {"agg", "beta"}:
-            raise ValueError("%s: census=%r: True or dict(agg=3, beta=None) expected" % (name, census))
+        if not isinstance(census, dict) or set(census) - {"agg", "beta", "refine"}:
+            raise ValueError("%s: census=%r: True or dict(agg=3, beta=None, refine=False) expected" % (name, census))
+        refine = census.get("refine", False)
+        if not isinstance(refine, bool):
+            raise ValueError("%s: census=: refine=%r must be True or False" % (name, refine))
         if self.filters is not None or self.prefiltered:
             raise ValueError("%s: census= needs the raw-patch model (no learned filters, not prefiltered)" % name)
         if f16_scale:
             raise ValueError("%s: census= is not available with f16_scale" % name)
         if subpixel:
-            raise ValueError("%s: census= is not available with subpixel=True (the refinement re-forms SSD costs)" % name)
+            raise ValueError("%s: census= is not available with subpixel=True (the refinement re-forms SSD costs): census=dict(refine=True) refines on "
+                             "the census cost" % name)
         kh, kw = self._hk()
         if kh != kw:
             raise ValueError("%s: census= needs square patches, got %r x %r" % (name, kh, kw))
@@ -406,16 +410,17 @@ class MultiscaleModel(Module):
             raise ValueError("%s: two C x H x W frames of one shape expected, got %s and %s" % (name, tuple(i0.shape), tuple(i1.shape)))
         k, agg, beta = _pyramid_args(name, i0.shape[0], kh, census.get("agg", 3), census.get("beta"))
         i0, i1 = _on_device(name, (i0, i1), dtype=None, expected="census=: CUDA tensors expected")   # (the device check comes last)
-        return i0, i1, k, agg, beta
+        return i0, i1, k, agg, beta, refine
 
     def _forward_flow_census(self, cen, one_call):
         """the class map and the flow planes of the census pyramid: the one call (float32 or uint8 frames), or the staged per-scale volumes
-        through _probs and dfe_cascade_flow_f32 -- the same bits"""
+        through _probs and dfe_cascade_flow_f32 -- the same bits; refine: the vee fit on the census cost behind either (the one call's
+        _subpixel_ form, or dfe_multiscale_census_refine_subpixel_f32 on the staged class map)"""
         from .census import censusPyramidScaleVolume
 
         g = self.geometry
         maxh, maxw = _g(g, "maxh"), _g(g, "maxw")
-        i0, i1, k, agg, beta = cen
+        i0, i1, k, agg, beta, refine = cen
         l = lib()
         rr, n = ratios_array(self.ratios)
         i0, i1, H, W = _pad_to_multiple(i0, i1, self.ratios[-1])
@@ -424,7 +429,7 @@ class MultiscaleModel(Module):
         idx = torch.empty((H, W), dtype=torch.int64, device=i0.device)
         flow = torch.empty((2, H, W), dtype=torch.float32, device=i0.device)
         if one_call:
-            fn = l.dfe_multiscale_census_flow_pair_u8 if i0.dtype == torch.uint8 else l.dfe_multiscale_census_flow_pair_f32
+            fn = getattr(l, "dfe_multiscale_census_flow_pair_%s%s" % ("subpixel_" if refine else "", "u8" if i0.dtype == torch.uint8 else "f32"))
             ctx.check(fn(ctx.handle, ptr(i0), ptr(i1), Cc, H, W, k, maxh, maxw, rr, n, agg, beta, ptr(flow), ptr(idx)))
             self.volumes, self.probs = None, None
         else:
@@ -432,6 +437,8 @@ class MultiscaleModel(Module):
             self.volumes = [censusPyramidScaleVolume(f0, f1, r, k, maxh, maxw, agg, beta) for r in self.ratios]
             self.probs = self._probs(self.volumes)
             ctx.check(l.dfe_cascade_flow_f32(ctx.handle, _ptr_array(self.probs), rr, n, H, W, maxh, maxw, ptr(idx), None, ptr(flow[0]), ptr(flow[1])))
+            if refine:
+                ctx.check(l.dfe_multiscale_census_refine_subpixel_f32(ctx.handle, ptr(f0), ptr(f1), Cc, H, W, k, maxh, maxw, rr, n, agg, ptr(idx), ptr(flow)))
         return ctx, idx, flow[0], flow[1], H, W
 
     def forwardFlow(self, input, process_full=True, one_call=True, f16_scale=None, subpixel=False, census=None):
@@ -446,10 +453,14 @@ class MultiscaleModel(Module):
         dfe_multiscale_flow_pair_subpixel_f32, or dfe_multiscale_refine_subpixel_f32 behind the staged path).  The table gains y_sub, x_sub
         (float32 [H][W]) and full carries them; index, y, x and the confidences are those of subpixel=False.
         census (raw-patch model, square patches of side 3, 5 or 7, 1 .. 4 channels, fp32 volumes, no refinement; not in the reference):
-        True or dict(agg=3, beta=None) -- every scale scores by the census cost instead of the SSD (include/dfe.h):
+        True or dict(agg=3, beta=None, refine=False) -- every scale scores by the census cost instead of the SSD (include/dfe.h):
         k x k signatures, Hamming distances summed over the channels and an agg x agg box (1, 3 or 5), times beta (None:
         0.25 / (C agg^2)) in front of the soft-min.  For frame pairs whose exposure differs.  float32 or uint8 frames; one_call:
         dfe_multiscale_census_flow_pair_f32 / _u8, else censusPyramidScaleVolume per scale through the staged chain -- the same bits.
+        refine=True in the dict: the flow is refined per axis by the vee fit through the winning cell's integer census
+        cost and its two neighbours' at the winning scale (dfe_multiscale_census_flow_pair_subpixel_f32 / _u8, or
+        dfe_multiscale_census_refine_subpixel_f32 behind the staged path); the table gains y_sub, x_sub as subpixel=True gives them on the SSD
+        pyramid, and index, y, x are those of refine=False.  Meant for agg >= 3 or several channels.
         None leaves every bit and every launch as it is."""
         g = self.geometry
         maxh, maxw = _g(g, "maxh"), _g(g, "maxw")
@@ -467,6 +478,7 @@ class MultiscaleModel(Module):
         cen = self._census_arg(census, input, f16_scale, subpixel)
         if cen is not None:
             ctx, idx, fy, fx, H, W = self._forward_flow_census(cen, one_call)
+            subpixel = cen[5]   # (the table carries the refined flow as the SSD refinement's does)
         elif one_call and not self.prefiltered and (self.filters is not None or kh == kw):
             i0, i1 = input
             i0, i1 = _f32c(i0, "MultiscaleModel: input[1]"), _f32c(i1, "MultiscaleModel: input[2]")

@@ -530,6 +530,56 @@ int dfe_multiscale_census_flow_pair_f32(dfe_ctx *ctx, const float *I0, const flo
 int dfe_multiscale_census_flow_pair_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int maxh,
                                        int maxw, const int *ratios, int nratios, int agg, float beta, float *flow, int64_t *idx);
 
+/* ---- sub-pixel flow on the raw census cost: the single-scale matcher and the pyramid (NOT in the reference) --- */
+/* For an output pixel (y, x) with chosen cell (r, s) -- the step's first minimum with the centre tie-break, whatever the window's
+ * parity; decoded flow dy = r - (hWin-1)/2, dx = s - (wWin-1)/2 -- cost(r', s') is the aggregated integer census cost of
+ * dfe_census_cost_volume_f32 for that pixel and cell: exact in fp32, at most 63 C a^2.  A Hamming cost is V-shaped around its
+ * minimum, so the fit is the equiangular ("vee") one, not the SSD paths' parabola.  Per axis (x shown; y alike with r -+ 1), in fp32:
+ *   c0 = cost(r, s), cm = cost(r, s-1), cp = cost(r, s+1);
+ *   off = 0 if s-1 < 0 or s+1 >= wWin (a neighbour outside the searched window);
+ *   else m = max(cm - c0, cp - c0); off = m > 0 ? clamp((cm - cp) / (2 m), -0.5, 0.5) : 0   (one IEEE division; everything before
+ *     it is an exact integer);
+ *   fx = (float)dx + off_x, fy = (float)dy + off_y.
+ * Where c0 is the minimum |off| <= 0.5 without the clamp; the clamp and the m > 0 test matter only for a class map from another
+ * producer.  Two equal minima side by side give +-0.5, the point between them.  The class, best and match never change.  Because the
+ * costs are integers every result is defined bit for bit.  Meant for agg >= 3 or several channels: one channel without a box has too
+ * few bits to refine on.
+ * dfe_census_refine_subpixel_f32: the refinement alone, from the 1-based idx [Ha][Wa] of dfe_census_flow_f32 and the signatures it
+ *   read; fy / fx written at [(y + pad_t) * pitch + x + pad_l].  Pixels whose idx is outside 1 .. hWin wWin keep what fy / fx held.
+ *   The limits and error codes of dfe_census_flow_f32; pitch >= pad_l + Wa, pads >= 0 (DFE_E_SHAPE).  One launch, a thread per pixel: the
+ *   five costs are re-formed from the two signature planes, frame 0's a x a box shared by all five, frame 1's plus-shaped footprint of
+ *   (a + 2)^2 - 4 signatures, a popcount per pair.
+ * dfe_census_flow_depth_pair_subpixel_f32 / _u8: the arguments and outputs of dfe_census_flow_depth_pair_f32 / _u8; the step runs
+ *   unchanged, then its pasted flow is refined and depth / depth_conf (NULL together, as there) are the step's per-pixel formula on the
+ *   refined flow.  match and the zero border are the step's.  Bit-identical to the staged public calls plus the paste. */
+int dfe_census_refine_subpixel_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1, int C, int Hp, int Wp, int hWin, int wWin,
+                                   int agg, const int64_t *idx, float *fy, float *fx, int pitch, int pad_t, int pad_l);
+int dfe_census_flow_depth_pair_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin,
+                                            int wWin, int agg, float foe_x, float foe_y, float *flow, float *match, float *depth,
+                                            float *depth_conf);
+int dfe_census_flow_depth_pair_subpixel_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin,
+                                           int wWin, int agg, float foe_x, float foe_y, float scale, float *flow, float *match,
+                                           float *depth, float *depth_conf);
+/* The pyramid.  A pixel's class id decodes (x2yxMultiNumber, dfe_x2yx_multi) to a scale with ratio r and a cell (a, b) of the
+ * maxh x maxw window, as in dfe_multiscale_refine_subpixel_f32.  The costs are the integer census costs of that scale -- step 4 above,
+ * before the multiply by beta, which cancels in the fit and would only add rounding -- at the scale's pixel (y / r, x / r), inside
+ * a coarse scale's ring hole too.  The rule above per axis, then
+ *   fx = (float)(dx r) + (float)r * off   (product and sum separately rounded).
+ * The class id, and with it the integer flow, never changes; the refined flow is within r / 2 of it per axis.
+ * dfe_multiscale_census_refine_subpixel_f32: the refinement alone, from any 1-based class map idx [H][W] into flow [2][H][W]; it
+ *   prepares the padded scales and their signatures itself.  Pixels whose idx is no class id keep what flow held.  The limits of
+ *   dfe_multiscale_census_flow_pair_f32 (no beta).
+ * dfe_multiscale_census_flow_pair_subpixel_f32 / _u8: the arguments of dfe_multiscale_census_flow_pair_f32 / _u8; the matcher runs
+ *   unchanged, then flow (required) is refined in place from the signatures the call already made; idx (optional) is the matcher's. */
+int dfe_multiscale_census_refine_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh,
+                                              int maxw, const int *ratios, int nratios, int agg, const int64_t *idx, float *flow);
+int dfe_multiscale_census_flow_pair_subpixel_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int maxh,
+                                                 int maxw, const int *ratios, int nratios, int agg, float beta, float *flow,
+                                                 int64_t *idx);
+int dfe_multiscale_census_flow_pair_subpixel_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k,
+                                                int maxh, int maxw, const int *ratios, int nratios, int agg, float beta, float *flow,
+                                                int64_t *idx);
+
 /* ---- N2: gradients of the two matchers (training drivers call model:backward through them) ------- */
 /* replaces: nn.SpatialMatching:updateGradInput / nn.SpatialRadialMatching:updateGradInput (un-vendored nnx), reached
  *   from radial/train_radial_opticalflow.lua:228-252 and opticalflow.lua:296-338.  gradOut has the forward output's
