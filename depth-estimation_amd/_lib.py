@@ -122,6 +122,7 @@ PROTOTYPES = {
     "dfe_set_scratch_limit": (C.c_int, [C.c_void_p, C.c_size_t]),
     "dfe_device_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     "dfe_device_free": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "dfe_contig_pool_trim": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dfe_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "dfe_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "dfe_profile_read_each": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int]),

@@ -2,6 +2,8 @@
 #include "dfe_internal.h"
 #include <cstring>
 #include <cstdlib>
+#include "dfe_contig_pool.h"
+#include <vector>
 
 static thread_local char g_create_err[512] = "";
 
@@ -28,6 +30,21 @@ int dfe_fail(dfe_ctx *ctx, int code, const char *fmt, ...) {
     return code;
 }
 
+// Physically contiguous blocks are never given back to the driver behind the caller's back: a block that a ctx lets go of (a growth, its
+// destruction, dfe_device_free) goes idle in the process-wide pool and serves the next contiguous request of its device that it can
+// hold (dfe_contig_pool.h has the reason and the contract; dfe_contig_pool_trim is the one way out of the pool).
+static DfeContigPool g_contig;
+
+// what every release of a ctx's memory goes through: a contiguous block goes idle in the pool, anything else back to the driver
+static hipError_t dfe_release(void *p) {
+    if (!p) return hipSuccess;
+    switch (g_contig.release(p)) {
+    case DfeContigPool::Idle: return hipSuccess;
+    case DfeContigPool::NotInUse: return hipErrorInvalidDevicePointer;   // released twice: it may be somebody else's by now
+    default: return hipFree(p);
+    }
+}
+
 // The one place that allocates and frees what a ctx owns (dfe_ctx_destroy frees the rest): grow-only, empty (nullptr, 0) after a failure.
 int dfe_grow(dfe_ctx *ctx, DfeBuf &b, size_t bytes, const char *name, int flags, bool *contig_out) {
     if (contig_out) *contig_out = false;
@@ -38,7 +55,7 @@ int dfe_grow(dfe_ctx *ctx, DfeBuf &b, size_t bytes, const char *name, int flags,
     DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     void *p = b.p;
     b = DfeBuf();
-    if (p) DFE_HIP(ctx, hipFree(p));
+    if (p) DFE_HIP(ctx, dfe_release(p));
     p = nullptr;
     hipError_t e = hipErrorUnknown;
     bool contig = false;
@@ -52,9 +69,17 @@ int dfe_grow(dfe_ctx *ctx, DfeBuf &b, size_t bytes, const char *name, int flags,
     // block; in contiguous memory the planes' fixed distance puts those streams on the same channels (conv 4 -> 10 planes: 45.6 against
     // 36.1 us for a VGA pair, vga-learned 0.211 against 0.196 ms, tools/conv_place_probe.py), which scattered pages break up.
     if ((flags & DFE_GROW_CONTIG) && ctx->opt_bool(DFE_OPT_ARENA_CONTIG, true)) {
-        e = hipExtMallocWithFlags(&p, bytes, hipDeviceMallocContiguous);
-        contig = e == hipSuccess;
-        if (!contig) { (void)hipGetLastError(); p = nullptr; }
+        size_t pooled = 0;
+        if ((p = g_contig.take(ctx->device, bytes, &pooled))) {   // an idle block of the pool, possibly larger: the buffer is as large as the block
+            bytes = pooled;
+            e = hipSuccess;
+            contig = true;
+        } else {
+            e = hipExtMallocWithFlags(&p, bytes, hipDeviceMallocContiguous);
+            contig = e == hipSuccess;
+            if (contig) g_contig.add(ctx->device, p, bytes);
+            else { (void)hipGetLastError(); p = nullptr; }
+        }
     }
     if (!contig) e = hipMalloc(&p, bytes);
     // (a failed allocation is reported here; it must not stay behind as the thread's last HIP error, where the caller's next launch
@@ -94,10 +119,20 @@ int dfe_device_alloc(dfe_ctx *ctx, size_t bytes, void **ptr, int *contiguous) {
     return DFE_OK;
 }
 
+int dfe_contig_pool_trim(dfe_ctx *ctx, size_t keep_bytes, size_t *idle_bytes) {
+    DFE_ENTER(ctx);
+    DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<void *> out;
+    const size_t left = g_contig.trim(ctx->device, keep_bytes, &out);
+    if (idle_bytes) *idle_bytes = left;
+    for (void *p : out) DFE_HIP(ctx, hipFree(p));
+    return DFE_OK;
+}
+
 int dfe_device_free(dfe_ctx *ctx, void *ptr) {
     if (!ptr) return DFE_OK;
     DFE_HIP(ctx, hipStreamSynchronize(ctx->stream));   // nothing of this ctx may still be writing there
-    DFE_HIP(ctx, hipFree(ptr));
+    DFE_HIP(ctx, dfe_release(ptr));
     return DFE_OK;
 }
 
@@ -195,7 +230,7 @@ void dfe_ctx_destroy(dfe_ctx *ctx) {
     for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
     for (const dfe_ctx::StageEvent &e : ctx->stage_events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (DfeBuf *b : {&ctx->scratch, &ctx->scratch_plain, &ctx->cn_coef, &ctx->ingest, &ctx->aux, &ctx->i8_verdict})
-        if (b->p) (void)hipFree(b->p);
+        if (b->p) (void)dfe_release(b->p);
     for (int i = 0; i < DFE_NSLOT; ++i) {
         if (ctx->slot[i].p) (void)hipFree(ctx->slot[i].p);
         if (ctx->copied[i]) (void)hipEventDestroy(ctx->copied[i]);

@@ -340,8 +340,10 @@ int dfe_graph_finish(dfe_ctx *ctx, dfe_ctx::GraphSlot &slot, int rc);
 int dfe_scratch(dfe_ctx *ctx, size_t bytes, void **out, bool plain = false);
 int dfe_aux_scratch(dfe_ctx *ctx, size_t bytes, void **out);   // the ctx's side buffer, grown to at least `bytes`
 // grows `b` to at least `bytes`: no-op when it is large enough; else drains ctx->stream (and the copy stream with
-// DFE_GROW_COPY_STREAM), frees, allocates (physically contiguous first with DFE_GROW_CONTIG and option arena_contig).  On failure `b` is
-// empty, HIP's last error is cleared and DFE_E_ALLOC names the buffer
+// DFE_GROW_COPY_STREAM), releases the old block (hipFree; a physically contiguous one goes idle in the process's pool instead,
+// dfe_contig_pool.h), allocates (with DFE_GROW_CONTIG and option arena_contig: an idle contiguous block of the pool that holds `bytes`,
+// else a new contiguous one, else hipMalloc; b.bytes is the block's size, which may exceed `bytes`).  On failure `b` is empty, HIP's last
+// error is cleared and DFE_E_ALLOC names the buffer
 enum { DFE_GROW_CONTIG = 1, DFE_GROW_COPY_STREAM = 2 };
 int dfe_grow(dfe_ctx *ctx, DfeBuf &b, size_t bytes, const char *name, int flags = 0, bool *contig_out = nullptr);
 // A launcher's layout `lay` (a function over a DfeCarve & that takes its buffers in order, dfe_carve.h) run for the size, the arena grown

@@ -37,6 +37,7 @@ int dfe_flow_last_path(dfe_ctx *ctx, int *i8_taken);
 int dfe_set_scratch_limit(dfe_ctx *ctx, size_t bytes);
 int dfe_device_alloc(dfe_ctx *ctx, size_t bytes, void **ptr, int *contiguous);
 int dfe_device_free(dfe_ctx *ctx, void *ptr);
+int dfe_contig_pool_trim(dfe_ctx *ctx, size_t keep_bytes, size_t *idle_bytes);
 int dfe_profile_enable(dfe_ctx *ctx, int on);
 int dfe_profile_read(dfe_ctx *ctx, double *total_ms, int *launches);
 int dfe_profile_read_each(dfe_ctx *ctx, double *total_ms, int *launches, float *each_ms, int cap);

@@ -132,9 +132,19 @@ int dfe_set_scratch_limit(dfe_ctx *ctx, size_t bytes);
  * sweeps write a volume at up to 10 % more bytes per second into contiguous memory than into an unlucky plain allocation (the ctx's own arena is
  * allocated the same way, option "arena_contig").  Any device pointer works as `out`; this is the allocation that is fastest to fill.
  * replaces: torch.Tensor():resize() of the matcher's output on the reference side (SpatialMatching.lua:24), for callers that want the
- * placement.  dfe_device_free releases it (NULL is allowed). */
+ * placement.  dfe_device_free releases it (NULL is allowed).
+ * A contiguous block is NOT handed back to the driver when it is released -- by dfe_device_free, by a growth of the ctx's arena or by
+ * dfe_ctx_destroy: it goes idle in a pool of the process and serves the next contiguous request on its device that it can hold (the
+ * smallest such block; freeing such memory is not safe on the driver this was developed on).  Hence: the block
+ * behind *ptr may be larger than `bytes` (the caller owns all of it until it frees it) and holds whatever its last user left; a second
+ * dfe_device_free of the same pointer fails with DFE_E_HIP and changes nothing; memory that the process's contexts took as contiguous
+ * stays with the process until dfe_contig_pool_trim. */
 int dfe_device_alloc(dfe_ctx *ctx, size_t bytes, void **ptr, int *contiguous);
 int dfe_device_free(dfe_ctx *ctx, void *ptr);
+/* Gives idle blocks of that pool on the ctx's device back to the driver (hipFree), largest first, until at most keep_bytes of them stay;
+ * *idle_bytes (may be NULL) = what stays.  keep_bytes = SIZE_MAX frees nothing and only reports.  Synchronises the ctx stream.  For a
+ * process that needs the memory more than it fears the driver's defect: allocations made after a trim are exposed to it again. */
+int dfe_contig_pool_trim(dfe_ctx *ctx, size_t keep_bytes, size_t *idle_bytes);
 /* per-launch HIP-event timing of the cost-volume kernel on the ctx stream (bench.py's roofline):
  * enable, run, then read the summed kernel time and launch count (read synchronises and resets) */
 int dfe_profile_enable(dfe_ctx *ctx, int on);

@@ -13,55 +13,12 @@ import torch
 
 from tests import egomotion_cases as cases
 from tests import tracker_ref64 as tr
+from tests.arena_run import SENTINEL, conv_layer, filled, float_pair, grow_and_reuse, u8_pair
 
 pytestmark = pytest.mark.gpu
-SENTINEL = -9
-
-
-def filled(cuda, *shape, dtype=torch.float32):
-    return torch.full(shape, SENTINEL, dtype=dtype, device=cuda)
-
-
-def same(a, b):
-    return torch.equal(a, b) if torch.is_tensor(a) else np.array_equal(a, b)
-
-
-def grow_and_reuse(run, A, B, more=(), options=None):
-    """run(ctx, case) -> list of outputs (device tensors, or numpy arrays for host results).  One context runs A, B, A and then `more`;
-    every result equals the one a fresh context gives for that case alone."""
-    from depth_estimation_amd.context import Context
-
-    def ctx_new():
-        c = Context(0)
-        for k, v in (options or {}).items():
-            c.set_option(k, v)
-        return c
-
-    order = (A, B, A) + tuple(more)
-    alone = {}
-    for case in order:
-        if case not in alone:
-            c = ctx_new()
-            alone[case] = run(c, case)
-            torch.cuda.synchronize()
-            c.close()
-    c = ctx_new()
-    for i, case in enumerate(order):
-        got = run(c, case)
-        torch.cuda.synchronize()
-        assert len(got) == len(alone[case])
-        for j, (g, w) in enumerate(zip(got, alone[case])):
-            assert same(g, w), "call %d (case %r): output %d differs from a fresh context's" % (i, case, j)
-    c.close()
 
 
 # ------------------------------------------------------------------ single-scale SSD step on uint8 frames
-def u8_pair(H, W, seed=7):
-    rng = np.random.default_rng(seed)
-    u0 = rng.integers(0, 256, (3, H, W), dtype=np.uint8)
-    return torch.from_numpy(u0), torch.from_numpy(np.roll(u0, (1, -2), axis=(1, 2)))
-
-
 @pytest.mark.parametrize("win,options", [(33, None), (33, {"cv_novol": 0}), (17, None)], ids=["volume-free", "volume", "tail-pass"])
 def test_u8_pair_step(dfe, cuda, win, options):
     """dfe_flow_depth_pair_u8: the frame buffer and the arena of the volume-free sweep, of the volume path (cv_novol = 0) and of a 17 x 17
@@ -96,24 +53,6 @@ def test_pipelined_ingest_slots(dfe, cuda):
 
 
 # ------------------------------------------------------------------ learned filter stacks
-def conv_layer(cuda, nIn, nOut, k, tanh, seed):
-    from depth_estimation_amd._lib import FilterLayer
-
-    g = torch.Generator().manual_seed(seed)
-    w = ((torch.rand((nOut, nIn, k, k), generator=g) - 0.5) * (2.0 / (k * k * nIn))).to(cuda)
-    b = ((torch.rand((nOut,), generator=g) - 0.5) * 0.1).to(cuda)
-    L = FilterLayer()
-    L.nIn, L.nOut, L.kH, L.kW, L.tanh_after = nIn, nOut, k, k, tanh
-    L.weight, L.bias, L.conn, L.nConn = w.data_ptr(), b.data_ptr(), None, 0
-    return L, (w, b)
-
-
-def float_pair(cuda, H, W, seed=11):
-    g = torch.Generator().manual_seed(seed)
-    f0 = torch.rand((3, H, W), generator=g)
-    return f0.to(cuda), torch.roll(f0, (1, -1), dims=(1, 2)).contiguous().to(cuda)
-
-
 @pytest.mark.parametrize("form", ["index+scores", "no index, no scores", "mean"])
 def test_single_scale_filtered(dfe, cuda, form):
     """dfe_flow_pair_filtered_f32 / _mean_f32 in the plain arena: stack 3 -> 4 (5 x 5, tanh), 4 -> 10 (5 x 5), window 16 x 16; 3 x 40 x 64
