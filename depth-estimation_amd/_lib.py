@@ -201,6 +201,18 @@ PROTOTYPES = {
                                             + [C.c_void_p] * 5),
     "dfe_census_flow_depth_pair_sgm2_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_float] * 5 + [C.c_uint, C.c_int, C.c_float]
                                            + [C.c_void_p] * 5),
+    "dfe_sgm_aggregate_guided_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_float, C.c_float, C.c_uint, C.c_int, C.c_void_p, C.c_void_p]
+                                     + [C.c_void_p, C.c_int, C.c_float, C.c_float]),
+    "dfe_sgm_plane_pick_guided_f32": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_float, C.c_uint, C.c_int, C.c_float] + [C.c_void_p] * 7
+                                      + [C.c_void_p, C.c_int, C.c_float, C.c_float]),
+    "dfe_flow_depth_pair_sgm_guided_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float] * 4 + [C.c_uint, C.c_int] + [C.c_float] * 3
+                                           + [C.c_void_p] * 4),
+    "dfe_flow_depth_pair_sgm_guided_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_float] * 5 + [C.c_uint, C.c_int] + [C.c_float] * 3
+                                          + [C.c_void_p] * 4),
+    "dfe_census_flow_depth_pair_sgm_guided_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_float] * 4 + [C.c_uint, C.c_int]
+                                                  + [C.c_float] * 3 + [C.c_void_p] * 5),
+    "dfe_census_flow_depth_pair_sgm_guided_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_float] * 5 + [C.c_uint, C.c_int]
+                                                 + [C.c_float] * 3 + [C.c_void_p] * 5),
     "dfe_census_radial_cost_volume_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "dfe_census_radial_flow_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p] * 4),
     "dfe_census_radial_flow_depth_pair_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_float, C.c_float, C.c_uint,

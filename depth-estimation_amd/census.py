@@ -168,6 +168,9 @@ def _pair(a, b, k, hWin, wWin, agg, fx, fy, scale, sgm=None, subpixel=False, ref
     name, mid, outs = "dfe_census_flow_depth_pair_", (), (ptr(flow), ptr(match))
     if refine:
         name += "subpixel_"
+    elif sgm is not None and sgm[5] is not None:   # the guided entry: _sgm2_'s arguments, then sigma and P2_edge; frame `a` guides
+        res["unique"] = torch.empty_like(match)
+        name, mid, outs = name + "sgm_guided_", sgm[:3] + (int(bool(subpixel)), sgm[3]) + sgm[5], outs + (ptr(res["unique"]),)
     elif sgm is not None and (subpixel or sgm[4]):
         res["unique"] = torch.empty_like(match)
         name, mid, outs = name + "sgm2_", sgm[:3] + (int(bool(subpixel)), sgm[3]), outs + (ptr(res["unique"]),)
@@ -200,6 +203,9 @@ def censusFlowDepthPair(img1, img2, k, hWin, wWin, foe, agg=3, scale=1.0, consis
     dfe_census_flow_depth_pair_sgm2_f32 / _u8 entries -- the flow moves by the per-axis parabola through the AGGREGATE, and the dict gains
     unique [H][W], the uniqueness (second - best) / second of the aggregate gated by min_unique, 0 outside the region; scores keeps its
     meaning, and fill and median still weigh by scores > 0.
+    sigma= or P2_edge= (None: P1) in the sgm dict: dfe_census_flow_depth_pair_sgm_guided_f32 / _u8 -- the call's
+    first frame on the region guides P2, which falls to P2_edge across its edges (sigma in the frame's units, bytes times scale for uint8
+    frames: scale matters here only); the dict gains unique as above.  With consistency= the backward call is guided by ITS first frame, img2.
     refine=True (without sgm, else ValueError): dfe_census_flow_depth_pair_subpixel_f32 / _u8 -- the step runs
     unchanged, then its flow moves per axis by the vee fit through the RAW census cost of the chosen cell and its two neighbours'; depth and
     depth_conf are made from the refined flow, scores and the border are the step's.  With consistency= both directions are refined; gate,

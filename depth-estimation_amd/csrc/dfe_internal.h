@@ -499,8 +499,9 @@ DFE_HIDDEN int dfe_sgm_check(dfe_ctx *ctx, const char *fn, int H, int W, int D, 
 // ... and its launches behind them, for a caller that has carved the arena itself.  work: dfe_sgm_work_planes(paths, agg != NULL) planes of
 // H * W * D floats (one per direction; none when the only direction goes straight to agg); agg [H][W][D] or NULL; flow [H][W] or NULL
 DFE_HIDDEN size_t dfe_sgm_work_planes(unsigned paths, bool agg_given);
+struct SgmPen;   // (sgm_common.h: the penalty planes of a guided call; NULL: one P2 for the whole frame)
 DFE_HIDDEN int dfe_sgm_run(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *work, float *agg,
-                           float *flow);
+                           float *flow, const SgmPen *pen = nullptr);
 
 // radial_pipeline.hip -- the stages around the matcher that the radial one calls and the census radial one call (census_radial.hip) share
 // the warp's buffers: two polar frames [C][H][Wp], the radius table (H floats), the angle's sine and cosine (W doubles each), and the

@@ -15,6 +15,8 @@
 //       L(d -+ 1) by one row shift each (a lane without a neighbour keeps the +Inf it is given as `old`), six more VALU operations,
 //       nothing through LDS.  The loads of the next kSgmAhead steps are in flight (a chain's addresses are known from its first step:
 //       the walk is SgmCursor of sgm_common.h, which sgm_plane.hip's path kernel shares, as it does the row minimum).
+//   guided_sgm_path_kernel<LPL>   the same body with the step's P2 taken from the direction's penalty plane (sgm_penalty.hip; DESIGN.md
+//       section 4.38): one value per 16-lane row, fetched with the step's costs through the same look-ahead.
 //   sgm_sum_kernel<LPL, FLOW>   agg = ((L_a + L_b) + L_c) + ... in ascending direction order, 16 lanes a pixel as above; the first
 //       minimum over the labels by a row reduction on (value, label); the aggregate is stored only if somebody reads it.
 #include "sgm_common.h"
@@ -40,8 +42,10 @@ __device__ __forceinline__ float sgm_row_shl1(float v, float edge) {   // lane j
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(edge), __float_as_int(v), 0x101, 0xf, 0xf, false));
 }
 
-template <int LPL>
-__global__ __launch_bounds__(64) void sgm_path_kernel(const SgmJob a) {
+// the body of the two path kernels.  GUIDED: the step's P2 is a cell of the direction's penalty plane (sgm_penalty.hip), one value per
+// 16-lane row, fetched with the step's costs through the same look-ahead, so a step's dependent chain keeps its length
+template <int LPL, bool GUIDED>
+__device__ __forceinline__ void sgm_path_body(const SgmJob &a, const SgmPen *pen) {
 #pragma clang fp contract(off)
     const float inf = __builtin_inff();
     const int k = blockIdx.y;                    // which of the directions
@@ -73,11 +77,24 @@ __global__ __launch_bounds__(64) void sgm_path_kernel(const SgmJob a) {
     float cb[kSgmAhead][LPL];
     int pixb[kSgmAhead];
     bool stb[kSgmAhead];
+    float penb[GUIDED ? kSgmAhead : 1];
+    const float *__restrict__ pplane = nullptr;
+    bool atq = false;
+    int qpix = 0;                                // the pixel fetched before this one: the step's predecessor (the first step has none and starts)
+    if constexpr (GUIDED) {
+        pplane = pen->plane[k];
+        atq = pen->atq[k] != 0;
+        qpix = f.y * a.W + f.x;
+    }
     auto fetch = [&](int slot) {
         const int pix = f.y * a.W + f.x;
         const long long e = (long long)pix * a.D;
 #pragma unroll
         for (int j = 0; j < LPL; ++j) cb[slot][j] = a.C[e + dc[j]];
+        if constexpr (GUIDED) {
+            penb[slot] = pplane[atq ? qpix : pix];
+            qpix = pix;
+        }
         pixb[slot] = pix;
         stb[slot] = f.start;
         ++fs;
@@ -97,12 +114,14 @@ __global__ __launch_bounds__(64) void sgm_path_kernel(const SgmJob a) {
             for (int j = 0; j < LPL; ++j) c[j] = in[j] ? cb[u][j] : inf;
             const int pix = pixb[u];
             const bool start = stb[u];
+            float P2 = a.P2;
+            if constexpr (GUIDED) P2 = penb[u];
             fetch(u);
             // L_r(p, d) = C(p, d) + (min(L(q, d), L(q, d - 1) + P1, L(q, d + 1) + P1, m + P2) - m), m = min_k L(q, k)
             float m = l[0];
             if constexpr (LPL == 2) m = fminf(m, l[1]);
             m = sgm_row_min(m);
-            const float far = m + a.P2;
+            const float far = m + P2;
             float lo[LPL], hi[LPL];              // L(q, d - 1), L(q, d + 1)
             if constexpr (LPL == 1) {
                 lo[0] = sgm_row_shr1(l[0], inf);
@@ -125,6 +144,15 @@ __global__ __launch_bounds__(64) void sgm_path_kernel(const SgmJob a) {
                 if (keep && in[j]) out[(long long)pix * a.D + d0 + j] = l[j];
         }
     }
+}
+
+template <int LPL>
+__global__ __launch_bounds__(64) void sgm_path_kernel(const SgmJob a) {
+    sgm_path_body<LPL, false>(a, nullptr);
+}
+template <int LPL>
+__global__ __launch_bounds__(64) void guided_sgm_path_kernel(const SgmJob a, const SgmPen pen) {
+    sgm_path_body<LPL, true>(a, &pen);
 }
 
 // agg = the n planes summed in order; flow = its first minimum.  16 lanes a pixel, 16 pixels a block
@@ -178,7 +206,7 @@ size_t dfe_sgm_work_planes(unsigned paths, bool agg_given) {
 // The launches of dfe_sgm_aggregate_f32 behind its argument checks.  work: dfe_sgm_work_planes(paths, agg != NULL) planes;
 // agg [H][W][D] or NULL; flow [H][W] or NULL.
 int dfe_sgm_run(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *work, float *agg,
-                float *flow) {
+                float *flow, const SgmPen *pen) {
     const bool direct = dfe_sgm_work_planes(paths, agg != nullptr) == 0;   // one direction, and its L is the aggregate the caller wants
     SgmJob a{};
     a.C = volume;
@@ -189,7 +217,10 @@ int dfe_sgm_run(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1
     for (int k = 0; k < a.n; ++k) a.L[k] = direct ? agg : work + (size_t)k * H * W * D;
     DfeProfScope prof(ctx);
     const dim3 grid((unsigned)dfe_cdiv(H > W ? H : W, 4), (unsigned)a.n);
-    if (D <= 16) hipLaunchKernelGGL(sgm_path_kernel<1>, grid, dim3(64), 0, ctx->stream, a);
+    if (pen) {
+        if (D <= 16) hipLaunchKernelGGL(guided_sgm_path_kernel<1>, grid, dim3(64), 0, ctx->stream, a, *pen);
+        else hipLaunchKernelGGL(guided_sgm_path_kernel<2>, grid, dim3(64), 0, ctx->stream, a, *pen);
+    } else if (D <= 16) hipLaunchKernelGGL(sgm_path_kernel<1>, grid, dim3(64), 0, ctx->stream, a);
     else hipLaunchKernelGGL(sgm_path_kernel<2>, grid, dim3(64), 0, ctx->stream, a);
     DFE_LAUNCH_CHECK(ctx);
     float *aout = direct ? nullptr : agg;
@@ -214,20 +245,47 @@ int dfe_sgm_check(dfe_ctx *ctx, const char *fn, int H, int W, int D, float P1, f
     return DFE_OK;
 }
 
+namespace {
+
+// the two aggregate entries behind DFE_ENTER (g: NULL for the unguided one)
+int sgm_aggregate(dfe_ctx *ctx, const char *fn, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *agg, float *flow,
+                  const SgmGuide *g) {
+    DFE_REQUIRE(ctx, volume && (agg || flow), DFE_E_ARG, "%s: %s", fn, volume ? "agg and flow are both NULL" : "volume is NULL");
+    DFE_REQUIRE(ctx, agg != volume, DFE_E_ARG, "%s: agg must not be the volume (every direction reads it)", fn);
+    int rc = dfe_sgm_check(ctx, fn, H, W, D, P1, P2, paths, ring);
+    if (!rc && g) rc = sgm_guide_check(ctx, fn, P1, P2, *g);
+    if (rc) return rc;
+    const bool guided = g && sgm_guided(*g);
+    float *work = nullptr, *planes = nullptr;
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
+        work = c.take<float>(dfe_sgm_work_planes(paths, agg != nullptr) * H * W * D);
+        if (guided) planes = c.take<float>(sgm_penalty_floats(paths, H, W));
+    });
+    if (rc) return rc;
+    DfeStageScope st(ctx, DFE_STAGE_MATCH);
+    SgmPen pen{};
+    if (guided) {
+        rc = sgm_penalty_run(ctx, *g, H, W, P2, paths, planes, &pen);
+        if (rc) return rc;
+    }
+    return dfe_sgm_run(ctx, volume, H, W, D, P1, P2, paths, ring, work, agg, flow, guided ? &pen : nullptr);
+}
+
+}  // namespace
+
 extern "C" {
 
 int dfe_sgm_aggregate_f32(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *agg,
                           float *flow) {
     DFE_ENTER(ctx);
-    DFE_REQUIRE(ctx, volume && (agg || flow), DFE_E_ARG, "dfe_sgm_aggregate_f32: %s", volume ? "agg and flow are both NULL" : "volume is NULL");
-    DFE_REQUIRE(ctx, agg != volume, DFE_E_ARG, "dfe_sgm_aggregate_f32: agg must not be the volume (every direction reads it)");
-    int rc = dfe_sgm_check(ctx, "dfe_sgm_aggregate_f32", H, W, D, P1, P2, paths, ring);
-    if (rc) return rc;
-    float *work = nullptr;
-    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { work = c.take<float>(dfe_sgm_work_planes(paths, agg != nullptr) * H * W * D); });
-    if (rc) return rc;
-    DfeStageScope st(ctx, DFE_STAGE_MATCH);
-    return dfe_sgm_run(ctx, volume, H, W, D, P1, P2, paths, ring, work, agg, flow);
+    return sgm_aggregate(ctx, "dfe_sgm_aggregate_f32", volume, H, W, D, P1, P2, paths, ring, agg, flow, nullptr);
+}
+
+int dfe_sgm_aggregate_guided_f32(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *agg,
+                                 float *flow, const float *guide, int Cg, float sigma, float P2_edge) {
+    DFE_ENTER(ctx);
+    const SgmGuide g{guide, false, 1.f, Cg, (size_t)H * W, W, sigma, P2_edge};
+    return sgm_aggregate(ctx, "dfe_sgm_aggregate_guided_f32", volume, H, W, D, P1, P2, paths, ring, agg, flow, &g);
 }
 
 }  // extern "C"

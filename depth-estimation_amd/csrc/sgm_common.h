@@ -1,6 +1,7 @@
-// sgm_common.h -- what the semi-global files (sgm.hip, sgm_plane.hip, sgm_pick.hip; nobody else includes this) hold to ONE definition,
+// sgm_common.h -- what the semi-global files (sgm.hip, sgm_plane.hip, sgm_pick.hip, sgm_penalty.hip; nobody else includes this) hold to ONE definition,
 // because the device is tested against the numpy definitions bit for bit and a fix made in one copy only would be a silent divergence:
 //   host    the direction table, the paths / P1 / P2 check (the work-planes rule is dfe_sgm_work_planes, dfe_internal.h)
+//           the guide and the penalty planes of the edge-aware entries (sgm_penalty.hip)
 //   device  the 16-lane row minimum; the line cursor of the two path kernels; the summed arg-min of the plane family -- the ordered sum,
 //           the (value, class) reduction, the centre rule, the stores of the winner -- which sgmp_sum_kernel and sgpk_pick_kernel share
 // (not in dfe_wave.h: that file is hashed whole into the traffic profiles, and nothing here touches the kernels they describe)
@@ -31,6 +32,32 @@ inline int sgm_params_check(dfe_ctx *ctx, const char *fn, float P1, float P2, un
     return DFE_OK;
 }
 
+// ---- the guided penalty (sgm_penalty.hip defines the functions) ----
+// Where P2(p, r) comes from: a guide image on the volume's pixel grid, as floats or as bytes read as float(byte) * scale
+struct SgmGuide {
+    const void *g;         // channel c's pixel (y, x) at g[c chan + y pitch + x]; NULL: no guide
+    bool bytes;
+    float scale;           // (bytes only)
+    int Cg;
+    size_t chan;
+    int pitch;
+    float sigma, P2_edge;
+};
+// what the guided path kernels take beside their job: for the job's direction k the [H][W] plane of its AXIS, which holds P2(p, r) at p
+// for the axis' even bit r -- and, (a - b)^2 and (b - a)^2 having the same bits, P2(p, -r) at p's predecessor p + r for the odd bit
+struct SgmPen {
+    const float *plane[8];
+    int atq[8];            // 1: direction k reads its plane at the predecessor's pixel
+};
+inline bool sgm_guided(const SgmGuide &g) { return g.g && g.sigma > 0.f; }   // (sigma NaN: not guided)
+// the rules of the guided entries on top of the unguided ones'
+DFE_HIDDEN int sgm_guide_check(dfe_ctx *ctx, const char *fn, float P1, float P2, const SgmGuide &g);
+// floats of the penalty planes of a guided call: H * W per axis that `paths` touches
+DFE_HIDDEN size_t sgm_penalty_floats(unsigned paths, int H, int W);
+// one launch: every cell of the planes of the axes `paths` touches, the predecessor's column taken modulo W (the ring's wrap pair; on the
+// plane such a step is a chain start and its cell is written and not used), P2 where the predecessor's row lies outside.  Fills `pen`
+DFE_HIDDEN int sgm_penalty_run(dfe_ctx *ctx, const SgmGuide &g, int H, int W, float P2, unsigned paths, float *planes, SgmPen *pen);
+
 // ---- the plane family's job and outputs (sgm_plane.hip defines the functions; sgm_pick.hip launches the path kernel through them) ----
 struct SgmpJob {
     const float *C;      // [H][W][cells]
@@ -57,9 +84,10 @@ DFE_HIDDEN int sgmp_check(dfe_ctx *ctx, const char *fn, int H, int W, int hWin, 
 // The job of a call: direction k into work + k planes of H * W * cells floats (dfe_sgm_work_planes(paths, agg != NULL) of them), or the
 // only direction straight into agg, which is then set to NULL: nothing is left to store.  paths == 0 (the pick): the volume is the one plane
 DFE_HIDDEN SgmpJob sgmp_job(const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, float *work, float *&agg);
-DFE_HIDDEN int sgmp_launch_paths(dfe_ctx *ctx, const SgmpJob &a);   // sgmp_path_kernel for the job's directions
+DFE_HIDDEN int sgmp_launch_paths(dfe_ctx *ctx, const SgmpJob &a, const SgmPen *pen = nullptr);   // sgmp_path_kernel for the job's directions (pen: its guided form)
 // the two launches behind the checks: the paths, then the sum kernel for whatever `o` asks for
-DFE_HIDDEN int sgmp_run(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, float *work, SgmpOut o);
+DFE_HIDDEN int sgmp_run(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, float *work, SgmpOut o,
+                        const SgmPen *pen = nullptr);
 
 // ---- device ----
 

@@ -11,6 +11,9 @@
 //   The path launch is sgm_plane.hip's, unchanged (sgmp_launch_paths on sgmp_job's job); paths == 0 skips it and A = the volume.
 //   The one calls: dfe_flow_depth_pair_sgm_f32 / _u8 (the SSD step) and, in ONE body on census.hip's front end, the census entries
 //   dfe_census_flow_depth_pair_sgm_f32 / _u8 (sgmp_run: the plain aggregate) and dfe_census_flow_depth_pair_sgm2_f32 / _u8 (sgpk_run).
+//   The guided entries are the same bodies with a guide: dfe_sgm_plane_pick_guided_f32 and the one calls
+//   dfe_flow_depth_pair_sgm_guided_* / dfe_census_flow_depth_pair_sgm_guided_*, whose guide is frame 0 on the pasted region; the penalty
+//   planes (sgm_penalty.hip) are carved behind the direction planes and handed to the path launch.
 #include "sgm_common.h"
 #include "subpixel_offset.h"   // the parabola's vertex on one axis (include/dfe.h: this order, IEEE division)
 
@@ -81,10 +84,11 @@ int sgpk_check(dfe_ctx *ctx, const char *fn, int H, int W, int hWin, int wWin, f
 
 // The launches behind the checks: sgm_plane.hip's path kernel (paths != 0), then the pick.  work: dfe_sgm_work_planes(paths, o.agg != NULL)
 // planes; o: where the results go, and min_unique
-int sgpk_run(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, int subpixel, float *work, SgmpOut o) {
+int sgpk_run(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, int subpixel, float *work, SgmpOut o,
+             const SgmPen *pen = nullptr) {
     const SgmpJob a = sgmp_job(volume, H, W, hWin, wWin, P1, P2, paths, work, o.agg);
     if (paths) {
-        int rc = sgmp_launch_paths(ctx, a);
+        int rc = sgmp_launch_paths(ctx, a, pen);
         if (rc) return rc;
     }
     DfeProfScope prof(ctx);
@@ -96,10 +100,27 @@ int sgpk_run(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin
     return DFE_OK;
 }
 
-// the SSD one call behind its device guard, on float frames
+// The guide of a one call: its own frame 0 [C][H][W], all channels, cropped to the Hr x Wr pixels at (pad_t, pad_l) the volume's plane is
+// pasted at; bytes read as float(byte) * scale
+SgmGuide sgm_frame_guide(const void *I0, bool bytes, float scale, int C, int H, int W, int pad_t, int pad_l, float sigma, float P2_edge) {
+    const size_t off = (size_t)pad_t * W + pad_l;
+    const void *g = bytes ? (const void *)((const uint8_t *)I0 + off) : (const void *)((const float *)I0 + off);
+    return SgmGuide{g, bytes, scale, C, (size_t)H * W, W, sigma, P2_edge};
+}
+
+// the penalty planes of a guided call into `planes` (sgm_penalty_floats of them) and `pen`; *use = pen, or NULL where the call is not guided
+int sgm_guide_planes(dfe_ctx *ctx, const SgmGuide *gd, int H, int W, float P2, unsigned paths, float *planes, SgmPen *pen, const SgmPen **use) {
+    *use = nullptr;
+    if (!gd || !paths || !sgm_guided(*gd)) return DFE_OK;
+    const int rc = sgm_penalty_run(ctx, *gd, H, W, P2, paths, planes, pen);
+    if (!rc) *use = pen;
+    return rc;
+}
+
+// the SSD one call behind its device guard, on float frames (gd: sigma and P2_edge of the guided entries, else NULL)
 int sgpk_ssd_pair(dfe_ctx *ctx, const char *fn, const float *I0, const float *I1, const uint8_t *B0, const uint8_t *B1, float scale, int C, int H, int W, int k,
                   int hWin, int wWin, float foe_x, float foe_y, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *scores,
-                  float *depth, float *depth_conf) {
+                  float *depth, float *depth_conf, const SgmGuide *gd = nullptr) {
     // the single-scale step's checks, in its order, then the aggregation's and the pick's: everything is refused before any launch
     const bool bytes = B0 || B1;
     DFE_REQUIRE(ctx, (bytes ? B0 && B1 : I0 && I1) && flow && scores, DFE_E_ARG, "%s: NULL tensor", fn);
@@ -109,8 +130,9 @@ int sgpk_ssd_pair(dfe_ctx *ctx, const char *fn, const float *I0, const float *I1
     DFE_REQUIRE(ctx, Ho > 0 && Wo > 0, DFE_E_SHAPE, "%s: frame %dx%d too small for kernel %d + window %dx%d", fn, H, W, k, hWin, wWin);
     DFE_REQUIRE(ctx, paths != 0u, DFE_E_ARG, "%s: paths=0x%x must be 1 .. 255 (bit r = direction r)", fn, paths);
     int rc = sgpk_check(ctx, fn, Ho, Wo, hWin, wWin, P1, P2, paths, min_unique);
+    if (!rc && gd) rc = sgm_guide_check(ctx, fn, P1, P2, *gd);
     if (rc) return rc;
-    float *f0 = nullptr, *f1 = nullptr, *vol = nullptr, *work = nullptr;
+    float *f0 = nullptr, *f1 = nullptr, *vol = nullptr, *work = nullptr, *planes = nullptr;
     const size_t n = (size_t)C * H * W, plane = (size_t)Ho * Wo * hWin * wWin;
     // The whole volume: the vertical paths need every row, so there are no bands.  In the PLAIN arena: the volume and the n planes lie a
     // fixed distance apart, and in physically contiguous memory the build and the path launch are slower for it (VGA, 17 x 17, 4 paths:
@@ -119,6 +141,7 @@ int sgpk_ssd_pair(dfe_ctx *ctx, const char *fn, const float *I0, const float *I1
         if (bytes) { f0 = c.take<float>(n); f1 = c.take<float>(n); }
         vol = c.take<float>(plane);
         work = c.take<float>(dfe_sgm_work_planes(paths, false) * plane);
+        if (gd && gd->sigma > 0.f) planes = c.take<float>(sgm_penalty_floats(paths, Ho, Wo));
     }, /*plain*/ true);
     if (rc) return rc;
     if (bytes) {   // float(byte) * scale, as dfe_flow_depth_pair_u8 converts
@@ -137,7 +160,14 @@ int sgpk_ssd_pair(dfe_ctx *ctx, const char *fn, const float *I0, const float *I1
         o.fy = flow; o.fx = flow + (size_t)H * W;
         o.unique = scores; o.min_unique = min_unique;
         o.pitch = W; o.pad_t = pad_t; o.pad_l = pad_l;
-        rc = sgpk_run(ctx, vol, Ho, Wo, hWin, wWin, P1, P2, paths, subpixel, work, o);
+        SgmPen pen{};
+        const SgmPen *use = nullptr;
+        if (gd) {   // (the float frame 0, converted above for the byte entry)
+            const SgmGuide g = sgm_frame_guide(I0, false, 1.f, C, H, W, pad_t, pad_l, gd->sigma, gd->P2_edge);
+            rc = sgm_guide_planes(ctx, &g, Ho, Wo, P2, paths, planes, &pen, &use);
+            if (rc) return rc;
+        }
+        rc = sgpk_run(ctx, vol, Ho, Wo, hWin, wWin, P1, P2, paths, subpixel, work, o, use);
         if (rc) return rc;
     }
     DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
@@ -148,21 +178,25 @@ int sgpk_ssd_pair(dfe_ctx *ctx, const char *fn, const float *I0, const float *I1
 // sgmp_run) or the pick (sgpk_run).  Everything is refused before any launch: the census checks, then the aggregation's, then the pick's
 int sgm_census_pair(dfe_ctx *ctx, const char *fn, bool pick, const void *I0, const void *I1, bool bytes, int C, int H, int W, int k, int hWin, int wWin, int agg,
                     float foe_x, float foe_y, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *match, float *unique,
-                    float *depth, float *depth_conf) {
+                    float *depth, float *depth_conf, const SgmGuide *gd = nullptr) {
     DfeCensusPair g;
     int rc = dfe_census_pair_check(ctx, fn, I0 && I1 && flow && match, (depth == nullptr) == (depth_conf == nullptr), C, H, W, k, hWin, wWin, agg, &g);
     if (rc) return rc;
     if (pick) DFE_REQUIRE(ctx, paths != 0u, DFE_E_ARG, "%s: paths=0x%x must be 1 .. 255 (bit r = direction r)", fn, paths);
     rc = pick ? sgpk_check(ctx, fn, g.Ha, g.Wa, hWin, wWin, P1, P2, paths, min_unique) : sgmp_check(ctx, fn, g.Ha, g.Wa, hWin, wWin, P1, P2, paths);
+    if (!rc && gd) rc = sgm_guide_check(ctx, fn, P1, P2, *gd);
     if (rc) return rc;
     uint64_t *sig0 = nullptr, *sig1 = nullptr;
-    float *vol = nullptr, *work = nullptr;
+    float *vol = nullptr, *work = nullptr, *planes = nullptr;
+    SgmGuide fg{};                               // the guide of a guided entry: frame 0 on the region (scale: gd's)
+    if (gd) fg = sgm_frame_guide(I0, bytes, gd->scale, C, H, W, g.pad_t, g.pad_l, gd->sigma, gd->P2_edge);
     const size_t n = (size_t)C * g.Hp * g.Wp, plane = (size_t)g.Ha * g.Wa * hWin * wWin;
     rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
         sig0 = c.take<uint64_t>(n);
         sig1 = c.take<uint64_t>(n);
         vol = c.take<float>(plane);
         work = c.take<float>(dfe_sgm_work_planes(paths, false) * plane);
+        if (gd && sgm_guided(fg)) planes = c.take<float>(sgm_penalty_floats(paths, g.Ha, g.Wa));
     });
     if (rc) return rc;
     rc = dfe_census_pair_transforms(ctx, I0, I1, bytes, C, H, W, k, sig0, sig1);
@@ -178,11 +212,45 @@ int sgm_census_pair(dfe_ctx *ctx, const char *fn, bool pick, const void *I0, con
         o.den = (float)((k * k - 1) * C * agg * agg);
         o.unique = unique; o.min_unique = min_unique;
         o.pitch = W; o.pad_t = g.pad_t; o.pad_l = g.pad_l;
-        rc = pick ? sgpk_run(ctx, vol, g.Ha, g.Wa, hWin, wWin, P1, P2, paths, subpixel, work, o) : sgmp_run(ctx, vol, g.Ha, g.Wa, hWin, wWin, P1, P2, paths, work, o);
+        SgmPen pen{};
+        const SgmPen *use = nullptr;
+        rc = sgm_guide_planes(ctx, gd ? &fg : nullptr, g.Ha, g.Wa, P2, paths, planes, &pen, &use);
+        if (rc) return rc;
+        rc = pick ? sgpk_run(ctx, vol, g.Ha, g.Wa, hWin, wWin, P1, P2, paths, subpixel, work, o, use)
+                  : sgmp_run(ctx, vol, g.Ha, g.Wa, hWin, wWin, P1, P2, paths, work, o, use);
         if (rc) return rc;
     }
     DfeStageScope ex(ctx, DFE_STAGE_EXTRACT);
     return dfe_pair_border_depth(ctx, flow, match, H, W, g.pad_t, g.pad_l, g.Ha, g.Wa, foe_x, foe_y, depth, depth_conf);
+}
+
+// the two pick entries behind DFE_ENTER (g: NULL for the unguided one; paths == 0 aggregates nothing and ignores the guide)
+int sgpk_entry(dfe_ctx *ctx, const char *fn, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, int subpixel,
+               float min_unique, float *agg, int64_t *idx, float *flow_y, float *flow_x, float *best, float *second, float *unique, const SgmGuide *g) {
+    DFE_REQUIRE(ctx, volume && (agg || idx || flow_y || flow_x || best || second || unique), DFE_E_ARG, "%s: %s", fn,
+                volume ? "every output is NULL" : "volume is NULL");
+    DFE_REQUIRE(ctx, agg != volume, DFE_E_ARG, "%s: agg must not be the volume (every direction reads it)", fn);
+    int rc = sgpk_check(ctx, fn, H, W, hWin, wWin, P1, P2, paths, min_unique);
+    if (!rc && g) rc = sgm_guide_check(ctx, fn, P1, P2, *g);
+    if (rc) return rc;
+    const bool guided = g && paths && sgm_guided(*g);
+    float *work = nullptr, *planes = nullptr;
+    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) {
+        work = c.take<float>(dfe_sgm_work_planes(paths, agg != nullptr) * H * W * (size_t)(hWin * wWin));
+        if (guided) planes = c.take<float>(sgm_penalty_floats(paths, H, W));
+    });
+    if (rc) return rc;
+    SgmpOut o{};
+    o.agg = agg;
+    o.idx = (long long *)idx; o.fy = flow_y; o.fx = flow_x;
+    o.best = best; o.second = second; o.unique = unique; o.min_unique = min_unique;
+    o.pitch = W;
+    DfeStageScope st(ctx, DFE_STAGE_MATCH);
+    SgmPen pen{};
+    const SgmPen *use = nullptr;
+    rc = sgm_guide_planes(ctx, g, H, W, P2, paths, planes, &pen, &use);
+    if (rc) return rc;
+    return sgpk_run(ctx, volume, H, W, hWin, wWin, P1, P2, paths, subpixel, work, o, use);
 }
 
 }  // namespace
@@ -192,22 +260,17 @@ extern "C" {
 int dfe_sgm_plane_pick_f32(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, int subpixel,
                            float min_unique, float *agg, int64_t *idx, float *flow_y, float *flow_x, float *best, float *second, float *unique) {
     DFE_ENTER(ctx);
-    const char *fn = "dfe_sgm_plane_pick_f32";
-    DFE_REQUIRE(ctx, volume && (agg || idx || flow_y || flow_x || best || second || unique), DFE_E_ARG, "%s: %s", fn,
-                volume ? "every output is NULL" : "volume is NULL");
-    DFE_REQUIRE(ctx, agg != volume, DFE_E_ARG, "%s: agg must not be the volume (every direction reads it)", fn);
-    int rc = sgpk_check(ctx, fn, H, W, hWin, wWin, P1, P2, paths, min_unique);
-    if (rc) return rc;
-    float *work = nullptr;
-    rc = dfe_scratch_carve(ctx, [&](DfeCarve &c) { work = c.take<float>(dfe_sgm_work_planes(paths, agg != nullptr) * H * W * (size_t)(hWin * wWin)); });
-    if (rc) return rc;
-    SgmpOut o{};
-    o.agg = agg;
-    o.idx = (long long *)idx; o.fy = flow_y; o.fx = flow_x;
-    o.best = best; o.second = second; o.unique = unique; o.min_unique = min_unique;
-    o.pitch = W;
-    DfeStageScope st(ctx, DFE_STAGE_MATCH);
-    return sgpk_run(ctx, volume, H, W, hWin, wWin, P1, P2, paths, subpixel, work, o);
+    return sgpk_entry(ctx, "dfe_sgm_plane_pick_f32", volume, H, W, hWin, wWin, P1, P2, paths, subpixel, min_unique, agg, idx, flow_y, flow_x, best, second,
+                      unique, nullptr);
+}
+
+int dfe_sgm_plane_pick_guided_f32(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, int subpixel,
+                                  float min_unique, float *agg, int64_t *idx, float *flow_y, float *flow_x, float *best, float *second, float *unique,
+                                  const float *guide, int Cg, float sigma, float P2_edge) {
+    DFE_ENTER(ctx);
+    const SgmGuide g{guide, false, 1.f, Cg, (size_t)H * W, W, sigma, P2_edge};
+    return sgpk_entry(ctx, "dfe_sgm_plane_pick_guided_f32", volume, H, W, hWin, wWin, P1, P2, paths, subpixel, min_unique, agg, idx, flow_y, flow_x, best,
+                      second, unique, &g);
 }
 
 int dfe_flow_depth_pair_sgm_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x, float foe_y,
@@ -260,6 +323,46 @@ int dfe_census_flow_depth_pair_sgm2_u8(dfe_ctx *ctx, const uint8_t *I0, const ui
     DFE_REQUIRE(ctx, scale > 0, DFE_E_ARG, "dfe_census_flow_depth_pair_sgm2_u8: scale=%g must be positive", (double)scale);
     return sgm_census_pair(ctx, "dfe_census_flow_depth_pair_sgm2_u8", true, I0, I1, true, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, P1, P2, paths, subpixel,
                            min_unique, flow, match, unique, depth, depth_conf);
+}
+
+int dfe_flow_depth_pair_sgm_guided_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x, float foe_y,
+                                       float P1, float P2, unsigned paths, int subpixel, float min_unique, float sigma, float P2_edge, float *flow,
+                                       float *scores, float *depth, float *depth_conf) {
+    DFE_ENTER(ctx);
+    const SgmGuide gd{nullptr, false, 1.f, C, 0, 0, sigma, P2_edge};
+    return sgpk_ssd_pair(ctx, "dfe_flow_depth_pair_sgm_guided_f32", I0, I1, nullptr, nullptr, 1.f, C, H, W, k, hWin, wWin, foe_x, foe_y, P1, P2, paths, subpixel,
+                         min_unique, flow, scores, depth, depth_conf, &gd);
+}
+
+int dfe_flow_depth_pair_sgm_guided_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x,
+                                      float foe_y, float scale, float P1, float P2, unsigned paths, int subpixel, float min_unique, float sigma,
+                                      float P2_edge, float *flow, float *scores, float *depth, float *depth_conf) {
+    DFE_ENTER(ctx);
+    const char *fn = "dfe_flow_depth_pair_sgm_guided_u8";
+    DFE_REQUIRE(ctx, I0 && I1, DFE_E_ARG, "%s: NULL frame", fn);
+    DFE_REQUIRE(ctx, C > 0 && H > 0 && W > 0 && scale > 0, DFE_E_ARG, "%s: C=%d %dx%d scale=%g", fn, C, H, W, (double)scale);
+    const SgmGuide gd{nullptr, false, 1.f, C, 0, 0, sigma, P2_edge};
+    return sgpk_ssd_pair(ctx, fn, nullptr, nullptr, I0, I1, scale, C, H, W, k, hWin, wWin, foe_x, foe_y, P1, P2, paths, subpixel, min_unique, flow, scores, depth,
+                         depth_conf, &gd);
+}
+
+int dfe_census_flow_depth_pair_sgm_guided_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, int agg,
+                                              float foe_x, float foe_y, float P1, float P2, unsigned paths, int subpixel, float min_unique, float sigma,
+                                              float P2_edge, float *flow, float *match, float *unique, float *depth, float *depth_conf) {
+    DFE_ENTER(ctx);
+    const SgmGuide gd{nullptr, false, 1.f, C, 0, 0, sigma, P2_edge};
+    return sgm_census_pair(ctx, "dfe_census_flow_depth_pair_sgm_guided_f32", true, I0, I1, false, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, P1, P2, paths,
+                           subpixel, min_unique, flow, match, unique, depth, depth_conf, &gd);
+}
+
+int dfe_census_flow_depth_pair_sgm_guided_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, int agg,
+                                             float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths, int subpixel, float min_unique,
+                                             float sigma, float P2_edge, float *flow, float *match, float *unique, float *depth, float *depth_conf) {
+    DFE_ENTER(ctx);
+    DFE_REQUIRE(ctx, scale > 0, DFE_E_ARG, "dfe_census_flow_depth_pair_sgm_guided_u8: scale=%g must be positive", (double)scale);
+    const SgmGuide gd{nullptr, true, scale, C, 0, 0, sigma, P2_edge};
+    return sgm_census_pair(ctx, "dfe_census_flow_depth_pair_sgm_guided_u8", true, I0, I1, true, C, H, W, k, hWin, wWin, agg, foe_x, foe_y, P1, P2, paths,
+                           subpixel, min_unique, flow, match, unique, depth, depth_conf, &gd);
 }
 
 }  // extern "C"

@@ -12,6 +12,8 @@
 //       double-buffered LDS plane of (hWin + 2) x (wWin + 2) floats with a +Inf frame, from which the four neighbour reads need no edge
 //       test; one barrier a step.  m = a register min over j and one wave reduction.  C(p, .) is loaded along the class axis, the loads
 //       of the next AHEAD steps in flight (a line's addresses are wave-uniform integers, known from its first step).
+//   guided_sgmp_path_kernel<J, AHEAD>   the same body with the step's P2 taken from the direction's penalty plane (sgm_penalty.hip;
+//       DESIGN.md section 4.38): a wave-uniform value, fetched a chunk of up to 64 steps at a time into LDS behind the two planes.
 //   sgmp_sum_kernel<FLOW>   a wave a pixel: agg = ((L_a + L_b) + L_c) + ... in ascending direction order, stored only if somebody
 //       reads it; the first minimum in class order by a wave reduction on (value, class), the centre class winning an exact tie; the
 //       decoded flow and, for the census one call, the match score of the RAW cost at the chosen class, at the pasted positions.  Its
@@ -34,10 +36,16 @@ __device__ __forceinline__ float sgmp_wave_min(float v) {
     return fminf(fminf(r0, r1), fminf(r2, r3));
 }
 
-template <int J, int AHEAD>
-__global__ __launch_bounds__(64) void sgmp_path_kernel(const SgmpJob a) {
+extern __shared__ float sgmp_lds[];              // two planes of (hWin + 2) x (wWin + 2): L_r(q, .) inside a +Inf frame
+
+// the body of the two path kernels.  GUIDED: the step's P2 is a cell of the direction's penalty plane (sgm_penalty.hip), a wave-uniform
+// value.  The wave fetches the penalties of 64 steps at once, lane i that of step s + i (a line's pixels have a closed form), into 64
+// floats of LDS behind the two planes, and a step reads its own from there with its neighbour cells: no register is held across
+// steps, where a slot per step of the look-ahead, in VGPRs or SGPRs, cost the 5- and 9-cell forms an occupancy class; a step's
+// dependent chain keeps its length
+template <int J, int AHEAD, bool GUIDED>
+__device__ __forceinline__ void sgmp_path_body(const SgmpJob &a, const SgmPen *pen) {
 #pragma clang fp contract(off)
-    extern __shared__ float sgmp_lds[];          // two planes of (hWin + 2) x (wWin + 2): L_r(q, .) inside a +Inf frame
     const float inf = __builtin_inff();
     const int k = blockIdx.y;                    // which of the directions
     const int dy = a.dy[k], dx = a.dx[k];
@@ -68,6 +76,24 @@ __global__ __launch_bounds__(64) void sgmp_path_kernel(const SgmpJob a) {
     float cb[AHEAD][J];
     int pixb[AHEAD];
     bool stb[AHEAD];
+    constexpr int kChunk = 64 / AHEAD * AHEAD;   // steps a fetch of penalties serves: whole groups of the look-ahead
+    float *pen_lds = sgmp_lds + 2 * plane;       // P2 of step cbase + i at [i], for the chunk of the line that is being walked
+    int cbase = -kChunk;
+    auto pen_fetch = [&](int first) {            // the penalties of the steps first + lane (past the line: the last step's again)
+        int st = first + lane;
+        st = st < nsteps ? st : nsteps - 1;
+        if (pen->atq[k]) st = st > 0 ? st - 1 : 0;   // the plane's cell is the predecessor's: the pixel of the step before (step 0 starts)
+        int y, x;
+        if (horizontal) {
+            y = line;
+            x = dx > 0 ? st : a.W - 1 - st;
+        } else {                                 // SgmCursor's walk: down or up from x = line, through the sides modulo W
+            y = dy > 0 ? st : a.H - 1 - st;
+            x = (line + st * dx) % a.W;
+            x = x < 0 ? x + a.W : x;
+        }
+        return pen->plane[k][(size_t)y * a.W + x];
+    };
     auto fetch = [&](int slot) {
         const int pix = f.y * a.W + f.x;
         const float *__restrict__ src = a.C + (size_t)pix * a.cells;
@@ -88,6 +114,13 @@ __global__ __launch_bounds__(64) void sgmp_path_kernel(const SgmpJob a) {
     for (int j = 0; j < J; ++j) l[j] = inf;
     int cur = 0;                                 // the LDS plane that holds L_r(q, .)
     for (int s = 0; s < nsteps; s += AHEAD) {
+        if constexpr (GUIDED) {
+            if (s - cbase == kChunk) {           // a chunk begins (the last step's barrier is behind the reads of the chunk before)
+                cbase = s;
+                pen_lds[lane] = pen_fetch(s);
+                __syncthreads();
+            }
+        }
 #pragma unroll
         for (int u = 0; u < AHEAD; ++u) {
             if (s + u >= nsteps) break;          // (wave-uniform, as every branch of this loop)
@@ -96,6 +129,8 @@ __global__ __launch_bounds__(64) void sgmp_path_kernel(const SgmpJob a) {
             for (int j = 0; j < J; ++j) c[j] = in[j] ? cb[u][j] : inf;
             const int pix = pixb[u];
             const bool start = stb[u];
+            float P2 = a.P2;
+            if constexpr (GUIDED) P2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(pen_lds[s + u - cbase])));   // (uniform: into an SGPR, as a.P2 is)
             if (fs < nsteps) fetch(u);
             if (start) {
 #pragma unroll
@@ -106,7 +141,7 @@ __global__ __launch_bounds__(64) void sgmp_path_kernel(const SgmpJob a) {
 #pragma unroll
                 for (int j = 1; j < J; ++j) m = fminf(m, l[j]);
                 m = sgmp_wave_min(m);
-                const float far = m + a.P2;
+                const float far = m + P2;
                 const float *q = sgmp_lds + cur * plane;
 #pragma unroll
                 for (int j = 0; j < J; ++j) {
@@ -132,6 +167,15 @@ __global__ __launch_bounds__(64) void sgmp_path_kernel(const SgmpJob a) {
             __syncthreads();                     // one wave: orders its LDS stores before the next step's neighbour reads
         }
     }
+}
+
+template <int J, int AHEAD>
+__global__ __launch_bounds__(64) void sgmp_path_kernel(const SgmpJob a) {
+    sgmp_path_body<J, AHEAD, false>(a, nullptr);
+}
+template <int J, int AHEAD>
+__global__ __launch_bounds__(64) void guided_sgmp_path_kernel(const SgmpJob a, const SgmPen pen) {
+    sgmp_path_body<J, AHEAD, true>(a, &pen);
 }
 
 // agg = the n planes summed in order; its first minimum with the centre rule.  A wave a pixel, four pixels a block
@@ -182,17 +226,23 @@ SgmpJob sgmp_job(const float *volume, int H, int W, int hWin, int wWin, float P1
     return a;
 }
 
-int sgmp_launch_paths(dfe_ctx *ctx, const SgmpJob &a) {
+int sgmp_launch_paths(dfe_ctx *ctx, const SgmpJob &a, const SgmPen *pen) {
     DfeProfScope prof(ctx);
     const dim3 grid((unsigned)(a.H > a.W ? a.H : a.W), (unsigned)a.n);
-    const size_t lds = (size_t)2 * (a.hWin + 2) * (a.wWin + 2) * sizeof(float);   // 26352 bytes at the most (1 x 1096)
+    const size_t lds = (size_t)2 * (a.hWin + 2) * (a.wWin + 2) * sizeof(float) + (pen ? 64 * sizeof(float) : 0);   // 26352 bytes at the most (1 x 1096), and a chunk of penalties
     const int J = dfe_cdiv(a.cells, 64);
-#define DFE_SGMP_PATH(JJ, AA) hipLaunchKernelGGL((sgmp_path_kernel<JJ, AA>), grid, dim3(64), lds, ctx->stream, a)
-    if (J <= 1) DFE_SGMP_PATH(1, 8);
-    else if (J <= 2) DFE_SGMP_PATH(2, 8);
-    else if (J <= 5) DFE_SGMP_PATH(5, 4);
-    else if (J <= 9) DFE_SGMP_PATH(9, 4);
-    else DFE_SGMP_PATH(kSgmpMaxJ, 2);
+    // (GA: the guided form's look-ahead -- one step less at 9 cells a lane, which came out three registers above the 96 of its twin's
+    //  five waves a SIMD at four)
+#define DFE_SGMP_PATH(JJ, AA, GA)                                                                                \
+    do {                                                                                                         \
+        if (pen) hipLaunchKernelGGL((guided_sgmp_path_kernel<JJ, GA>), grid, dim3(64), lds, ctx->stream, a, *pen); \
+        else hipLaunchKernelGGL((sgmp_path_kernel<JJ, AA>), grid, dim3(64), lds, ctx->stream, a);                  \
+    } while (0)
+    if (J <= 1) DFE_SGMP_PATH(1, 8, 8);
+    else if (J <= 2) DFE_SGMP_PATH(2, 8, 8);
+    else if (J <= 5) DFE_SGMP_PATH(5, 4, 4);
+    else if (J <= 9) DFE_SGMP_PATH(9, 4, 3);
+    else DFE_SGMP_PATH(kSgmpMaxJ, 2, 2);
 #undef DFE_SGMP_PATH
     DFE_LAUNCH_CHECK(ctx);
     ctx->last_kernel = "sgmp_path_kernel";
@@ -200,10 +250,11 @@ int sgmp_launch_paths(dfe_ctx *ctx, const SgmpJob &a) {
 }
 
 // The two launches behind the checks.  work: dfe_sgm_work_planes(paths, o.agg != NULL) planes; o: where the results go
-int sgmp_run(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, float *work, SgmpOut o) {
+int sgmp_run(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, float *work, SgmpOut o,
+             const SgmPen *pen) {
     const SgmpJob a = sgmp_job(volume, H, W, hWin, wWin, P1, P2, paths, work, o.agg);
     DfeProfScope prof(ctx);
-    int rc = sgmp_launch_paths(ctx, a);
+    int rc = sgmp_launch_paths(ctx, a, pen);
     if (rc) return rc;
     const bool flow = o.idx || o.fy || o.fx || o.match;
     if (o.agg || flow) {

@@ -70,6 +70,12 @@ int dfe_flow_depth_pair_sgm_f32(dfe_ctx *ctx, const float *I0, const float *I1, 
 int dfe_flow_depth_pair_sgm_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *scores, float *depth, float *depth_conf);
 int dfe_census_flow_depth_pair_sgm2_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *match, float *unique, float *depth, float *depth_conf);
 int dfe_census_flow_depth_pair_sgm2_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *flow, float *match, float *unique, float *depth, float *depth_conf);
+int dfe_sgm_aggregate_guided_f32(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring, float *agg, float *flow, const float *guide, int Cg, float sigma, float P2_edge);
+int dfe_sgm_plane_pick_guided_f32(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2, unsigned paths, int subpixel, float min_unique, float *agg, int64_t *idx, float *flow_y, float *flow_x, float *best, float *second, float *unique, const float *guide, int Cg, float sigma, float P2_edge);
+int dfe_flow_depth_pair_sgm_guided_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x, float foe_y, float P1, float P2, unsigned paths, int subpixel, float min_unique, float sigma, float P2_edge, float *flow, float *scores, float *depth, float *depth_conf);
+int dfe_flow_depth_pair_sgm_guided_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths, int subpixel, float min_unique, float sigma, float P2_edge, float *flow, float *scores, float *depth, float *depth_conf);
+int dfe_census_flow_depth_pair_sgm_guided_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float P1, float P2, unsigned paths, int subpixel, float min_unique, float sigma, float P2_edge, float *flow, float *match, float *unique, float *depth, float *depth_conf);
+int dfe_census_flow_depth_pair_sgm_guided_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin, int wWin, int agg, float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths, int subpixel, float min_unique, float sigma, float P2_edge, float *flow, float *match, float *unique, float *depth, float *depth_conf);
 int dfe_census_radial_cost_volume_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1, int C, int Hp, int W, int hWin, int agg, float *out);
 int dfe_census_radial_flow_f32(dfe_ctx *ctx, const uint64_t *sig0, const uint64_t *sig1, int C, int Hp, int W, int nbits, int hWin, int agg, int subpixel, int zero_last_row, float *volume, float *flow, float *best, float *match);
 int dfe_census_radial_flow_depth_pair_f32(dfe_ctx *ctx, const dfe_census_radial_params *p, const float *prev, const float *cur, double e2x, double e2y, float P1, float P2, unsigned paths, int ring, int subpixel, float *volume, float *agg_volume, float *polar_flow, float *match, float *cart_flow, float *depth, float *conf);

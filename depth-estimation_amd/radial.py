@@ -275,25 +275,37 @@ def _sgm_params(P1, P2, paths, ring, W, who):
     return P1, P2
 
 
-def semiGlobalAggregate(volume, P1, P2, paths=0x0f, ring=0, want_volume=True):
+def semiGlobalAggregate(volume, P1, P2, paths=0x0f, ring=0, want_volume=True, guide=None, sigma=0.0, P2_edge=None):
     """Not in the reference: semi-global aggregation of a matcher volume [H][W][D] (D <= 32, float32) along the
     directions whose bits `paths` has set -- 0 (0, +1), 1 (0, -1), 2 (+1, 0), 3 (-1, 0), 4 (+1, +1), 5 (-1, -1), 6 (+1, -1), 7 (-1, +1) as
     (dy, dx) -- with the penalty P1 for a label change of one and P2 for any other; ring = G > 0: the columns are a ring and a horizontal
     path warms up over G columns (include/dfe.h: dfe_sgm_aggregate_f32).  Returns (flow [H][W] = the first minimum of the aggregate as
-    float, aggregate [H][W][D] or None without want_volume: the aggregate then never leaves the library's scratch)."""
+    float, aggregate [H][W][D] or None without want_volume: the aggregate then never leaves the library's scratch).
+    guide (Cg x H x W float32, on the volume's pixel grid), sigma, P2_edge (None: P1): the edge-aware penalty of DESIGN.md section 4.38
+    (dfe_sgm_aggregate_guided_f32) -- between pixels whose guide values differ the P2 of a step falls from P2 to P2_edge by
+    max(0, 1 - d^2 / sigma^2); on a ring the pair (x = 0, x = W - 1) has its own penalty.  sigma needs a guide; with none of the three
+    named the call is the unguided one, launch for launch."""
+    from .sgm_plane import _guide_arg
+
     if volume.dim() != 3 or min(volume.shape) < 1:
         raise ValueError("semiGlobalAggregate: volume H x W x D expected, got %s" % (tuple(volume.shape),))
     H, W, D = volume.shape
     if D > 32:
         raise ValueError("semiGlobalAggregate: D=%d labels (32 at most)" % D)
     P1, P2 = _sgm_params(P1, P2, paths, ring, W, "semiGlobalAggregate")
+    edge = _guide_arg(guide, sigma, P2_edge, P1, P2, H, W, volume, "semiGlobalAggregate")
     if not volume.is_cuda or volume.dtype != torch.float32:
         raise TypeError("semiGlobalAggregate: a float32 CUDA tensor expected")
     volume = volume.contiguous()
     ctx = get_ctx(volume)
     flow = torch.empty((H, W), dtype=torch.float32, device=volume.device)
     agg = torch.empty_like(volume) if want_volume else None
-    ctx.check(lib().dfe_sgm_aggregate_f32(ctx.handle, ptr(volume), H, W, D, P1, P2, paths, ring, ptr(agg) if want_volume else None, ptr(flow)))
+    args = (ctx.handle, ptr(volume), H, W, D, P1, P2, paths, ring, ptr(agg) if want_volume else None, ptr(flow))
+    if edge is None:
+        ctx.check(lib().dfe_sgm_aggregate_f32(*args))
+    else:
+        g, Cg, sg, pe = edge
+        ctx.check(lib().dfe_sgm_aggregate_guided_f32(*args, None if g is None else ptr(g), Cg, sg, pe))
     return flow, agg
 
 

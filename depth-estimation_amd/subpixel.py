@@ -97,7 +97,9 @@ def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False
     sgm: None, (P1, P2) or dict(P1=, P2=, paths=0x0f, min_unique=0.0) -- the whole SSD volume goes through
     semiGlobalPick before the arg-min (dfe_flow_depth_pair_sgm_f32 / _u8).  scores is then the uniqueness of the aggregate, (second - best) /
     second gated by min_unique, and threshold is ignored; subpixel=True refines on the aggregate, not on the raw costs.  fill and median work
-    unchanged, through scores > 0.  consistency= together with sgm= raises ValueError.  None leaves every bit and every launch as it is."""
+    unchanged, through scores > 0.  consistency= together with sgm= raises ValueError.  None leaves every bit and every launch as it is.
+    sigma= or P2_edge= (None: P1) in the sgm dict: dfe_flow_depth_pair_sgm_guided_f32 / _u8 -- img1 on the output
+    region guides P2, which falls to P2_edge across its edges; sigma is in the frame's own units (bytes times scale for uint8 frames)."""
     median = _median_arg(median)
     sgm = _sgm_pick_arg(sgm, "flowDepthPair")
     if sgm is not None and consistency is not None:
@@ -112,12 +114,13 @@ def flowDepthPair(img1, img2, k, hWin, wWin, foe, threshold=0.21, subpixel=False
     fx, fy = float(foe[0]), float(foe[1])
     l = lib()
     if sgm is not None:
-        P1, P2, paths, min_unique, _ = sgm
-        tail = (P1, P2, paths, int(bool(subpixel)), min_unique, ptr(flow), ptr(scores), ptr(depth), ptr(conf))
+        P1, P2, paths, min_unique, _, edge = sgm
+        name = "dfe_flow_depth_pair_sgm_" + ("" if edge is None else "guided_")     # (sigma, P2_edge behind min_unique: frame 0 guides)
+        tail = (P1, P2, paths, int(bool(subpixel)), min_unique) + (edge or ()) + (ptr(flow), ptr(scores), ptr(depth), ptr(conf))
         if a.dtype == torch.uint8:
-            rc = l.dfe_flow_depth_pair_sgm_u8(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, float(scale), *tail)
+            rc = getattr(l, name + "u8")(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, float(scale), *tail)
         else:
-            rc = l.dfe_flow_depth_pair_sgm_f32(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, *tail)
+            rc = getattr(l, name + "f32")(ctx.handle, ptr(a), ptr(b), C, H, W, k, hWin, wWin, fx, fy, *tail)
         ctx.check(rc)
         return _with_fill({"flow": flow, "scores": scores, "depth": depth, "depth_conf": conf}, fill, median, a, k, hWin, wWin, fx, fy)
     if consistency is not None:

@@ -450,6 +450,53 @@ int dfe_census_flow_depth_pair_sgm2_u8(dfe_ctx *ctx, const uint8_t *I0, const ui
                                        int subpixel, float min_unique, float *flow, float *match, float *unique, float *depth,
                                        float *depth_conf);
 
+/* ---- edge-aware semi-global aggregation: P2 adapted to a guide image, for both label families (NOT in the reference; DESIGN section
+ * 4.38) ------------------------------------------------------------------------------------------------------------------------------- */
+/* Everything is as dfe_sgm_aggregate_f32 / dfe_sgm_plane_aggregate_f32 / dfe_sgm_plane_pick_f32 define it, except the term m + P2 of a
+ * step: for a pixel p whose predecessor on direction r is q = p - r it is m + P2(p, r).  guide [Cg][H][W], float32, Cg >= 1, on the
+ * volume's own pixel grid; on a ring q's column is taken modulo W, so the pair (x = 0, x = W - 1) has a penalty of its own.
+ *   Host:    inv_s2 = 1.0f / (sigma * sigma);  span = P2 - P2_edge;  both in float.
+ *   Device:  fp32, rounded on its own, not contracted:
+ *            d2 = sum over c of (g_c(p) - g_c(q))^2, in channel order, starting from the first square;
+ *            w = max(0, 1 - d2 * inv_s2); a w that is not finite counts as 0.
+ *   Penalty: P2(p, r) = P2_edge + span * w; where w == 1 exactly P2(p, r) = P2 with no arithmetic, so a flat guide gives the unguided
+ *            bits.  This is the range term of dfe_weighted_median_f32 and dfe_guided_upsample_f32 applied to P2.
+ *   Unguided: guide == NULL, or sigma <= 0 or NaN: P2(p, r) = P2, and the entry returns the bits of the unguided entry with its launches.
+ *   Unchanged: a chain start (L = C) uses no penalty; the P1 terms, the order of the sum, the first minimum, the centre rule, the
+ *            uniqueness and the sub-pixel rules.  (a - b)^2 and (b - a)^2 have the same bits: direction r at p and direction -r at
+ *            p - r use the same number.
+ * Errors: the unguided entry's, and P2_edge finite with P1 <= P2_edge <= P2, Cg >= 1 with a guide (DFE_E_ARG).  Refused before any launch.
+ * One launch more than the unguided entry: a pre-pass writes P2(p, r) for the even direction of each axis the paths lie on into an
+ * [H][W] plane in the ctx's scratch arena (four at the most: the odd direction reads the plane at its predecessor); the path kernels'
+ * guided forms fetch a step's penalty with its costs.  A NaN or Inf guide sample gives P2_edge on the steps that touch it. */
+int dfe_sgm_aggregate_guided_f32(dfe_ctx *ctx, const float *volume, int H, int W, int D, float P1, float P2, unsigned paths, int ring,
+                                 float *agg, float *flow, const float *guide, int Cg, float sigma, float P2_edge);
+/* dfe_sgm_plane_pick_f32 under the guided penalty.  It serves the plain aggregate too (best, second, unique NULL and subpixel 0 give
+ * dfe_sgm_plane_aggregate_f32's outputs); paths == 0 stays the winner-takes-all read, and the guide is ignored there. */
+int dfe_sgm_plane_pick_guided_f32(dfe_ctx *ctx, const float *volume, int H, int W, int hWin, int wWin, float P1, float P2,
+                                  unsigned paths, int subpixel, float min_unique, float *agg, int64_t *idx, float *flow_y, float *flow_x,
+                                  float *best, float *second, float *unique, const float *guide, int Cg, float sigma, float P2_edge);
+/* dfe_flow_depth_pair_sgm_f32 / _u8 and dfe_census_flow_depth_pair_sgm2_f32 / _u8 under the guided penalty: their arguments plus sigma
+ * and P2_edge.  The guide is the call's own frame 0, all C channels, cropped to the pixels the volume's plane is pasted at; for the
+ * byte entries float(byte) * scale, as dfe_u8_to_f32 gives (the census entry compares the bytes as they are, so scale matters to it
+ * only here: sigma is in the units of float(byte) * scale).  Bit-identical to the staged public calls -- the volume, then
+ * dfe_sgm_plane_pick_guided_f32 on that crop -- plus the paste. */
+int dfe_flow_depth_pair_sgm_guided_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin, int wWin,
+                                       float foe_x, float foe_y, float P1, float P2, unsigned paths, int subpixel, float min_unique,
+                                       float sigma, float P2_edge, float *flow, float *scores, float *depth, float *depth_conf);
+int dfe_flow_depth_pair_sgm_guided_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin,
+                                      int wWin, float foe_x, float foe_y, float scale, float P1, float P2, unsigned paths, int subpixel,
+                                      float min_unique, float sigma, float P2_edge, float *flow, float *scores, float *depth,
+                                      float *depth_conf);
+int dfe_census_flow_depth_pair_sgm_guided_f32(dfe_ctx *ctx, const float *I0, const float *I1, int C, int H, int W, int k, int hWin,
+                                              int wWin, int agg, float foe_x, float foe_y, float P1, float P2, unsigned paths,
+                                              int subpixel, float min_unique, float sigma, float P2_edge, float *flow, float *match,
+                                              float *unique, float *depth, float *depth_conf);
+int dfe_census_flow_depth_pair_sgm_guided_u8(dfe_ctx *ctx, const uint8_t *I0, const uint8_t *I1, int C, int H, int W, int k, int hWin,
+                                             int wWin, int agg, float foe_x, float foe_y, float scale, float P1, float P2,
+                                             unsigned paths, int subpixel, float min_unique, float sigma, float P2_edge, float *flow,
+                                             float *match, float *unique, float *depth, float *depth_conf);
+
 /* ---- the census cost for the radial (polar) matcher: an exposure-robust polar flow that needs no trained weights (NOT in the
  * reference, whose radial matcher scores learned features by the sum of squared differences) ---------------- */
 /* Integers only up to the score, so every result below is exact.  With W = wInput, lpad = (kw - 1) / 2 and rpad = kw - 1 - lpad (the
