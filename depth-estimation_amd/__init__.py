@@ -61,6 +61,11 @@ no CPU fallback -- a missing library or device raises.
                                                         output_extraction_method 'max' or 'mean' -- network.py)
     imageScale, DepthEstimationAPI(...).nextFrameDepth  (image.scale; depth_estimation_api.lua:134-198, video -> depth per camera
                                                         frame over the library's stream object -- stream.py)
+    DepthEstimationAPI(..., post=dict(consistency=tol, fill=True | levels, median=k | (k, sigma), temporal=dict(tol=...)))
+                                                        (not in the reference: the forward-backward check, hole filling, the guided median
+                                                        and the temporal filter behind the pair step INSIDE the stream object, the filter's
+                                                        state on the device -- last["flow_post"], weight_post, consistent, depth_post,
+                                                        depth_post_conf, depth_fused, depth_fused_weight, depth_fused_flag -- stream.py)
 """
 from ._lib import lib, DfeError, LIB_PATH  # noqa: F401
 from .context import Context, get_ctx  # noqa: F401

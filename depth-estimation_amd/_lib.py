@@ -242,6 +242,10 @@ PROTOTYPES = {
     "dfe_stream_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "dfe_stream_push_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 5 + [C.POINTER(C.c_double)] * 2 + [c_i32p] * 3),
     "dfe_stream_push_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 5 + [C.POINTER(C.c_double)] * 2 + [c_i32p] * 3),
+    "dfe_stream_post_check": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "dfe_stream_create_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "dfe_stream_push_post_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float] + [C.c_void_p] * 6 + [C.POINTER(C.c_double)] * 2 + [c_i32p] * 3),
+    "dfe_stream_push_post_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 6 + [C.POINTER(C.c_double)] * 2 + [c_i32p] * 3),
     "dfe_stream_reset": (C.c_int, [C.c_void_p]),
     "dfe_stream_destroy": (None, [C.c_void_p]),
 }
@@ -272,6 +276,28 @@ class StreamParams(C.Structure):
                 ("dist", C.c_double * 5), ("layers", C.POINTER(FilterLayer)), ("nlayers", C.c_int), ("maxh", C.c_int), ("maxw", C.c_int), ("extraction", C.c_int),
                 ("threshold", C.c_double), ("rectify", C.c_int), ("fix_mask_offset", C.c_int), ("tracker", TrackerParams), ("ransac_max_dist", C.c_double),
                 ("iterations", C.c_int), ("seed", C.c_uint), ("min_inlier_ratio", C.c_double)]
+
+
+class StreamPost(C.Structure):
+    """dfe_stream_post (include/dfe.h); struct_size is filled in"""
+    _fields_ = [("struct_size", C.c_int), ("consistency_tol", C.c_float), ("fill", C.c_int), ("fill_levels", C.c_int), ("median_k", C.c_int),
+                ("median_sigma", C.c_float), ("temporal", C.c_int), ("t_tol", C.c_float), ("t_wmax", C.c_float), ("t_decay", C.c_float), ("t_has_gain", C.c_int),
+                ("t_gain", C.c_float), ("t_has_bias", C.c_int), ("t_bias", C.c_float), ("t_splat", C.c_int), ("t_ztol", C.c_float), ("t_quant", C.c_float),
+                ("t_min_cover", C.c_float)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(StreamPost)
+
+
+class StreamPostOut(C.Structure):
+    """dfe_stream_post_out (include/dfe.h): device pointers, each may be None; struct_size is filled in"""
+    _fields_ = [("struct_size", C.c_int)] + [(k, C.c_void_p) for k in ("flow_bw", "consistent", "flow_post", "weight_post", "depth_post", "depth_post_conf",
+                                                                       "depth_fused", "fused_weight", "fused_flag")]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = C.sizeof(StreamPostOut)
 
 
 _lib = None

@@ -4,8 +4,10 @@
 // and the previous frame's features (last_filtered) -- in two slots each that swap roles per push, and runs the public entries in the
 // reference's order on them: every result equals the composition of those entries bit for bit.  All device memory is one block made by
 // dfe_stream_create; a push allocates nothing of its own.
+// A stream made by dfe_stream_create_post also carries the post-processing chain of stream_post.hip (consistency, fill, median, temporal
+// fusion), run behind the pair step by dfe_stream_push_post_*.
 // Also here: dfe_mask_paste_mul_f32, the mask2:narrow():copy(mask) + cmul(full_confidences) of :176-182 in one launch.
-#include "dfe_internal.h"
+#include "stream_post.h"
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -71,6 +73,8 @@ struct dfe_stream {
     float *warped_img = nullptr;        // IMAGE: the rectified previous scaled frame
     float *warped = nullptr;            // the rectified previous features
     float *rmask = nullptr, *conf = nullptr, *flow_i = nullptr, *mask_i = nullptr, *spare = nullptr;
+    bool has_post = false;              // made by dfe_stream_create_post
+    DfeStreamPost post;
 };
 
 namespace {
@@ -91,8 +95,10 @@ int stream_filter(dfe_stream *s, const float *in, float *dst) {
     return DFE_OK;
 }
 
+// post_call: one of dfe_stream_push_post_* (the stream has the chain); po: its outputs, may be NULL
 int stream_push(dfe_stream *s, const float *frame, const uint8_t *frame8, float scale, float imu_tx, float *im_scaled, float *flow, float *mask, float *depth,
-                float *depth_conf, double *R9, double *T3, int *n_found, int *n_inliers, int *status) {
+                float *depth_conf, double *R9, double *T3, int *n_found, int *n_inliers, int *status, bool post_call = false,
+                const dfe_stream_post_out *po = nullptr) {
     dfe_ctx *ctx = s->ctx;
     const dfe_stream_params &p = s->p;
     const StreamShapes &sh = s->sh;
@@ -124,6 +130,7 @@ int stream_push(dfe_stream *s, const float *frame, const uint8_t *frame8, float 
     if (!s->primed) {
         s->primed = true;
         s->cur = pv;
+        s->post.thave = false;
         if (n_found) *n_found = 0;
         if (n_inliers) *n_inliers = 0;
         if (status) *status = 0;
@@ -146,6 +153,10 @@ int stream_push(dfe_stream *s, const float *frame, const uint8_t *frame8, float 
         if (mask) DFE_HIP(ctx, hipMemsetAsync(mask, 0, nimg * 4, ctx->stream));
         if (depth) DFE_HIP(ctx, hipMemsetAsync(depth, 0, nimg * 4, ctx->stream));
         if (depth_conf) DFE_HIP(ctx, hipMemsetAsync(depth_conf, 0, nimg * 4, ctx->stream));
+        if (post_call) {
+            rc = dfe_stream_post_zero(ctx, s->post, po);
+            if (rc) return rc;
+        }
     } else {
         // the rotation taken out of the previous frame (:147; test_opticalflow.lua:284 warps the image and filters it)
         if (p.rectify == 0) {
@@ -167,7 +178,7 @@ int stream_push(dfe_stream *s, const float *frame, const uint8_t *frame8, float 
             rc = dfe_flow_pair_filtered_f32(ctx, prevf, s->feat[c], sh.K, sh.Hf, sh.Wf, nullptr, 0, p.maxh, p.maxw, p.extraction == 1, p.threshold, p.hImg, p.wImg,
                                             flow_o, s->conf, nullptr, nullptr);
         if (rc) return rc;
-        if (mask || want_depth) {
+        if (mask || want_depth || post_call) {
             rc = dfe_enlarge_mask_f32(ctx, s->rmask, s->Hm, s->Wm, sh.ix, sh.iy);                  // (:172-174)
             if (rc) return rc;
             rc = dfe_mask_paste_mul_f32(ctx, s->rmask, s->Hm, s->Wm, s->conf, p.hImg, p.wImg, sh.oy, sh.ox, mask_o);   // (:176-182)
@@ -179,9 +190,18 @@ int stream_push(dfe_stream *s, const float *frame, const uint8_t *frame8, float 
             rc = dfe_flow_to_depth_ardrone(ctx, flow_o + nimg, mask_o, p.hImg, p.wImg, imu_tx, d, dc);
             if (rc) return rc;
         }
+        if (post_call) {
+            const DfeStreamPostIn in{flow_o, mask_o, prevf, s->feat[c], s->scaled[pv], p.rectify == 1 ? s->warped_img : nullptr, sh.K, sh.Hf, sh.Wf, p.maxh, p.maxw,
+                                     p.extraction, p.threshold, s->Ksmall, R, imu_tx};
+            rc = dfe_stream_post_run(ctx, s->post, in, po);
+            if (rc) return rc;
+        }
     }
     // last_im = im; last_im_scaled = im_scaled; last_filtered = filtered (:187-189): the slots swap roles
     s->cur = pv;
+    // the temporal state: advanced by the chain, forgotten behind a bad image and behind a plain push (nothing to carry it with)
+    if (post_call && !bad && s->post.o.temporal) { s->post.tcur = 1 - s->post.tcur; s->post.thave = true; }
+    else s->post.thave = false;
     if (pose) {
         if (R9) memcpy(R9, R, sizeof(R));
         if (T3) memcpy(T3, T, sizeof(T));
@@ -222,20 +242,25 @@ int dfe_stream_shapes(const dfe_stream_params *p, int *Hf, int *Wf, int *H1, int
     return DFE_OK;
 }
 
-int dfe_stream_create(dfe_ctx *ctx, const dfe_stream_params *p, dfe_stream **out) {
-    DFE_ENTER(ctx);
-    DFE_REQUIRE(ctx, out, DFE_E_ARG, "dfe_stream_create: out is NULL");
+}  // extern "C"
+
+namespace {
+
+// dfe_stream_create (post == NULL) and dfe_stream_create_post behind their device guard
+int stream_create(dfe_ctx *ctx, const char *fn, const dfe_stream_params *p, const dfe_stream_post *post, dfe_stream **out) {
+    DFE_REQUIRE(ctx, out, DFE_E_ARG, "%s: out is NULL", fn);
     *out = nullptr;
     StreamShapes sh;
-    int rc = stream_shapes(ctx, "dfe_stream_create", p, &sh);
+    int rc = stream_shapes(ctx, fn, p, &sh);
     if (rc) return rc;
-    DFE_REQUIRE(ctx, (long long)p->Hsrc * p->Wsrc < (1ll << 31), DFE_E_SHAPE, "dfe_stream_create: frame %dx%d", p->Hsrc, p->Wsrc);
+    if (post && (rc = dfe_stream_post_validate(ctx, fn, post))) return rc;
+    DFE_REQUIRE(ctx, (long long)p->Hsrc * p->Wsrc < (1ll << 31), DFE_E_SHAPE, "%s: frame %dx%d", fn, p->Hsrc, p->Wsrc);
     double Ki[9];
-    DFE_REQUIRE(ctx, dfe_mat3_inv(p->K, Ki), DFE_E_ARG, "dfe_stream_create: K is singular");
-    DFE_REQUIRE(ctx, p->iterations >= 1 && p->iterations <= 65536 && p->ransac_max_dist > 0, DFE_E_ARG, "dfe_stream_create: iterations=%d (1..65536) ransac_max_dist=%g",
+    DFE_REQUIRE(ctx, dfe_mat3_inv(p->K, Ki), DFE_E_ARG, "%s: K is singular", fn);
+    DFE_REQUIRE(ctx, p->iterations >= 1 && p->iterations <= 65536 && p->ransac_max_dist > 0, DFE_E_ARG, "%s: iterations=%d (1..65536) ransac_max_dist=%g", fn,
                 p->iterations, p->ransac_max_dist);
     dfe_stream *s = new (std::nothrow) dfe_stream;
-    DFE_REQUIRE(ctx, s, DFE_E_ALLOC, "dfe_stream_create: out of host memory");
+    DFE_REQUIRE(ctx, s, DFE_E_ALLOC, "%s: out of host memory", fn);
     s->ctx = ctx;
     s->p = *p;
     if (p->nlayers) memcpy(s->layers, p->layers, (size_t)p->nlayers * sizeof(dfe_filter_layer));
@@ -261,13 +286,67 @@ int dfe_stream_create(dfe_ctx *ctx, const dfe_stream_params *p, dfe_stream **out
         c.take<float>(nimg);                       // take keeps what follows where the stream's first layout put it
         s->mask_i = c.take<float>(nimg);
         s->spare = c.take<float>(nimg);
+        if (s->has_post) s->post.take(c, p->rectify == 1);
         return c.off;
     };
-    rc = dfe_grow(ctx, s->block, lay(DfeCarve()), "dfe_stream_create");
+    if (post) {
+        s->has_post = true;
+        s->post.o = *post;
+        s->post.C = p->C; s->post.H = p->hImg; s->post.W = p->wImg;
+        s->post.y0 = (p->hImg - sh.H1) / 2; s->post.x0 = (p->wImg - sh.W1) / 2; s->post.Ho = sh.H1; s->post.Wo = sh.W1;
+    }
+    rc = dfe_grow(ctx, s->block, lay(DfeCarve()), fn);
     if (rc) { delete s; return rc; }
     lay(DfeCarve(s->block.p));
     *out = s;
     return DFE_OK;
+}
+
+// a push of the post form: the stream must have the chain, and post_out the size this library knows
+int stream_post_args(dfe_stream *s, const char *fn, const void *frame, const dfe_stream_post_out *po) {
+    DFE_REQUIRE(s->ctx, s->has_post, DFE_E_ARG, "%s: the stream was made by dfe_stream_create, not dfe_stream_create_post", fn);
+    DFE_REQUIRE(s->ctx, frame, DFE_E_ARG, "%s: frame is NULL", fn);
+    DFE_REQUIRE(s->ctx, !po || po->struct_size == (int)sizeof(dfe_stream_post_out), DFE_E_ARG, "%s: post_out.struct_size = %d, this library's dfe_stream_post_out has %d bytes",
+                fn, po ? po->struct_size : 0, (int)sizeof(dfe_stream_post_out));
+    return DFE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dfe_stream_create(dfe_ctx *ctx, const dfe_stream_params *p, dfe_stream **out) {
+    DFE_ENTER(ctx);
+    return stream_create(ctx, "dfe_stream_create", p, nullptr, out);
+}
+
+int dfe_stream_post_check(const dfe_stream_params *p, const dfe_stream_post *post) {
+    StreamShapes s;
+    int rc = stream_shapes(nullptr, "dfe_stream_post_check", p, &s);
+    if (rc) return rc;
+    return dfe_stream_post_validate(nullptr, "dfe_stream_post_check", post);
+}
+
+int dfe_stream_create_post(dfe_ctx *ctx, const dfe_stream_params *p, const dfe_stream_post *post, dfe_stream **out) {
+    DFE_ENTER(ctx);
+    DFE_REQUIRE(ctx, post, DFE_E_ARG, "dfe_stream_create_post: post is NULL");
+    return stream_create(ctx, "dfe_stream_create_post", p, post, out);
+}
+
+int dfe_stream_push_post_f32(dfe_stream *s, const float *frame, float imu_tx, float *im_scaled, float *flow, float *mask, float *depth, float *depth_conf,
+                             const dfe_stream_post_out *post_out, double *R9, double *T3, int *n_found, int *n_inliers, int *status) {
+    if (!s) return dfe_fail(nullptr, DFE_E_ARG, "dfe_stream_push_post_f32: stream is NULL");
+    DFE_ENTER(s->ctx);
+    if (int rc = stream_post_args(s, "dfe_stream_push_post_f32", frame, post_out)) return rc;
+    return stream_push(s, frame, nullptr, 1.f, imu_tx, im_scaled, flow, mask, depth, depth_conf, R9, T3, n_found, n_inliers, status, true, post_out);
+}
+
+int dfe_stream_push_post_u8(dfe_stream *s, const uint8_t *frame, float scale, float imu_tx, float *im_scaled, float *flow, float *mask, float *depth,
+                            float *depth_conf, const dfe_stream_post_out *post_out, double *R9, double *T3, int *n_found, int *n_inliers, int *status) {
+    if (!s) return dfe_fail(nullptr, DFE_E_ARG, "dfe_stream_push_post_u8: stream is NULL");
+    DFE_ENTER(s->ctx);
+    if (int rc = stream_post_args(s, "dfe_stream_push_post_u8", frame, post_out)) return rc;
+    return stream_push(s, nullptr, frame, scale, imu_tx, im_scaled, flow, mask, depth, depth_conf, R9, T3, n_found, n_inliers, status, true, post_out);
 }
 
 int dfe_stream_push_f32(dfe_stream *s, const float *frame, float imu_tx, float *im_scaled, float *flow, float *mask, float *depth, float *depth_conf, double *R9,
@@ -289,6 +368,7 @@ int dfe_stream_push_u8(dfe_stream *s, const uint8_t *frame, float scale, float i
 int dfe_stream_reset(dfe_stream *s) {
     if (!s) return dfe_fail(nullptr, DFE_E_ARG, "dfe_stream_reset: stream is NULL");
     s->primed = false;
+    s->post.thave = false;
     return DFE_OK;
 }
 

@@ -12,6 +12,8 @@ typedef struct dfe_census_radial_params { int C, hImg, wImg; int hInput, wInput;
 typedef struct dfe_filter_layer { int nIn, nOut, kH, kW; const float *weight; const float *bias; const int32_t *conn; int nConn; int tanh_after; } dfe_filter_layer;
 typedef struct dfe_tracker_params { int max_points; float quality; float min_dist; int win; int levels; int max_iters; float eps; float min_eig; float max_err; } dfe_tracker_params;
 typedef struct dfe_stream_params { int C, Hsrc, Wsrc; int hImg, wImg; double K[9]; int has_dist; double dist[5]; const dfe_filter_layer *layers; int nlayers; int maxh, maxw; int extraction; double threshold; int rectify; int fix_mask_offset; dfe_tracker_params tracker; double ransac_max_dist; int iterations; unsigned seed; double min_inlier_ratio; } dfe_stream_params;
+typedef struct dfe_stream_post { int struct_size; float consistency_tol; int fill; int fill_levels; int median_k; float median_sigma; int temporal; float t_tol, t_wmax, t_decay; int t_has_gain; float t_gain; int t_has_bias; float t_bias; int t_splat; float t_ztol, t_quant, t_min_cover; } dfe_stream_post;
+typedef struct dfe_stream_post_out { int struct_size; float *flow_bw; float *consistent; float *flow_post; float *weight_post; float *depth_post; float *depth_post_conf; float *depth_fused; float *fused_weight; float *fused_flag; } dfe_stream_post_out;
 int dfe_version(void);
 const char *dfe_kernel_revision(void);
 int dfe_ctx_create(int device, void *stream, int own_stream, dfe_ctx **out);
@@ -186,6 +188,10 @@ int dfe_stream_push_f32(dfe_stream *s, const float *frame, float imu_tx, float *
 int dfe_stream_push_u8(dfe_stream *s, const uint8_t *frame, float scale, float imu_tx, float *im_scaled, float *flow, float *mask, float *depth, float *depth_conf, double *R9, double *T3, int *n_found, int *n_inliers, int *status);
 int dfe_stream_reset(dfe_stream *s);
 void dfe_stream_destroy(dfe_stream *s);
+int dfe_stream_post_check(const dfe_stream_params *p, const dfe_stream_post *post);
+int dfe_stream_create_post(dfe_ctx *ctx, const dfe_stream_params *p, const dfe_stream_post *post, dfe_stream **out);
+int dfe_stream_push_post_f32(dfe_stream *s, const float *frame, float imu_tx, float *im_scaled, float *flow, float *mask, float *depth, float *depth_conf, const dfe_stream_post_out *post_out, double *R9, double *T3, int *n_found, int *n_inliers, int *status);
+int dfe_stream_push_post_u8(dfe_stream *s, const uint8_t *frame, float scale, float imu_tx, float *im_scaled, float *flow, float *mask, float *depth, float *depth_conf, const dfe_stream_post_out *post_out, double *R9, double *T3, int *n_found, int *n_inliers, int *status);
 ]]
 
 local M = {}

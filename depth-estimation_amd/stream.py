@@ -10,7 +10,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import DfeError, FilterLayer, StreamParams, lib
+from ._lib import DfeError, FilterLayer, StreamParams, StreamPost, StreamPostOut, lib
 from .context import get_ctx, ptr
 from .opticalflow_model import _g
 from .sfm2 import _d, _sfm, _tracker_params
@@ -84,6 +84,67 @@ def stream_shapes(params):
     return dict(zip(("Hf", "Wf", "H1", "W1", "oy", "ox", "ix", "iy"), (x.value for x in v)))
 
 
+POST_KEYS = ("consistency", "fill", "median", "temporal")
+POST_TEMPORAL_KEYS = ("tol", "wmax", "decay", "gain", "bias", "key_channel", "splat", "ztol", "quant", "min_cover")
+
+
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def stream_post(post):
+    """dfe_stream_post (include/dfe.h) from DepthEstimationAPI's post= dict: consistency=tol (None / 0: off), fill=True | levels (False /
+    None: off), median=k | (k, sigma) (None: off; sigma <= 0: unguided), temporal=dict(tol=, wmax=8.0, decay=1.0, gain=None, bias=None,
+    splat="nearest", ztol=None, quant=1024.0, min_cover=0.25): TemporalFilter's keywords for the one depth channel (key_channel, if given,
+    is 0).  ValueError for what the library would refuse."""
+    from .fields import _check_decay, _check_splat, _check_tol_wmax, _host_floats
+
+    if not isinstance(post, dict) or set(post) - set(POST_KEYS):
+        raise ValueError("post=%r: a dict with keys of %s expected" % (post, POST_KEYS))
+    o = StreamPost()
+    tol = post.get("consistency")
+    if tol is not None:
+        tol = float(tol)
+        if not tol >= 0.0:
+            raise ValueError("post: consistency=%r must be >= 0" % (tol,))
+        o.consistency_tol = tol
+    fill = post.get("fill")
+    if not (fill is None or isinstance(fill, bool) or (_is_int(fill) and fill >= 0)):
+        raise ValueError("post: fill=%r: True, False or a number of levels >= 0" % (fill,))
+    if fill is not None and fill is not False:
+        o.fill, o.fill_levels = 1, 0 if fill is True else int(fill)
+    median = post.get("median")
+    if median is not None:
+        k, sigma = median if isinstance(median, (tuple, list)) and len(median) == 2 else (median, 0.0)
+        if not _is_int(k) or not 1 <= k <= 15 or k % 2 == 0:
+            raise ValueError("post: median=%r: k or (k, sigma) with k odd, 1 .. 15" % (median,))
+        o.median_k, o.median_sigma = k, float(sigma)
+    t = post.get("temporal")
+    if t is not None:
+        if not isinstance(t, dict) or "tol" not in t or set(t) - set(POST_TEMPORAL_KEYS):
+            raise ValueError("post: temporal=%r: a dict with tol and keys of %s expected" % (t, POST_TEMPORAL_KEYS))
+        if t.get("key_channel", 0) != 0:
+            raise ValueError("post: temporal key_channel=%r: the session's filter has one channel, depth (0)" % (t["key_channel"],))
+        splat = t.get("splat", "nearest")
+        if splat not in ("nearest", "bilinear"):
+            raise ValueError("post: temporal splat=%r: \"nearest\" or \"bilinear\"" % (splat,))
+        o.temporal = 1
+        o.t_tol, o.t_wmax = _check_tol_wmax("post: temporal", t["tol"], t.get("wmax", 8.0))
+        o.t_decay = _check_decay("post: temporal", t.get("decay", 1.0))
+        for what, has, val in (("gain", "t_has_gain", "t_gain"), ("bias", "t_has_bias", "t_bias")):
+            v = t.get(what)
+            if v is not None:
+                v = _host_floats("post: temporal", what, v if isinstance(v, (tuple, list)) else (v,), 1)
+                setattr(o, has, 1)
+                setattr(o, val, v[0])
+        o.t_splat = 1 if splat == "bilinear" else 0
+        ztol = t.get("ztol")
+        o.t_ztol, o.t_quant, o.t_min_cover = (o.t_tol if ztol is None else float(ztol)), float(t.get("quant", 1024.0)), float(t.get("min_cover", 0.25))
+        if o.t_splat:
+            _check_splat("post: temporal", o.t_ztol, o.t_quant, o.t_min_cover)
+    return o
+
+
 class DepthEstimationAPI:
     """depth_estimation_api.lua as an object.  geometry: hImg, wImg, maxh, maxw, output_extraction_method ('max' / 'mean'; the script sets
     'mean', :31); filter: the getFilter module (loaded.filter, :28) or None for raw frames; K 3 x 3 and distP (k1, k2, p1, p2, k3) of the
@@ -94,15 +155,22 @@ class DepthEstimationAPI:
     tracker's and the RANSAC's, as sfm2.getEgoMotion2 takes them.  The stream is made when the first frame shows the camera's size.
     temporal: None, or dict(tol=, wmax=, decay=, gain=, bias=, key_channel=, splat=, ztol=, quant=, min_cover=), TemporalFilter's own
     keywords passed through (temporal.py; not in the reference; splat="bilinear": the sub-pixel splat), for a filter that fuses the
-    depth of every push that was given imu_tx with what the earlier ones left (nextFrameDepth)."""
+    depth of every push that was given imu_tx with what the earlier ones left (nextFrameDepth).
+    post: None, or dict(consistency=tol, fill=True | levels, median=k | (k, sigma), temporal=dict(tol=, wmax=, decay=, gain=, bias=, splat=,
+    ztol=, quant=, min_cover=)): the post-processing chain inside the stream object (include/dfe.h: dfe_stream_create_post,
+    dfe_stream_push_post_*; stream_post above) -- the forward-backward check, hole filling, the guided weighted median and the temporal
+    filter with its state on the device, without Python between the stages.  post["temporal"] and temporal= exclude each other."""
 
-    def __init__(self, geometry, filter, K, distP=None, calibration=None, rectify="features", u8Scale=1.0 / 255.0, temporal=None, **sfm):
+    def __init__(self, geometry, filter, K, distP=None, calibration=None, rectify="features", u8Scale=1.0 / 255.0, temporal=None, post=None, **sfm):
         self.geometry, self.filter, self.K, self.distP = geometry, filter, K, distP
         self.kw = dict(sfm, calibration=calibration, rectify=rectify)
         self.u8Scale = float(u8Scale)
         self.handle, self.ctx, self.shape, self.params, self._keep = None, None, None, None, None
         self.last = {}
         self.temporal = None
+        self.post = None if post is None else stream_post(post)
+        if self.post is not None and self.post.temporal and temporal is not None:
+            raise ValueError("DepthEstimationAPI: post[\"temporal\"] and temporal= are two forms of one filter: give one")
         if temporal is not None:
             from .temporal import TemporalFilter
 
@@ -113,7 +181,10 @@ class DepthEstimationAPI:
         self.params, self._keep = stream_params(self.geometry, self.filter, self.K, self.distP, Cc, H, W, **self.kw)
         self.ctx = get_ctx(frame)
         h = C.c_void_p()
-        self.ctx.check(lib().dfe_stream_create(self.ctx.handle, C.byref(self.params), C.byref(h)))
+        if self.post is None:
+            self.ctx.check(lib().dfe_stream_create(self.ctx.handle, C.byref(self.params), C.byref(h)))
+        else:
+            self.ctx.check(lib().dfe_stream_create_post(self.ctx.handle, C.byref(self.params), C.byref(self.post), C.byref(h)))
         self.handle, self.shape = h, (Cc, H, W)
 
     def nextFrameDepth(self, frame, imu_tx=None):
@@ -122,7 +193,9 @@ class DepthEstimationAPI:
         depth / depth_conf (ARdroneAPI::computeDepthMapFromFlow on the x-flow and the mask).  With temporal= a result that was given imu_tx
         also has depth_fused, depth_fused_weight, depth_fused_flag: the filter's push of depth[None], depth_conf and the flow planes with
         rectify = (K_small, R), K_small = diag(wImg / Wsrc, hImg / Hsrc, 1) K; the first frame, a bad image (no usable pose: the grid cannot
-        be carried), a push without imu_tx (no depth) and reset() reset the filter."""
+        be carried), a push without imu_tx (no depth) and reset() reset the filter.  With post= a result also has flow_post [2][h][w],
+        weight_post, consistent (consistency on), with imu_tx depth_post / depth_post_conf, and with post["temporal"] (imu_tx required:
+        ValueError without) depth_fused, depth_fused_weight, depth_fused_flag, all computed inside the stream."""
         if frame.dim() != 3 or frame.dtype not in (torch.float32, torch.uint8):
             raise TypeError("nextFrameDepth: a float32 or uint8 C x H x W tensor expected")
         frame = frame.contiguous()
@@ -132,6 +205,8 @@ class DepthEstimationAPI:
             raise DfeError(-2, "nextFrameDepth: frame %s, the stream was opened for %s" % (tuple(frame.shape), self.shape))
         if get_ctx(frame) is not self.ctx:
             raise DfeError(-1, "nextFrameDepth: the frame is on another device or stream than the first one")
+        if self.post is not None and self.post.temporal and imu_tx is None:
+            raise ValueError("nextFrameDepth: post[\"temporal\"] fuses depth: imu_tx is required")
         p, dev = self.params, frame.device
         ims = torch.empty((p.C, p.hImg, p.wImg), dtype=torch.float32, device=dev)
         flow = torch.empty((2, p.hImg, p.wImg), dtype=torch.float32, device=dev)
@@ -139,17 +214,35 @@ class DepthEstimationAPI:
         depth = torch.empty_like(mask) if imu_tx is not None else None
         dconf = torch.empty_like(mask) if imu_tx is not None else None
         R, T, nf, ni, st = (C.c_double * 9)(), (C.c_double * 3)(), C.c_int(), C.c_int(), C.c_int()
-        tail = (float(imu_tx or 0.0), ptr(ims), ptr(flow), ptr(mask), ptr(depth), ptr(dconf), R, T, C.byref(nf), C.byref(ni), C.byref(st))
-        if frame.dtype == torch.uint8:
-            self.ctx.check(lib().dfe_stream_push_u8(self.handle, ptr(frame), self.u8Scale, *tail))
+        head = (float(imu_tx or 0.0), ptr(ims), ptr(flow), ptr(mask), ptr(depth), ptr(dconf))
+        tail = (R, T, C.byref(nf), C.byref(ni), C.byref(st))
+        posted = {}
+        if self.post is not None:
+            posted = dict(flow_post=torch.empty_like(flow), weight_post=torch.empty_like(mask))
+            if self.post.consistency_tol > 0:
+                posted["consistent"] = torch.empty_like(mask)
+            if imu_tx is not None:
+                posted.update(depth_post=torch.empty_like(mask), depth_post_conf=torch.empty_like(mask))
+            if self.post.temporal:
+                posted.update(depth_fused=torch.empty_like(mask), depth_fused_weight=torch.empty_like(mask), depth_fused_flag=torch.empty_like(mask))
+            po = StreamPostOut()
+            for k, t in posted.items():
+                setattr(po, {"depth_fused_weight": "fused_weight", "depth_fused_flag": "fused_flag"}.get(k, k), ptr(t))
+            head += (C.byref(po),)
+            push_u8, push_f32 = lib().dfe_stream_push_post_u8, lib().dfe_stream_push_post_f32
         else:
-            self.ctx.check(lib().dfe_stream_push_f32(self.handle, ptr(frame), *tail))
+            push_u8, push_f32 = lib().dfe_stream_push_u8, lib().dfe_stream_push_f32
+        if frame.dtype == torch.uint8:
+            self.ctx.check(push_u8(self.handle, ptr(frame), self.u8Scale, *head, *tail))
+        else:
+            self.ctx.check(push_f32(self.handle, ptr(frame), *head, *tail))
         self.last = dict(status=st.value, im_scaled=ims, nFound=nf.value, nInliers=ni.value)
         if self.temporal is not None and (st.value != 1 or imu_tx is None):   # nothing to carry the state with: it starts over
             self.temporal.reset()
         if st.value == 0:
             return None
         self.last.update(yflow=flow[0], xflow=flow[1], mask=mask, R=torch.tensor(R[:], dtype=torch.float64).reshape(3, 3), T=torch.tensor(T[:], dtype=torch.float64))
+        self.last.update(posted)
         if imu_tx is not None:
             self.last.update(depth=depth, depth_conf=dconf)
             if self.temporal is not None and st.value == 1:

@@ -1469,10 +1469,84 @@ int dfe_stream_push_f32(dfe_stream *s, const float *frame, float imu_tx, float *
                         float *depth_conf, double *R9, double *T3, int *n_found, int *n_inliers, int *status);
 int dfe_stream_push_u8(dfe_stream *s, const uint8_t *frame, float scale, float imu_tx, float *im_scaled, float *flow, float *mask,
                        float *depth, float *depth_conf, double *R9, double *T3, int *n_found, int *n_inliers, int *status);
-/* forgets the previous frame: the next push returns status 0 */
+/* forgets the previous frame: the next push returns status 0 (a post stream, below, also forgets its temporal state) */
 int dfe_stream_reset(dfe_stream *s);
 /* (before its ctx is destroyed) */
 void dfe_stream_destroy(dfe_stream *s);
+
+/* ---- the session's post-processing chain: consistency, fill, median and temporal fusion behind the pair step (NOT in the reference;
+ * DESIGN section 4.39).  dfe_stream_params, dfe_stream_create and dfe_stream_push_* above stay as they are; a stream made by
+ * dfe_stream_create_post also takes dfe_stream_push_post_*.  Both structs begin with their own size, so a later version can grow them:
+ * a struct_size other than sizeof is DFE_E_ARG. */
+typedef struct dfe_stream_post {
+    int struct_size;           /* sizeof(dfe_stream_post) */
+    float consistency_tol;     /* > 0: the forward-backward check with this tol; 0: off; negative or NaN: DFE_E_ARG */
+    int fill;                  /* 0 / 1: dfe_fill_holes_f32 */
+    int fill_levels;           /* its `levels` (>= 0) */
+    int median_k;              /* 0: off; odd 1 .. 15: dfe_weighted_median_f32's k */
+    float median_sigma;        /* its sigma; <= 0: unguided */
+    int temporal;              /* 0 / 1: the temporal depth filter (temporal.py's TemporalFilter on the one depth channel, key_channel 0).
+                                  The members below are read only with temporal == 1 */
+    float t_tol, t_wmax, t_decay;   /* tol >= 0; wmax finite and >= 1e-6; decay in (0, 1] */
+    int t_has_gain;            /* 0 / 1: depth' = t_gain depth + t_bias from one grid to the next, each term only where it is given */
+    float t_gain;
+    int t_has_bias;
+    float t_bias;
+    int t_splat;               /* 0 nearest (dfe_forward_warp_f32), 1 bilinear (dfe_forward_splat_f32, with the three members below) */
+    float t_ztol, t_quant, t_min_cover;   /* t_splat == 1: ztol finite and >= 0, quant finite and > 0, 0 <= min_cover <= 1 */
+} dfe_stream_post;
+typedef struct dfe_stream_post_out {   /* device pointers, each may be NULL */
+    int struct_size;           /* sizeof(dfe_stream_post_out) */
+    float *flow_bw;            /* [2][hImg][wImg]  (consistency on, else not written) */
+    float *consistent;         /* [hImg][wImg]     (consistency on, else not written) */
+    float *flow_post;          /* [2][hImg][wImg] */
+    float *weight_post;        /* [hImg][wImg] */
+    float *depth_post;         /* [hImg][wImg] */
+    float *depth_post_conf;    /* [hImg][wImg] */
+    float *depth_fused;        /* [hImg][wImg]     (temporal on, else not written) */
+    float *fused_weight;       /* [hImg][wImg]     (temporal on, else not written) */
+    float *fused_flag;         /* [hImg][wImg]     (temporal on, else not written) */
+} dfe_stream_post_out;
+/* Host only, no ctx (as dfe_stream_shapes): checks p as dfe_stream_shapes does (its codes, DFE_E_SHAPE included), then every member of
+ * post (DFE_E_ARG); dfe_last_error(NULL) has the text. */
+int dfe_stream_post_check(const dfe_stream_params *p, const dfe_stream_post *post);
+/* dfe_stream_create with the chain's options: every buffer the chain needs, the temporal state included, lies in the stream's own block
+ * (pushes allocate nothing of their own). */
+int dfe_stream_create_post(dfe_ctx *ctx, const dfe_stream_params *p, const dfe_stream_post *post, dfe_stream **out);
+/* dfe_stream_push_f32 / _u8 with the chain behind it.  The plain outputs (im_scaled .. status) are bit-identical to the plain push
+ * whatever the options.  The chain runs on a push with status 1, after the plain steps; each stage is the public entry named, so every
+ * post output equals the composition of those entries bit for bit.  With
+ *   R      the matcher's region (floor((hImg - H1) / 2), floor((wImg - W1) / 2), H1, W1) of dfe_stream_shapes,
+ *   prevf  the rectified previous features the forward matcher read, cur the current features,
+ *   guide  dfe_remove_ego_motion_f32(previous scaled frame, C, hImg, wImg, K_small, Rot, inverse = 1) -- IMAGE mode: the frame the session
+ *          rectified anyway; FEATURES mode: one more warp (feature grid and image grid share K_small, as in the reference, so the two
+ *          are aligned to within the filter's crop):
+ * 1. consistency (consistency_tol > 0): flow_bw = the session's matcher entry on (cur, prevf), flow planes only (extraction 0, 1:
+ *    dfe_flow_pair_filtered_f32 with the stream's threshold; 2: _mean_f32); consistent = dfe_flow_consistency_f32(flow, flow_bw, hImg,
+ *    wImg, R, tol); kept = (mask > 0 ? 1 : 0) consistent.  Without the stage kept = (mask > 0 ? 1 : 0).  mask is the push's own output.
+ * 2. fill: dense, filled = dfe_fill_holes_f32(flow, 2, .., kept, R, fill_levels); w = kept > 0 ? filled : 0.25f filled.
+ * 3. median (median_k): med, valid = dfe_weighted_median_f32(src, 2, .., w, guide, C, median_sigma, median_k, R), with src, w = dense and
+ *    the w of stage 2 when fill is on, else flow and kept.
+ * 4. flow_post = med, else dense, else flow; weight_post = valid, else filled, else mask consistent (one rounded product; without the
+ *    consistency stage no factor is applied: with nothing enabled weight_post has mask's bits).  depth_post, depth_post_conf =
+ *    dfe_flow_to_depth_ardrone(flow_post plane 1, weight_post, imu_tx), computed when a depth output of the chain is asked for or temporal
+ *    is on.
+ * 5. temporal: TemporalFilter.push(depth_post[None], depth_post_conf, flow_post, rectify = (K_small, Rot)) of temporal.py with the state in
+ *    the stream.  The first result after a create, a reset or a bad image: dfe_temporal_fuse_f32 against a zero prior.  After that:
+ *    dfe_forward_warp_f32 (t_splat 1: dfe_forward_splat_f32) of the state and its weight along the STORED flow, keyed on the state, with
+ *    gain, bias and decay; dfe_remove_ego_motion_f32 of the two planes (prior, weight), which lie next to each other; the weight times
+ *    the warp's mask (one rounded product); dfe_temporal_fuse_f32 over the whole frame with (depth_post, depth_post_conf).  The result
+ *    and flow_post become the state.  The stage runs on every status-1 push of dfe_stream_push_post_*, whatever outputs were asked for.
+ * post_out may be NULL (the state still advances).  Status 0 writes no post output.  Status 2 zeroes every post output that was given
+ * and resets the temporal state.  Any error leaves the stream and the temporal state as they were.
+ * dfe_stream_push_f32 / _u8 on a post stream return the plain result and reset the temporal state: the pair's post-processed depth was
+ * not computed, so there is nothing to carry.  dfe_stream_push_post_* on a stream of dfe_stream_create is DFE_E_ARG. */
+int dfe_stream_push_post_f32(dfe_stream *s, const float *frame, float imu_tx, float *im_scaled, float *flow, float *mask, float *depth,
+                             float *depth_conf, const dfe_stream_post_out *post_out, double *R9, double *T3, int *n_found,
+                             int *n_inliers, int *status);
+int dfe_stream_push_post_u8(dfe_stream *s, const uint8_t *frame, float scale, float imu_tx, float *im_scaled, float *flow, float *mask,
+                            float *depth, float *depth_conf, const dfe_stream_post_out *post_out, double *R9, double *T3, int *n_found,
+                            int *n_inliers, int *status);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,469 @@
+"""GPU suite (-m gpu), part 12b: the session's post-processing chain (dfe_stream_create_post, dfe_stream_push_post_*: consistency, fill,
+guided median, depth, temporal fusion inside the stream object) against the composition of the public Python ops it replaces, bit for
+bit, on the frames of tests/test_gpu_stream.py: 3 x 240 x 320 views of tracker_ref64.two_view_pair, the sequence [im0, im1, im0],
+imu_tx = 1.  Outputs are written into buffers pre-filled with -7 that are 64 elements longer than the result: the tail must keep its -7,
+and an output that a push must not write keeps it everywhere."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from tests import tracker_ref64 as tr
+from tests.egomotion_cases import ARDRONE_DIST
+from tests.test_gpu_stream import FILL, GAINS, OUTPUTS, Config, Stream, composition, frames, guarded, make_filter, sfm_kw, unguard
+
+pytestmark = pytest.mark.gpu
+
+E_ARG = -1
+POST_OUT = ("flow_bw", "consistent", "flow_post", "weight_post", "depth_post", "depth_post_conf", "depth_fused", "fused_weight", "fused_flag")
+PLAIN = ("R", "T", "im_scaled", "flow", "mask", "depth", "dconf")
+# The tolerances come from what the composition gives on this pair (printed by test_composition_is_not_degenerate): the 'max' flows are
+# integers and the 'mean' ones within a fraction of them, so a forward-backward residual of 1 px separates the matched pixels from the
+# occluded band; depths are |x - W / 2| / |mode| with integer modes, so 2 units of depth let neighbouring modes of the far field agree
+TOL_FB, T_TOL = 1.0, 2.0
+TEMPORAL = dict(tol=T_TOL, wmax=4.0, decay=0.9, gain=(1.0,), bias=(0.0,))
+STAGES = {
+    "consistency": dict(consistency=TOL_FB),
+    "fill": dict(fill=True),
+    "median guided": dict(median=(5, 40.0)),
+    "fill + median": dict(fill=2, median=(5, 40.0)),
+    "all four": dict(consistency=TOL_FB, fill=True, median=(5, 40.0), temporal=TEMPORAL),
+}
+
+
+def post_of(stages, splat="nearest"):
+    post = dict(stages)
+    if "temporal" in post:
+        post["temporal"] = dict(post["temporal"], splat=splat, min_cover=0.25, quant=1024.0)
+    return post
+
+
+class PostStream:
+    """dfe_stream_create_post and dfe_stream_push_post_* driven directly, every device output in a guarded buffer"""
+
+    def __init__(self, dfe, cuda, cfg, filt, K, post, shape=(3, 240, 320)):
+        self.dfe, self.cuda, self.ctx = dfe, cuda, dfe.get_ctx(0)
+        self.p, self.keep = dfe.stream.stream_params(cfg.geometry, filt, K, cfg.dist, *shape, **cfg.extra())
+        self.post = dfe.stream.stream_post(post)
+        self.h = C.c_void_p()
+        self.ctx.check(dfe.lib().dfe_stream_create_post(self.ctx.handle, C.byref(self.p), C.byref(self.post), C.byref(self.h)))
+        self.on = dict(flow_bw=self.post.consistency_tol > 0, consistent=self.post.consistency_tol > 0, depth_fused=bool(self.post.temporal),
+                       fused_weight=bool(self.post.temporal), fused_flag=bool(self.post.temporal))
+
+    def push(self, frame, imu_tx=1.0, u8_scale=None, expect=0, want=OUTPUTS, want_post=POST_OUT, plain=False):
+        """one push.  want / want_post name the outputs that get a buffer; want_post None passes post_out = NULL; plain: the old
+        dfe_stream_push_* entry on this stream"""
+        from depth_estimation_amd._lib import StreamPostOut
+
+        p, cuda, lib = self.p, self.cuda, self.dfe.lib()
+        n = p.hImg * p.wImg
+        shapes = dict(im_scaled=(p.C, p.hImg, p.wImg), flow=(2, p.hImg, p.wImg), mask=(p.hImg, p.wImg), depth=(p.hImg, p.wImg), dconf=(p.hImg, p.wImg))
+        shapes.update({k: ((2, p.hImg, p.wImg) if k.startswith("flow") else (p.hImg, p.wImg)) for k in POST_OUT})
+        bufs = {k: guarded(int(np.prod(shapes[k])), cuda) for k in tuple(want) + tuple(want_post or ())}
+        po = StreamPostOut()
+        for k in want_post or ():
+            setattr(po, k, bufs[k].data_ptr())
+        R, Tt, nf, ni, st = (C.c_double * 9)(*([-7.0] * 9)), (C.c_double * 3)(*([-7.0] * 3)), C.c_int(-7), C.c_int(-7), C.c_int(-7)
+        head = (imu_tx,) + tuple(bufs[k].data_ptr() if k in bufs else None for k in OUTPUTS)
+        if not plain:
+            head += (None if want_post is None else C.byref(po),)
+        tail = (R, Tt, C.byref(nf), C.byref(ni), C.byref(st))
+        fptr = None if frame is None else frame.data_ptr()
+        if frame is not None and frame.dtype == torch.uint8:
+            rc = (lib.dfe_stream_push_u8 if plain else lib.dfe_stream_push_post_u8)(self.h, fptr, u8_scale, *head, *tail)
+        else:
+            rc = (lib.dfe_stream_push_f32 if plain else lib.dfe_stream_push_post_f32)(self.h, fptr, *head, *tail)
+        assert rc == expect, (rc, lib.dfe_last_error(self.ctx.handle))
+        if rc:
+            assert all((bufs[k] == FILL).all() for k in bufs if k != "im_scaled") and st.value == -7, "a refused push wrote a result"
+            return None
+        out = dict(status=st.value, nf=nf.value, ni=ni.value, R=np.array(R[:]).reshape(3, 3), T=np.array(Tt[:]))
+        first = st.value == 0
+        for k in want:
+            out[k] = unguard(bufs[k], shapes[k], k, k == "im_scaled" or (k != "flow" and not first))
+        for k in want_post or ():
+            # written: on a result or a bad image, where the output's stage is on (a bad image zeroes every output); flows may hold -7
+            written = not first and not plain and (st.value == 2 or self.on.get(k, True))
+            out[k] = unguard(bufs[k], shapes[k], k, written and not k.startswith("flow"))
+            if not written:
+                assert (out[k] == FILL).all(), "%s was written by a push with status %d" % (k, st.value)
+            elif st.value == 2:
+                assert not out[k].any(), "%s is not zero behind a bad image" % k
+        return out
+
+    def reset(self):
+        assert self.dfe.lib().dfe_stream_reset(self.h) == 0
+
+    def close(self):
+        self.dfe.lib().dfe_stream_destroy(self.h)
+
+
+_cache = {}
+
+
+def pair_parts(dfe, cfg, key, filt, K, prev, cur):
+    """the plain composition of a pair and the tensors the chain's composition needs beside it; made once per configuration and pair"""
+    if key not in _cache:
+        base = composition(dfe, cfg, filt, K, prev, cur)
+        g = cfg.geometry
+        h, w = g["hImg"], g["wImg"]
+        if cfg.dist is not None:
+            prev, cur = dfe.sfm2.undistortImage(prev, K, cfg.dist), dfe.sfm2.undistortImage(cur, K, cfg.dist)
+        ps, cs = dfe.imageScale(prev, w, h), dfe.imageScale(cur, w, h)
+        Ks = np.array(K, np.float64).copy()
+        Ks[0] *= w / prev.shape[2]
+        Ks[1] *= h / prev.shape[1]
+        R = torch.from_numpy(base["R"].copy())
+        fcur = filt.forward(cs).clone()
+        guide = dfe.sfm2.removeEgoMotion(ps, Ks, R, inverse=True)[0]
+        wprev = dfe.sfm2.removeEgoMotion(filt.forward(ps).clone(), Ks, R, inverse=True)[0] if cfg.rectify == "features" else filt.forward(guide).clone()
+        bw = dfe.getModel(dict(g, prefilter=True), True, True, device=cs.device).forwardFlow([fcur, wprev], cfg.threshold)["full"].clone()
+        H1, W1 = fcur.shape[1] - g["maxh"] + 1, fcur.shape[2] - g["maxw"] + 1
+        _cache[key] = dict(base=base, Ks=Ks, R=R, guide=guide, bw=bw, region=((h - H1) // 2, (w - W1) // 2, H1, W1), flow=torch.from_numpy(base["flow"]).to(cs.device),
+                           mask=torch.from_numpy(base["mask"]).to(cs.device))
+    return _cache[key]
+
+
+def post_composition(dfe, parts, post, tf):
+    """the chain stitched from the public Python ops on a pair's plain results; tf: the TemporalFilter that carries the state, or None"""
+    flow, mask, Rg = parts["flow"], parts["mask"], parts["region"]
+    out, t = {}, {}
+    kept = (mask > 0).to(torch.float32)
+    weight_post = mask
+    if post.get("consistency"):
+        cons = dfe.flowConsistency(flow, parts["bw"], post["consistency"], Rg)[0]
+        kept = kept * cons
+        weight_post = mask * cons
+        out.update(flow_bw=parts["bw"], consistent=cons)
+    src, wgt, flow_post = flow, kept, flow
+    fill = post.get("fill")
+    if fill:
+        dense, filled = dfe.fillHoles(flow, kept, Rg, 0 if fill is True else int(fill))
+        wgt = torch.where(kept > 0, filled, 0.25 * filled)
+        src = flow_post = dense
+        weight_post = filled
+        t.update(filled=filled)
+    if post.get("median"):
+        k, sigma = post["median"]
+        flow_post, weight_post = dfe.weightedMedian(src, wgt, parts["guide"], k, sigma, Rg)
+    depth, dconf = dfe.computeDepthMapFromFlow(flow_post[1], weight_post, 1.0)
+    out.update(flow_post=flow_post, weight_post=weight_post, depth_post=depth, depth_post_conf=dconf)
+    if tf is not None:
+        fused, fw, flag = tf.push(depth[None], dconf, flow_post, rectify=(parts["Ks"], parts["R"]))
+        out.update(depth_fused=fused[0], fused_weight=fw, fused_flag=flag)
+    res = {k: v.cpu().numpy() for k, v in out.items()}
+    res["_kept"], res["_region"] = kept.cpu().numpy(), Rg
+    res.update({"_" + k: v.cpu().numpy() for k, v in t.items()})
+    return res
+
+
+def sequence_composition(dfe, cuda, cfg, ckey, filt, post, seq=("01", "10")):
+    """the chain's composition over the pairs of [im0, im1, im0, ...]: a list of (plain, post) results, the temporal state carried"""
+    im0, im1, _, K = frames(cuda)
+    ims = {"0": im0, "1": im1}
+    tf = dfe.TemporalFilter(**post["temporal"]) if "temporal" in post else None
+    res = []
+    for pair in seq:
+        parts = pair_parts(dfe, cfg, ckey + (pair,), filt, K, ims[pair[0]], ims[pair[1]])
+        res.append((parts["base"], post_composition(dfe, parts, post, tf)))
+    return res
+
+
+def assert_post_same(got, want, what):
+    base, post = want
+    assert got["status"] == 1 and (got["nf"], got["ni"]) == (base["nf"], base["ni"]), what
+    for k in PLAIN:
+        assert np.array_equal(got[k], base[k]), "%s: plain output %s differs from the composition (%d elements)" % (what, k, (got[k] != base[k]).sum())
+    for k in POST_OUT:
+        if k in post:
+            assert np.array_equal(got[k], post[k]), "%s: %s differs from the composition (%d elements)" % (what, k, (got[k] != post[k]).sum())
+        else:
+            assert (got[k] == FILL).all(), "%s: %s was written though its stage is off" % (what, k)
+
+
+def run_post_sequence(dfe, cuda, cfg, ckey, post):
+    im0, im1, _, K = frames(cuda)
+    filt = make_filter(dfe, cuda, cfg.gain)
+    s = PostStream(dfe, cuda, cfg, filt, K, post)
+    try:
+        r1 = s.push(im0)
+        assert r1["status"] == 0
+        r2, r3 = s.push(im1), s.push(im0)
+    finally:
+        s.close()
+    w2, w3 = sequence_composition(dfe, cuda, cfg, ckey, filt, post)
+    assert_post_same(r2, w2, "push 2")
+    assert_post_same(r3, w3, "push 3 (the carried state: warp, rotation, fuse)")
+    return (r2, r3), (w2, w3)
+
+
+def half(method="mean", rectify="features", **kw):
+    return Config(120, 160, 16, method=method, rectify=rectify, **kw), ("half", method, rectify)
+
+
+# ------------------------------------------------------------------------------------------------------- 1. equals the composition
+CASES = [(st, "nearest", r, m) for st in STAGES for r in ("features", "image") for m in ("max", "mean")] + \
+        [("all four", "bilinear", r, m) for r in ("features", "image") for m in ("max", "mean")]
+
+
+@pytest.mark.parametrize("stages,splat,rectify,method", CASES, ids=["%s, %s, %s, %s" % c for c in CASES])
+def test_post_equals_composition_half_size(dfe, cuda, stages, splat, rectify, method):
+    """Geometry 120 x 160, a 16 x 16 window (the matcher goes through the stand-alone ops): every post output of pushes 2 and 3 of
+    [im0, im1, im0] equals the composition of the public Python ops bit for bit, an output whose stage is off is not written, and the
+    plain outputs equal the plain composition's."""
+    cfg, ckey = half(method, rectify)
+    run_post_sequence(dfe, cuda, cfg, ckey, post_of(STAGES[stages], splat))
+
+
+def test_post_equals_composition_full_size(dfe, cuda):
+    """Geometry 240 x 320 (scale 1 : 1), a 17 x 17 window: the matcher's fused soft-arg-max epilogue, in both directions"""
+    run_post_sequence(dfe, cuda, Config(240, 320, 17, method="mean"), ("full", "mean", "features"), post_of(STAGES["all four"], "bilinear"))
+
+
+def test_post_plain_outputs_equal_a_plain_stream(dfe, cuda):
+    """the plain outputs of a post push are those of dfe_stream_push_f32 on a stream of dfe_stream_create, bit for bit, whatever the chain"""
+    im0, im1, _, K = frames(cuda)
+    cfg, _ = half()
+    filt = make_filter(dfe, cuda)
+    a, b = Stream(dfe, cuda, cfg, filt, K), PostStream(dfe, cuda, cfg, filt, K, post_of(STAGES["all four"]))
+    try:
+        for im in (im0, im1, im0):
+            ra, rb = a.push(im), b.push(im)
+            for k in ra:
+                assert np.array_equal(ra[k], rb[k]), k
+    finally:
+        a.close()
+        b.close()
+
+
+# ------------------------------------------------------------------------------------------------ 2. the comparison is not empty
+@pytest.mark.parametrize("method", ["max", "mean"])
+def test_composition_is_not_degenerate(dfe, cuda, method):
+    """What keeps the comparisons above from passing on empty planes, asserted on the composition alone: the consistency mask keeps some
+    pixels of R and rejects some, the fill finds values where nothing was kept, the median changes the flow inside R, and the fusion of
+    push 3 finds prior and measurement in agreement somewhere (flag 3)."""
+    cfg, ckey = half(method)
+    filt = make_filter(dfe, cuda, cfg.gain)
+    for splat in ("nearest", "bilinear"):
+        (b2, w2), (b3, w3) = sequence_composition(dfe, cuda, cfg, ckey, filt, post_of(STAGES["all four"], splat))
+        y0, x0, Ho, Wo = w2["_region"]
+        inR = np.zeros_like(b2["mask"], bool)
+        inR[y0:y0 + Ho, x0:x0 + Wo] = True
+        for w, b in ((w2, b2), (w3, b3)):
+            kept, rej = int((w["consistent"][inR] == 1).sum()), int((w["consistent"][inR] == 0).sum())
+            holes = int(((w["_filled"] == 1) & (w["_kept"] == 0)).sum())
+            moved = int((w["flow_post"] != b["flow"])[:, inR].sum())
+            flags = {int(f): int((w["fused_flag"] == f).sum()) for f in np.unique(w["fused_flag"])}
+            print("%s %s: consistent keeps %d of R, rejects %d; %d holes filled; flow_post differs from flow in %d elements of R; flags %s" %
+                  (method, splat, kept, rej, holes, moved, flags))
+            assert kept > 0 and rej > 0 and holes > 0 and moved > 0
+        assert set(np.unique(w2["fused_flag"])) <= {0.0, 2.0}       # the first result: a zero prior
+        assert (w3["fused_flag"] == 3).any()
+    (_, wm), _ = sequence_composition(dfe, cuda, cfg, ckey, filt, post_of(STAGES["median guided"]))
+    assert (wm["flow_post"] != b2["flow"])[:, inR].any()
+
+
+# ------------------------------------------------------------------------------------------------------------ 3. nothing enabled
+@pytest.mark.parametrize("rectify", ["features", "image"])
+def test_post_nothing_enabled(dfe, cuda, rectify):
+    """all stages off: flow_post = flow, weight_post = mask, depth_post = depth, depth_post_conf = depth_conf, bit for bit; the outputs of
+    the stages that are off are not written"""
+    im0, im1, _, K = frames(cuda)
+    cfg, _ = half(rectify=rectify)
+    filt = make_filter(dfe, cuda)
+    s = PostStream(dfe, cuda, cfg, filt, K, {})
+    try:
+        s.push(im0)
+        for im in (im1, im0):
+            r = s.push(im)
+            assert r["status"] == 1 and r["mask"].any() and r["dconf"].any()
+            for a, b in (("flow_post", "flow"), ("weight_post", "mask"), ("depth_post", "depth"), ("depth_post_conf", "dconf")):
+                assert np.array_equal(r[a].view(np.uint32), r[b].view(np.uint32)), a
+    finally:
+        s.close()
+
+
+# --------------------------------------------------------------------------------------------------- 4. optional outputs, guards
+POST_SUBSETS = [(k,) for k in POST_OUT] + [("depth_post", "fused_flag"), ("flow_bw", "weight_post", "depth_fused"), ("consistent", "flow_post", "depth_post_conf",
+                                                                                                                      "fused_weight"), ()]
+
+
+@pytest.mark.parametrize("splat", ["nearest", "bilinear"])
+def test_post_optional_outputs(dfe, cuda, splat):
+    """every post output may be NULL, and so may post_out: whatever subset is asked for equals the same output of the pushes that ask for
+    all nine (the guards are checked by every push), with and without the plain outputs.  The temporal state advances whatever is asked
+    for: behind three pushes with post_out = NULL, the fourth push's depth_fused equals the composition's over the whole sequence."""
+    im0, im1, _, K = frames(cuda)
+    cfg, ckey = half()
+    filt = make_filter(dfe, cuda)
+    post = post_of(STAGES["all four"], splat)
+    full = PostStream(dfe, cuda, cfg, filt, K, post)
+    try:
+        full.push(im0)
+        want = [full.push(im1), full.push(im0)]
+    finally:
+        full.close()
+    for i, sub in enumerate(POST_SUBSETS):
+        plain = OUTPUTS if i % 2 else ()
+        s = PostStream(dfe, cuda, cfg, filt, K, post)
+        try:
+            assert s.push(im0, want=plain, want_post=sub)["status"] == 0
+            got = [s.push(im1, want=plain, want_post=sub), s.push(im0, want=plain, want_post=sub)]
+        finally:
+            s.close()
+        for g, w in zip(got, want):
+            assert set(g) == set(sub) | set(plain) | {"status", "nf", "ni", "R", "T"}
+            for k in g:
+                assert np.array_equal(g[k], w[k]), (sub, k)
+    s = PostStream(dfe, cuda, cfg, filt, K, post)
+    try:
+        for im in (im0, im1, im0):
+            s.push(im, want=(), want_post=None)
+        r4 = s.push(im1, want=(), want_post=("depth_fused", "fused_weight", "fused_flag"))
+    finally:
+        s.close()
+    w4 = sequence_composition(dfe, cuda, cfg, ckey, filt, post, seq=("01", "10", "01"))[2][1]
+    for k in ("depth_fused", "fused_weight", "fused_flag"):
+        assert np.array_equal(r4[k], w4[k]), k
+    assert (w4["fused_flag"] >= 3).any()
+
+
+# ------------------------------------------------------------------------------------------------------------------ 5. state rules
+def test_post_state_rules(dfe, cuda):
+    """[flat, im0, im1, im0], a reset, [im0, im1, (no frame), im0], an old push, im1.  Status 0 writes no post output (PostStream.push
+    checks it); the bad image (the flat frame holds no corner) zeroes every post output and resets the temporal state, so the push behind
+    it fuses against a zero prior (flags 0 and 2 only) and equals the composition of a fresh sequence; so does the one behind a reset; a
+    refused push changes nothing; an old dfe_stream_push_f32 on the post stream returns the plain result, writes no post output and resets
+    the temporal state."""
+    im0, im1, flat, K = frames(cuda)
+    cfg, ckey = half()
+    filt = make_filter(dfe, cuda)
+    post = post_of(STAGES["all four"])
+    w01, w10 = sequence_composition(dfe, cuda, cfg, ckey, filt, post)
+    fresh10 = sequence_composition(dfe, cuda, cfg, ckey, filt, post, seq=("10",))[0]
+    assert (w10[1]["fused_flag"] == 3).any() and not np.array_equal(w10[1]["depth_fused"], fresh10[1]["depth_fused"])   # the state matters
+    s = PostStream(dfe, cuda, cfg, filt, K, post)
+    try:
+        assert s.push(flat)["status"] == 0
+        bad = s.push(im0)
+        assert bad["status"] == 2 and not any(bad[k].any() for k in ("flow", "mask", "depth", "dconf") + POST_OUT)
+        r = s.push(im1)
+        assert set(np.unique(r["fused_flag"])) <= {0.0, 2.0}
+        assert_post_same(r, w01, "the push behind a bad image")
+        assert_post_same(s.push(im0), w10, "the push after that")
+        s.reset()
+        assert s.push(im0)["status"] == 0
+        r = s.push(im1)
+        assert set(np.unique(r["fused_flag"])) <= {0.0, 2.0}
+        assert_post_same(r, w01, "the pair behind a reset")
+        assert s.push(None, expect=E_ARG) is None                  # a refused push: stream and temporal state stay
+        assert_post_same(s.push(im0), w10, "the push behind a refused one")
+        old = s.push(im1, plain=True)                              # (PostStream.push: no post output was written)
+        assert old["status"] == 1
+        for k in PLAIN:
+            assert np.array_equal(old[k], w01[0][k]), k
+        assert_post_same(s.push(im0), fresh10, "the push behind an old push: a zero prior")
+    finally:
+        s.close()
+
+
+def test_post_push_argument_errors(dfe, cuda):
+    """a post push on a plain stream, a post_out of another size and a NULL stream are refused; creation refuses a bad option"""
+    from depth_estimation_amd._lib import StreamPost, StreamPostOut
+
+    im0, im1, _, K = frames(cuda)
+    cfg, _ = half()
+    filt = make_filter(dfe, cuda)
+    lib, ctx = dfe.lib(), dfe.get_ctx(0)
+    none = [None] * 5
+    tail = [None] * 5
+    plain = Stream(dfe, cuda, cfg, filt, K)
+    s = PostStream(dfe, cuda, cfg, filt, K, post_of(STAGES["consistency"]))
+    try:
+        assert lib.dfe_stream_push_post_f32(plain.h, im0.data_ptr(), 1.0, *none, None, *tail) == E_ARG
+        assert lib.dfe_stream_push_post_f32(None, im0.data_ptr(), 1.0, *none, None, *tail) == E_ARG
+        assert lib.dfe_stream_push_post_u8(None, im0.data_ptr(), 1.0, 1.0, *none, None, *tail) == E_ARG
+        po = StreamPostOut()
+        po.struct_size -= 8
+        assert lib.dfe_stream_push_post_f32(s.h, im0.data_ptr(), 1.0, *none, C.byref(po), *tail) == E_ARG
+        st = C.c_int(-7)
+        assert lib.dfe_stream_push_post_f32(s.h, im0.data_ptr(), 1.0, *none, None, None, None, None, None, C.byref(st)) == 0 and st.value == 0   # still the first frame
+        p, keep = dfe.stream.stream_params(cfg.geometry, filt, K, None, 3, 240, 320, **cfg.extra())
+        o, h = StreamPost(), C.c_void_p()
+        o.median_k = 4
+        assert lib.dfe_stream_create_post(ctx.handle, C.byref(p), C.byref(o), C.byref(h)) == E_ARG and not h.value
+        assert lib.dfe_stream_create_post(ctx.handle, C.byref(p), None, C.byref(h)) == E_ARG and not h.value
+    finally:
+        plain.close()
+        s.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------- 6. u8 push
+@pytest.mark.parametrize("dist", [None, ARDRONE_DIST], ids=["as it is", "undistorted"])
+def test_post_u8_push(dfe, cuda, dist):
+    """dfe_stream_push_post_u8 on bytes with scale 1 / 255 gives what dfe_stream_push_post_f32 gives on float32(byte) x float32(1 / 255),
+    every plain and post output bit for bit, with and without the undistortion (the frames and the tracker's floor as in
+    test_stream_u8_push_and_reset)"""
+    im0, im1, _, K = frames(cuda)
+    b0, b1 = (im0 / np.float32(GAINS[2])).round().clamp(0, 255).to(torch.uint8), (im1 / np.float32(GAINS[2])).round().clamp(0, 255).to(torch.uint8)
+    f0, f1 = b0.to(torch.float32) * np.float32(1.0 / 255.0), b1.to(torch.float32) * np.float32(1.0 / 255.0)
+    cfg = Config(120, 160, 16, method="mean", dist=dist, sfm=sfm_kw(trackerMinEig=tr.ROUTE["min_eig"] / 255.0 ** 2), gain=255.0 / 128)
+    filt = make_filter(dfe, cuda, cfg.gain)
+    post = post_of(STAGES["all four"], "bilinear")
+    post["median"] = (5, 40.0 / 255.0)                             # the guide is 255 times darker
+    s8, sf = PostStream(dfe, cuda, cfg, filt, K, post), PostStream(dfe, cuda, cfg, filt, K, post)
+    try:
+        for i, (b, f) in enumerate(((b0, f0), (b1, f1), (b0, f0))):
+            r8, rf = s8.push(b, u8_scale=1.0 / 255.0), sf.push(f)
+            assert r8["status"] == rf["status"] == (0 if i == 0 else 1)
+            for k in r8:
+                assert np.array_equal(r8[k], rf[k]), (i, k)
+        assert r8["weight_post"].any() and (r8["fused_flag"] == 3).any()
+    finally:
+        s8.close()
+        sf.close()
+
+
+# -------------------------------------------------------------------------------------------------------------------- 7. Python
+def test_python_post(dfe, cuda):
+    """DepthEstimationAPI(post=...): self.last holds the C results under the documented names, the return tuple is unchanged; a push
+    without imu_tx is refused with post["temporal"]; post=None gives the dict it gave before"""
+    im0, im1, _, K = frames(cuda)
+    cfg, _ = half()
+    filt = make_filter(dfe, cuda)
+    post = post_of(STAGES["all four"])
+    s = PostStream(dfe, cuda, cfg, filt, K, post)
+    try:
+        s.push(im0)
+        want = [s.push(im1), s.push(im0)]
+    finally:
+        s.close()
+    api = dfe.DepthEstimationAPI(cfg.geometry, filt, K, u8Scale=1.0, post=post, **cfg.extra())
+    assert api.nextFrameDepth(im0, imu_tx=1.0) is None and api.last["status"] == 0 and "flow_post" not in api.last
+    names = dict(flow_post="flow_post", weight_post="weight_post", consistent="consistent", depth_post="depth_post", depth_post_conf="depth_post_conf",
+                 depth_fused="depth_fused", depth_fused_weight="fused_weight", depth_fused_flag="fused_flag")
+    for im, w in zip((im1, im0), want):
+        got = api.nextFrameDepth(im, imu_tx=1.0)
+        assert isinstance(got, tuple) and len(got) == 3
+        assert np.array_equal(got[0].cpu().numpy(), w["im_scaled"]) and np.array_equal(got[1].cpu().numpy(), w["flow"][1]) and np.array_equal(got[2].cpu().numpy(), w["mask"])
+        for k, c in names.items():
+            assert np.array_equal(api.last[k].cpu().numpy(), w[c]), k
+        assert np.array_equal(api.last["depth"].cpu().numpy(), w["depth"])
+    with pytest.raises(ValueError):
+        api.nextFrameDepth(im1)
+    api.close()
+    a, b = dfe.DepthEstimationAPI(cfg.geometry, filt, K, post=None, **cfg.extra()), dfe.DepthEstimationAPI(cfg.geometry, filt, K, **cfg.extra())
+    for im in (im0, im1):
+        a.nextFrameDepth(im, imu_tx=1.0)
+        b.nextFrameDepth(im, imu_tx=1.0)
+    assert set(a.last) == set(b.last) == {"status", "im_scaled", "nFound", "nInliers", "yflow", "xflow", "mask", "R", "T", "depth", "depth_conf"}
+    for k in a.last:
+        assert (a.last[k] == b.last[k]) if isinstance(a.last[k], int) else torch.equal(a.last[k], b.last[k]), k
+    a.close()
+    b.close()
+    fo = dfe.DepthEstimationAPI(cfg.geometry, filt, K, post=dict(fill=True), **cfg.extra())   # without imu_tx: no depth of the chain either
+    fo.nextFrameDepth(im0)
+    fo.nextFrameDepth(im1)
+    assert fo.last["status"] == 1 and "depth_post" not in fo.last and "consistent" not in fo.last and fo.last["weight_post"].any()
+    fo.close()
