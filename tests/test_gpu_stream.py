@@ -1,7 +1,8 @@
 """GPU suite (-m gpu), part 12: the stream layer -- dfe_image_scale_f32 / _u8 against the float64 reference written from the definition
 (tests/stream_ref64.py), dfe_mask_paste_mul_f32 against numpy, and the stream object (dfe_stream_*: nextFrameDepth() of
 depth_estimation_api.lua:134-198) against the composition of the public ops it replaces, bit for bit, through the first frame, a result,
-a second result that needs the right frame kept, the bad-image gate and a reset.  Outputs are written into buffers pre-filled with -7
+a second result that needs the right frame kept, the bad-image gate and a reset -- at 240 x 320 frames with square layers and windows, and
+at an asymmetric case with odd plane sizes, other plane counts and other stack depths.  Outputs are written into buffers pre-filled with -7
 that are 64 elements longer than the result: the tail must keep its -7.  Every figure a test bounds is printed before it is asserted."""
 import ctypes as C
 
@@ -130,14 +131,16 @@ GAINS = (0.9, 1.0, 1.1)                                           # the per-chan
 _shared = {}
 
 
-def frames(cuda):
-    """(im0, im1, flat) 3 x 240 x 320 device tensors of the two-view pair and its planted K; made once"""
-    if "frames" not in _shared:
-        tv = tr.two_view_pair()
-        w = torch.tensor(GAINS, device=cuda).reshape(3, 1, 1)
+def frames(cuda, size=(240, 320), planes=3):
+    """(im0, im1, flat, K): C x H x W device tensors of the two-view pair of that size and its planted K; made once per size and plane
+    count.  Three planes: the luminance pair times the per-channel GAINS; one plane: the pair as two_view_pair gives it."""
+    key = ("frames", tuple(size), planes)
+    if key not in _shared:
+        tv = tr.two_view_pair(*size)
+        w = torch.tensor(GAINS if planes == 3 else (1.0,), device=cuda).reshape(planes, 1, 1)
         im0, im1 = (T(tv["im0"], cuda).unsqueeze(0) * w).contiguous(), (T(tv["im1"], cuda).unsqueeze(0) * w).contiguous()
-        _shared["frames"] = (im0, im1, torch.full_like(im0, 100.0), tv["K"])
-    return _shared["frames"]
+        _shared[key] = (im0, im1, torch.full_like(im0, 100.0), tv["K"])
+    return _shared[key]
 
 
 def sfm_kw(**over):
@@ -148,19 +151,39 @@ def sfm_kw(**over):
     return kw
 
 
-def make_filter(dfe, cuda, gain=1.0 / 128):
+def make_filter(dfe, cuda, gain=1.0 / 128, layers=LAYERS, peak=10.0):
     """getFilter with seeded weights; the first layer is scaled down so that frames of 0..255 do not saturate its tanh, and the last one up
-    so that the matching costs differ enough between cells for the soft-max to peak (confidences need a probability above 0.11)"""
-    filt = dfe.getFilter(dict(layers=LAYERS), device=cuda, generator=torch.Generator().manual_seed(11))
+    so that the matching costs differ enough between cells for the soft-max to peak (confidences need a probability above 0.11).  An
+    empty layer list gives None: the raw frames are the features (stream_params' filter=None, nlayers == 0)."""
+    if not layers:
+        return None
+    filt = dfe.getFilter(dict(layers=list(layers)), device=cuda, generator=torch.Generator().manual_seed(11))
     filt.modules[0].weight.mul_(gain)
-    filt.modules[-1].weight.mul_(10.0)
+    filt.modules[-1].weight.mul_(peak)
     return filt
 
 
+def features(filt, x):
+    """the filter stack's output on a frame, in a tensor of its own; filt None: the frame is its own feature map"""
+    return x if filt is None else filt.forward(x).clone()
+
+
 class Config:
-    def __init__(self, hImg, wImg, win, method="max", threshold=None, rectify="features", dist=None, fix=False, ratio=0.2, sfm=None, gain=1.0 / 128):
-        self.geometry = dict(hImg=hImg, wImg=wImg, maxh=win, maxw=win, layers=LAYERS, output_extraction_method=method)
+    """win: the window's side, or (maxh, maxw); layers: geometry.layers, () for raw frames; shape: the camera frames' (C, Hsrc, Wsrc)"""
+
+    def __init__(self, hImg, wImg, win, method="max", threshold=None, rectify="features", dist=None, fix=False, ratio=0.2, sfm=None, gain=1.0 / 128, layers=LAYERS,
+                 shape=(3, 240, 320), peak=10.0):
+        self.peak = peak                                          # the last layer's gain (make_filter)
+        maxh, maxw = win if isinstance(win, tuple) else (win, win)
+        self.geometry = dict(hImg=hImg, wImg=wImg, maxh=maxh, maxw=maxw, layers=list(layers), output_extraction_method=method)
         self.threshold, self.rectify, self.dist, self.fix, self.ratio, self.sfm, self.gain = threshold, rectify, dist, fix, ratio, sfm or sfm_kw(), gain
+        self.layers, self.shape = tuple(layers), tuple(shape)
+
+    def frames(self, cuda):
+        return frames(cuda, self.shape[1:], self.shape[0])
+
+    def filter(self, dfe, cuda):
+        return make_filter(dfe, cuda, self.gain, self.layers, self.peak)
 
     def extra(self):
         return dict(self.sfm, rectify=self.rectify, threshold=self.threshold, fixMaskOffset=self.fix, minInlierRatio=self.ratio)
@@ -172,9 +195,9 @@ OUTPUTS = ("im_scaled", "flow", "mask", "depth", "dconf")         # the device o
 class Stream:
     """the C ABI driven directly, every device output in a guarded buffer"""
 
-    def __init__(self, dfe, cuda, cfg, filt, K, shape=(3, 240, 320), tweak=None):
+    def __init__(self, dfe, cuda, cfg, filt, K, tweak=None):
         self.dfe, self.cuda, self.ctx = dfe, cuda, dfe.get_ctx(0)
-        self.p, self.keep = dfe.stream.stream_params(cfg.geometry, filt, K, cfg.dist, *shape, **cfg.extra())
+        self.p, self.keep = dfe.stream.stream_params(cfg.geometry, filt, K, cfg.dist, *cfg.shape, **cfg.extra())
         if tweak:                                                 # (a value the Python layer would refuse on the host)
             tweak(self.p)
         self.h = C.c_void_p()
@@ -210,7 +233,7 @@ class Stream:
         self.dfe.lib().dfe_stream_destroy(self.h)
 
 
-def composition(dfe, cfg, filt, K, prev, cur):
+def composition(dfe, cfg, filt, K, prev, cur, imu_tx=1.0):
     """what a caller had to stitch before the stream existed, from the public ops, in the reference's order"""
     g = cfg.geometry
     h, w = g["hImg"], g["wImg"]
@@ -221,12 +244,12 @@ def composition(dfe, cfg, filt, K, prev, cur):
     Ks = np.array(K, np.float64).copy()
     Ks[0] *= w / prev.shape[2]
     Ks[1] *= h / prev.shape[1]
-    fcur = filt.forward(cs).clone()
+    fcur = features(filt, cs)
     if cfg.rectify == "features":
-        wprev, mask = dfe.sfm2.removeEgoMotion(filt.forward(ps).clone(), Ks, R, inverse=True)
+        wprev, mask = dfe.sfm2.removeEgoMotion(features(filt, ps), Ks, R, inverse=True)
     else:
         wimg, mask = dfe.sfm2.removeEgoMotion(ps, Ks, R, inverse=True)
-        wprev = filt.forward(wimg).clone()
+        wprev = features(filt, wimg)
     model = dfe.getModel(dict(g, prefilter=True), True, True, device=cs.device)
     po = model.forwardFlow([wprev, fcur], cfg.threshold)
     full, fc = po["full"], po["full_confidences"]
@@ -239,7 +262,7 @@ def composition(dfe, cfg, filt, K, prev, cur):
     mask2 = torch.zeros((h, w), device=cs.device)
     mask2[oy:oy + mask.shape[0], ox:ox + mask.shape[1]] = mask
     mask2 = mask2 * fc
-    depth, dconf = dfe.computeDepthMapFromFlow(full[1], mask2, 1.0)
+    depth, dconf = dfe.computeDepthMapFromFlow(full[1], mask2, imu_tx)
     return dict(status=1, nf=nf, ni=ni, R=R.numpy(), T=Tt.numpy(), im_scaled=cs.cpu().numpy(), flow=full.cpu().numpy(), mask=mask2.cpu().numpy(),
                 depth=depth.cpu().numpy(), dconf=dconf.cpu().numpy())
 
@@ -254,21 +277,24 @@ def assert_same(got, want, what):
 FUSED = ("feat_matching_flat_kernel+softmax", "feat_matching_flat_mean_kernel")   # the matcher with the per-pixel tail in its epilogue
 
 
-def run_sequence(dfe, cuda, cfg, fused=False):
-    im0, im1, _, K = frames(cuda)
-    filt = make_filter(dfe, cuda, cfg.gain)
+def run_sequence(dfe, cuda, cfg, fused=False, imu=(1.0, 1.0, 1.0), frame_scale=1.0):
+    """[im0, im1, im0] (times frame_scale) through a stream of cfg, push i with imu_tx = imu[i]; pushes 2 and 3 against the composition"""
+    im0, im1, _, K = cfg.frames(cuda)
+    if frame_scale != 1.0:
+        im0, im1 = im0 * np.float32(frame_scale), im1 * np.float32(frame_scale)
+    filt = cfg.filter(dfe, cuda)
     s = Stream(dfe, cuda, cfg, filt, K)
     try:
-        r1 = s.push(im0)
+        r1 = s.push(im0, imu_tx=imu[0])
         assert r1["status"] == 0 and (r1["nf"], r1["ni"]) == (0, 0)
         assert np.array_equal(r1["im_scaled"], dfe.imageScale(im0 if cfg.dist is None else dfe.sfm2.undistortImage(im0, K, cfg.dist), s.p.wImg, s.p.hImg).cpu().numpy())
-        r2 = s.push(im1)
+        r2 = s.push(im1, imu_tx=imu[1])
         assert (dfe.get_ctx(0).last_kernel() in FUSED) == fused, dfe.get_ctx(0).last_kernel()   # (nothing behind the matcher's step names a kernel)
-        r3 = s.push(im0)
+        r3 = s.push(im0, imu_tx=imu[2])
     finally:
         s.close()
-    assert_same(r2, composition(dfe, cfg, filt, K, im0, im1), "push 2")
-    assert_same(r3, composition(dfe, cfg, filt, K, im1, im0), "push 3 (im1 -> im0: the stream must have kept im1 and ITS features)")
+    assert_same(r2, composition(dfe, cfg, filt, K, im0, im1, imu[1]), "push 2")
+    assert_same(r3, composition(dfe, cfg, filt, K, im1, im0, imu[2]), "push 3 (im1 -> im0: the stream must have kept im1 and ITS features)")
     assert not np.array_equal(r2["flow"], r3["flow"])
     print("stream %s %s: push 2 %d / %d inliers, push 3 %d / %d; mask keeps %d and %d pixels" % (cfg.geometry["output_extraction_method"], cfg.rectify, r2["ni"], r2["nf"],
                                                                                               r3["ni"], r3["nf"], int(r2["mask"].sum()), int(r3["mask"].sum())))
@@ -307,17 +333,107 @@ def test_stream_equals_composition_full_size(dfe, cuda, method):
     run_sequence(dfe, cuda, Config(240, 320, 17, method=method), fused=True)
 
 
-@pytest.mark.parametrize("dist", [None, ARDRONE_DIST], ids=["as it is", "undistorted"])
-def test_stream_u8_push_and_reset(dfe, cuda, dist):
-    """bytes round(255 frame) with scale 1 / 255 (frame in 0..1) give what the f32 push on float32(byte) x float32(1 / 255) gives, bit for
-    bit -- converted straight into the frame's slot, or with `has_dist` into the staging buffer in front of the undistortion; after a
-    reset a push returns status 0 again, and the pair after it is computed from the frames pushed after it.  The frames are 255 times
-    darker than the other tests', so the tracker's eigenvalue floor goes down by 255^2, and the first layer's gain up by 255."""
-    im0, im1, _, K = frames(cuda)
+# ---- off the 240 x 320, square-window case.  In cases A and B x and y are interchangeable (hImg - H1 == wImg - W1, so ix == iy and ox == oy),
+# every plane is a multiple of 256 floats, C is 3 and the stack has two layers.  The asymmetric case: camera frames 3 x 149 x 203 (90741
+# bytes, odd), geometry 67 x 93 (n = 6231, odd; scale ratios 2.22 and 2.18), a stack whose kernel is 7 rows by 9 columns and a window of
+# 10 rows by 17 columns.  By the reference's rules (depth_estimation_api.lua:172-179; tests/test_stream_cpu.py pins them on the host):
+# Hf, Wf = 61, 85; H1, W1 = 52, 69; oy, ox = 2, 3 (3, 4 with fix_mask_offset; 0, 0 in image mode); ix, iy = 12, 8.
+ASYM_SHAPE, ASYM_LAYERS, ASYM_WIN = (3, 149, 203), ((3, 3, 5, 4), (4, 7, 3, 4)), (10, 17)
+ASYM_SHAPES = dict(Hf=61, Wf=85, H1=52, W1=69, oy=2, ox=3, ix=12, iy=8)
+MONO_SHAPE, MONO_LAYERS = (1, 149, 203), ((1, 5, 5, 4), (4, 5, 5, 4))
+# The last layer's gain at this geometry is 40, not make_filter's 10.  With 10 the soft-max over the window's 170 cells stays flat on these
+# frames: no probability passes 0.11 (the composition's thresholded mask is empty), and the 'mean' flows stay under 2.5 px, so that every
+# depth is the far value 100 whatever imu_tx is.  With 40 the thresholded mask keeps about 2550 pixels, the 'mean' flows reach 6 to 7.6 px
+# and are not integers (from 80 on they are: the soft-max is one-hot), and some 550 to 1000 depths lie below 100.
+ASYM_PEAK = 40.0
+
+
+def asym(**kw):
+    kw = dict(dict(layers=ASYM_LAYERS, shape=ASYM_SHAPE, peak=ASYM_PEAK), **kw)
+    return Config(67, 93, ASYM_WIN, **kw)
+
+
+CASES_ASYM = [
+    ("max features", dict(method="max"), dict()),
+    ("max threshold features fixed offset", dict(method="max", threshold=0.11, fix=True), dict(oy=3, ox=4)),
+    ("mean image", dict(method="mean", rectify="image"), dict(oy=0, ox=0)),
+    ("mean features undistorted", dict(method="mean", dist=ARDRONE_DIST), dict()),
+]
+
+
+@pytest.mark.parametrize("name,kw,off", CASES_ASYM, ids=[c[0] for c in CASES_ASYM])
+def test_stream_equals_composition_asymmetric(dfe, cuda, name, kw, off):
+    """The asymmetric case: no two of the x / y pairs (Hf, Wf), (H1, W1), (oy, ox), (ix, iy) are equal, so an exchanged pair in the
+    enlargeMask or the paste call changes the mask; n is odd, so the second flow plane starts at an odd element."""
+    cfg = asym(**kw)
+    p, keep = dfe.stream.stream_params(cfg.geometry, cfg.filter(dfe, cuda), cfg.frames(cuda)[3], cfg.dist, *cfg.shape, **cfg.extra())
+    assert dfe.stream.stream_shapes(p) == dict(ASYM_SHAPES, **off)
+    run_sequence(dfe, cuda, cfg)
+
+
+@pytest.mark.parametrize("rectify", ["features", "image"])
+def test_stream_one_plane(dfe, cuda, rectify):
+    """C = 1: the luminance pair as two_view_pair gives it, a stack whose first layer reads one plane, the asymmetric window"""
+    run_sequence(dfe, cuda, asym(method="mean", rectify=rectify, layers=MONO_LAYERS, shape=MONO_SHAPE))
+
+
+# Raw frames are matched pixel by pixel on their 0..255 values.  RAW_SCALE multiplies the frames (and RAW_SCALE^2 the tracker's eigenvalue
+# floor, as in test_stream_u8_push_and_reset): 1.0 unless the soft-max saturated on raw bytes and left the composition's mask empty
+RAW_SCALE = 1.0
+RAW_CASES = [(r, planes, m) for r in ("image", "features") for planes in (3, 1) for m in ("max", "mean")]
+
+
+def raw_config(rectify, planes, method):
+    return Config(67, 93, ASYM_WIN, method=method, rectify=rectify, fix=rectify == "features", layers=(), shape=(planes, 149, 203),
+                  sfm=sfm_kw(trackerMinEig=tr.ROUTE["min_eig"] * RAW_SCALE ** 2))
+
+
+@pytest.mark.parametrize("rectify,planes,method", RAW_CASES, ids=["%s C=%d %s" % c for c in RAW_CASES])
+def test_stream_raw_frames(dfe, cuda, rectify, planes, method):
+    """filter=None, nlayers == 0: the scaled frame is its own feature map (feat[i] is scaled[i]), in image mode the matcher reads the
+    rectified frame itself, and the features' offset is zero, which the reference's offset (-1) cannot express: fix_mask_offset"""
+    cfg = raw_config(rectify, planes, method)
+    assert cfg.filter(dfe, cuda) is None
+    run_sequence(dfe, cuda, cfg, frame_scale=RAW_SCALE)
+
+
+DEPTHS = [("one layer", ((3, 5, 5, 4),)), ("three layers", ((3, 3, 3, 4), (4, 3, 3, 4), (4, 3, 3, 6)))]
+
+
+@pytest.mark.parametrize("rectify", ["features", "image"])
+@pytest.mark.parametrize("name,layers", DEPTHS, ids=[d[0] for d in DEPTHS])
+def test_stream_stack_depths(dfe, cuda, name, layers, rectify):
+    """one layer: the stack writes straight into the feature map and the stream carves no intermediate planes; three layers: both of
+    them are in use, and the last layer's plane count (6) is not the intermediate ones' (4)"""
+    run_sequence(dfe, cuda, asym(method="mean", rectify=rectify, layers=layers))
+
+
+def test_stream_three_wide_layers_full_size(dfe, cuda):
+    """Three layers of ten planes at 240 x 320 (case B's frames, window and fused matcher).  At 67 x 93 a layer is a few dozen blocks that
+    all stage their input before any of them stores, so a stack that read and wrote ONE intermediate buffer would still come out right;
+    here the middle layer is 900 blocks of the batched convolution, each holding 54 KB of LDS, more than the device keeps resident at
+    once, and the later ones would read rows that the earlier ones have overwritten.  ('max': behind these 3 x 3 layers the soft-max is
+    too flat for 'mean' to call any pixel confident, and the composition's mask would be empty.)"""
+    run_sequence(dfe, cuda, Config(240, 320, 17, method="max", layers=((3, 3, 3, 10), (10, 3, 3, 10), (10, 3, 3, 4))), fused=True)
+
+
+def test_stream_imu_tx(dfe, cuda):
+    """imu_tx = 1.0, 0.5 and 2.0 on the three pushes: each pair's depth is the composition's with that pair's value, and the value
+    matters (on the composition alone: the depth of push 2 at 0.5 is not the depth at 1.0)"""
+    cfg = asym(method="mean")
+    im0, im1, _, K = cfg.frames(cuda)
+    filt = cfg.filter(dfe, cuda)
+    a, b = composition(dfe, cfg, filt, K, im0, im1, 0.5), composition(dfe, cfg, filt, K, im0, im1, 1.0)
+    assert a["dconf"].any() and not np.array_equal(a["depth"], b["depth"])
+    run_sequence(dfe, cuda, cfg, imu=(1.0, 0.5, 2.0))
+
+
+def u8_push_and_reset(dfe, cuda, cfg):
+    """the rule of test_stream_u8_push_and_reset on cfg's frames"""
+    im0, im1, _, K = cfg.frames(cuda)
     b0, b1 = (im0 / np.float32(GAINS[2])).round().clamp(0, 255).to(torch.uint8), (im1 / np.float32(GAINS[2])).round().clamp(0, 255).to(torch.uint8)
     f0, f1 = b0.to(torch.float32) * np.float32(1.0 / 255.0), b1.to(torch.float32) * np.float32(1.0 / 255.0)
-    cfg = Config(120, 160, 16, method="mean", dist=dist, sfm=sfm_kw(trackerMinEig=tr.ROUTE["min_eig"] / 255.0 ** 2), gain=255.0 / 128)
-    filt = make_filter(dfe, cuda, cfg.gain)
+    filt = cfg.filter(dfe, cuda)
     s8, sf = Stream(dfe, cuda, cfg, filt, K), Stream(dfe, cuda, cfg, filt, K)
     try:
         for i, (b, f) in enumerate(((b0, f0), (b1, f1), (b0, f0))):
@@ -334,6 +450,23 @@ def test_stream_u8_push_and_reset(dfe, cuda, dist):
     finally:
         s8.close()
         sf.close()
+
+
+@pytest.mark.parametrize("dist", [None, ARDRONE_DIST], ids=["as it is", "undistorted"])
+def test_stream_u8_push_odd_byte_count(dfe, cuda, dist):
+    """the rule of test_stream_u8_push_and_reset on the asymmetric case's frames: 3 x 149 x 203 = 90741 bytes, so the conversion's last
+    group of bytes is a partial one"""
+    assert int(np.prod(ASYM_SHAPE)) % 2 == 1
+    u8_push_and_reset(dfe, cuda, asym(method="mean", dist=dist, sfm=sfm_kw(trackerMinEig=tr.ROUTE["min_eig"] / 255.0 ** 2), gain=255.0 / 128))
+
+
+@pytest.mark.parametrize("dist", [None, ARDRONE_DIST], ids=["as it is", "undistorted"])
+def test_stream_u8_push_and_reset(dfe, cuda, dist):
+    """bytes round(255 frame) with scale 1 / 255 (frame in 0..1) give what the f32 push on float32(byte) x float32(1 / 255) gives, bit for
+    bit -- converted straight into the frame's slot, or with `has_dist` into the staging buffer in front of the undistortion; after a
+    reset a push returns status 0 again, and the pair after it is computed from the frames pushed after it.  The frames are 255 times
+    darker than the other tests', so the tracker's eigenvalue floor goes down by 255^2, and the first layer's gain up by 255."""
+    u8_push_and_reset(dfe, cuda, Config(120, 160, 16, method="mean", dist=dist, sfm=sfm_kw(trackerMinEig=tr.ROUTE["min_eig"] / 255.0 ** 2), gain=255.0 / 128))
 
 
 SUBSETS = [("depth",), ("dconf",), ("mask",), ("flow",), ("flow", "depth"), ("mask", "dconf"), ()]

@@ -1,8 +1,9 @@
 """GPU suite (-m gpu), part 12b: the session's post-processing chain (dfe_stream_create_post, dfe_stream_push_post_*: consistency, fill,
 guided median, depth, temporal fusion inside the stream object) against the composition of the public Python ops it replaces, bit for
 bit, on the frames of tests/test_gpu_stream.py: 3 x 240 x 320 views of tracker_ref64.two_view_pair, the sequence [im0, im1, im0],
-imu_tx = 1.  Outputs are written into buffers pre-filled with -7 that are 64 elements longer than the result: the tail must keep its -7,
-and an output that a push must not write keeps it everywhere."""
+imu_tx = 1 -- and, in section 1b, off that point: 3 x 149 x 203 and 1 x 149 x 203 views at geometry 67 x 93 with a 7 x 9 stack and a
+10 x 17 window, other stage sets, other temporal parameters, other imu_tx.  Outputs are written into buffers pre-filled with -7 that are
+64 elements longer than the result: the tail must keep its -7, and an output that a push must not write keeps it everywhere."""
 import ctypes as C
 
 import numpy as np
@@ -11,7 +12,9 @@ import torch
 
 from tests import tracker_ref64 as tr
 from tests.egomotion_cases import ARDRONE_DIST
-from tests.test_gpu_stream import FILL, GAINS, OUTPUTS, Config, Stream, composition, frames, guarded, make_filter, sfm_kw, unguard
+from tests.consistency_ref64 import consistency_ref
+from tests.test_gpu_stream import (FILL, GAINS, MONO_LAYERS, MONO_SHAPE, OUTPUTS, RAW_SCALE, Config, Stream, asym, composition, features, frames, guarded, make_filter,
+                                   raw_config, sfm_kw, unguard)
 
 pytestmark = pytest.mark.gpu
 
@@ -42,9 +45,9 @@ def post_of(stages, splat="nearest"):
 class PostStream:
     """dfe_stream_create_post and dfe_stream_push_post_* driven directly, every device output in a guarded buffer"""
 
-    def __init__(self, dfe, cuda, cfg, filt, K, post, shape=(3, 240, 320)):
+    def __init__(self, dfe, cuda, cfg, filt, K, post):
         self.dfe, self.cuda, self.ctx = dfe, cuda, dfe.get_ctx(0)
-        self.p, self.keep = dfe.stream.stream_params(cfg.geometry, filt, K, cfg.dist, *shape, **cfg.extra())
+        self.p, self.keep = dfe.stream.stream_params(cfg.geometry, filt, K, cfg.dist, *cfg.shape, **cfg.extra())
         self.post = dfe.stream.stream_post(post)
         self.h = C.c_void_p()
         self.ctx.check(dfe.lib().dfe_stream_create_post(self.ctx.handle, C.byref(self.p), C.byref(self.post), C.byref(self.h)))
@@ -115,9 +118,9 @@ def pair_parts(dfe, cfg, key, filt, K, prev, cur):
         Ks[0] *= w / prev.shape[2]
         Ks[1] *= h / prev.shape[1]
         R = torch.from_numpy(base["R"].copy())
-        fcur = filt.forward(cs).clone()
+        fcur = features(filt, cs)
         guide = dfe.sfm2.removeEgoMotion(ps, Ks, R, inverse=True)[0]
-        wprev = dfe.sfm2.removeEgoMotion(filt.forward(ps).clone(), Ks, R, inverse=True)[0] if cfg.rectify == "features" else filt.forward(guide).clone()
+        wprev = dfe.sfm2.removeEgoMotion(features(filt, ps), Ks, R, inverse=True)[0] if cfg.rectify == "features" else features(filt, guide)
         bw = dfe.getModel(dict(g, prefilter=True), True, True, device=cs.device).forwardFlow([fcur, wprev], cfg.threshold)["full"].clone()
         H1, W1 = fcur.shape[1] - g["maxh"] + 1, fcur.shape[2] - g["maxw"] + 1
         _cache[key] = dict(base=base, Ks=Ks, R=R, guide=guide, bw=bw, region=((h - H1) // 2, (w - W1) // 2, H1, W1), flow=torch.from_numpy(base["flow"]).to(cs.device),
@@ -125,7 +128,7 @@ def pair_parts(dfe, cfg, key, filt, K, prev, cur):
     return _cache[key]
 
 
-def post_composition(dfe, parts, post, tf):
+def post_composition(dfe, parts, post, tf, imu_tx=1.0):
     """the chain stitched from the public Python ops on a pair's plain results; tf: the TemporalFilter that carries the state, or None"""
     flow, mask, Rg = parts["flow"], parts["mask"], parts["region"]
     out, t = {}, {}
@@ -146,8 +149,8 @@ def post_composition(dfe, parts, post, tf):
         t.update(filled=filled)
     if post.get("median"):
         k, sigma = post["median"]
-        flow_post, weight_post = dfe.weightedMedian(src, wgt, parts["guide"], k, sigma, Rg)
-    depth, dconf = dfe.computeDepthMapFromFlow(flow_post[1], weight_post, 1.0)
+        flow_post, weight_post = dfe.weightedMedian(src, wgt, parts["guide"] if sigma > 0 else None, k, sigma, Rg)   # (sigma <= 0: unguided)
+    depth, dconf = dfe.computeDepthMapFromFlow(flow_post[1], weight_post, imu_tx)
     out.update(flow_post=flow_post, weight_post=weight_post, depth_post=depth, depth_post_conf=dconf)
     if tf is not None:
         fused, fw, flag = tf.push(depth[None], dconf, flow_post, rectify=(parts["Ks"], parts["R"]))
@@ -158,21 +161,34 @@ def post_composition(dfe, parts, post, tf):
     return res
 
 
-def sequence_composition(dfe, cuda, cfg, ckey, filt, post, seq=("01", "10")):
-    """the chain's composition over the pairs of [im0, im1, im0, ...]: a list of (plain, post) results, the temporal state carried"""
-    im0, im1, _, K = frames(cuda)
+def scaled_frames(cuda, cfg, frame_scale=1.0):
+    im0, im1, flat, K = cfg.frames(cuda)
+    if frame_scale != 1.0:
+        im0, im1 = im0 * np.float32(frame_scale), im1 * np.float32(frame_scale)
+    return im0, im1, flat, K
+
+
+def sequence_composition(dfe, cuda, cfg, ckey, filt, post, seq=("01", "10"), imu=None, frame_scale=1.0):
+    """the chain's composition over the pairs of [im0, im1, im0, ...]: a list of (plain, post) results, the temporal state carried;
+    imu: the pairs' imu_tx (1 by default); ckey names cfg, its frames and frame_scale in the cache"""
+    im0, im1, _, K = scaled_frames(cuda, cfg, frame_scale)
     ims = {"0": im0, "1": im1}
     tf = dfe.TemporalFilter(**post["temporal"]) if "temporal" in post else None
     res = []
-    for pair in seq:
+    for i, pair in enumerate(seq):
         parts = pair_parts(dfe, cfg, ckey + (pair,), filt, K, ims[pair[0]], ims[pair[1]])
-        res.append((parts["base"], post_composition(dfe, parts, post, tf)))
+        base, tx = parts["base"], 1.0 if imu is None else imu[i]
+        if tx != 1.0:                                              # the plain depth of this pair at its own imu_tx
+            depth, dconf = dfe.computeDepthMapFromFlow(parts["flow"][1], parts["mask"], tx)
+            base = dict(base, depth=depth.cpu().numpy(), dconf=dconf.cpu().numpy())
+        res.append((base, post_composition(dfe, parts, post, tf, tx)))
     return res
 
 
 def assert_post_same(got, want, what):
     base, post = want
     assert got["status"] == 1 and (got["nf"], got["ni"]) == (base["nf"], base["ni"]), what
+    assert base["mask"].any() and base["flow"].any() and base["dconf"].any(), "%s: the composition's result is empty" % what
     for k in PLAIN:
         assert np.array_equal(got[k], base[k]), "%s: plain output %s differs from the composition (%d elements)" % (what, k, (got[k] != base[k]).sum())
     for k in POST_OUT:
@@ -182,17 +198,17 @@ def assert_post_same(got, want, what):
             assert (got[k] == FILL).all(), "%s: %s was written though its stage is off" % (what, k)
 
 
-def run_post_sequence(dfe, cuda, cfg, ckey, post):
-    im0, im1, _, K = frames(cuda)
-    filt = make_filter(dfe, cuda, cfg.gain)
+def run_post_sequence(dfe, cuda, cfg, ckey, post, imu=(1.0, 1.0, 1.0), frame_scale=1.0):
+    im0, im1, _, K = scaled_frames(cuda, cfg, frame_scale)
+    filt = cfg.filter(dfe, cuda)
     s = PostStream(dfe, cuda, cfg, filt, K, post)
     try:
-        r1 = s.push(im0)
+        r1 = s.push(im0, imu_tx=imu[0])
         assert r1["status"] == 0
-        r2, r3 = s.push(im1), s.push(im0)
+        r2, r3 = s.push(im1, imu_tx=imu[1]), s.push(im0, imu_tx=imu[2])
     finally:
         s.close()
-    w2, w3 = sequence_composition(dfe, cuda, cfg, ckey, filt, post)
+    w2, w3 = sequence_composition(dfe, cuda, cfg, ckey, filt, post, imu=imu[1:], frame_scale=frame_scale)
     assert_post_same(r2, w2, "push 2")
     assert_post_same(r3, w3, "push 3 (the carried state: warp, rotation, fuse)")
     return (r2, r3), (w2, w3)
@@ -235,6 +251,174 @@ def test_post_plain_outputs_equal_a_plain_stream(dfe, cuda):
     finally:
         a.close()
         b.close()
+
+
+# ------------------------------------------------------------------------------ 1b. off the 240 x 320, square-window, unit-gain case
+# The asymmetric case of tests/test_gpu_stream.py: 3 x 149 x 203 frames, geometry 67 x 93 (n = 6231, odd: every second plane the chain
+# addresses as base + n starts at an odd element), a 7 x 9 stack, a 10 x 17 window.  The chain's region is the matcher's output rectangle,
+# (floor((67 - 52) / 2), floor((93 - 69) / 2), 52, 69): y0 = 7 is not x0 = 12, and not iy = 8 either.
+ASYM_REGION = (7, 12, 52, 69)
+# The tolerances at this geometry, from what test_composition_is_not_degenerate_asymmetric prints: |flow| <= 8.00 for 'max' (integers) and
+# <= 7.60 / 7.67 for 'mean' (features / image), the flows of the 240 x 320 pair divided by 2.2.  With a forward-backward residual of 1 px
+# `consistent` keeps 2246 / 2266 of the region's 3588 pixels for 'max' and 943 / 957 for 'mean' (push 3; the rest is rejected), the fill
+# finds 1464 to 2925 holes and the median moves 3757 to 6940 flow elements.  Depths are |x - 46| / |mode| with integer modes of at most 8,
+# at most 100; with 2 units of depth push 3 fuses 1700 to 1897 pixels in agreement (flag 3) and resets 1606 to 1805 (flag 5): the same
+# values as at half size separate the two populations here.
+ASYM_TOL_FB, ASYM_T_TOL = TOL_FB, T_TOL
+ASYM_ALL = dict(consistency=ASYM_TOL_FB, fill=True, median=(5, 40.0), temporal=dict(TEMPORAL, tol=ASYM_T_TOL))
+
+
+def asym_cfg(method="mean", rectify="features", **kw):
+    return asym(method=method, rectify=rectify, **kw), ("asym", method, rectify) + tuple(sorted(kw.items()))
+
+
+def region_mask(shape, region):
+    y0, x0, Ho, Wo = region
+    inR = np.zeros(shape, bool)
+    inR[y0:y0 + Ho, x0:x0 + Wo] = True
+    return inR
+
+
+def assert_consistent_is_the_reference(r, region, tol, what):
+    """`consistent` of a push against tests/consistency_ref64 on the push's own flow and flow_bw over `region`, by the rules of
+    test_gpu_consistency.py: integer flows ('max'; residuals that meet the tolerance exactly are the common case) give the reference's
+    mask bit for bit, sub-pixel flows give it outside the doubt band |err - tol| <= 1e-3, which may hold 1 % of the pixels; zero outside
+    the region"""
+    em, ee = consistency_ref(r["flow"], r["flow_bw"], region, tol)
+    inR = region_mask(em.shape, region)
+    assert not r["consistent"][~inR].any(), "%s: consistent is not zero outside %s" % (what, region)
+    assert np.isin(r["consistent"], (0.0, 1.0)).all()
+    integer = all(np.array_equal(r[k], np.rint(r[k])) for k in ("flow", "flow_bw"))
+    sure = np.ones(em.shape, bool) if integer else ~(np.abs(ee - tol) <= 1e-3)
+    print("%s: the reference keeps %d of R and rejects %d; %d pixels in the doubt band" % (what, int(em[inR].sum()), int((em[inR] == 0).sum()), int((~sure).sum())))
+    assert np.count_nonzero(~sure) <= 0.01 * sure.size
+    assert np.array_equal(r["consistent"][sure], em[sure]), "%s: consistent differs from the float64 reference over %s in %d pixels" % (
+        what, region, np.count_nonzero(r["consistent"][sure] != em[sure]))
+    assert em[inR].any() and not em[inR].all()
+
+
+CASES_ASYM = [("nearest", r, m) for r in ("features", "image") for m in ("max", "mean")] + [("bilinear", r, "mean") for r in ("features", "image")]
+
+
+@pytest.mark.parametrize("splat,rectify,method", CASES_ASYM, ids=["%s, %s, %s" % c for c in CASES_ASYM])
+def test_post_equals_composition_asymmetric(dfe, cuda, splat, rectify, method):
+    """All four stages at the asymmetric case.  The region the composition derives from the shapes is (7, 12, 52, 69); the four operators
+    that take (y0, x0, Ho, Wo) get it in that order, or a plane differs.  Independent of the composition: `consistent` is the float64
+    reference's mask on the push's own two flows over that region, and zero outside it."""
+    cfg, ckey = asym_cfg(method, rectify)
+    (r2, r3), (w2, w3) = run_post_sequence(dfe, cuda, cfg, ckey, post_of(ASYM_ALL, splat))
+    assert w2[1]["_region"] == ASYM_REGION and w3[1]["_region"] == ASYM_REGION
+    for r, what in ((r2, "push 2"), (r3, "push 3")):
+        assert_consistent_is_the_reference(r, ASYM_REGION, ASYM_TOL_FB, "%s %s %s" % (rectify, method, what))
+
+
+@pytest.mark.parametrize("rectify", ["features", "image"])
+def test_post_consistency_only_asymmetric(dfe, cuda, rectify):
+    """consistency alone (the `mc` plane): weight_post is float32(mask) * consistent computed in numpy, flow_post is flow, and
+    `consistent` is the float64 reference's over (7, 12, 52, 69)"""
+    cfg, ckey = asym_cfg("mean", rectify)
+    (r2, r3), _ = run_post_sequence(dfe, cuda, cfg, ckey, post_of(dict(consistency=ASYM_TOL_FB)))
+    for r, what in ((r2, "push 2"), (r3, "push 3")):
+        assert_consistent_is_the_reference(r, ASYM_REGION, ASYM_TOL_FB, "consistency only, %s %s" % (rectify, what))
+        assert np.array_equal(r["weight_post"], np.float32(r["mask"]) * r["consistent"]) and r["weight_post"].any()
+        assert np.array_equal(r["flow_post"], r["flow"])
+
+
+@pytest.mark.parametrize("method", ["max", "mean"])
+@pytest.mark.parametrize("rectify", ["features", "image"])
+def test_composition_is_not_degenerate_asymmetric(dfe, cuda, rectify, method):
+    """test_composition_is_not_degenerate's conditions at the asymmetric case, on the composition alone: both pairs give a mask, a flow
+    and a depth confidence, `consistent` keeps some pixels of the region and rejects some, at least one hole is filled, the median moves
+    the flow inside the region, and push 3 has flag 3 somewhere"""
+    cfg, ckey = asym_cfg(method, rectify)
+    filt = cfg.filter(dfe, cuda)
+    for splat in ("nearest", "bilinear"):
+        (b2, w2), (b3, w3) = sequence_composition(dfe, cuda, cfg, ckey, filt, post_of(ASYM_ALL, splat))
+        assert w2["_region"] == ASYM_REGION
+        inR = region_mask(b2["mask"].shape, ASYM_REGION)
+        for w, b in ((w2, b2), (w3, b3)):
+            assert b["mask"].any() and b["flow"].any() and b["dconf"].any()
+            kept, rej = int((w["consistent"][inR] == 1).sum()), int((w["consistent"][inR] == 0).sum())
+            holes = int(((w["_filled"] == 1) & (w["_kept"] == 0)).sum())
+            moved = int((w["flow_post"] != b["flow"])[:, inR].sum())
+            flags = {int(f): int((w["fused_flag"] == f).sum()) for f in np.unique(w["fused_flag"])}
+            print("asymmetric %s %s %s: %d / %d inliers; |flow| <= %.2f; depth_post <= %.1f; consistent keeps %d of R, rejects %d; %d holes filled; flow_post differs "
+                  "from flow in %d elements of R; flags %s" % (rectify, method, splat, b["ni"], b["nf"], np.abs(b["flow"]).max(), w["depth_post"].max(), kept, rej,
+                                                               holes, moved, flags))
+            assert kept > 0 and rej > 0 and holes > 0 and moved > 0
+        assert set(np.unique(w2["fused_flag"])) <= {0.0, 2.0}
+        assert (w3["fused_flag"] == 3).any()
+
+
+# the stage sets whose buffers dfe_stream_post_run selects differently from STAGES': the median behind the consistency without the fill
+# (src = flow, wsrc = kept), the fusion on the consistency-only plane, the fusion alone and behind the fill, a median without its guide
+# (sigma <= 0; the chain still makes the guide), a bounded fill in front of a 3 x 3 median
+STAGES_MORE = {
+    "consistency + median": dict(consistency=TOL_FB, median=(5, 40.0)),
+    "consistency + temporal": dict(consistency=TOL_FB, temporal=TEMPORAL),
+    "temporal": dict(temporal=TEMPORAL),
+    "fill + temporal": dict(fill=True, temporal=TEMPORAL),
+    "median unguided": dict(median=(7, 0.0)),
+    "fill 1 level + median 3": dict(fill=1, median=(3, 40.0)),
+}
+CASES_MORE = [(st, r) for st in STAGES_MORE for r in ("features", "image")]
+
+
+@pytest.mark.parametrize("stages,rectify", CASES_MORE, ids=["%s, %s" % c for c in CASES_MORE])
+def test_post_more_stage_sets_half_size(dfe, cuda, stages, rectify):
+    cfg, ckey = half("mean", rectify)
+    (r2, r3), (w2, w3) = run_post_sequence(dfe, cuda, cfg, ckey, post_of(STAGES_MORE[stages]))
+    assert r3["weight_post"].any() and r3["depth_post_conf"].any()
+    if "temporal" in STAGES_MORE[stages]:
+        assert (w3[1]["fused_flag"] == 3).any()                    # the carried state is in use
+    if stages == "median unguided":                                # (on the composition alone) the guide does matter where it is used
+        guided = sequence_composition(dfe, cuda, cfg, ckey, cfg.filter(dfe, cuda), post_of(dict(median=(7, 40.0))))[0][1]
+        assert not np.array_equal(guided["flow_post"], w2[1]["flow_post"])
+
+
+# gain, bias and decay off their identity values, and the NULL-pointer paths of the warp and the splat (t_has_gain / t_has_bias == 0)
+T_PARAMS = [("gain bias decay 1", dict(gain=(0.9,), bias=(0.5,), decay=1.0)), ("gain alone", dict(gain=(0.9,), bias=None)), ("bias alone", dict(gain=None, bias=(0.5,))),
+            ("neither", dict(gain=None, bias=None))]
+
+
+@pytest.mark.parametrize("splat", ["nearest", "bilinear"])
+@pytest.mark.parametrize("name,tkw", T_PARAMS, ids=[t[0] for t in T_PARAMS])
+def test_post_temporal_parameters(dfe, cuda, name, tkw, splat):
+    cfg, ckey = half()
+    post = post_of(dict(STAGES["all four"], temporal=dict(TEMPORAL, **tkw)), splat)
+    (r2, r3), (w2, w3) = run_post_sequence(dfe, cuda, cfg, ckey, post)
+    assert (w3[1]["fused_flag"] >= 1).any()
+    if name == "gain bias decay 1":                                # (on the composition alone) the values matter: not the identity's result
+        ident = post_of(dict(STAGES["all four"], temporal=dict(TEMPORAL, gain=(1.0,), bias=(0.0,), decay=1.0)), splat)
+        i3 = sequence_composition(dfe, cuda, cfg, ckey, cfg.filter(dfe, cuda), ident)[1][1]
+        assert not np.array_equal(i3["depth_fused"], w3[1]["depth_fused"])
+
+
+def test_post_imu_tx(dfe, cuda):
+    """imu_tx = 1.0, 0.5, 2.0 on the three pushes of the asymmetric case: depth, depth_post, depth_post_conf and the fused outputs are
+    the composition's with each pair's own value (a chain handed 1, or the previous push's value, differs)"""
+    cfg, ckey = asym_cfg("max")                                    # (integer flows up to 8 px: many depths below the far value 100)
+    (r2, r3), (w2, w3) = run_post_sequence(dfe, cuda, cfg, ckey, post_of(ASYM_ALL), imu=(1.0, 0.5, 2.0))
+    one = sequence_composition(dfe, cuda, cfg, ckey, cfg.filter(dfe, cuda), post_of(ASYM_ALL))
+    for w, o in zip((w2, w3), one):
+        assert w[1]["depth_post_conf"].any() and not np.array_equal(w[1]["depth_post"], o[1]["depth_post"])
+        assert not np.array_equal(w[1]["depth_fused"], o[1]["depth_fused"]) and not np.array_equal(w[0]["depth"], o[0]["depth"])
+
+
+def test_post_one_plane(dfe, cuda):
+    """C = 1, features mode, all four stages: the guide of the median is a one-plane warp of the chain's own"""
+    cfg = asym(method="mean", layers=MONO_LAYERS, shape=MONO_SHAPE)
+    (r2, r3), (w2, w3) = run_post_sequence(dfe, cuda, cfg, ("mono", "mean", "features"), post_of(ASYM_ALL))
+    assert (w2[1]["flow_post"] != w2[0]["flow"]).any() and r3["weight_post"].any()
+    plain = sequence_composition(dfe, cuda, cfg, ("mono", "mean", "features"), cfg.filter(dfe, cuda), post_of(dict(ASYM_ALL, median=(5, 0.0))))
+    assert not np.array_equal(plain[0][1]["flow_post"], w2[1]["flow_post"])   # (on the composition alone) the guide is in use
+
+
+def test_post_raw_frames(dfe, cuda):
+    """filter=None, image mode, C = 3, all four stages: the backward matcher reads the scaled frame and the rectified frame themselves"""
+    cfg = raw_config("image", 3, "mean")
+    (r2, r3), _ = run_post_sequence(dfe, cuda, cfg, ("raw", "mean", "image", RAW_SCALE), post_of(ASYM_ALL), frame_scale=RAW_SCALE)
+    assert r3["weight_post"].any() and r3["consistent"].any()
 
 
 # ------------------------------------------------------------------------------------------------ 2. the comparison is not empty
@@ -467,3 +651,33 @@ def test_python_post(dfe, cuda):
     fo.nextFrameDepth(im1)
     assert fo.last["status"] == 1 and "depth_post" not in fo.last and "consistent" not in fo.last and fo.last["weight_post"].any()
     fo.close()
+
+
+def test_python_post_asymmetric(dfe, cuda):
+    """DepthEstimationAPI(post=...) at the asymmetric case: the tensors it allocates from the params (67 x 93 planes of odd length) hold
+    the C results under the documented names, bit for bit, with imu_tx = 0.5"""
+    cfg, _ = asym_cfg()
+    im0, im1, _, K = cfg.frames(cuda)
+    filt = cfg.filter(dfe, cuda)
+    post = post_of(ASYM_ALL, "bilinear")
+    s = PostStream(dfe, cuda, cfg, filt, K, post)
+    try:
+        s.push(im0, imu_tx=0.5)
+        want = [s.push(im1, imu_tx=0.5), s.push(im0, imu_tx=0.5)]
+    finally:
+        s.close()
+    api = dfe.DepthEstimationAPI(cfg.geometry, filt, K, u8Scale=1.0, post=post, **cfg.extra())
+    assert api.nextFrameDepth(im0, imu_tx=0.5) is None
+    names = dict(yflow=("flow", 0), xflow=("flow", 1), mask="mask", depth="depth", depth_conf="dconf", flow_post="flow_post", weight_post="weight_post",
+                 consistent="consistent", depth_post="depth_post", depth_post_conf="depth_post_conf", depth_fused="depth_fused", depth_fused_weight="fused_weight",
+                 depth_fused_flag="fused_flag", im_scaled="im_scaled")
+    for im, w in zip((im1, im0), want):
+        got = api.nextFrameDepth(im, imu_tx=0.5)
+        assert api.last["status"] == 1 and tuple(got[1].shape) == (67, 93)
+        assert np.array_equal(got[0].cpu().numpy(), w["im_scaled"]) and np.array_equal(got[1].cpu().numpy(), w["flow"][1]) and np.array_equal(got[2].cpu().numpy(), w["mask"])
+        for k, c in names.items():
+            ref = w[c[0]][c[1]] if isinstance(c, tuple) else w[c]
+            assert np.array_equal(api.last[k].cpu().numpy(), ref), k
+        assert np.array_equal(api.last["R"].numpy(), w["R"]) and (api.last["nFound"], api.last["nInliers"]) == (w["nf"], w["ni"])
+    assert (want[1]["fused_flag"] == 3).any() and want[1]["weight_post"].any()
+    api.close()

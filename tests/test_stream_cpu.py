@@ -71,6 +71,43 @@ def test_stream_shapes_vga_to_half(dfe):
     assert dfe.stream.stream_shapes(p) == dict(Hf=228, Wf=308, H1=213, W1=293, oy=6, ox=6, ix=14, iy=14)
 
 
+# The asymmetric geometry of the GPU suites (tests/test_gpu_stream.py, ASYM): 67 x 93 from 149 x 203 frames, a stack whose kernel is 7 rows
+# by 9 columns, a window of 10 rows by 17 columns.  The numbers are the reference's rules (depth_estimation_api.lua:172-179) worked by
+# hand: Hf, Wf = 67 - 6, 93 - 8; H1, W1 = 61 - 9, 85 - 16; oy, ox = floor(6 / 2) - 1, floor(8 / 2) - 1; ix, iy = ceil(24 / 2), ceil(15 / 2).
+# No two of the x / y pairs are equal, so a swap anywhere in stream_shapes shows.
+ASYM = dict(hImg=67, wImg=93, layers=((3, 3, 5, 4), (4, 7, 3, 4)), win=(10, 17), Hsrc=149, Wsrc=203)
+ASYM_T = dict(hImg=93, wImg=67, layers=((3, 5, 3, 4), (4, 3, 7, 4)), win=(17, 10), Hsrc=203, Wsrc=149)   # x and y exchanged
+
+
+def test_stream_shapes_asymmetric(dfe):
+    p, keep = params(dfe, **ASYM)
+    assert shapes(dfe, p) == (0, (61, 85, 52, 69, 2, 3, 12, 8))                    # Hf, Wf, H1, W1, oy, ox, ix, iy
+    assert dfe.stream.stream_shapes(p) == dict(Hf=61, Wf=85, H1=52, W1=69, oy=2, ox=3, ix=12, iy=8)
+    p, keep = params(dfe, fix=1, **ASYM)
+    assert shapes(dfe, p) == (0, (61, 85, 52, 69, 3, 4, 12, 8))
+    assert dfe.stream.stream_shapes(p) == dict(Hf=61, Wf=85, H1=52, W1=69, oy=3, ox=4, ix=12, iy=8)
+    for fix in (0, 1):
+        p, keep = params(dfe, rectify=1, fix=fix, **ASYM)
+        assert shapes(dfe, p) == (0, (61, 85, 52, 69, 0, 0, 12, 8))
+    assert dfe.stream.stream_shapes(p) == dict(Hf=61, Wf=85, H1=52, W1=69, oy=0, ox=0, ix=12, iy=8)
+
+
+def test_stream_shapes_asymmetric_transposed(dfe):
+    """frame, geometry, every layer's kernel and the window with x and y exchanged: every pair of the tuple comes out exchanged"""
+    def swap(t):
+        Hf, Wf, H1, W1, oy, ox, ix, iy = t
+        return (Wf, Hf, W1, H1, ox, oy, iy, ix)
+
+    for kw in (dict(), dict(fix=1), dict(rectify=1)):
+        p, keep = params(dfe, **dict(ASYM, **kw))
+        q, keep2 = params(dfe, **dict(ASYM_T, **kw))
+        rc, t = shapes(dfe, p)
+        assert rc == 0 and shapes(dfe, q) == (0, swap(t)), kw
+    q, keep2 = params(dfe, **ASYM_T)
+    assert shapes(dfe, q) == (0, (85, 61, 69, 52, 3, 2, 8, 12))
+    assert dfe.stream.stream_shapes(q) == dict(Hf=85, Wf=61, H1=69, W1=52, oy=3, ox=2, ix=8, iy=12)
+
+
 def test_stream_shapes_image_mode_offset_is_zero(dfe):
     for fix in (0, 1):
         p, keep = params(dfe, rectify=1, fix=fix)
