@@ -12,6 +12,7 @@ import torch
 from tests import oracle as orc
 from tests import tracker_ref64 as tr
 from tests.egomotion_cases import check_pose_algebra, rot_angle, t_angle
+from tests.tracker_cases import MIN_EIG, TRACKER_CASES, tracker_points
 
 pytestmark = pytest.mark.gpu
 
@@ -160,30 +161,6 @@ def test_pyr_down_against_float64(dfe, cuda, H, W):
 
 
 # ------------------------------------------------------------------------------------------------------------------- 4. tracker
-def tracker_points(H, W, N, seed, specials):
-    """N points: random over the frame less a 2 px rim (most windows hang over the frame edge on purpose; the rim keeps the share of results
-    within 0.5 px of the edge, where the status may differ, small), the first ones replaced by the special points"""
-    rng = np.random.default_rng(seed)
-    pts = np.stack([rng.uniform(2, W - 3, N), rng.uniform(2, H - 3, N)], 1).astype(np.float32)
-    sp = np.array(specials, np.float32).reshape(-1, 2)[:N]
-    pts[: len(sp)] = sp
-    return pts
-
-
-TRACKER_CASES = [
-    # name,                 frame,     shift,         N,   win, levels, max_iters, eps
-    ("one point",           (120, 160), (3.3, -2.6),   1,   21, 3, 10, 0.0),
-    ("win 3, one level",    (120, 160), (0.37, -0.21), 63,  3,  1, 10, 0.0),
-    ("win 31, four levels", (120, 160), (9.3, -6.6),   64,  31, 4, 10, 0.0),
-    ("win 21, one level",   (120, 160), (0.37, -0.21), 65,  21, 1, 10, 0.0),
-    ("257 points",          (120, 160), (3.3, -2.6),   257, 21, 3, 10, 0.0),
-    ("257 points, eps",     (120, 160), (3.3, -2.6),   257, 21, 3, 30, 0.01),
-    ("24 x 32, four levels", (24, 32),  (1.3, -0.8),   65,  21, 4, 10, 0.0),
-    ("24 x 32, eps",        (24, 32),   (1.3, -0.8),   64,  3,  3, 30, 0.01),
-]
-MIN_EIG = 1.0
-
-
 @pytest.mark.parametrize("case", TRACKER_CASES, ids=[c[0] for c in TRACKER_CASES])
 def test_tracker_against_lk64(dfe, cuda, case):
     """Point by point against lk64 on the same input (a shared wrong minimum is no failure).  Positions of the points both sides track:
